@@ -34,10 +34,6 @@ import os
 import sys
 import time
 
-# before anything initialises HIP: the host pipeline wants more hardware queues than the runtime's default of 4
-# (vgaudio_amd/__init__.py does the same; this covers an import order where torch touches the GPU first)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -72,7 +68,14 @@ def parse():
                     help="process-group backend for N > 1 (nccl = RCCL; gloo moves the gather through host memory: for trying "
                          "the N > 1 path on a box with fewer GPUs than ranks)")
     ap.add_argument("--share-gpu", action="store_true", help="every rank uses cuda:0 (N > 1 plumbing test on a 1-GPU box; implies --backend gloo)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's units) as DIR/<name>.npy, "
+                         "float32 or float64, at most 64 MB in all: outputs too large for that are sampled with a fixed seed "
+                         "(git ignores bench_outputs/)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def usable_cpus():
@@ -205,6 +208,45 @@ def base_line(args, cx, metric, value, ms_per_step, dtype, workload, config, roo
     if cpu:
         out["speedup_vs_cpu_baseline"] = round(value / cpu["value"], 2)
     return out
+
+
+DUMP_BYTES = 63 * 10**6          # --dump-outputs: array bytes written in all (the .npy headers stay under 64 MB with them)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: writes outputs {name: device tensor [units, ...]} as path/<name>.npy, integers of up to 16 bits and
+    float32 as float32 (exact), anything wider as float64.  An output of at most DUMP_BYTES / 16 is written whole; the
+    larger ones share the rest of DUMP_BYTES, each half as <name>_rows (whole rows, or their first columns when one row
+    is too long, of units drawn without replacement) and half as <name>_scatter (single elements at positions drawn from
+    the whole array, in flat order).  The draws come from one generator seeded with DUMP_SEED and depend on the shapes
+    only, so runs with the same arguments write the same positions."""
+    import numpy as np
+    import torch
+
+    def itemsize(t):
+        return 4 if t.element_size() <= 2 or t.dtype == torch.float32 else 8
+
+    def host(t):
+        return t.cpu().numpy().astype(np.float32 if itemsize(t) == 4 else np.float64)
+
+    whole = {k: t for k, t in outputs.items() if t.numel() * itemsize(t) <= DUMP_BYTES // 16}
+    big = [k for k in outputs if k not in whole]
+    files = {k: host(t) for k, t in whole.items()}
+    if big:
+        half = (DUMP_BYTES - sum(t.numel() * itemsize(t) for t in whole.values())) // len(big) // 2
+    rng = np.random.default_rng(DUMP_SEED)
+    for k in big:
+        t = outputs[k].reshape(outputs[k].shape[0], -1)
+        rows, cols, item = t.shape[0], t.shape[1], itemsize(t)
+        c = min(cols, max(1, half // item))
+        r = np.sort(rng.choice(rows, min(rows, max(1, half // (c * item))), replace=False))
+        files[k + "_rows"] = host(t[torch.from_numpy(r).to(t.device), :c])
+        pos = np.unique(rng.integers(0, rows * cols, max(1, half // item), dtype=np.int64))
+        files[k + "_scatter"] = host(t[torch.from_numpy(pos // cols).to(t.device), torch.from_numpy(pos % cols).to(t.device)])
+    os.makedirs(path, exist_ok=True)
+    for k, a in files.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 # ====================================================================================================== GC-ADPCM
@@ -895,6 +937,8 @@ def run_gc(args, cx):
 
     elapsed, evs = timed_steps(cx, args, step, 3)
     coefs = state["coefs"]
+    if args.dump_outputs and cx.rank == 0:
+        dump_outputs(args.dump_outputs, {"coefs": coefs, "adpcm": adpcm[:, :vdev.gc_byte_count(n)]})
     coef_ms, enc_ms = mean_ms(evs, 0, 1), mean_ms(evs, 1, 2)
     ms_per_step = elapsed / max(args.steps, 1) * 1e3
     samples_per_step = nch * n * cx.world
@@ -1076,6 +1120,8 @@ def run_adx(args, cx):
     elapsed, evs = timed_steps(cx, args, step, 3)
     if int(status.item()) != 0:
         raise SystemExit("ADX decode reported a bad frame")
+    if args.dump_outputs and cx.rank == 0:
+        dump_outputs(args.dump_outputs, {"adx": adx[:, :nb], "history": hist, "decoded": dec[:, :n]})
     enc_ms, dec_ms = mean_ms(evs, 0, 1), mean_ms(evs, 1, 2)
     ms_per_step = elapsed / max(args.steps, 1) * 1e3
     value = nch * n * cx.world / (ms_per_step * 1e-3) / 1e6
@@ -1215,6 +1261,8 @@ def run_hca(args, cx):
             events[1].record()
 
     elapsed, evs = timed_steps(cx, args, step, 2)
+    if args.dump_outputs and cx.rank == 0:
+        dump_outputs(args.dump_outputs, {"frames": frames[:, :fbytes]})
     enc_ms = mean_ms(evs, 0, 1)
     # decode beside it (not part of the step)
     e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -1307,7 +1355,7 @@ def other_configs(args, cx):
     out = {}
     for codec, fn in (("adx", run_adx), ("hca", run_hca)):
         a = copy.copy(args)
-        a.codec, a.steps, a.warmup, a.no_e2e = codec, 3, 1, True
+        a.codec, a.steps, a.warmup, a.no_e2e, a.dump_outputs = codec, 3, 1, True, None
         a.channels, a.streams, a.seconds = 4096, 1024, 60.0
         threads, _ = usable_cpus()
         a.cpu_channels = 8 * threads if codec == "adx" else 2 * max(1, threads - 1)

@@ -73,12 +73,10 @@ int vga_set_progress_callback(vga_progress_fn fn, void *user);
 void vga_release_cached_memory(void);
 /* Process-wide side effects of the host-buffer (`*_batch`) entry points, stated here because a drop-in must not surprise
  * its host (details: INTEGRATION.md, "What the host pipeline does to the process"):
- *  - loading the library sets the environment variable GPU_MAX_HW_QUEUES=16 unless the host has set it or has set
- *    VGA_HIP_NO_ENV=1 (the HIP runtime reads the variable when it initialises; with the default of 4 hardware queues a
- *    copy stream shares a queue with a kernel stream and every download waits for the last kernel).  setenv is not
- *    thread-safe against a host thread calling getenv at that moment: a host that cares sets the variable itself before
- *    loading the library, or opts out.  If the runtime was already up when the library was loaded (it then never saw the
- *    value), or fewer than 6 queues are configured, the calls run one kernel lane instead of two -- slower, not wrong;
+ *  - the calls run two kernel lanes when the host has configured 6 or more hardware queues (environment variable
+ *    GPU_MAX_HW_QUEUES, read when the library is loaded; the library never sets it) and one lane otherwise -- slower, not
+ *    wrong: with the runtime's default of 4 queues a copy stream shares a queue with a kernel stream and every download
+ *    waits for the last kernel;
  *  - input rows of 256 KB or more (and the output rows of a decode) are page-locked with hipHostRegister for the duration
  *    of the call; a row that cannot be registered is copied through the runtime's pageable path;
  *  - one feeder and two drainer threads per call, joined before it returns. */

@@ -70,7 +70,9 @@ WORKER = textwrap.dedent("""
         assert "wrong digest: [1]" in g.verify(rows, torch.from_numpy(coefs).reshape(count, 16), adpcm.shape[1])
         g.all_adpcm.copy_(keep)
         assert g.verify(rows, torch.from_numpy(coefs).reshape(count, 16), adpcm.shape[1]).startswith("own rows identical")
-    dist.barrier()
+    # the barrier as a collective on a CPU tensor: dist.barrier() probes for an accelerator, which opens the GPU in every
+    # rank, and these ranks stand in for GPUs on the CPU
+    dist.all_reduce(torch.zeros(1))
     dist.destroy_process_group()
 """)
 

@@ -9,8 +9,6 @@
 #include "gcadpcm_kernels.hpp"
 
 #include <cmath>
-#include <dirent.h>
-#include <unistd.h>
 
 namespace vga {
 
@@ -49,45 +47,17 @@ static thread_local int g_hca_frames_per_group = 0;
 int hca_frames_per_group_override() { return g_hca_frames_per_group; }
 
 // The host pipeline runs an upload stream, a download stream and two lanes of kernels next to whatever streams the host
-// has; the HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless told otherwise), and a copy
-// stream that shares a queue with a kernel stream waits behind that stream's kernels (measured: every download of a
-// 4096-channel encode ended only when the last kernel had, 660 ms instead of 533 ms).  The variable is read when the
-// runtime initialises, so it is set when this library is loaded -- only if the host has not set it; a host that
-// initialises HIP before loading the library sets it itself.
-// Whether the runtime had already been brought up when this library was loaded: its KFD device is then open.
-static bool runtime_is_up()
+// has; the HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (the runtime's default of four unless the
+// host sets it), and a copy stream that shares a queue with a kernel stream waits behind that stream's kernels (measured:
+// every download of a 4096-channel encode ended only when the last kernel had, 660 ms instead of 533 ms).  So the calls run
+// a second kernel lane only when the host has configured enough queues for it.  How many hardware queues a process opens
+// is the host's decision (the queues of a GPU are shared by every process on it): the library reads the variable and
+// never sets it.
+static int g_queues_seen_by_runtime = 4;             // what the HIP runtime reads from the variable (its default when unset)
+__attribute__((constructor)) static void read_hardware_queues()
 {
-    DIR *d = opendir("/proc/self/fd");
-    if (!d) return false;
-    bool up = false;
-    char path[64], target[64];
-    while (dirent *e = readdir(d)) {
-        std::snprintf(path, sizeof path, "/proc/self/fd/%s", e->d_name);
-        const ssize_t n = readlink(path, target, sizeof target - 1);
-        if (n > 0) {
-            target[n] = 0;
-            if (std::strcmp(target, "/dev/kfd") == 0) { up = true; break; }
-        }
-    }
-    closedir(d);
-    return up;
-}
-
-static int g_queues_seen_by_runtime = 4;             // what the HIP runtime reads (or read) from GPU_MAX_HW_QUEUES
-__attribute__((constructor)) static void ask_for_hardware_queues()
-{
-    const char *host = std::getenv("GPU_MAX_HW_QUEUES");
-    const char *opt_out = std::getenv("VGA_HIP_NO_ENV");
-    if (host) {
-        g_queues_seen_by_runtime = std::atoi(host);  // the host's choice (set before it brought the runtime up, one assumes)
-    } else if (opt_out && opt_out[0] && opt_out[0] != '0') {
-        g_queues_seen_by_runtime = 4;                // the runtime's default
-    } else if (runtime_is_up()) {
-        g_queues_seen_by_runtime = 4;                // too late: the runtime initialised without the variable
-    } else {
-        setenv("GPU_MAX_HW_QUEUES", "16", 0);
-        g_queues_seen_by_runtime = 16;
-    }
+    if (const char *host = std::getenv("GPU_MAX_HW_QUEUES"))
+        g_queues_seen_by_runtime = std::atoi(host);
 }
 
 int hardware_queues_requested() { return g_queues_seen_by_runtime; }

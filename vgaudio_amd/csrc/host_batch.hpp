@@ -23,7 +23,7 @@ PipeOverride &pipe_override();                       // capi_gcadpcm.hip
 // the calling thread's last pipeline run, plus what the entry point spent around it (device allocation, small copies)
 struct PipeReport { pipe::Stats stats; double t_alloc = 0, t_entry = 0; };
 PipeReport &pipe_report();                           // capi_gcadpcm.hip
-int hardware_queues_requested();                     // capi_gcadpcm.hip: GPU_MAX_HW_QUEUES as this process will see it (4 when unset)
+int hardware_queues_requested();                     // capi_gcadpcm.hip: GPU_MAX_HW_QUEUES as this process sees it (the runtime's default when unset)
 
 // vga_set_devices(): the GPUs the host-pointer entry points spread one call's units over (empty: the calling thread's
 // current device, nothing is spread) -- capi_gcadpcm.hip
