@@ -193,12 +193,10 @@ static int adx_encode_batch_one(const int16_t *const *pcm, int nch, int pcm_leng
         job.d_out = d_out.as<char>();
         job.d_out_pitch = (size_t)out_pitch;
     }
-    job.compute = [&](int first, int count, hipStream_t s, std::string &why) -> int {
-        const int rc = adx::launch_encode(d_pcm.as<int16_t>() + (int64_t)first * pcm_pitch, pcm_pitch, count, pcm_length, dp,
-                                          d_out.as<uint8_t>() + (int64_t)first * out_pitch, out_pitch, d_hist.as<int16_t>() + first, s);
-        if (rc) why = vga_last_error();
-        return rc;
-    };
+    job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
+        return adx::launch_encode(d_pcm.as<int16_t>() + (int64_t)first * pcm_pitch, pcm_pitch, count, pcm_length, dp,
+                                  d_out.as<uint8_t>() + (int64_t)first * out_pitch, out_pitch, d_hist.as<int16_t>() + first, s);
+    });
     if (int rc = run_batch_pipeline(job, ADX_CHUNK_CHANNELS)) return rc;
     if (history_out) VGA_HIP_TRY(hipMemcpy(history_out, d_hist.p, (size_t)nch * 2, hipMemcpyDeviceToHost));
     return VGA_OK;
@@ -249,12 +247,10 @@ static int adx_decode_batch_one(const uint8_t *const *adpcm, int adpcm_length, i
     job.out_row_bytes = (size_t)sample_count * 2;
     job.d_out = d_pcm.as<char>();
     job.d_out_pitch = (size_t)pcm_pitch * 2;
-    job.compute = [&](int first, int count, hipStream_t s, std::string &why) -> int {
-        const int rc = adx::launch_decode(d_in.as<uint8_t>() + (int64_t)first * in_pitch, in_pitch, count, sample_count, dp,
-                                          d_pcm.as<int16_t>() + (int64_t)first * pcm_pitch, pcm_pitch, d_status.as<int>(), s);
-        if (rc) why = vga_last_error();
-        return rc;
-    };
+    job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
+        return adx::launch_decode(d_in.as<uint8_t>() + (int64_t)first * in_pitch, in_pitch, count, sample_count, dp,
+                                  d_pcm.as<int16_t>() + (int64_t)first * pcm_pitch, pcm_pitch, d_status.as<int>(), s);
+    });
     if (int rc = run_batch_pipeline(job, ADX_CHUNK_CHANNELS)) return rc;
     int status = 0;
     VGA_HIP_TRY(hipMemcpy(&status, d_status.p, sizeof(int), hipMemcpyDeviceToHost));
@@ -316,67 +312,32 @@ int adx_encode_batch_v_one(const int16_t *const *pcm, const int *lengths, int nc
     // shorter, and the equal-length kernels still fill their launch (10 008 files: 578 ms against 591-601 with 1024, 647-651
     // with 128 -- 79 launches of ~10 ms are more than the upload hides; profiles/r05_q_ragged_host_orders.log)
     const BucketPlan plan = plan_buckets(group, length, 256, ADX_BUCKET_VOLUME, false);
-    const int chunks = (int)plan.chunk_begin.size() - 1;
-    // device layout: chunk k's rows pitch_k apart behind the chunks before it
-    std::vector<int64_t> pcm_base(chunks + 1, 0), out_base(chunks + 1, 0), pcm_pitch(chunks), out_pitch(chunks);
-    std::vector<const vga_adx_params *> chunk_params(chunks);
-    for (int k = 0; k < chunks; k++) {
-        const int count = plan.chunk_begin[k + 1] - plan.chunk_begin[k];
-        chunk_params[k] = &params[plan.order[plan.chunk_begin[k]]];
-        pcm_pitch[k] = round_up(std::max(plan.chunk_length[k], 1), 8);
-        out_pitch[k] = round_up(std::max(vga_adx_encoded_byte_count(plan.chunk_length[k], chunk_params[k]), 2), 16);
-        pcm_base[k + 1] = pcm_base[k] + pcm_pitch[k] * count;
-        out_base[k + 1] = out_base[k] + out_pitch[k] * count;
-    }
-    std::vector<const void *> in_rows(nch);
-    std::vector<void *> out_rows(nch);
-    std::vector<size_t> in_size(nch), in_off(nch), out_size(nch), out_off(nch);
-    size_t max_in = 16, max_out = 16;
-    for (int k = 0; k < chunks; k++)
-        for (int i = plan.chunk_begin[k]; i < plan.chunk_begin[k + 1]; i++) {
-            const int c = plan.order[i], j = i - plan.chunk_begin[k];
-            in_rows[i] = pcm[c];
-            out_rows[i] = out[c];
-            in_size[i] = (size_t)lengths[c] * 2;
-            in_off[i] = (size_t)(pcm_base[k] + j * pcm_pitch[k]) * 2;
-            out_size[i] = (size_t)vga_adx_encoded_byte_count(lengths[c], &params[c]);
-            out_off[i] = (size_t)(out_base[k] + j * out_pitch[k]);
-            max_in = std::max(max_in, (size_t)pcm_pitch[k] * 2);
-            max_out = std::max(max_out, (size_t)out_pitch[k]);
-        }
+    const BucketLayout lay = layout_buckets(
+        plan, 1, 1,
+        [&](int k) {
+            const vga_adx_params *p = &params[plan.order[plan.chunk_begin[k]]];
+            return RowPitch{round_up(std::max(plan.chunk_length[k], 1), 8) * 2,
+                            round_up(std::max(vga_adx_encoded_byte_count(plan.chunk_length[k], p), 2), 16)};
+        },
+        [&](int c, int) { return InRow{pcm[c], (size_t)lengths[c] * 2}; },
+        [&](int c, int) { return OutRow{out[c], (size_t)vga_adx_encoded_byte_count(lengths[c], &params[c])}; });
     DevBuf d_pcm, d_out, d_hist, d_own;
     // every channel's own frame count, in the plan's order: the seams in a channel's padding are left alone (adx_kernels.hpp)
     std::vector<int> own(nch);
     for (int i = 0; i < nch; i++) own[i] = divide_by_round_up(lengths[plan.order[i]] + params[plan.order[i]].padding, 32);   // (frames of the padded stream)
     VGA_HIP_TRY(d_own.alloc((size_t)nch * sizeof(int)));
     VGA_HIP_TRY(hipMemcpy(d_own.p, own.data(), (size_t)nch * sizeof(int), hipMemcpyHostToDevice));
-    VGA_HIP_TRY(d_pcm.alloc((size_t)pcm_base[chunks] * 2 + 64));
-    VGA_HIP_TRY(hipMemset(d_pcm.p, 0, (size_t)pcm_base[chunks] * 2 + 64));           // the padding behind every row is silence
-    VGA_HIP_TRY(d_out.alloc((size_t)out_base[chunks] + 64));
+    if (int rc = lay.alloc(d_pcm, d_out)) return rc;                                    // the padding behind every row is silence
     VGA_HIP_TRY(d_hist.alloc((size_t)nch * 2));
     pipe::Job job;
     job.units = nch;
-    job.chunk_begin = plan.chunk_begin;
-    job.in_rows = in_rows.data();
-    job.in_row_sizes = in_size.data();
-    job.d_in_offsets = in_off.data();
-    job.in_row_bytes = max_in;
-    job.d_in_pitch = max_in;
-    job.d_in = d_pcm.as<char>();
-    job.out_rows = out_rows.data();
-    job.out_row_sizes = out_size.data();
-    job.d_out_offsets = out_off.data();
-    job.out_row_bytes = max_out;
-    job.d_out_pitch = max_out;
-    job.d_out = d_out.as<char>();
-    job.compute = [&](int first, int count, hipStream_t s, std::string &why) -> int {
+    lay.bind(job, d_pcm, d_out);
+    job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         const int k = plan.chunk_of(first);
-        const int rc = adx::launch_encode(d_pcm.as<int16_t>() + pcm_base[k], pcm_pitch[k], count, plan.chunk_length[k], dps[plan.chunk_group[k] / 2],
-                                          d_out.as<uint8_t>() + out_base[k], out_pitch[k], d_hist.as<int16_t>() + first, s,
-                                          d_own.as<int>() + first);
-        if (rc) why = vga_last_error();
-        return rc;
-    };
+        return adx::launch_encode(d_pcm.as<int16_t>() + lay.in.base[k] / 2, lay.in.pitch[k] / 2, count, plan.chunk_length[k],
+                                  dps[plan.chunk_group[k] / 2], d_out.as<uint8_t>() + lay.out.base[k], lay.out.pitch[k],
+                                  d_hist.as<int16_t>() + first, s, d_own.as<int>() + first);
+    });
     if (int rc = run_batch_pipeline(job, ADX_CHUNK_CHANNELS)) return rc;
     if (history_out) {
         std::vector<int16_t> h(nch);
@@ -414,68 +375,34 @@ int adx_decode_batch_v_one(const uint8_t *const *adpcm, const int *adpcm_lengths
     }
     if (int rc = require_device()) return rc;
     const BucketPlan plan = plan_buckets(group, length, ADX_CHUNK_CHANNELS, ADX_BUCKET_VOLUME, false);
-    const int chunks = (int)plan.chunk_begin.size() - 1;
-    std::vector<int64_t> in_base(chunks + 1, 0), pcm_base(chunks + 1, 0), in_pitch(chunks), pcm_pitch(chunks);
-    for (int k = 0; k < chunks; k++) {
-        const int count = plan.chunk_begin[k + 1] - plan.chunk_begin[k];
-        const vga_adx_params &p = params[plan.order[plan.chunk_begin[k]]];
-        const int spf = (p.frame_size - 2) * 2;
-        const int64_t bytes = (int64_t)(p.padding / spf) * p.frame_size + (int64_t)divide_by_round_up(plan.chunk_length[k], spf) * p.frame_size;
-        in_pitch[k] = round_up(std::max<int64_t>(bytes, 2), 16);
-        pcm_pitch[k] = round_up(std::max(plan.chunk_length[k], 1), 8);
-        in_base[k + 1] = in_base[k] + in_pitch[k] * count;
-        pcm_base[k + 1] = pcm_base[k] + pcm_pitch[k] * count;
-    }
-    std::vector<const void *> in_rows(nch);
-    std::vector<void *> out_rows(nch);
-    std::vector<size_t> in_size(nch), in_off(nch), out_size(nch), out_off(nch);
-    size_t max_in = 16, max_out = 16;
-    for (int k = 0; k < chunks; k++)
-        for (int i = plan.chunk_begin[k]; i < plan.chunk_begin[k + 1]; i++) {
-            const int c = plan.order[i], j = i - plan.chunk_begin[k];
-            in_rows[i] = adpcm[c];
-            out_rows[i] = pcm_out[c];
-            in_size[i] = need[c];
-            in_off[i] = (size_t)(in_base[k] + j * in_pitch[k]);
-            out_size[i] = (size_t)sample_counts[c] * 2;
-            out_off[i] = (size_t)(pcm_base[k] + j * pcm_pitch[k]) * 2;
-            max_in = std::max(max_in, (size_t)in_pitch[k]);
-            max_out = std::max(max_out, (size_t)pcm_pitch[k] * 2);
-        }
+    const BucketLayout lay = layout_buckets(
+        plan, 1, 1,
+        [&](int k) {
+            const vga_adx_params &p = params[plan.order[plan.chunk_begin[k]]];
+            const int spf = (p.frame_size - 2) * 2;
+            const int64_t bytes = (int64_t)(p.padding / spf) * p.frame_size + (int64_t)divide_by_round_up(plan.chunk_length[k], spf) * p.frame_size;
+            return RowPitch{round_up(std::max<int64_t>(bytes, 2), 16), round_up(std::max(plan.chunk_length[k], 1), 8) * 2};
+        },
+        [&](int c, int) { return InRow{adpcm[c], need[c]}; },
+        [&](int c, int) { return OutRow{pcm_out[c], (size_t)sample_counts[c] * 2}; });
     DevBuf d_in, d_pcm, d_status, d_own;
     std::vector<int> own(nch);                                                      // (as the encoder's: the plan's order)
     for (int i = 0; i < nch; i++) own[i] = sample_counts[plan.order[i]];
     VGA_HIP_TRY(d_own.alloc((size_t)nch * sizeof(int)));
     VGA_HIP_TRY(hipMemcpy(d_own.p, own.data(), (size_t)nch * sizeof(int), hipMemcpyHostToDevice));
-    VGA_HIP_TRY(d_in.alloc((size_t)in_base[chunks] + 64));
-    VGA_HIP_TRY(hipMemset(d_in.p, 0, (size_t)in_base[chunks] + 64));                 // frames behind a row's end: scale 0, filter 0
-    VGA_HIP_TRY(d_pcm.alloc((size_t)pcm_base[chunks] * 2 + 64));
+    if (int rc = lay.alloc(d_in, d_pcm)) return rc;                                 // frames behind a row's end: scale 0, filter 0
     VGA_HIP_TRY(d_status.alloc(sizeof(int)));
     VGA_HIP_TRY(hipMemset(d_status.p, 0, sizeof(int)));
     pipe::Job job;
     job.units = nch;
-    job.chunk_begin = plan.chunk_begin;
-    job.in_rows = in_rows.data();
-    job.in_row_sizes = in_size.data();
-    job.d_in_offsets = in_off.data();
-    job.in_row_bytes = max_in;
-    job.d_in_pitch = max_in;
-    job.d_in = d_in.as<char>();
-    job.out_rows = out_rows.data();
-    job.out_row_sizes = out_size.data();
-    job.d_out_offsets = out_off.data();
-    job.out_row_bytes = max_out;
-    job.d_out_pitch = max_out;
-    job.d_out = d_pcm.as<char>();
-    job.compute = [&](int first, int count, hipStream_t s, std::string &why) -> int {
+    lay.bind(job, d_in, d_pcm);
+    job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         const int k = plan.chunk_of(first);
-        int rc = VGA_OK;
-        if (plan.chunk_length[k] > 0)
-            rc = adx::launch_decode(d_in.as<uint8_t>() + in_base[k], in_pitch[k], count, plan.chunk_length[k], dps[plan.chunk_group[k]],
-                                    d_pcm.as<int16_t>() + pcm_base[k], pcm_pitch[k], d_status.as<int>(), s, d_own.as<int>() + first);
-        if (rc) why = vga_last_error();
-        return rc;
-    };
+        if (plan.chunk_length[k] <= 0) return VGA_OK;
+        return adx::launch_decode(d_in.as<uint8_t>() + lay.in.base[k], lay.in.pitch[k], count, plan.chunk_length[k], dps[plan.chunk_group[k]],
+                                  d_pcm.as<int16_t>() + lay.out.base[k] / 2, lay.out.pitch[k] / 2, d_status.as<int>(), s,
+                                  d_own.as<int>() + first);
+    });
     if (int rc = run_batch_pipeline(job, ADX_CHUNK_CHANNELS)) return rc;
     int status = 0;
     VGA_HIP_TRY(hipMemcpy(&status, d_status.p, sizeof(int), hipMemcpyDeviceToHost));

@@ -302,12 +302,11 @@ constexpr int GC_MIN_SHARE_CHANNELS = 128;
 // shape tables (local channel indices, offsets from the call's buffers).
 struct RaggedCall {
     int nch = 0;
-    std::vector<size_t> pcm_bytes, pcm_off_bytes, adpcm_bytes, adpcm_off_bytes;   // per channel (caller order)
+    RaggedRows pcm_rows, adpcm_rows;                  // per channel (caller order)
     std::vector<int> chunk_begin;
     std::vector<RaggedShape> chunks;
     std::vector<gc::Ragged> views;
     DevBuf pcm, adpcm, coefs, h1, h2, tables, status;
-    size_t max_pcm_row = 0, max_adpcm_row = 0;
     int64_t max_chunk_records = 1;
     int max_chunk_channels = 1;
 
@@ -348,16 +347,16 @@ struct RaggedCall {
             max_chunk_records = std::max(max_chunk_records, chunks[k].records);
             max_chunk_channels = std::max(max_chunk_channels, chunks[k].count);
         }
-        pcm_bytes.resize(n); pcm_off_bytes.resize(n); adpcm_bytes.resize(n); adpcm_off_bytes.resize(n);
+        pcm_rows.size.resize(n); pcm_rows.off.resize(n); adpcm_rows.size.resize(n); adpcm_rows.off.resize(n);
         for (size_t k = 0; k < chunks.size(); k++)
             for (int i = 0; i < chunks[k].count; i++) {
                 const int c = chunk_begin[k] + i;
-                pcm_bytes[c] = (size_t)counts[c] * 2;
-                pcm_off_bytes[c] = (size_t)chunks[k].pcm_off[i] * 2;
-                adpcm_bytes[c] = (size_t)vga_gcadpcm_sample_count_to_byte_count(counts[c]);
-                adpcm_off_bytes[c] = (size_t)chunks[k].adpcm_off[i];
-                max_pcm_row = std::max<size_t>(max_pcm_row, (size_t)round_up((int64_t)pcm_bytes[c], 16));
-                max_adpcm_row = std::max<size_t>(max_adpcm_row, (size_t)round_up((int64_t)adpcm_bytes[c], 16));
+                pcm_rows.size[c] = (size_t)counts[c] * 2;
+                pcm_rows.off[c] = (size_t)chunks[k].pcm_off[i] * 2;
+                adpcm_rows.size[c] = (size_t)vga_gcadpcm_sample_count_to_byte_count(counts[c]);
+                adpcm_rows.off[c] = (size_t)chunks[k].adpcm_off[i];
+                pcm_rows.max_pitch = std::max<size_t>(pcm_rows.max_pitch, (size_t)round_up((int64_t)pcm_rows.size[c], 16));
+                adpcm_rows.max_pitch = std::max<size_t>(adpcm_rows.max_pitch, (size_t)round_up((int64_t)adpcm_rows.size[c], 16));
             }
         VGA_HIP_TRY(pcm.alloc((size_t)pcm_base * 2 + GUARD_BYTES));
         VGA_HIP_TRY(adpcm.alloc((size_t)adpcm_base + GUARD_BYTES));
@@ -414,22 +413,10 @@ int encode_batch_v_rows(const int16_t *const *pcm, const int *counts, int nch, c
     job.units = nch;
     job.compute_lanes = hardware_queues_requested() >= 6 ? LANES : 1;
     job.chunk_begin = call.chunk_begin;
-    job.in_rows = (const void *const *)pcm;
-    job.in_row_sizes = call.pcm_bytes.data();
-    job.d_in_offsets = call.pcm_off_bytes.data();
-    job.in_row_bytes = std::max<size_t>(call.max_pcm_row, 16);
-    job.d_in = call.pcm.as<char>();
-    job.d_in_pitch = job.in_row_bytes;
-    if (encode) {
-        job.out_rows = (void *const *)adpcm_out;
-        job.out_row_sizes = call.adpcm_bytes.data();
-        job.d_out_offsets = call.adpcm_off_bytes.data();
-        job.out_row_bytes = std::max<size_t>(call.max_adpcm_row, 16);
-        job.d_out = call.adpcm.as<char>();
-        job.d_out_pitch = job.out_row_bytes;
-    }
+    bind_in(job, (const void *const *)pcm, call.pcm_rows, call.pcm.as<char>());
+    if (encode) bind_out(job, (void *const *)adpcm_out, call.adpcm_rows, call.adpcm.as<char>());
     // EncodeChannel (GcAdpcmFormat.cs:129-135) for the chunk's channels: coefficients, then encode
-    job.compute = [&](int first, int count, hipStream_t s, std::string &why) -> int {
+    job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         const int lane = pipe::compute_lane();
         const int k = call.chunk_of(first);
         const RaggedShape &sh = call.chunks[k];
@@ -441,9 +428,8 @@ int encode_batch_v_rows(const int16_t *const *pcm, const int *counts, int nch, c
             rc = launch_encode_group(sh, call.views[k], call.pcm.as<int16_t>(), d_coefs, call.h1.p ? call.h1.as<int16_t>() + first : nullptr,
                                      call.h2.p ? call.h2.as<int16_t>() + first : nullptr, call.adpcm.as<uint8_t>(), s, scratch[lane].p,
                                      scratch[lane].bytes);
-        if (rc) why = vga_last_error();
         return rc;
-    };
+    });
     const int lanes_used = job.compute_lanes;
     for (int l = 0; l < lanes_used; l++) {
         if (encode) VGA_HIP_TRY(scratch[l].alloc(gc::encode_scratch_bytes(call.max_chunk_channels)));
@@ -472,19 +458,9 @@ int decode_batch_v_rows(const uint8_t *const *adpcm, const int16_t *coefs, const
     pipe::Job job;
     job.units = nch;
     job.chunk_begin = call.chunk_begin;
-    job.in_rows = (const void *const *)adpcm;
-    job.in_row_sizes = call.adpcm_bytes.data();
-    job.d_in_offsets = call.adpcm_off_bytes.data();
-    job.in_row_bytes = std::max<size_t>(call.max_adpcm_row, 16);
-    job.d_in = call.adpcm.as<char>();
-    job.d_in_pitch = job.in_row_bytes;
-    job.out_rows = (void *const *)pcm_out;
-    job.out_row_sizes = call.pcm_bytes.data();
-    job.d_out_offsets = call.pcm_off_bytes.data();
-    job.out_row_bytes = std::max<size_t>(call.max_pcm_row, 16);
-    job.d_out = call.pcm.as<char>();
-    job.d_out_pitch = job.out_row_bytes;
-    job.compute = [&](int first, int count, hipStream_t s, std::string &why) -> int {
+    bind_in(job, (const void *const *)adpcm, call.adpcm_rows, call.adpcm.as<char>());
+    bind_out(job, (void *const *)pcm_out, call.pcm_rows, call.pcm.as<char>());
+    job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         const int k = call.chunk_of(first);
         const RaggedShape &sh = call.chunks[k];
         int rc = VGA_OK;
@@ -493,9 +469,8 @@ int decode_batch_v_rows(const uint8_t *const *adpcm, const int16_t *coefs, const
             rc = launch_decode_group(sh, call.views[k], call.adpcm.as<uint8_t>(), call.coefs.as<int16_t>() + (int64_t)first * 16,
                                      call.h1.p ? call.h1.as<int16_t>() + first : nullptr, call.h2.p ? call.h2.as<int16_t>() + first : nullptr,
                                      call.pcm.as<int16_t>(), call.status.as<int>(), s);
-        if (rc) why = vga_last_error();
         return rc;
-    };
+    });
     if (int rc = run_batch_pipeline(job, nch)) return rc;
     int status = 0;
     VGA_HIP_TRY(hipMemcpy(&status, call.status.p, sizeof(int), hipMemcpyDeviceToHost));

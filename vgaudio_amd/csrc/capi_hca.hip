@@ -588,12 +588,10 @@ static int hca_encode_batch_one(const int16_t *const *pcm, int nstreams, const v
         job.d_out = d_frames.as<char>();
         job.d_out_pitch = (size_t)frames_pitch;
     }
-    job.compute = [&](int first, int count, hipStream_t s, std::string &why) -> int {
-        const int rc = vga_hca_encode_device(d_pcm.as<int16_t>() + (int64_t)first * stream_pitch, stream_pitch, ch_pitch, count, n, &h,
-                                             d_frames.as<uint8_t>() + (int64_t)first * frames_pitch, frames_pitch, d_status.as<int>(), s);
-        if (rc) why = vga_last_error();
-        return rc;
-    };
+    job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
+        return vga_hca_encode_device(d_pcm.as<int16_t>() + (int64_t)first * stream_pitch, stream_pitch, ch_pitch, count, n, &h,
+                                     d_frames.as<uint8_t>() + (int64_t)first * frames_pitch, frames_pitch, d_status.as<int>(), s);
+    });
     if (int rc = run_batch_pipeline(job, HCA_CHUNK_STREAMS)) return rc;
     int status = 0;
     VGA_HIP_TRY(hipMemcpy(&status, d_status.p, sizeof(int), hipMemcpyDeviceToHost));
@@ -655,14 +653,12 @@ static int hca_decode_batch_one(const vga_hca_info *h, const uint8_t *const *fra
         job.d_out = d_pcm.as<char>();
         job.d_out_pitch = (size_t)ch_pitch * 2;
     }
-    job.compute = [&](int first, int count, hipStream_t s, std::string &why) -> int {
-        const int rc = vga_hca_decode_device(h, d_frames.as<uint8_t>() + (int64_t)first * frames_pitch, frames_pitch, count,
-                                             d_pcm.as<int16_t>() + (int64_t)first * stream_pitch, stream_pitch, ch_pitch,
-                                             d_ws.as<char>() + (size_t)first * ws_per_stream, (size_t)count * ws_per_stream,
-                                             d_status.as<int>(), s);
-        if (rc) why = vga_last_error();
-        return rc;
-    };
+    job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
+        return vga_hca_decode_device(h, d_frames.as<uint8_t>() + (int64_t)first * frames_pitch, frames_pitch, count,
+                                     d_pcm.as<int16_t>() + (int64_t)first * stream_pitch, stream_pitch, ch_pitch,
+                                     d_ws.as<char>() + (size_t)first * ws_per_stream, (size_t)count * ws_per_stream,
+                                     d_status.as<int>(), s);
+    });
     if (int rc = run_batch_pipeline(job, HCA_CHUNK_STREAMS)) return rc;
     int status = 0;
     VGA_HIP_TRY(hipMemcpy(&status, d_status.p, sizeof(int), hipMemcpyDeviceToHost));
@@ -711,64 +707,30 @@ int hca_encode_v_job(const std::vector<int> &units, int nch, const int16_t *cons
     const BucketPlan plan = plan_buckets(group, length, HCA_CHUNK_STREAMS, HCA_BUCKET_VOLUME, true);
     const int chunks = (int)plan.chunk_begin.size() - 1;
     std::vector<vga_hca_info> chunk_info(chunks);
-    std::vector<int64_t> pcm_base(chunks + 1, 0), fr_base(chunks + 1, 0), ch_pitch(chunks), fr_pitch(chunks);
-    for (int k = 0; k < chunks; k++) {
-        const int count = plan.chunk_begin[k + 1] - plan.chunk_begin[k];
-        chunk_info[k] = infos[units[plan.order[plan.chunk_begin[k + 1] - 1]]];       // the bucket's longest stream
-        ch_pitch[k] = round_up(std::max(plan.chunk_length[k], 1), 8);
-        fr_pitch[k] = round_up((int64_t)chunk_info[k].frame_count * chunk_info[k].frame_size + 8, 16);
-        pcm_base[k + 1] = pcm_base[k] + ch_pitch[k] * nch * count;
-        fr_base[k + 1] = fr_base[k] + fr_pitch[k] * count;
-    }
-    std::vector<const void *> in_rows((size_t)n * nch);
-    std::vector<void *> out_rows(n);
-    std::vector<size_t> in_size((size_t)n * nch), in_off((size_t)n * nch), out_size(n), out_off(n);
-    size_t max_in = 16, max_out = 16;
-    for (int k = 0; k < chunks; k++)
-        for (int i = plan.chunk_begin[k]; i < plan.chunk_begin[k + 1]; i++) {
-            const int u = units[plan.order[i]], j = i - plan.chunk_begin[k];
-            for (int c = 0; c < nch; c++) {
-                in_rows[(size_t)i * nch + c] = pcm[first_row[u] + c];
-                in_size[(size_t)i * nch + c] = (size_t)configs[u].sample_count * 2;
-                in_off[(size_t)i * nch + c] = (size_t)(pcm_base[k] + ((int64_t)j * nch + c) * ch_pitch[k]) * 2;
-            }
-            out_rows[i] = frames_out[u];
-            out_size[i] = (size_t)infos[u].frame_count * infos[u].frame_size;
-            out_off[i] = (size_t)(fr_base[k] + j * fr_pitch[k]);
-            max_in = std::max(max_in, (size_t)ch_pitch[k] * 2);
-            max_out = std::max(max_out, (size_t)fr_pitch[k]);
-        }
+    for (int k = 0; k < chunks; k++) chunk_info[k] = infos[units[plan.order[plan.chunk_begin[k + 1] - 1]]];   // the bucket's longest stream
+    // a unit is a stream: nch rows of PCM in, one row of frames out
+    const BucketLayout lay = layout_buckets(
+        plan, nch, 1,
+        [&](int k) {
+            return RowPitch{round_up(std::max(plan.chunk_length[k], 1), 8) * 2,
+                            round_up((int64_t)chunk_info[k].frame_count * chunk_info[k].frame_size + 8, 16)};
+        },
+        [&](int i, int c) { return InRow{pcm[first_row[units[i]] + c], (size_t)configs[units[i]].sample_count * 2}; },
+        [&](int i, int) { return OutRow{frames_out[units[i]], (size_t)infos[units[i]].frame_count * infos[units[i]].frame_size}; });
     DevBuf d_pcm, d_frames, d_status;
-    VGA_HIP_TRY(d_pcm.alloc((size_t)pcm_base[chunks] * 2 + 64));
-    VGA_HIP_TRY(hipMemset(d_pcm.p, 0, (size_t)pcm_base[chunks] * 2 + 64));           // silence behind every row
-    VGA_HIP_TRY(d_frames.alloc((size_t)fr_base[chunks] + 64));
+    if (int rc = lay.alloc(d_pcm, d_frames)) return rc;                             // silence behind every row
     VGA_HIP_TRY(d_status.alloc(sizeof(int)));
     VGA_HIP_TRY(hipMemset(d_status.p, 0, sizeof(int)));
     pipe::Job job;
     job.units = n;
-    job.chunk_begin = plan.chunk_begin;
-    job.in_rows_per_unit = nch;
-    job.in_rows = in_rows.data();
-    job.in_row_sizes = in_size.data();
-    job.d_in_offsets = in_off.data();
-    job.in_row_bytes = max_in;
-    job.d_in_pitch = max_in;
-    job.d_in = d_pcm.as<char>();
-    job.out_rows = out_rows.data();
-    job.out_row_sizes = out_size.data();
-    job.d_out_offsets = out_off.data();
-    job.out_row_bytes = max_out;
-    job.d_out_pitch = max_out;
-    job.d_out = d_frames.as<char>();
-    job.compute = [&](int first, int count, hipStream_t s, std::string &why) -> int {
+    lay.bind(job, d_pcm, d_frames);
+    job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         const int k = plan.chunk_of(first);
-        int rc = VGA_OK;
-        if (chunk_info[k].frame_count > 0)
-            rc = vga_hca_encode_device(d_pcm.as<int16_t>() + pcm_base[k], ch_pitch[k] * nch, ch_pitch[k], count, plan.chunk_length[k],
-                                       &chunk_info[k], d_frames.as<uint8_t>() + fr_base[k], fr_pitch[k], d_status.as<int>(), s);
-        if (rc) why = vga_last_error();
-        return rc;
-    };
+        if (chunk_info[k].frame_count <= 0) return VGA_OK;
+        const int64_t ch_pitch = lay.in.pitch[k] / 2;
+        return vga_hca_encode_device(d_pcm.as<int16_t>() + lay.in.base[k] / 2, ch_pitch * nch, ch_pitch, count, plan.chunk_length[k],
+                                     &chunk_info[k], d_frames.as<uint8_t>() + lay.out.base[k], lay.out.pitch[k], d_status.as<int>(), s);
+    });
     if (int rc = run_batch_pipeline(job, HCA_CHUNK_STREAMS)) return rc;
     int status = 0;
     VGA_HIP_TRY(hipMemcpy(&status, d_status.p, sizeof(int), hipMemcpyDeviceToHost));

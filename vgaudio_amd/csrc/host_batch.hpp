@@ -19,24 +19,33 @@ struct PipeOverride {
 // transfer_kernels.hip
 int launch_transfer(const pipe::Job::TransferPiece *pieces, int n, hipStream_t stream);
 int device_cu_count();                               // common.hpp
-PipeOverride &pipe_override();                       // capi_gcadpcm.hip
+
+// The calling thread's settings from the test hooks (vga_testing_*_this_thread, include/vgaudio_hip_testing.h), handed on as
+// a whole to the threads that run a call's other shares.  A new hook is a field here and its setter in runtime.hip.
+struct ThreadSettings {
+    int force_open_seams = 0;
+    int encoder_layout = 0;                          // 0: the launcher's choice by batch size
+    int coefs_variant = 0;
+    int encoder_segments = 0;
+    int encoder_persistent = 0;
+    int hca_frames_per_group = 0;
+    PipeOverride pipe;
+};
+ThreadSettings &thread_settings();                   // runtime.hip (thread-local)
+inline PipeOverride &pipe_override() { return thread_settings().pipe; }
 // the calling thread's last pipeline run, plus what the entry point spent around it (device allocation, small copies)
 struct PipeReport { pipe::Stats stats; double t_alloc = 0, t_entry = 0; };
-PipeReport &pipe_report();                           // capi_gcadpcm.hip
-int hardware_queues_requested();                     // capi_gcadpcm.hip: GPU_MAX_HW_QUEUES as this process sees it (the runtime's default when unset)
+PipeReport &pipe_report();                           // runtime.hip
+int hardware_queues_requested();                     // runtime.hip: GPU_MAX_HW_QUEUES as this process sees it (the runtime's default when unset)
 
 // vga_set_devices(): the GPUs the host-pointer entry points spread one call's units over (empty: the calling thread's
-// current device, nothing is spread) -- capi_gcadpcm.hip
+// current device, nothing is spread) -- runtime.hip
 std::vector<int> batch_devices();
-// the calling thread's test hooks (include/vgaudio_hip_testing.h), handed on to the threads that run a call's other shares
-struct ThreadHooks { int force_open_seams, encoder_layout, coefs_variant, encoder_segments, hca_frames_per_group; PipeOverride pipe; int encoder_persistent = 0; };
-ThreadHooks capture_thread_hooks();                  // capi_gcadpcm.hip
-void apply_thread_hooks(const ThreadHooks &h);       // capi_gcadpcm.hip
 
 // vga_set_progress_callback(): the calling thread's callback, and the state of one call's reports -- shared by the call's
 // device shares, whose pipelines report chunks from their own worker threads
 struct ProgressCallback { void (*fn)(void *user, int64_t done, int64_t total) = nullptr; void *user = nullptr; };
-ProgressCallback progress_callback();                // capi_gcadpcm.hip (thread-local)
+ProgressCallback progress_callback();                // runtime.hip (thread-local)
 struct ProgressSink {
     ProgressCallback cb;
     int64_t total = 0, done = 0;
@@ -48,7 +57,7 @@ struct ProgressSink {
         cb.fn(cb.user, done, total);
     }
 };
-ProgressSink *&current_progress_sink();              // capi_gcadpcm.hip (thread-local): the call this thread works for
+ProgressSink *&current_progress_sink();              // runtime.hip (thread-local): the call this thread works for
 
 // Runs body(first_unit, unit_count) -- the single-device form of an entry point, which reports failures through
 // set_error() + its status code -- once per share of `units` over vga_set_devices()'s list (pipe::run_on_devices: a host
@@ -68,7 +77,7 @@ inline int for_each_device_share(int units, int min_units, Body &&body)
     const std::vector<int> devices = batch_devices();
     if (devices.empty() || units <= 0) return body(0, units);
     const std::vector<pipe::Share> shares = pipe::plan_shares(devices, units, min_units);
-    const ThreadHooks hooks = capture_thread_hooks();
+    const ThreadSettings settings = thread_settings();
     if (shares.size() == 1) {                          // one GPU, but the listed one
         int before = 0;
         VGA_HIP_TRY(hipGetDevice(&before));
@@ -80,7 +89,7 @@ inline int for_each_device_share(int units, int min_units, Body &&body)
     ProgressSink *const shared_sink = current_progress_sink();
     const pipe::Result r = pipe::run_on_devices(shares, [&](const pipe::Share &sh, std::string &why) -> int {
         if (sh.index != 0) {
-            apply_thread_hooks(hooks);
+            thread_settings() = settings;
             current_progress_sink() = shared_sink;
         }
         const int rc = body(sh.first, sh.count);
@@ -89,6 +98,18 @@ inline int for_each_device_share(int units, int min_units, Body &&body)
     });
     if (r.code) set_error("%s", r.why.c_str());
     return r.code;
+}
+
+// pipe::Job::compute from a chunk's launches, body(first_unit, unit_count, stream), which reports a failure through
+// set_error() + its status code: the pipeline is handed the message with the code
+template <class Body>
+inline decltype(pipe::Job::compute) chunk_compute(Body body)
+{
+    return [body](int first, int count, hipStream_t s, std::string &why) -> int {
+        const int rc = body(first, count, s);
+        if (rc) why = vga_last_error();
+        return rc;
+    };
 }
 
 // bytes a job uploads / downloads (ragged jobs: the sum of their rows)
@@ -274,6 +295,110 @@ inline BucketPlan plan_buckets(const std::vector<int> &group, const std::vector<
     }
     r.chunk_begin.push_back(n);
     return r;
+}
+
+// ---------------------------------------------------------------- ragged jobs: every row at its own device offset
+// One direction of a ragged job, in the job's row order: every row's true size and its offset in the device buffer (bytes),
+// and the largest pitch a row has there (the pipeline's staging holds whole rows of it).
+struct RaggedRows {
+    std::vector<size_t> size, off;
+    size_t max_pitch = 16;
+};
+inline void bind_in(pipe::Job &job, const void *const *rows, const RaggedRows &r, char *d)
+{
+    job.in_rows = rows;
+    job.in_row_sizes = r.size.data();
+    job.d_in_offsets = r.off.data();
+    job.in_row_bytes = r.max_pitch;
+    job.d_in_pitch = r.max_pitch;
+    job.d_in = d;
+}
+inline void bind_out(pipe::Job &job, void *const *rows, const RaggedRows &r, const char *d)
+{
+    job.out_rows = rows;
+    job.out_row_sizes = r.size.data();
+    job.d_out_offsets = r.off.data();
+    job.out_row_bytes = r.max_pitch;
+    job.d_out_pitch = r.max_pitch;
+    job.d_out = d;
+}
+
+// The device image of a bucketed call (plan_buckets): chunk k's rows lie pitch[k] bytes apart behind the chunks before it,
+// a unit's rows next to each other.  A chunk's kernels run every row to the chunk's longest length, on into its padding.
+struct BucketLayout {
+    struct Side {
+        int rows_per_unit = 1;
+        std::vector<int64_t> base, pitch;    // per chunk, bytes; base[chunks]: the rows' total
+        RaggedRows rows;
+    };
+    std::vector<int> chunk_begin;
+    Side in, out;
+    std::vector<const void *> in_host;       // the caller's rows, in the plan's order
+    std::vector<void *> out_host;
+
+    // both buffers with 64 bytes of slack; the input's padding is zeros: the kernels rely on silence behind every row
+    int alloc(DevBuf &d_in, DevBuf &d_out) const
+    {
+        VGA_HIP_TRY(d_in.alloc((size_t)in.base.back() + 64));
+        VGA_HIP_TRY(hipMemset(d_in.p, 0, (size_t)in.base.back() + 64));
+        VGA_HIP_TRY(d_out.alloc((size_t)out.base.back() + 64));
+        return VGA_OK;
+    }
+    void bind(pipe::Job &job, const DevBuf &d_in, const DevBuf &d_out) const
+    {
+        job.chunk_begin = chunk_begin;
+        job.in_rows_per_unit = in.rows_per_unit;
+        job.out_rows_per_unit = out.rows_per_unit;
+        bind_in(job, in_host.data(), in.rows, d_in.as<char>());
+        bind_out(job, out_host.data(), out.rows, d_out.as<char>());
+    }
+};
+struct RowPitch { int64_t in, out; };      // bytes
+struct InRow { const void *p; size_t bytes; };
+struct OutRow { void *p; size_t bytes; };
+
+// one side's chunk bases and rows; s.pitch is set
+template <class Ptr, class RowOf>
+inline void lay_out_rows(const BucketPlan &plan, BucketLayout::Side &s, std::vector<Ptr> &host, RowOf row_of)
+{
+    const int chunks = (int)plan.chunk_begin.size() - 1;
+    const size_t rows = plan.order.size() * (size_t)s.rows_per_unit;
+    s.base.assign(chunks + 1, 0);
+    host.resize(rows);
+    s.rows.size.resize(rows);
+    s.rows.off.resize(rows);
+    for (int k = 0; k < chunks; k++) {
+        s.base[k + 1] = s.base[k] + s.pitch[k] * s.rows_per_unit * (plan.chunk_begin[k + 1] - plan.chunk_begin[k]);
+        for (int i = plan.chunk_begin[k]; i < plan.chunk_begin[k + 1]; i++)
+            for (int r = 0; r < s.rows_per_unit; r++) {
+                const size_t row = (size_t)i * s.rows_per_unit + r;
+                const auto h = row_of(plan.order[i], r);
+                host[row] = h.p;
+                s.rows.size[row] = h.bytes;
+                s.rows.off[row] = (size_t)(s.base[k] + ((int64_t)(i - plan.chunk_begin[k]) * s.rows_per_unit + r) * s.pitch[k]);
+                s.rows.max_pitch = std::max(s.rows.max_pitch, (size_t)s.pitch[k]);
+            }
+    }
+}
+
+// pitch_of(k) -> RowPitch: chunk k's row pitches; in_row(unit, r) -> InRow, out_row(unit, r) -> OutRow: row r of the caller's
+// unit (a value of plan.order) and its true size
+template <class PitchOf, class InRowOf, class OutRowOf>
+inline BucketLayout layout_buckets(const BucketPlan &plan, int in_rows_per_unit, int out_rows_per_unit, PitchOf pitch_of,
+                                   InRowOf in_row, OutRowOf out_row)
+{
+    BucketLayout L;
+    L.chunk_begin = plan.chunk_begin;
+    L.in.rows_per_unit = in_rows_per_unit;
+    L.out.rows_per_unit = out_rows_per_unit;
+    for (int k = 0; k + 1 < (int)plan.chunk_begin.size(); k++) {
+        const RowPitch p = pitch_of(k);
+        L.in.pitch.push_back(p.in);
+        L.out.pitch.push_back(p.out);
+    }
+    lay_out_rows(plan, L.in, L.in_host, in_row);
+    lay_out_rows(plan, L.out, L.out_host, out_row);
+    return L;
 }
 
 }  // namespace vga
