@@ -286,6 +286,120 @@ int vga_dsp_write_device(const uint8_t *d_adpcm, int64_t adpcm_pitch, int adpcm_
                          const int16_t *d_gain, const int16_t *d_start_context, const int16_t *d_loop_context,
                          int nch, const vga_dsp_params *p, uint8_t *d_file, void *stream);
 
+/* ----------------------------------------------------------------------
+ * NintendoWare streams for GC-ADPCM: BRSTM (VGAudio/Containers/NintendoWare/BrstmWriter.cs, BrstmReader.cs),
+ * BCSTM and BFSTM (BCFstmWriter.cs, BCFstmReader.cs), configured as BxstmConfiguration.cs.
+ * Write path: vga_nwstm_layout_for -> vga_gcadpcm_build_channels_* with layout.channel (the writer's loop
+ * alignment and seek tables, BrstmWriter.cs:88-103) -> vga_nwstm_write_device.  WAV -> encode -> build ->
+ * BFSTM therefore stays in HBM.  Only RecalculateSeekTable = RecalculateLoopContext = true (the defaults) is
+ * supported: the seek table and loop context always come from the channel builder, and a nonzero keep_* flag
+ * returns VGA_ERR_ARGUMENT.  Read path: vga_nwstm_parse (host) -> vga_nwstm_read_device -> vga_gcadpcm_decode_device.
+ * -------------------------------------------------------------------- */
+#define VGA_NW_RSTM 0 /* NwTarget.Revolution */
+#define VGA_NW_CSTM 1 /* NwTarget.Ctr */
+#define VGA_NW_FSTM 2 /* NwTarget.Cafe */
+#define VGA_NW_LITTLE_ENDIAN 0
+#define VGA_NW_BIG_ENDIAN 1
+#define VGA_NW_TRACK_STANDARD 0 /* BrstmTrackType */
+#define VGA_NW_TRACK_SHORT 1
+#define VGA_NW_SEEK_STANDARD 0  /* BrstmSeekTableType */
+#define VGA_NW_SEEK_SHORT 1
+#define VGA_NW_MAX_CHANNELS 255 /* the stream info's channel count is a byte */
+#define VGA_NW_MAX_TRACKS 255
+/* AudioTrack (Formats/AudioTrack.cs); written through the reference's (byte) casts */
+typedef struct { int channel_count, left, right, volume, panning; } vga_nw_track;
+typedef struct {
+    int target;                          /* VGA_NW_RSTM / CSTM / FSTM */
+    int sample_rate;                     /* BRSTM keeps (ushort)SampleRate */
+    int sample_count;                    /* GcAdpcmFormat.SampleCount of the encoded channels */
+    int looping, loop_start, loop_end;   /* the format's loop, before the writer aligns it */
+    int samples_per_interleave;          /* 0 = 14336; must be divisible by 14 */
+    int samples_per_seek_table_entry;    /* 0 = 14336; at least 2 */
+    int loop_point_alignment;            /* 0 = 14336 */
+    int track_type, seek_table_type;     /* BRSTM only: VGA_NW_TRACK_*, VGA_NW_SEEK_* */
+    uint32_t version;                    /* packed NwVersion (major << 24 | minor << 16); 0 = 2.1 (CSTM) / 0.3 (FSTM) */
+    int endianness;                      /* -1 = the target's default (CSTM little, FSTM big); BRSTM is always big */
+    int track_count;                     /* 0 = AudioTrack.GetDefaultTrackList(nch) (volume 0x7f, panning 0x40) */
+    int keep_seek_table, keep_loop_context;   /* RecalculateSeekTable / RecalculateLoopContext = false: unsupported */
+} vga_nwstm_params;
+typedef struct {
+    int target, endianness;
+    uint32_t version;
+    int include_track_info, include_region_info, include_unaligned_loop;   /* Common.cs:103-135 (CSTM / FSTM) */
+    int version_word;                    /* what the header carries: GetVersion(Type) << 16 (BCFstmWriter.cs:147-169) */
+    int looping, loop_start, loop_end, sample_count;   /* as the file carries them: SampleCount = LoopEnd when looping */
+    int alignment_needed;                /* the writer re-encodes the loop (GcAdpcmFormat.WithAlignment) */
+    vga_gcadpcm_channel_params channel;  /* pass to vga_gcadpcm_build_channels_* before writing */
+    int channel_sample_count, channel_adpcm_bytes, channel_seek_entries;   /* what that build leaves per channel */
+    int samples_per_interleave, interleave_size, interleave_count;
+    int last_block_samples, last_block_size_without_padding, last_block_size;
+    int samples_per_seek_table_entry, bytes_per_seek_table_entry, seek_table_entry_count;
+    int track_count;
+    int header_size;                     /* 0x40 */
+    int head_block_offset, head_block_size;   /* HEAD (BRSTM) / INFO (CSTM, FSTM) */
+    int head1_size, head2_size, head3_size;   /* its three parts before padding */
+    int seek_block_offset, seek_block_size;   /* ADPC / SEEK */
+    int data_block_offset, data_block_size;
+    int audio_data_offset;               /* DataBlockOffset + 0x20 */
+    int audio_data_size;                 /* one channel's audio with padding: GetNextMultiple(bytes, 0x20) */
+    int file_size;
+} vga_nwstm_layout;
+/* size math only (no device needed).  VGA_ERR_OUT_OF_RANGE as BxstmConfiguration's setters (an interleave not
+ * divisible by 14, a seek-table entry below 2), for loop points WithLoop rejects, an unsupported version or a file
+ * past 2 GiB; VGA_ERR_ARGUMENT for an unknown target, nch outside 1..255 or a keep_* flag. */
+int vga_nwstm_layout_for(const vga_nwstm_params *p, int nch, vga_nwstm_layout *out);
+/* nfiles equally shaped files of nch channels; file f's channel c is row f*nch+c of every pitched input:
+ *   d_adpcm  GetAdpcmAudio() after the build, adpcm_len bytes per row (layout.channel_adpcm_bytes);
+ *   d_coefs  16 shorts per row; d_gain 1 short per row or NULL (0);
+ *   d_start_context / d_loop_context 3 shorts per row (pred/scale, hist1, hist2) or NULL (start: (adpcm[0], 0, 0);
+ *            loop: zeros); a file that does not loop carries its start context as loop context;
+ *   d_seek   the builder's seek tables, seek_entries entries (2 shorts each) per row, seek_pitch in shorts.
+ * tracks: params.track_count entries, or NULL for the default list.  Image f goes to d_files + f*file_pitch
+ * (file_pitch >= layout.file_size and a multiple of 16 when nfiles > 1); every byte of each image is written. */
+int vga_nwstm_write_device(const vga_nwstm_params *p, int nch, int nfiles, const vga_nw_track *tracks,
+                           const uint8_t *d_adpcm, int64_t adpcm_pitch, int adpcm_len, const int16_t *d_coefs,
+                           const int16_t *d_gain, const int16_t *d_start_context, const int16_t *d_loop_context,
+                           const int16_t *d_seek, int64_t seek_pitch, int seek_entries, uint8_t *d_files,
+                           int64_t file_pitch, void *stream);
+/* one file from host arrays (as vga_dsp_write): adpcm[c] adpcm_len bytes, seek[c] 2*seek_entries shorts;
+ * file_out: layout.file_size bytes */
+int vga_nwstm_write(const vga_nwstm_params *p, int nch, const vga_nw_track *tracks, const uint8_t *const *adpcm,
+                    int adpcm_len, const int16_t *coefs, const int16_t *gain, const int16_t *start_context,
+                    const int16_t *loop_context, const int16_t *const *seek, int seek_entries, uint8_t *file_out);
+typedef struct {
+    int target, endianness;
+    uint32_t version;                    /* BRSTM: major << 24 | minor << 16 of its 2-byte version */
+    int codec, looping, loop_start, sample_count, sample_rate, channel_count;
+    int has_unaligned_loop, loop_start_unaligned, loop_end_unaligned;
+    int interleave_count, interleave_size, samples_per_interleave;
+    int last_block_size_without_padding, last_block_samples, last_block_size;
+    int bytes_per_seek_table_entry, samples_per_seek_table_entry;
+    int track_type, seek_table_type;     /* BRSTM: as found (the ADPC size selects Standard or Short) */
+    int has_track_info, track_count;
+    vga_nw_track tracks[VGA_NW_MAX_TRACKS];
+    int16_t coefs[VGA_NW_MAX_CHANNELS][16];
+    int16_t gain[VGA_NW_MAX_CHANNELS];
+    int16_t start_context[VGA_NW_MAX_CHANNELS][3];
+    int16_t loop_context[VGA_NW_MAX_CHANNELS][3];
+    int seek_table_offset, seek_entries; /* channel c's entry e: 2 shorts at seek_table_offset + (e*channel_count + c)*4 */
+    int seek_big_endian;                 /* BRSTM big-endian; BCSTM and BFSTM little-endian */
+    int head_block_offset, head_block_size, seek_block_offset, seek_block_size, data_block_offset, data_block_size;
+    int audio_data_offset, audio_data_length;   /* the interleaved audio: DeInterleave(length, InterleaveSize, ...) */
+    int adpcm_bytes;                     /* one channel after the read: SampleCountToByteCount(sample_count) */
+    int file_size;
+} vga_nwstm_info;
+/* host only.  VGA_ERR_INVALID_DATA for what the reference readers reject (magic, byte order mark, block sizes that
+ * disagree, a file shorter than stated, data past its end); VGA_ERR_INVALID_OP, naming what was found, for PCM8 /
+ * PCM16 streams, CWAV / FWAV and CSTP / FSTP files. */
+int vga_nwstm_parse(const uint8_t *file, size_t size, vga_nwstm_info *out);
+/* nfiles images that share one parsed geometry at d_files + f*file_pitch -> row f*channel_count+c of d_adpcm
+ * (info->adpcm_bytes per row), the layout vga_gcadpcm_decode_device takes */
+int vga_nwstm_read_device(const vga_nwstm_info *info, const uint8_t *d_files, int64_t file_pitch, int nfiles,
+                          uint8_t *d_adpcm, int64_t adpcm_pitch, void *stream);
+/* host form: adpcm_out[c] info->adpcm_bytes bytes; seek_out[c] (or NULL) 2*info->seek_entries shorts as stored */
+int vga_nwstm_read(const uint8_t *file, size_t size, const vga_nwstm_info *info, uint8_t *const *adpcm_out,
+                   int16_t *const *seek_out);
+
 /* ======================================================================
  * CRI ADX
  * ====================================================================== */

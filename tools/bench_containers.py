@@ -118,6 +118,35 @@ def main():
     ms = timed(lambda: _lib.check(L.vga_hca_write_device(C.byref(info), frames.data_ptr(), fpitch, ns, None, 1.0, 0, 0,
                                                          files.data_ptr(), fsz + 14, st())))
     rec("hca_images", ms, 2 * ns * info.frame_count * info.frame_size, streams=ns)
+
+    # BFSTM images: 4096 channels x 60 s as 2048 stereo files, one launch per kernel for the whole batch
+    nf, nch = 2048, 2
+    nwp = _lib.NwParamsC()
+    nwp.target, nwp.sample_rate, nwp.sample_count, nwp.endianness = 2, 48000, n, -1
+    nwl = _lib.NwLayoutC()
+    _lib.check(L.vga_nwstm_layout_for(C.byref(nwp), nch, C.byref(nwl)))
+    nb = nwl.channel_adpcm_bytes
+    pitch = (nb + 15) // 16 * 16
+    adpcm = torch.randint(0, 256, (nf * nch, pitch), dtype=torch.uint8, device=dev)
+    coefs = torch.zeros((nf * nch, 16), dtype=torch.int16, device=dev)
+    ne = nwl.channel_seek_entries
+    seek = torch.zeros((nf * nch, 2 * ne), dtype=torch.int16, device=dev)
+    fpitch = (nwl.file_size + 255) // 256 * 256
+    files = torch.empty((nf, fpitch), dtype=torch.uint8, device=dev)
+    ms = timed(lambda: _lib.check(L.vga_nwstm_write_device(C.byref(nwp), nch, nf, None, adpcm.data_ptr(), pitch, nb,
+                                                           coefs.data_ptr(), None, None, None, seek.data_ptr(), 2 * ne, ne,
+                                                           files.data_ptr(), fpitch, st())))
+    rec("nwstm_write", ms, nf * nch * nb + nf * nwl.file_size, channels=nf * nch, files=nf,
+        note="BFSTM: header + seek + interleave kernels, every image byte written once")
+    info = _lib.NwInfoC()
+    one = files[0, :nwl.file_size].cpu().numpy()
+    _lib.check(L.vga_nwstm_parse(one.ctypes.data_as(_lib.u8p), len(one), C.byref(info)))
+    back = torch.empty_like(adpcm)
+    ms = timed(lambda: _lib.check(L.vga_nwstm_read_device(C.byref(info), files.data_ptr(), fpitch, nf, back.data_ptr(), pitch,
+                                                          st())))
+    assert torch.equal(back[:, :nb], adpcm[:, :nb])
+    rec("nwstm_read", ms, 2 * nf * nch * info.adpcm_bytes, channels=nf * nch, files=nf, note="BFSTM DATA -> pitched channels")
+    del adpcm, seek, files, back
     print(json.dumps(out))
 
 

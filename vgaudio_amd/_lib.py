@@ -189,6 +189,12 @@ SIGNATURES = {
     "vga_dsp_layout_for": (ci, [vp, ci, vp]),
     "vga_dsp_write": (ci, [u8pp, ci, i16p, i16p, i16p, i16p, ci, vp, u8p]),
     "vga_dsp_write_device": (ci, [vp, i64, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
+    "vga_nwstm_layout_for": (ci, [vp, ci, vp]),
+    "vga_nwstm_write_device": (ci, [vp, ci, ci, vp, vp, i64, ci, vp, vp, vp, vp, vp, i64, ci, vp, i64, vp]),
+    "vga_nwstm_write": (ci, [vp, ci, vp, u8pp, ci, i16p, i16p, i16p, i16p, i16pp, ci, u8p]),
+    "vga_nwstm_parse": (ci, [u8p, C.c_size_t, vp]),
+    "vga_nwstm_read_device": (ci, [vp, vp, i64, ci, vp, i64, vp]),
+    "vga_nwstm_read": (ci, [u8p, C.c_size_t, vp, u8pp, i16pp]),
     "vga_gcadpcm_channel_layout_for": (ci, [vp, vp]),
     "vga_gcadpcm_build_channels_batch": (ci, [u8pp, i16p, ci, vp, u8pp, i16pp, i16pp, i16p]),
     "vga_gcadpcm_build_channels_workspace_bytes": (C.c_size_t, [ci, vp]),
@@ -268,6 +274,57 @@ class GcChannelLayoutC(C.Structure):
     """vga_gcadpcm_channel_layout"""
     _fields_ = [(n, C.c_int) for n in ("alignment_needed", "loop_start_aligned", "sample_count_aligned",
                                        "seek_table_entries")]
+
+
+NW_MAX_CHANNELS = NW_MAX_TRACKS = 255
+
+
+class NwTrackC(C.Structure):
+    """vga_nw_track"""
+    _fields_ = [(n, C.c_int) for n in ("channel_count", "left", "right", "volume", "panning")]
+
+
+class NwParamsC(C.Structure):
+    """vga_nwstm_params"""
+    _fields_ = ([(n, C.c_int) for n in ("target", "sample_rate", "sample_count", "looping", "loop_start", "loop_end",
+                                        "samples_per_interleave", "samples_per_seek_table_entry", "loop_point_alignment",
+                                        "track_type", "seek_table_type")]
+                + [("version", C.c_uint32)]
+                + [(n, C.c_int) for n in ("endianness", "track_count", "keep_seek_table", "keep_loop_context")])
+
+
+class NwLayoutC(C.Structure):
+    """vga_nwstm_layout"""
+    _fields_ = ([("target", C.c_int), ("endianness", C.c_int), ("version", C.c_uint32)]
+                + [(n, C.c_int) for n in ("include_track_info", "include_region_info", "include_unaligned_loop",
+                                          "version_word", "looping", "loop_start", "loop_end", "sample_count",
+                                          "alignment_needed")]
+                + [("channel", GcChannelParamsC)]
+                + [(n, C.c_int) for n in (
+                    "channel_sample_count", "channel_adpcm_bytes", "channel_seek_entries", "samples_per_interleave",
+                    "interleave_size", "interleave_count", "last_block_samples", "last_block_size_without_padding",
+                    "last_block_size", "samples_per_seek_table_entry", "bytes_per_seek_table_entry",
+                    "seek_table_entry_count", "track_count", "header_size", "head_block_offset", "head_block_size",
+                    "head1_size", "head2_size", "head3_size", "seek_block_offset", "seek_block_size",
+                    "data_block_offset", "data_block_size", "audio_data_offset", "audio_data_size", "file_size")])
+
+
+class NwInfoC(C.Structure):
+    """vga_nwstm_info"""
+    _fields_ = ([("target", C.c_int), ("endianness", C.c_int), ("version", C.c_uint32)]
+                + [(n, C.c_int) for n in (
+                    "codec", "looping", "loop_start", "sample_count", "sample_rate", "channel_count", "has_unaligned_loop",
+                    "loop_start_unaligned", "loop_end_unaligned", "interleave_count", "interleave_size",
+                    "samples_per_interleave", "last_block_size_without_padding", "last_block_samples", "last_block_size",
+                    "bytes_per_seek_table_entry", "samples_per_seek_table_entry", "track_type", "seek_table_type",
+                    "has_track_info", "track_count")]
+                + [("tracks", NwTrackC * NW_MAX_TRACKS), ("coefs", (C.c_int16 * 16) * NW_MAX_CHANNELS),
+                   ("gain", C.c_int16 * NW_MAX_CHANNELS), ("start_context", (C.c_int16 * 3) * NW_MAX_CHANNELS),
+                   ("loop_context", (C.c_int16 * 3) * NW_MAX_CHANNELS)]
+                + [(n, C.c_int) for n in (
+                    "seek_table_offset", "seek_entries", "seek_big_endian", "head_block_offset", "head_block_size",
+                    "seek_block_offset", "seek_block_size", "data_block_offset", "data_block_size", "audio_data_offset",
+                    "audio_data_length", "adpcm_bytes", "file_size")])
 
 
 class HcaInfoC(C.Structure):

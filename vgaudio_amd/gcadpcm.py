@@ -192,6 +192,29 @@ class GcAdpcmContext:
         self.PredScale, self.Hist1, self.Hist2 = int(predScale), int(hist1), int(hist2)
 
 
+class AudioTrack:
+    """Formats/AudioTrack.cs: one track of a multi-track container (BRSTM / BCSTM / BFSTM)."""
+
+    def __init__(self, ChannelCount=0, ChannelLeft=0, ChannelRight=0, Volume=0x7f, Panning=0x40):
+        self.ChannelCount, self.ChannelLeft, self.ChannelRight = ChannelCount, ChannelLeft, ChannelRight
+        self.Volume, self.Panning = Volume, Panning
+
+    def __eq__(self, other):
+        return isinstance(other, AudioTrack) and vars(self) == vars(other)
+
+    def __repr__(self):
+        return "AudioTrack(%d, %d, %d, 0x%x, 0x%x)" % (self.ChannelCount, self.ChannelLeft, self.ChannelRight,
+                                                      self.Volume, self.Panning)
+
+    @staticmethod
+    def GetDefaultTrackList(channelCount):       # AudioTrack.cs:69-82
+        out = []
+        for i in range(-(-channelCount // 2)):
+            n = min(channelCount - i * 2, 2)
+            out.append(AudioTrack(n, i * 2, i * 2 + 1 if n >= 2 else 0))
+        return out
+
+
 class GcAdpcmChannel:
     """Formats/GcAdpcm/GcAdpcmChannel.cs.  A channel made by the 3-argument constructor carries only the
     encoded audio; build_channels() (the batched GcAdpcmChannelBuilder.Build) adds what the reference derives:
@@ -278,7 +301,7 @@ class GcAdpcmFormat:
     ONE batched GPU call (the reference's Parallel.For over channels, GcAdpcmFormat.cs:65 / :45 / :32)."""
 
     def __init__(self, channels=None, sampleRate=48000, looping=False, loopStart=0, loopEnd=0, alignmentMultiple=0,
-                 samplesPerSeekTableEntry=0):
+                 samplesPerSeekTableEntry=0, tracks=None):
         self.SampleRate = sampleRate
         self.Looping = bool(looping)
         self.UnalignedLoopStart = loopStart if looping else 0
@@ -289,6 +312,8 @@ class GcAdpcmFormat:
         # GcAdpcmFormat(GcAdpcmFormatBuilder) rebuilds every channel with the format's loop (:27-40)
         self.Channels = build_channels(chans, self.Looping, self.UnalignedLoopStart, self.UnalignedLoopEnd, alignmentMultiple,
                                        samplesPerSeekTableEntry)
+        # AudioFormatBase.cs:48: an empty or missing list means the default one
+        self.Tracks = list(tracks) if tracks else AudioTrack.GetDefaultTrackList(len(self.Channels))
 
     @property
     def ChannelCount(self):
@@ -319,7 +344,7 @@ class GcAdpcmFormat:
     def _clone(self, **kw):
         a = dict(sampleRate=self.SampleRate, looping=self.Looping, loopStart=self.UnalignedLoopStart,
                  loopEnd=self.UnalignedLoopEnd, alignmentMultiple=self.AlignmentMultiple,
-                 samplesPerSeekTableEntry=self.SamplesPerSeekTableEntry)
+                 samplesPerSeekTableEntry=self.SamplesPerSeekTableEntry, tracks=self.Tracks)
         a.update(kw)
         base = [GcAdpcmChannel(c.Adpcm, c.Coefs, c.UnalignedSampleCount) for c in self.Channels]
         return GcAdpcmFormat(base, **a)
