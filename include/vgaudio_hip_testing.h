@@ -74,12 +74,33 @@ void vga_testing_host_pipeline_tail_this_thread(int tail_units);
 int vga_testing_plan_buckets(const int *group, const int *length, int n, int max_units, long long max_volume, int longest_first,
                              int *order_out, int *chunk_begin_out, int *chunk_length_out, int *chunk_group_out, int max_chunks);
 void vga_testing_buckets_order_this_thread(int order);
-/* Page-locked rows of the host-pointer entry points: 0 (default) = moved by transfer kernels on compute units reserved for
- * them (calls of 256 MB and more), 1 = one hipMemcpyAsync per row as until round 5 -- for calls made from the calling thread. */
+/* Page-locked rows of the host-pointer entry points, for calls made from the calling thread: 0 (default) = moved by transfer
+ * kernels on compute units reserved for them (calls of 256 MB and more whose rows average under 4 MB), 1 = one hipMemcpyAsync
+ * per row as until round 5, 2 = transfer kernels whatever the call's size: the gather of direct uploads (one feeder), the
+ * scatter of direct downloads and of staged ring slots, on masked streams.  Other values: 0.
+ * vga_testing_host_transfer_piece_bytes_this_thread() sets the largest piece one workgroup of those kernels copies
+ * (0 = the pipeline's 256 KB; at least 4096), so that rows of a few KB travel in several pieces.  Results must not depend on
+ * either. */
 void vga_testing_host_transfer_this_thread(int mode);
+void vga_testing_host_transfer_piece_bytes_this_thread(int bytes);
 /* Compute streams of the host-pointer entry points' pipeline (chunk k's kernels on stream k % lanes, at most 4): 0 = the
- * entry point's own choice -- for calls made from the calling thread (timing comparisons; results must not depend on it). */
+ * entry point's own choice -- for calls made from the calling thread.  The GC-ADPCM encoders size their per-lane buffers for
+ * the count before they allocate; the entry points that share one buffer between chunks (vga_gcadpcm_calculate_coefficients_batch,
+ * vga_gcadpcm_encode_with_coefs_batch) always run one lane.  Results must not depend on it. */
 void vga_testing_host_compute_lanes_this_thread(int lanes);
+
+/* Failure injection for calls made from the calling thread: the nth step (counting from 1, from this call of the hook on) of
+ * the given kind is refused -- the entry point returns VGA_ERR_DEVICE and vga_last_error() reads
+ * "step refused by vga_testing_fail_step_this_thread".  A refused step is a host-side error return: nothing of it is handed
+ * to HIP.  The steps the calling thread's pipelines run on their feeder and drainer threads (transfer launches) count
+ * towards the calling thread's setting.  A call spread over several GPUs (vga_set_devices) gives every other share's thread
+ * a copy of the setting, which counts that share's steps on its own.  kind 0 (or nth <= 0) switches the injection off. */
+enum {
+    VGA_TESTING_STEP_CHUNK_COMPUTE = 1,      /* a pipeline chunk's kernel launches (pipe::Job::compute) */
+    VGA_TESTING_STEP_TRANSFER = 2,           /* a transfer-kernel launch of the pipeline (gather, scatter, staged scatter) */
+    VGA_TESTING_STEP_HCA_STREAM_FRAMES = 3   /* the frame launch of vga_hca_stream_encode (calls that complete frames) */
+};
+void vga_testing_fail_step_this_thread(int kind, int nth);
 
 /* Where the wall time of the calling thread's last pipelined call went, in seconds (diagnostics for bench.py's e2e
  * block): [0] total [1] set-up [2] feeders' memcpy (sum over threads) [3] feeders waiting for a ring slot [4] feeders

@@ -28,7 +28,7 @@ def main():
     ap.add_argument("--orders", type=int, nargs="+", default=[1, 0], help="1: shortest chunks first, 0: longest first")
     ap.add_argument("--feeders", type=int, nargs="+", default=[0], help="feeder threads (0: the pipeline's one; negative: a stream each)")
     ap.add_argument("--chunk-units", type=int, nargs="+", default=[0], help="largest number of units in a chunk (0: the entry point's 1024)")
-    ap.add_argument("--transfer", type=int, nargs="+", default=[0], help="page-locked rows: 0 = by transfer kernels (round 6), 1 = one copy per row")
+    ap.add_argument("--transfer", type=int, nargs="+", default=[0], help="page-locked rows: 0 = by transfer kernels for large calls (round 6), 1 = one copy per row, 2 = transfer kernels whatever the size")
     ap.add_argument("--lanes", type=int, nargs="+", default=[0], help="compute streams of the pipeline (0: the entry point's choice)")
     args = ap.parse_args()
     import torch

@@ -18,6 +18,11 @@ VGA_ERR_INVALID_DATA = -3
 VGA_ERR_INVALID_OP = -4
 VGA_ERR_DEVICE = -5
 
+# step kinds of vga_testing_fail_step_this_thread (include/vgaudio_hip_testing.h)
+VGA_TESTING_STEP_CHUNK_COMPUTE = 1
+VGA_TESTING_STEP_TRANSFER = 2
+VGA_TESTING_STEP_HCA_STREAM_FRAMES = 3
+
 
 class VgaError(RuntimeError):
     """Base class; subclasses mirror the .NET exception the reference throws."""
@@ -169,7 +174,9 @@ SIGNATURES = {
     "vga_testing_host_pipeline_tail_this_thread": (None, [ci]),
     "vga_testing_buckets_order_this_thread": (None, [ci]),
     "vga_testing_host_transfer_this_thread": (None, [ci]),
+    "vga_testing_host_transfer_piece_bytes_this_thread": (None, [ci]),
     "vga_testing_host_compute_lanes_this_thread": (None, [ci]),
+    "vga_testing_fail_step_this_thread": (None, [ci, ci]),
     "vga_testing_plan_buckets": (ci, [C.POINTER(ci), C.POINTER(ci), ci, ci, C.c_longlong, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci),
                                  C.POINTER(ci), ci]),
     "vga_testing_hca_device_info": (ci, [vp, vp, ci]),

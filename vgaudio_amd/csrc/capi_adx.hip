@@ -193,6 +193,7 @@ static int adx_encode_batch_one(const int16_t *const *pcm, int nch, int pcm_leng
         job.d_out = d_out.as<char>();
         job.d_out_pitch = (size_t)out_pitch;
     }
+    job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         return adx::launch_encode(d_pcm.as<int16_t>() + (int64_t)first * pcm_pitch, pcm_pitch, count, pcm_length, dp,
                                   d_out.as<uint8_t>() + (int64_t)first * out_pitch, out_pitch, d_hist.as<int16_t>() + first, s);
@@ -247,6 +248,7 @@ static int adx_decode_batch_one(const uint8_t *const *adpcm, int adpcm_length, i
     job.out_row_bytes = (size_t)sample_count * 2;
     job.d_out = d_pcm.as<char>();
     job.d_out_pitch = (size_t)pcm_pitch * 2;
+    job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         return adx::launch_decode(d_in.as<uint8_t>() + (int64_t)first * in_pitch, in_pitch, count, sample_count, dp,
                                   d_pcm.as<int16_t>() + (int64_t)first * pcm_pitch, pcm_pitch, d_status.as<int>(), s);
@@ -332,6 +334,7 @@ int adx_encode_batch_v_one(const int16_t *const *pcm, const int *lengths, int nc
     pipe::Job job;
     job.units = nch;
     lay.bind(job, d_pcm, d_out);
+    job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         const int k = plan.chunk_of(first);
         return adx::launch_encode(d_pcm.as<int16_t>() + lay.in.base[k] / 2, lay.in.pitch[k] / 2, count, plan.chunk_length[k],
@@ -396,6 +399,7 @@ int adx_decode_batch_v_one(const uint8_t *const *adpcm, const int *adpcm_lengths
     pipe::Job job;
     job.units = nch;
     lay.bind(job, d_in, d_pcm);
+    job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         const int k = plan.chunk_of(first);
         if (plan.chunk_length[k] <= 0) return VGA_OK;

@@ -414,7 +414,8 @@ static int calculate_coefficients_batch_one(const int16_t *const *pcm, int nch, 
         return gc::launch_coefs(b.pcm.as<int16_t>() + (int64_t)first * b.pcm_pitch, b.pcm_pitch, count, length,
                                 b.coefs.as<int16_t>() + (int64_t)first * 16, b.ws.p, s);
     });
-    // one chunk's workspace: the chunks' kernels run one after the other on the compute stream
+    // one chunk's workspace: the chunks' kernels run one after the other on the compute stream (one lane, whatever the
+    // lanes hook says)
     VGA_HIP_TRY(b.ws.alloc(vga_gcadpcm_coefs_workspace_bytes(planned_chunk_units(job, GC_CHUNK_CHANNELS), length)));
     if (int rc = run_batch_pipeline(job, GC_CHUNK_CHANNELS)) return rc;
     VGA_HIP_TRY(hipMemcpy(coefs_out, b.coefs.p, (size_t)nch * 32, hipMemcpyDeviceToHost));
@@ -459,7 +460,7 @@ static int encode_with_coefs_batch_one(const int16_t *const *pcm, int nch, int p
     const int nbytes = vga_gcadpcm_sample_count_to_byte_count(sample_count);
     b.adpcm_pitch = round_up(nbytes, 16);
     VGA_HIP_TRY(b.adpcm.alloc((size_t)nch * b.adpcm_pitch));
-    DevBuf scratch;                                       // the encoder's piece states: one chunk at a time uses it
+    DevBuf scratch;                                       // the encoder's piece states: one chunk at a time uses it (one lane)
     pipe::Job job;
     job.units = nch;
     job.in_rows = (const void *const *)pcm;
@@ -515,12 +516,11 @@ static int encode_batch_one(const int16_t *const *pcm, int nch, int sample_count
     VGA_HIP_TRY(b.adpcm.alloc((size_t)nch * b.adpcm_pitch));
     // two compute lanes: a chunk's kernels need not wait for the chunk before (the short chunks at the end of the upload
     // are bound by the latency of one channel's coefficient search, ~25 ms, not by the chip); each lane has its own
-    // piece states and workspace
-    constexpr int LANES = 2;
-    DevBuf scratch[LANES], ws[LANES];
+    // piece states and workspace.  A lane more than the queues hold would stall the copies.  One channel is one chunk: one lane.
+    DevBuf scratch[pipe::kMaxComputeLanes], ws[pipe::kMaxComputeLanes];
     pipe::Job job;
     job.units = nch;
-    job.compute_lanes = hardware_queues_requested() >= 6 ? LANES : 1;   // a lane more than the queues hold would stall the copies
+    job.compute_lanes = nch > 1 ? planned_compute_lanes(hardware_queues_requested() >= 6 ? 2 : 1) : 1;
     if (sample_count > 0) {
         job.in_rows = (const void *const *)pcm;
         job.in_row_bytes = (size_t)sample_count * sizeof(int16_t);
@@ -546,8 +546,7 @@ static int encode_batch_one(const int16_t *const *pcm, int nch, int sample_count
         return rc;
     });
     const int chunk = planned_chunk_units(job, GC_CHUNK_CHANNELS);
-    const int lanes_used = nch > 1 ? job.compute_lanes : 1;           // (a single chunk is split in two as well)
-    for (int l = 0; l < lanes_used; l++) {
+    for (int l = 0; l < job.compute_lanes; l++) {                     // (a single chunk of several channels may be split in two)
         VGA_HIP_TRY(scratch[l].alloc(gc::encode_scratch_bytes(chunk)));
         VGA_HIP_TRY(ws[l].alloc(vga_gcadpcm_coefs_workspace_bytes(chunk, sample_count)));
     }
@@ -601,6 +600,7 @@ static int decode_batch_one(const uint8_t *const *adpcm, const int16_t *coefs, i
     job.out_row_bytes = (size_t)sample_count * 2;
     job.d_out = b.pcm.as<char>();
     job.d_out_pitch = (size_t)b.pcm_pitch * 2;
+    job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         return gc::launch_decode(b.adpcm.as<uint8_t>() + (int64_t)first * b.adpcm_pitch, b.adpcm_pitch,
                                  b.coefs.as<int16_t>() + (int64_t)first * 16, count, sample_count,

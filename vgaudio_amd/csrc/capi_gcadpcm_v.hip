@@ -407,11 +407,10 @@ int encode_batch_v_rows(const int16_t *const *pcm, const int *counts, int nch, c
     if (int rc = call.upload_hist(hist1, hist2)) return rc;
     if (!with_coefs) VGA_HIP_TRY(hipMemcpy(call.coefs.p, coefs_in, (size_t)nch * 32, hipMemcpyHostToDevice));
     const bool encode = adpcm_out != nullptr;
-    constexpr int LANES = 2;
-    DevBuf scratch[LANES], ws[LANES];
+    DevBuf scratch[pipe::kMaxComputeLanes], ws[pipe::kMaxComputeLanes];   // per lane (vga_gcadpcm_encode_batch)
     pipe::Job job;
     job.units = nch;
-    job.compute_lanes = hardware_queues_requested() >= 6 ? LANES : 1;
+    job.compute_lanes = planned_compute_lanes(hardware_queues_requested() >= 6 ? 2 : 1);
     job.chunk_begin = call.chunk_begin;
     bind_in(job, (const void *const *)pcm, call.pcm_rows, call.pcm.as<char>());
     if (encode) bind_out(job, (void *const *)adpcm_out, call.adpcm_rows, call.adpcm.as<char>());
@@ -430,8 +429,7 @@ int encode_batch_v_rows(const int16_t *const *pcm, const int *counts, int nch, c
                                      scratch[lane].bytes);
         return rc;
     });
-    const int lanes_used = job.compute_lanes;
-    for (int l = 0; l < lanes_used; l++) {
+    for (int l = 0; l < job.compute_lanes; l++) {
         if (encode) VGA_HIP_TRY(scratch[l].alloc(gc::encode_scratch_bytes(call.max_chunk_channels)));
         if (with_coefs) VGA_HIP_TRY(ws[l].alloc((size_t)call.max_chunk_records * 16));
     }
@@ -460,6 +458,7 @@ int decode_batch_v_rows(const uint8_t *const *adpcm, const int16_t *coefs, const
     job.chunk_begin = call.chunk_begin;
     bind_in(job, (const void *const *)adpcm, call.adpcm_rows, call.adpcm.as<char>());
     bind_out(job, (void *const *)pcm_out, call.pcm_rows, call.pcm.as<char>());
+    job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         const int k = call.chunk_of(first);
         const RaggedShape &sh = call.chunks[k];

@@ -312,16 +312,18 @@ int vga_hca_stream_encode(vga_hca_stream *st, const int16_t *const *pcm, uint8_t
     int device = -1;
     (void)hipGetDevice(&device);
     if (device != st->device) { set_error("the stream was created on device %d, the current one is %d", st->device, device); return VGA_ERR_ARGUMENT; }
-    // the block joins the stream's PCM in HBM (blocks past the stream's end carry nothing the reference reads)
+    // the block joins the stream's PCM in HBM (blocks past the stream's end carry nothing the reference reads).  A call that
+    // fails is rolled back to before its block, chunks_fed included: the retry writes the same block to the same slot.
+    const int saved_fed = st->chunks_fed;
     if (st->chunks_fed < st->chunks) {
         const int64_t ch_pitch = (int64_t)st->chunks * hca::SPF;
         for (int c = 0; c < st->nch; c++)
             VGA_HIP_TRY(hipMemcpyAsync(st->d_pcm.as<int16_t>() + c * ch_pitch + (int64_t)st->chunks_fed * hca::SPF, pcm[c],
                                        hca::SPF * sizeof(int16_t), hipMemcpyHostToDevice, st->s));
-        st->chunks_fed++;
         // the caller reuses its block buffer for the next call (CriHcaFormat.cs:50-56 does): the block is on the device before
         // this call returns, whether or not it completes a frame
         VGA_HIP_TRY(hipStreamSynchronize(st->s));
+        st->chunks_fed++;
     }
     // ---- the reference's counters through this call (Encode :126-156 and what it calls): how many frames does it complete?
     // They are walked on the object and put back if the frames they promise cannot be delivered (launch, copy or status
@@ -329,6 +331,7 @@ int vga_hca_stream_encode(vga_hca_stream *st, const int16_t *const *pcm, uint8_t
     const int saved_pre = st->buffer_pre, saved_pos = st->buffer_pos, saved_samples = st->samples_processed,
               saved_frames = st->frames_processed;
     auto roll_back = [&](int rc) {
+        st->chunks_fed = saved_fed;
         st->buffer_pre = saved_pre;
         st->buffer_pos = saved_pos;
         st->samples_processed = saved_samples;
@@ -387,6 +390,10 @@ int vga_hca_stream_encode(vga_hca_stream *st, const int16_t *const *pcm, uint8_t
     };
     // the status word is this call's: an error of an earlier call was reported by that call
     if (!hip_ok(hipMemsetAsync(st->d_status.p, 0, sizeof(int), st->s), "hipMemsetAsync")) return roll_back(VGA_ERR_DEVICE);
+    if (refuse_step(VGA_TESTING_STEP_HCA_STREAM_FRAMES)) {
+        set_error("%s", kRefusedStep);
+        return roll_back(VGA_ERR_DEVICE);
+    }
     if (int rc = hca::launch_encode(st->d_pcm.as<int16_t>(), ch_pitch * st->nch, ch_pitch, 1, st->map, st->dev, st->d_frames.as<uint8_t>(),
                                     frames_pitch, pow, st->d_status.as<int>(), st->s, first, count))
         return roll_back(rc);
@@ -588,6 +595,7 @@ static int hca_encode_batch_one(const int16_t *const *pcm, int nstreams, const v
         job.d_out = d_frames.as<char>();
         job.d_out_pitch = (size_t)frames_pitch;
     }
+    job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         return vga_hca_encode_device(d_pcm.as<int16_t>() + (int64_t)first * stream_pitch, stream_pitch, ch_pitch, count, n, &h,
                                      d_frames.as<uint8_t>() + (int64_t)first * frames_pitch, frames_pitch, d_status.as<int>(), s);
@@ -653,6 +661,7 @@ static int hca_decode_batch_one(const vga_hca_info *h, const uint8_t *const *fra
         job.d_out = d_pcm.as<char>();
         job.d_out_pitch = (size_t)ch_pitch * 2;
     }
+    job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         return vga_hca_decode_device(h, d_frames.as<uint8_t>() + (int64_t)first * frames_pitch, frames_pitch, count,
                                      d_pcm.as<int16_t>() + (int64_t)first * stream_pitch, stream_pitch, ch_pitch,
@@ -724,6 +733,7 @@ int hca_encode_v_job(const std::vector<int> &units, int nch, const int16_t *cons
     pipe::Job job;
     job.units = n;
     lay.bind(job, d_pcm, d_frames);
+    job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         const int k = plan.chunk_of(first);
         if (chunk_info[k].frame_count <= 0) return VGA_OK;

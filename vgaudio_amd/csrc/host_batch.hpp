@@ -1,10 +1,13 @@
 // host_batch.hpp -- glue between the host-pointer entry points of the C ABI and host_pipeline.hpp.
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include "common.hpp"
 #include "host_pipeline.hpp"
+#include "../../include/vgaudio_hip_testing.h"
 
 namespace vga {
 
@@ -13,9 +16,16 @@ namespace vga {
 struct PipeOverride {
     int feeders = 0, drainers = 0, chunk_units = 0, slot_bytes = 0, tail_units = 0;   // slot_bytes < 0: direct copies (no staging ring); > 0: staged
     int buckets_order = 0;                   // plan_buckets: 0 = the entry point's own order, 1 = shortest chunks first, 2 = longest first
-    int transfer = 0;                        // direct rows: 0 = by transfer kernels on reserved compute units (round 6), 1 = one copy per row
-    int compute_lanes = 0;                   // > 0: that many compute streams (chunk k on stream k % lanes) whatever the entry point asked for
+    int transfer = 0;                        // 0 = transfer kernels on reserved compute units for large calls (round 6), 1 = never, 2 = always
+    int piece_bytes = 0;                     // > 0: Job::piece_bytes (the pipeline keeps its floor of 4096)
+    int compute_lanes = 0;                   // > 0: that many compute streams (chunk k on stream k % lanes): planned_compute_lanes()
 };
+// vga_testing_fail_step_this_thread(): the nth step of one kind (VGA_TESTING_STEP_*) is refused with VGA_ERR_DEVICE and
+// kRefusedStep before anything of it reaches HIP.  `seen` counts the steps of that kind so far.
+struct FailStep {
+    int kind = 0, nth = 0, seen = 0;
+};
+constexpr const char *kRefusedStep = "step refused by vga_testing_fail_step_this_thread";
 // transfer_kernels.hip
 int launch_transfer(const pipe::Job::TransferPiece *pieces, int n, hipStream_t stream);
 int device_cu_count();                               // common.hpp
@@ -30,13 +40,29 @@ struct ThreadSettings {
     int encoder_persistent = 0;
     int hca_frames_per_group = 0;
     PipeOverride pipe;
+    FailStep fail;
 };
 ThreadSettings &thread_settings();                   // runtime.hip (thread-local)
 inline PipeOverride &pipe_override() { return thread_settings().pipe; }
+// true when this step of the calling thread is the one vga_testing_fail_step_this_thread() asked to refuse (counts the step)
+inline bool refuse_step(int kind)
+{
+    FailStep &f = thread_settings().fail;
+    return f.kind == kind && ++f.seen == f.nth;
+}
 // the calling thread's last pipeline run, plus what the entry point spent around it (device allocation, small copies)
 struct PipeReport { pipe::Stats stats; double t_alloc = 0, t_entry = 0; };
 PipeReport &pipe_report();                           // runtime.hip
 int hardware_queues_requested();                     // runtime.hip: GPU_MAX_HW_QUEUES as this process sees it (the runtime's default when unset)
+// The compute lanes (pipe::Job::compute_lanes) of a host-pointer call: the lanes hook (vga_testing_host_compute_lanes_this_thread)
+// when it is set, else the entry point's own choice, at most pipe::kMaxComputeLanes.  An entry point asks once, before it
+// allocates anything per lane, and hands the answer to its job: it holds per-lane state for exactly the lanes the pipeline
+// runs.  (run_batch_pipeline() does not change the count.)
+inline int planned_compute_lanes(int own_choice)
+{
+    const int hook = pipe_override().compute_lanes;
+    return std::max(1, std::min(hook > 0 ? hook : own_choice, pipe::kMaxComputeLanes));
+}
 
 // vga_set_devices(): the GPUs the host-pointer entry points spread one call's units over (empty: the calling thread's
 // current device, nothing is spread) -- runtime.hip
@@ -106,6 +132,10 @@ template <class Body>
 inline decltype(pipe::Job::compute) chunk_compute(Body body)
 {
     return [body](int first, int count, hipStream_t s, std::string &why) -> int {
+        if (refuse_step(VGA_TESTING_STEP_CHUNK_COMPUTE)) {   // (the pipeline runs this on the calling thread)
+            why = kRefusedStep;
+            return VGA_ERR_DEVICE;
+        }
         const int rc = body(first, count, s);
         if (rc) why = vga_last_error();
         return rc;
@@ -171,7 +201,6 @@ inline int run_batch_pipeline(pipe::Job &job, int default_chunk_units)
     // two drainer threads hand the rows out.  So: one feeder with direct uploads, two drainers behind a ring, all
     // uploads on one stream and all downloads on another (a slot = the rows a worker takes at a time); slot_bytes < 0
     // (testing hook) makes both directions direct, > 0 both staged.
-    if (o.compute_lanes > 0) job.compute_lanes = o.compute_lanes;
     job.feeders = o.feeders > 0 ? o.feeders : (o.feeders < 0 ? -o.feeders : 1);   // (test hook, negative: that many feeders, a stream each)
     job.drainers = o.drainers > 0 ? o.drainers : (out_total >= ((size_t)256 << 20) ? 2 : 1);
     // rows worth page-locking one by one: from 256 KB on (smaller rows are cheap to copy into the ring)
@@ -199,6 +228,7 @@ inline int run_batch_pipeline(pipe::Job &job, int default_chunk_units)
     // chunk's kernels + download after it, whenever the first kernel started (profiles/r03_b_pipeline_timeline_head_chunk.log:
     // 539 and 550 ms against 518-538 ms without).
     job.head_units = 0;
+    std::shared_ptr<std::atomic<int>> transfers_seen;    // transfer launches so far (vga_testing_fail_step_this_thread)
     // Round 6: page-locked rows travel by transfer kernels (transfer_kernels.hip) on sixteen compute units of their own -- a
     // ragged call's 10 008 uploads no longer leave the copy engine idle between rows.  Calls of at least 256 MB only: below,
     // the rows are few and the masked streams' two rounds of persistent workgroups cost more than the copies' gaps.
@@ -206,8 +236,16 @@ inline int run_batch_pipeline(pipe::Job &job, int default_chunk_units)
     // (sixteen compute units less for the call's own kernels, the link shared with the scatter) -- the 4096 rows of 5.8 MB of
     // configs[1]'s equal-length call are better off with a copy each (519-535 ms against 590), the 10 008 files of a ragged
     // batch (2.4 MB on average) with the kernels (597 -> 556 ms): rows under 4 MB on average.
-    if (o.transfer == 0 && in_total + out_total >= ((size_t)256 << 20) && in_row_typical < ((size_t)4 << 20)) {
-        job.transfer = [](const pipe::Job::TransferPiece *pieces, int n, hipStream_t s, std::string &why) -> int {
+    // (Test hook: transfer == 2 takes this path whatever the call's size.)
+    if (o.transfer == 2 || (o.transfer == 0 && in_total + out_total >= ((size_t)256 << 20) && in_row_typical < ((size_t)4 << 20))) {
+        // the launches run on the feeder and drainer threads: they count towards the calling thread's refused step
+        const FailStep fail = thread_settings().fail;
+        auto seen = std::make_shared<std::atomic<int>>(fail.seen);
+        job.transfer = [fail, seen](const pipe::Job::TransferPiece *pieces, int n, hipStream_t s, std::string &why) -> int {
+            if (fail.kind == VGA_TESTING_STEP_TRANSFER && seen->fetch_add(1) + 1 == fail.nth) {
+                why = kRefusedStep;
+                return VGA_ERR_DEVICE;
+            }
             const int rc = launch_transfer(pieces, n, s);
             if (rc) why = vga_last_error();
             return rc;
@@ -223,10 +261,13 @@ inline int run_batch_pipeline(pipe::Job &job, int default_chunk_units)
         if (o.drainers == 0 && !job.direct_out && out_total >= ((size_t)1 << 30)) job.drainers = 4;
         job.total_cus = device_cu_count();
         job.transfer_cus = 16;
+        if (o.piece_bytes > 0) job.piece_bytes = (size_t)o.piece_bytes;
+        transfers_seen = seen;
     }
     if (ProgressSink *sink = current_progress_sink())  // vga_set_progress_callback(): one report per chunk
         job.chunk_done = [sink](int, int count) { sink->add(count); };
     const pipe::Result r = pipe::run(job);
+    if (transfers_seen && thread_settings().fail.kind == VGA_TESTING_STEP_TRANSFER) thread_settings().fail.seen = transfers_seen->load();
     pipe_report().stats = r.stats;
     if (r.code) {
         set_error("%s", r.why.c_str());

@@ -171,6 +171,7 @@ struct PinnedBlock {
 // input rows [u * in_rows_per_unit, (u + 1) * in_rows_per_unit) and the output rows [u * out_rows_per_unit, ...).
 // the compute lane of the chunk whose callback is running on this thread (0 when compute_lanes == 1)
 inline int &compute_lane() { static thread_local int lane = 0; return lane; }
+constexpr int kMaxComputeLanes = 4;      // Job::compute_lanes above this run as this many
 
 struct Job {
     int units = 0;
@@ -393,7 +394,7 @@ inline Result run(const Job &job)
     // everything HIP-side is created up front on the calling thread, destroyed after every thread has joined
     std::vector<hipStream_t> fstream(F, nullptr), dstream(D, nullptr);
     std::vector<hipEvent_t> fslot(F * R, nullptr), dslot(D * R, nullptr), upl(F * chunks, nullptr), comp(chunks, nullptr);
-    const int CL = std::max(1, std::min(job.compute_lanes, 4));
+    const int CL = std::max(1, std::min(job.compute_lanes, kMaxComputeLanes));
     std::vector<hipStream_t> cstreams(CL, nullptr);
     PinnedBlock in_ring, out_ring;
     bool ok = true;

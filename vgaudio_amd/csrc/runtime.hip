@@ -187,7 +187,13 @@ void vga_testing_host_pipeline_this_thread(int feeders, int drainers, int chunk_
 }
 void vga_testing_host_pipeline_tail_this_thread(int tail_units) { g_settings.pipe.tail_units = tail_units > 0 ? tail_units : 0; }
 void vga_testing_buckets_order_this_thread(int order) { g_settings.pipe.buckets_order = order == 1 || order == 2 ? order : 0; }
-void vga_testing_host_transfer_this_thread(int mode) { g_settings.pipe.transfer = mode == 1 ? 1 : 0; }
+void vga_testing_host_transfer_this_thread(int mode) { g_settings.pipe.transfer = mode == 1 || mode == 2 ? mode : 0; }
+void vga_testing_host_transfer_piece_bytes_this_thread(int bytes) { g_settings.pipe.piece_bytes = bytes > 0 ? bytes : 0; }
+void vga_testing_fail_step_this_thread(int kind, int nth)
+{
+    const bool on = kind >= VGA_TESTING_STEP_CHUNK_COMPUTE && kind <= VGA_TESTING_STEP_HCA_STREAM_FRAMES && nth > 0;
+    g_settings.fail = FailStep{on ? kind : 0, on ? nth : 0, 0};
+}
 void vga_testing_host_compute_lanes_this_thread(int lanes) { g_settings.pipe.compute_lanes = lanes > 0 ? lanes : 0; }
 
 int vga_testing_plan_buckets(const int *group, const int *length, int n, int max_units, long long max_volume, int longest_first,
