@@ -137,7 +137,8 @@ def test_decoders_hand_a_few_never_closing_channels_from_the_tail_kernel_to_the_
     """A batch of ordinary channels with ONE or two rows whose seams never close (GC-ADPCM: the 440 Hz sine; ADX: the clipped
     square): far fewer open seams than the fix-up's `many`, so the tail kernel chains them -- and a lane that has walked its
     budget (4096 frames, ADX 2048) without meeting hands its channel to the REPAIR launch in mid-launch (first_open[ch] = k + 1,
-    slow_seams raised to `many`; gc_decode_kernel.hip / adx_kernels.hip tail kernels).  Every row against the oracle."""
+    slow_seams raised to `many`; seam_tail in seams.hpp, which both decoders' tail kernels run).  Every row against the
+    oracle."""
     d = torch.device("cuda:0")
     L = _lib.lib()
     st = torch.cuda.current_stream().cuda_stream

@@ -9,6 +9,7 @@
 // Formats/CriAdx/CriAdxFormat.cs:67 / :37).  Frame size is a run-time parameter.
 #include "common.hpp"
 #include "adx_kernels.hpp"
+#include "seams.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -276,10 +277,8 @@ __global__ __launch_bounds__(64) void adx_decode_fs18_direct_kernel(
     int repair_piece = 0;
     if (repair) {
         if (slow_seams[0] < slow_seams[1]) return;                        // few: adx_decode_fs18_tail_kernel has them
-        int k = live ? first_open[ch] : 0x7f000000;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) k = min(k, __shfl_xor(k, o));
-        if (k <= 0 || k >= 0x7f000000) return;
+        const int k = wave_first_open(first_open, live, ch);
+        if (!is_open(k)) return;
         repair_piece = k;
     }
     const int64_t first_frame = (int64_t)(repair ? repair_piece : (int)blockIdx.y) * seg_frames;   // even (seg_frames is)
@@ -527,125 +526,44 @@ __device__ __forceinline__ void adx_decode_frame_serial(const uint8_t *fr, const
     }
 }
 
-// Closes the seams between time segments: one lane per (channel, seam), all seams at once.  From the history the piece
-// before ended on (its last two samples: final provided THAT piece's own seam closes) decode again frame by frame
-// over the guessed run's samples until both histories coincide at a frame end -- from there on the guessed run is
-// what the serial decoder produces.  A seam that does not close inside its piece records its index in
-// first_open[channel]; adx_decode_fs18_tail_kernel then decodes that channel serially from there.  Exact in every case.
+// The ADX side of the seam protocol (seams.hpp): lane = channel at the dense pitch.  own_samples (the ragged entry point's
+// length buckets, capi_adx.hip): the channel is a shorter stream padded to total_samples.
+template <bool V4>
+struct AdxDecodeSeams {
+    static constexpr int FRAME_SAMPLES = 32, FRAME_BYTES = 18;
+    static constexpr int SLOW_SEAM = ADX_DECODE_SLOW_SEAM, SLOW_POLL = 128, TAIL_BUDGET = ADX_DECODE_TAIL_BUDGET;
+    static constexpr bool HAS_OWN = true;
+    const uint8_t *adpcm; int64_t in_pitch; AdxDeviceParams p; int16_t *pcm; int64_t pcm_pitch; const int *own_samples;
+    const uint8_t *src; int16_t *dst;                                    // (open)
+    __device__ int channel(int slot) const { return slot; }
+    __device__ int length(int, int total) const { return total; }
+    __device__ int64_t own(int ch, int total) const { return own_samples ? (int64_t)own_samples[ch] : (int64_t)total; }
+    __device__ void open(int ch)
+    {
+        src = adpcm + (int64_t)ch * in_pitch;
+        dst = pcm + (int64_t)ch * pcm_pitch;
+    }
+    __device__ void decode(const uint8_t *fr, int valid, int &h1, int &h2, int16_t *o) const { adx_decode_frame_serial<V4>(fr, p, valid, h1, h2, o); }
+};
+
 template <bool V4>
 __global__ __launch_bounds__(64) void adx_decode_fs18_fixup_kernel(
     const uint8_t *__restrict__ adpcm, int64_t in_pitch, int nch, int total_samples, int seg_frames, AdxDeviceParams p,
     int16_t *__restrict__ pcm, int64_t pcm_pitch, int *__restrict__ first_open, int *__restrict__ seam_open, int force_open,
     int *__restrict__ slow_seams, const int *__restrict__ own_samples)
 {
-    const int ch = blockIdx.x * 64 + threadIdx.x;
-    const int k = blockIdx.y + 1;
-    const int64_t f0 = (int64_t)k * seg_frames;
-    if (ch >= nch || f0 * 32 >= total_samples) return;
-    // own_samples (the ragged entry point's length buckets, capi_adx.hip): the channel is a shorter stream padded to
-    // total_samples; a seam in its padding is nobody's output, and neither is what a run does once it has passed the
-    // channel's own samples (two runs through zero frames need never meet: -1 is a fixed point of the predictor's floor)
-    const int64_t own = own_samples ? (int64_t)own_samples[ch] : (int64_t)total_samples;
-    if (f0 * 32 >= own) return;
-    const uint8_t *src = adpcm + (int64_t)ch * in_pitch;
-    int16_t *dst = pcm + (int64_t)ch * pcm_pitch;
-    // Seed read concurrently with seam k-1's lane rewriting piece k-1 -- same invariant as gc_decode_fixup_kernel
-    // (gc_decode_kernel.hip): a seam that closes leaves the piece's last samples with the values they already hold,
-    // one that stays open hands pieces k.. to the tail kernel, which redoes them from the final samples.
-    int hist1 = dst[f0 * 32 - 1], hist2 = dst[f0 * 32 - 2];
-    // (round 5, as gc_decode_fixup_kernel: a seam still open after ADX_DECODE_SLOW_SEAM frames counts as slow; once the batch
-    // holds slow_seams[1] of them the lanes give up and the REPAIR launch of the direct kernel decodes from their pieces on)
-    int walked = 0;
-    bool counted = false, gave_up = false;
-    const bool countable = !seam_forced_open(force_open, ch, k) || force_open == 3;
-    for (int64_t f = f0; f < f0 + seg_frames && f * 32 < total_samples; f++) {
-        const int valid = (int)((int64_t)total_samples - f * 32 < 32 ? (int64_t)total_samples - f * 32 : 32);
-        int16_t *o = dst + f * 32;
-        int g1 = 0, g2 = 0;                             // the guessed run's history at this frame's end
-        if (valid == 32) { g1 = o[31]; g2 = o[30]; }
-        adx_decode_frame_serial<V4>(src + f * 18, p, valid, hist1, hist2, o);
-        if (valid == 32 && hist1 == g1 && hist2 == g2 && !seam_forced_open(force_open, ch, k)) return;
-        if (valid < 32) return;                         // the stream's last, partial frame: nothing follows
-        if ((f + 1) * 32 >= own) return;                // the channel's own samples are all final
-        if (++walked == ADX_DECODE_SLOW_SEAM && countable) {
-            atomicAdd(&slow_seams[0], 1);
-            counted = true;
-        }
-        if (walked >= ADX_DECODE_SLOW_SEAM && (walked & 127) == 0 &&
-            __hip_atomic_load(&slow_seams[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= slow_seams[1]) {
-            gave_up = true;
-            break;
-        }
-    }
-    const bool piece_follows = f0 + seg_frames < ((int64_t)total_samples + 31) / 32;
-    if (!counted && piece_follows && countable) atomicAdd(&slow_seams[0], 1);
-    if (piece_follows || gave_up) {                     // open (and a piece follows), or this piece itself is left unfinished
-        if (piece_follows) seam_open[(int64_t)(k - 1) * nch + ch] = 1;
-        atomicMin(&first_open[ch], k);
-    }
+    seam_fixup(AdxDecodeSeams<V4>{adpcm, in_pitch, p, pcm, pcm_pitch, own_samples}, nch, total_samples, seg_frames, first_open,
+               seam_open, force_open, slow_seams);
 }
 
-// Channels with an open seam (practically none): decode serially from the piece after it to the end of the stream.
-// The channels with an open seam, piece after piece -- as gc_decode_tail_kernel (gc_decode_kernel.hip): the piece after
-// an open seam is decoded again from the final samples until it agrees with what the piece holds at a frame end; a run
-// that does not meet carries on into the next piece; a later open seam starts the same again.
 template <bool V4>
 __global__ __launch_bounds__(64) void adx_decode_fs18_tail_kernel(
     const uint8_t *__restrict__ adpcm, int64_t in_pitch, int nch, int total_samples, int seg_frames, int segments, AdxDeviceParams p,
     int16_t *__restrict__ pcm, int64_t pcm_pitch, int *__restrict__ first_open, const int *__restrict__ seam_open,
     int force_open, int *__restrict__ slow_seams, const int *__restrict__ own_samples)
 {
-    const int ch = blockIdx.x * 64 + threadIdx.x;
-    if (ch >= nch) return;
-    const int64_t own = own_samples ? (int64_t)own_samples[ch] : (int64_t)total_samples;       // (see the fix-up kernel)
-    // many seams that would not close -- or a lane of this launch has handed a channel over (below): the REPAIR launch runs,
-    // and it takes every channel whose first_open is still set, this one included
-    if (__hip_atomic_load(&slow_seams[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= slow_seams[1]) return;
-    const int k0 = first_open[ch];
-    if (k0 <= 0 || k0 >= 0x7f000000) return;
-    int walked_total = 0;                               // frames this lane has decoded again (see ADX_DECODE_TAIL_BUDGET)
-    const uint8_t *src = adpcm + (int64_t)ch * in_pitch;
-    int16_t *dst = pcm + (int64_t)ch * pcm_pitch;
-    bool carry = false;
-    int hist1 = 0, hist2 = 0;
-    for (int k = k0; k < segments; k++) {
-        const int64_t f0 = (int64_t)k * seg_frames;
-        if (f0 * 32 >= total_samples || f0 * 32 >= own) break;
-        const bool flagged = seam_open[(int64_t)(k - 1) * nch + ch] != 0;
-        bool apart = false;
-        if (carry) {
-            apart = true;
-            for (int64_t f = f0; f < f0 + seg_frames && f * 32 < total_samples; f++) {
-                const int valid = (int)((int64_t)total_samples - f * 32 < 32 ? (int64_t)total_samples - f * 32 : 32);
-                int16_t *o = dst + f * 32;
-                int g1 = 0, g2 = 0;
-                if (valid == 32) { g1 = o[31]; g2 = o[30]; }
-                adx_decode_frame_serial<V4>(src + f * 18, p, valid, hist1, hist2, o);
-                walked_total++;
-                if (valid == 32 && hist1 == g1 && hist2 == g2 && !seam_forced_open(force_open, ch, k)) { apart = false; break; }
-                if ((f + 1) * 32 >= own) { apart = false; break; }          // past the channel's own samples: as good as met
-            }
-        }
-        const int64_t f1 = f0 + seg_frames;
-        if (apart) {
-            carry = true;
-            // A run that has not met after ADX_DECODE_TAIL_BUDGET frames (a tone, a clipped wave: it never will) is not
-            // walked to the end of the stream by ONE lane: pieces up to this one are final now, the REPAIR launch decodes
-            // the channel's wave from the next piece on at the direct kernel's speed (bench.py signal_sensitivity: 43
-            // such channels in 4096 cost this kernel 347 ms).  Seams the test hook holds open do not count.
-            if (walked_total >= ADX_DECODE_TAIL_BUDGET && f1 * 32 < total_samples && (force_open == 0 || force_open == 3)) {
-                first_open[ch] = k + 1;
-                atomicMax(&slow_seams[0], slow_seams[1]);
-                return;
-            }
-        } else if (flagged && f1 * 32 < total_samples) {
-            carry = true;
-            hist1 = dst[f1 * 32 - 1];
-            hist2 = dst[f1 * 32 - 2];
-        } else
-            carry = false;
-    }
-    first_open[ch] = 0x7f7f7f7f;                        // done: nothing of this channel is left for the REPAIR launch
+    seam_tail(AdxDecodeSeams<V4>{adpcm, in_pitch, p, pcm, pcm_pitch, own_samples}, nch, total_samples, seg_frames, segments,
+              first_open, seam_open, force_open, slow_seams);
 }
 
 // A frame's 32 input samples as the 16 dwords they are loaded as; sample j sign-extended (one v_bfe_i32 / v_ashrrev, or an
@@ -780,10 +698,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     int k = blockIdx.y;
     if (REPAIR) {
         if (open_seams[0] < many) return;              // few: adx_encode_fs18_tail_kernel has chained them
-        int ko = ch_raw < nch ? first_open[ch_raw] : 0x7f000000;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) ko = min(ko, __shfl_xor(ko, o));
-        if (ko <= 0 || ko >= 0x7f000000) return;       // no open seam among this wave's channels
+        const int ko = wave_first_open(first_open, ch_raw < nch, ch_raw);
+        if (!is_open(ko)) return;                      // no open seam among this wave's channels
         k = ko;
     }
     const int ch = ch_raw;
@@ -1126,7 +1042,7 @@ __global__ __launch_bounds__(64) void adx_encode_fs18_tail_kernel(
     if (ch >= nch) return;
     if (open_seams[0] >= many) return;                 // many seams that would not close: the REPAIR launch takes them all
     const int k0 = first_open[ch];
-    if (k0 <= 0 || k0 >= 0x7f000000) return;
+    if (k0 <= 0 || k0 >= SEAM_OPEN_LIMIT) return;      // (!is_open(k0), spelt out: the call compiles to another compare)
     const int64_t own_end = own_frames ? (int64_t)own_frames[ch] : ((int64_t)total_length + 31) / 32;   // (see the fix-up kernel)
     const int16_t *src = pcm + (int64_t)ch * pcm_pitch;
     uint8_t *dst = out + (int64_t)ch * out_pitch;
@@ -1184,13 +1100,8 @@ int launch_encode(const int16_t *d_pcm, int64_t pcm_pitch, int nch, int pcm_leng
         const int groups64 = (nch + 63) / 64;
         const int cus = device_cu_count();
         const int frames = (pcm_length + 31) / 32;
-        int segments = cus * 4 * ADX_DIRECT_WAVES_PER_SIMD / groups64;
-        if (segments > frames / ADX_DIRECT_MIN_PIECE_FRAMES) segments = frames / ADX_DIRECT_MIN_PIECE_FRAMES;
-        if (segments < 1) segments = 1;
-        if (segments > 64) segments = 64;
-        if (encoder_segments_override() > 0) segments = std::min(std::max(frames / 64, 1), encoder_segments_override());   // test hook
-        int seg_frames = (frames + segments - 1) / segments;
-        seg_frames += seg_frames & 1;
+        const PiecePlan plan = plan_pieces(frames, cus * 4 * ADX_DIRECT_WAVES_PER_SIMD / groups64, ADX_DIRECT_MIN_PIECE_FRAMES, 64, 2);
+        const int segments = plan.segments, seg_frames = plan.seg_frames;
         AsyncBuf scratch;                              // freed (stream-ordered) on every exit path
         int16_t *seg_state = nullptr;                  // [segments][nch][2] final histories, then [nch] first open seam
         int *first_open = nullptr, *seam_open = nullptr, *seam_end = nullptr, *queue = nullptr;
@@ -1206,14 +1117,13 @@ int launch_encode(const int16_t *d_pcm, int64_t pcm_pitch, int nch, int pcm_leng
             seam_end = seam_open + (size_t)(segments - 1) * nch;
             queue = seam_end + (size_t)(segments - 1) * nch;
             crumbs = reinterpret_cast<uint2 *>(scratch.as<unsigned char>() + small_bytes);
-            VGA_HIP_TRY(hipMemsetAsync(first_open, 0x7f, (size_t)nch * sizeof(int), stream));
+            VGA_HIP_TRY(fill_no_open_seams(first_open, nch, stream));
             VGA_HIP_TRY(hipMemsetAsync(seam_open, 0, flag_bytes, stream));
             VGA_HIP_TRY(hipMemsetAsync(queue, 0, 2 * sizeof(int), stream));
         }
         int *open_seams = queue ? queue + 1 : nullptr; // seams still open at the end of their pieces
-        // "many": one seam in 64, and at least 8 -- as the decoders' threshold (gc_decode_kernel.hip); test hook mode 3 = any
-        const int many = force_open_seams() == 3 ? 1
-                         : (int)std::min<int64_t>(0x7fffffff, std::max<int64_t>(8, (int64_t)nch * (segments - 1) / 64));
+        // "many" as the decoders' threshold; test hook mode 3 = any
+        const int many = force_open_seams() == 3 ? 1 : many_open_seams(nch, segments);
         // the fix-up's persistent waves: one per SIMD, fewer when there are not that many seams
         int fixup_waves = cus * 4 * ADX_FIXUP_WAVES_PER_SIMD;
 #ifdef VGA_TUNING   // tools/build_variants.sh only
@@ -1279,32 +1189,12 @@ int launch_decode(const uint8_t *d_adpcm, int64_t in_pitch, int nch, int sample_
         // row position per (channel, piece): at configs[2] 8 / 16 / 32 / 64 pieces take 8.5 / 8.0 / 13.1 / 12.1 ms (and 12 or
         // 24, which leave some SIMDs with two waves and some with one, 11 ms)
         const int groups = (nch + 63) / 64;
-        const int cus = device_cu_count();
         const int frames = (sample_count + 31) / 32;
-        int segments = cus * 4 / groups;
-        if (segments > frames / 512) segments = frames / 512;
-        if (segments < 1) segments = 1;
-        // every piece boundary is a seam that may still be open at the end of its piece (an integer IIR can keep two runs
-        // one LSB apart for good; the tail kernel then decodes the next piece again from the true history, piece after
-        // piece while the runs stay apart): at most 64 pieces
-        if (segments > 64) segments = 64;
-        if (encoder_segments_override() > 0) segments = std::min(std::max(frames / 8, 1), encoder_segments_override());   // test hook
-        int seg_frames = (frames + segments - 1) / segments;
-        seg_frames += seg_frames & 1;
-        AsyncBuf scratch;                              // freed (stream-ordered) on every exit path
-        int *first_open = nullptr, *seam_open = nullptr, *slow_seams = nullptr;
-        if (segments > 1) {
-            const size_t flag_bytes = (size_t)(segments - 1) * nch * sizeof(int);
-            VGA_HIP_TRY(scratch.alloc((size_t)nch * sizeof(int) + flag_bytes + 16, stream));
-            first_open = scratch.as<int>();
-            seam_open = first_open + nch;
-            slow_seams = seam_open + (size_t)(segments - 1) * nch;         // [0] seams that stayed open, [1] how many make "many"
-            VGA_HIP_TRY(hipMemsetAsync(first_open, 0x7f, (size_t)nch * sizeof(int), stream));
-            VGA_HIP_TRY(hipMemsetAsync(seam_open, 0, flag_bytes + 16, stream));
-            const int many = (int)std::min<int64_t>(0x7fffffff, std::max<int64_t>(8, (int64_t)nch * (segments - 1) / 64));   // (gc_decode_kernel.hip)
-            // (a fill, not a copy from this stack frame: a pageable host-to-device copy makes the call wait for the stream)
-            VGA_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(slow_seams + 1), many, 1, stream));
-        }
+        const PiecePlan plan = plan_pieces(frames, device_cu_count() * 4 / groups, 512, 8, 2);
+        const int segments = plan.segments, seg_frames = plan.seg_frames;
+        DecodeSeams ds;
+        if (segments > 1)
+            if (const int rc = ds.init(nch, segments, stream)) return rc;
 #define VGA_ADX_DEC_T(V)                                                                                                 \
         {                                                                                                                \
             hipLaunchKernelGGL((adx_decode_fs18_direct_kernel<V, false>), dim3(groups, segments), dim3(64), 0, stream,   \
@@ -1313,16 +1203,16 @@ int launch_decode(const uint8_t *d_adpcm, int64_t in_pitch, int nch, int sample_
             VGA_HIP_TRY(hipGetLastError());                                                                              \
             if (segments > 1) {                                                                                          \
                 hipLaunchKernelGGL(adx_decode_fs18_fixup_kernel<V>, dim3(groups, segments - 1), dim3(64), 0, stream,    \
-                                   d_adpcm, in_pitch, nch, sample_count, seg_frames, p, d_pcm, pcm_pitch, first_open,   \
-                                   seam_open, force_open_seams(), slow_seams, d_own_samples);                           \
+                                   d_adpcm, in_pitch, nch, sample_count, seg_frames, p, d_pcm, pcm_pitch, ds.first_open, \
+                                   ds.seam_open, force_open_seams(), ds.slow_seams, d_own_samples);                     \
                 VGA_HIP_TRY(hipGetLastError());                                                                          \
                 hipLaunchKernelGGL(adx_decode_fs18_tail_kernel<V>, dim3(groups), dim3(64), 0, stream, d_adpcm, in_pitch, \
-                                   nch, sample_count, seg_frames, segments, p, d_pcm, pcm_pitch, first_open, seam_open,  \
-                                   force_open_seams(), slow_seams, d_own_samples);                                      \
+                                   nch, sample_count, seg_frames, segments, p, d_pcm, pcm_pitch, ds.first_open,          \
+                                   ds.seam_open, force_open_seams(), ds.slow_seams, d_own_samples);                     \
                 VGA_HIP_TRY(hipGetLastError());                                                                          \
                 hipLaunchKernelGGL((adx_decode_fs18_direct_kernel<V, true>), dim3(groups, 1), dim3(64), 0, stream,       \
                                    d_adpcm, in_pitch, nch, sample_count, seg_frames, p, d_pcm, pcm_pitch, d_status,      \
-                                   (const int *)first_open, (const int *)slow_seams);                                   \
+                                   (const int *)ds.first_open, (const int *)ds.slow_seams);                             \
             }                                                                                                            \
         }
         if (p.version == 4) VGA_ADX_DEC_T(true)

@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include "gcadpcm_kernels.hpp"
+#include "seams.hpp"
 
 #include <cstdlib>
 
@@ -61,10 +62,8 @@ __global__ __launch_bounds__(64) void gc_decode_direct_kernel(
     int repair_piece = 0;
     if (repair) {
         if (slow_seams[0] < slow_seams[1]) return;                        // few open seams: gc_decode_tail_kernel has them
-        int k = live ? first_open[ch] : 0x7f000000;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) k = imin(k, __shfl_xor(k, o));
-        if (k <= 0 || k >= 0x7f000000) return;                            // none of these channels has an open seam
+        const int k = wave_first_open(first_open, live, ch);
+        if (!is_open(k)) return;                                           // none of these channels has an open seam
         repair_piece = k;
     }
     const int64_t first_frame = (int64_t)(repair ? repair_piece : (int)blockIdx.y) * seg_frames;   // a multiple of 8 (seg_frames is)
@@ -281,142 +280,44 @@ __device__ __forceinline__ void gc_decode_frame_serial(const uint8_t *fr, const 
     }
 }
 
-// Closes the seams between time segments: one lane per (channel, seam), all seams at once.  From the history the piece
-// before ended on (its last two samples: final provided THAT piece's own seam closes) decode again frame by frame over
-// the guessed run's samples until both histories coincide at a frame end -- from there on the guessed run decoded
-// exactly what the serial decoder would have.  A seam that does not close inside its piece records its index in
-// first_open[channel]; gc_decode_tail_kernel then decodes that channel serially from the next piece on.  Always exact.
+// The GC-ADPCM side of the seam protocol (seams.hpp): a lane's channel is rg.order[slot] with its own length and offsets
+// when the batch is ragged, the slot at the dense pitch otherwise.
+struct GcDecodeSeams {
+    static constexpr int FRAME_SAMPLES = 14, FRAME_BYTES = 8;
+    static constexpr int SLOW_SEAM = GC_DECODE_SLOW_SEAM, SLOW_POLL = 256, TAIL_BUDGET = GC_DECODE_TAIL_BUDGET;
+    static constexpr bool HAS_OWN = false;
+    const uint8_t *adpcm; int64_t adpcm_pitch; const int16_t *coefs; int16_t *pcm; int64_t pcm_pitch; Ragged rg;
+    const uint8_t *src; int16_t *dst; int cf[16];                        // (open)
+    __device__ int channel(int slot) const { return rg.order ? rg.order[slot] : slot; }
+    __device__ int length(int ch, int total) const { return rg.order ? rg.length[ch] : total; }
+    __device__ int64_t own(int, int total) const { return total; }
+    __device__ void open(int ch)
+    {
+        src = adpcm + (rg.order ? rg.adpcm_off[ch] : (int64_t)ch * adpcm_pitch);
+        dst = pcm + (rg.order ? rg.pcm_off[ch] : (int64_t)ch * pcm_pitch);
+#pragma unroll
+        for (int i = 0; i < 16; i++) cf[i] = coefs[ch * 16 + i];
+    }
+    __device__ void decode(const uint8_t *fr, int valid, int &h1, int &h2, int16_t *o) const { gc_decode_frame_serial(fr, cf, valid, h1, h2, o); }
+};
+
 __global__ __launch_bounds__(64) void gc_decode_fixup_kernel(
     const uint8_t *__restrict__ adpcm, int64_t adpcm_pitch, const int16_t *__restrict__ coefs, int nch,
     int total_samples, int seg_frames, int16_t *__restrict__ pcm, int64_t pcm_pitch, int *__restrict__ first_open,
     int *__restrict__ seam_open, int force_open, const Ragged rg, int *__restrict__ slow_seams)
 {
-    const int slot = blockIdx.x * 64 + threadIdx.x;
-    const int k = blockIdx.y + 1;
-    const int64_t f0 = (int64_t)k * seg_frames;
-    if (slot >= nch) return;
-    const int ch = rg.order ? rg.order[slot] : slot;
-    if (rg.order) total_samples = rg.length[ch];
-    if (f0 * 14 >= total_samples) return;
-    const uint8_t *src = adpcm + (rg.order ? rg.adpcm_off[ch] : (int64_t)ch * adpcm_pitch);
-    int16_t *dst = pcm + (rg.order ? rg.pcm_off[ch] : (int64_t)ch * pcm_pitch);
-    int cf[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) cf[i] = coefs[ch * 16 + i];
-    const int full_frames = total_samples / 14;
-    // Seed = the last two samples of piece k-1, read while seam k-1's lane (another thread, all seams run at once) may
-    // still be rewriting that piece.  Invariant that makes this safe: if seam k-1 CLOSES, the samples it rewrites past
-    // its closing frame are untouched and the ones before it get the values of the serial run -- the tail of piece
-    // k-1, which is what is read here, is identical before and after (a closing seam never reaches the last frame
-    // without having matched the guessed run there, i.e. it rewrites those two samples with the values they hold);
-    // if seam k-1 stays OPEN, first_open[ch] <= k-1 and gc_decode_tail_kernel decodes pieces k.. again from the final
-    // samples, overwriting whatever this lane produced from a possibly stale seed.  Either way the output is exact.
-    int h1 = dst[f0 * 14 - 1], h2 = dst[f0 * 14 - 2];
-    // Round 5: a seam still open after GC_DECODE_SLOW_SEAM frames counts as slow (slow_seams[0]); once the batch holds
-    // slow_seams[1] of them -- a batch of tones: their seams never close -- the lanes stop walking their pieces (12 800 frames
-    // each at configs[1]) and leave everything from their piece on to the REPAIR launch of the direct kernel, which decodes
-    // the affected waves as one piece.  Below that count nothing changes: a seam runs to its piece's end and
-    // gc_decode_tail_kernel chains the few that stay open.  (A lane only gives up when the count has been reached, so
-    // "somebody gave up" implies the REPAIR launch runs.)
-    int walked = 0;
-    bool counted = false, gave_up = false;
-    // (seams the test hook holds open are not counted -- modes 1 and 2 exercise the tail kernel as before -- unless it asks for it: 3)
-    const bool countable = !seam_forced_open(force_open, ch, k) || force_open == 3;
-    for (int64_t f = f0; f < f0 + seg_frames && f * 14 < total_samples; f++) {
-        const int valid = f < full_frames ? 14 : total_samples - (int)(f * 14);
-        int16_t *o = dst + f * 14;
-        int g1 = 0, g2 = 0;                            // the guessed run's history at this frame's end
-        if (valid == 14) { g1 = o[13]; g2 = o[12]; }
-        gc_decode_frame_serial(src + f * 8, cf, valid, h1, h2, o);
-        if (valid == 14 && h1 == g1 && h2 == g2 && !seam_forced_open(force_open, ch, k)) return;
-        if (valid < 14) return;                        // the stream's last, partial frame: nothing follows
-        if (++walked == GC_DECODE_SLOW_SEAM && countable) {
-            atomicAdd(&slow_seams[0], 1);
-            counted = true;
-        }
-        if (walked >= GC_DECODE_SLOW_SEAM && (walked & 255) == 0 &&
-            __hip_atomic_load(&slow_seams[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= slow_seams[1]) {
-            gave_up = true;
-            break;
-        }
-    }
-    const bool piece_follows = (f0 + seg_frames) * 14 < total_samples;
-    if (!counted && piece_follows && countable) atomicAdd(&slow_seams[0], 1);   // (a piece shorter than the limit that never closed)
-    if (piece_follows || gave_up) {                    // open (and a piece follows), or this piece itself is left unfinished
-        if (piece_follows) seam_open[(int64_t)(k - 1) * nch + ch] = 1;
-        atomicMin(&first_open[ch], k);
-    }
+    seam_fixup(GcDecodeSeams{adpcm, adpcm_pitch, coefs, pcm, pcm_pitch, rg}, nch, total_samples, seg_frames, first_open, seam_open,
+               force_open, slow_seams);
 }
 
-// Channels with an open seam (practically none): seam k re-decoded all of piece k, so that piece is final; everything
-// after it was seeded from samples that have changed since and is decoded again here, serially.
-// The channels with an open seam, piece after piece (one lane per channel; lanes without one leave at once).  A seam
-// that ran out of frames has made ITS piece final, but the piece after it was seeded from samples that have changed
-// since: that piece is decoded again from the final samples -- next to what it holds, which is a run of the same
-// recurrence from some other history -- until both agree at a frame end; from there on the stored samples are the
-// serial decoder's.  (Round 1 decoded the whole rest of the channel again: 220 ms for a 60 s channel.)  A run that
-// does not meet by the end of a piece carries on into the next one; a later open seam of the channel starts the same
-// again.  seam_open[(k - 1) * nch + ch] != 0: seam k (the start of piece k) stayed open.
 __global__ __launch_bounds__(64) void gc_decode_tail_kernel(
     const uint8_t *__restrict__ adpcm, int64_t adpcm_pitch, const int16_t *__restrict__ coefs, int nch,
     int total_samples, int seg_frames, int segments, int16_t *__restrict__ pcm, int64_t pcm_pitch,
     int *__restrict__ first_open, const int *__restrict__ seam_open, int force_open, const Ragged rg,
     int *__restrict__ slow_seams)
 {
-    const int slot = blockIdx.x * 64 + threadIdx.x;
-    if (slot >= nch) return;
-    // many seams that would not close -- or a lane of this launch has handed a channel over (below): the REPAIR launch of the
-    // direct kernel runs, and it takes every channel whose first_open is still set, this one included
-    if (__hip_atomic_load(&slow_seams[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= slow_seams[1]) return;
-    const int ch = rg.order ? rg.order[slot] : slot;
-    if (rg.order) total_samples = rg.length[ch];
-    const int k0 = first_open[ch];
-    if (k0 <= 0 || k0 >= 0x7f000000) return;
-    int walked_total = 0;                              // frames this lane has decoded again (see GC_DECODE_TAIL_BUDGET)
-    const uint8_t *src = adpcm + (rg.order ? rg.adpcm_off[ch] : (int64_t)ch * adpcm_pitch);
-    int16_t *dst = pcm + (rg.order ? rg.pcm_off[ch] : (int64_t)ch * pcm_pitch);
-    int cf[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) cf[i] = coefs[ch * 16 + i];
-    const int full_frames = total_samples / 14;
-    bool carry = false;                                // the piece before ended on samples other than the ones this piece was seeded from
-    int h1 = 0, h2 = 0;
-    for (int k = k0; k < segments; k++) {
-        const int64_t f0 = (int64_t)k * seg_frames;
-        if (f0 * 14 >= total_samples) break;
-        const bool flagged = seam_open[(int64_t)(k - 1) * nch + ch] != 0;
-        bool apart = false;
-        if (carry) {
-            apart = true;
-            for (int64_t f = f0; f < f0 + seg_frames && f * 14 < total_samples; f++) {
-                const int valid = f < full_frames ? 14 : total_samples - (int)(f * 14);
-                int16_t *o = dst + f * 14;
-                int g1 = 0, g2 = 0;
-                if (valid == 14) { g1 = o[13]; g2 = o[12]; }
-                gc_decode_frame_serial(src + f * 8, cf, valid, h1, h2, o);
-                walked_total++;
-                if (valid == 14 && h1 == g1 && h2 == g2 && !seam_forced_open(force_open, ch, k)) { apart = false; break; }
-            }
-        }
-        const int64_t f1 = f0 + seg_frames;            // the next piece's first frame
-        if (apart) {
-            carry = true;                              // (h1, h2): the true samples at the end of this piece
-            // A run that has not met after GC_DECODE_TAIL_BUDGET frames (a pure tone: it never will) is not walked to the end
-            // of the stream by ONE lane: the pieces up to this one are final now, the REPAIR launch decodes the channel's wave
-            // from the next piece on at the direct kernel's speed.  Seams the test hook holds open do not count.
-            if (walked_total >= GC_DECODE_TAIL_BUDGET && f1 * 14 < total_samples && (force_open == 0 || force_open == 3)) {
-                first_open[ch] = k + 1;
-                atomicMax(&slow_seams[0], slow_seams[1]);
-                return;
-            }
-        } else if (flagged && f1 * 14 < total_samples) {
-            carry = true;                              // this piece's own seam ran out of frames: the piece is final, its end the truth
-            h1 = dst[f1 * 14 - 1];
-            h2 = dst[f1 * 14 - 2];
-        } else
-            carry = false;
-    }
-    first_open[ch] = 0x7f7f7f7f;                       // done: nothing of this channel is left for the REPAIR launch
+    seam_tail(GcDecodeSeams{adpcm, adpcm_pitch, coefs, pcm, pcm_pitch, rg}, nch, total_samples, seg_frames, segments, first_open,
+              seam_open, force_open, slow_seams);
 }
 
 int launch_decode(const uint8_t *d_adpcm, int64_t adpcm_pitch, const int16_t *d_coefs, int nch, int sample_count,
@@ -427,23 +328,20 @@ int launch_decode(const uint8_t *d_adpcm, int64_t adpcm_pitch, const int16_t *d_
     if (rgp) sample_count = rg.max_length;
     if (nch <= 0 || sample_count <= 0) return VGA_OK;
     // as many time pieces as put one wave on every SIMD (a wave = 64 channels of one piece), each at least 1024 frames long
-    // and a multiple of eight frames; at most 64 (every seam is a chance of a run that never meets, see adx_kernels.hip)
+    // and a multiple of eight frames
     const int frames = (sample_count + 13) / 14;
     const int groups = (nch + 63) / 64;
     const int cus = device_cu_count();
-    int segments = cus * 4 / groups;
+    int want = cus * 4 / groups;
     if (rgp) {
         // ragged: pieces of one length for every channel, twice as many waves as the chip holds at once (the short ones
-        // make room), `segments` = what the longest channel needs
-        const int64_t want = (int64_t)cus * 4 * 2;
-        const int64_t piece = std::max<int64_t>((rg.total_frames + 64 * want - 1) / (64 * want), 1024);
-        segments = (int)((frames + piece - 1) / piece);
+        // make room), `want` = what the longest channel needs
+        const int64_t waves = (int64_t)cus * 4 * 2;
+        const int64_t piece = std::max<int64_t>((rg.total_frames + 64 * waves - 1) / (64 * waves), 1024);
+        want = (int)((frames + piece - 1) / piece);
     }
-    if (segments > frames / 1024) segments = frames / 1024;
-    if (segments < 1) segments = 1;
-    if (segments > 64) segments = 64;
-    if (encoder_segments_override() > 0) segments = std::min(std::max(frames / 8, 1), encoder_segments_override());   // test hook
-    const int seg_frames = ((frames + segments - 1) / segments + 7) / 8 * 8;
+    const PiecePlan plan = plan_pieces(frames, want, 1024, 8, 8);
+    const int segments = plan.segments, seg_frames = plan.seg_frames;
     // rows of samples on 16-byte boundaries: whole 224-byte runs leave as 16-byte stores
     const bool turned = (pcm_pitch % 8) == 0 && ((uintptr_t)d_pcm % 16) == 0;
 #define VGA_GC_DIRECT(TURNED_, RAGGED_, REPAIR_, PIECES_, OPEN_, SLOW_)                                                          \
@@ -467,27 +365,17 @@ int launch_decode(const uint8_t *d_adpcm, int64_t adpcm_pitch, const int16_t *d_
 #undef VGA_GC_DIRECT
     VGA_HIP_TRY(direct(segments, nullptr, nullptr));
     if (segments > 1) {
-        AsyncBuf scratch;                              // freed (stream-ordered) on every exit path
-        const size_t flag_bytes = (size_t)(segments - 1) * nch * sizeof(int);
-        VGA_HIP_TRY(scratch.alloc((size_t)nch * sizeof(int) + flag_bytes + 16, stream));
-        int *first_open = scratch.as<int>();
-        int *seam_open = first_open + nch;
-        int *slow_seams = seam_open + (size_t)(segments - 1) * nch;        // [0] seams that stayed open, [1] how many make "many"
-        VGA_HIP_TRY(hipMemsetAsync(first_open, 0x7f, (size_t)nch * sizeof(int), stream));
-        VGA_HIP_TRY(hipMemsetAsync(seam_open, 0, flag_bytes + 16, stream));
-        // "many": one seam in 64, and at least 8 (the synthetic set's handful of slow channels stays with the tail kernel, whose
-        // runs meet again after a while; a batch of tones has every seam open)
-        const int many = std::max<int64_t>(8, (int64_t)nch * (segments - 1) / 64) > 0x7fffffff ? 0x7fffffff
-                       : (int)std::max<int64_t>(8, (int64_t)nch * (segments - 1) / 64);
-        // (a fill, not a copy from this stack frame: a pageable host-to-device copy makes the call wait for the stream)
-        VGA_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(slow_seams + 1), many, 1, stream));
+        DecodeSeams ds;
+        if (const int rc = ds.init(nch, segments, stream)) return rc;
         hipLaunchKernelGGL(gc_decode_fixup_kernel, dim3((nch + 63) / 64, segments - 1), dim3(64), 0, stream, d_adpcm, adpcm_pitch,
-                           d_coefs, nch, sample_count, seg_frames, d_pcm, pcm_pitch, first_open, seam_open, force_open_seams(), rg, slow_seams);
+                           d_coefs, nch, sample_count, seg_frames, d_pcm, pcm_pitch, ds.first_open, ds.seam_open, force_open_seams(), rg,
+                           ds.slow_seams);
         VGA_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(gc_decode_tail_kernel, dim3((nch + 63) / 64), dim3(64), 0, stream, d_adpcm, adpcm_pitch, d_coefs, nch,
-                           sample_count, seg_frames, segments, d_pcm, pcm_pitch, first_open, seam_open, force_open_seams(), rg, slow_seams);
+                           sample_count, seg_frames, segments, d_pcm, pcm_pitch, ds.first_open, ds.seam_open, force_open_seams(), rg,
+                           ds.slow_seams);
         VGA_HIP_TRY(hipGetLastError());
-        VGA_HIP_TRY(direct(1, first_open, slow_seams));
+        VGA_HIP_TRY(direct(1, ds.first_open, ds.slow_seams));
     }
     return VGA_OK;
 }

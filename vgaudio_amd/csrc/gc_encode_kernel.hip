@@ -22,6 +22,7 @@
 #include "common.hpp"
 #include "gc_encode_core.hpp"
 #include "gcadpcm_kernels.hpp"
+#include "seams.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -274,7 +275,7 @@ __device__ __forceinline__ void gc_encode_piece(
     int64_t first_frame = seg.first(by);
     int repair_piece = 0;
     if (repair) {
-        int k = 0x7f000000;
+        int k = SEAM_OPEN_LIMIT;
         for (int g = 0; g < CS; g++) {
             const int slot = bx * CS + g;
             if (slot < nch) {
@@ -282,7 +283,7 @@ __device__ __forceinline__ void gc_encode_piece(
                 k = first_open[c] < k ? first_open[c] : k;
             }
         }
-        if (k <= 0 || k >= 0x7f000000) return;
+        if (!is_open(k)) return;
         repair_piece = k;
         first_frame = seg.first(k);
     }
@@ -1201,7 +1202,7 @@ __global__ __launch_bounds__(64) void gc_encode_chain_kernel(
     const int slot = live ? slot_raw : nch - 1;
     const int ch = rg.order ? rg.order[slot] : slot;
     if (rg.order) total_samples = rg.length[ch];        // ragged: per lane from here on
-    const int mine = live ? first_open[ch] : 0x7f7f7f7f;
+    const int mine = live ? first_open[ch] : SEAM_NONE;
     int kmin = mine;
 #pragma unroll
     for (int o = LPC; o < 64; o <<= 1) kmin = imin(kmin, __shfl_xor(kmin, o));
@@ -1255,7 +1256,7 @@ __global__ __launch_bounds__(64) void gc_encode_chain_kernel(
         encode_tail_frame<LPC>(src, dst, c0, c1, coef_ok, pr, total_samples, v0, v1, live && have && total_samples % 14 != 0);
     (void)last_k;
     if (live && lead && frames_run) atomicAdd(&g_vga_gc_stats[2], (unsigned long long)frames_run);
-    if (live && lead) first_open[ch] = 0x7f7f7f7f;
+    if (live && lead) first_open[ch] = SEAM_NONE;
 }
 
 // A piece must be longer than the slowest seam of the batch takes to close, or that channel's seams all stay open and the
@@ -1417,7 +1418,7 @@ static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch
         queue = reinterpret_cast<int *>(base + 3 * state_bytes + open_bytes);
         if (segments > 1) {
             seg_state = reinterpret_cast<int16_t *>(base);
-            VGA_HIP_TRY(hipMemsetAsync(first_open, 0x7f, (size_t)nch * sizeof(int), stream));
+            VGA_HIP_TRY(fill_no_open_seams(first_open, nch, stream));
         } else
             seg_state = nullptr;
         seam_count = queue + 4;
