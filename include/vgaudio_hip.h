@@ -286,6 +286,37 @@ int vga_dsp_write_device(const uint8_t *d_adpcm, int64_t adpcm_pitch, int adpcm_
                          const int16_t *d_gain, const int16_t *d_start_context, const int16_t *d_loop_context,
                          int nch, const vga_dsp_params *p, uint8_t *d_file, void *stream);
 
+/* DSP reader: VGAudio/Containers/Dsp/DspReader.cs:15-115, DspStructure.cs:10-74.
+ * Read path: vga_dsp_parse (host) -> vga_dsp_read_device -> vga_gcadpcm_decode_device (coefs from the info). */
+#define VGA_DSP_MAX_CHANNELS 255       /* the header allows 32767; more than 255 channels -> VGA_ERR_INVALID_OP */
+typedef struct {
+    int sample_count, nibble_count, sample_rate;       /* DspReader.cs:59-61 */
+    int looping, format;                               /* Looping = (ReadInt16() == 1); Format must be 0 */
+    int start_addr, end_addr, cur_addr;                /* nibble addresses */
+    int channel_count;                                 /* 0 in the header reads as 1 (:71) */
+    int frames_per_interleave;
+    int loop_start, loop_end;                          /* NibbleToSample(start_addr / end_addr) (DspStructure.cs:68-72) */
+    int16_t coefs[VGA_DSP_MAX_CHANNELS][16];
+    int16_t gain[VGA_DSP_MAX_CHANNELS];
+    int16_t start_context[VGA_DSP_MAX_CHANNELS][3];    /* pred/scale, hist1, hist2 as stored */
+    int16_t loop_context[VGA_DSP_MAX_CHANNELS][3];     /* as stored: the reader does not recalculate it */
+    int audio_offset;                                  /* 0x60 * channel_count */
+    int adpcm_bytes;                                   /* one channel: SampleCountToByteCount(sample_count) */
+    int interleave_size;                               /* frames_per_interleave * 8 (several channels) */
+    int data_length;                                   /* bytes read: adpcm_bytes (mono), GetNextMultiple(adpcm_bytes, 8) * nch */
+} vga_dsp_info;
+/* host only; never reads past `size`.  VGA_ERR_INVALID_DATA for what DspReader throws: a file shorter than 0x60 +
+ * adpcm_bytes (the reference's check, :87-90), sample and nibble counts that disagree, format != 0, a header or audio
+ * that runs past the end (EndOfStreamException, DeInterleave's ArgumentOutOfRangeException), frames per interleave <= 0
+ * with several channels, negative counts; VGA_ERR_INVALID_OP for more than VGA_DSP_MAX_CHANNELS channels. */
+int vga_dsp_parse(const uint8_t *file, size_t size, vga_dsp_info *out);
+/* nfiles images that share one parsed geometry at d_files + f*file_pitch -> row f*channel_count+c of d_adpcm
+ * (info->adpcm_bytes per row, adpcm_pitch >= that), the layout vga_gcadpcm_decode_device takes.  One launch. */
+int vga_dsp_read_device(const vga_dsp_info *info, const uint8_t *d_files, int64_t file_pitch, int nfiles, uint8_t *d_adpcm,
+                        int64_t adpcm_pitch, void *stream);
+/* host form: adpcm_out[c] info->adpcm_bytes bytes */
+int vga_dsp_read(const uint8_t *file, size_t size, const vga_dsp_info *info, uint8_t *const *adpcm_out);
+
 /* ----------------------------------------------------------------------
  * NintendoWare streams for GC-ADPCM: BRSTM (VGAudio/Containers/NintendoWare/BrstmWriter.cs, BrstmReader.cs),
  * BCSTM and BFSTM (BCFstmWriter.cs, BCFstmReader.cs), configured as BxstmConfiguration.cs.
@@ -492,6 +523,37 @@ int vga_adx_write(const uint8_t *const *audio, int audio_len, const int16_t *his
 int vga_adx_write_device(const uint8_t *d_audio, int64_t audio_pitch, int audio_len, const int16_t *d_history, int nch,
                          const vga_adx_file_params *p, uint8_t *d_file, void *stream);
 
+/* ADX reader: VGAudio/Containers/Adx/AdxReader.cs:14-131, AdxStructure.cs:7-32.
+ * Read path: vga_adx_parse (host) -> vga_adx_read_device -> [revision != 0: vga_adx_find_key_device over the caller's
+ * candidates, or the caller's key -> vga_adx_crypt_device with encryption_type = revision; no key found: the audio stays
+ * as it is, as in the reference] -> vga_adx_decode_device with sample_count - inserted_samples samples, padding =
+ * inserted_samples, history = history[c][0] (CriAdxChannel(audio, HistorySamples[c][0], Version), ToAudioStream :38-57). */
+typedef struct {
+    int header_size;                   /* signed 16-bit; the audio starts at header_size + 4 */
+    int type, frame_size, bit_depth, channel_count, sample_rate;
+    int sample_count;                  /* includes inserted_samples */
+    int highpass_frequency, version;
+    int revision;                      /* the encryption type: 8 or 9 when encrypted */
+    int inserted_samples, loop_count, looping, loop_type;
+    int loop_start_sample, loop_start_byte, loop_end_sample, loop_end_byte;   /* read only when loop_count > 0 */
+    int16_t history[255][2];           /* HistorySamples (version >= 4; zeros otherwise) */
+    int audio_offset;                  /* header_size + 4 */
+    int samples_per_frame;             /* NibbleCountToSampleCount(frame_size * 2, frame_size) */
+    int frame_count;                   /* DivideByRoundUp(sample_count, samples_per_frame) */
+    int audio_bytes;                   /* one channel: frame_count * frame_size */
+} vga_adx_file_info;
+/* host only; never reads past `size`.  VGA_ERR_INVALID_DATA: no 0x8000 signature, a header or audio that runs past the
+ * end, an audio offset below 0, a frame size whose frames hold no samples, no channels, a negative sample count. */
+int vga_adx_parse(const uint8_t *file, size_t size, vga_adx_file_info *out);
+/* nfiles images that share one parsed geometry -> row f*channel_count+c of d_audio (info->audio_bytes per row, the
+ * frames of one channel back to back: DeInterleave(audioSize, FrameSize, ChannelCount)).  18-byte frames with d_audio
+ * and audio_pitch multiples of 16 and at most 113 channels take a kernel that moves 16-byte vectors both ways; every
+ * other shape takes a general de-interleave.  One launch. */
+int vga_adx_read_device(const vga_adx_file_info *info, const uint8_t *d_files, int64_t file_pitch, int nfiles, uint8_t *d_audio,
+                        int64_t audio_pitch, void *stream);
+/* host form: audio_out[c] info->audio_bytes bytes, still encrypted if the file is */
+int vga_adx_read(const uint8_t *file, size_t size, const vga_adx_file_info *info, uint8_t *const *audio_out);
+
 /* ======================================================================
  * CRI HCA
  * ====================================================================== */
@@ -602,6 +664,40 @@ int vga_hca_write(const vga_hca_info *info, const uint8_t *frames, const char *c
 int vga_hca_write_device(const vga_hca_info *info, const uint8_t *d_frames, int64_t frames_pitch, int nstreams,
                          const char *comment, float volume, int encryption_type, int encrypted_ids, uint8_t *d_files,
                          int64_t file_pitch, void *stream);
+
+/* HCA reader: VGAudio/Containers/Hca/HcaReader.cs:20-253, Codecs/CriHca/HcaInfo.cs:5-57.
+ * Read path: vga_hca_parse (host) -> vga_hca_read_device -> [encryption_type 1: vga_hca_key_tables(1); 56: the caller's
+ * key, or vga_hca_find_key_device over the caller's candidates (none matches: "Cannot find key to decrypt HCA file.",
+ * InvalidDataException) -> vga_hca_crypt_device; then encryption_type = 0] -> vga_hca_decode_device with info.hca. */
+typedef struct {
+    vga_hca_info hca;                  /* after the reader's fix-ups: UseAthCurve below version 0x200 without an ath chunk,
+                                        * TrackCount >= 1, CalculateHfrValues, SampleCount clamped to LoopEndSample */
+    int version;                       /* signed 16-bit */
+    int encryption_type;               /* ciph chunk (0 without one) */
+    float volume;                      /* rva chunk (1 without one) */
+    int vbr_max_frame_size, vbr_noise_level;   /* vbr chunk */
+    int dec_stereo_type;               /* dec chunk */
+    int reserved1, reserved2;          /* comp chunk */
+    int has_ath_chunk, has_comment;
+    char comment[256];                 /* comm chunk: the bytes up to the terminator (at most 255), NUL-terminated;
+                                        * hca.comment_length counts its bytes */
+    int frames_offset;                 /* HeaderSize: the frames follow back to back */
+} vga_hca_file_info;
+/* host only; never reads past `size`.  Chunk ids are read with their top bits cleared.  VGA_ERR_INVALID_DATA: no HCA
+ * signature, a header or frames that run past the end, a negative header size or frame count, frames shorter than
+ * their CRC; VGA_ERR_INVALID_OP, naming the chunk, for an unknown chunk (NotSupportedException), and for what the
+ * decoder here cannot take: more than 8 (or no) channels, frames outside 8..65535 bytes, more than 128 bands, more than
+ * 8 HFR groups, or a comment longer than 255 bytes. */
+int vga_hca_parse(const uint8_t *file, size_t size, vga_hca_file_info *out);
+/* nfiles images that share one parsed geometry -> stream f's frames at d_frames + f*frames_pitch, back to back, the
+ * layout vga_hca_decode_device takes: frames_pitch a multiple of 4 and at least frame_count*frame_size + 8 (the 8 bytes
+ * after the frames are zeroed).  d_bad_crc (nfiles ints, or NULL) receives the number of frames of each file whose
+ * CRC-16 does not match; such frames are kept, as in the reference.  Every frame size up to 65535 bytes is checked.
+ * One launch (plus a clear of d_bad_crc). */
+int vga_hca_read_device(const vga_hca_file_info *info, const uint8_t *d_files, int64_t file_pitch, int nfiles,
+                        uint8_t *d_frames, int64_t frames_pitch, int *d_bad_crc, void *stream);
+/* host form: frames_out frame_count*frame_size bytes; *bad_crc_out (or NULL) the count of bad frames */
+int vga_hca_read(const uint8_t *file, size_t size, const vga_hca_file_info *info, uint8_t *frames_out, int *bad_crc_out);
 
 /* ----------------------------------------------------------------------
  * WAVE, 16-bit PCM: the step before the codec path.

@@ -121,6 +121,11 @@ int vga_testing_hca_frames_per_group_this_thread(int frames);
  * needs no GPU: the CPU suite feeds it to the lane emulator of the HCA decoder (tests/host/hca_decode_emulator.cpp). */
 int vga_testing_hca_device_info(const void *hca_info, void *out, int out_bytes);
 
+/* The ADX file reader (vga_adx_read_device) moves 18-byte frames with a kernel of 16-byte vectors when the rows are 16-byte
+ * aligned.  on != 0 sends calls made from the calling thread to the general de-interleave instead; the bytes must not
+ * change.  Returns the previous setting. */
+int vga_testing_adx_read_general_this_thread(int on);
+
 #ifdef __cplusplus
 }
 #endif

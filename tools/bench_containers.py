@@ -147,6 +147,84 @@ def main():
     assert torch.equal(back[:, :nb], adpcm[:, :nb])
     rec("nwstm_read", ms, 2 * nf * nch * info.adpcm_bytes, channels=nf * nch, files=nf, note="BFSTM DATA -> pitched channels")
     del adpcm, seek, files, back
+
+    # the file readers: one image built on the host, replicated over the batch (the kernels do not look at the bytes)
+    def tile(img, count):
+        fp = (len(img) + 255) // 256 * 256
+        t = torch.zeros((count, fp), dtype=torch.uint8, device=dev)
+        t[:, :len(img)] = torch.from_numpy(img).to(dev)
+        return t, fp
+
+    rng = np.random.default_rng(1)
+    # DSP: 2048 stereo files of 60 s
+    nf, nch = 2048, 2
+    dp = _lib.DspParamsC(48000, n, 0, 0, 0, 0x3800, 1, 1)
+    dl = _lib.DspLayoutC()
+    _lib.check(L.vga_dsp_layout_for(C.byref(dp), nch, C.byref(dl)))
+    nb = L.vga_gcadpcm_sample_count_to_byte_count(n)
+    rows = [rng.integers(0, 256, nb, dtype=np.uint8) for _ in range(nch)]
+    img = np.zeros(dl.file_size, np.uint8)
+    co = np.zeros((nch, 16), np.int16)
+    _lib.check(L.vga_dsp_write((_lib.u8p * nch)(*[r.ctypes.data_as(_lib.u8p) for r in rows]), nb, co.ctypes.data_as(_lib.i16p), None,
+                               None, None, nch, C.byref(dp), img.ctypes.data_as(_lib.u8p)))
+    di = _lib.DspInfoC()
+    _lib.check(L.vga_dsp_parse(img.ctypes.data_as(_lib.u8p), len(img), C.byref(di)))
+    files, fp = tile(img, nf)
+    pitch = (nb + 15) // 16 * 16
+    back = torch.empty((nf * nch, pitch), dtype=torch.uint8, device=dev)
+    ms = timed(lambda: _lib.check(L.vga_dsp_read_device(C.byref(di), files.data_ptr(), fp, nf, back.data_ptr(), pitch, st())))
+    assert all(torch.equal(back[c::nch, :nb], torch.from_numpy(rows[c]).to(dev).expand(nf, nb)) for c in range(nch))
+    rec("dsp_read", ms, 2 * nf * nch * nb, channels=nf * nch, files=nf, note="DSP audio -> pitched channels (interleave 8 KiB)")
+    del files, back
+
+    # ADX: 2048 stereo files of 60 s, 18-byte frames; the 16-byte-vector kernel and the general de-interleave
+    ap = _lib.AdxFileParamsC(48000, n, 0, 0, 0, 0, 18, 4, 3, 500, 0, 1)
+    al = _lib.AdxFileLayoutC()
+    _lib.check(L.vga_adx_file_layout_for(C.byref(ap), nch, C.byref(al)))
+    ab = al.frame_count * 18
+    rows = [rng.integers(0, 256, ab, dtype=np.uint8) for _ in range(nch)]
+    img = np.zeros(al.file_size, np.uint8)
+    hist = np.zeros(nch, np.int16)
+    _lib.check(L.vga_adx_write((_lib.u8p * nch)(*[r.ctypes.data_as(_lib.u8p) for r in rows]), ab, hist.ctypes.data_as(_lib.i16p), nch,
+                               C.byref(ap), img.ctypes.data_as(_lib.u8p)))
+    ai = _lib.AdxFileInfoC()
+    _lib.check(L.vga_adx_parse(img.ctypes.data_as(_lib.u8p), len(img), C.byref(ai)))
+    files, fp = tile(img, nf)
+    pitch = (ab + 15) // 16 * 16
+    back = torch.empty((nf * nch, pitch), dtype=torch.uint8, device=dev)
+    read = lambda: _lib.check(L.vga_adx_read_device(C.byref(ai), files.data_ptr(), fp, nf, back.data_ptr(), pitch, st()))
+    ms = timed(read)
+    assert all(torch.equal(back[c::nch, :ab], torch.from_numpy(rows[c]).to(dev).expand(nf, ab)) for c in range(nch))
+    L.vga_testing_adx_read_general_this_thread(1)
+    ms_general = timed(read)
+    L.vga_testing_adx_read_general_this_thread(0)
+    assert all(torch.equal(back[c::nch, :ab], torch.from_numpy(rows[c]).to(dev).expand(nf, ab)) for c in range(nch))
+    rec("adx_read", ms, 2 * nf * nch * ab, channels=nf * nch, files=nf, general_path_ms=round(ms_general, 3),
+        general_path_GB_per_s=round(2 * nf * nch * ab / ms_general / 1e6, 1),
+        note="18-byte frames: 16-byte vectors through LDS; general_path = the 2-byte-granule de-interleave")
+    del files, back
+
+    # HCA: 1024 stereo streams of 60 s, quality High, every frame's CRC-16 checked
+    ns = 1024
+    info = _lib.HcaInfoC()
+    hp = _lib.HcaParamsC(2, 0, 0, 2, 48000, n, 0, 0, 0)
+    _lib.check(L.vga_hca_encoder_initialize(C.byref(hp), C.byref(info)))
+    fb = info.frame_count * info.frame_size
+    fr = rng.integers(0, 256, fb, dtype=np.uint8)
+    img = np.zeros(L.vga_hca_file_size(C.byref(info)), np.uint8)
+    _lib.check(L.vga_hca_write(C.byref(info), fr.ctypes.data_as(_lib.u8p), None, 1.0, 0, 0, img.ctypes.data_as(_lib.u8p)))
+    hi = _lib.HcaFileInfoC()
+    _lib.check(L.vga_hca_parse(img.ctypes.data_as(_lib.u8p), len(img), C.byref(hi)))
+    files, fp = tile(img, ns)
+    pitch = (fb + 8 + 15) // 16 * 16
+    back = torch.empty((ns, pitch), dtype=torch.uint8, device=dev)
+    bad = torch.empty(ns, dtype=torch.int32, device=dev)
+    ms = timed(lambda: _lib.check(L.vga_hca_read_device(C.byref(hi), files.data_ptr(), fp, ns, back.data_ptr(), pitch, bad.data_ptr(),
+                                                        st())))
+    assert torch.equal(back[:, :fb], torch.from_numpy(fr).to(dev).expand(ns, fb))
+    rec("hca_read", ms, 2 * ns * fb, streams=ns, frames_per_stream=info.frame_count, frame_size=info.frame_size,
+        note="frames copied to the decoder's layout, CRC-16 of every frame checked (random frames: all counted bad)")
+    del files, back
     print(json.dumps(out))
 
 

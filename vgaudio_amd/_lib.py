@@ -202,6 +202,16 @@ SIGNATURES = {
     "vga_nwstm_parse": (ci, [u8p, C.c_size_t, vp]),
     "vga_nwstm_read_device": (ci, [vp, vp, i64, ci, vp, i64, vp]),
     "vga_nwstm_read": (ci, [u8p, C.c_size_t, vp, u8pp, i16pp]),
+    "vga_dsp_parse": (ci, [u8p, C.c_size_t, vp]),
+    "vga_dsp_read_device": (ci, [vp, vp, i64, ci, vp, i64, vp]),
+    "vga_dsp_read": (ci, [u8p, C.c_size_t, vp, u8pp]),
+    "vga_adx_parse": (ci, [u8p, C.c_size_t, vp]),
+    "vga_adx_read_device": (ci, [vp, vp, i64, ci, vp, i64, vp]),
+    "vga_adx_read": (ci, [u8p, C.c_size_t, vp, u8pp]),
+    "vga_hca_parse": (ci, [u8p, C.c_size_t, vp]),
+    "vga_hca_read_device": (ci, [vp, vp, i64, ci, vp, i64, vp, vp]),
+    "vga_hca_read": (ci, [u8p, C.c_size_t, vp, u8p, C.POINTER(ci)]),
+    "vga_testing_adx_read_general_this_thread": (ci, [ci]),
     "vga_gcadpcm_channel_layout_for": (ci, [vp, vp]),
     "vga_gcadpcm_build_channels_batch": (ci, [u8pp, i16p, ci, vp, u8pp, i16pp, i16pp, i16p]),
     "vga_gcadpcm_build_channels_workspace_bytes": (C.c_size_t, [ci, vp]),
@@ -342,6 +352,37 @@ class HcaInfoC(C.Structure):
         "total_band_count", "base_band_count", "stereo_band_count", "hfr_band_count", "bands_per_hfr_group",
         "hfr_group_count", "looping", "loop_start_frame", "loop_end_frame", "pre_loop_samples", "post_loop_samples",
         "use_ath_curve", "comment_length")]
+
+
+DSP_MAX_CHANNELS = 255
+
+
+class DspInfoC(C.Structure):
+    """vga_dsp_info"""
+    _fields_ = ([(n, C.c_int) for n in ("sample_count", "nibble_count", "sample_rate", "looping", "format", "start_addr",
+                                        "end_addr", "cur_addr", "channel_count", "frames_per_interleave", "loop_start",
+                                        "loop_end")]
+                + [("coefs", (C.c_int16 * 16) * DSP_MAX_CHANNELS), ("gain", C.c_int16 * DSP_MAX_CHANNELS),
+                   ("start_context", (C.c_int16 * 3) * DSP_MAX_CHANNELS), ("loop_context", (C.c_int16 * 3) * DSP_MAX_CHANNELS)]
+                + [(n, C.c_int) for n in ("audio_offset", "adpcm_bytes", "interleave_size", "data_length")])
+
+
+class AdxFileInfoC(C.Structure):
+    """vga_adx_file_info"""
+    _fields_ = ([(n, C.c_int) for n in ("header_size", "type", "frame_size", "bit_depth", "channel_count", "sample_rate",
+                                        "sample_count", "highpass_frequency", "version", "revision", "inserted_samples",
+                                        "loop_count", "looping", "loop_type", "loop_start_sample", "loop_start_byte",
+                                        "loop_end_sample", "loop_end_byte")]
+                + [("history", (C.c_int16 * 2) * 255)]
+                + [(n, C.c_int) for n in ("audio_offset", "samples_per_frame", "frame_count", "audio_bytes")])
+
+
+class HcaFileInfoC(C.Structure):
+    """vga_hca_file_info"""
+    _fields_ = ([("hca", HcaInfoC), ("version", C.c_int), ("encryption_type", C.c_int), ("volume", C.c_float)]
+                + [(n, C.c_int) for n in ("vbr_max_frame_size", "vbr_noise_level", "dec_stereo_type", "reserved1", "reserved2",
+                                          "has_ath_chunk", "has_comment")]
+                + [("comment", C.c_char * 256), ("frames_offset", C.c_int)])
 
 
 class HcaParamsC(C.Structure):

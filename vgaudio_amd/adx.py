@@ -1,12 +1,13 @@
-"""ADX container writer -- host-side mirror of VGAudio/Containers/Adx/AdxWriter.cs and
-AdxConfiguration.cs.  The image is assembled on the GPU (vga_adx_write), encryption included (vga_adx_crypt); there is no CPU path."""
+"""ADX container -- host-side mirror of VGAudio/Containers/Adx/AdxWriter.cs, AdxReader.cs and
+AdxConfiguration.cs.  The image is assembled and taken apart on the GPU (vga_adx_write, vga_adx_read), encryption
+included (vga_adx_crypt, vga_adx_find_key_device); only the header is parsed on the host.  There is no CPU path."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 from ._lib import check, u8p
-from .criadx import CriAdxEncryption, CriAdxFormat, CriAdxParameters, CriAdxType
+from .criadx import CriAdxChannel, CriAdxEncryption, CriAdxFormat, CriAdxParameters, CriAdxType
 from .gcadpcm import Pcm16Format, _i16, _ptr_array
 
 
@@ -64,3 +65,49 @@ class AdxWriter:
         check(_lib.lib().vga_adx_write(_ptr_array(u8p, src), len(src[0]), _i16(hist), fmt.ChannelCount, C.byref(p),
                                        out.ctypes.data_as(u8p)))
         return out.tobytes()
+
+
+def parse(data):
+    """vga_adx_parse: AdxReader.ReadHeader plus the checks ReadData makes (no device work)."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    info = _lib.AdxFileInfoC()
+    check(_lib.lib().vga_adx_parse(buf.ctypes.data_as(u8p), len(buf), C.byref(info)))
+    return info
+
+
+class AdxReader:
+    """AudioReader<AdxReader, AdxStructure, AdxConfiguration> (Containers/Adx/AdxReader.cs).  EncryptionKey: a CriAdxKey
+    or None; Keys: the candidates FindKey tries when the file is encrypted and no key is given (the reference's list,
+    CriAdxEncryptionKeys.cs, stays with the caller).  No key found: the audio stays encrypted, as in the reference."""
+
+    def __init__(self, EncryptionKey=None, Keys=None):
+        self.EncryptionKey = EncryptionKey
+        self.Keys = list(Keys) if Keys else []
+
+    def ReadMetadata(self, data):
+        return parse(data)
+
+    def ReadFormat(self, data):
+        return self.ReadWithConfig(data)[0]
+
+    def ReadWithConfig(self, data):
+        data = bytes(data)
+        info = parse(data)
+        buf = np.frombuffer(data, dtype=np.uint8)
+        audio = [np.zeros(info.audio_bytes, dtype=np.uint8) for _ in range(info.channel_count)]
+        check(_lib.lib().vga_adx_read(buf.ctypes.data_as(u8p), len(buf), C.byref(info), _ptr_array(u8p, audio)))
+        key = self.EncryptionKey                                 # ReadFile (:31): EncryptionKey ?? FindKey(structure)
+        if key is None and info.revision != 0:
+            key = CriAdxEncryption.FindKey(audio, info.revision, info.frame_size, self.Keys)
+        if key is not None:                                      # ToAudioStream (:40-43)
+            CriAdxEncryption.EncryptDecrypt(audio, key, info.revision, info.frame_size)
+        cfg = AdxConfiguration(FrameSize=info.frame_size, Type=info.type, EncryptionType=info.revision, EncryptionKey=key)
+        return self._to_format(info, audio), cfg                 # GetConfiguration (:59-69)
+
+    @staticmethod
+    def _to_format(info, audio):
+        """ToAudioStream (:45-56)."""
+        ins = info.inserted_samples
+        chans = [CriAdxChannel(audio[c], int(info.history[c][0]), info.version) for c in range(info.channel_count)]
+        return CriAdxFormat(chans, info.sample_count - ins, info.sample_rate, info.frame_size, info.highpass_frequency, ins,
+                            info.type, info.version, bool(info.looping), info.loop_start_sample - ins, info.loop_end_sample - ins)

@@ -6,6 +6,7 @@
 #include <memory>
 #include "host_batch.hpp"
 #include "hca_kernels.hpp"
+#include "hca_frame_crc.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -140,7 +141,7 @@ int make_device_info(const vga_hca_info &h, hca::DeviceInfo &d)
     return VGA_OK;
 }
 
-// x^(8k) mod (x^16 + x^15 + x^2 + 1), k = 0..4095, uploaded once per device
+// x^(8k) mod (x^16 + x^15 + x^2 + 1), k = 0..65535 (hca_crc::kPowEntries: any frame a file can declare), uploaded once per device
 struct CrcPow {
     std::mutex mu;
     uint16_t *dev[64] = {};
@@ -169,9 +170,9 @@ int vga::hca::crc_pow_table(const uint16_t **out)
     if (device < 0 || device >= 64) { set_error("device index out of range"); return VGA_ERR_DEVICE; }
     std::lock_guard<std::mutex> lock(g_crc_pow.mu);
     if (!g_crc_pow.dev[device]) {
-        static uint16_t host[4096];
+        static uint16_t host[hca_crc::kPowEntries];
         unsigned v = 1;                      // x^0
-        for (int k = 0; k < 4096; k++) {
+        for (int k = 0; k < hca_crc::kPowEntries; k++) {
             host[k] = (uint16_t)v;
             for (int j = 0; j < 8; j++) v = ((v << 1) ^ ((v & 0x8000u) ? 0x8005u : 0u)) & 0xFFFFu;
         }

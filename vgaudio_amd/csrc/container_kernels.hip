@@ -8,13 +8,6 @@
 namespace vga {
 namespace container {
 
-template <int G> struct Granule;
-template <> struct Granule<1> { using type = uint8_t; };
-template <> struct Granule<2> { using type = uint16_t; };
-template <> struct Granule<4> { using type = uint32_t; };
-template <> struct Granule<8> { using type = uint2; };
-template <> struct Granule<16> { using type = uint4; };
-
 // One thread per G-byte granule of the OUTPUT (coalesced stores; loads are contiguous inside one interleave block).
 // G divides every segment size, so a granule never straddles two rows; a short input leaves zero gaps.
 template <int G>

@@ -2,6 +2,9 @@
 #pragma once
 #include "common.hpp"
 
+#include <algorithm>
+#include <type_traits>
+
 namespace vga {
 namespace container {
 
@@ -27,6 +30,82 @@ int launch_replicate(const uint8_t *d_header, int header_size, uint8_t *d_files,
 // pcm + c * pitch (in samples).
 int launch_pcm16_deinterleave(const uint8_t *interleaved, int sample_count, int nch, int16_t *pcm, int64_t pitch, hipStream_t stream);
 int launch_pcm16_interleave(const int16_t *pcm, int64_t pitch, int sample_count, int nch, uint8_t *interleaved, hipStream_t stream);
+
+
+// ---------------------------------------------------------------- shared by the container readers
+// (nwstm.hip: BRSTM / BCSTM / BFSTM; container_readers.hip: DSP and the general ADX path)
+
+template <int G> struct Granule;
+template <> struct Granule<1> { using type = uint8_t; };
+template <> struct Granule<2> { using type = uint16_t; };
+template <> struct Granule<4> { using type = uint32_t; };
+template <> struct Granule<8> { using type = uint2; };
+template <> struct Granule<16> { using type = uint4; };
+
+constexpr int kMaxGridY = 65535;                 // rows of one de-interleave launch (grid y)
+
+// DeInterleave(stream, length, InterleaveSize, ChannelCount, outputSize) (Utilities/Interleave.cs:118-167): the gather
+// back to one row per channel.  blockIdx.y = file * nch + channel, one thread per G-byte granule of the output row
+// (coalesced stores), reading the channel's contiguous run of its interleave block (coalesced loads).  Bytes of the
+// row that no block supplies stay zero, as in the reference's fresh byte[outputSize].
+template <int G>
+__global__ __launch_bounds__(256) void deinterleave_kernel(const uint8_t *__restrict__ files, int64_t file_pitch,
+                                                           int audio_offset, int nch, uint32_t input_size,
+                                                           uint32_t interleave, uint32_t output_size,
+                                                           uint8_t *__restrict__ dst, int64_t dst_pitch, int row0)
+{
+    using T = typename Granule<G>::type;
+    const uint32_t off = ((uint32_t)blockIdx.x * 256 + threadIdx.x) * G;
+    if (off >= output_size) return;
+    const int row = row0 + blockIdx.y, f = row / nch, o = row - f * nch;
+    const uint32_t in_blocks = (input_size + interleave - 1) / interleave, out_blocks = (output_size + interleave - 1) / interleave;
+    const uint32_t to_copy = in_blocks < out_blocks ? in_blocks : out_blocks;
+    const uint32_t b = off / interleave, within = off - b * interleave;
+    uint32_t n = 0, cur_in = interleave;
+    if (b < to_copy) {
+        cur_in = b == in_blocks - 1 ? input_size - (in_blocks - 1) * interleave : interleave;
+        const uint32_t cur_out = b == out_blocks - 1 ? output_size - (out_blocks - 1) * interleave : interleave;
+        n = cur_in < cur_out ? cur_in : cur_out;
+    }
+    const uint8_t *s = files + (int64_t)f * file_pitch + audio_offset + (uint64_t)interleave * b * nch + (uint64_t)cur_in * o + within;
+    uint8_t *d = dst + (int64_t)row * dst_pitch + off;
+    if (within + G <= n && off + G <= output_size) {
+        *reinterpret_cast<T *>(d) = *reinterpret_cast<const T *>(s);
+        return;
+    }
+    for (int k = 0; k < G && off + k < output_size; k++) d[k] = within + k < n ? s[k] : 0;
+}
+
+template <class F>
+int pick_granule(uint64_t align, F &&go)
+{
+    if (!(align & 15)) go(std::integral_constant<int, 16>{});
+    else if (!(align & 7)) go(std::integral_constant<int, 8>{});
+    else if (!(align & 3)) go(std::integral_constant<int, 4>{});
+    else if (!(align & 1)) go(std::integral_constant<int, 2>{});
+    else go(std::integral_constant<int, 1>{});
+    VGA_HIP_TRY(hipGetLastError());
+    return VGA_OK;
+}
+
+// DeInterleave for `rows` rows (file = row / nch, channel = row % nch) of equally shaped images at files + f * file_pitch,
+// each channel's audio `input_size` bytes in blocks of `interleave` bytes from audio_offset on, into rows of output_size
+// bytes; `align` ORs every address and size the granule must divide.  One launch per 65535 rows.
+inline int launch_deinterleave(uint64_t align, const uint8_t *files, int64_t file_pitch, int audio_offset, int nch, int rows,
+                               uint32_t input_size, uint32_t interleave, uint32_t output_size, uint8_t *dst, int64_t dst_pitch,
+                               hipStream_t s)
+{
+    for (int r0 = 0; r0 < rows; r0 += kMaxGridY) {
+        const int nr = std::min(rows - r0, kMaxGridY);
+        if (int rc = pick_granule(align, [&](auto g) {
+                constexpr int G = decltype(g)::value;
+                hipLaunchKernelGGL(deinterleave_kernel<G>, dim3((unsigned)(((output_size + G - 1) / G + 255) / 256), nr), dim3(256), 0, s,
+                                   files, file_pitch, audio_offset, nch, input_size, interleave, output_size, dst, dst_pitch, r0);
+            }))
+            return rc;
+    }
+    return VGA_OK;
+}
 
 }  // namespace container
 }  // namespace vga

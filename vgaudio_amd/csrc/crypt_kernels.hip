@@ -5,6 +5,7 @@
 // writes every byte once.
 #include "crypt_kernels.hpp"
 #include "hca_device.hpp"
+#include "hca_frame_crc.hpp"
 
 namespace vga {
 namespace crypt {
@@ -78,20 +79,8 @@ __global__ __launch_bounds__(256) void adx_test_keys_kernel(const uint8_t *__res
     if (threadIdx.x == 0) valid[blockIdx.x] = bad ? 0 : 1;
 }
 
-// multiply in GF(2)[x] / (x^16 + x^15 + x^2 + 1)
-__device__ __forceinline__ unsigned gf_mul16(unsigned a, unsigned b)
-{
-    unsigned r = 0;
-#pragma unroll
-    for (int i = 15; i >= 0; i--) {
-        r = ((r << 1) ^ ((r & 0x8000u) ? 0x8005u : 0u)) & 0xFFFFu;
-        if ((a >> i) & 1u) r ^= b;
-    }
-    return r;
-}
-
 // CryptFrame (:20-33): one wave per frame.  Each lane substitutes a contiguous chunk and CRCs it; the chunk CRCs
-// are shifted to their place with x^(8k) mod P (crc_pow, the encoder's table) and XOR-reduced across the wave.
+// are combined across the wave (hca_frame_crc.hpp).
 __global__ __launch_bounds__(64) void hca_crypt_kernel(uint8_t *__restrict__ frames, int64_t frames_pitch, int frame_count,
                                                        int frame_size, const uint8_t *__restrict__ table,
                                                        const uint16_t *__restrict__ crc_pow)
@@ -104,19 +93,14 @@ __global__ __launch_bounds__(64) void hca_crypt_kernel(uint8_t *__restrict__ fra
     const int stream = (int)(idx / frame_count), frame = (int)(idx - (int64_t)stream * frame_count);
     uint8_t *a = frames + (int64_t)stream * frames_pitch + (int64_t)frame * frame_size;
     const int nbytes = frame_size - 2;
-    const int chunk = (nbytes + 63) / 64;
-    const int begin = min(lane * chunk, nbytes), end = min(begin + chunk, nbytes);
+    const hca_crc::Chunk ch = hca_crc::lane_chunk(lane, nbytes);
     unsigned crc = 0;
-    for (int i = begin; i < end; i++) {
+    for (int i = ch.begin; i < ch.end; i++) {
         const unsigned byte = sub[a[i]];
         a[i] = (uint8_t)byte;
-        crc ^= byte << 8;
-#pragma unroll
-        for (int j = 0; j < 8; j++) crc = ((crc << 1) ^ ((crc & 0x8000u) ? 0x8005u : 0u)) & 0xFFFFu;
+        crc = hca_crc::step(crc, byte);
     }
-    unsigned part = begin < end ? gf_mul16(crc, crc_pow[nbytes - end]) : 0u;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) part ^= (unsigned)__shfl_xor((int)part, o);
+    const unsigned part = hca_crc::wave_combine(crc, ch, nbytes, crc_pow);
     if (lane == 0) {
         a[nbytes] = (uint8_t)(part >> 8);
         a[nbytes + 1] = (uint8_t)part;

@@ -3,6 +3,7 @@
 // and taken apart in HBM, nfiles equally shaped files per launch.  Everything on the device is byte movement:
 // HBM-bound, every byte of an image read or written once.
 #include "common.hpp"
+#include "container_kernels.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -250,12 +251,9 @@ __global__ __launch_bounds__(256) void nw_seek_kernel(const int16_t *__restrict_
     d[1] = (uint8_t)(big ? v : v >> 8);
 }
 
-template <int G> struct Granule;
-template <> struct Granule<1> { using type = uint8_t; };
-template <> struct Granule<2> { using type = uint16_t; };
-template <> struct Granule<4> { using type = uint32_t; };
-template <> struct Granule<8> { using type = uint2; };
-template <> struct Granule<16> { using type = uint4; };
+using container::Granule;
+using container::kMaxGridY;
+using container::pick_granule;
 
 // Interleave(channels, InterleaveSize, AudioDataSize) (Utilities/Interleave.cs:43-78) into the DATA block of every
 // image at once: blockIdx.y is the file, one thread per G-byte granule of the OUTPUT (coalesced stores; the loads are
@@ -296,51 +294,6 @@ __global__ __launch_bounds__(256) void nw_interleave_kernel(const uint8_t *__res
     *reinterpret_cast<T *>(dst + (int64_t)f * file_pitch + o) = v;
 }
 
-// DeInterleave(stream, length, InterleaveSize, ChannelCount, outputSize) (Utilities/Interleave.cs:118-167): the gather
-// back to one row per channel.  blockIdx.y = file * nch + channel, one thread per G-byte granule of the output row
-// (coalesced stores), reading the channel's contiguous run of its interleave block (coalesced loads).  Bytes of the
-// row that no block supplies stay zero, as in the reference's fresh byte[outputSize].
-template <int G>
-__global__ __launch_bounds__(256) void nw_deinterleave_kernel(const uint8_t *__restrict__ files, int64_t file_pitch,
-                                                              int audio_offset, int nch, uint32_t input_size,
-                                                              uint32_t interleave, uint32_t output_size,
-                                                              uint8_t *__restrict__ dst, int64_t dst_pitch, int row0)
-{
-    using T = typename Granule<G>::type;
-    const uint32_t off = ((uint32_t)blockIdx.x * 256 + threadIdx.x) * G;
-    if (off >= output_size) return;
-    const int row = row0 + blockIdx.y, f = row / nch, o = row - f * nch;
-    const uint32_t in_blocks = (input_size + interleave - 1) / interleave, out_blocks = (output_size + interleave - 1) / interleave;
-    const uint32_t to_copy = in_blocks < out_blocks ? in_blocks : out_blocks;
-    const uint32_t b = off / interleave, within = off - b * interleave;
-    uint32_t n = 0, cur_in = interleave;
-    if (b < to_copy) {
-        cur_in = b == in_blocks - 1 ? input_size - (in_blocks - 1) * interleave : interleave;
-        const uint32_t cur_out = b == out_blocks - 1 ? output_size - (out_blocks - 1) * interleave : interleave;
-        n = cur_in < cur_out ? cur_in : cur_out;
-    }
-    const uint8_t *s = files + (int64_t)f * file_pitch + audio_offset + (uint64_t)interleave * b * nch + (uint64_t)cur_in * o + within;
-    uint8_t *d = dst + (int64_t)row * dst_pitch + off;
-    if (within + G <= n && off + G <= output_size) {
-        *reinterpret_cast<T *>(d) = *reinterpret_cast<const T *>(s);
-        return;
-    }
-    for (int k = 0; k < G && off + k < output_size; k++) d[k] = within + k < n ? s[k] : 0;
-}
-
-template <class F>
-int pick_granule(uint64_t align, F &&go)
-{
-    if (!(align & 15)) go(std::integral_constant<int, 16>{});
-    else if (!(align & 7)) go(std::integral_constant<int, 8>{});
-    else if (!(align & 3)) go(std::integral_constant<int, 4>{});
-    else if (!(align & 1)) go(std::integral_constant<int, 2>{});
-    else go(std::integral_constant<int, 1>{});
-    VGA_HIP_TRY(hipGetLastError());
-    return VGA_OK;
-}
-
-constexpr int kMaxGridY = 65535;
 
 }  // namespace nwstm
 }  // namespace vga
@@ -918,18 +871,8 @@ int vga_nwstm_read_device(const vga_nwstm_info *I, const uint8_t *d_files, int64
     const uint32_t in_blocks = in ? (in + il - 1) / il : 0, last_in = in ? in - (in_blocks - 1) * il : 0;
     const uint64_t align = (uint64_t)(uintptr_t)d_files | (uint64_t)(nfiles > 1 ? file_pitch : 0) | (uint64_t)I->audio_data_offset |
                            il | last_in | (uint64_t)(uintptr_t)d_adpcm | (uint64_t)adpcm_pitch;
-    hipStream_t s = (hipStream_t)stream;
-    const int rows = nfiles * nch;
-    for (int r0 = 0; r0 < rows; r0 += nwstm::kMaxGridY) {
-        const int nr = std::min(rows - r0, nwstm::kMaxGridY);
-        if (int rc = nwstm::pick_granule(align, [&](auto g) {
-                constexpr int G = decltype(g)::value;
-                hipLaunchKernelGGL(nwstm::nw_deinterleave_kernel<G>, dim3((unsigned)(((out + G - 1) / G + 255) / 256), nr), dim3(256), 0, s, d_files,
-                                   file_pitch, I->audio_data_offset, nch, in, il, out, d_adpcm, adpcm_pitch, r0);
-            }))
-            return rc;
-    }
-    return VGA_OK;
+    return container::launch_deinterleave(align, d_files, file_pitch, I->audio_data_offset, nch, nfiles * nch, in, il, out, d_adpcm,
+                                          adpcm_pitch, (hipStream_t)stream);
 }
 
 int vga_nwstm_read(const uint8_t *file, size_t size, const vga_nwstm_info *I, uint8_t *const *adpcm_out, int16_t *const *seek_out)

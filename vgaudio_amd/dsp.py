@@ -1,13 +1,13 @@
-"""DSP container writer for GC-ADPCM -- the host-side mirror of
-VGAudio/Containers/Dsp/DspWriter.cs and DspConfiguration.cs.  The file image is assembled on the GPU
-(vga_dsp_write); there is no CPU path."""
+"""DSP container for GC-ADPCM -- the host-side mirror of VGAudio/Containers/Dsp/DspWriter.cs,
+DspReader.cs and DspConfiguration.cs.  The file image is assembled and taken apart on the GPU (vga_dsp_write,
+vga_dsp_read); only the header is parsed on the host (vga_dsp_parse).  There is no CPU path."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 from ._lib import check, i16p, u8p
-from .gcadpcm import GcAdpcmFormat, _i16, _ptr_array
+from .gcadpcm import GcAdpcmChannel, GcAdpcmContext, GcAdpcmFormat, _i16, _ptr_array
 
 
 class DspConfiguration:
@@ -72,3 +72,47 @@ class DspWriter:
         check(_lib.lib().vga_dsp_write(_ptr_array(u8p, src), len(src[0]), _i16(coefs), _i16(gain), _i16(start), _i16(loop),
                                        nch, C.byref(p), out.ctypes.data_as(u8p)))
         return out.tobytes()
+
+
+def parse(data):
+    """vga_dsp_parse: DspReader.ReadHeader plus the checks ReadData makes (no device work)."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    info = _lib.DspInfoC()
+    check(_lib.lib().vga_dsp_parse(buf.ctypes.data_as(u8p), len(buf), C.byref(info)))
+    return info
+
+
+class DspReader:
+    """AudioReader<DspReader, DspStructure, DspConfiguration> (Containers/Dsp/DspReader.cs): ReadFormat(bytes) ->
+    GcAdpcmFormat, ReadWithConfig(bytes) -> (format, configuration), ReadMetadata(bytes) -> the parsed header
+    (vga_dsp_info) without audio."""
+
+    def ReadMetadata(self, data):
+        return parse(data)
+
+    def ReadFormat(self, data):
+        return self.ReadWithConfig(data)[0]
+
+    def ReadWithConfig(self, data):
+        data = bytes(data)
+        info = parse(data)
+        buf = np.frombuffer(data, dtype=np.uint8)
+        adpcm = [np.zeros(info.adpcm_bytes, dtype=np.uint8) for _ in range(info.channel_count)]
+        check(_lib.lib().vga_dsp_read(buf.ctypes.data_as(u8p), len(buf), C.byref(info), _ptr_array(u8p, adpcm)))
+        return self._to_format(info, adpcm), DspConfiguration()      # GetConfiguration: AudioReader's default (new TConfig())
+
+    @staticmethod
+    def _to_format(info, adpcm):
+        """ToAudioStream (:33-55): the stored coefficients, gain, start and loop contexts; nothing is recomputed."""
+        from .nwstm import _stored_format
+        looping = bool(info.looping)
+        chans = []
+        for c in range(info.channel_count):
+            ch = GcAdpcmChannel(adpcm[c], np.array(info.coefs[c][:], dtype=np.int16), info.sample_count)
+            ch.Gain = int(info.gain[c])
+            ch.StartContext = GcAdpcmContext(*info.start_context[c][:])
+            if looping:                                          # WithLoop(..).WithLoopContext(LoopStart, ..)
+                ch.LoopContext = GcAdpcmContext(*info.loop_context[c][:])
+                ch.LoopContextStart = info.loop_start
+            chans.append(ch)
+        return _stored_format(chans, info.sample_rate, looping, info.loop_start, info.loop_end, None)
