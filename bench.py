@@ -12,19 +12,25 @@
 --codec adx: configs[2], 4096 channels CRI ADX encode + decode round trip.  A step = encode + decode.
 --codec hca: configs[3], 1024 stereo streams CRI HCA encode, quality High.  A step = encode (decode is timed beside it).
 
-Channels/streams shard across GPUs with no data-path collective (weak scaling: every rank owns its own units);
-with N > 1 the gc line also reports the step with the final RCCL gather of the bitstream to rank 0.
+Channels/streams shard across GPUs with no data-path collective (weak scaling: every rank owns its own units).
 Rank 0 prints ONE JSON line.
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, the K timed steps, --dump-outputs if given,
+the line.  Its roofline holds what the timed steps' own events and the committed profiles give; it launches nothing else.
+--full adds everything else the benchmark measures and checks, after the timed steps (the --no-* options trim it):
+the CPU baseline with its bit-for-bit check, decode launches (roofline.other_kernels), e2e, and per codec: gc
+mixed_lengths, signal_sensitivity, other_configs (the ADX and HCA lines at their BASELINE shapes), and with N > 1 the
+step with the final RCCL gather of the bitstream to rank 0, weak_scaling and e2e_multi; adx looping.
 
 roofline    : the dominant kernel; achieved = algorithmic bytes per launch (GC encode 2 + 8/14 B/sample,
               ADX 2.5625 B/sample, HCA 2 + 682/2048 B/channel-sample) / mean HIP-event duration of that launch;
               traffic = HBM bytes per launch from the committed rocprofv3 PMC passes (profiles/), valid for the
               profiled shape only.
-cpu_baseline: the oracle (C restatement of the reference, "port") run with the reference's scheduling -- one task per
+cpu_baseline: (--full) the oracle (C restatement of the reference, "port") run with the reference's scheduling -- one task per
               channel (Parallel.For, GcAdpcmFormat.cs:65; CriAdxFormat.cs:67) or per stream (HCA has no intra-file
               parallelism, CriHcaFormat.cs:53-81; Cli/Batch.cs:24-25) -- on a bounded sample; the same leg compares its
               output with this run's GPU output for those units, bit for bit.  The oracle is touched nowhere else.
-e2e         : (gc, N = 1) one vga_gcadpcm_encode_batch call through the host-pointer C ABI -- what a P/Invoke caller
+e2e         : (--full; gc, N = 1) one vga_gcadpcm_encode_batch call through the host-pointer C ABI -- what a P/Invoke caller
               gets, pageable host arrays in and out -- next to the PCIe-bound time for the same bytes.
 """
 import argparse
@@ -56,6 +62,9 @@ def parse():
     ap.add_argument("--channels", type=int, default=4096, help="channels per GPU (gc, adx)")
     ap.add_argument("--streams", type=int, default=1024, help="stereo streams per GPU (hca)")
     ap.add_argument("--seconds", type=float, default=60.0, help="audio seconds per channel @48 kHz")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything besides the headline: CPU baseline, "
+                         "decode launches, e2e, mixed lengths, signal classes, other configs, ADX looping, the N > 1 gather")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-channels", type=int, default=0, help="units in the CPU baseline sample (0 = auto)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host-pointer ABI measurement")
@@ -946,12 +955,12 @@ def run_gc(args, cx):
 
     gather = scaling = None
     if cx.rank != 0:
-        if cx.world > 1:
+        if cx.world > 1 and args.full:
             guarded(cx, None, lambda: multi_gpu_extras(adpcm, coefs))
         return None
     # the other direction (GcAdpcmDecoder.Decode), outside the timed steps: three launches between HIP events
     dec_ms = 0.0
-    if cx.world == 1:
+    if cx.world == 1 and args.full:
         back = vdev.alloc_pcm(nch, n, cx.dev)
         vdev.gc_decode(adpcm, coefs, n, out=back)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1000,6 +1009,14 @@ def run_gc(args, cx):
     # return at once unless a seam stayed open); launch_ms spans them, the rocprofv3 kernel stats under profiles/ list them
     # separately (their averages add up to it)
     persistent = nch >= 512                 # plan_encode_pieces: one channel group per 32 workgroups (gc_encode_kernel.hip)
+    other_kernels = {"gc_coefs_kernel": {
+        "launch_ms": round(coef_ms, 3),
+        "achieved": round(COEF_BYTES_PER_SAMPLE * nch * n / (coef_ms * 1e-3) / 1e9, 2) if coef_ms > 0 else 0.0}}
+    if args.full:
+        other_kernels["gc_decode_direct_kernel (+fixup, tail; not part of the step)"] = {
+            "traffic": (pmc.get("gc_decode_direct_kernel") or {}).get("traffic_bytes_per_launch") if pmc and full else None,
+            "launch_ms": round(dec_ms, 3),
+            "achieved": round(ENC_BYTES_PER_SAMPLE * nch * n / (dec_ms * 1e-3) / 1e9, 2) if dec_ms > 0 else 0.0}
     roofline = {"bound": "hbm", "kernel": "gc_encode_persistent_kernel" if persistent else "gc_encode_kernel", "achieved": round(achieved, 2),
                 "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
                 "traffic": traffic, "traffic_source": pmc_note, "algorithmic_bytes_per_launch": enc_bytes, "launch_ms": round(enc_ms, 3),
@@ -1008,19 +1025,13 @@ def run_gc(args, cx):
                 "launch_ms_each": [round(e[1].elapsed_time(e[2]), 2) for e in evs],
                 "launch_parts": (["gc_encode_persistent_kernel (pieces from a queue, seams inside)"] if persistent else
                                  ["gc_encode_kernel<false>", "gc_encode_seam_kernel"]) + ["gc_encode_chain_kernel", "gc_encode_kernel<true>"],
-                "other_kernels": {"gc_coefs_kernel": {
-                    "launch_ms": round(coef_ms, 3),
-                    "achieved": round(COEF_BYTES_PER_SAMPLE * nch * n / (coef_ms * 1e-3) / 1e9, 2) if coef_ms > 0 else 0.0},
-                    "gc_decode_direct_kernel (+fixup, tail; not part of the step)": {
-                        "traffic": (pmc.get("gc_decode_direct_kernel") or {}).get("traffic_bytes_per_launch") if pmc and full else None,
-                        "launch_ms": round(dec_ms, 3),
-                        "achieved": round(ENC_BYTES_PER_SAMPLE * nch * n / (dec_ms * 1e-3) / 1e9, 2) if dec_ms > 0 else 0.0}},
+                "other_kernels": other_kernels,
                 "pipeline_achieved": round(PIPE_BYTES_PER_SAMPLE * nch * n / ((coef_ms + enc_ms) * 1e-3) / 1e9, 2)
                 if coef_ms + enc_ms > 0 else 0.0,
                 "issue": issue, "issue_source": sq_note}
 
     cpu = None
-    if not args.no_cpu_baseline and cx.world == 1:          # the CPU leg runs at N=1 only (rank 0's host cores)
+    if args.full and not args.no_cpu_baseline and cx.world == 1:     # the CPU leg runs at N=1 only (rank 0's host cores)
         threads, cpu_note = usable_cpus()
         cch = args.cpu_channels or min(nch, 24 * threads)
         host = pcm[:cch, :n].cpu().numpy()
@@ -1046,7 +1057,7 @@ def run_gc(args, cx):
                     "int32", f"BASELINE configs[1]: {nch} mono channels x 48 kHz x {args.seconds:g} s GC-ADPCM coefficient "
                              f"search + encode per GPU",
                     {"channels_per_gpu": nch, "samples_per_channel": n, "bit_exact_channels_checked": verified}, roofline, cpu)
-    if cx.world > 1:
+    if cx.world > 1 and args.full:
         # the line so far is complete without what follows: if the extras fail, it is printed with the failure named; if
         # they hang (a collective that never returns), a watchdog prints it and ends this rank
         res = guarded(cx, out, lambda: multi_gpu_extras(adpcm, coefs))
@@ -1058,9 +1069,9 @@ def run_gc(args, cx):
         out["gather"] = gather
     if scaling:
         out["weak_scaling"] = scaling
-    if not args.no_e2e and cx.world == 1:
+    if args.full and not args.no_e2e and cx.world == 1:
         out["e2e"] = measure_e2e(cx, args, pcm, n, coefs, adpcm)
-    if not args.no_mixed and cx.world == 1:
+    if args.full and not args.no_mixed and cx.world == 1:
         del pcm, adpcm, ws
         torch.cuda.empty_cache()
         try:
@@ -1069,7 +1080,7 @@ def run_gc(args, cx):
             raise
         except Exception as e:                          # noqa: BLE001 -- the line is worth more than this block
             out["mixed_lengths"] = {"error": f"{type(e).__name__}: {e}"}
-    if not args.no_signals and cx.world == 1:
+    if args.full and not args.no_signals and cx.world == 1:
         torch.cuda.empty_cache()
         try:
             out["signal_sensitivity"] = measure_signal_sensitivity(cx, args)
@@ -1077,7 +1088,7 @@ def run_gc(args, cx):
             raise
         except Exception as e:                          # noqa: BLE001 -- the line is worth more than this block
             out["signal_sensitivity"] = {"error": f"{type(e).__name__}: {e}"}
-    if not args.no_e2e and cx.world > 1:
+    if args.full and not args.no_e2e and cx.world > 1:
         # one process, N GPUs: the same 4096-channel call as the N = 1 line's e2e block, its channels spread over all
         # GPUs of the job by the library (the other ranks are idle at the final barrier meanwhile)
         devs = [0] * cx.world if args.share_gpu else list(range(cx.world))
@@ -1145,7 +1156,7 @@ def run_adx(args, cx):
                     if pmc and nch == 4096 and n == 2880000 else None}},
                 "pipeline_achieved": round(2 * bytes_launch / ((enc_ms + dec_ms) * 1e-3) / 1e9, 2) if enc_ms + dec_ms > 0 else 0.0}
     cpu, verified = None, 0
-    if not args.no_cpu_baseline and cx.world == 1:
+    if args.full and not args.no_cpu_baseline and cx.world == 1:
         threads, cpu_note = usable_cpus()
         cch = args.cpu_channels or min(nch, 64 * threads)
         host = pcm[:cch, :n].cpu().numpy()
@@ -1166,7 +1177,7 @@ def run_adx(args, cx):
     # of the alignment -- LoopStart = 1000 in a mono file: Padding = 1024 - 1000 = 24 -- and until round 6 a padded stream took
     # the lane-per-channel kernels (decode of this shape: 1.1 s).  The same channels with that padding, outside the timed region.
     looping = None
-    if cx.world == 1:
+    if cx.world == 1 and args.full:
         lp = lib.AdxParams()
         L.vga_adx_default_params(C.byref(lp))
         lp.padding = 24
@@ -1201,7 +1212,7 @@ def run_adx(args, cx):
             looping["bit_exact_channels_checked"] = len(idx)
         del ladx, ldec
     e2e = None
-    if not args.no_e2e and cx.world == 1:
+    if args.full and not args.no_e2e and cx.world == 1:
         avail = host_memory_available()
         want_ch = nch
         if avail is not None and want_ch * (2 * n + nb) > 0.7 * avail:
@@ -1265,14 +1276,16 @@ def run_hca(args, cx):
         dump_outputs(args.dump_outputs, {"frames": frames[:, :fbytes]})
     enc_ms = mean_ms(evs, 0, 1)
     # decode beside it (not part of the step)
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    for _ in range(2):
-        e[0].record()
-        lib.check(L.vga_hca_decode_device(C.byref(info), frames.data_ptr(), fpitch, ns, dec.data_ptr(), 2 * ch_pitch, ch_pitch,
-                                          ws.data_ptr(), wsb, status.data_ptr(), cx.st()))
-        e[1].record()
-        torch.cuda.synchronize()
-    dec_ms = e[0].elapsed_time(e[1])
+    dec_ms = 0.0
+    if args.full:
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for _ in range(2):
+            e[0].record()
+            lib.check(L.vga_hca_decode_device(C.byref(info), frames.data_ptr(), fpitch, ns, dec.data_ptr(), 2 * ch_pitch, ch_pitch,
+                                              ws.data_ptr(), wsb, status.data_ptr(), cx.st()))
+            e[1].record()
+            torch.cuda.synchronize()
+        dec_ms = e[0].elapsed_time(e[1])
     if int(status.item()) != 0:
         raise SystemExit("HCA kernels reported an error status")
     ms_per_step = elapsed / max(args.steps, 1) * 1e3
@@ -1291,11 +1304,11 @@ def run_hca(args, cx):
                 "algorithmic_bytes_per_launch": bytes_launch, "launch_ms": round(enc_ms, 3),
                 "other_kernels": {"hca_scan_kernel + hca_frames_kernel (decode)": {
                     "launch_ms": round(dec_ms, 3),
-                    "achieved": round(bytes_launch / (dec_ms * 1e-3) / 1e9, 2) if dec_ms > 0 else 0.0}},
+                    "achieved": round(bytes_launch / (dec_ms * 1e-3) / 1e9, 2) if dec_ms > 0 else 0.0}} if args.full else {},
                 "mfma": "the exact path uses no MFMA: a dense 128x128 DCT-IV reassociates the f64 sums (LABNOTES.md 4.4; "
                         "measured variant: tools/bench_hca_mfma.py, profiles/)"}
     cpu, verified = None, 0
-    if not args.no_cpu_baseline and cx.world == 1:
+    if args.full and not args.no_cpu_baseline and cx.world == 1:
         threads, cpu_note = usable_cpus()
         workers = max(1, threads - 1)                          # Cli/Batch.cs:25: ProcessorCount - 1 workers, one file each
         cs = args.cpu_channels or min(ns, 16 * workers)
@@ -1317,7 +1330,7 @@ def run_hca(args, cx):
                          f"(the reference has no intra-file parallelism, CriHcaFormat.cs:53-81; Cli/Batch.cs:24-25 runs "
                          f"ProcessorCount-1 files at a time; {cpu_note}); C restatement of CriHcaFormat.EncodeFromPcm16, {dt:.1f} s wall"}
     e2e = None
-    if not args.no_e2e and cx.world == 1:
+    if args.full and not args.no_e2e and cx.world == 1:
         avail = host_memory_available()
         want_s = ns
         per_stream = 2 * 2 * n + fbytes
@@ -1386,7 +1399,8 @@ def main():
         import gc
         gc.collect()
         cx.torch.cuda.empty_cache()
-    if args.codec == "gc" and cx.world == 1 and out is not None and not args.no_other_configs and args.channels == 4096 and args.seconds == 60.0:
+    if (args.full and args.codec == "gc" and cx.world == 1 and out is not None and not args.no_other_configs and args.channels == 4096
+            and args.seconds == 60.0):
         import torch
         torch.cuda.empty_cache()
         out["other_configs"] = other_configs(args, cx)

@@ -1,7 +1,8 @@
 #!/bin/bash
-# start offsets and durations of the last kernels of `bench.py --codec adx` (rocprofv3 --kernel-trace): where a launch's gaps are
+# start offsets and durations of the last kernels of `bench.py --full --codec adx` (rocprofv3 --kernel-trace): where a launch's gaps are
+R=$(cd "$(dirname "$0")/.." && pwd)
 D=$(mktemp -d /tmp/tl.XXXX)
-cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $D -o t -- python $GRAFT_REPO_ROOT/bench.py --codec adx --steps 3 --warmup 1 --no-cpu-baseline > $D/log 2>&1
+cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $D -o t -- python $R/bench.py --full --codec adx --steps 3 --warmup 1 --no-cpu-baseline > $D/log 2>&1
 python3 - $D <<'PY'
 import csv, sys, glob
 f = glob.glob(sys.argv[1] + '/**/*kernel_trace.csv', recursive=True)[0]
