@@ -431,6 +431,159 @@ int vga_nwstm_read_device(const vga_nwstm_info *info, const uint8_t *d_files, in
 int vga_nwstm_read(const uint8_t *file, size_t size, const vga_nwstm_info *info, uint8_t *const *adpcm_out,
                    int16_t *const *seek_out);
 
+/* ----------------------------------------------------------------------
+ * HPS (HAL DSP stream, " HALPST"), IDSP and GENH for GC-ADPCM: VGAudio/Containers/Hps, Idsp, Genh.
+ * Write path: *_layout_for -> vga_gcadpcm_build_channels_* with layout.channel -> *_write_device.
+ * Read path: *_parse (host) -> *_read_device -> vga_gcadpcm_decode_device.  Every container is limited to
+ * 255 channels (more: VGA_ERR_INVALID_OP); GENH keeps the reference's 1-2.  Parsers never read past `size`.
+ * -------------------------------------------------------------------- */
+#define VGA_GC_CONTAINER_MAX_CHANNELS 255
+/* HPS writer (HpsWriter.cs).  The reference cannot write a file of 3, 7, 11, ... channels (nch % 4 == 3): its
+ * BlockInfo.TotalSize counts a block header of 4 + 8*nch bytes where WriteBlock writes 12 + 8*nch, so the padded
+ * header is 0x20 longer than counted and the writes overrun the fixed-size image; those counts return
+ * VGA_ERR_INVALID_OP.  An empty stream (no block) returns VGA_ERR_OUT_OF_RANGE, as the reference indexes blocks[0]. */
+typedef struct {
+    int sample_rate;
+    int sample_count;                    /* the format's UnalignedSampleCount */
+    int looping, loop_start, loop_end;   /* the format's loop before the writer aligns it */
+} vga_hps_params;
+typedef struct {
+    int header_size;                     /* GetNextMultiple(max(0x80, 0x10 + 0x38*nch), 0x20) */
+    int channel_size;                    /* GetNextMultiple(0x10000 / nch, 0x20): bytes of one channel per full block */
+    int alignment;                       /* ByteCountToSampleCount(channel_size): the loop alignment */
+    int alignment_needed;                /* the loop start is not a multiple of `alignment` */
+    vga_gcadpcm_channel_params channel;  /* pass to vga_gcadpcm_build_channels_* before writing */
+    int sample_count, looping, loop_start, loop_end;   /* the aligned format's */
+    int channel_adpcm_bytes;             /* GetAdpcmAudio() after that build: SampleCountToByteCount(sample_count) */
+    int block_header_size;               /* GetNextMultiple(12 + 8*nch, 0x20), as written */
+    int block_count, loop_block;         /* CreateBlockMap (:114-160); loop_block = block_count - 1 without a loop */
+    int file_size;
+} vga_hps_layout;
+/* one BlockInfo (HpsWriter.cs:162-185) */
+typedef struct {
+    int offset, next_offset;             /* the last next_offset points at the loop block, or is -1 */
+    int start_sample;                    /* NibbleToSample(nibble + 2) */
+    int byte_in_index;                   /* the block's first byte in every channel's ADPCM */
+    int channel_size, written_size, total_size, end_nibble;
+} vga_hps_block;
+int vga_hps_layout_for(const vga_hps_params *p, int nch, vga_hps_layout *out);
+/* blocks: layout.block_count entries (capacity at least that, else VGA_ERR_ARGUMENT) */
+int vga_hps_block_map(const vga_hps_params *p, int nch, vga_hps_block *blocks, int capacity);
+/* nfiles equally shaped files; file f's channel c is row f*nch+c of every pitched input:
+ *   d_adpcm  GetAdpcmAudio() after the build, adpcm_len bytes per row (layout.channel_adpcm_bytes);
+ *   d_coefs  16 shorts per row; d_gain 1 short per row or NULL (0); d_start_context 3 shorts per row or NULL
+ *            ((adpcm[0], 0, 0));
+ *   d_pcm    the rows the block headers' hist1 / hist2 come from (GcAdpcmChannel's Pcm field, pcm_len samples per
+ *            row, pcm_pitch in samples) or NULL for zeros.  A block whose hist index falls at or past pcm_len
+ *            returns VGA_ERR_OUT_OF_RANGE (the reference's IndexOutOfRangeException).
+ * Image f goes to d_files + f*file_pitch (file_pitch >= layout.file_size, a multiple of 16 when nfiles > 1); every
+ * byte is written.  Stream-ordered: the block map reaches the device as kernel arguments, nothing synchronises. */
+int vga_hps_write_device(const vga_hps_params *p, int nch, int nfiles, const uint8_t *d_adpcm, int64_t adpcm_pitch,
+                         int adpcm_len, const int16_t *d_coefs, const int16_t *d_gain, const int16_t *d_start_context,
+                         const int16_t *d_pcm, int64_t pcm_pitch, int pcm_len, uint8_t *d_files, int64_t file_pitch,
+                         void *stream);
+/* one file from host arrays: adpcm[c] adpcm_len bytes, pcm[c] pcm_len samples (pcm NULL: zeros); file_out:
+ * layout.file_size bytes */
+int vga_hps_write(const vga_hps_params *p, int nch, const uint8_t *const *adpcm, int adpcm_len, const int16_t *coefs,
+                  const int16_t *gain, const int16_t *start_context, const int16_t *const *pcm, int pcm_len,
+                  uint8_t *file_out);
+/* HPS reader (HpsReader.cs) */
+typedef struct {
+    int sample_rate, channel_count;
+    int sample_count;                    /* NibbleToSample(EndAddress) + 1, equal in every channel */
+    int looping, loop_start;             /* the last block's NextOffset names a block: the nibbles before it */
+    int max_block_size[VGA_GC_CONTAINER_MAX_CHANNELS], end_address[VGA_GC_CONTAINER_MAX_CHANNELS];
+    int16_t coefs[VGA_GC_CONTAINER_MAX_CHANNELS][16];
+    int16_t gain[VGA_GC_CONTAINER_MAX_CHANNELS];
+    int16_t start_context[VGA_GC_CONTAINER_MAX_CHANNELS][3];
+    int16_t loop_context[VGA_GC_CONTAINER_MAX_CHANNELS][3];   /* the loop block's header context, zeros without a loop */
+    int block_count;                     /* blocks up to the first NextOffset <= its own offset */
+    int adpcm_bytes;                     /* one channel's audio: the sum of the blocks' AudioSizeBytes */
+} vga_hps_info;
+typedef struct {
+    int offset, next_offset, size, final_nibble;
+    int audio_offset;                    /* the block's audio start; channel c at audio_offset + size / nch * c */
+    int audio_bytes;                     /* AudioSizeBytes = (final_nibble + 1) / 2 rounded up */
+    int out_offset;                      /* where the block's bytes land in the channel's row */
+} vga_hps_block_info;
+/* host only.  blocks NULL: fills info (block_count included) and stops; else blocks holds capacity entries (at least
+ * info->block_count).  VGA_ERR_INVALID_DATA for a missing magic, reads past the end, channel sample counts that
+ * differ, no channels, audio shorter than the sample count; VGA_ERR_INVALID_OP for more than 255 channels. */
+int vga_hps_parse(const uint8_t *file, size_t size, vga_hps_info *info, vga_hps_block_info *blocks, int capacity);
+/* nfiles images that share one parsed geometry -> row f*channel_count+c of d_adpcm (info->adpcm_bytes per row) */
+int vga_hps_read_device(const vga_hps_info *info, const vga_hps_block_info *blocks, const uint8_t *d_files,
+                        int64_t file_pitch, int nfiles, uint8_t *d_adpcm, int64_t adpcm_pitch, void *stream);
+int vga_hps_read(const uint8_t *file, size_t size, const vga_hps_info *info, const vga_hps_block_info *blocks,
+                 uint8_t *const *adpcm_out);
+
+/* IDSP writer (IdspWriter.cs, IdspConfiguration.cs) */
+typedef struct {
+    int sample_rate;
+    int sample_count;                    /* the format's UnalignedSampleCount */
+    int looping, loop_start, loop_end;   /* the format's loop before the writer aligns it */
+    int block_size;                      /* IdspConfiguration.BlockSize (the reference's default 0x10): 0 = not
+                                          * interleaved, else a multiple of 8 that the loop is aligned to */
+    int trim_file;                       /* Configuration.TrimFile */
+} vga_idsp_params;
+typedef struct {
+    int alignment_needed;
+    vga_gcadpcm_channel_params channel;  /* pass to vga_gcadpcm_build_channels_* before writing */
+    int channel_sample_count, channel_adpcm_bytes;   /* what that build leaves per channel */
+    int sample_count, looping, loop_start, loop_end; /* as the header carries them (:19-27) */
+    int start_addr, end_addr, cur_addr;
+    int interleave_size;                 /* BlockSize, or AudioDataSize when 0 */
+    int header_size;                     /* 0x40 + 0x60*nch */
+    int audio_data_size;                 /* one channel, padded to the interleave (to 8 bytes when not interleaved) */
+    int file_size;
+} vga_idsp_layout;
+/* VGA_ERR_OUT_OF_RANGE for a negative block size or one not divisible by 8 (the BlockSize setter) and for loop
+ * points WithLoop rejects; VGA_ERR_INVALID_OP for a block size of 0 with no audio (the reference divides by 0). */
+int vga_idsp_layout_for(const vga_idsp_params *p, int nch, vga_idsp_layout *out);
+/* as vga_hps_write_device without the PCM rows, plus d_loop_context (3 shorts per row or NULL for zeros) */
+int vga_idsp_write_device(const vga_idsp_params *p, int nch, int nfiles, const uint8_t *d_adpcm, int64_t adpcm_pitch,
+                          int adpcm_len, const int16_t *d_coefs, const int16_t *d_gain, const int16_t *d_start_context,
+                          const int16_t *d_loop_context, uint8_t *d_files, int64_t file_pitch, void *stream);
+int vga_idsp_write(const vga_idsp_params *p, int nch, const uint8_t *const *adpcm, int adpcm_len, const int16_t *coefs,
+                   const int16_t *gain, const int16_t *start_context, const int16_t *loop_context, uint8_t *file_out);
+/* IDSP reader (IdspReader.cs).  The header's fields are named as the reader reads them: header_size is the writer's
+ * stream info size (0x40), audio_data_offset the writer's header size. */
+typedef struct {
+    int channel_count, sample_rate, sample_count, loop_start, loop_end;
+    int interleave_size, header_size, channel_info_size, audio_data_offset, audio_data_length;
+    int looping;                         /* any channel's loop flag is 1 */
+    int channel_sample_count[VGA_GC_CONTAINER_MAX_CHANNELS], channel_looping[VGA_GC_CONTAINER_MAX_CHANNELS];
+    int start_address[VGA_GC_CONTAINER_MAX_CHANNELS], end_address[VGA_GC_CONTAINER_MAX_CHANNELS];
+    int16_t coefs[VGA_GC_CONTAINER_MAX_CHANNELS][16];
+    int16_t gain[VGA_GC_CONTAINER_MAX_CHANNELS];
+    int16_t start_context[VGA_GC_CONTAINER_MAX_CHANNELS][3];
+    int16_t loop_context[VGA_GC_CONTAINER_MAX_CHANNELS][3];
+    int interleave;                      /* DeInterleave's: interleave_size, or audio_data_length when 0 */
+    int adpcm_bytes;                     /* SampleCountToByteCount(sample_count): DeInterleave's output size */
+} vga_idsp_info;
+/* VGA_ERR_INVALID_DATA for a missing magic, reads past the end, no channels, a zero interleave, audio past the end;
+ * VGA_ERR_INVALID_OP for more than 255 channels */
+int vga_idsp_parse(const uint8_t *file, size_t size, vga_idsp_info *out);
+int vga_idsp_read_device(const vga_idsp_info *info, const uint8_t *d_files, int64_t file_pitch, int nfiles, uint8_t *d_adpcm,
+                         int64_t adpcm_pitch, void *stream);
+int vga_idsp_read(const uint8_t *file, size_t size, const vga_idsp_info *info, uint8_t *const *adpcm_out);
+
+/* GENH reader (GenhReader.cs; the reference has no GENH writer).  Little-endian header; the coefficients sit at
+ * absolute offsets in the byte order coef_type names (bit 1 little-endian), bit 0 (Split) reads 8 even and 8 odd
+ * shorts from coef_offset and coef_split_offset.  sample_count = loop_end; the file loops when loop_start != -1. */
+typedef struct {
+    int channel_count, interleave, sample_rate, loop_start, loop_end, codec, audio_data_offset, header_size;
+    int coef_offset[2], interleave_type, coef_type, coef_split_offset[2];
+    int sample_count, looping;
+    int16_t coefs[2][16];
+    int adpcm_bytes;                     /* SampleCountToByteCount(sample_count) per channel */
+} vga_genh_info;
+/* VGA_ERR_INVALID_DATA for a missing magic, 0 or more than 2 channels, a header that ends after the audio offset,
+ * reads past the end, an interleave <= 0 (DeInterleave divides by it) */
+int vga_genh_parse(const uint8_t *file, size_t size, vga_genh_info *out);
+int vga_genh_read_device(const vga_genh_info *info, const uint8_t *d_files, int64_t file_pitch, int nfiles, uint8_t *d_adpcm,
+                         int64_t adpcm_pitch, void *stream);
+int vga_genh_read(const uint8_t *file, size_t size, const vga_genh_info *info, uint8_t *const *adpcm_out);
+
 /* ======================================================================
  * CRI ADX
  * ====================================================================== */

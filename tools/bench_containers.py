@@ -177,6 +177,62 @@ def main():
     rec("dsp_read", ms, 2 * nf * nch * nb, channels=nf * nch, files=nf, note="DSP audio -> pitched channels (interleave 8 KiB)")
     del files, back
 
+    # HPS, IDSP and GENH: 2048 stereo files of 60 s, device-resident
+    adpcm = torch.randint(0, 256, (nf * nch, pitch), dtype=torch.uint8, device=dev)
+    coefs = torch.zeros((nf * nch, 16), dtype=torch.int16, device=dev)
+    back = torch.empty_like(adpcm)
+    hp = _lib.HpsParamsC(48000, n, 0, 0, 0)
+    hl = _lib.HpsLayoutC()
+    _lib.check(L.vga_hps_layout_for(C.byref(hp), nch, C.byref(hl)))
+    fp = (hl.file_size + 255) // 256 * 256
+    files = torch.empty((nf, fp), dtype=torch.uint8, device=dev)
+    ms = timed(lambda: _lib.check(L.vga_hps_write_device(C.byref(hp), nch, nf, adpcm.data_ptr(), pitch, nb, coefs.data_ptr(), None, None,
+                                                         None, 0, 0, files.data_ptr(), fp, st())))
+    rec("hps_write", ms, nf * nch * nb + nf * hl.file_size, channels=nf * nch, files=nf, blocks_per_file=hl.block_count,
+        note="header kernel (stream + block headers) + body kernel, every image byte written once")
+    hi = _lib.HpsInfoC()
+    one = files[0, :hl.file_size].cpu().numpy()
+    _lib.check(L.vga_hps_parse(one.ctypes.data_as(_lib.u8p), len(one), C.byref(hi), None, 0))
+    hb = (_lib.HpsBlockInfoC * hi.block_count)()
+    _lib.check(L.vga_hps_parse(one.ctypes.data_as(_lib.u8p), len(one), C.byref(hi), hb, hi.block_count))
+    ms = timed(lambda: _lib.check(L.vga_hps_read_device(C.byref(hi), hb, files.data_ptr(), fp, nf, back.data_ptr(), pitch, st())))
+    assert torch.equal(back[:, :nb], adpcm[:, :nb])
+    rec("hps_read", ms, 2 * nf * nch * nb, channels=nf * nch, files=nf, note="block gather -> pitched channels")
+    del files
+    ip = _lib.IdspParamsC(48000, n, 0, 0, 0, 0x10, 1)
+    il = _lib.IdspLayoutC()
+    _lib.check(L.vga_idsp_layout_for(C.byref(ip), nch, C.byref(il)))
+    fp = (il.file_size + 255) // 256 * 256
+    files = torch.empty((nf, fp), dtype=torch.uint8, device=dev)
+    ms = timed(lambda: _lib.check(L.vga_idsp_write_device(C.byref(ip), nch, nf, adpcm.data_ptr(), pitch, nb, coefs.data_ptr(), None, None,
+                                                          None, files.data_ptr(), fp, st())))
+    rec("idsp_write", ms, nf * nch * nb + nf * il.file_size, channels=nf * nch, files=nf,
+        note="header kernel + batched interleave (BlockSize 0x10), every image byte written once")
+    ii = _lib.IdspInfoC()
+    one = files[0, :il.file_size].cpu().numpy()
+    _lib.check(L.vga_idsp_parse(one.ctypes.data_as(_lib.u8p), len(one), C.byref(ii)))
+    back.zero_()
+    ms = timed(lambda: _lib.check(L.vga_idsp_read_device(C.byref(ii), files.data_ptr(), fp, nf, back.data_ptr(), pitch, st())))
+    assert torch.equal(back[:, :nb], adpcm[:, :nb])
+    rec("idsp_read", ms, 2 * nf * nch * nb, channels=nf * nch, files=nf, note="de-interleave of 16-byte blocks")
+    del files
+    # GENH: the IDSP images' audio region read as GENH (interleave 0x10), the header in front of it
+    import struct
+    hdr = np.zeros(il.header_size, np.uint8)
+    struct.pack_into("<4s14i", hdr, 0, b"GENH", nch, 0x10, 48000, -1, n, 12, il.header_size, 0x40, 0x40, 0x40, 0, 0, 0, 0)
+    gi = _lib.GenhInfoC()
+    probe = np.concatenate([hdr, np.zeros(nch * nb, np.uint8)])
+    _lib.check(L.vga_genh_parse(probe.ctypes.data_as(_lib.u8p), len(probe), C.byref(gi)))
+    files = torch.empty((nf, fp), dtype=torch.uint8, device=dev)
+    _lib.check(L.vga_idsp_write_device(C.byref(ip), nch, nf, adpcm.data_ptr(), pitch, nb, coefs.data_ptr(), None, None, None,
+                                       files.data_ptr(), fp, st()))
+    back.zero_()
+    ms = timed(lambda: _lib.check(L.vga_genh_read_device(C.byref(gi), files.data_ptr(), fp, nf, back.data_ptr(), pitch, st())))
+    assert torch.equal(back[:, :nb - 16], adpcm[:, :nb - 16])   # GENH's short last block sits differently from IDSP's padded one
+    rec("genh_read", ms, 2 * nf * nch * nb, channels=nf * nch, files=nf,
+        note="de-interleave of 16-byte blocks, an unpadded 3-byte last block (GENH header)")
+    del files, back, adpcm
+
     # ADX: 2048 stereo files of 60 s, 18-byte frames; the 16-byte-vector kernel and the general de-interleave
     ap = _lib.AdxFileParamsC(48000, n, 0, 0, 0, 0, 18, 4, 3, 500, 0, 1)
     al = _lib.AdxFileLayoutC()

@@ -202,6 +202,22 @@ SIGNATURES = {
     "vga_nwstm_parse": (ci, [u8p, C.c_size_t, vp]),
     "vga_nwstm_read_device": (ci, [vp, vp, i64, ci, vp, i64, vp]),
     "vga_nwstm_read": (ci, [u8p, C.c_size_t, vp, u8pp, i16pp]),
+    "vga_hps_layout_for": (ci, [vp, ci, vp]),
+    "vga_hps_block_map": (ci, [vp, ci, vp, ci]),
+    "vga_hps_write_device": (ci, [vp, ci, ci, vp, i64, ci, vp, vp, vp, vp, i64, ci, vp, i64, vp]),
+    "vga_hps_write": (ci, [vp, ci, u8pp, ci, i16p, i16p, i16p, i16pp, ci, u8p]),
+    "vga_hps_parse": (ci, [u8p, C.c_size_t, vp, vp, ci]),
+    "vga_hps_read_device": (ci, [vp, vp, vp, i64, ci, vp, i64, vp]),
+    "vga_hps_read": (ci, [u8p, C.c_size_t, vp, vp, u8pp]),
+    "vga_idsp_layout_for": (ci, [vp, ci, vp]),
+    "vga_idsp_write_device": (ci, [vp, ci, ci, vp, i64, ci, vp, vp, vp, vp, vp, i64, vp]),
+    "vga_idsp_write": (ci, [vp, ci, u8pp, ci, i16p, i16p, i16p, i16p, u8p]),
+    "vga_idsp_parse": (ci, [u8p, C.c_size_t, vp]),
+    "vga_idsp_read_device": (ci, [vp, vp, i64, ci, vp, i64, vp]),
+    "vga_idsp_read": (ci, [u8p, C.c_size_t, vp, u8pp]),
+    "vga_genh_parse": (ci, [u8p, C.c_size_t, vp]),
+    "vga_genh_read_device": (ci, [vp, vp, i64, ci, vp, i64, vp]),
+    "vga_genh_read": (ci, [u8p, C.c_size_t, vp, u8pp]),
     "vga_dsp_parse": (ci, [u8p, C.c_size_t, vp]),
     "vga_dsp_read_device": (ci, [vp, vp, i64, ci, vp, i64, vp]),
     "vga_dsp_read": (ci, [u8p, C.c_size_t, vp, u8pp]),
@@ -342,6 +358,79 @@ class NwInfoC(C.Structure):
                     "seek_table_offset", "seek_entries", "seek_big_endian", "head_block_offset", "head_block_size",
                     "seek_block_offset", "seek_block_size", "data_block_offset", "data_block_size", "audio_data_offset",
                     "audio_data_length", "adpcm_bytes", "file_size")])
+
+
+GC_CONTAINER_MAX_CHANNELS = 255
+_GCM = GC_CONTAINER_MAX_CHANNELS
+
+
+class HpsParamsC(C.Structure):
+    """vga_hps_params"""
+    _fields_ = [(n, C.c_int) for n in ("sample_rate", "sample_count", "looping", "loop_start", "loop_end")]
+
+
+class HpsLayoutC(C.Structure):
+    """vga_hps_layout"""
+    _fields_ = ([(n, C.c_int) for n in ("header_size", "channel_size", "alignment", "alignment_needed")]
+                + [("channel", GcChannelParamsC)]
+                + [(n, C.c_int) for n in ("sample_count", "looping", "loop_start", "loop_end", "channel_adpcm_bytes",
+                                          "block_header_size", "block_count", "loop_block", "file_size")])
+
+
+class HpsBlockC(C.Structure):
+    """vga_hps_block"""
+    _fields_ = [(n, C.c_int) for n in ("offset", "next_offset", "start_sample", "byte_in_index", "channel_size", "written_size",
+                                       "total_size", "end_nibble")]
+
+
+class HpsInfoC(C.Structure):
+    """vga_hps_info"""
+    _fields_ = ([(n, C.c_int) for n in ("sample_rate", "channel_count", "sample_count", "looping", "loop_start")]
+                + [("max_block_size", C.c_int * _GCM), ("end_address", C.c_int * _GCM), ("coefs", (C.c_int16 * 16) * _GCM),
+                   ("gain", C.c_int16 * _GCM), ("start_context", (C.c_int16 * 3) * _GCM),
+                   ("loop_context", (C.c_int16 * 3) * _GCM)]
+                + [(n, C.c_int) for n in ("block_count", "adpcm_bytes")])
+
+
+class HpsBlockInfoC(C.Structure):
+    """vga_hps_block_info"""
+    _fields_ = [(n, C.c_int) for n in ("offset", "next_offset", "size", "final_nibble", "audio_offset", "audio_bytes",
+                                       "out_offset")]
+
+
+class IdspParamsC(C.Structure):
+    """vga_idsp_params"""
+    _fields_ = [(n, C.c_int) for n in ("sample_rate", "sample_count", "looping", "loop_start", "loop_end", "block_size",
+                                       "trim_file")]
+
+
+class IdspLayoutC(C.Structure):
+    """vga_idsp_layout"""
+    _fields_ = ([("alignment_needed", C.c_int), ("channel", GcChannelParamsC)]
+                + [(n, C.c_int) for n in ("channel_sample_count", "channel_adpcm_bytes", "sample_count", "looping", "loop_start",
+                                          "loop_end", "start_addr", "end_addr", "cur_addr", "interleave_size", "header_size",
+                                          "audio_data_size", "file_size")])
+
+
+class IdspInfoC(C.Structure):
+    """vga_idsp_info"""
+    _fields_ = ([(n, C.c_int) for n in ("channel_count", "sample_rate", "sample_count", "loop_start", "loop_end",
+                                        "interleave_size", "header_size", "channel_info_size", "audio_data_offset",
+                                        "audio_data_length", "looping")]
+                + [("channel_sample_count", C.c_int * _GCM), ("channel_looping", C.c_int * _GCM),
+                   ("start_address", C.c_int * _GCM), ("end_address", C.c_int * _GCM), ("coefs", (C.c_int16 * 16) * _GCM),
+                   ("gain", C.c_int16 * _GCM), ("start_context", (C.c_int16 * 3) * _GCM),
+                   ("loop_context", (C.c_int16 * 3) * _GCM)]
+                + [(n, C.c_int) for n in ("interleave", "adpcm_bytes")])
+
+
+class GenhInfoC(C.Structure):
+    """vga_genh_info"""
+    _fields_ = ([(n, C.c_int) for n in ("channel_count", "interleave", "sample_rate", "loop_start", "loop_end", "codec",
+                                        "audio_data_offset", "header_size")]
+                + [("coef_offset", C.c_int * 2), ("interleave_type", C.c_int), ("coef_type", C.c_int),
+                   ("coef_split_offset", C.c_int * 2), ("sample_count", C.c_int), ("looping", C.c_int),
+                   ("coefs", (C.c_int16 * 16) * 2), ("adpcm_bytes", C.c_int)])
 
 
 class HcaInfoC(C.Structure):

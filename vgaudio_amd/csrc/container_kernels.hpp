@@ -76,6 +76,45 @@ __global__ __launch_bounds__(256) void deinterleave_kernel(const uint8_t *__rest
     for (int k = 0; k < G && off + k < output_size; k++) d[k] = within + k < n ? s[k] : 0;
 }
 
+// Interleave(channels, InterleaveSize, outputSize) (Utilities/Interleave.cs:43-78) into the audio region of every
+// image at once (the NW stream and IDSP writers): blockIdx.y is the file, one thread per G-byte granule of the OUTPUT
+// (coalesced stores; the loads are contiguous runs inside one interleave block of one channel).  G divides the
+// interleave and the last block, so a granule never straddles two rows.  Every byte of the region is written: what
+// the reference leaves untouched in its zeroed MemoryStream is written as zero here, so the images need no memset.
+template <int G>
+__global__ __launch_bounds__(256) void interleave_files_kernel(const uint8_t *__restrict__ src, int64_t pitch, int nch,
+                                                               uint32_t input_size, uint32_t interleave, uint32_t output_size,
+                                                               uint8_t *__restrict__ dst, int64_t file_pitch)
+{
+    using T = typename Granule<G>::type;
+    const uint64_t o64 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * G;
+    if (o64 >= (uint64_t)output_size * nch) return;
+    const uint32_t o = (uint32_t)o64;                      // images are < 2 GiB (FileSize is an int)
+    const int f = blockIdx.y;
+    const uint32_t in_blocks = (input_size + interleave - 1) / interleave, out_blocks = (output_size + interleave - 1) / interleave;
+    const uint32_t stride = interleave * nch;
+    uint32_t b = o / stride;
+    if (b > out_blocks - 1) b = out_blocks - 1;            // the (short) last block's rows are packed more tightly
+    const uint32_t r = o - b * stride;
+    const uint32_t cur_out = b == out_blocks - 1 ? output_size - (out_blocks - 1) * interleave : interleave;
+    const uint32_t i = r / cur_out, within = r - i * cur_out;
+    uint32_t n = 0;                                        // bytes of this row segment that come from the channel
+    if (b < in_blocks) {                                   // blocksToCopy = min(inBlockCount, outBlockCount)
+        const uint32_t cur_in = b == in_blocks - 1 ? input_size - (in_blocks - 1) * interleave : interleave;
+        n = cur_in < cur_out ? cur_in : cur_out;
+    }
+    const uint8_t *s = src + (int64_t)(f * nch + (int)i) * pitch + (uint64_t)interleave * b + within;
+    T v;
+    if (within + G <= n) {
+        v = *reinterpret_cast<const T *>(s);
+    } else {
+        uint8_t tmp[G];
+        for (int k = 0; k < G; k++) tmp[k] = within + k < n ? s[k] : 0;
+        memcpy(&v, tmp, G);
+    }
+    *reinterpret_cast<T *>(dst + (int64_t)f * file_pitch + o) = v;
+}
+
 template <class F>
 int pick_granule(uint64_t align, F &&go)
 {
@@ -101,6 +140,27 @@ inline int launch_deinterleave(uint64_t align, const uint8_t *files, int64_t fil
                 constexpr int G = decltype(g)::value;
                 hipLaunchKernelGGL(deinterleave_kernel<G>, dim3((unsigned)(((output_size + G - 1) / G + 255) / 256), nr), dim3(256), 0, s,
                                    files, file_pitch, audio_offset, nch, input_size, interleave, output_size, dst, dst_pitch, r0);
+            }))
+            return rc;
+    }
+    return VGA_OK;
+}
+
+// Interleave for nfiles equally shaped images: file f's channel c is row f*nch+c of src (input_size bytes each),
+// interleaved in blocks of `interleave` bytes into output_size * nch bytes at dst + f * file_pitch; `align` ORs every
+// address, pitch and block size the granule must divide.  One launch per 65535 files.
+inline int launch_interleave_files(uint64_t align, const uint8_t *src, int64_t pitch, int nch, int nfiles, uint32_t input_size,
+                                   uint32_t interleave, uint32_t output_size, uint8_t *dst, int64_t file_pitch, hipStream_t s)
+{
+    const uint64_t total = (uint64_t)output_size * nch;
+    if (total == 0) return VGA_OK;
+    for (int f0 = 0; f0 < nfiles; f0 += kMaxGridY) {
+        const int nf = std::min(nfiles - f0, kMaxGridY);
+        if (int rc = pick_granule(align, [&](auto g) {
+                constexpr int G = decltype(g)::value;
+                hipLaunchKernelGGL(interleave_files_kernel<G>, dim3((unsigned)((total / G + 255) / 256), nf), dim3(256), 0, s,
+                                   src ? src + (int64_t)f0 * nch * pitch : nullptr, pitch, nch, input_size, interleave,
+                                   output_size, dst + (int64_t)f0 * file_pitch, file_pitch);
             }))
             return rc;
     }

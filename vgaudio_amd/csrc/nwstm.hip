@@ -251,49 +251,7 @@ __global__ __launch_bounds__(256) void nw_seek_kernel(const int16_t *__restrict_
     d[1] = (uint8_t)(big ? v : v >> 8);
 }
 
-using container::Granule;
 using container::kMaxGridY;
-using container::pick_granule;
-
-// Interleave(channels, InterleaveSize, AudioDataSize) (Utilities/Interleave.cs:43-78) into the DATA block of every
-// image at once: blockIdx.y is the file, one thread per G-byte granule of the OUTPUT (coalesced stores; the loads are
-// contiguous runs inside one interleave block of one channel).  G divides the interleave and the last block, so a
-// granule never straddles two rows.  Every byte of the region is written: what the reference leaves untouched in its
-// zeroed MemoryStream is written as zero here, so the images need no memset.
-template <int G>
-__global__ __launch_bounds__(256) void nw_interleave_kernel(const uint8_t *__restrict__ src, int64_t pitch, int nch,
-                                                            uint32_t input_size, uint32_t interleave, uint32_t output_size,
-                                                            uint8_t *__restrict__ dst, int64_t file_pitch)
-{
-    using T = typename Granule<G>::type;
-    const uint64_t o64 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * G;
-    if (o64 >= (uint64_t)output_size * nch) return;
-    const uint32_t o = (uint32_t)o64;                      // images are < 2 GiB (FileSize is an int)
-    const int f = blockIdx.y;
-    const uint32_t in_blocks = (input_size + interleave - 1) / interleave, out_blocks = (output_size + interleave - 1) / interleave;
-    const uint32_t stride = interleave * nch;
-    uint32_t b = o / stride;
-    if (b > out_blocks - 1) b = out_blocks - 1;            // the (short) last block's rows are packed more tightly
-    const uint32_t r = o - b * stride;
-    const uint32_t cur_out = b == out_blocks - 1 ? output_size - (out_blocks - 1) * interleave : interleave;
-    const uint32_t i = r / cur_out, within = r - i * cur_out;
-    uint32_t n = 0;                                        // bytes of this row segment that come from the channel
-    if (b < in_blocks) {                                   // blocksToCopy = min(inBlockCount, outBlockCount)
-        const uint32_t cur_in = b == in_blocks - 1 ? input_size - (in_blocks - 1) * interleave : interleave;
-        n = cur_in < cur_out ? cur_in : cur_out;
-    }
-    const uint8_t *s = src + (int64_t)(f * nch + (int)i) * pitch + (uint64_t)interleave * b + within;
-    T v;
-    if (within + G <= n) {
-        v = *reinterpret_cast<const T *>(s);
-    } else {
-        uint8_t tmp[G];
-        for (int k = 0; k < G; k++) tmp[k] = within + k < n ? s[k] : 0;
-        memcpy(&v, tmp, G);
-    }
-    *reinterpret_cast<T *>(dst + (int64_t)f * file_pitch + o) = v;
-}
-
 
 }  // namespace nwstm
 }  // namespace vga
@@ -530,19 +488,8 @@ int vga_nwstm_write_device(const vga_nwstm_params *p, int nch, int nfiles, const
     const uint32_t out_blocks = (out + il - 1) / il, last_out = out - (out_blocks - 1) * il;
     const uint64_t align = (uint64_t)(uintptr_t)d_adpcm | (uint64_t)adpcm_pitch | il | last_out |
                            (uint64_t)(uintptr_t)(d_files + L.audio_data_offset) | (uint64_t)(nfiles > 1 ? file_pitch : 0);
-    const uint64_t total = (uint64_t)out * nch;
-    for (int f0 = 0; f0 < nfiles; f0 += nwstm::kMaxGridY) {
-        const int nf = std::min(nfiles - f0, nwstm::kMaxGridY);
-        if (int rc = nwstm::pick_granule(align, [&](auto g) {
-                constexpr int G = decltype(g)::value;
-                hipLaunchKernelGGL(nwstm::nw_interleave_kernel<G>, dim3((unsigned)((total / G + 255) / 256), nf), dim3(256), 0, s,
-                                   d_adpcm ? d_adpcm + (int64_t)f0 * nch * adpcm_pitch : nullptr, adpcm_pitch, nch,
-                                   (uint32_t)adpcm_len, il, out, d_files + (int64_t)f0 * file_pitch + L.audio_data_offset,
-                                   file_pitch);
-            }))
-            return rc;
-    }
-    return VGA_OK;
+    return container::launch_interleave_files(align, d_adpcm, adpcm_pitch, nch, nfiles, (uint32_t)adpcm_len, il, out,
+                                              d_files + L.audio_data_offset, file_pitch, s);
 }
 
 int vga_nwstm_write(const vga_nwstm_params *p, int nch, const vga_nw_track *tracks, const uint8_t *const *adpcm, int adpcm_len,

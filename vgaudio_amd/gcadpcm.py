@@ -232,6 +232,9 @@ class GcAdpcmChannel:
         self.LoopContextStart = 0
         self.StartContext = GcAdpcmContext(adpcm[0] if len(adpcm) else 0, 0, 0)
         self.Gain = 0
+        # the reference's private Pcm field (GcAdpcmChannel.cs:9,34,51-54): the PCM the channel's builder decoded for a
+        # loop context or seek table, carried through clones, or None.  Only the HPS writer reads it (GetHist1 / GetHist2).
+        self.Pcm = None
 
     @property
     def SampleCount(self):                       # GcAdpcmChannel.cs:11
@@ -268,8 +271,9 @@ def build_channels(channels, looping=False, loopStart=0, loopEnd=0, alignmentMul
     want_ctx = loopContext and L.loop_start_aligned != 0
     if not (L.alignment_needed or want_ctx or L.seek_table_entries or keepPcm):
         out = [GcAdpcmChannel(c.Adpcm, c.Coefs, n) for c in channels]           # nothing to derive
-        for o in out:
+        for o, c in zip(out, channels):
             o.SamplesPerSeekTableEntry = samplesPerSeekTableEntry
+            o.Pcm = c.Pcm
         return out
     src = [np.ascontiguousarray(c.Adpcm, dtype=np.uint8) for c in channels]
     coefs = np.ascontiguousarray(np.stack([c.Coefs for c in channels]), dtype=np.int16)
@@ -292,6 +296,10 @@ def build_channels(channels, looping=False, loopStart=0, loopEnd=0, alignmentMul
         o.SamplesPerSeekTableEntry = samplesPerSeekTableEntry
         o.LoopContext = GcAdpcmContext(*ctx[i].tolist())
         o.LoopContextStart = L.loop_start_aligned
+        # GcAdpcmChannel(builder): b.Pcm when the loop was aligned, else b.AlignedPcm -- the PCM decoded for the loop
+        # context or seek table when the carried field was empty
+        decoded = want_ctx or bool(L.seek_table_entries)
+        o.Pcm = c.Pcm if L.alignment_needed or c.Pcm is not None or not decoded else pcm[i]
         out.append(o)
     return out
 
@@ -347,6 +355,8 @@ class GcAdpcmFormat:
                  samplesPerSeekTableEntry=self.SamplesPerSeekTableEntry, tracks=self.Tracks)
         a.update(kw)
         base = [GcAdpcmChannel(c.Adpcm, c.Coefs, c.UnalignedSampleCount) for c in self.Channels]
+        for b, c in zip(base, self.Channels):
+            b.Pcm = c.Pcm                        # GetCloneBuilder: Pcm = Pcm
         return GcAdpcmFormat(base, **a)
 
     def WithLoop(self, loop, loopStart=None, loopEnd=None):          # AudioFormatBase.WithLoop (:61-63)
