@@ -839,8 +839,13 @@ typedef struct {
 /* host only; never reads past `size`.  Chunk ids are read with their top bits cleared.  VGA_ERR_INVALID_DATA: no HCA
  * signature, a header or frames that run past the end, a negative header size or frame count, frames shorter than
  * their CRC; VGA_ERR_INVALID_OP, naming the chunk, for an unknown chunk (NotSupportedException), and for what the
- * decoder here cannot take: more than 8 (or no) channels, frames outside 8..65535 bytes, more than 128 bands, more than
- * 8 HFR groups, or a comment longer than 255 bytes. */
+ * decoder here cannot take: more than 8 (or no) channels, frames outside 8..65535 bytes (the comp / dec chunks' frame
+ * size is signed 16-bit, so files stop at 32767), a total band count or base + stereo band count above 128, more than 8
+ * HFR groups, or a comment longer than 255 bytes.  A dec chunk with a base band count above the total gives a negative
+ * stereo band count, and comp bands past the total a negative HFR group count; both are kept and decode as in the
+ * reference.  Headers the reference takes but then throws IndexOutOfRangeException on are parsed, and the decode calls
+ * refuse them with VGA_ERR_OUT_OF_RANGE: stereo bands with a track count of 2 or more (fewer channels per track than
+ * channels), or a stereo-secondary channel coding more than 128 bands. */
 int vga_hca_parse(const uint8_t *file, size_t size, vga_hca_file_info *out);
 /* nfiles images that share one parsed geometry -> stream f's frames at d_frames + f*frames_pitch, back to back, the
  * layout vga_hca_decode_device takes: frames_pitch a multiple of 4 and at least frame_count*frame_size + 8 (the 8 bytes

@@ -1091,7 +1091,12 @@ int vgo_hca_encode(const int16_t *pcm, long pitch, const vgo_hca_params *c, vgo_
 }
 
 /* ------------------------------------------------------------------ decoder */
-/* CriHcaPacking.cs:185-211 */
+/* The reference's arrays hold 128 scale factors / resolutions / spectra and 8 HFR scales; where it indexes past them it
+ * throws IndexOutOfRangeException.  HCA_OUT_OF_RANGE stands for that throw. */
+#define HCA_OUT_OF_RANGE (-6)
+
+/* CriHcaPacking.cs:185-211.  1; 0 (a value out of range: UnpackFrameHeader returns false); HCA_OUT_OF_RANGE (output[i],
+ * i >= 128) */
 static int delta_decode(bit_reader *r, int delta_bits, int data_bits, int count, int *output)
 {
     output[0] = br_read(r, data_bits);
@@ -1101,9 +1106,11 @@ static int delta_decode(bit_reader *r, int delta_bits, int data_bits, int count,
         int delta = br_read_offset_binary_positive(r, delta_bits);
         if (delta < max_delta) {
             int value = output[i - 1] + delta;
-            if (value < 0 || value > max_value) return 0;
+            if (value < 0 || value > max_value) return 0;             /* checked before the store (:193-196) */
+            if (i >= SPSF) return HCA_OUT_OF_RANGE;                    /* output[i] = value (:197) */
             output[i] = value;
         } else {
+            if (i >= SPSF) return HCA_OUT_OF_RANGE;                    /* output[i] = ReadInt (:201) */
             output[i] = br_read(r, data_bits);
         }
     }
@@ -1119,13 +1126,16 @@ static int read_scale_factors(hca_channel *ch, bit_reader *r)
         return 1;
     }
     if (ch->sf_delta_bits >= 6) {
-        for (int i = 0; i < ch->coded_sf_count; i++) ch->scale_factors[i] = br_read(r, 6);
+        for (int i = 0; i < ch->coded_sf_count; i++) {
+            if (i >= SPSF) return HCA_OUT_OF_RANGE;                    /* ScaleFactors[i] (:122) */
+            ch->scale_factors[i] = br_read(r, 6);
+        }
         return 1;
     }
     return delta_decode(r, ch->sf_delta_bits, 6, ch->coded_sf_count, ch->scale_factors);
 }
 
-/* CriHcaPacking.cs:10-15, :71-183, :213-229.  -3: InvalidDataException("Invalid frame header") */
+/* CriHcaPacking.cs:10-15, :71-183, :213-229.  -3: InvalidDataException("Invalid frame header"); HCA_OUT_OF_RANGE */
 static int unpack_frame(hca_frame *f, bit_reader *r)
 {
     int sync = br_read(r, 16);
@@ -1134,15 +1144,22 @@ static int unpack_frame(hca_frame *f, bit_reader *r)
     f->evaluation_boundary = br_read(r, 7);
     for (int c = 0; c < f->nch; c++) {
         hca_channel *ch = &f->ch[c];
-        if (!read_scale_factors(ch, r)) return 1;                     /* UnpackFrameHeader returns false */
+        const int ok = read_scale_factors(ch, r);
+        if (ok < 0) return ok;
+        if (!ok) return 1;                                            /* UnpackFrameHeader returns false */
         for (int i = 0; i < f->evaluation_boundary; i++)
             ch->resolution[i] = calculate_resolution(ch->scale_factors[i], f->ath_curve[i] + f->acceptable_noise_level - 1);
-        for (int i = f->evaluation_boundary; i < ch->coded_sf_count; i++)
+        for (int i = f->evaluation_boundary; i < ch->coded_sf_count; i++) {
+            if (i >= SPSF) return HCA_OUT_OF_RANGE;                    /* Resolution[i], ScaleFactors[i] (:92-95) */
             ch->resolution[i] = calculate_resolution(ch->scale_factors[i], f->ath_curve[i] + f->acceptable_noise_level);
+        }
         if (ch->type == CH_STEREO_SECONDARY) {
             for (int i = 0; i < SUBFRAMES; i++) ch->intensity[i] = br_read(r, 4);
         } else if (f->hca.hfr_group_count > 0) {
-            for (int i = 0; i < f->hca.hfr_group_count; i++) ch->hfr_scales[i] = br_read(r, 6);
+            for (int i = 0; i < f->hca.hfr_group_count; i++) {
+                if (i >= 8) return HCA_OUT_OF_RANGE;                   /* HfrScales[i] (:138-144) */
+                ch->hfr_scales[i] = br_read(r, 6);
+            }
         }
     }
     /* ReadSpectralCoefficients :148-183 */
@@ -1246,6 +1263,7 @@ static int decode_frame(hca_frame *f, const uint8_t *audio, int16_t *const *pcm_
                 for (int i = 0; i < h->bands_per_hfr_group && band < hfr_band_count; band++, i++) {
                     int high_band = hfr_start_band + band;
                     int low_band = hfr_start_band - band - 1;
+                    if (low_band < 0 || high_band >= SPSF) return HCA_OUT_OF_RANGE;   /* ScaleFactors[lowBand], Spectra[sf][highBand] (:136-140) */
                     int index = ch->hfr_scales[group] - ch->scale_factors[low_band] + 64;
                     for (int sf = 0; sf < SUBFRAMES; sf++)
                         ch->spectra[sf][high_band] = T_ScaleConversion[index & 127] * ch->spectra[sf][low_band];
@@ -1261,9 +1279,11 @@ static int decode_frame(hca_frame *f, const uint8_t *audio, int16_t *const *pcm_
                 double *l = f->ch[c].spectra[sf];
                 double *r2 = f->ch[c + 1].spectra[sf];
                 int iq = f->ch[c + 1].intensity[sf];
-                double ratio_l = T_IntensityRatio[iq < 15 ? iq : 14];
+                if (iq >= 15) return HCA_OUT_OF_RANGE;                 /* IntensityRatioTable has 15 entries (:157) */
+                double ratio_l = T_IntensityRatio[iq];
                 double ratio_r = ratio_l - 2.0;
                 for (int b = h->base_band_count; b < h->total_band_count; b++) {
+                    if (b >= SPSF) return HCA_OUT_OF_RANGE;            /* r[b] (:161) */
                     r2[b] = l[b] * ratio_r;
                     l[b] *= ratio_l;
                 }
@@ -1290,7 +1310,12 @@ int vgo_hca_decode(const vgo_hca_info *h, const uint8_t *frames, int16_t *pcm_ou
     ensure_tables();
     pthread_once(&g_scale_once, init_scale);
     const int nch = h->channel_count;
-    if (nch < 1 || nch > 8) return -2;
+    if (nch < 1 || nch > 8 || h->track_count < 1) return -2;
+    /* GetChannelTypes returns channelsPerTrack entries and new CriHcaFrame indexes them for every channel
+     * (CriHcaFrame.cs:20-29, :36-51): with stereo bands and fewer channels per track than channels it throws before the
+     * first frame */
+    const int cpt = nch / h->track_count;
+    if (h->stereo_band_count != 0 && cpt != 1 && cpt < nch) return HCA_OUT_OF_RANGE;
     hca_frame *f = frame_new(h);
     int16_t *buf[8];
     for (int c = 0; c < nch; c++) {

@@ -191,7 +191,10 @@ int vgo_hca_encoder_init(const vgo_hca_params *c, vgo_hca_info *h, int *post_sam
 /* CriHcaFormat.EncodeFromPcm16 (Formats/CriHca/CriHcaFormat.cs:34-84): pcm planar (channel c at
  * pcm + c*pitch); frames_out = frame_count*frame_size bytes.  0, -2, -3 (InvalidData: bitrate too low) */
 int vgo_hca_encode(const int16_t *pcm, long pitch, const vgo_hca_params *c, vgo_hca_info *info_out, uint8_t *frames_out);
-/* CriHcaDecoder.Decode (CriHcaDecoder.cs:11-45): pcm_out planar, sample_count samples per channel */
+/* CriHcaDecoder.Decode (CriHcaDecoder.cs:11-45): pcm_out planar, sample_count samples per channel.  0; -2 (no or more than
+ * 8 channels, track count below 1); -3 (InvalidData: a bad sync word); -6 (IndexOutOfRangeException: intensity 15, more
+ * than 128 coded bands or 8 HFR groups, HFR or stereo bands past 128, too few channels per track for the channel
+ * types) -- at the frame where the reference throws; the PCM of the frames before it is kept */
 int vgo_hca_decode(const vgo_hca_info *h, const uint8_t *frames, int16_t *pcm_out, long pitch);
 int vgo_hca_encode_batch(const int16_t *pcm, long stream_pitch, long ch_pitch, int nstreams, const vgo_hca_params *p,
                          uint8_t *frames, long frames_pitch, int threads);

@@ -950,6 +950,13 @@ def _read_scale_factors(ch, r):                                # :110-127, Delta
     return True
 
 
+def _index(i, length):
+    """A C# array access: a negative index throws IndexOutOfRangeException, which Python would read from the end."""
+    if not 0 <= i < length:
+        raise IndexError(f"index {i} outside an array of {length}")
+    return i
+
+
 def decode_frame(audio, frame):
     """CriHcaDecoder.DecodeFrame (:72-81): returns [channels][1024] shorts."""
     t = Tables.get()
@@ -974,6 +981,7 @@ def decode_frame(audio, frame):
                 i = 0
                 while i < h.bands_per_hfr_group and band < hfr_bands:
                     hi, lo = start + band, start - band - 1
+                    _index(lo, SUB)                            # ScaleFactors[lowBand], Spectra[sf][lowBand] (:137-140)
                     index = ch.hfr_scales[group] - ch.scale_factors[lo] + 64
                     for sf in range(SUBFRAMES):
                         ch.spectra[sf][hi] = t.scale_conversion[index] * ch.spectra[sf][lo]

@@ -90,7 +90,7 @@ int emu_hca_scan(const DeviceInfo *info, const uint8_t *stream, int64_t pitch, u
         Res res{};
         Out out{records + (size_t)f * lay.record_bytes};
         ScanParams P{info->nch, info->frame_size * 8, (int)(a0 & 3) * 8, info->hfr_group_count, info->coded_count,
-                     info->channel_type, info->ath_curve, lay.wide_offsets};
+                     info->channel_type, info->ath_curve, lay.wide_offsets, info->stereo_band_count > 0};
         all |= scan_frame(P, src, ring, res, out, tab);
         if (out.at > lay.record_bytes) return -1;
     }

@@ -186,35 +186,56 @@ def _device_info_words(info):
     return np.frombuffer(bytes(out), np.int32, 27)
 
 
-def test_decode_of_garbage_frames_reads_zeros_past_the_end_like_the_reference():
+def test_decode_of_garbage_frames_reads_zeros_past_the_end_and_refuses_intensity_15():
     """Random bits behind a valid header (raw 6-bit scale factors, so that delta decoding cannot fail) make the decoder
     walk far past the frame's end, where BitReader.PeekInt yields zeros (BitReader.cs:55-61); the scan's chunk offsets
-    then point past the frame.  PCM must still equal the oracle's, for every frame alignment."""
+    then point past the frame.  A random secondary intensity of 15 throws IndexOutOfRangeException in the reference
+    (CriHcaDecoder.cs:157): the decoder then refuses the call as the oracle does; with every 15 lowered to 14 the same
+    frames decode to the oracle's PCM, for every frame alignment."""
+    from vgaudio_amd import _lib
     rng = np.random.default_rng(11)
     n = 1024 * 40 + 300
+    refused = 0
     for nch, quality, bitrate in ((2, "High", 0), (1, "Lowest", 0), (2, "Lowest", 0), (2, "High", 48047), (4, "Middle", 0)):
         pcm = synth.generate(nch, n)
         rc, info, frames = po.hca_encode(pcm, po.hca_params(nch, n, quality=quality, bitrate=bitrate))
         assert rc == 0
         words = _device_info_words(info)
         fr = np.array(frames, np.uint8).reshape(info.frame_count, info.frame_size)
+        fr14 = fr.copy()
         for f in range(1, info.frame_count, 2):
             bits = rng.integers(0, 2, info.frame_size * 8).astype(np.uint8)
             bits[:16] = 1
             pos = 32
+            intensities = []                                        # bit positions of the secondaries' intensities
             for c in range(nch):
                 bits[pos:pos + 3] = (1, 1, int(rng.integers(0, 2)))
                 pos += 3 + 6 * int(words[19 + c])
+                if words[11 + c] == 2:
+                    intensities += [pos + 4 * i for i in range(8)]
                 pos += 32 if words[11 + c] == 2 else 6 * info.hfr_group_count
             if f % 3 == 0:
                 bits[info.frame_size * 4:] = 1
             fr[f] = np.packbits(bits)
-        rc, want = po.hca_decode(info, fr.reshape(-1))
-        assert rc == 0
+            for p in intensities:
+                if bits[p:p + 4].all():
+                    bits[p + 3] = 0                                 # 15 -> 14
+            fr14[f] = np.packbits(bits)
         fmt = CriHcaFormat().EncodeFromPcm16(Pcm16Format(list(pcm), 48000), CriHcaParameters(Quality=Q[quality], Bitrate=bitrate))
-        got = CriHcaDecoder.Decode(fmt.Hca, [fr, fr[::1].copy()])
+        rc, want = po.hca_decode(info, fr.reshape(-1))
+        assert rc in (0, -6)
+        if rc == -6:
+            refused += 1
+            with pytest.raises(_lib.ArgumentOutOfRangeError):
+                CriHcaDecoder.Decode(fmt.Hca, [fr14, fr])
+        else:
+            assert np.array_equal(fr, fr14)
+        rc, want = po.hca_decode(info, fr14.reshape(-1))
+        assert rc == 0
+        got = CriHcaDecoder.Decode(fmt.Hca, [fr14, fr14[::1].copy()])
         for d in got:
             assert np.array_equal(np.stack(d), np.asarray(want).reshape(nch, n)), (nch, quality, bitrate)
+    assert refused > 0
 
 
 def test_long_streams_carry_the_overlap_across_frame_runs():

@@ -44,8 +44,9 @@ def device_info(info):
     return out
 
 
-def emu_decode(emu, info, frames, frames_per_group, shift=0):
-    """frames: uint8 [frame_count * frame_size]; returns (flags, pcm [nch, sample_count])"""
+def emu_decode(emu, info, frames, frames_per_group, shift=0, allow_flags=False):
+    """frames: uint8 [frame_count * frame_size]; returns (flags, pcm [nch, sample_count]); with allow_flags a scan that
+    flags a frame returns (flags, None)"""
     d = device_info(info)
     fbytes = info.frame_count * info.frame_size
     pitch = (fbytes + 8 + 15) // 16 * 16
@@ -56,6 +57,8 @@ def emu_decode(emu, info, frames, frames_per_group, shift=0):
     u8p = C.POINTER(C.c_uint8)
     flags = emu.emu_hca_scan(d, stream.ctypes.data_as(u8p), pitch, records.ctypes.data_as(u8p))
     assert flags >= 0
+    if flags and allow_flags:
+        return flags, None
     n = info.sample_count
     pcm = np.zeros((info.channel_count, max(n, 1)), np.int16)
     rc = emu.emu_hca_frames(d, stream.ctypes.data_as(u8p), pitch, records.ctypes.data_as(u8p),
@@ -91,34 +94,53 @@ def test_emulated_kernels_match_the_oracle(emu, nch, quality, n, bitrate, group)
     assert np.array_equal(got, np.asarray(want).reshape(nch, n))
 
 
-def test_garbage_frames_read_zeros_past_the_end_like_the_reference(emu):
+def test_garbage_frames_read_zeros_past_the_end_and_flag_intensity_15(emu):
     """Frames that are random bits after a valid header walk far past the frame's end (BitReader.PeekInt then yields
-    zeros, BitReader.cs:55-61); scale factors are sent raw (delta bits 6/7) so that delta decoding cannot fail."""
+    zeros, BitReader.cs:55-61); scale factors are sent raw (delta bits 6/7) so that delta decoding cannot fail.  A random
+    secondary intensity of 15 throws IndexOutOfRangeException in the reference (CriHcaDecoder.cs:157): the scan flags it
+    (bit 32) where the oracle refuses; with every 15 lowered to 14 the same frames decode to the oracle's PCM."""
     rng = np.random.default_rng(5)
     n = 1024 * 6
+    flagged = 0
     for nch, quality in ((2, "High"), (1, "Lowest"), (2, "Lowest")):
         pcm = _signal(nch, n, 3)
         rc, info, frames = po.hca_encode(pcm, po.hca_params(nch, n, quality=quality))
         assert rc == 0
         fr = np.array(frames, np.uint8).reshape(info.frame_count, info.frame_size)
+        fr14 = fr.copy()
         dinfo = np.frombuffer(bytes(device_info(info)), np.int32, 27)      # [11:19] channel types, [19:27] coded counts
         for f in range(1, info.frame_count):
             bits = rng.integers(0, 2, info.frame_size * 8).astype(np.uint8)
             bits[:16] = 1                                           # sync word
             pos = 32
+            intensities = []                                        # bit positions of the secondaries' intensities
             for c in range(nch):                                    # raw 6-bit scale factors for every channel
                 bits[pos:pos + 3] = (1, 1, int(rng.integers(0, 2)))
                 pos += 3 + 6 * int(dinfo[19 + c])
+                if dinfo[11 + c] == 2:
+                    intensities += [pos + 4 * i for i in range(8)]
                 pos += 32 if dinfo[11 + c] == 2 else 6 * info.hfr_group_count      # intensity / HFR scales
             if f % 3 == 0:
                 bits[info.frame_size * 4:] = 1                      # long codes at the end: far past the frame
             fr[f] = np.packbits(bits)
+            for p in intensities:
+                if bits[p:p + 4].all():
+                    bits[p + 3] = 0                                 # 15 -> 14
+            fr14[f] = np.packbits(bits)
         rc, want = po.hca_decode(info, fr.reshape(-1))
+        assert rc in (0, -6)
+        if rc == -6:
+            flagged += 1
+            assert emu_decode(emu, info, fr.reshape(-1), 1, allow_flags=True)[0] == 32
+        else:
+            assert np.array_equal(fr, fr14)
+        rc, want = po.hca_decode(info, fr14.reshape(-1))
         assert rc == 0
         for group in (1, 4):
-            flags, got = emu_decode(emu, info, fr.reshape(-1), group)
+            flags, got = emu_decode(emu, info, fr14.reshape(-1), group)
             assert flags == 0
             assert np.array_equal(got, np.asarray(want).reshape(nch, n)), (nch, quality, group)
+    assert flagged > 0
 
 
 def test_dct_lane_decomposition_is_bit_exact(emu):

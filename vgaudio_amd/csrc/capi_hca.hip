@@ -99,15 +99,26 @@ void channel_types(const vga_hca_info &h, int types[8])
     if (src) for (int i = 0; i < cpt; i++) types[i] = src[i];
 }
 
+// A negative StereoBandCount (a dec chunk whose base band count exceeds the total, HcaReader.cs:179-186) and a negative
+// HfrGroupCount (comp bands beyond the total, HcaInfo.CalculateHfrValues) decode in the reference: ApplyIntensityStereo
+// and the HFR scales need counts above 0 (CriHcaDecoder.cs:119, :149; CriHcaPacking.cs:101), as the kernels do.  What
+// it indexes past its arrays for is VGA_ERR_OUT_OF_RANGE (IndexOutOfRangeException), refused before any frame.
 int make_device_info(const vga_hca_info &h, hca::DeviceInfo &d)
 {
     if (h.channel_count < 1 || h.channel_count > 8 || h.frame_size < 8 || h.frame_size > 0xFFFF || h.frame_count < 0 ||
-        h.total_band_count < 0 || h.total_band_count > 128 || h.base_band_count < 0 || h.stereo_band_count < 0 ||
-        h.base_band_count + h.stereo_band_count > 128 || h.hfr_group_count < 0 || h.hfr_group_count > 8 ||
+        h.total_band_count < 0 || h.total_band_count > 128 || h.base_band_count < 0 || h.hfr_group_count > 8 ||
         (h.hfr_group_count > 0 && h.bands_per_hfr_group <= 0)) {
         set_error("HcaInfo is inconsistent (channels %d, frame size %d, bands %d/%d/%d, hfr groups %d)", h.channel_count,
                   h.frame_size, h.total_band_count, h.base_band_count, h.stereo_band_count, h.hfr_group_count);
         return VGA_ERR_ARGUMENT;
+    }
+    // GetChannelTypes returns channelsPerTrack entries and new CriHcaFrame indexes them for every channel
+    // (CriHcaFrame.cs:20-29, :36-51): with stereo bands and more than one track it throws before the first frame
+    const int cpt = h.channel_count / (h.track_count > 0 ? h.track_count : 1);
+    if (h.stereo_band_count != 0 && cpt != 1 && cpt < h.channel_count) {
+        set_error("Index was outside the bounds of the array (%d channels, %d per track, stereo bands %d)", h.channel_count, cpt,
+                  h.stereo_band_count);
+        return VGA_ERR_OUT_OF_RANGE;
     }
     memset(&d, 0, sizeof d);
     d.nch = h.channel_count;
@@ -127,6 +138,15 @@ int make_device_info(const vga_hca_info &h, hca::DeviceInfo &d)
         d.channel_type[i] = types[i];
         d.coded_count[i] = types[i] == hca::CH_STEREO_SECONDARY ? h.base_band_count
                                                                  : h.base_band_count + h.stereo_band_count;
+        if (i >= h.channel_count) continue;
+        if (d.coded_count[i] < 0) {
+            set_error("HcaInfo is inconsistent (channel %d codes %d bands)", i, d.coded_count[i]);
+            return VGA_ERR_ARGUMENT;
+        }
+        if (d.coded_count[i] > 128) {                           // ScaleFactors / Resolution[i] (CriHcaPacking.cs:89-95, :120-122)
+            set_error("Index was outside the bounds of the array (channel %d codes %d bands)", i, d.coded_count[i]);
+            return VGA_ERR_OUT_OF_RANGE;
+        }
     }
     if (h.use_ath_curve) {                                     // CriHcaFrame.ScaleAthCurve :60-83
         int acc = 0, i;
@@ -195,6 +215,9 @@ int status_to_error(int status)
     if (status & 4) { set_error("Bitrate is set too low."); return VGA_ERR_INVALID_DATA; }     // CriHcaEncoder.cs:471
     if (status & 8) { set_error("evaluation boundary search failed (NotImplementedException in the reference)"); return VGA_ERR_INVALID_OP; }
     if (status & 1) { set_error("Invalid frame header"); return VGA_ERR_INVALID_DATA; }        // CriHcaPacking.cs:76
+    // (hca_decode_core.hpp scan_frame) a frame whose secondary channel carries intensity 15: IntensityRatioTable has 15
+    // entries (CriHcaDecoder.cs:157).  A batch that also holds a bad sync word reports that, whichever frame comes first.
+    if (status & 32) { set_error("Index was outside the bounds of the array (intensity 15)"); return VGA_ERR_OUT_OF_RANGE; }
     if (status & 2) { set_error("scale-factor delta out of range (frame state would be stale in the reference)"); return VGA_ERR_INVALID_DATA; }
     return VGA_OK;
 }

@@ -155,7 +155,8 @@ struct BeReader {
 
 int invalid(const char *msg) { set_error("%s", msg); return VGA_ERR_INVALID_DATA; }
 int64_t next_multiple(int64_t v, int64_t m) { return m <= 0 || v % m == 0 ? v : v + m - v % m; }   // Helpers.cs:71-80
-int div_round_up(int v, int d) { return v / d + (v % d != 0 ? 1 : 0); }                          // Extensions.cs:145
+// Extensions.cs:145, (int)Math.Ceiling((double)v / d): a negative quotient rounds towards zero (-1 / 8 -> 0)
+int div_round_up(int v, int d) { return v / d + (v % d != 0 && (v < 0) == (d < 0) ? 1 : 0); }
 
 // the general de-interleave for nfiles images (Interleave.cs:118-167)
 int deinterleave(const uint8_t *d_files, int64_t file_pitch, int nfiles, int audio_offset, int nch, uint32_t in, uint32_t il,
@@ -524,9 +525,11 @@ int vga_hca_parse(const uint8_t *file, size_t size, vga_hca_file_info *out)
     if (H.frame_count > 0 && H.frame_size < 2) return invalid("frames shorter than their CRC");
     if ((int64_t)size - header_size < (int64_t)H.frame_count * std::max(H.frame_size, 0)) return invalid("file ends inside the frames");
     if (too_long_comment) { set_error("comment longer than 255 bytes"); return VGA_ERR_INVALID_OP; }
+    // A negative stereo band count (dec chunk, base > total) or HFR group count (comp bands past the total) decodes in the
+    // reference and is kept; a secondary channel's base band count above 128 is refused by the decoder
+    // (VGA_ERR_OUT_OF_RANGE, where the reference throws), as are stereo bands with more than one track.
     if (H.channel_count < 1 || H.channel_count > 8 || H.frame_size < 8 || H.frame_size > 0xFFFF || H.total_band_count > 128 ||
-        H.base_band_count < 0 || H.stereo_band_count < 0 || H.base_band_count + H.stereo_band_count > 128 || H.hfr_group_count < 0 ||
-        H.hfr_group_count > 8) {
+        H.base_band_count < 0 || H.base_band_count + H.stereo_band_count > 128 || H.hfr_group_count > 8) {
         set_error("HCA stream the decoder cannot take (channels %d, frame size %d, bands %d/%d/%d, hfr groups %d)", H.channel_count,
                   H.frame_size, H.total_band_count, H.base_band_count, H.stereo_band_count, H.hfr_group_count);
         return VGA_ERR_INVALID_OP;

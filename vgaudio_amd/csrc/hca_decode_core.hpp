@@ -191,6 +191,7 @@ struct ScanParams {
     const int *channel_type;           // [nch]
     const uint8_t *ath_curve;          // [128]
     int wide_offsets;
+    int intensity_used;                // StereoBandCount > 0: ApplyIntensityStereo reads the secondaries' intensities
 };
 
 template <class Src, class Ring>
@@ -280,7 +281,9 @@ struct OffsetPacker {
 };
 
 // Returns the frame's flags (bit 0: bad sync word, bit 1: scale-factor delta decoding failed -- the reference then keeps
-// the previous frame's state, which a frame-parallel decoder cannot reproduce: the caller reports it).
+// the previous frame's state, which a frame-parallel decoder cannot reproduce: the caller reports it; bit 5: an intensity
+// of 15 that ApplyIntensityStereo looks up in its 15-entry table, IndexOutOfRangeException in the reference,
+// CriHcaDecoder.cs:157 -- only while no earlier channel of the frame failed, since UnpackFrameHeader stops there).
 template <class Src, class Ring, class Res, class Out, class Tab>
 VGA_HD int scan_frame(const ScanParams &P, Src &src, Ring &ring, Res &res, Out &out, const Tab &tab)
 {
@@ -342,7 +345,13 @@ VGA_HD int scan_frame(const ScanParams &P, Src &src, Ring &ring, Res &res, Out &
         uint32_t aux[4] = {0, 0, 0, 0};
         r.service();
         if (P.channel_type[c] == 2 /* StereoSecondary */) {
-            for (int i = 0; i < 8; i++) aux[i >> 2] |= (uint32_t)r.read(4) << (8 * (i & 3));
+            bool fifteen = false;
+            for (int i = 0; i < 8; i++) {
+                const int iq = r.read(4);
+                fifteen |= iq == 15;
+                aux[i >> 2] |= (uint32_t)iq << (8 * (i & 3));
+            }
+            if (fifteen && P.intensity_used && !(flags & 2)) flags |= 32;
         } else if (P.hfr_group_count > 0) {
             for (int i = 0; i < P.hfr_group_count; i++) aux[2 + (i >> 2)] |= (uint32_t)r.read(6) << (8 * (i & 3));
         }

@@ -22,7 +22,8 @@
 // A frame whose scale-factor delta decoding fails keeps stale state in the reference
 // (UnpackFrameHeader returns false, CriHcaPacking.cs:84); that is sequential state a frame-parallel
 // decoder cannot reproduce -- such frames (corrupt streams only) are flagged in *status (bit 1), an
-// invalid sync word in bit 0 (the reference throws InvalidDataException).
+// invalid sync word in bit 0 (the reference throws InvalidDataException), an intensity of 15 in bit 5 (the reference
+// throws IndexOutOfRangeException; the frames kernel's min(iq, 14) only keeps the table read inside the table).
 #include "common.hpp"
 #include "hca_device.hpp"
 #include "hca_decode_core.hpp"
@@ -160,6 +161,7 @@ __global__ __launch_bounds__(64) void hca_scan_kernel(const uint8_t *__restrict_
     P.channel_type = s_type;
     P.ath_curve = s_ath;
     P.wide_offsets = lay.wide_offsets;
+    P.intensity_used = info.stereo_band_count > 0;
     const int flags = scan_frame(P, src, ring, res, out, T);
     out.finish();
     if (live && flags && status) atomicOr(status, flags);
