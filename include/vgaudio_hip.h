@@ -7,7 +7,11 @@
  * caller owns (and, from C#, pins) every buffer, the callee keeps no pointer
  * past return.  All exports are thread-safe and re-entrant: host-buffer
  * entry points create and destroy their own HIP stream; *_device entry points
- * run on the caller's stream and never synchronise it.
+ * run on the caller's stream and never synchronise it (scratch, where a call
+ * needs any, is allocated and freed in stream order on that stream).  The
+ * exceptions return a host value and so synchronise the caller's stream:
+ * vga_adx_find_key_device, vga_hca_find_key_device and
+ * vga_hca_byte_position_counts_device.
  *
  * Errors: the reference throws .NET exceptions; here every fallible function
  * returns an int status that the managed shim maps back:
@@ -900,7 +904,8 @@ int vga_adx_crypt(uint8_t *const *audio, int audio_len, int nch, const vga_adx_k
                   int frame_size);
 int vga_adx_crypt_device(uint8_t *d_audio, int64_t audio_pitch, int audio_len, int nch, const vga_adx_key *key,
                          int encryption_type, int frame_size, void *stream);
-/* FindKey over `keys` (host array): *index_out = first candidate every frame header agrees with, or -1 */
+/* FindKey over `keys` (host array): *index_out = first candidate every frame header agrees with, or -1.
+ * Returns a host value: synchronises the caller's stream. */
 int vga_adx_find_key_device(const uint8_t *d_audio, int64_t audio_pitch, int audio_len, int nch, int encryption_type,
                             int frame_size, const vga_adx_key *keys, int nkeys, int *index_out, void *stream);
 /* The brute-force key search of the reference's `crackadx` tool for one file (VGAudio.Tools/CrackAdx/GuessAdx.cs:118-218:
@@ -924,12 +929,13 @@ int vga_hca_crypt_device(uint8_t *d_frames, int64_t frames_pitch, int nstreams, 
  * (CriHcaPacking.UnpackFrame), or -1.  VGA_ERR_INVALID_DATA: a frame's sync word is wrong (InvalidDataException). */
 int vga_hca_find_key(const vga_hca_info *info, const uint8_t *frames, int frame_count, const uint8_t *decryption_tables,
                      int nkeys, int *index_out);
+/* device-resident frames; returns a host value: synchronises the caller's stream */
 int vga_hca_find_key_device(const vga_hca_info *info, const uint8_t *d_frames, int frame_count,
                             const uint8_t *decryption_tables, int nkeys, int *index_out, void *stream);
 /* The statistics the reference's `crackhca` analysis starts from (VGAudio.Tools/CrackHca/Crack.cs:43-80): how often each
  * byte value occurs at each of the first `positions` (<= 64; the tool uses 30) bytes of the frames.  counts_out:
  * positions x 256 uint32 in host memory.  The table solver that follows (Solver.cs, Table.cs) is interactive analysis
- * on those 30 x 256 numbers and stays with the tool. */
+ * on those 30 x 256 numbers and stays with the tool.  Returns host counts: synchronises the caller's stream. */
 int vga_hca_byte_position_counts_device(const uint8_t *d_frames, int64_t frames_pitch, int nstreams, int frame_count,
                                         int frame_size, int positions, uint32_t *counts_out, void *stream);
 

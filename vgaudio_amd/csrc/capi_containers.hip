@@ -234,9 +234,8 @@ int vga_hca_write_device(const vga_hca_info *h, const uint8_t *d_frames, int64_t
     std::vector<uint8_t> header((size_t)h->header_size);
     if (int rc = vga_hca_file_header(h, comment, volume, encryption_type, encrypted_ids, header.data())) return rc;
     hipStream_t s = (hipStream_t)stream;
-    // the header goes into image 0 straight from the host, the other images copy it on the device
-    VGA_HIP_TRY(hipMemcpyAsync(d_files, header.data(), header.size(), hipMemcpyHostToDevice, s));
-    VGA_HIP_TRY(hipStreamSynchronize(s));                   // `header` is pageable and dies with this frame
+    // the header goes into image 0 as kernel arguments, the other images copy it on the device
+    if (int rc = container::upload_bytes(header.data(), h->header_size, d_files, s)) return rc;
     if (nstreams > 1)
         if (int rc = container::launch_replicate(d_files, h->header_size, d_files + file_pitch, file_pitch, nstreams - 1, s)) return rc;
     if (audio > 0)                                          // WriteData (:173-179): the frames, back to back
@@ -491,8 +490,7 @@ int vga_wave_write_pcm16_device(const int16_t *d_pcm, int64_t pcm_pitch, int nch
     const int hs = wave_header_size(p, nch);
     wave_header(p, nch, size, header);
     hipStream_t s = (hipStream_t)stream;
-    VGA_HIP_TRY(hipMemcpyAsync(d_file, header, (size_t)hs, hipMemcpyHostToDevice, s));
-    VGA_HIP_TRY(hipStreamSynchronize(s));                   // `header` lives on this stack frame
+    if (int rc = container::upload_bytes(header, hs, d_file, s)) return rc;
     return container::launch_pcm16_interleave(d_pcm, pcm_pitch, p->sample_count, nch, d_file + hs, s);
 }
 

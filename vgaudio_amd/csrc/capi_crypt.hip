@@ -326,12 +326,8 @@ int vga_hca_crypt_device(uint8_t *d_frames, int64_t frames_pitch, int nstreams, 
     const uint16_t *pow = nullptr;
     if (int rc = hca::crc_pow_table(&pow)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    DevBuf d_table;
-    VGA_HIP_TRY(d_table.alloc(256));
-    VGA_HIP_TRY(hipMemcpyAsync(d_table.p, table, 256, hipMemcpyHostToDevice, s));
-    if (int rc = crypt::launch_hca_crypt(d_frames, frames_pitch, nstreams, frame_count, frame_size, d_table.as<uint8_t>(), pow, s)) return rc;
-    VGA_HIP_TRY(hipStreamSynchronize(s));                               // d_table is freed on return
-    return VGA_OK;
+    // the table travels by value as a kernel argument: nothing to stage, nothing to wait for
+    return crypt::launch_hca_crypt(d_frames, frames_pitch, nstreams, frame_count, frame_size, table, pow, s);
 }
 
 int vga_hca_crypt(uint8_t *frames, int frame_count, int frame_size, const uint8_t *table)

@@ -3,10 +3,47 @@
 #include "common.hpp"
 
 #include <algorithm>
+#include <cstring>
 #include <type_traits>
 
 namespace vga {
 namespace container {
+
+// Host tables and headers reach the device as kernel arguments, in stream order: no staging copy from pageable memory, no
+// wait for the stream, and nothing to keep alive after the launch (the *_device entry points never synchronise).  A launch
+// carries N elements of T (at most a few KiB of arguments); longer tables take several launches.
+template <class T, int N> struct TableChunk { T v[N]; };
+template <class T, int N>
+__global__ __launch_bounds__(256) void table_upload_kernel(TableChunk<T, N> c, int n, T *__restrict__ dst)
+{
+    for (int i = threadIdx.x; i < n; i += 256) dst[i] = c.v[i];
+}
+
+// host[0 .. n) -> dst[0 .. n) on stream s (dst: device memory at T's alignment)
+template <class T, int N = 64>
+int upload_to(const T *host, int n, T *dst, hipStream_t s)
+{
+    static_assert(sizeof(TableChunk<T, N>) <= 2048, "a chunk must stay well under the 4 KiB kernel-argument limit");
+    for (int i = 0; i < n; i += N) {
+        TableChunk<T, N> c;
+        const int k = std::min(N, n - i);
+        std::memcpy(c.v, host + i, (size_t)k * sizeof(T));
+        hipLaunchKernelGGL((table_upload_kernel<T, N>), dim3(1), dim3(256), 0, s, c, k, dst + i);
+        VGA_HIP_TRY(hipGetLastError());
+    }
+    return VGA_OK;
+}
+
+// the same into stream-ordered scratch that lives until `buf` goes out of scope (hipFreeAsync on s)
+template <class T>
+int upload_table(const T *host, int n, AsyncBuf &buf, hipStream_t s)
+{
+    VGA_HIP_TRY(buf.alloc((size_t)n * sizeof(T), s));
+    return upload_to(host, n, buf.as<T>(), s);
+}
+
+// header bytes (built on the host) -> dst, 1 KiB per launch
+inline int upload_bytes(const uint8_t *host, int n, uint8_t *dst, hipStream_t s) { return upload_to<uint8_t, 1024>(host, n, dst, s); }
 
 // InterleaveExtensions.Interleave(byte[][], Stream, interleaveSize, outputSize) (Utilities/Interleave.cs:43-78) from
 // `count` rows of `input_size` bytes (row r at src + r * pitch) into dst (output_size * count bytes, already zeroed).

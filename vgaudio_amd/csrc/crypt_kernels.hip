@@ -7,6 +7,8 @@
 #include "hca_device.hpp"
 #include "hca_frame_crc.hpp"
 
+#include <cstring>
+
 namespace vga {
 namespace crypt {
 
@@ -81,13 +83,15 @@ __global__ __launch_bounds__(256) void adx_test_keys_kernel(const uint8_t *__res
 
 // CryptFrame (:20-33): one wave per frame.  Each lane substitutes a contiguous chunk and CRCs it; the chunk CRCs
 // are combined across the wave (hca_frame_crc.hpp).
+struct HcaCryptTable { uint8_t v[256]; };   // a substitution table as a kernel argument
+
 __global__ __launch_bounds__(64) void hca_crypt_kernel(uint8_t *__restrict__ frames, int64_t frames_pitch, int frame_count,
-                                                       int frame_size, const uint8_t *__restrict__ table,
+                                                       int frame_size, HcaCryptTable table,
                                                        const uint16_t *__restrict__ crc_pow)
 {
     __shared__ uint8_t sub[256];
     const int lane = threadIdx.x;
-    for (int i = lane; i < 256; i += 64) sub[i] = table[i];
+    for (int i = lane; i < 256; i += 64) sub[i] = table.v[i];
     __syncthreads();
     const int64_t idx = blockIdx.x;
     const int stream = (int)(idx / frame_count), frame = (int)(idx - (int64_t)stream * frame_count);
@@ -320,12 +324,14 @@ int launch_adx_test_keys(const uint8_t *d_audio, int64_t pitch, int frame_count,
 }
 
 int launch_hca_crypt(uint8_t *d_frames, int64_t frames_pitch, int nstreams, int frame_count, int frame_size,
-                     const uint8_t *d_table, const uint16_t *d_crc_pow, hipStream_t stream)
+                     const uint8_t *table, const uint16_t *d_crc_pow, hipStream_t stream)
 {
     const int64_t total = (int64_t)nstreams * frame_count;
     if (total <= 0) return VGA_OK;
+    HcaCryptTable t;
+    std::memcpy(t.v, table, sizeof t.v);
     hipLaunchKernelGGL(hca_crypt_kernel, dim3((unsigned)total), dim3(64), 0, stream, d_frames, frames_pitch, frame_count, frame_size,
-                       d_table, d_crc_pow);
+                       t, d_crc_pow);
     VGA_HIP_TRY(hipGetLastError());
     return VGA_OK;
 }

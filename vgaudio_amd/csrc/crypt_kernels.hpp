@@ -13,8 +13,9 @@ int launch_adx_crypt(uint8_t *d_audio, int64_t pitch, int frame_count, int nch, 
 int launch_adx_test_keys(const uint8_t *d_audio, int64_t pitch, int frame_count, int nch, int frame_size, int encryption_type,
                          const AdxKey *d_keys, int nkeys, int *d_valid, hipStream_t stream);
 // d_crc_pow: uint16[hca_crc::kPowEntries] (at least 4096), x^(8k) mod 0x18005 (the HCA encoder's table)
+// table: 256 bytes in HOST memory, passed to the kernel by value (stream-ordered, no staging buffer)
 int launch_hca_crypt(uint8_t *d_frames, int64_t frames_pitch, int nstreams, int frame_count, int frame_size,
-                     const uint8_t *d_table, const uint16_t *d_crc_pow, hipStream_t stream);
+                     const uint8_t *table, const uint16_t *d_crc_pow, hipStream_t stream);
 
 // GuessAdx.Run / TryScale (VGAudio.Tools/CrackAdx/GuessAdx.cs:118-179): survivors appended to d_out[cap][3], *d_count = how many
 int launch_adx_guess_keys(const uint16_t *d_scales, int nscales, int start_frame, int encryption_type, const uint32_t *d_seed_bitmap,

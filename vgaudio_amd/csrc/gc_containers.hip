@@ -71,30 +71,6 @@ using container::Granule;
 using container::kMaxGridY;
 using container::pick_granule;
 
-// Host tables (the HPS block maps) reach the device as kernel arguments, in stream order: no staging copy from pageable
-// memory and nothing to keep alive after the launch.
-constexpr int kTableChunk = 64;
-template <class T> struct TableChunk { T v[kTableChunk]; };
-template <class T>
-__global__ __launch_bounds__(kTableChunk) void table_upload_kernel(TableChunk<T> c, int n, T *__restrict__ dst)
-{
-    if ((int)threadIdx.x < n) dst[threadIdx.x] = c.v[threadIdx.x];
-}
-
-template <class T>
-int upload_table(const T *host, int n, AsyncBuf &buf, hipStream_t s)
-{
-    VGA_HIP_TRY(buf.alloc((size_t)n * sizeof(T), s));
-    for (int i = 0; i < n; i += kTableChunk) {
-        TableChunk<T> c;
-        const int k = std::min(kTableChunk, n - i);
-        std::memcpy(c.v, host + i, (size_t)k * sizeof(T));
-        hipLaunchKernelGGL(table_upload_kernel<T>, dim3(1), dim3(kTableChunk), 0, s, c, k, buf.as<T>() + i);
-        VGA_HIP_TRY(hipGetLastError());
-    }
-    return VGA_OK;
-}
-
 // byte `pos` of a big-endian field of `n` bytes holding v
 __device__ __forceinline__ uint8_t be(int v, int n, int pos) { return (uint8_t)((uint32_t)v >> (8 * (n - 1 - pos))); }
 
@@ -530,7 +506,7 @@ int vga_hps_write_device(const vga_hps_params *p, int nch, int nfiles, const uin
     if (L.block_count >= kMaxGridY) { set_error("%d blocks: at most %d per call", L.block_count, kMaxGridY - 1); return VGA_ERR_ARGUMENT; }
     hipStream_t s = (hipStream_t)stream;
     AsyncBuf d_map;
-    if (int rc = gcc::upload_table(m.data(), L.block_count, d_map, s)) return rc;
+    if (int rc = container::upload_table(m.data(), L.block_count, d_map, s)) return rc;
     gcc::HpsArgs a{nch, p->sample_rate, vga_gcadpcm_sample_to_nibble(L.sample_count - 1), L.header_size, L.block_header_size,
                    adpcm_pitch, pcm_pitch};
     int max_written = 0;
@@ -703,7 +679,7 @@ int vga_hps_read_device(const vga_hps_info *I, const vga_hps_block_info *blocks,
     if (max_bytes == 0) return VGA_OK;
     hipStream_t s = (hipStream_t)stream;
     AsyncBuf d_map;
-    if (int rc = gcc::upload_table(blocks, I->block_count, d_map, s)) return rc;
+    if (int rc = container::upload_table(blocks, I->block_count, d_map, s)) return rc;
     const int rows = nfiles * nch;
     for (int b0 = 0; b0 < I->block_count; b0 += kMaxGridY)
         for (int r0 = 0; r0 < rows; r0 += kMaxGridY) {
