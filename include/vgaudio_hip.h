@@ -425,7 +425,7 @@ typedef struct {
 } vga_nwstm_info;
 /* host only.  VGA_ERR_INVALID_DATA for what the reference readers reject (magic, byte order mark, block sizes that
  * disagree, a file shorter than stated, data past its end); VGA_ERR_INVALID_OP, naming what was found, for PCM8 /
- * PCM16 streams, CWAV / FWAV and CSTP / FSTP files. */
+ * PCM16 streams (vga_nwstm_pcm_parse in vgaudio_hip_pcm.h reads those), CWAV / FWAV and CSTP / FSTP files. */
 int vga_nwstm_parse(const uint8_t *file, size_t size, vga_nwstm_info *out);
 /* nfiles images that share one parsed geometry at d_files + f*file_pitch -> row f*channel_count+c of d_adpcm
  * (info->adpcm_bytes per row), the layout vga_gcadpcm_decode_device takes */
@@ -865,7 +865,8 @@ int vga_hca_read(const uint8_t *file, size_t size, const vga_hca_file_info *info
  * WAVE, 16-bit PCM: the step before the codec path.
  * VGAudio/Containers/Wave/WaveReader.cs:13-100 + Utilities/Riff/RiffParser.cs:36-78 (parse: host),
  * Utilities/Interleave.cs:188-207 InterleavedByteToShort / :168-186 ShortToInterleavedByte (device transposes),
- * Containers/Wave/WaveWriter.cs:12-165.  8-bit files are parsed but not converted (Pcm8 is outside this path).
+ * Containers/Wave/WaveWriter.cs:12-165.  8-bit files are parsed here and converted by the vga_wave_*pcm8* calls
+ * of vgaudio_hip_pcm.h.
  * -------------------------------------------------------------------- */
 typedef struct {
     int channel_count, sample_rate, bits_per_sample;

@@ -2,7 +2,7 @@
 """Measurements for the SURVEY 8f rows (containers, WAVE transposes, encryption passes): device-resident kernel
 times and the HBM traffic they stand for (bytes read + written / time).  Prints one JSON object.
 
-    python tools/bench_containers.py
+    python tools/bench_containers.py          (--pcm: the copy ceiling and the PCM stream rows only)
 """
 import ctypes as C
 import json
@@ -27,6 +27,41 @@ def timed(fn, reps=5):
     return min(a.elapsed_time(b) for a, b in evs)
 
 
+def pcm_rows(L, dev, st, rec, n):
+    """BFSTM PCM16 / PCM8 images (vgaudio_hip_pcm.h): 4096 channels x 60 s as 2048 stereo files, written from and read
+    to int16 rows (PCM16 big-endian: a byte swap each way; PCM8: EncodeSigned / DecodeSigned), device-resident"""
+    import torch
+    from vgaudio_amd import _lib
+    nf, nch = 2048, 2
+    pitch = (n + 15) // 16 * 16
+    rows = torch.randint(-32768, 32768, (nf * nch, pitch), dtype=torch.int16, device=dev)
+    for codec, name in ((1, "pcm16"), (0, "pcm8")):
+        p = _lib.NwParamsC()
+        p.target, p.sample_rate, p.sample_count, p.endianness = 2, 48000, n, -1
+        lay = _lib.NwLayoutC()
+        _lib.check(L.vga_nwstm_pcm_layout_for(C.byref(p), codec, nch, C.byref(lay)))
+        fpitch = (lay.file_size + 255) // 256 * 256
+        files = torch.empty((nf, fpitch), dtype=torch.uint8, device=dev)
+        ms = timed(lambda: _lib.check(L.vga_nwstm_pcm_write_device(C.byref(p), codec, nch, nf, None, rows.data_ptr(), 0, pitch,
+                                                                   files.data_ptr(), fpitch, st())))
+        rec("nwstm_%s_write" % name, ms, nf * nch * n * 2 + nf * lay.file_size, channels=nf * nch, files=nf,
+            note="BFSTM %s from int16 rows: header + converting interleave, every image byte written once" % name.upper())
+        info = _lib.NwInfoC()
+        one = files[0, :lay.file_size].cpu().numpy()
+        _lib.check(L.vga_nwstm_pcm_parse(one.ctypes.data_as(_lib.u8p), len(one), C.byref(info)))
+        back = torch.empty_like(rows)
+        ms = timed(lambda: _lib.check(L.vga_nwstm_pcm_read_device(C.byref(info), files.data_ptr(), fpitch, nf, back.data_ptr(), 0,
+                                                                  pitch, st())))
+        if codec == 1:
+            assert torch.equal(back[:, :n], rows[:, :n])
+        else:
+            assert torch.equal(back[:, :n], (rows[:, :n] >> 8) << 8)
+        rec("nwstm_%s_read" % name, ms, nf * nch * info.adpcm_bytes + nf * nch * n * 2, channels=nf * nch, files=nf,
+            note="BFSTM %s DATA -> int16 rows" % name.upper())
+        del files, back
+    del rows
+
+
 def main():
     import torch
     from vgaudio_amd import _lib
@@ -44,6 +79,10 @@ def main():
     ms = timed(lambda: dst.copy_(src))
     rec("hbm_copy_ceiling", ms, 2 * src.numel(), note="torch copy_ of 4 GiB")
     del src, dst
+    if "--pcm" in sys.argv[1:]:                             # the ceiling and the PCM stream rows only
+        pcm_rows(L, dev, st, rec, 60 * 48000)
+        print(json.dumps(out))
+        return
 
     n = 60 * 48000
     # DSP image: 1024 channels x 60 s of GC-ADPCM (1.69 GB image)
@@ -147,6 +186,7 @@ def main():
     assert torch.equal(back[:, :nb], adpcm[:, :nb])
     rec("nwstm_read", ms, 2 * nf * nch * info.adpcm_bytes, channels=nf * nch, files=nf, note="BFSTM DATA -> pitched channels")
     del adpcm, seek, files, back
+    pcm_rows(L, dev, st, rec, n)
 
     # the file readers: one image built on the host, replicated over the batch (the kernels do not look at the bytes)
     def tile(img, count):

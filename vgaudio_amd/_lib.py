@@ -202,6 +202,20 @@ SIGNATURES = {
     "vga_nwstm_parse": (ci, [u8p, C.c_size_t, vp]),
     "vga_nwstm_read_device": (ci, [vp, vp, i64, ci, vp, i64, vp]),
     "vga_nwstm_read": (ci, [u8p, C.c_size_t, vp, u8pp, i16pp]),
+    # include/vgaudio_hip_pcm.h
+    "vga_pcm8_encode_device": (ci, [vp, i64, ci, ci, ci, vp, i64, vp]),
+    "vga_pcm8_decode_device": (ci, [vp, i64, ci, ci, ci, vp, i64, vp]),
+    "vga_nwstm_pcm_layout_for": (ci, [vp, ci, ci, vp]),
+    "vga_nwstm_pcm_write_device": (ci, [vp, ci, ci, ci, vp, vp, ci, i64, vp, i64, vp]),
+    "vga_nwstm_pcm_write": (ci, [vp, ci, ci, vp, vp, ci, u8p]),
+    "vga_nwstm_pcm_parse": (ci, [u8p, C.c_size_t, vp]),
+    "vga_nwstm_pcm_read_device": (ci, [vp, vp, i64, ci, vp, ci, i64, vp]),
+    "vga_nwstm_pcm_read": (ci, [u8p, C.c_size_t, vp, vp, ci]),
+    "vga_wave_pcm8_file_size": (i64, [vp, ci]),
+    "vga_wave_write_pcm8": (ci, [vp, ci, ci, vp, u8p]),
+    "vga_wave_write_pcm8_device": (ci, [vp, ci, i64, ci, vp, vp, vp]),
+    "vga_wave_read_pcm8": (ci, [u8p, i64, vp, vp, ci]),
+    "vga_wave_deinterleave_pcm8_device": (ci, [vp, ci, ci, vp, ci, i64, vp]),
     "vga_hps_layout_for": (ci, [vp, ci, vp]),
     "vga_hps_block_map": (ci, [vp, ci, vp, ci]),
     "vga_hps_write_device": (ci, [vp, ci, ci, vp, i64, ci, vp, vp, vp, vp, i64, ci, vp, i64, vp]),

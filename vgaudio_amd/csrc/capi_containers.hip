@@ -2,6 +2,7 @@
 // GC-ADPCM entry points).  Images are assembled in HBM; the host-pointer forms stage through the device.
 #include "common.hpp"
 #include "container_kernels.hpp"
+#include "../../include/vgaudio_hip_pcm.h"
 
 #include <algorithm>
 #include <cstring>
@@ -303,8 +304,9 @@ int wave_header_size(const vga_wave_params *p, int nch) { return 12 + 8 + (nch >
 
 // WriteRiffHeader / WriteFmtChunk / WriteSmplChunk / the data chunk's header (WaveWriter.cs:56-129); every chunk
 // size here is even, so the reference's 2-byte alignment steps never move the position
-void wave_header(const vga_wave_params *p, int nch, int64_t file_size, uint8_t *out)
+void wave_header(const vga_wave_params *p, int nch, int64_t file_size, uint8_t *out, int bytes_per_sample = 2)
 {
+    const int bps = bytes_per_sample;
     LeWriter w{out};
     w.tag("RIFF");
     w.u32((int)(file_size - 8));
@@ -314,12 +316,12 @@ void wave_header(const vga_wave_params *p, int nch, int64_t file_size, uint8_t *
     w.u16(nch > 2 ? 0xFFFE : 1);
     w.u16(nch);
     w.u32(p->sample_rate);
-    w.u32(p->sample_rate * 2 * nch);
-    w.u16(2 * nch);
-    w.u16(16);
+    w.u32(p->sample_rate * bps * nch);
+    w.u16(bps * nch);
+    w.u16(8 * bps);
     if (nch > 2) {
         w.u16(22);
-        w.u16(16);
+        w.u16(8 * bps);
         w.u32(wave_channel_mask(nch));
         std::memcpy(w.c, kSubtypePcm, 16);
         w.c += 16;
@@ -336,7 +338,7 @@ void wave_header(const vga_wave_params *p, int nch, int64_t file_size, uint8_t *
         w.u32(0);
     }
     w.tag("data");
-    w.u32(nch * p->sample_count * 2);
+    w.u32(nch * p->sample_count * bps);
 }
 
 }  // namespace
@@ -516,6 +518,112 @@ int vga_wave_write_pcm16(const int16_t *const *pcm, int nch, const vga_wave_para
     VGA_HIP_TRY(hipMemcpyAsync(file_out, d_file.p, (size_t)size, hipMemcpyDeviceToHost, st.s));
     VGA_HIP_TRY(hipStreamSynchronize(st.s));
     (void)hs;
+    return VGA_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- WAVE, 8-bit (WaveWriter.cs with WaveCodec.Pcm8Bit)
+namespace {
+
+bool bad_kind(int kind) { if (kind == VGA_SAMPLES_S16 || kind == VGA_SAMPLES_8BIT) return false; set_error("unknown sample kind %d", kind); return true; }
+int elem_size(int kind) { return kind == VGA_SAMPLES_S16 ? 2 : 1; }
+
+}  // namespace
+
+extern "C" {
+
+// WaveWriter.FileSize (WaveWriter.cs:25-30) with BytesPerSample 1: DataChunkSize = nch * samples, odd sizes included
+int64_t vga_wave_pcm8_file_size(const vga_wave_params *p, int nch)
+{
+    if (!p || nch < 1 || nch > 0x7FFF || p->sample_count < 0) { set_error("bad WAVE parameters"); return VGA_ERR_ARGUMENT; }
+    const int64_t size = wave_header_size(p, nch) + (int64_t)nch * p->sample_count;
+    if (size > 0x7FFFFFFF) { set_error("WAVE file would exceed 2 GiB (FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
+    return size;
+}
+
+int vga_wave_write_pcm8_device(const void *d_samples, int sample_kind, int64_t pitch, int nch, const vga_wave_params *p,
+                               uint8_t *d_file, void *stream)
+{
+    const int64_t size = vga_wave_pcm8_file_size(p, nch);
+    if (size < 0) return (int)size;
+    if (bad_kind(sample_kind)) return VGA_ERR_ARGUMENT;
+    if (!d_file || (p->sample_count > 0 && (!d_samples || pitch < p->sample_count))) { set_error("null pointer / pitch < sample count"); return VGA_ERR_ARGUMENT; }
+    uint8_t header[160];
+    const int hs = wave_header_size(p, nch);
+    wave_header(p, nch, size, header, 1);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = container::upload_bytes(header, hs, d_file, s)) return rc;
+    return container::launch_pcm8_interleave(d_samples, sample_kind == VGA_SAMPLES_S16, pitch, p->sample_count, nch, d_file + hs, s);
+}
+
+int vga_wave_write_pcm8(const void *const *samples, int sample_kind, int nch, const vga_wave_params *p, uint8_t *file_out)
+{
+    const int64_t size = vga_wave_pcm8_file_size(p, nch);
+    if (size < 0) return (int)size;
+    if (bad_kind(sample_kind)) return VGA_ERR_ARGUMENT;
+    if (!samples || !file_out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
+    if (p->sample_count == 0) { wave_header(p, nch, size, file_out, 1); return VGA_OK; }
+    for (int c = 0; c < nch; c++)
+        if (!samples[c]) { set_error("samples[%d] is null", c); return VGA_ERR_ARGUMENT; }
+    if (int rc = require_device()) return rc;
+    Stream st;
+    VGA_HIP_TRY(st.create());
+    DevBuf d_in, d_file;
+    const int es = elem_size(sample_kind);
+    const int64_t pitch = round_up(p->sample_count, 16);
+    VGA_HIP_TRY(d_in.alloc((size_t)nch * pitch * es));
+    VGA_HIP_TRY(d_file.alloc((size_t)size));
+    for (int c = 0; c < nch; c++)
+        VGA_HIP_TRY(hipMemcpyAsync(d_in.as<uint8_t>() + c * pitch * es, samples[c], (size_t)p->sample_count * es, hipMemcpyHostToDevice, st.s));
+    if (int rc = vga_wave_write_pcm8_device(d_in.p, sample_kind, pitch, nch, p, d_file.as<uint8_t>(), st.s)) return rc;
+    VGA_HIP_TRY(hipMemcpyAsync(file_out, d_file.p, (size_t)size, hipMemcpyDeviceToHost, st.s));
+    VGA_HIP_TRY(hipStreamSynchronize(st.s));
+    return VGA_OK;
+}
+
+// DeInterleave(1, nch) (WaveReader.cs:47) on the device, through Pcm8Codec.Decode for int16 rows
+int vga_wave_deinterleave_pcm8_device(const uint8_t *d_data, int sample_count, int nch, void *d_samples, int sample_kind,
+                                      int64_t pitch, void *stream)
+{
+    if (sample_count < 0 || nch < 0) { set_error("negative size"); return VGA_ERR_ARGUMENT; }
+    if (bad_kind(sample_kind)) return VGA_ERR_ARGUMENT;
+    if (sample_count == 0 || nch == 0) return VGA_OK;
+    if (!d_data || !d_samples || pitch < sample_count) { set_error("null pointer / pitch < sample count"); return VGA_ERR_ARGUMENT; }
+    return container::launch_pcm8_deinterleave(d_data, sample_count, nch, d_samples, sample_kind == VGA_SAMPLES_S16, pitch,
+                                               (hipStream_t)stream);
+}
+
+// WaveReader for an 8-bit file in host memory: out[c] = info->sample_count elements of sample_kind
+int vga_wave_read_pcm8(const uint8_t *file, int64_t file_len, const vga_wave_info *w, void *const *out, int sample_kind)
+{
+    if (!file || !w || !out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
+    if (bad_kind(sample_kind)) return VGA_ERR_ARGUMENT;
+    if (w->bits_per_sample != 8) { set_error("only 8-bit PCM is read here (vga_wave_read_pcm16 reads 16-bit files)"); return VGA_ERR_ARGUMENT; }
+    if (w->channel_count < 1) { set_error("info does not describe this file"); return VGA_ERR_ARGUMENT; }
+    if (w->data_size % w->channel_count != 0) {                                                        // Interleave.cs:83-85
+        set_error("The input array length (%d) must be divisible by the number of outputs.", w->data_size);
+        return VGA_ERR_INVALID_DATA;
+    }
+    const int64_t bytes = (int64_t)w->sample_count * w->channel_count;
+    if (w->data_offset < 0 || w->data_offset + bytes > file_len) { set_error("info does not describe this file"); return VGA_ERR_ARGUMENT; }
+    for (int c = 0; c < w->channel_count; c++)
+        if (!out[c]) { set_error("out[%d] is null", c); return VGA_ERR_ARGUMENT; }
+    if (bytes == 0) return VGA_OK;
+    if (int rc = require_device()) return rc;
+    Stream st;
+    VGA_HIP_TRY(st.create());
+    DevBuf d_in, d_out;
+    const int es = elem_size(sample_kind);
+    const int64_t pitch = round_up(w->sample_count, 16);
+    VGA_HIP_TRY(d_in.alloc((size_t)bytes));
+    VGA_HIP_TRY(d_out.alloc((size_t)w->channel_count * pitch * es));
+    VGA_HIP_TRY(hipMemcpyAsync(d_in.p, file + w->data_offset, (size_t)bytes, hipMemcpyHostToDevice, st.s));
+    if (int rc = vga_wave_deinterleave_pcm8_device(d_in.as<uint8_t>(), w->sample_count, w->channel_count, d_out.p, sample_kind, pitch, st.s))
+        return rc;
+    for (int c = 0; c < w->channel_count; c++)
+        VGA_HIP_TRY(hipMemcpyAsync(out[c], d_out.as<uint8_t>() + c * pitch * es, (size_t)w->sample_count * es, hipMemcpyDeviceToHost, st.s));
+    VGA_HIP_TRY(hipStreamSynchronize(st.s));
     return VGA_OK;
 }
 

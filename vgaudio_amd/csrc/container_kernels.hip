@@ -211,5 +211,82 @@ int launch_pcm16_interleave(const int16_t *pcm, int64_t pitch, int sample_count,
     return VGA_OK;
 }
 
+
+// ---------------------------------------------------------------- WAVE: interleaved 8-bit PCM <-> planar channels
+// The same tiles for 8-bit files (WaveWriter.cs:106-107 Interleave(stream, 1), WaveReader.cs:47 DeInterleave(1, nch)),
+// fused with Pcm8Codec.Encode / Decode (Pcm8Codec.cs:5-28) when the rows are int16: b = (s >> 8) ^ 0x80,
+// s = (sbyte)(b ^ 0x80) << 8.  A frame is nch bytes, so the interleaved side is byte-addressed at any alignment.
+__device__ __forceinline__ uint8_t to_u8(int16_t s) { return (uint8_t)((s >> 8) ^ 0x80); }
+__device__ __forceinline__ uint8_t to_u8(uint8_t b) { return b; }
+template <class R> __device__ __forceinline__ R from_u8(uint8_t b);
+template <> __device__ __forceinline__ int16_t from_u8<int16_t>(uint8_t b) { return (int16_t)((int8_t)(b ^ 0x80) * 256); }
+template <> __device__ __forceinline__ uint8_t from_u8<uint8_t>(uint8_t b) { return b; }
+
+template <class R>
+__global__ __launch_bounds__(256) void pcm8_deinterleave_kernel(const uint8_t *__restrict__ in, int n, int nch,
+                                                                R *__restrict__ out, int64_t pitch)
+{
+    __shared__ uint8_t tile[PCM_TS][PCM_TC + 1];
+    const int i0 = blockIdx.x * PCM_TS, c0 = blockIdx.y * PCM_TC;
+    const int st = min(PCM_TS, n - i0), ct = min(PCM_TC, nch - c0);
+    for (int e = threadIdx.x; e < st * ct; e += 256) {
+        const int s = e / ct, c = e - s * ct;
+        tile[s][c] = in[(int64_t)(i0 + s) * nch + c0 + c];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < st * ct; e += 256) {
+        const int c = e / st, s = e - c * st;
+        out[(int64_t)(c0 + c) * pitch + i0 + s] = from_u8<R>(tile[s][c]);
+    }
+}
+
+template <class R>
+__global__ __launch_bounds__(256) void pcm8_interleave_kernel(const R *__restrict__ in, int64_t pitch, int n, int nch,
+                                                              uint8_t *__restrict__ out)
+{
+    __shared__ uint8_t tile[PCM_TS][PCM_TC + 1];
+    const int i0 = blockIdx.x * PCM_TS, c0 = blockIdx.y * PCM_TC;
+    const int st = min(PCM_TS, n - i0), ct = min(PCM_TC, nch - c0);
+    for (int e = threadIdx.x; e < st * ct; e += 256) {
+        const int c = e / st, s = e - c * st;
+        tile[s][c] = to_u8(in[(int64_t)(c0 + c) * pitch + i0 + s]);
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < st * ct; e += 256) {
+        const int s = e / ct, c = e - s * ct;
+        out[(int64_t)(i0 + s) * nch + c0 + c] = tile[s][c];
+    }
+}
+
+int launch_pcm8_deinterleave(const uint8_t *interleaved, int sample_count, int nch, void *rows, bool s16, int64_t pitch,
+                             hipStream_t stream)
+{
+    if (sample_count <= 0 || nch <= 0) return VGA_OK;
+    const dim3 grid((sample_count + PCM_TS - 1) / PCM_TS, (nch + PCM_TC - 1) / PCM_TC);
+    if (s16)
+        hipLaunchKernelGGL(pcm8_deinterleave_kernel<int16_t>, grid, dim3(256), 0, stream, interleaved, sample_count, nch,
+                           static_cast<int16_t *>(rows), pitch);
+    else
+        hipLaunchKernelGGL(pcm8_deinterleave_kernel<uint8_t>, grid, dim3(256), 0, stream, interleaved, sample_count, nch,
+                           static_cast<uint8_t *>(rows), pitch);
+    VGA_HIP_TRY(hipGetLastError());
+    return VGA_OK;
+}
+
+int launch_pcm8_interleave(const void *rows, bool s16, int64_t pitch, int sample_count, int nch, uint8_t *interleaved,
+                           hipStream_t stream)
+{
+    if (sample_count <= 0 || nch <= 0) return VGA_OK;
+    const dim3 grid((sample_count + PCM_TS - 1) / PCM_TS, (nch + PCM_TC - 1) / PCM_TC);
+    if (s16)
+        hipLaunchKernelGGL(pcm8_interleave_kernel<int16_t>, grid, dim3(256), 0, stream, static_cast<const int16_t *>(rows),
+                           pitch, sample_count, nch, interleaved);
+    else
+        hipLaunchKernelGGL(pcm8_interleave_kernel<uint8_t>, grid, dim3(256), 0, stream, static_cast<const uint8_t *>(rows),
+                           pitch, sample_count, nch, interleaved);
+    VGA_HIP_TRY(hipGetLastError());
+    return VGA_OK;
+}
+
 }  // namespace container
 }  // namespace vga

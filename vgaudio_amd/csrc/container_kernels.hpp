@@ -67,6 +67,11 @@ int launch_replicate(const uint8_t *d_header, int header_size, uint8_t *d_files,
 // pcm + c * pitch (in samples).
 int launch_pcm16_deinterleave(const uint8_t *interleaved, int sample_count, int nch, int16_t *pcm, int64_t pitch, hipStream_t stream);
 int launch_pcm16_interleave(const int16_t *pcm, int64_t pitch, int sample_count, int nch, uint8_t *interleaved, hipStream_t stream);
+// WAVE 8-bit PCM <-> planar rows: int16 rows (s16, through Pcm8Codec.Encode / Decode) or unsigned byte rows as stored
+int launch_pcm8_deinterleave(const uint8_t *interleaved, int sample_count, int nch, void *rows, bool s16, int64_t pitch,
+                             hipStream_t stream);
+int launch_pcm8_interleave(const void *rows, bool s16, int64_t pitch, int sample_count, int nch, uint8_t *interleaved,
+                           hipStream_t stream);
 
 
 // ---------------------------------------------------------------- shared by the container readers

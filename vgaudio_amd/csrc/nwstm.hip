@@ -4,6 +4,8 @@
 // HBM-bound, every byte of an image read or written once.
 #include "common.hpp"
 #include "container_kernels.hpp"
+#include "pcm_kernels.hpp"
+#include "../../include/vgaudio_hip_pcm.h"
 
 #include <algorithm>
 #include <cstring>
@@ -21,7 +23,7 @@ enum : int {
     kStreamSeekBlock = 0x4001, kStreamDataBlock = 0x4002, kStreamRegionBlock = 0x4003, kStreamPrefetchDataBlock = 0x4004,
     kStreamInfo = 0x4100, kTrackInfo = 0x4101, kChannelInfo = 0x4102
 };
-constexpr int kCodecGcAdpcm = 2;                            // NwCodec.cs
+constexpr int kCodecPcm8 = 0, kCodecPcm16 = 1, kCodecGcAdpcm = 2;   // NwCodec.cs
 
 int64_t next_multiple(int64_t v, int64_t m) { return m <= 0 || v % m == 0 ? v : v + m - v % m; }   // Helpers.cs:71-80
 int div_round_up(int v, int d) { return v / d + (v % d != 0 ? 1 : 0); }                          // Extensions.cs:145
@@ -48,6 +50,7 @@ struct HeaderArgs {
     int last_block_size, samples_per_seek_table_entry, track_short, track_info, region_info, unaligned_loop, version_word;
     int head_offset, head_size, head1_size, head2_size, seek_offset, seek_size, data_offset, data_size, audio_offset;
     int file_size, track_count;
+    int codec, bytes_per_seek_table_entry;                  // NwCodec: GC-ADPCM, or PCM8 / PCM16 (no seek block)
     TrackK tracks[VGA_NW_MAX_TRACKS];
 };
 
@@ -63,8 +66,9 @@ struct Cursor {
     __device__ void tag(const char *t) { for (int k = 0; k < 4; k++) put8(t[k]); }   // WriteUTF8: bytes as they are
 };
 
-// One workgroup per image: the threads zero everything in front of the seek block and between the DATA header and the
-// audio, then lane 0 writes the file header and HEAD (BrstmWriter.cs:130-260) or INFO (BCFstmWriter.cs:171-333).
+// One workgroup per image: the threads zero everything in front of the seek block (of the DATA block for PCM, which
+// has none) and between the DATA header and the audio, then lane 0 writes the file header and HEAD
+// (BrstmWriter.cs:130-260) or INFO (BCFstmWriter.cs:171-333).  PCM streams take the writers' Codec != GcAdpcm branches.
 __global__ __launch_bounds__(64) void nw_header_kernel(HeaderArgs a, const uint8_t *__restrict__ adpcm, int64_t adpcm_pitch,
                                                        int adpcm_len, const int16_t *__restrict__ coefs,
                                                        const int16_t *__restrict__ gain, const int16_t *__restrict__ start_ctx,
@@ -72,7 +76,8 @@ __global__ __launch_bounds__(64) void nw_header_kernel(HeaderArgs a, const uint8
                                                        int64_t file_pitch)
 {
     uint8_t *img = files + (int64_t)blockIdx.x * file_pitch;
-    for (int k = threadIdx.x; k < a.seek_offset; k += 64) img[k] = 0;
+    const bool gc = a.codec == kCodecGcAdpcm;
+    for (int k = threadIdx.x, end = gc ? a.seek_offset : a.data_offset; k < end; k += 64) img[k] = 0;
     for (int k = a.data_offset + threadIdx.x; k < a.audio_offset; k += 64) img[k] = 0;
     __syncthreads();
     if (threadIdx.x != 0) return;
@@ -110,7 +115,7 @@ __global__ __launch_bounds__(64) void nw_header_kernel(HeaderArgs a, const uint8
         c.put32(kOffsetMarker); c.put32(24);
         c.put32(kOffsetMarker); c.put32(24 + a.head1_size);
         c.put32(kOffsetMarker); c.put32(24 + a.head1_size + a.head2_size);
-        c.put8(kCodecGcAdpcm);                              // WriteHeadBlock1 (:164-183)
+        c.put8(a.codec);                                    // WriteHeadBlock1 (:164-183)
         c.put8(a.looping);
         c.put8(nch);                                        // (byte)ChannelCount
         c.put8(0);
@@ -126,7 +131,7 @@ __global__ __launch_bounds__(64) void nw_header_kernel(HeaderArgs a, const uint8
         c.put32(a.last_block_samples);
         c.put32(a.last_block_size);
         c.put32(a.samples_per_seek_table_entry);
-        c.put32(4);
+        c.put32(a.bytes_per_seek_table_entry);
         const int tinfo = a.track_short ? 4 : 0x0c;         // WriteHeadBlock2 (:185-216)
         c.put8(T);
         c.put8(a.track_short ? 0 : 1);
@@ -145,9 +150,11 @@ __global__ __launch_bounds__(64) void nw_header_kernel(HeaderArgs a, const uint8
         c.put8(0);
         c.put16(0);
         base = 24 + 0x34 + a.head2_size + 4;
-        for (int i = 0; i < nch; i++) { c.put32(kOffsetMarker); c.put32(base + nch * 8 + 0x38 * i); }
+        const int cinfo = gc ? 0x38 : 8;                    // ChannelInfoSize
+        for (int i = 0; i < nch; i++) { c.put32(kOffsetMarker); c.put32(base + nch * 8 + cinfo * i); }
         for (int i = 0; i < nch; i++) {
             c.put32(kOffsetMarker);
+            if (!gc) { c.put32(0); continue; }
             c.put32(base + nch * 8 + 0x38 * i + 8);
             coef(c, i);
             c.put16(gain ? gain[row0 + i] : 0);
@@ -155,9 +162,11 @@ __global__ __launch_bounds__(64) void nw_header_kernel(HeaderArgs a, const uint8
             ctx(c, i, true);
             c.put16(0);
         }
-        c.pos = a.seek_offset;                              // WriteAdpcBlock (:258-267)
-        c.tag("ADPC");
-        c.put32(a.seek_size);
+        if (gc) {
+            c.pos = a.seek_offset;                          // WriteAdpcBlock (:258-267)
+            c.tag("ADPC");
+            c.put32(a.seek_size);
+        }
         c.pos = a.data_offset;                              // WriteDataBlock (:270-274)
         c.tag("DATA");
         c.put32(a.data_size);
@@ -169,10 +178,10 @@ __global__ __launch_bounds__(64) void nw_header_kernel(HeaderArgs a, const uint8
     c.put16(0x40);
     c.put32(a.version_word);
     c.put32(a.file_size);
-    c.put16(3);
+    c.put16(gc ? 3 : 2);
     c.put16(0);
     c.put16(kStreamInfoBlock); c.put16(0); c.put32(a.head_offset); c.put32(a.head_size);
-    c.put16(kStreamSeekBlock); c.put16(0); c.put32(a.seek_offset); c.put32(a.seek_size);
+    if (gc) { c.put16(kStreamSeekBlock); c.put16(0); c.put32(a.seek_offset); c.put32(a.seek_size); }
     c.put16(kStreamDataBlock); c.put16(0); c.put32(a.data_offset); c.put32(a.data_size);
     c.pos = a.head_offset;                                  // WriteInfoBlock (:199-223)
     c.tag("INFO");
@@ -181,7 +190,7 @@ __global__ __launch_bounds__(64) void nw_header_kernel(HeaderArgs a, const uint8
     if (a.track_info) { c.put16(kReferenceTable); c.put16(0); c.put32(24 + a.head1_size); }
     else { c.put32(0); c.put32(-1); }
     c.put16(kReferenceTable); c.put16(0); c.put32(24 + a.head1_size + a.head2_size);
-    c.put8(kCodecGcAdpcm);                                  // WriteInfoBlock1 (:225-258)
+    c.put8(a.codec);                                        // WriteInfoBlock1 (:225-258)
     c.put8(a.looping);
     c.put8(nch);
     c.put8(0);
@@ -194,7 +203,7 @@ __global__ __launch_bounds__(64) void nw_header_kernel(HeaderArgs a, const uint8
     c.put32(a.last_block_size_without_padding);
     c.put32(a.last_block_samples);
     c.put32(a.last_block_size);
-    c.put32(4);
+    c.put32(a.bytes_per_seek_table_entry);
     c.put32(a.samples_per_seek_table_entry);
     c.put16(kSampleData); c.put16(0); c.put32(0x18);
     if (a.region_info) { c.put16(kByteTable); c.put16(0); c.put32(0); c.put32(-1); }
@@ -214,16 +223,21 @@ __global__ __launch_bounds__(64) void nw_header_kernel(HeaderArgs a, const uint8
             c.put32(t.channel_count);
             c.put8(t.left); c.put8(t.right); c.put16(0);
         }
-    for (int i = 0; i < nch; i++) { c.put16(kGcAdpcmInfo); c.put16(0); c.put32(8 * nch - 8 * i + 0x2e * i); }
     for (int i = 0; i < nch; i++) {
-        coef(c, i);
-        ctx(c, i, false);
-        ctx(c, i, true);
-        c.put16(0);
+        if (gc) { c.put16(kGcAdpcmInfo); c.put16(0); c.put32(8 * nch - 8 * i + 0x2e * i); }
+        else { c.put32(0); c.put32(-1); }                   // a null reference: PCM has no channel info body
     }
-    c.pos = a.seek_offset;                                  // WriteSeekBlock (:335-344)
-    c.tag("SEEK");
-    c.put32(a.seek_size);
+    if (gc) {
+        for (int i = 0; i < nch; i++) {
+            coef(c, i);
+            ctx(c, i, false);
+            ctx(c, i, true);
+            c.put16(0);
+        }
+        c.pos = a.seek_offset;                              // WriteSeekBlock (:335-344)
+        c.tag("SEEK");
+        c.put32(a.seek_size);
+    }
     c.pos = a.data_offset;                                  // WriteDataBlock (:346-352): bytes 8..0x20 stay zero
     c.tag("DATA");
     c.put32(a.data_size);
@@ -286,7 +300,8 @@ void fill_tracks(const vga_nwstm_layout &L, const vga_nw_track *tracks, nwstm::H
     }
 }
 
-void header_args(const vga_nwstm_layout &L, const vga_nwstm_params *p, int nch, const vga_nw_track *tracks, nwstm::HeaderArgs *a)
+void header_args(const vga_nwstm_layout &L, const vga_nwstm_params *p, int nch, const vga_nw_track *tracks, nwstm::HeaderArgs *a,
+                 int codec = kCodecGcAdpcm)
 {
     std::memset(a, 0, sizeof *a);
     a->target = L.target; a->big = L.endianness; a->nch = nch; a->looping = L.looping; a->sample_rate = p->sample_rate;
@@ -300,6 +315,7 @@ void header_args(const vga_nwstm_layout &L, const vga_nwstm_params *p, int nch, 
     a->head1_size = L.head1_size; a->head2_size = L.head2_size; a->seek_offset = L.seek_block_offset;
     a->seek_size = L.seek_block_size; a->data_offset = L.data_block_offset; a->data_size = L.data_block_size;
     a->audio_offset = L.audio_data_offset; a->file_size = L.file_size; a->track_count = L.track_count;
+    a->codec = codec; a->bytes_per_seek_table_entry = L.bytes_per_seek_table_entry;
     fill_tracks(L, tracks, a);
 }
 
@@ -325,6 +341,42 @@ struct Ref { int type, offset, base; int abs() const { return base + offset; } b
 Ref read_ref(Reader &r, int base) { Ref x; x.type = r.i16(); r.pos += 2; x.offset = r.i32(); x.base = base; return x; }
 
 int invalid(const char *msg) { set_error("%s", msg); return VGA_ERR_INVALID_DATA; }
+
+int pcm_codec_check(int codec)
+{
+    if (codec == kCodecPcm8 || codec == kCodecPcm16) return VGA_OK;
+    if (codec == kCodecGcAdpcm) set_error("the stream is GC-ADPCM (codec 2): read it with vga_nwstm_parse");
+    else set_error("stream codec %d is neither PCM8 (0) nor PCM16 (1)", codec);
+    return VGA_ERR_INVALID_OP;
+}
+
+// the target's byte order and the version fields (BrstmWriter.cs:119, BCFstmWriter.cs:27,57-65,147-162)
+int target_and_version(const vga_nwstm_params *p, vga_nwstm_layout *L)
+{
+    L->target = p->target;
+    if (p->target == VGA_NW_RSTM) {
+        L->endianness = VGA_NW_BIG_ENDIAN;                  // BrstmWriter.cs:119
+        L->version = 0x01000000u;
+    } else {
+        L->endianness = p->endianness < 0 ? (p->target == VGA_NW_CSTM ? VGA_NW_LITTLE_ENDIAN : VGA_NW_BIG_ENDIAN) : (p->endianness != 0);
+        uint32_t v = p->version ? p->version : (p->target == VGA_NW_CSTM ? 0x02010000u : 0x00030000u);
+        const int major = v >> 24, minor = (v >> 16) & 0xff;
+        if ((v & 0xffff) != 0 || (p->target == VGA_NW_CSTM ? (major != 2 || minor > 3) : (major != 0 || minor < 2 || minor > 5))) {
+            set_error("version %u.%u.%u is not one this writer produces (BCSTM 2.0-2.3, BFSTM 0.2-0.5)", major, minor, (v >> 8) & 0xff);
+            return VGA_ERR_OUT_OF_RANGE;
+        }
+        L->version = v;
+        L->include_track_info = include_track_info(v);
+        L->include_region_info = include_region_info(v);
+        L->include_unaligned_loop = include_unaligned_loop(v);
+        // BCFstmWriter.GetVersion (:147-162): the configured Version only selects which fields exist
+        const int word = p->target == VGA_NW_FSTM ? (L->include_unaligned_loop ? 4 : 3)
+                         : (L->include_track_info && L->include_region_info) ? 0x201
+                         : (!L->include_track_info && L->include_region_info) ? 0x202 : 0x200;
+        L->version_word = word << 16;
+    }
+    return VGA_OK;
+}
 
 }  // namespace
 
@@ -363,28 +415,7 @@ int vga_nwstm_layout_for(const vga_nwstm_params *p, int nch, vga_nwstm_layout *L
         loop_start = p->loop_start;
         loop_end = p->loop_end;
     }
-    L->target = p->target;
-    if (p->target == VGA_NW_RSTM) {
-        L->endianness = VGA_NW_BIG_ENDIAN;                  // BrstmWriter.cs:119
-        L->version = 0x01000000u;
-    } else {
-        L->endianness = p->endianness < 0 ? (p->target == VGA_NW_CSTM ? VGA_NW_LITTLE_ENDIAN : VGA_NW_BIG_ENDIAN) : (p->endianness != 0);
-        uint32_t v = p->version ? p->version : (p->target == VGA_NW_CSTM ? 0x02010000u : 0x00030000u);
-        const int major = v >> 24, minor = (v >> 16) & 0xff;
-        if ((v & 0xffff) != 0 || (p->target == VGA_NW_CSTM ? (major != 2 || minor > 3) : (major != 0 || minor < 2 || minor > 5))) {
-            set_error("version %u.%u.%u is not one this writer produces (BCSTM 2.0-2.3, BFSTM 0.2-0.5)", major, minor, (v >> 8) & 0xff);
-            return VGA_ERR_OUT_OF_RANGE;
-        }
-        L->version = v;
-        L->include_track_info = include_track_info(v);
-        L->include_region_info = include_region_info(v);
-        L->include_unaligned_loop = include_unaligned_loop(v);
-        // BCFstmWriter.GetVersion (:147-162): the configured Version only selects which fields exist
-        const int word = p->target == VGA_NW_FSTM ? (L->include_unaligned_loop ? 4 : 3)
-                         : (L->include_track_info && L->include_region_info) ? 0x201
-                         : (!L->include_track_info && L->include_region_info) ? 0x202 : 0x200;
-        L->version_word = word << 16;
-    }
+    if (int rc = target_and_version(p, L)) return rc;
     // SetupWriter (BrstmWriter.cs:88-103): WithAlignment when the loop start is not aligned; every channel is then
     // rebuilt with LoopAlignmentMultiple and SamplesPerSeekTableEntry -- vga_gcadpcm_build_channels_* does both
     L->channel.sample_count = p->sample_count;
@@ -540,7 +571,8 @@ int vga_nwstm_write(const vga_nwstm_params *p, int nch, const vga_nw_track *trac
 
 // BrstmReader.ReadFile / BCFstmReader.ReadFile up to the audio (host only): the checks of the reference readers,
 // then what Common.ToAdpcmStream (Common.cs:67-97) needs.
-int vga_nwstm_parse(const uint8_t *file, size_t size, vga_nwstm_info *out)
+// pcm: the PCM8 / PCM16 streams vga_nwstm_pcm_parse reads; else the GC-ADPCM ones of vga_nwstm_parse
+static int parse_nw(const uint8_t *file, size_t size, vga_nwstm_info *out, bool pcm)
 {
     if (!file || !out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     std::memset(out, 0, sizeof *out);
@@ -590,7 +622,8 @@ int vga_nwstm_parse(const uint8_t *file, size_t size, vga_nwstm_info *out)
         I.samples_per_seek_table_entry = r.i32();
         I.bytes_per_seek_table_entry = r.i32();
         if (r.eof) return invalid("file ends inside the stream info");
-        if (I.codec != kCodecGcAdpcm) { set_error("BRSTM codec %d (PCM8 = 0, PCM16 = 1) is not GC-ADPCM", I.codec); return VGA_ERR_INVALID_OP; }
+        if (!pcm && I.codec != kCodecGcAdpcm) { set_error("BRSTM codec %d (PCM8 = 0, PCM16 = 1) is not GC-ADPCM", I.codec); return VGA_ERR_INVALID_OP; }
+        if (pcm) { if (int rc = pcm_codec_check(I.codec)) return rc; }
         if (!ti.is(kByteTable)) return invalid("Could not read track info.");
         r.pos = ti.abs();                                   // TrackInfo.ReadBrstm
         I.track_count = r.u8();
@@ -627,7 +660,7 @@ int vga_nwstm_parse(const uint8_t *file, size_t size, vga_nwstm_info *out)
             found++;
         }
         if (r.eof) return invalid("file ends inside the channel info");
-        if (found < I.channel_count) return invalid("fewer channel infos than channels");
+        if (!pcm && found < I.channel_count) return invalid("fewer channel infos than channels");
         if (I.seek_block_offset != 0) {                     // ReadAdpcBlock
             r.pos = I.seek_block_offset;
             if (!r.tag("ADPC")) return invalid("Unknown or invalid ADPC block");
@@ -718,7 +751,8 @@ int vga_nwstm_parse(const uint8_t *file, size_t size, vga_nwstm_info *out)
         if (include_unaligned_loop(I.version)) { I.loop_start_unaligned = r.i32(); I.loop_end_unaligned = r.i32(); I.has_unaligned_loop = 1; }
         if (include_checksum(I.version)) r.i32();
         if (r.eof) return invalid("file ends inside the stream info");
-        if (I.codec != kCodecGcAdpcm) { set_error("stream codec %d (PCM8 = 0, PCM16 = 1) is not GC-ADPCM", I.codec); return VGA_ERR_INVALID_OP; }
+        if (!pcm && I.codec != kCodecGcAdpcm) { set_error("stream codec %d (PCM8 = 0, PCM16 = 1) is not GC-ADPCM", I.codec); return VGA_ERR_INVALID_OP; }
+        if (pcm) { if (int rc = pcm_codec_check(I.codec)) return rc; }
         I.track_type = VGA_NW_TRACK_STANDARD;
         if (ti.is(kReferenceTable)) {                       // TrackInfo.ReadBfstm
             r.pos = ti.abs();
@@ -762,7 +796,7 @@ int vga_nwstm_parse(const uint8_t *file, size_t size, vga_nwstm_info *out)
                 for (int k = 0; k < 3; k++) I.loop_context[found][k] = (int16_t)r.i16();
                 found++;
             }
-            if (found < I.channel_count) return invalid("fewer channel infos than channels");
+            if (!pcm && found < I.channel_count) return invalid("fewer channel infos than channels");
         } else {
             return invalid("Could not read channel info.");
         }
@@ -801,9 +835,21 @@ int vga_nwstm_parse(const uint8_t *file, size_t size, vga_nwstm_info *out)
     if (I.audio_data_length < 0 || I.audio_data_offset < 0 || I.audio_data_offset + (int64_t)I.audio_data_length > len)
         return invalid("Specified length is greater than the number of bytes remaining in the Stream");
     if (I.audio_data_length % I.channel_count != 0) return invalid("The input length must be divisible by the number of outputs.");
+    if (pcm) {                                              // Common.SamplesToBytes(SampleCount, Codec)
+        const int64_t row = (int64_t)I.sample_count * (I.codec == kCodecPcm16 ? 2 : 1);
+        if (row > 0x7FFFFFFF) return invalid("sample count too large for one channel's bytes");
+        std::memset(I.coefs, 0, sizeof I.coefs);
+        std::memset(I.gain, 0, sizeof I.gain);
+        std::memset(I.start_context, 0, sizeof I.start_context);
+        std::memset(I.loop_context, 0, sizeof I.loop_context);
+        I.adpcm_bytes = (int)row;
+        return VGA_OK;
+    }
     I.adpcm_bytes = bytes_of(I.sample_count);
     return VGA_OK;
 }
+
+int vga_nwstm_parse(const uint8_t *file, size_t size, vga_nwstm_info *out) { return parse_nw(file, size, out, false); }
 
 int vga_nwstm_read_device(const vga_nwstm_info *I, const uint8_t *d_files, int64_t file_pitch, int nfiles, uint8_t *d_adpcm,
                           int64_t adpcm_pitch, void *stream)
@@ -851,6 +897,223 @@ int vga_nwstm_read(const uint8_t *file, size_t size, const vga_nwstm_info *I, ui
     if (int rc = vga_nwstm_read_device(I, d_file.as<uint8_t>(), (int64_t)bytes, 1, d_out.as<uint8_t>(), apitch, st.s)) return rc;
     for (int c = 0; c < nch; c++)
         VGA_HIP_TRY(hipMemcpyAsync(adpcm_out[c], d_out.as<uint8_t>() + c * apitch, (size_t)I->adpcm_bytes, hipMemcpyDeviceToHost, st.s));
+    VGA_HIP_TRY(hipStreamSynchronize(st.s));
+    return VGA_OK;
+}
+
+
+// ---------------------------------------------------------------- PCM8 / PCM16 streams (the writers' Codec != GcAdpcm)
+
+// BxstmConfiguration with Codec = Pcm16Bit / Pcm8Bit and the size math of BrstmWriter.cs:22-74 / BCFstmWriter.cs:23-83
+int vga_nwstm_pcm_layout_for(const vga_nwstm_params *p, int codec, int nch, vga_nwstm_layout *L)
+{
+    if (!p || !L) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
+    std::memset(L, 0, sizeof *L);
+    if (codec != kCodecPcm8 && codec != kCodecPcm16) {
+        set_error("codec %d: this call writes PCM8 (0) or PCM16 (1) streams (vga_nwstm_layout_for for GC-ADPCM)", codec);
+        return VGA_ERR_ARGUMENT;
+    }
+    if (p->target < VGA_NW_RSTM || p->target > VGA_NW_FSTM) { set_error("unknown NintendoWare target %d", p->target); return VGA_ERR_ARGUMENT; }
+    if (nch < 1 || nch > VGA_NW_MAX_CHANNELS) { set_error("channel count %d out of range (1..%d)", nch, VGA_NW_MAX_CHANNELS); return VGA_ERR_ARGUMENT; }
+    const int bps = codec == kCodecPcm16 ? 2 : 1;
+    const int def = 0x2000 / bps;                           // BytesToSamples(DefaultInterleave, Codec)
+    const int spi = p->samples_per_interleave ? p->samples_per_interleave : def;
+    if (spi < 1) return out_of_range("Number of samples per interleave must be positive");   // no divisible-by-14 rule
+    const int spe = p->samples_per_seek_table_entry ? p->samples_per_seek_table_entry : def;
+    if (spe < 2) return out_of_range("Number of samples per interleave must be 2 or greater");
+    if (p->sample_rate < 0 || p->sample_count < 0) return out_of_range("negative sample rate / sample count");
+    if (p->track_type != VGA_NW_TRACK_STANDARD && p->track_type != VGA_NW_TRACK_SHORT) { set_error("unknown BRSTM track type"); return VGA_ERR_ARGUMENT; }
+    if (p->seek_table_type != VGA_NW_SEEK_STANDARD && p->seek_table_type != VGA_NW_SEEK_SHORT) { set_error("unknown BRSTM seek table type"); return VGA_ERR_ARGUMENT; }
+    if (p->track_count < 0 || p->track_count > VGA_NW_MAX_TRACKS) {
+        set_error("track count %d out of range (0 = the default list, at most %d)", p->track_count, VGA_NW_MAX_TRACKS);
+        return VGA_ERR_OUT_OF_RANGE;
+    }
+    int loop_start = 0, loop_end = 0;
+    if (p->looping) {                                       // AudioFormatBaseBuilder.WithLoop (:30-43)
+        if (p->loop_start < 0 || p->loop_start > p->sample_count || p->loop_end < 0 || p->loop_end > p->sample_count)
+            return out_of_range("Loop points must be less than the number of samples and non-negative.");
+        if (p->loop_end < p->loop_start) return out_of_range("The loop end must be greater than the loop start");
+        loop_start = p->loop_start;
+        loop_end = p->loop_end;
+    }
+    if (int rc = target_and_version(p, L)) return rc;
+    if (L->include_unaligned_loop) {                        // BCFstmWriter.cs:250-254 reads Adpcm.LoopStart
+        set_error("BCSTM 2.3+ / BFSTM 0.4+ carry GC-ADPCM unaligned loop points, which a PCM stream does not have "
+                  "(the reference writer fails on a null GcAdpcmFormat): choose an earlier version");
+        return VGA_ERR_INVALID_OP;
+    }
+    const int64_t row = (int64_t)p->sample_count * bps;
+    if ((int64_t)spi * bps > 0x7FFFFFFF) return out_of_range("Number of samples per interleave too large for the interleave's int size");
+    if (row > 0x7FFFFFFF) { set_error("file would exceed 2 GiB (the reference's FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
+    L->channel_sample_count = p->sample_count;
+    L->channel_adpcm_bytes = (int)row;
+    L->looping = p->looping ? 1 : 0;
+    L->loop_start = loop_start;                              // no loop alignment for PCM
+    L->loop_end = loop_end;
+    const int sc = L->looping ? loop_end : p->sample_count;  // SampleCount = LoopEnd when looping
+    L->sample_count = sc;
+    L->track_count = p->track_count ? p->track_count : div_round_up(nch, 2);
+    L->samples_per_interleave = spi;
+    L->interleave_size = spi * bps;
+    L->interleave_count = div_round_up(sc, spi);
+    L->last_block_samples = sc - (L->interleave_count - 1) * spi;
+    L->last_block_size_without_padding = L->last_block_samples * bps;
+    L->last_block_size = (int)next_multiple(L->last_block_size_without_padding, 0x20);
+    const bool rstm = p->target == VGA_NW_RSTM;
+    L->samples_per_seek_table_entry = rstm ? 0 : spe;       // BrstmWriter.cs:51-52 vs BCFstmWriter.cs:51-52
+    L->bytes_per_seek_table_entry = rstm ? 0 : 4;
+    L->seek_table_entry_count = 0;
+    const int64_t audio_data_size = next_multiple((int64_t)sc * bps, 0x20);
+    const int T = L->track_count;
+    L->header_size = 0x40;
+    if (rstm) {
+        L->head1_size = 0x34;
+        L->head2_size = 4 + 8 * T + (p->track_type == VGA_NW_TRACK_SHORT ? 4 : 0x0c) * T;
+        L->head3_size = 4 + 8 * nch + 8 * nch;              // ChannelInfoSize 8
+    } else {
+        L->head1_size = 0x38 + (L->include_region_info ? 0xc : 0);
+        L->head2_size = L->include_track_info ? 4 + 8 * T : 0;
+        L->head3_size = 4 + 8 * nch + (L->include_track_info ? 0x14 * T : 0) + 8 * nch;   // ChannelInfoSize 0
+    }
+    const int64_t head = next_multiple(8 + 24 + L->head1_size + L->head2_size + L->head3_size, 0x20);
+    const int64_t data = 0x20 + audio_data_size * nch;
+    const int64_t file = 0x40 + head + data;
+    if (file > 0x7FFFFFFF) { set_error("file would exceed 2 GiB (the reference's FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
+    L->head_block_offset = 0x40;
+    L->head_block_size = (int)head;
+    L->seek_block_offset = 0;                               // no ADPC / SEEK block
+    L->seek_block_size = 0;
+    L->data_block_offset = (int)(0x40 + head);
+    L->data_block_size = (int)data;
+    L->audio_data_offset = L->data_block_offset + 0x20;
+    L->audio_data_size = (int)audio_data_size;
+    L->file_size = (int)file;
+    return VGA_OK;
+}
+
+int vga_nwstm_pcm_write_device(const vga_nwstm_params *p, int codec, int nch, int nfiles, const vga_nw_track *tracks,
+                               const void *d_samples, int sample_kind, int64_t pitch, uint8_t *d_files, int64_t file_pitch,
+                               void *stream)
+{
+    vga_nwstm_layout L;
+    if (int rc = vga_nwstm_pcm_layout_for(p, codec, nch, &L)) return rc;
+    if (int rc = check_track_list(p, tracks)) return rc;
+    if (sample_kind != VGA_SAMPLES_S16 && sample_kind != VGA_SAMPLES_8BIT) { set_error("unknown sample kind %d", sample_kind); return VGA_ERR_ARGUMENT; }
+    if (codec == kCodecPcm16 && sample_kind != VGA_SAMPLES_S16) { set_error("a PCM16 stream is written from VGA_SAMPLES_S16 rows"); return VGA_ERR_ARGUMENT; }
+    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
+    if (nfiles == 0) return VGA_OK;
+    if (!d_files || (p->sample_count > 0 && !d_samples)) { set_error("null device pointer"); return VGA_ERR_ARGUMENT; }
+    if (file_pitch < L.file_size || (nfiles > 1 && (file_pitch & 15))) {
+        set_error("file pitch %lld: at least the file size %d and a multiple of 16", (long long)file_pitch, L.file_size);
+        return VGA_ERR_ARGUMENT;
+    }
+    if (p->sample_count > 0 && pitch < p->sample_count) { set_error("pitch < sample count"); return VGA_ERR_ARGUMENT; }
+    if ((int64_t)nfiles * nch > 0x7FFFFFFF / 16) { set_error("too many files in one call"); return VGA_ERR_ARGUMENT; }
+    hipStream_t s = (hipStream_t)stream;
+    nwstm::HeaderArgs a;
+    header_args(L, p, nch, tracks, &a, codec);
+    hipLaunchKernelGGL(nwstm::nw_header_kernel, dim3(nfiles), dim3(64), 0, s, a, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                       d_files, file_pitch);
+    VGA_HIP_TRY(hipGetLastError());
+    const uint32_t in = (uint32_t)L.channel_adpcm_bytes, il = (uint32_t)L.interleave_size, out = (uint32_t)L.audio_data_size;
+    uint8_t *audio = d_files + L.audio_data_offset;
+    if (out == 0) return VGA_OK;
+    if (sample_kind == VGA_SAMPLES_8BIT || (codec == kCodecPcm16 && L.endianness == VGA_NW_LITTLE_ENDIAN)) {
+        // the rows' bytes are the file's bytes: the GC-ADPCM interleave as it is
+        const int64_t bpitch = sample_kind == VGA_SAMPLES_S16 ? pitch * 2 : pitch;
+        const uint32_t out_blocks = (out + il - 1) / il, last_out = out - (out_blocks - 1) * il;
+        const uint64_t align = (uint64_t)(uintptr_t)d_samples | (uint64_t)bpitch | il | last_out | (uint64_t)(uintptr_t)audio |
+                               (uint64_t)(nfiles > 1 ? file_pitch : 0);
+        return container::launch_interleave_files(align, static_cast<const uint8_t *>(d_samples), bpitch, nch, nfiles, in, il, out,
+                                                  audio, file_pitch, s);
+    }
+    return pcm::launch_interleave_files(codec == kCodecPcm16 ? pcm::kSwap16 : pcm::kPcm8, static_cast<const int16_t *>(d_samples),
+                                        pitch, nch, nfiles, in, il, out, audio, file_pitch, s);
+}
+
+int vga_nwstm_pcm_write(const vga_nwstm_params *p, int codec, int nch, const vga_nw_track *tracks, const void *const *samples,
+                        int sample_kind, uint8_t *file_out)
+{
+    vga_nwstm_layout L;
+    if (int rc = vga_nwstm_pcm_layout_for(p, codec, nch, &L)) return rc;
+    if (int rc = check_track_list(p, tracks)) return rc;
+    if (sample_kind != VGA_SAMPLES_S16 && sample_kind != VGA_SAMPLES_8BIT) { set_error("unknown sample kind %d", sample_kind); return VGA_ERR_ARGUMENT; }
+    if (!file_out || (p->sample_count > 0 && !samples)) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
+    for (int c = 0; c < nch && p->sample_count > 0; c++)
+        if (!samples[c]) { set_error("channel %d: null pointer", c); return VGA_ERR_ARGUMENT; }
+    if (int rc = require_device()) return rc;
+    Stream st;
+    VGA_HIP_TRY(st.create());
+    const int es = sample_kind == VGA_SAMPLES_S16 ? 2 : 1;
+    const int64_t pitch = round_up(p->sample_count > 0 ? p->sample_count : 1, 16);
+    DevBuf d_in, d_file;
+    VGA_HIP_TRY(d_in.alloc((size_t)nch * pitch * es));
+    VGA_HIP_TRY(d_file.alloc((size_t)L.file_size));
+    for (int c = 0; c < nch && p->sample_count > 0; c++)
+        VGA_HIP_TRY(hipMemcpyAsync(d_in.as<uint8_t>() + c * pitch * es, samples[c], (size_t)p->sample_count * es, hipMemcpyHostToDevice, st.s));
+    if (int rc = vga_nwstm_pcm_write_device(p, codec, nch, 1, tracks, d_in.p, sample_kind, pitch, d_file.as<uint8_t>(), L.file_size, st.s))
+        return rc;
+    VGA_HIP_TRY(hipMemcpyAsync(file_out, d_file.p, (size_t)L.file_size, hipMemcpyDeviceToHost, st.s));
+    VGA_HIP_TRY(hipStreamSynchronize(st.s));
+    return VGA_OK;
+}
+
+// BrstmReader / BCFstmReader up to the audio for PCM8 / PCM16 streams (Common.ToPcm16Stream / ToPcm8Stream)
+int vga_nwstm_pcm_parse(const uint8_t *file, size_t size, vga_nwstm_info *out) { return parse_nw(file, size, out, true); }
+
+int vga_nwstm_pcm_read_device(const vga_nwstm_info *I, const uint8_t *d_files, int64_t file_pitch, int nfiles, void *d_samples,
+                              int sample_kind, int64_t pitch, void *stream)
+{
+    if (!I || nfiles < 0) { set_error("null / negative argument"); return VGA_ERR_ARGUMENT; }
+    if (I->codec != kCodecPcm8 && I->codec != kCodecPcm16) { set_error("info is not a PCM8 / PCM16 stream (vga_nwstm_pcm_parse)"); return VGA_ERR_ARGUMENT; }
+    if (sample_kind != VGA_SAMPLES_S16 && sample_kind != VGA_SAMPLES_8BIT) { set_error("unknown sample kind %d", sample_kind); return VGA_ERR_ARGUMENT; }
+    if (I->codec == kCodecPcm16 && sample_kind != VGA_SAMPLES_S16) { set_error("a PCM16 stream is read to VGA_SAMPLES_S16 rows"); return VGA_ERR_ARGUMENT; }
+    const int bps = I->codec == kCodecPcm16 ? 2 : 1;
+    if (nfiles == 0 || I->adpcm_bytes == 0) return VGA_OK;
+    const int nch = I->channel_count;
+    if (nch < 1 || I->interleave_size <= 0 || I->audio_data_length < 0 || I->audio_data_length % nch || I->adpcm_bytes != I->sample_count * bps) {
+        set_error("info does not describe a stream");
+        return VGA_ERR_ARGUMENT;
+    }
+    if (!d_files || !d_samples || pitch < I->sample_count) { set_error("null pointer / pitch < %d", I->sample_count); return VGA_ERR_ARGUMENT; }
+    if (nfiles > 1 && file_pitch < (int64_t)I->audio_data_offset + I->audio_data_length) { set_error("file pitch smaller than the stream"); return VGA_ERR_ARGUMENT; }
+    const uint32_t in = (uint32_t)(I->audio_data_length / nch), il = (uint32_t)I->interleave_size, out = (uint32_t)I->adpcm_bytes;
+    hipStream_t s = (hipStream_t)stream;
+    if (sample_kind == VGA_SAMPLES_8BIT || (I->codec == kCodecPcm16 && I->endianness == VGA_NW_LITTLE_ENDIAN)) {
+        // the file's bytes are the rows' bytes: the GC-ADPCM de-interleave as it is
+        const int64_t bpitch = sample_kind == VGA_SAMPLES_S16 ? pitch * 2 : pitch;
+        const uint32_t in_blocks = in ? (in + il - 1) / il : 0, last_in = in ? in - (in_blocks - 1) * il : 0;
+        const uint64_t align = (uint64_t)(uintptr_t)d_files | (uint64_t)(nfiles > 1 ? file_pitch : 0) | (uint64_t)I->audio_data_offset |
+                               il | last_in | (uint64_t)(uintptr_t)d_samples | (uint64_t)bpitch;
+        return container::launch_deinterleave(align, d_files, file_pitch, I->audio_data_offset, nch, nfiles * nch, in, il, out,
+                                              static_cast<uint8_t *>(d_samples), bpitch, s);
+    }
+    return pcm::launch_deinterleave(I->codec == kCodecPcm16 ? pcm::kSwap16 : pcm::kPcm8, d_files, file_pitch, I->audio_data_offset, nch,
+                                    nfiles * nch, in, il, out, static_cast<int16_t *>(d_samples), pitch, s);
+}
+
+int vga_nwstm_pcm_read(const uint8_t *file, size_t size, const vga_nwstm_info *I, void *const *out, int sample_kind)
+{
+    if (!file || !I || !out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
+    if (sample_kind != VGA_SAMPLES_S16 && sample_kind != VGA_SAMPLES_8BIT) { set_error("unknown sample kind %d", sample_kind); return VGA_ERR_ARGUMENT; }
+    const int nch = I->channel_count;
+    if (I->audio_data_offset < 0 || (int64_t)I->audio_data_offset + I->audio_data_length > (int64_t)size) { set_error("info does not describe this file"); return VGA_ERR_ARGUMENT; }
+    for (int c = 0; c < nch; c++)
+        if (!out[c]) { set_error("channel %d: null pointer", c); return VGA_ERR_ARGUMENT; }
+    if (I->sample_count == 0) return VGA_OK;
+    if (int rc = require_device()) return rc;
+    Stream st;
+    VGA_HIP_TRY(st.create());
+    const int es = sample_kind == VGA_SAMPLES_S16 ? 2 : 1;
+    const int64_t pitch = round_up(I->sample_count, 16);
+    const size_t bytes = (size_t)I->audio_data_offset + (size_t)I->audio_data_length;
+    DevBuf d_file, d_out;
+    VGA_HIP_TRY(d_file.alloc(bytes));
+    VGA_HIP_TRY(d_out.alloc((size_t)nch * pitch * es));
+    VGA_HIP_TRY(hipMemcpyAsync(d_file.p, file, bytes, hipMemcpyHostToDevice, st.s));
+    if (int rc = vga_nwstm_pcm_read_device(I, d_file.as<uint8_t>(), (int64_t)bytes, 1, d_out.p, sample_kind, pitch, st.s)) return rc;
+    for (int c = 0; c < nch; c++)
+        VGA_HIP_TRY(hipMemcpyAsync(out[c], d_out.as<uint8_t>() + c * pitch * es, (size_t)I->sample_count * es, hipMemcpyDeviceToHost, st.s));
     VGA_HIP_TRY(hipStreamSynchronize(st.s));
     return VGA_OK;
 }

@@ -1,7 +1,7 @@
-"""NintendoWare streams for GC-ADPCM -- the host-side mirror of VGAudio/Containers/NintendoWare: BrstmWriter.cs,
+"""NintendoWare streams for GC-ADPCM, PCM16 and PCM8 -- the host-side mirror of VGAudio/Containers/NintendoWare: BrstmWriter.cs,
 BCFstmWriter.cs, BrstmReader.cs, BCFstmReader.cs, BxstmConfiguration.cs and Common.ToAdpcmStream.  Size math and
 parsing run on the host (vga_nwstm_layout_for / vga_nwstm_parse); the images are assembled and taken apart on the
-GPU (vga_nwstm_write / vga_nwstm_read).  There is no CPU path."""
+GPU (vga_nwstm_write / vga_nwstm_read; the vga_nwstm_pcm_* calls for PCM).  There is no CPU path."""
 import ctypes as C
 import enum
 
@@ -9,7 +9,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, i16p, u8p
-from .gcadpcm import AudioTrack, GcAdpcmChannel, GcAdpcmContext, GcAdpcmFormat, _i16, _ptr_array
+from .gcadpcm import AudioTrack, GcAdpcmChannel, GcAdpcmContext, GcAdpcmFormat, Pcm16Format, _i16, _ptr_array
+from .pcm8 import Pcm8Format, Pcm8SignedFormat
 
 DEFAULT_SAMPLES = 14336                          # BytesToSamples(0x2000, GcAdpcm) (BxstmConfiguration.cs:17)
 
@@ -66,15 +67,29 @@ class NwVersion:
         return "NwVersion(%d, %d, %d, %d)" % (self.Major, self.Minor, self.Micro, self.Revision)
 
 
-class BxstmConfiguration:
-    """BxstmConfiguration.cs: the options of the BRSTM, BCSTM and BFSTM writers."""
+def BytesToSamples(byteCount, codec):            # Common.cs:30-43
+    codec = NwCodec(codec)
+    if codec == NwCodec.GcAdpcm:
+        return byteCount // 8 * 14 + max(byteCount % 8 * 2 - 2, 0)
+    return {NwCodec.Pcm16Bit: byteCount // 2, NwCodec.Pcm8Bit: byteCount}.get(codec, 0)
 
-    def __init__(self, SamplesPerInterleave=DEFAULT_SAMPLES, SamplesPerSeekTableEntry=DEFAULT_SAMPLES,
-                 LoopPointAlignment=DEFAULT_SAMPLES, Endianness=None, Version=None, TrackType=BrstmTrackType.Standard,
-                 SeekTableType=BrstmSeekTableType.Standard, RecalculateSeekTable=True, RecalculateLoopContext=True):
-        self.SamplesPerInterleave = SamplesPerInterleave
-        self.SamplesPerSeekTableEntry = SamplesPerSeekTableEntry
-        self.LoopPointAlignment = LoopPointAlignment
+
+class BxstmConfiguration:
+    """BxstmConfiguration.cs: the options of the BRSTM, BCSTM and BFSTM writers.  An option left at None follows the
+    codec: BytesToSamples(0x2000, Codec), i.e. 14336 for GC-ADPCM, 4096 for PCM16 and 8192 for PCM8."""
+
+    def __init__(self, SamplesPerInterleave=None, SamplesPerSeekTableEntry=None,
+                 LoopPointAlignment=None, Endianness=None, Version=None, TrackType=BrstmTrackType.Standard,
+                 SeekTableType=BrstmSeekTableType.Standard, RecalculateSeekTable=True, RecalculateLoopContext=True,
+                 Codec=NwCodec.GcAdpcm):
+        self.Codec = NwCodec(Codec)
+        self._spi = self._spe = self._align = None
+        if SamplesPerInterleave is not None:
+            self.SamplesPerInterleave = SamplesPerInterleave
+        if SamplesPerSeekTableEntry is not None:
+            self.SamplesPerSeekTableEntry = SamplesPerSeekTableEntry
+        if LoopPointAlignment is not None:
+            self.LoopPointAlignment = LoopPointAlignment
         self.Endianness = Endianness
         self.Version = Version
         self.TrackType = BrstmTrackType(TrackType)
@@ -82,21 +97,32 @@ class BxstmConfiguration:
         self.RecalculateSeekTable = RecalculateSeekTable
         self.RecalculateLoopContext = RecalculateLoopContext
 
+    def _default(self):
+        return BytesToSamples(0x2000, self.Codec)
+
     @property
     def SamplesPerInterleave(self):
-        return self._spi
+        return self._spi if self._spi is not None else self._default()
 
     @SamplesPerInterleave.setter
-    def SamplesPerInterleave(self, value):       # :42-59
+    def SamplesPerInterleave(self, value):       # :42-59 (the divisible-by-14 rule is GC-ADPCM's)
         if value < 1:
             raise _lib.ArgumentOutOfRangeError("Number of samples per interleave must be positive")
-        if value % 14 != 0:
+        if self.Codec == NwCodec.GcAdpcm and value % 14 != 0:
             raise _lib.ArgumentOutOfRangeError("Number of samples per interleave must be divisible by 14")
         self._spi = int(value)
 
     @property
+    def LoopPointAlignment(self):
+        return self._align if self._align is not None else self._default()
+
+    @LoopPointAlignment.setter
+    def LoopPointAlignment(self, value):
+        self._align = int(value)
+
+    @property
     def SamplesPerSeekTableEntry(self):
-        return self._spe
+        return self._spe if self._spe is not None else self._default()
 
     @SamplesPerSeekTableEntry.setter
     def SamplesPerSeekTableEntry(self, value):   # :70-80
@@ -146,9 +172,62 @@ class _NwWriter:
         check(_lib.lib().vga_nwstm_layout_for(C.byref(p), fmt.ChannelCount, C.byref(L)))
         return L
 
+    def _pcm_params(self, fmt, track_count):
+        c = self.Configuration
+        p = _lib.NwParamsC()
+        p.target = int(self.target)
+        p.sample_rate = fmt.SampleRate
+        p.sample_count = fmt.SampleCount
+        p.looping = int(fmt.Looping)
+        p.loop_start, p.loop_end = fmt.LoopStart, fmt.LoopEnd
+        p.samples_per_interleave = c.SamplesPerInterleave
+        p.samples_per_seek_table_entry = c.SamplesPerSeekTableEntry
+        p.loop_point_alignment = c.LoopPointAlignment
+        p.track_type, p.seek_table_type = int(c.TrackType), int(c.SeekTableType)
+        p.version = c.Version.Version if c.Version is not None else 0
+        p.endianness = -1 if c.Endianness is None else int(c.Endianness)
+        p.track_count = track_count
+        return p
+
+    def PcmLayout(self, fmt):
+        """vga_nwstm_pcm_layout_for for the configured PCM codec (no device work)."""
+        L = _lib.NwLayoutC()
+        tracks = getattr(fmt, "Tracks", None) or AudioTrack.GetDefaultTrackList(fmt.ChannelCount)
+        p = self._pcm_params(fmt, len(tracks))
+        check(_lib.lib().vga_nwstm_pcm_layout_for(C.byref(p), int(self.Configuration.Codec), fmt.ChannelCount, C.byref(L)))
+        return L
+
+    def _get_pcm_file(self, audio):
+        """SetupWriter's Pcm16Bit / Pcm8Bit branches: GetFormat<Pcm16Format> / GetFormat<Pcm8SignedFormat>.  A
+        Pcm16Format is converted on the device while it is interleaved (EncodeSigned for PCM8)."""
+        codec = self.Configuration.Codec
+        if isinstance(audio, Pcm8SignedFormat) and codec == NwCodec.Pcm8Bit:
+            rows, kind = audio.Channels, VGA_SAMPLES_8BIT
+        elif isinstance(audio, Pcm16Format):
+            rows, kind = audio.Channels, VGA_SAMPLES_S16
+        elif isinstance(audio, Pcm8Format):
+            return self._get_pcm_file(audio.ToPcm16())
+        else:
+            raise _lib.ArgumentError("a %s stream is written from a Pcm16Format or Pcm8SignedFormat" % codec.name)
+        tracks = list(getattr(audio, "Tracks", None) or AudioTrack.GetDefaultTrackList(audio.ChannelCount))
+        p = self._pcm_params(audio, len(tracks))
+        L = _lib.NwLayoutC()
+        check(_lib.lib().vga_nwstm_pcm_layout_for(C.byref(p), int(codec), audio.ChannelCount, C.byref(L)))
+        tr = (_lib.NwTrackC * max(len(tracks), 1))()
+        for i, t in enumerate(tracks):
+            tr[i] = _lib.NwTrackC(t.ChannelCount, t.ChannelLeft, t.ChannelRight, t.Volume, t.Panning)
+        dtype = np.int16 if kind == VGA_SAMPLES_S16 else np.uint8
+        rows = [np.ascontiguousarray(r, dtype=dtype) for r in rows]
+        ptrs = (C.c_void_p * max(len(rows), 1))(*[r.ctypes.data for r in rows])
+        out = np.zeros(L.file_size, dtype=np.uint8)
+        check(_lib.lib().vga_nwstm_pcm_write(C.byref(p), int(codec), audio.ChannelCount, tr, ptrs, kind, out.ctypes.data_as(u8p)))
+        return out.tobytes()
+
     def GetFile(self, audio, configuration=None):
         if configuration is not None:
             self.Configuration = configuration
+        if self.Configuration.Codec in (NwCodec.Pcm16Bit, NwCodec.Pcm8Bit):
+            return self._get_pcm_file(audio)
         if not isinstance(audio, GcAdpcmFormat):
             raise _lib.ArgumentError("the NintendoWare writers take a GcAdpcmFormat (encode PCM with EncodeFromPcm16 first)")
         tracks = list(audio.Tracks)
@@ -196,6 +275,17 @@ class BCFstmWriter(_NwWriter):
         self.target = NwTarget(target)
 
 
+VGA_SAMPLES_S16, VGA_SAMPLES_8BIT = 0, 1          # include/vgaudio_hip_pcm.h
+
+
+def parse_pcm(data):
+    """vga_nwstm_pcm_parse: a PCM8 / PCM16 stream's header and tracks (no device work)."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    info = _lib.NwInfoC()
+    check(_lib.lib().vga_nwstm_pcm_parse(buf.ctypes.data_as(u8p), len(buf), C.byref(info)))
+    return info
+
+
 def parse(data):
     """vga_nwstm_parse: the stream's header, tracks and channel infos (no device work)."""
     buf = np.frombuffer(bytes(data), dtype=np.uint8)
@@ -239,6 +329,30 @@ class _NwReader:
                                         _ptr_array(i16p, seek) if seek else None))
         return self._to_format(info, adpcm, seek)
 
+    def ReadAnyFormat(self, data):
+        """AudioReader.ReadFormat through Common.ToAudioStream (Common.cs:45-65): GcAdpcmFormat, Pcm16Format or
+        Pcm8SignedFormat by the stream's codec byte.  The loop end reads back as SampleCount (Common.cs:105,114)."""
+        data = bytes(data)
+        if len(data) >= 4 and data[:4] not in self.magics:
+            parse(data)                                          # the reference's refusal for a foreign file
+            raise _lib.InvalidDataError("File has no %s header" % " or ".join(m.decode() for m in self.magics))
+        try:
+            info = parse_pcm(data)
+        except _lib.InvalidOperationError:
+            return self.ReadFormat(data)                         # GC-ADPCM (or a refusal of vga_nwstm_parse)
+        nch = info.channel_count
+        pcm16 = info.codec == NwCodec.Pcm16Bit
+        rows = [np.zeros(info.sample_count, dtype=np.int16 if pcm16 else np.uint8) for _ in range(nch)]
+        ptrs = (C.c_void_p * nch)(*[r.ctypes.data for r in rows])
+        buf = np.frombuffer(data, dtype=np.uint8)
+        check(_lib.lib().vga_nwstm_pcm_read(buf.ctypes.data_as(u8p), len(buf), C.byref(info), ptrs,
+                                            VGA_SAMPLES_S16 if pcm16 else VGA_SAMPLES_8BIT))
+        fmt = Pcm16Format(rows, info.sample_rate) if pcm16 else Pcm8SignedFormat(rows, info.sample_rate)
+        fmt.WithLoop(bool(info.looping), info.loop_start, info.sample_count)
+        tracks = [AudioTrack(t.channel_count, t.left, t.right, t.volume, t.panning) for t in info.tracks[:info.track_count]]
+        fmt.Tracks = tracks if tracks else AudioTrack.GetDefaultTrackList(nch)
+        return fmt
+
     @staticmethod
     def _to_format(info, adpcm, seek):
         """Common.ToAdpcmStream (Common.cs:67-97)."""
@@ -270,8 +384,9 @@ class BCFstmReader(_NwReader):
 
 def configuration_of(info):
     """GetConfiguration (BrstmReader.cs:40-54, BCFstmReader.cs:52-69): the options that write the file again."""
-    c = BxstmConfiguration()
-    c.SamplesPerSeekTableEntry = info.samples_per_seek_table_entry
+    c = BxstmConfiguration(Codec=info.codec)
+    if info.codec == NwCodec.GcAdpcm or info.target != NwTarget.Revolution:
+        c.SamplesPerSeekTableEntry = info.samples_per_seek_table_entry
     c.SamplesPerInterleave = info.samples_per_interleave
     if info.target == NwTarget.Revolution:
         c.TrackType = BrstmTrackType(info.track_type)
