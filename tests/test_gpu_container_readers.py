@@ -157,14 +157,27 @@ def test_adx_device_read_equals_host_read_every_residue(offset):
 @pytest.mark.parametrize("offset", range(16))
 @pytest.mark.parametrize("nch", [1, 2, 3])
 def test_dsp_device_read_equals_host_read(offset, nch):
-    fmt = GcAdpcmFormat().EncodeFromPcm16(pcm16(nch, 14 * 300 + offset))
+    _dsp_device_read_equals_host_read(nch, 14 * 300 + offset, offset)
+
+
+@pytest.mark.parametrize("offset", range(16))
+@pytest.mark.parametrize("nch", [2, 3])
+def test_dsp_device_read_short_last_block(offset, nch):
+    """interleave 64 bytes, last block 8, files 16 bytes apart: at offset 0 the read moves 16-byte granules, and the last
+    block, shorter than one, goes byte by byte"""
+    _dsp_device_read_equals_host_read(nch, 14 * 8 * 37 + 1, offset, pitch_to_16=True)
+
+
+def _dsp_device_read_equals_host_read(nch, n, offset, pitch_to_16=False):
+    fmt = GcAdpcmFormat().EncodeFromPcm16(pcm16(nch, n))
     img = DspWriter(DspConfiguration(SamplesPerInterleave=14 * 8)).GetFile(fmt)
     info = _lib.DspInfoC()
     _lib.check(L().vga_dsp_parse(_u8(img).ctypes.data_as(_lib.u8p), len(img), C.byref(info)))
     for c in range(nch):
         assert np.array_equal(_host_rows(L().vga_dsp_read, info, img, nch, info.adpcm_bytes)[c], fmt.Channels[c].GetAdpcmAudio())
     nf = 4
-    d, fp, imgs = _batch(img, nf, offset, offset + 3, vary=(info.audio_offset, info.audio_offset + info.data_length), seed=offset)
+    extra = -len(img) % 16 if pitch_to_16 else offset + 3
+    d, fp, imgs = _batch(img, nf, offset, extra, vary=(info.audio_offset, info.audio_offset + info.data_length), seed=offset)
     want = [r for a in imgs for r in _host_rows(L().vga_dsp_read, info, a, nch, info.adpcm_bytes)]
     assert not np.array_equal(want[0], want[nch])                     # the files differ
     for row_pitch in ((info.adpcm_bytes + 15) // 16 * 16, info.adpcm_bytes + 1):

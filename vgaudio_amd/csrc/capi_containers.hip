@@ -1,23 +1,13 @@
 // capi_containers.hip -- C ABI of the ADX and HCA container writers (DSP lives next to the
 // GC-ADPCM entry points).  Images are assembled in HBM; the host-pointer forms stage through the device.
-#include "common.hpp"
-#include "container_kernels.hpp"
-#include "../../include/vgaudio_hip_pcm.h"
+#include "container_host.hpp"
 
-#include <algorithm>
-#include <cstring>
+#include <vector>
 
 using namespace vga;
+using namespace vga::container;
 
 namespace {
-
-int get_next_multiple(int value, int multiple)              // Utilities/Helpers.cs:71-80
-{
-    if (multiple <= 0) return value;
-    if (value % multiple == 0) return value;
-    return value + multiple - value % multiple;
-}
-int div_round_up(int v, int d) { return (v + d - 1) / d; }
 
 // Utilities/Crc16.cs:12-18 with polynomial 0x8005 (HcaWriter.cs:18), MSB first, initial value 0
 uint16_t crc16(const uint8_t *data, int size)
@@ -29,16 +19,6 @@ uint16_t crc16(const uint8_t *data, int size)
     }
     return crc;
 }
-
-struct HostCursor {
-    uint8_t *buf;
-    int size, pos;
-    bool overflow = false;
-    void put8(int v) { if (pos < size) buf[pos] = (uint8_t)v; else overflow = true; pos++; }
-    void put16(int v) { put8(v >> 8); put8(v); }
-    void put32(int v) { put16(v >> 16); put16(v); }
-    void putn(const void *p, int n) { for (int i = 0; i < n; i++) put8(((const uint8_t *)p)[i]); }
-};
 
 int adx_args(const vga_adx_file_params *p, int nch, int audio_len, vga_adx_file_layout *L, container::AdxHeaderArgs *a)
 {
@@ -80,7 +60,7 @@ int vga_adx_file_layout_for(const vga_adx_file_params *p, int nch, vga_adx_file_
     L->base_header_size = p->looping ? (p->version == 4 ? 60 : 52) : (p->version == 4 ? 36 : 32);        // :30
     if (p->looping) {                                                                                   // :58-69
         const int start = vga_adx_sample_count_to_byte_count(p->loop_start, p->frame_size) * nch + L->base_header_size + 4;
-        L->alignment_bytes = get_next_multiple(start, 0x800) - start;
+        L->alignment_bytes = (int)next_multiple(start, 0x800) - start;
         if (p->version == 3) L->alignment_bytes += p->alignment_samples / spf * 0x800;
     }
     L->header_size = L->base_header_size + L->alignment_bytes;
@@ -89,9 +69,9 @@ int vga_adx_file_layout_for(const vga_adx_file_params *p, int nch, vga_adx_file_
     if (audio_size + L->audio_offset + 0x1000 > 0x7FFFFFFF) { set_error("ADX file would exceed 2 GiB (FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
     L->audio_size = (int)audio_size;
     L->footer_offset = L->audio_offset + L->audio_size;
-    L->footer_size = p->looping ? get_next_multiple(L->footer_offset + p->frame_size, 0x800) - L->footer_offset : p->frame_size;
+    L->footer_size = p->looping ? (int)next_multiple(L->footer_offset + p->frame_size, 0x800) - L->footer_offset : p->frame_size;
     L->loop_start_offset = L->audio_offset + vga_adx_sample_count_to_byte_count(p->loop_start, p->frame_size) * nch;
-    L->loop_end_offset = L->audio_offset + get_next_multiple(vga_adx_sample_count_to_byte_count(p->loop_end, p->frame_size), p->frame_size) * nch;
+    L->loop_end_offset = L->audio_offset + (int)next_multiple(vga_adx_sample_count_to_byte_count(p->loop_end, p->frame_size), p->frame_size) * nch;
     L->file_size = L->audio_offset + L->audio_size + L->footer_size;                                    // :18
     return VGA_OK;
 }
@@ -125,23 +105,16 @@ int vga_adx_write(const uint8_t *const *audio, int audio_len, const int16_t *his
     for (int c = 0; c < nch; c++)
         if (audio_len > 0 && !audio[c]) { set_error("audio[%d] is null", c); return VGA_ERR_ARGUMENT; }
     if (p->version == 4 && !history) { set_error("version 4 headers carry the channel histories"); return VGA_ERR_ARGUMENT; }
-    if (int rc = require_device()) return rc;
-    Stream st;
-    VGA_HIP_TRY(st.create());
-    DevBuf d_audio, d_hist, d_file;
-    const int64_t pitch = round_up(audio_len > 0 ? audio_len : 1, 16);
-    VGA_HIP_TRY(d_audio.alloc((size_t)nch * pitch));
-    VGA_HIP_TRY(d_hist.alloc((size_t)nch * 2));
-    VGA_HIP_TRY(d_file.alloc((size_t)L.file_size));
-    for (int c = 0; c < nch && audio_len > 0; c++)
-        VGA_HIP_TRY(hipMemcpyAsync(d_audio.as<uint8_t>() + c * pitch, audio[c], (size_t)audio_len, hipMemcpyHostToDevice, st.s));
-    if (history) VGA_HIP_TRY(hipMemcpyAsync(d_hist.p, history, (size_t)nch * 2, hipMemcpyHostToDevice, st.s));
-    if (int rc = vga_adx_write_device(d_audio.as<uint8_t>(), pitch, audio_len, history ? d_hist.as<int16_t>() : nullptr, nch, p,
-                                      d_file.as<uint8_t>(), st.s))
-        return rc;
-    VGA_HIP_TRY(hipMemcpyAsync(file_out, d_file.p, (size_t)L.file_size, hipMemcpyDeviceToHost, st.s));
-    VGA_HIP_TRY(hipStreamSynchronize(st.s));
-    return VGA_OK;
+    HostStage h;
+    uint8_t *d_audio = nullptr;
+    const int16_t *d_hist = nullptr;
+    int64_t pitch = 0;
+    if (int rc = h.open()) return rc;
+    if (int rc = h.rows(audio, nch, audio_len, &d_audio, &pitch)) return rc;
+    if (int rc = h.table(history, (size_t)nch, &d_hist)) return rc;
+    return h.write_image(file_out, (size_t)L.file_size, [&](uint8_t *d_file, hipStream_t s) {
+        return vga_adx_write_device(d_audio, pitch, audio_len, d_hist, nch, p, d_file, s);
+    });
 }
 
 // ---------------------------------------------------------------- HCA (Containers/Hca/HcaWriter.cs:12-185)
@@ -163,7 +136,7 @@ int vga_hca_file_header(const vga_hca_info *h, const char *comment, float volume
     if (!h || !header_out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     if (h->header_size < 8 || h->header_size > 0x7FFF) { set_error("HCA header size %d out of range", h->header_size); return VGA_ERR_OUT_OF_RANGE; }
     std::memset(header_out, 0, (size_t)h->header_size);
-    HostCursor c{header_out, h->header_size - 2, 0};
+    ByteWriter c{header_out, h->header_size - 2, 0, true};
     // WriteChunkId (:158-171): with an encryption key every non-zero id byte gets its top bit set
     auto chunk = [&](const char *id, int n) { for (int i = 0; i < n; i++) c.put8(id[i] && encrypted_ids ? (id[i] | 0x80) : id[i]); };
     chunk("HCA\0", 4);                                      // :84-89
@@ -210,10 +183,10 @@ int vga_hca_file_header(const vga_hca_info *h, const char *comment, float volume
         chunk("pad", 3);                                   // :154-157: three bytes
     } else {
         chunk("comm\0", 5);                                // :148-152
-        c.putn(comment, (int)std::strlen(comment) + 1);
+        c.bytes(comment, (int)std::strlen(comment) + 1);
     }
     if (c.overflow) {
-        set_error("HCA header chunks (%d bytes) do not fit HeaderSize %d", c.pos, h->header_size);
+        set_error("HCA header chunks (%d bytes) do not fit HeaderSize %d", (int)c.pos, h->header_size);
         return VGA_ERR_INVALID_OP;
     }
     const uint16_t crc = crc16(header_out, h->header_size - 2);   // :75-79
@@ -263,23 +236,7 @@ int vga_hca_write(const vga_hca_info *h, const uint8_t *frames, const char *comm
 // ---------------------------------------------------------------- WAVE, 16-bit PCM
 namespace {
 
-// The reference's little-endian BinaryReader over the file: reads past the end throw (EndOfStreamException),
-// which the boundary reports as VGA_ERR_INVALID_DATA.
-struct RiffReader {
-    const uint8_t *p;
-    int64_t len, pos = 0;
-    bool eof = false;
-    bool has(int64_t n) { if (pos + n > len) { eof = true; return false; } return true; }
-    int u16() { if (!has(2)) return 0; const int v = p[pos] | (p[pos + 1] << 8); pos += 2; return v; }
-    int i16() { return (int16_t)u16(); }
-    int i32() { if (!has(4)) return 0; const uint32_t v = (uint32_t)p[pos] | ((uint32_t)p[pos + 1] << 8) | ((uint32_t)p[pos + 2] << 16) | ((uint32_t)p[pos + 3] << 24); pos += 4; return (int)v; }
-    bool tag(char out[4]) { if (!has(4)) return false; std::memcpy(out, p + pos, 4); pos += 4; return true; }
-    void skip_to(int64_t target) { if (target > pos) pos = std::min(target, len); }   // ReadBytes(remaining) stops at the end
-};
-
 const uint8_t kSubtypePcm[16] = {0x01, 0x00, 0x00, 0x00, 0x00, 0x00, 0x10, 0x00, 0x80, 0x00, 0x00, 0xAA, 0x00, 0x38, 0x9B, 0x71};
-
-int invalid(const char *msg) { set_error("%s", msg); return VGA_ERR_INVALID_DATA; }
 
 int wave_channel_mask(int n)                                // WaveWriter.cs:147-164
 {
@@ -293,13 +250,6 @@ int wave_channel_mask(int n)                                // WaveWriter.cs:147
     }
 }
 
-struct LeWriter {
-    uint8_t *c;
-    void tag(const char *t) { std::memcpy(c, t, 4); c += 4; }
-    void u16(int v) { c[0] = (uint8_t)v; c[1] = (uint8_t)(v >> 8); c += 2; }
-    void u32(int v) { u16(v); u16(v >> 16); }
-};
-
 int wave_header_size(const vga_wave_params *p, int nch) { return 12 + 8 + (nch > 2 ? 40 : 16) + (p->looping ? 8 + 0x3c : 0) + 8; }
 
 // WriteRiffHeader / WriteFmtChunk / WriteSmplChunk / the data chunk's header (WaveWriter.cs:56-129); every chunk
@@ -307,38 +257,37 @@ int wave_header_size(const vga_wave_params *p, int nch) { return 12 + 8 + (nch >
 void wave_header(const vga_wave_params *p, int nch, int64_t file_size, uint8_t *out, int bytes_per_sample = 2)
 {
     const int bps = bytes_per_sample;
-    LeWriter w{out};
+    ByteWriter w{out, wave_header_size(p, nch)};
     w.tag("RIFF");
-    w.u32((int)(file_size - 8));
+    w.put32((int)(file_size - 8));
     w.tag("WAVE");
     w.tag("fmt ");
-    w.u32(nch > 2 ? 40 : 16);
-    w.u16(nch > 2 ? 0xFFFE : 1);
-    w.u16(nch);
-    w.u32(p->sample_rate);
-    w.u32(p->sample_rate * bps * nch);
-    w.u16(bps * nch);
-    w.u16(8 * bps);
+    w.put32(nch > 2 ? 40 : 16);
+    w.put16(nch > 2 ? 0xFFFE : 1);
+    w.put16(nch);
+    w.put32(p->sample_rate);
+    w.put32(p->sample_rate * bps * nch);
+    w.put16(bps * nch);
+    w.put16(8 * bps);
     if (nch > 2) {
-        w.u16(22);
-        w.u16(8 * bps);
-        w.u32(wave_channel_mask(nch));
-        std::memcpy(w.c, kSubtypePcm, 16);
-        w.c += 16;
+        w.put16(22);
+        w.put16(8 * bps);
+        w.put32(wave_channel_mask(nch));
+        w.bytes(kSubtypePcm, 16);
     }
     if (p->looping) {
         w.tag("smpl");
-        w.u32(0x3c);
-        for (int i = 0; i < 7; i++) w.u32(0);
-        w.u32(1);
-        for (int i = 0; i < 3; i++) w.u32(0);
-        w.u32(p->loop_start);
-        w.u32(p->loop_end);
-        w.u32(0);
-        w.u32(0);
+        w.put32(0x3c);
+        for (int i = 0; i < 7; i++) w.put32(0);
+        w.put32(1);
+        for (int i = 0; i < 3; i++) w.put32(0);
+        w.put32(p->loop_start);
+        w.put32(p->loop_end);
+        w.put32(0);
+        w.put32(0);
     }
     w.tag("data");
-    w.u32(nch * p->sample_count * bps);
+    w.put32(nch * p->sample_count * bps);
 }
 
 }  // namespace
@@ -350,17 +299,17 @@ int vga_wave_parse(const uint8_t *file, int64_t file_len, vga_wave_info *w)
 {
     if (!file || !w || file_len < 0) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     std::memset(w, 0, sizeof *w);
-    RiffReader r{file, file_len};
+    ByteReader r{file, file_len};
     char id[4], type[4];
-    if (!r.tag(id)) return invalid("file ends inside the RIFF header");
+    if (!r.bytes(id, 4)) return invalid("file ends inside the RIFF header");
     const int64_t riff_size = r.i32();
-    if (!r.tag(type) || r.eof) return invalid("file ends inside the RIFF header");
+    if (!r.bytes(type, 4) || r.eof) return invalid("file ends inside the RIFF header");
     if (std::memcmp(id, "RIFF", 4) != 0) return invalid("Not a valid RIFF file");                    // RiffChunk.cs:21-24
     const int64_t riff_end = 8 + riff_size;                                                            // RiffParser.cs:44-45
     bool have_fmt = false, have_data = false, have_smpl = false, have_ext = false, ext_pcm = false;
     int format_tag = 0, block_align = 0, smpl_loops = 0, smpl_start = 0, smpl_end = 0;
     while (r.pos + 8 < riff_end) {
-        if (!r.tag(id)) return invalid("RIFF size runs past the end of the file");
+        if (!r.bytes(id, 4)) return invalid("RIFF size runs past the end of the file");
         const int64_t size = r.i32();
         if (r.eof) return invalid("file ends inside a chunk header");
         if (size < 0) return invalid("negative chunk size");
@@ -455,22 +404,13 @@ int vga_wave_read_pcm16(const uint8_t *file, int64_t file_len, const vga_wave_in
     const int64_t bytes = (int64_t)w->sample_count * w->channel_count * 2;
     if (w->data_offset < 0 || w->data_offset + bytes > file_len) { set_error("info does not describe this file"); return VGA_ERR_ARGUMENT; }
     if (bytes == 0) return VGA_OK;
-    if (int rc = require_device()) return rc;
-    Stream st;
-    VGA_HIP_TRY(st.create());
-    DevBuf d_in, d_out;
-    const int64_t pitch = round_up(w->sample_count, 8);
-    VGA_HIP_TRY(d_in.alloc((size_t)bytes));
-    VGA_HIP_TRY(d_out.alloc((size_t)w->channel_count * pitch * 2));
-    VGA_HIP_TRY(hipMemcpyAsync(d_in.p, file + w->data_offset, (size_t)bytes, hipMemcpyHostToDevice, st.s));
-    if (int rc = container::launch_pcm16_deinterleave(d_in.as<uint8_t>(), w->sample_count, w->channel_count, d_out.as<int16_t>(), pitch, st.s))
-        return rc;
-    for (int c = 0; c < w->channel_count; c++) {
+    for (int c = 0; c < w->channel_count; c++)
         if (!pcm_out[c]) { set_error("pcm_out[%d] is null", c); return VGA_ERR_ARGUMENT; }
-        VGA_HIP_TRY(hipMemcpyAsync(pcm_out[c], d_out.as<int16_t>() + c * pitch, (size_t)w->sample_count * 2, hipMemcpyDeviceToHost, st.s));
-    }
-    VGA_HIP_TRY(hipStreamSynchronize(st.s));
-    return VGA_OK;
+    HostStage h;
+    return h.read_rows(file + w->data_offset, (size_t)bytes, pcm_out, w->channel_count, w->sample_count, 2,
+                       [&](const uint8_t *d_data, void *d, int64_t dp, hipStream_t s) {
+                           return container::launch_pcm16_deinterleave(d_data, w->sample_count, w->channel_count, static_cast<int16_t *>(d), dp, s);
+                       });
 }
 
 // WaveWriter.FileSize (WaveWriter.cs:25-30), 16-bit
@@ -501,24 +441,17 @@ int vga_wave_write_pcm16(const int16_t *const *pcm, int nch, const vga_wave_para
     const int64_t size = vga_wave_file_size(p, nch);
     if (size < 0) return (int)size;
     if (!pcm || !file_out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
-    const int hs = wave_header_size(p, nch);
     if (p->sample_count == 0) { wave_header(p, nch, size, file_out); return VGA_OK; }
-    if (int rc = require_device()) return rc;
-    Stream st;
-    VGA_HIP_TRY(st.create());
-    DevBuf d_in, d_file;
-    const int64_t pitch = round_up(p->sample_count, 8);
-    VGA_HIP_TRY(d_in.alloc((size_t)nch * pitch * 2));
-    VGA_HIP_TRY(d_file.alloc((size_t)size));
-    for (int c = 0; c < nch; c++) {
+    HostStage h;
+    int16_t *d_in = nullptr;
+    int64_t pitch = 0;
+    if (int rc = h.open()) return rc;
+    for (int c = 0; c < nch; c++)
         if (!pcm[c]) { set_error("pcm[%d] is null", c); return VGA_ERR_ARGUMENT; }
-        VGA_HIP_TRY(hipMemcpyAsync(d_in.as<int16_t>() + c * pitch, pcm[c], (size_t)p->sample_count * 2, hipMemcpyHostToDevice, st.s));
-    }
-    if (int rc = vga_wave_write_pcm16_device(d_in.as<int16_t>(), pitch, nch, p, d_file.as<uint8_t>(), st.s)) return rc;
-    VGA_HIP_TRY(hipMemcpyAsync(file_out, d_file.p, (size_t)size, hipMemcpyDeviceToHost, st.s));
-    VGA_HIP_TRY(hipStreamSynchronize(st.s));
-    (void)hs;
-    return VGA_OK;
+    if (int rc = h.rows(pcm, nch, p->sample_count, &d_in, &pitch)) return rc;
+    return h.write_image(file_out, (size_t)size, [&](uint8_t *d_file, hipStream_t s) {
+        return vga_wave_write_pcm16_device(d_in, pitch, nch, p, d_file, s);
+    });
 }
 
 }  // extern "C"
@@ -526,7 +459,6 @@ int vga_wave_write_pcm16(const int16_t *const *pcm, int nch, const vga_wave_para
 // ---------------------------------------------------------------- WAVE, 8-bit (WaveWriter.cs with WaveCodec.Pcm8Bit)
 namespace {
 
-bool bad_kind(int kind) { if (kind == VGA_SAMPLES_S16 || kind == VGA_SAMPLES_8BIT) return false; set_error("unknown sample kind %d", kind); return true; }
 int elem_size(int kind) { return kind == VGA_SAMPLES_S16 ? 2 : 1; }
 
 }  // namespace
@@ -547,7 +479,7 @@ int vga_wave_write_pcm8_device(const void *d_samples, int sample_kind, int64_t p
 {
     const int64_t size = vga_wave_pcm8_file_size(p, nch);
     if (size < 0) return (int)size;
-    if (bad_kind(sample_kind)) return VGA_ERR_ARGUMENT;
+    if (int rc = check_sample_kind(sample_kind)) return rc;
     if (!d_file || (p->sample_count > 0 && (!d_samples || pitch < p->sample_count))) { set_error("null pointer / pitch < sample count"); return VGA_ERR_ARGUMENT; }
     uint8_t header[160];
     const int hs = wave_header_size(p, nch);
@@ -561,25 +493,19 @@ int vga_wave_write_pcm8(const void *const *samples, int sample_kind, int nch, co
 {
     const int64_t size = vga_wave_pcm8_file_size(p, nch);
     if (size < 0) return (int)size;
-    if (bad_kind(sample_kind)) return VGA_ERR_ARGUMENT;
+    if (int rc = check_sample_kind(sample_kind)) return rc;
     if (!samples || !file_out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     if (p->sample_count == 0) { wave_header(p, nch, size, file_out, 1); return VGA_OK; }
     for (int c = 0; c < nch; c++)
         if (!samples[c]) { set_error("samples[%d] is null", c); return VGA_ERR_ARGUMENT; }
-    if (int rc = require_device()) return rc;
-    Stream st;
-    VGA_HIP_TRY(st.create());
-    DevBuf d_in, d_file;
-    const int es = elem_size(sample_kind);
-    const int64_t pitch = round_up(p->sample_count, 16);
-    VGA_HIP_TRY(d_in.alloc((size_t)nch * pitch * es));
-    VGA_HIP_TRY(d_file.alloc((size_t)size));
-    for (int c = 0; c < nch; c++)
-        VGA_HIP_TRY(hipMemcpyAsync(d_in.as<uint8_t>() + c * pitch * es, samples[c], (size_t)p->sample_count * es, hipMemcpyHostToDevice, st.s));
-    if (int rc = vga_wave_write_pcm8_device(d_in.p, sample_kind, pitch, nch, p, d_file.as<uint8_t>(), st.s)) return rc;
-    VGA_HIP_TRY(hipMemcpyAsync(file_out, d_file.p, (size_t)size, hipMemcpyDeviceToHost, st.s));
-    VGA_HIP_TRY(hipStreamSynchronize(st.s));
-    return VGA_OK;
+    HostStage h;
+    void *d_in = nullptr;
+    int64_t pitch = 0;
+    if (int rc = h.open()) return rc;
+    if (int rc = h.rows(samples, nch, p->sample_count, elem_size(sample_kind), &d_in, &pitch)) return rc;
+    return h.write_image(file_out, (size_t)size, [&](uint8_t *d_file, hipStream_t s) {
+        return vga_wave_write_pcm8_device(d_in, sample_kind, pitch, nch, p, d_file, s);
+    });
 }
 
 // DeInterleave(1, nch) (WaveReader.cs:47) on the device, through Pcm8Codec.Decode for int16 rows
@@ -587,7 +513,7 @@ int vga_wave_deinterleave_pcm8_device(const uint8_t *d_data, int sample_count, i
                                       int64_t pitch, void *stream)
 {
     if (sample_count < 0 || nch < 0) { set_error("negative size"); return VGA_ERR_ARGUMENT; }
-    if (bad_kind(sample_kind)) return VGA_ERR_ARGUMENT;
+    if (int rc = check_sample_kind(sample_kind)) return rc;
     if (sample_count == 0 || nch == 0) return VGA_OK;
     if (!d_data || !d_samples || pitch < sample_count) { set_error("null pointer / pitch < sample count"); return VGA_ERR_ARGUMENT; }
     return container::launch_pcm8_deinterleave(d_data, sample_count, nch, d_samples, sample_kind == VGA_SAMPLES_S16, pitch,
@@ -598,7 +524,7 @@ int vga_wave_deinterleave_pcm8_device(const uint8_t *d_data, int sample_count, i
 int vga_wave_read_pcm8(const uint8_t *file, int64_t file_len, const vga_wave_info *w, void *const *out, int sample_kind)
 {
     if (!file || !w || !out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
-    if (bad_kind(sample_kind)) return VGA_ERR_ARGUMENT;
+    if (int rc = check_sample_kind(sample_kind)) return rc;
     if (w->bits_per_sample != 8) { set_error("only 8-bit PCM is read here (vga_wave_read_pcm16 reads 16-bit files)"); return VGA_ERR_ARGUMENT; }
     if (w->channel_count < 1) { set_error("info does not describe this file"); return VGA_ERR_ARGUMENT; }
     if (w->data_size % w->channel_count != 0) {                                                        // Interleave.cs:83-85
@@ -610,21 +536,11 @@ int vga_wave_read_pcm8(const uint8_t *file, int64_t file_len, const vga_wave_inf
     for (int c = 0; c < w->channel_count; c++)
         if (!out[c]) { set_error("out[%d] is null", c); return VGA_ERR_ARGUMENT; }
     if (bytes == 0) return VGA_OK;
-    if (int rc = require_device()) return rc;
-    Stream st;
-    VGA_HIP_TRY(st.create());
-    DevBuf d_in, d_out;
-    const int es = elem_size(sample_kind);
-    const int64_t pitch = round_up(w->sample_count, 16);
-    VGA_HIP_TRY(d_in.alloc((size_t)bytes));
-    VGA_HIP_TRY(d_out.alloc((size_t)w->channel_count * pitch * es));
-    VGA_HIP_TRY(hipMemcpyAsync(d_in.p, file + w->data_offset, (size_t)bytes, hipMemcpyHostToDevice, st.s));
-    if (int rc = vga_wave_deinterleave_pcm8_device(d_in.as<uint8_t>(), w->sample_count, w->channel_count, d_out.p, sample_kind, pitch, st.s))
-        return rc;
-    for (int c = 0; c < w->channel_count; c++)
-        VGA_HIP_TRY(hipMemcpyAsync(out[c], d_out.as<uint8_t>() + c * pitch * es, (size_t)w->sample_count * es, hipMemcpyDeviceToHost, st.s));
-    VGA_HIP_TRY(hipStreamSynchronize(st.s));
-    return VGA_OK;
+    HostStage h;
+    return h.read_rows(file + w->data_offset, (size_t)bytes, out, w->channel_count, w->sample_count, elem_size(sample_kind),
+                       [&](const uint8_t *d_data, void *d, int64_t dp, hipStream_t s) {
+                           return vga_wave_deinterleave_pcm8_device(d_data, w->sample_count, w->channel_count, d, sample_kind, dp, s);
+                       });
 }
 
 }  // extern "C"

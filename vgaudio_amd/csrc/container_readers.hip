@@ -2,14 +2,11 @@
 // Containers/Hca/HcaReader.cs).  Parsing is host code; the audio is taken out of nfiles equally shaped images per launch
 // in HBM, in the row layouts the decoders take.  Keys and decryption stay with the caller, who composes them from the
 // existing key-search and crypt calls exactly as the reference's ToAudioStream does.
-#include "common.hpp"
-#include "container_kernels.hpp"
+#include "container_host.hpp"
 #include "hca_frame_crc.hpp"
 
-#include <algorithm>
-#include <cstring>
-
 using namespace vga;
+using namespace vga::container;
 
 namespace vga { namespace hca { int crc_pow_table(const uint16_t **out); } }   // capi_hca.hip
 
@@ -134,64 +131,6 @@ __global__ __launch_bounds__(64 * kHcaWaves) void hca_read_frames_kernel(const u
 // ---------------------------------------------------------------- host side
 namespace {
 
-// big-endian reads over a file in host memory (BinaryReader over BinaryReaderBE); a read past the end sets `eof`
-// (EndOfStreamException) and returns 0
-struct BeReader {
-    const uint8_t *p;
-    int64_t len, pos;
-    bool eof = false;
-    bool has(int64_t n) { if (pos < 0 || pos + n > len) { eof = true; return false; } return true; }
-    int u8() { if (!has(1)) return 0; return p[pos++]; }
-    int u16() { if (!has(2)) return 0; const int v = p[pos] << 8 | p[pos + 1]; pos += 2; return v; }
-    int i16() { return (int16_t)u16(); }
-    int i32()
-    {
-        if (!has(4)) return 0;
-        const uint32_t v = (uint32_t)p[pos] << 24 | (uint32_t)p[pos + 1] << 16 | (uint32_t)p[pos + 2] << 8 | p[pos + 3];
-        pos += 4;
-        return (int)v;
-    }
-};
-
-int invalid(const char *msg) { set_error("%s", msg); return VGA_ERR_INVALID_DATA; }
-int64_t next_multiple(int64_t v, int64_t m) { return m <= 0 || v % m == 0 ? v : v + m - v % m; }   // Helpers.cs:71-80
-// Extensions.cs:145, (int)Math.Ceiling((double)v / d): a negative quotient rounds towards zero (-1 / 8 -> 0)
-int div_round_up(int v, int d) { return v / d + (v % d != 0 && (v < 0) == (d < 0) ? 1 : 0); }
-
-// the general de-interleave for nfiles images (Interleave.cs:118-167)
-int deinterleave(const uint8_t *d_files, int64_t file_pitch, int nfiles, int audio_offset, int nch, uint32_t in, uint32_t il,
-                 uint32_t out, uint8_t *d_dst, int64_t dst_pitch, hipStream_t s)
-{
-    const uint32_t in_blocks = in ? (in + il - 1) / il : 0, last_in = in ? in - (in_blocks - 1) * il : 0;
-    // block sizes enter the granule only when there are several channels: one channel's single block is a plain copy,
-    // whose ragged end the kernel handles byte by byte
-    const uint64_t blocks = nch > 1 || in_blocks > 1 ? (uint64_t)il | last_in : 0;
-    const uint64_t align = (uint64_t)(uintptr_t)d_files | (uint64_t)(nfiles > 1 ? file_pitch : 0) | (uint64_t)(uint32_t)audio_offset |
-                           blocks | (uint64_t)(uintptr_t)d_dst | (uint64_t)dst_pitch;
-    return container::launch_deinterleave(align, d_files, file_pitch, audio_offset, nch, nfiles * nch, in, il, out, d_dst, dst_pitch, s);
-}
-
-// host forms: copy the image up, run the device read, copy rows back
-struct HostImage {
-    Stream st;
-    DevBuf file;
-    int upload(const uint8_t *p, size_t bytes)
-    {
-        if (int rc = require_device()) return rc;
-        VGA_HIP_TRY(st.create());
-        VGA_HIP_TRY(file.alloc(std::max<size_t>(bytes, 1)));
-        if (bytes) VGA_HIP_TRY(hipMemcpyAsync(file.p, p, bytes, hipMemcpyHostToDevice, st.s));
-        return VGA_OK;
-    }
-};
-
-int download_rows(uint8_t *const *out, int rows, const uint8_t *d, int64_t pitch, size_t bytes, hipStream_t s)
-{
-    for (int r = 0; r < rows; r++) VGA_HIP_TRY(hipMemcpyAsync(out[r], d + r * pitch, bytes, hipMemcpyDeviceToHost, s));
-    VGA_HIP_TRY(hipStreamSynchronize(s));
-    return VGA_OK;
-}
-
 thread_local int g_adx_read_general = 0;     // vga_testing_adx_read_general_this_thread (its own file: the codec kernels'
                                              // headers, which stamp the committed profiles, stay untouched)
 
@@ -214,7 +153,7 @@ int vga_dsp_parse(const uint8_t *file, size_t size, vga_dsp_info *out)
     if (!file || !out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     std::memset(out, 0, sizeof *out);
     vga_dsp_info &I = *out;
-    BeReader r{file, (int64_t)size, 0};
+    ByteReader r{file, (int64_t)size, 0, true};
     I.sample_count = r.i32();                               // ReadHeader (:57-101)
     I.nibble_count = r.i32();
     I.sample_rate = r.i32();
@@ -279,12 +218,12 @@ int vga_dsp_read_device(const vga_dsp_info *I, const uint8_t *d_files, int64_t f
         set_error("info does not describe a DSP file");
         return VGA_ERR_ARGUMENT;
     }
-    if (!d_files || !d_adpcm || adpcm_pitch < I->adpcm_bytes) { set_error("null pointer / adpcm pitch < %d", I->adpcm_bytes); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 1 && file_pitch < (int64_t)I->audio_offset + I->data_length) { set_error("file pitch smaller than the file"); return VGA_ERR_ARGUMENT; }
+    if (int rc = check_read_batch(d_files, d_adpcm, adpcm_pitch, I->adpcm_bytes, nfiles, file_pitch, (int64_t)I->audio_offset + I->data_length))
+        return rc;
     const uint32_t out = (uint32_t)I->adpcm_bytes;
     // mono: the bytes verbatim, one block; several channels: DeInterleave(length, interleave, nch, bytes)
     const uint32_t in = nch == 1 ? out : (uint32_t)(I->data_length / nch), il = nch == 1 ? out : (uint32_t)I->interleave_size;
-    return deinterleave(d_files, file_pitch, nfiles, I->audio_offset, nch, in, il, out, d_adpcm, adpcm_pitch, (hipStream_t)stream);
+    return deinterleave_images(d_files, file_pitch, nfiles, I->audio_offset, nch, in, il, out, d_adpcm, adpcm_pitch, (hipStream_t)stream);
 }
 
 int vga_dsp_read(const uint8_t *file, size_t size, const vga_dsp_info *I, uint8_t *const *adpcm_out)
@@ -299,13 +238,10 @@ int vga_dsp_read(const uint8_t *file, size_t size, const vga_dsp_info *I, uint8_
         if (!adpcm_out[c]) { set_error("channel %d: null pointer", c); return VGA_ERR_ARGUMENT; }
     if (I->adpcm_bytes == 0) return VGA_OK;
     const size_t bytes = (size_t)I->audio_offset + (size_t)I->data_length;
-    HostImage h;
-    if (int rc = h.upload(file, bytes)) return rc;
-    const int64_t pitch = round_up(I->adpcm_bytes, 16);
-    DevBuf d_out;
-    VGA_HIP_TRY(d_out.alloc((size_t)nch * pitch));
-    if (int rc = vga_dsp_read_device(I, h.file.as<uint8_t>(), (int64_t)bytes, 1, d_out.as<uint8_t>(), pitch, h.st.s)) return rc;
-    return download_rows(adpcm_out, nch, d_out.as<uint8_t>(), pitch, (size_t)I->adpcm_bytes, h.st.s);
+    HostStage h;
+    return h.read_rows(file, bytes, adpcm_out, nch, I->adpcm_bytes, 1, [&](const uint8_t *f, void *d, int64_t dp, hipStream_t s) {
+        return vga_dsp_read_device(I, f, (int64_t)bytes, 1, static_cast<uint8_t *>(d), dp, s);
+    });
 }
 
 // ---------------------------------------------------------------- ADX
@@ -314,7 +250,7 @@ int vga_adx_parse(const uint8_t *file, size_t size, vga_adx_file_info *out)
     if (!file || !out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     std::memset(out, 0, sizeof *out);
     vga_adx_file_info &I = *out;
-    BeReader r{file, (int64_t)size, 0};
+    ByteReader r{file, (int64_t)size, 0, true};
     const int sig = r.u16();                                // ReadFile (:18-21)
     if (r.eof || sig != 0x8000) return invalid("File doesn't have ADX signature (0x80 0x00)");
     I.header_size = r.i16();                                // ReadHeader (:71-114)
@@ -375,15 +311,15 @@ int vga_adx_read_device(const vga_adx_file_info *I, const uint8_t *d_files, int6
         set_error("info does not describe an ADX file");
         return VGA_ERR_ARGUMENT;
     }
-    if (!d_files || !d_audio || audio_pitch < I->audio_bytes) { set_error("null pointer / audio pitch < %d", I->audio_bytes); return VGA_ERR_ARGUMENT; }
-    const int64_t image = (int64_t)I->audio_offset + (int64_t)I->audio_bytes * nch;
-    if (nfiles > 1 && file_pitch < image) { set_error("file pitch smaller than the file"); return VGA_ERR_ARGUMENT; }
+    if (int rc = check_read_batch(d_files, d_audio, audio_pitch, I->audio_bytes, nfiles, file_pitch,
+                                  (int64_t)I->audio_offset + (int64_t)I->audio_bytes * nch))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     const bool fast = fs == readers::kAdxFrame && nch <= readers::kAdxMaxFastChannels && !g_adx_read_general &&
                       !(((uint64_t)(uintptr_t)d_audio | (uint64_t)audio_pitch) & 15);
     if (!fast) {
         const uint32_t row = (uint32_t)I->audio_bytes;
-        return deinterleave(d_files, file_pitch, nfiles, I->audio_offset, nch, row, (uint32_t)fs, row, d_audio, audio_pitch, s);
+        return deinterleave_images(d_files, file_pitch, nfiles, I->audio_offset, nch, row, (uint32_t)fs, row, d_audio, audio_pitch, s);
     }
     const int span = readers::kAdxSpanBytes / (readers::kAdxFrame * nch) / 8 * 8;
     const unsigned spans = (unsigned)((I->frame_count + span - 1) / span);
@@ -405,13 +341,10 @@ int vga_adx_read(const uint8_t *file, size_t size, const vga_adx_file_info *I, u
     for (int c = 0; c < nch; c++)
         if (!audio_out[c]) { set_error("channel %d: null pointer", c); return VGA_ERR_ARGUMENT; }
     if (I->audio_bytes == 0) return VGA_OK;
-    HostImage h;
-    if (int rc = h.upload(file, (size_t)bytes)) return rc;
-    const int64_t pitch = round_up(I->audio_bytes, 16);
-    DevBuf d_out;
-    VGA_HIP_TRY(d_out.alloc((size_t)nch * pitch));
-    if (int rc = vga_adx_read_device(I, h.file.as<uint8_t>(), bytes, 1, d_out.as<uint8_t>(), pitch, h.st.s)) return rc;
-    return download_rows(audio_out, nch, d_out.as<uint8_t>(), pitch, (size_t)I->audio_bytes, h.st.s);
+    HostStage h;
+    return h.read_rows(file, (size_t)bytes, audio_out, nch, I->audio_bytes, 1, [&](const uint8_t *f, void *d, int64_t dp, hipStream_t s) {
+        return vga_adx_read_device(I, f, bytes, 1, static_cast<uint8_t *>(d), dp, s);
+    });
 }
 
 // ---------------------------------------------------------------- HCA
@@ -422,12 +355,11 @@ int vga_hca_parse(const uint8_t *file, size_t size, vga_hca_file_info *out)
     vga_hca_file_info &I = *out;
     vga_hca_info &H = I.hca;
     I.volume = 1.0f;                                        // HcaInfo.Volume's default (HcaInfo.cs:45)
-    BeReader r{file, (int64_t)size, 0};
+    ByteReader r{file, (int64_t)size, 0, true};
     char id[5] = {0};
     auto chunk_id = [&]() {                                 // ReadChunkId (:226-236): top bits cleared
-        if (!r.has(4)) return false;
-        for (int k = 0; k < 4; k++) id[k] = (char)(file[r.pos + k] & 0x7f);
-        r.pos += 4;
+        if (!r.bytes(id, 4)) return false;
+        for (int k = 0; k < 4; k++) id[k] &= 0x7f;
         return true;
     };
     const bool have_sig = chunk_id();                       // ReadHcaHeader (:59-121)
@@ -576,18 +508,21 @@ int vga_hca_read(const uint8_t *file, size_t size, const vga_hca_file_info *I, u
     if (H.frame_count < 0 || I->frames_offset < 0 || I->frames_offset + bytes > (int64_t)size) { set_error("info does not describe this file"); return VGA_ERR_ARGUMENT; }
     if (bad_crc_out) *bad_crc_out = 0;
     if (bytes == 0) return VGA_OK;
-    HostImage h;
-    if (int rc = h.upload(file, (size_t)(I->frames_offset + bytes))) return rc;
-    DevBuf d_out, d_bad;
+    HostStage h;
+    const uint8_t *d_file = nullptr;
+    void *d_out = nullptr, *d_bad = nullptr;
     const int64_t pitch = round_up(bytes + 8, 16);
-    VGA_HIP_TRY(d_out.alloc((size_t)pitch));
-    VGA_HIP_TRY(d_bad.alloc(sizeof(int)));
-    if (int rc = vga_hca_read_device(I, h.file.as<uint8_t>(), I->frames_offset + bytes, 1, d_out.as<uint8_t>(), pitch, d_bad.as<int>(), h.st.s))
-        return rc;
-    VGA_HIP_TRY(hipMemcpyAsync(frames_out, d_out.p, (size_t)bytes, hipMemcpyDeviceToHost, h.st.s));
     int bad = 0;
-    VGA_HIP_TRY(hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, h.st.s));
-    VGA_HIP_TRY(hipStreamSynchronize(h.st.s));
+    if (int rc = h.open()) return rc;
+    if (int rc = h.image(file, (size_t)(I->frames_offset + bytes), &d_file)) return rc;
+    if (int rc = h.alloc((size_t)pitch, &d_out)) return rc;
+    if (int rc = h.alloc(sizeof(int), &d_bad)) return rc;
+    if (int rc = vga_hca_read_device(I, d_file, I->frames_offset + bytes, 1, static_cast<uint8_t *>(d_out), pitch, static_cast<int *>(d_bad),
+                                     h.stream()))
+        return rc;
+    if (int rc = h.back(frames_out, d_out, (size_t)bytes)) return rc;
+    if (int rc = h.back(&bad, d_bad, sizeof bad)) return rc;
+    if (int rc = h.finish()) return rc;
     if (bad_crc_out) *bad_crc_out = bad;
     return VGA_OK;
 }

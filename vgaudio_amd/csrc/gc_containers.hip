@@ -2,14 +2,12 @@
 // (Containers/Idsp/IdspWriter.cs, IdspReader.cs) and GENH (Containers/Genh/GenhReader.cs; the reference has no
 // writer).  Size math and parsing are host code; the images are assembled and taken apart in HBM, nfiles equally
 // shaped files per launch.  Everything on the device is byte movement: HBM-bound, every image byte written once.
-#include "common.hpp"
-#include "container_kernels.hpp"
+#include "container_host.hpp"
 
-#include <algorithm>
-#include <cstring>
 #include <vector>
 
 using namespace vga;
+using namespace vga::container;
 
 namespace {
 
@@ -17,49 +15,12 @@ constexpr int kMaxChannels = VGA_GC_CONTAINER_MAX_CHANNELS;
 constexpr int kHpsMaxBlockSize = 0x10000;                   // HpsWriter.MaxBlockSize, written for every channel count
 constexpr int kIdspStreamInfoSize = 0x40, kIdspChannelInfoSize = 0x60;   // IdspWriter.cs:33-34
 
-int64_t next_multiple(int64_t v, int64_t m) { return m <= 0 || v % m == 0 ? v : v + m - v % m; }   // Helpers.cs:71-80
-int div_round_up(int v, int d) { return v / d + (v % d != 0 ? 1 : 0); }                          // Extensions.cs:145
-int bytes_of(int samples) { return vga_gcadpcm_sample_count_to_byte_count(samples); }
-bool loop_points_aligned(int loop_start, int multiple) { return !(multiple != 0 && loop_start % multiple != 0); }   // Helpers.cs:82
-
-int invalid(const char *msg) { set_error("%s", msg); return VGA_ERR_INVALID_DATA; }
-int out_of_range(const char *msg) { set_error("%s", msg); return VGA_ERR_OUT_OF_RANGE; }
-
 int check_channels(int nch)
 {
     if (nch < 1) { set_error("channel count %d: at least one channel", nch); return VGA_ERR_ARGUMENT; }
     if (nch > kMaxChannels) { set_error("%d channels: at most %d are written here", nch, kMaxChannels); return VGA_ERR_INVALID_OP; }
     return VGA_OK;
 }
-
-// AudioFormatBaseBuilder.WithLoop (:30-43)
-int check_loop(int looping, int loop_start, int loop_end, int sample_count)
-{
-    if (sample_count < 0) return out_of_range("negative sample count");
-    if (!looping) return VGA_OK;
-    if (loop_start < 0 || loop_start > sample_count || loop_end < 0 || loop_end > sample_count)
-        return out_of_range("Loop points must be less than the number of samples and non-negative.");
-    if (loop_end < loop_start) return out_of_range("The loop end must be greater than the loop start");
-    return VGA_OK;
-}
-
-// Big- or little-endian reads over a file in host memory; reads past the end set `eof` (EndOfStreamException).
-struct Reader {
-    const uint8_t *p;
-    int64_t len, pos;
-    bool big, eof = false;
-    bool has(int64_t n) { if (pos < 0 || pos + n > len) { eof = true; return false; } return true; }
-    int u16() { if (!has(2)) return 0; const int v = big ? (p[pos] << 8 | p[pos + 1]) : (p[pos] | p[pos + 1] << 8); pos += 2; return v; }
-    int i16() { return (int16_t)u16(); }
-    int i32()
-    {
-        if (!has(4)) return 0;
-        const uint32_t b0 = p[pos], b1 = p[pos + 1], b2 = p[pos + 2], b3 = p[pos + 3];
-        pos += 4;
-        return (int)(big ? (b0 << 24 | b1 << 16 | b2 << 8 | b3) : (b3 << 24 | b2 << 16 | b1 << 8 | b0));
-    }
-    bool magic(const char *t, int n) { if (!has(n)) return false; const bool ok = std::memcmp(p + pos, t, n) == 0; pos += n; return ok; }
-};
 
 }  // namespace
 
@@ -375,77 +336,23 @@ int check_write(int nfiles, int nch, const uint8_t *d_adpcm, int64_t adpcm_pitch
     if (!d_files || !d_coefs || (adpcm_len > 0 && !d_adpcm)) { set_error("null device pointer"); return VGA_ERR_ARGUMENT; }
     if (adpcm_len < need) { set_error("adpcm rows of %d bytes: the layout needs %d", adpcm_len, need); return VGA_ERR_ARGUMENT; }
     if (adpcm_len > 0 && adpcm_pitch < adpcm_len) { set_error("adpcm pitch < length"); return VGA_ERR_ARGUMENT; }
-    if (file_pitch < file_size || (nfiles > 1 && (file_pitch & 15))) {
-        set_error("file pitch %lld: at least the file size %d and a multiple of 16", (long long)file_pitch, file_size);
-        return VGA_ERR_ARGUMENT;
-    }
-    if ((int64_t)nfiles * nch > 0x7FFFFFFF / 16) { set_error("too many files in one call"); return VGA_ERR_ARGUMENT; }
-    return VGA_OK;
+    return check_write_files(nfiles, nch, file_pitch, file_size);
 }
 
-// the general de-interleave (Interleave.cs:118-167) for nfiles images: one channel's single block is a plain copy, so
-// the block sizes enter the granule only when there are several channels or blocks.  The short last block (GENH's is
-// not padded) starts at last_in * channel in every row; the kernel moves a granule there only where the block holds a
-// whole one, so a last block shorter than the granule does not shrink it.
-int deinterleave(const uint8_t *d_files, int64_t file_pitch, int nfiles, int audio_offset, int nch, uint32_t in, uint32_t il,
-                 uint32_t out, uint8_t *d_dst, int64_t dst_pitch, hipStream_t s)
-{
-    const uint32_t in_blocks = in ? (in + il - 1) / il : 0, last_in = in ? in - (in_blocks - 1) * il : 0;
-    const bool several = nch > 1 || in_blocks > 1;
-    const uint64_t base = (uint64_t)(uintptr_t)d_files | (uint64_t)(nfiles > 1 ? file_pitch : 0) | (uint64_t)(uint32_t)audio_offset |
-                          (several ? (uint64_t)il : 0) | (uint64_t)(uintptr_t)d_dst | (uint64_t)dst_pitch;
-    uint64_t align = 1;
-    for (uint32_t g = 16; g > 1; g >>= 1)
-        if (!(base & (g - 1)) && (!several || last_in % g == 0 || last_in < g)) { align = base | g; break; }
-    return container::launch_deinterleave(align, d_files, file_pitch, audio_offset, nch, nfiles * nch, in, il, out, d_dst, dst_pitch, s);
-}
-
-// host forms: the image goes up, the device read runs, the rows come back
-int read_on_device(const uint8_t *file, size_t bytes, int nch, int row_bytes, uint8_t *const *out,
-                   int (*go)(const void *, const uint8_t *, int64_t, uint8_t *, int64_t, hipStream_t), const void *ctx)
-{
-    if (int rc = require_device()) return rc;
-    Stream st;
-    VGA_HIP_TRY(st.create());
-    DevBuf d_file, d_out;
-    const int64_t pitch = round_up(std::max(row_bytes, 1), 16);
-    VGA_HIP_TRY(d_file.alloc(std::max<size_t>(bytes, 1)));
-    VGA_HIP_TRY(d_out.alloc((size_t)nch * pitch));
-    if (bytes) VGA_HIP_TRY(hipMemcpyAsync(d_file.p, file, bytes, hipMemcpyHostToDevice, st.s));
-    if (int rc = go(ctx, d_file.as<uint8_t>(), (int64_t)bytes, d_out.as<uint8_t>(), pitch, st.s)) return rc;
-    for (int c = 0; c < nch; c++)
-        VGA_HIP_TRY(hipMemcpyAsync(out[c], d_out.as<uint8_t>() + c * pitch, (size_t)row_bytes, hipMemcpyDeviceToHost, st.s));
-    VGA_HIP_TRY(hipStreamSynchronize(st.s));
-    return VGA_OK;
-}
-
-// host forms of the writers: rows up, one device write, the image back
-struct HostRows {
-    Stream st;
-    DevBuf adpcm, coefs, gain, start, loop, pcm, file;
-    int64_t apitch = 16;
-    int up(const uint8_t *const *rows, int nch, int len)
+// the HPS and IDSP writers' host forms: the rows and tables go up
+struct StagedAdpcm {
+    uint8_t *adpcm = nullptr;
+    const int16_t *coefs = nullptr, *gain = nullptr, *start = nullptr, *loop = nullptr;
+    int64_t apitch = 0;
+    int up(HostStage &h, int nch, const uint8_t *const *rows, int len, const int16_t *c, const int16_t *g, const int16_t *sc,
+           const int16_t *lc)
     {
-        if (int rc = require_device()) return rc;
-        VGA_HIP_TRY(st.create());
-        apitch = round_up(std::max(len, 1), 16);
-        VGA_HIP_TRY(adpcm.alloc((size_t)nch * apitch));
-        for (int c = 0; c < nch && len > 0; c++)
-            VGA_HIP_TRY(hipMemcpyAsync(adpcm.as<uint8_t>() + c * apitch, rows[c], (size_t)len, hipMemcpyHostToDevice, st.s));
-        return VGA_OK;
-    }
-    int shorts(DevBuf &d, const int16_t *src, size_t n)
-    {
-        if (!src) return VGA_OK;
-        VGA_HIP_TRY(d.alloc(n * 2));
-        VGA_HIP_TRY(hipMemcpyAsync(d.p, src, n * 2, hipMemcpyHostToDevice, st.s));
-        return VGA_OK;
-    }
-    int down(uint8_t *out, int size)
-    {
-        VGA_HIP_TRY(hipMemcpyAsync(out, file.p, (size_t)size, hipMemcpyDeviceToHost, st.s));
-        VGA_HIP_TRY(hipStreamSynchronize(st.s));
-        return VGA_OK;
+        if (int rc = h.open()) return rc;
+        if (int rc = h.rows(rows, nch, len, &adpcm, &apitch)) return rc;
+        if (int rc = h.table(c, (size_t)nch * 16, &coefs)) return rc;
+        if (int rc = h.table(g, (size_t)nch, &gain)) return rc;
+        if (int rc = h.table(sc, (size_t)nch * 3, &start)) return rc;
+        return h.table(lc, (size_t)nch * 3, &loop);
     }
 };
 
@@ -544,24 +451,17 @@ int vga_hps_write(const vga_hps_params *p, int nch, const uint8_t *const *adpcm,
     if (pcm && pcm_len < 0) { set_error("negative pcm length"); return VGA_ERR_ARGUMENT; }
     for (int c = 0; pcm && c < nch && pcm_len > 0; c++)
         if (!pcm[c]) { set_error("channel %d: null pcm pointer", c); return VGA_ERR_ARGUMENT; }
-    HostRows h;
-    if (int rc = h.up(adpcm, nch, adpcm_len)) return rc;
-    if (int rc = h.shorts(h.coefs, coefs, (size_t)nch * 16)) return rc;
-    if (int rc = h.shorts(h.gain, gain, (size_t)nch)) return rc;
-    if (int rc = h.shorts(h.start, start_context, (size_t)nch * 3)) return rc;
-    const int64_t ppitch = round_up(std::max(pcm_len, 1), 8);
-    if (pcm) {
-        VGA_HIP_TRY(h.pcm.alloc((size_t)nch * ppitch * 2));
-        for (int c = 0; c < nch && pcm_len > 0; c++)
-            VGA_HIP_TRY(hipMemcpyAsync(h.pcm.as<int16_t>() + c * ppitch, pcm[c], (size_t)pcm_len * 2, hipMemcpyHostToDevice, h.st.s));
-    }
-    VGA_HIP_TRY(h.file.alloc((size_t)L.file_size));
-    if (int rc = vga_hps_write_device(p, nch, 1, h.adpcm.as<uint8_t>(), h.apitch, adpcm_len, h.coefs.as<int16_t>(),
-                                      gain ? h.gain.as<int16_t>() : nullptr, start_context ? h.start.as<int16_t>() : nullptr,
-                                      pcm ? h.pcm.as<int16_t>() : nullptr, ppitch, pcm_len, h.file.as<uint8_t>(), L.file_size,
-                                      h.st.s))
-        return rc;
-    return h.down(file_out, L.file_size);
+    HostStage h;
+    StagedAdpcm w;
+    int16_t *d_pcm = nullptr;
+    int64_t ppitch = 0;
+    if (int rc = w.up(h, nch, adpcm, adpcm_len, coefs, gain, start_context, nullptr)) return rc;
+    if (pcm)
+        if (int rc = h.rows(pcm, nch, pcm_len, &d_pcm, &ppitch)) return rc;
+    return h.write_image(file_out, (size_t)L.file_size, [&](uint8_t *d_file, hipStream_t s) {
+        return vga_hps_write_device(p, nch, 1, w.adpcm, w.apitch, adpcm_len, w.coefs, w.gain, w.start, d_pcm, ppitch, pcm_len, d_file,
+                                    L.file_size, s);
+    });
 }
 
 // HpsReader.ReadFile (:14-31) and what ToAudioStream (:33-65) checks
@@ -570,7 +470,7 @@ int vga_hps_parse(const uint8_t *file, size_t size, vga_hps_info *out, vga_hps_b
     if (!file || !out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     std::memset(out, 0, sizeof *out);
     vga_hps_info &I = *out;
-    Reader r{file, (int64_t)size, 0, true};
+    ByteReader r{file, (int64_t)size, 0, true};
     if (!r.magic(" HALPST\0", 8)) return invalid("File has no HALPST header");
     I.sample_rate = r.i32();                                // ReadHeader (:67-87)
     const int nch = r.i32();
@@ -626,7 +526,7 @@ int vga_hps_parse(const uint8_t *file, size_t size, vga_hps_info *out, vga_hps_b
         if (vga_gcadpcm_nibble_to_sample(I.end_address[c]) + 1 != I.sample_count) return invalid("Channels have differing sample counts");
     if (last.next_offset != -1) {
         // the loop start block: walk the chain again (blocks may be NULL); its header carries the loop context
-        Reader w{file, (int64_t)size, 0, true};
+        ByteReader w{file, (int64_t)size, 0, true};
         int64_t cur = 0, nxt = next_multiple(std::max<int64_t>(0x80, 0x10 + 0x38 * (int64_t)nch), 0x20);
         int64_t nibble = 0;
         while (nxt > cur) {
@@ -709,12 +609,11 @@ int vga_hps_read(const uint8_t *file, size_t size, const vga_hps_info *I, const 
         }
     }
     if (I->adpcm_bytes == 0) return VGA_OK;
-    struct Ctx { const vga_hps_info *I; const vga_hps_block_info *blocks; } ctx{I, blocks};
-    return read_on_device(file, size, I->channel_count, I->adpcm_bytes, adpcm_out,
-                          [](const void *c, const uint8_t *f, int64_t fp, uint8_t *d, int64_t dp, hipStream_t s) {
-                              const Ctx &x = *static_cast<const Ctx *>(c);
-                              return vga_hps_read_device(x.I, x.blocks, f, fp, 1, d, dp, s);
-                          }, &ctx);
+    HostStage h;
+    return h.read_rows(file, size, adpcm_out, I->channel_count, I->adpcm_bytes, 1,
+                       [&](const uint8_t *f, void *d, int64_t dp, hipStream_t s) {
+                           return vga_hps_read_device(I, blocks, f, (int64_t)size, 1, static_cast<uint8_t *>(d), dp, s);
+                       });
 }
 
 // ---------------------------------------------------------------- IDSP
@@ -743,13 +642,8 @@ int vga_idsp_write_device(const vga_idsp_params *p, int nch, int nfiles, const u
         VGA_HIP_TRY(hipGetLastError());
     }
     // WriteData (:98-104): Interleave(channels, InterleaveSize, AudioDataSize)
-    const uint32_t out = (uint32_t)L.audio_data_size, il = (uint32_t)L.interleave_size;
-    if (out == 0) return VGA_OK;
-    const uint32_t out_blocks = (out + il - 1) / il, last_out = out - (out_blocks - 1) * il;
-    const uint64_t align = (uint64_t)(uintptr_t)d_adpcm | (uint64_t)adpcm_pitch | il | last_out |
-                           (uint64_t)(uintptr_t)(d_files + L.header_size) | (uint64_t)(nfiles > 1 ? file_pitch : 0);
-    return container::launch_interleave_files(align, d_adpcm, adpcm_pitch, nch, nfiles, (uint32_t)adpcm_len, il, out,
-                                              d_files + L.header_size, file_pitch, s);
+    return interleave_images(d_adpcm, adpcm_pitch, nch, nfiles, (uint32_t)adpcm_len, (uint32_t)L.interleave_size,
+                             (uint32_t)L.audio_data_size, d_files + L.header_size, file_pitch, s);
 }
 
 int vga_idsp_write(const vga_idsp_params *p, int nch, const uint8_t *const *adpcm, int adpcm_len, const int16_t *coefs,
@@ -758,18 +652,12 @@ int vga_idsp_write(const vga_idsp_params *p, int nch, const uint8_t *const *adpc
     vga_idsp_layout L;
     if (int rc = vga_idsp_layout_for(p, nch, &L)) return rc;
     if (int rc = check_host_rows(adpcm, adpcm_len, nch, coefs, file_out)) return rc;
-    HostRows h;
-    if (int rc = h.up(adpcm, nch, adpcm_len)) return rc;
-    if (int rc = h.shorts(h.coefs, coefs, (size_t)nch * 16)) return rc;
-    if (int rc = h.shorts(h.gain, gain, (size_t)nch)) return rc;
-    if (int rc = h.shorts(h.start, start_context, (size_t)nch * 3)) return rc;
-    if (int rc = h.shorts(h.loop, loop_context, (size_t)nch * 3)) return rc;
-    VGA_HIP_TRY(h.file.alloc((size_t)L.file_size));
-    if (int rc = vga_idsp_write_device(p, nch, 1, h.adpcm.as<uint8_t>(), h.apitch, adpcm_len, h.coefs.as<int16_t>(),
-                                       gain ? h.gain.as<int16_t>() : nullptr, start_context ? h.start.as<int16_t>() : nullptr,
-                                       loop_context ? h.loop.as<int16_t>() : nullptr, h.file.as<uint8_t>(), L.file_size, h.st.s))
-        return rc;
-    return h.down(file_out, L.file_size);
+    HostStage h;
+    StagedAdpcm w;
+    if (int rc = w.up(h, nch, adpcm, adpcm_len, coefs, gain, start_context, loop_context)) return rc;
+    return h.write_image(file_out, (size_t)L.file_size, [&](uint8_t *d_file, hipStream_t s) {
+        return vga_idsp_write_device(p, nch, 1, w.adpcm, w.apitch, adpcm_len, w.coefs, w.gain, w.start, w.loop, d_file, L.file_size, s);
+    });
 }
 
 // IdspReader.ReadFile (:13-31)
@@ -778,7 +666,7 @@ int vga_idsp_parse(const uint8_t *file, size_t size, vga_idsp_info *out)
     if (!file || !out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     std::memset(out, 0, sizeof *out);
     vga_idsp_info &I = *out;
-    Reader r{file, (int64_t)size, 0, true};
+    ByteReader r{file, (int64_t)size, 0, true};
     if (!r.magic("IDSP", 4)) return invalid("File has no IDSP header");
     r.pos += 4;                                             // ReadIdspHeader (:72-103)
     I.channel_count = r.i32();
@@ -835,10 +723,11 @@ int vga_idsp_read_device(const vga_idsp_info *I, const uint8_t *d_files, int64_t
         return VGA_ERR_ARGUMENT;
     }
     if (nfiles == 0 || I->adpcm_bytes == 0) return VGA_OK;
-    if (!d_files || !d_adpcm || adpcm_pitch < I->adpcm_bytes) { set_error("null pointer / adpcm pitch < %d", I->adpcm_bytes); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 1 && file_pitch < I->audio_data_offset + (int64_t)nch * I->audio_data_length) { set_error("file pitch smaller than the file"); return VGA_ERR_ARGUMENT; }
-    return deinterleave(d_files, file_pitch, nfiles, I->audio_data_offset, nch, (uint32_t)I->audio_data_length, (uint32_t)I->interleave,
-                        (uint32_t)I->adpcm_bytes, d_adpcm, adpcm_pitch, (hipStream_t)stream);
+    if (int rc = check_read_batch(d_files, d_adpcm, adpcm_pitch, I->adpcm_bytes, nfiles, file_pitch,
+                                  I->audio_data_offset + (int64_t)nch * I->audio_data_length))
+        return rc;
+    return deinterleave_images(d_files, file_pitch, nfiles, I->audio_data_offset, nch, (uint32_t)I->audio_data_length,
+                               (uint32_t)I->interleave, (uint32_t)I->adpcm_bytes, d_adpcm, adpcm_pitch, (hipStream_t)stream);
 }
 
 int vga_idsp_read(const uint8_t *file, size_t size, const vga_idsp_info *I, uint8_t *const *adpcm_out)
@@ -849,10 +738,10 @@ int vga_idsp_read(const uint8_t *file, size_t size, const vga_idsp_info *I, uint
     if (nch < 1 || nch > kMaxChannels || I->audio_data_offset < 0 || bytes > (int64_t)size) { set_error("info does not describe this file"); return VGA_ERR_ARGUMENT; }
     if (int rc = check_out_rows(adpcm_out, nch)) return rc;
     if (I->adpcm_bytes == 0) return VGA_OK;
-    return read_on_device(file, (size_t)bytes, nch, I->adpcm_bytes, adpcm_out,
-                          [](const void *c, const uint8_t *f, int64_t fp, uint8_t *d, int64_t dp, hipStream_t s) {
-                              return vga_idsp_read_device(static_cast<const vga_idsp_info *>(c), f, fp, 1, d, dp, s);
-                          }, I);
+    HostStage h;
+    return h.read_rows(file, (size_t)bytes, adpcm_out, nch, I->adpcm_bytes, 1, [&](const uint8_t *f, void *d, int64_t dp, hipStream_t s) {
+        return vga_idsp_read_device(I, f, bytes, 1, static_cast<uint8_t *>(d), dp, s);
+    });
 }
 
 // ---------------------------------------------------------------- GENH
@@ -862,7 +751,7 @@ int vga_genh_parse(const uint8_t *file, size_t size, vga_genh_info *out)
     if (!file || !out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     std::memset(out, 0, sizeof *out);
     vga_genh_info &I = *out;
-    Reader r{file, (int64_t)size, 0, false};
+    ByteReader r{file, (int64_t)size, 0, false};
     if (!r.magic("GENH", 4)) return invalid("File has no GENH header");
     I.channel_count = r.i32();
     I.interleave = r.i32();
@@ -882,7 +771,7 @@ int vga_genh_parse(const uint8_t *file, size_t size, vga_genh_info *out)
     if (I.channel_count < 1) return invalid("File must have at least one channel.");
     if (I.channel_count > 2) return invalid("GENH does not support more than 2 channels with NGC DSP files.");
     if (I.header_size > I.audio_data_offset) return invalid("Audio data must come after the GENH header.");
-    Reader c{file, (int64_t)size, 0, (I.coef_type & 2) == 0};   // GenhCoefType.LittleEndian = 2, else big-endian
+    ByteReader c{file, (int64_t)size, 0, (I.coef_type & 2) == 0};   // GenhCoefType.LittleEndian = 2, else big-endian
     for (int ch = 0; ch < I.channel_count; ch++) {
         c.pos = I.coef_offset[ch];
         if (I.coef_type & 1) {                              // GenhCoefType.Split
@@ -913,11 +802,12 @@ int vga_genh_read_device(const vga_genh_info *I, const uint8_t *d_files, int64_t
     const int nch = I->channel_count;
     if (nch < 1 || nch > 2 || I->interleave <= 0 || I->adpcm_bytes < 0) { set_error("info does not describe a GENH file"); return VGA_ERR_ARGUMENT; }
     if (nfiles == 0 || I->adpcm_bytes == 0) return VGA_OK;
-    if (!d_files || !d_adpcm || adpcm_pitch < I->adpcm_bytes) { set_error("null pointer / adpcm pitch < %d", I->adpcm_bytes); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 1 && file_pitch < I->audio_data_offset + (int64_t)nch * I->adpcm_bytes) { set_error("file pitch smaller than the file"); return VGA_ERR_ARGUMENT; }
+    if (int rc = check_read_batch(d_files, d_adpcm, adpcm_pitch, I->adpcm_bytes, nfiles, file_pitch,
+                                  I->audio_data_offset + (int64_t)nch * I->adpcm_bytes))
+        return rc;
     // no output size: every channel's row is its whole input (inputSize = length / ChannelCount)
-    return deinterleave(d_files, file_pitch, nfiles, I->audio_data_offset, nch, (uint32_t)I->adpcm_bytes, (uint32_t)I->interleave,
-                        (uint32_t)I->adpcm_bytes, d_adpcm, adpcm_pitch, (hipStream_t)stream);
+    return deinterleave_images(d_files, file_pitch, nfiles, I->audio_data_offset, nch, (uint32_t)I->adpcm_bytes,
+                               (uint32_t)I->interleave, (uint32_t)I->adpcm_bytes, d_adpcm, adpcm_pitch, (hipStream_t)stream);
 }
 
 int vga_genh_read(const uint8_t *file, size_t size, const vga_genh_info *I, uint8_t *const *adpcm_out)
@@ -928,10 +818,10 @@ int vga_genh_read(const uint8_t *file, size_t size, const vga_genh_info *I, uint
     if (nch < 1 || nch > 2 || I->audio_data_offset < 0 || bytes > (int64_t)size) { set_error("info does not describe this file"); return VGA_ERR_ARGUMENT; }
     if (int rc = check_out_rows(adpcm_out, nch)) return rc;
     if (I->adpcm_bytes == 0) return VGA_OK;
-    return read_on_device(file, (size_t)bytes, nch, I->adpcm_bytes, adpcm_out,
-                          [](const void *c, const uint8_t *f, int64_t fp, uint8_t *d, int64_t dp, hipStream_t s) {
-                              return vga_genh_read_device(static_cast<const vga_genh_info *>(c), f, fp, 1, d, dp, s);
-                          }, I);
+    HostStage h;
+    return h.read_rows(file, (size_t)bytes, adpcm_out, nch, I->adpcm_bytes, 1, [&](const uint8_t *f, void *d, int64_t dp, hipStream_t s) {
+        return vga_genh_read_device(I, f, bytes, 1, static_cast<uint8_t *>(d), dp, s);
+    });
 }
 
 }  // extern "C"

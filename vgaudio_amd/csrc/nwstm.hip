@@ -2,16 +2,11 @@
 // BCSTM / BFSTM (BCFstmWriter.cs, BCFstmReader.cs).  Size math and parsing are host code; the images are assembled
 // and taken apart in HBM, nfiles equally shaped files per launch.  Everything on the device is byte movement:
 // HBM-bound, every byte of an image read or written once.
-#include "common.hpp"
-#include "container_kernels.hpp"
+#include "container_host.hpp"
 #include "pcm_kernels.hpp"
-#include "../../include/vgaudio_hip_pcm.h"
-
-#include <algorithm>
-#include <cstring>
-#include <type_traits>
 
 using namespace vga;
+using namespace vga::container;
 
 namespace {
 
@@ -24,10 +19,6 @@ enum : int {
     kStreamInfo = 0x4100, kTrackInfo = 0x4101, kChannelInfo = 0x4102
 };
 constexpr int kCodecPcm8 = 0, kCodecPcm16 = 1, kCodecGcAdpcm = 2;   // NwCodec.cs
-
-int64_t next_multiple(int64_t v, int64_t m) { return m <= 0 || v % m == 0 ? v : v + m - v % m; }   // Helpers.cs:71-80
-int div_round_up(int v, int d) { return v / d + (v % d != 0 ? 1 : 0); }                          // Extensions.cs:145
-int bytes_of(int samples) { return vga_gcadpcm_sample_count_to_byte_count(samples); }
 
 // Common.cs:103-140 on a packed NwVersion
 bool include_track_info(uint32_t v) { const int major = v >> 24; return (major == 0 && v <= 0x00020000u) || (major >= 2 && v <= 0x02010000u); }
@@ -273,14 +264,9 @@ using container::kMaxGridY;
 // ---------------------------------------------------------------- host side
 namespace {
 
-int out_of_range(const char *msg) { set_error("%s", msg); return VGA_ERR_OUT_OF_RANGE; }
-
+// the layout has checked the track count
 int check_track_list(const vga_nwstm_params *p, const vga_nw_track *tracks)
 {
-    if (p->track_count < 0 || p->track_count > VGA_NW_MAX_TRACKS) {
-        set_error("track count %d out of range (0 = the default list, at most %d)", p->track_count, VGA_NW_MAX_TRACKS);
-        return VGA_ERR_OUT_OF_RANGE;
-    }
     if (p->track_count > 0 && !tracks) { set_error("track_count %d with a null track list", p->track_count); return VGA_ERR_ARGUMENT; }
     return VGA_OK;
 }
@@ -319,28 +305,8 @@ void header_args(const vga_nwstm_layout &L, const vga_nwstm_params *p, int nch, 
     fill_tracks(L, tracks, a);
 }
 
-// Big- or little-endian reads over a file in host memory; reads past the end set `eof` (EndOfStreamException).
-struct Reader {
-    const uint8_t *p;
-    int64_t len, pos;
-    bool big, eof = false;
-    bool has(int64_t n) { if (pos < 0 || pos + n > len) { eof = true; return false; } return true; }
-    int u8() { if (!has(1)) return 0; return p[pos++]; }
-    int u16() { if (!has(2)) return 0; const int v = big ? (p[pos] << 8 | p[pos + 1]) : (p[pos] | p[pos + 1] << 8); pos += 2; return v; }
-    int i16() { return (int16_t)u16(); }
-    int i32()
-    {
-        if (!has(4)) return 0;
-        const uint32_t b0 = p[pos], b1 = p[pos + 1], b2 = p[pos + 2], b3 = p[pos + 3];
-        pos += 4;
-        return (int)(big ? (b0 << 24 | b1 << 16 | b2 << 8 | b3) : (b3 << 24 | b2 << 16 | b1 << 8 | b0));
-    }
-    bool tag(const char *t) { if (!has(4)) return false; const bool ok = std::memcmp(p + pos, t, 4) == 0; pos += 4; return ok; }
-};
 struct Ref { int type, offset, base; int abs() const { return base + offset; } bool is(int t) const { return type == t && offset > 0; } };
-Ref read_ref(Reader &r, int base) { Ref x; x.type = r.i16(); r.pos += 2; x.offset = r.i32(); x.base = base; return x; }
-
-int invalid(const char *msg) { set_error("%s", msg); return VGA_ERR_INVALID_DATA; }
+Ref read_ref(ByteReader &r, int base) { Ref x; x.type = r.i16(); r.pos += 2; x.offset = r.i32(); x.base = base; return x; }
 
 int pcm_codec_check(int codec)
 {
@@ -378,6 +344,112 @@ int target_and_version(const vga_nwstm_params *p, vga_nwstm_layout *L)
     return VGA_OK;
 }
 
+// BxstmConfiguration.cs:42-100 and the size math of BrstmWriter.cs:22-74 / BCFstmWriter.cs:23-83 for a GC-ADPCM, PCM8 or
+// PCM16 stream (L zeroed by the caller).  PCM has no divisible-by-14 rule, no loop alignment, no seek block and no
+// channel info body, and no version with unaligned loop points.
+int nw_layout(const vga_nwstm_params *p, int codec, int nch, vga_nwstm_layout *L)
+{
+    const bool gc = codec == kCodecGcAdpcm;
+    const int bps = codec == kCodecPcm16 ? 2 : 1;           // PCM bytes per sample
+    auto bytes = [&](int samples) { return gc ? bytes_of(samples) : samples * bps; };
+    if (p->target < VGA_NW_RSTM || p->target > VGA_NW_FSTM) { set_error("unknown NintendoWare target %d", p->target); return VGA_ERR_ARGUMENT; }
+    if (nch < 1 || nch > VGA_NW_MAX_CHANNELS) { set_error("channel count %d out of range (1..%d)", nch, VGA_NW_MAX_CHANNELS); return VGA_ERR_ARGUMENT; }
+    if (gc && (p->keep_seek_table || p->keep_loop_context)) {
+        set_error("only RecalculateSeekTable = RecalculateLoopContext = true is supported: the tables come from the channel builder");
+        return VGA_ERR_ARGUMENT;
+    }
+    const int def = gc ? kDefaultSamples : 0x2000 / bps;    // BytesToSamples(DefaultInterleave, Codec)
+    const int spi = p->samples_per_interleave ? p->samples_per_interleave : def;
+    if (spi < 1) return out_of_range("Number of samples per interleave must be positive");
+    if (gc && spi % 14 != 0) return out_of_range("Number of samples per interleave must be divisible by 14");
+    const int spe = p->samples_per_seek_table_entry ? p->samples_per_seek_table_entry : def;
+    if (spe < 2) return out_of_range("Number of samples per interleave must be 2 or greater");
+    const int align = p->loop_point_alignment ? p->loop_point_alignment : kDefaultSamples;
+    if (gc && align < 0) return out_of_range("negative loop point alignment");
+    if (p->sample_rate < 0 || p->sample_count < 0) return out_of_range("negative sample rate / sample count");
+    if (p->track_type != VGA_NW_TRACK_STANDARD && p->track_type != VGA_NW_TRACK_SHORT) { set_error("unknown BRSTM track type"); return VGA_ERR_ARGUMENT; }
+    if (p->seek_table_type != VGA_NW_SEEK_STANDARD && p->seek_table_type != VGA_NW_SEEK_SHORT) { set_error("unknown BRSTM seek table type"); return VGA_ERR_ARGUMENT; }
+    if (p->track_count < 0 || p->track_count > VGA_NW_MAX_TRACKS) {
+        set_error("track count %d out of range (0 = the default list, at most %d)", p->track_count, VGA_NW_MAX_TRACKS);
+        return VGA_ERR_OUT_OF_RANGE;
+    }
+    if (int rc = check_loop(p->looping, p->loop_start, p->loop_end, p->sample_count)) return rc;
+    const int loop_start = p->looping ? p->loop_start : 0, loop_end = p->looping ? p->loop_end : 0;
+    if (int rc = target_and_version(p, L)) return rc;
+    int shift = 0;
+    if (gc) {
+        // SetupWriter (BrstmWriter.cs:88-103): WithAlignment when the loop start is not aligned; every channel is then
+        // rebuilt with LoopAlignmentMultiple and SamplesPerSeekTableEntry -- vga_gcadpcm_build_channels_* does both
+        L->channel.sample_count = p->sample_count;
+        L->channel.looping = p->looping ? 1 : 0;
+        L->channel.loop_start = loop_start;
+        L->channel.loop_end = loop_end;
+        L->channel.loop_alignment_multiple = align;
+        L->channel.samples_per_seek_table_entry = spe;
+        vga_gcadpcm_channel_layout cl;
+        if (int rc = vga_gcadpcm_channel_layout_for(&L->channel, &cl)) return rc;
+        L->alignment_needed = cl.alignment_needed;
+        L->channel_sample_count = cl.sample_count_aligned;
+        L->channel_adpcm_bytes = bytes_of(cl.sample_count_aligned);
+        L->channel_seek_entries = cl.seek_table_entries;
+        shift = cl.alignment_needed ? cl.loop_start_aligned - loop_start : 0;          // GcAdpcmFormat.cs:19-22
+    } else {
+        if (L->include_unaligned_loop) {                    // BCFstmWriter.cs:250-254 reads Adpcm.LoopStart
+            set_error("BCSTM 2.3+ / BFSTM 0.4+ carry GC-ADPCM unaligned loop points, which a PCM stream does not have "
+                      "(the reference writer fails on a null GcAdpcmFormat): choose an earlier version");
+            return VGA_ERR_INVALID_OP;
+        }
+        const int64_t row = (int64_t)p->sample_count * bps;
+        if ((int64_t)spi * bps > 0x7FFFFFFF) return out_of_range("Number of samples per interleave too large for the interleave's int size");
+        if (row > 0x7FFFFFFF) { set_error("file would exceed 2 GiB (the reference's FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
+        L->channel_sample_count = p->sample_count;
+        L->channel_adpcm_bytes = (int)row;
+    }
+    L->looping = p->looping ? 1 : 0;
+    L->loop_start = loop_start + shift;
+    L->loop_end = loop_end + shift;
+    const int sc = L->looping ? L->loop_end : p->sample_count;                                       // SampleCount (:27)
+    L->sample_count = sc;
+    L->track_count = p->track_count ? p->track_count : div_round_up(nch, 2);
+    const bool rstm = p->target == VGA_NW_RSTM;
+    L->samples_per_interleave = spi;
+    L->interleave_size = bytes(spi);
+    L->interleave_count = div_round_up(sc, spi);
+    L->last_block_samples = sc - (L->interleave_count - 1) * spi;
+    L->last_block_size_without_padding = bytes(L->last_block_samples);
+    L->last_block_size = (int)next_multiple(L->last_block_size_without_padding, 0x20);
+    L->samples_per_seek_table_entry = gc || !rstm ? spe : 0;  // a PCM BRSTM writes zeros (BrstmWriter.cs:51-52)
+    L->bytes_per_seek_table_entry = gc || !rstm ? 4 : 0;
+    if (gc) L->seek_table_entry_count = rstm && p->seek_table_type == VGA_NW_SEEK_SHORT ? bytes_of(sc) / spe + 1 : div_round_up(sc, spe);
+    const int64_t audio_data_size = next_multiple(bytes(sc), 0x20);
+    const int T = L->track_count;
+    L->header_size = 0x40;
+    if (rstm) {
+        L->head1_size = 0x34;
+        L->head2_size = 4 + 8 * T + (p->track_type == VGA_NW_TRACK_SHORT ? 4 : 0x0c) * T;
+        L->head3_size = 4 + 8 * nch + (gc ? 0x38 : 8) * nch;                              // ChannelInfoSize
+    } else {
+        L->head1_size = 0x38 + (L->include_region_info ? 0xc : 0) + (L->include_unaligned_loop ? 8 : 0);
+        L->head2_size = L->include_track_info ? 4 + 8 * T : 0;
+        L->head3_size = 4 + 8 * nch + (L->include_track_info ? 0x14 * T : 0) + 8 * nch + (gc ? 0x2e : 0) * nch;
+    }
+    const int64_t head = next_multiple(8 + 24 + L->head1_size + L->head2_size + L->head3_size, 0x20);
+    const int64_t seek = gc ? next_multiple(8 + (int64_t)L->seek_table_entry_count * nch * 4, 0x20) : 0;   // PCM: no ADPC / SEEK
+    const int64_t data = 0x20 + audio_data_size * nch;
+    const int64_t file = 0x40 + head + seek + data;
+    if (file > 0x7FFFFFFF) { set_error("file would exceed 2 GiB (the reference's FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
+    L->head_block_offset = 0x40;
+    L->head_block_size = (int)head;
+    L->seek_block_offset = gc ? (int)(0x40 + head) : 0;
+    L->seek_block_size = (int)seek;
+    L->data_block_offset = (int)(0x40 + head + seek);
+    L->data_block_size = (int)data;
+    L->audio_data_offset = L->data_block_offset + 0x20;
+    L->audio_data_size = (int)audio_data_size;
+    L->file_size = (int)file;
+    return VGA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -386,96 +458,7 @@ int vga_nwstm_layout_for(const vga_nwstm_params *p, int nch, vga_nwstm_layout *L
 {
     if (!p || !L) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     std::memset(L, 0, sizeof *L);
-    if (p->target < VGA_NW_RSTM || p->target > VGA_NW_FSTM) { set_error("unknown NintendoWare target %d", p->target); return VGA_ERR_ARGUMENT; }
-    if (nch < 1 || nch > VGA_NW_MAX_CHANNELS) { set_error("channel count %d out of range (1..%d)", nch, VGA_NW_MAX_CHANNELS); return VGA_ERR_ARGUMENT; }
-    if (p->keep_seek_table || p->keep_loop_context) {
-        set_error("only RecalculateSeekTable = RecalculateLoopContext = true is supported: the tables come from the channel builder");
-        return VGA_ERR_ARGUMENT;
-    }
-    // BxstmConfiguration.cs:42-100
-    const int spi = p->samples_per_interleave ? p->samples_per_interleave : kDefaultSamples;
-    if (spi < 1) return out_of_range("Number of samples per interleave must be positive");
-    if (spi % 14 != 0) return out_of_range("Number of samples per interleave must be divisible by 14");
-    const int spe = p->samples_per_seek_table_entry ? p->samples_per_seek_table_entry : kDefaultSamples;
-    if (spe < 2) return out_of_range("Number of samples per interleave must be 2 or greater");
-    const int align = p->loop_point_alignment ? p->loop_point_alignment : kDefaultSamples;
-    if (align < 0) return out_of_range("negative loop point alignment");
-    if (p->sample_rate < 0 || p->sample_count < 0) return out_of_range("negative sample rate / sample count");
-    if (p->track_type != VGA_NW_TRACK_STANDARD && p->track_type != VGA_NW_TRACK_SHORT) { set_error("unknown BRSTM track type"); return VGA_ERR_ARGUMENT; }
-    if (p->seek_table_type != VGA_NW_SEEK_STANDARD && p->seek_table_type != VGA_NW_SEEK_SHORT) { set_error("unknown BRSTM seek table type"); return VGA_ERR_ARGUMENT; }
-    if (p->track_count < 0 || p->track_count > VGA_NW_MAX_TRACKS) {
-        set_error("track count %d out of range (0 = the default list, at most %d)", p->track_count, VGA_NW_MAX_TRACKS);
-        return VGA_ERR_OUT_OF_RANGE;
-    }
-    int loop_start = 0, loop_end = 0;
-    if (p->looping) {                                       // AudioFormatBaseBuilder.WithLoop (:30-43)
-        if (p->loop_start < 0 || p->loop_start > p->sample_count || p->loop_end < 0 || p->loop_end > p->sample_count)
-            return out_of_range("Loop points must be less than the number of samples and non-negative.");
-        if (p->loop_end < p->loop_start) return out_of_range("The loop end must be greater than the loop start");
-        loop_start = p->loop_start;
-        loop_end = p->loop_end;
-    }
-    if (int rc = target_and_version(p, L)) return rc;
-    // SetupWriter (BrstmWriter.cs:88-103): WithAlignment when the loop start is not aligned; every channel is then
-    // rebuilt with LoopAlignmentMultiple and SamplesPerSeekTableEntry -- vga_gcadpcm_build_channels_* does both
-    L->channel.sample_count = p->sample_count;
-    L->channel.looping = p->looping ? 1 : 0;
-    L->channel.loop_start = loop_start;
-    L->channel.loop_end = loop_end;
-    L->channel.loop_alignment_multiple = align;
-    L->channel.samples_per_seek_table_entry = spe;
-    vga_gcadpcm_channel_layout cl;
-    if (int rc = vga_gcadpcm_channel_layout_for(&L->channel, &cl)) return rc;
-    L->alignment_needed = cl.alignment_needed;
-    L->channel_sample_count = cl.sample_count_aligned;
-    L->channel_adpcm_bytes = bytes_of(cl.sample_count_aligned);
-    L->channel_seek_entries = cl.seek_table_entries;
-    const int shift = cl.alignment_needed ? cl.loop_start_aligned - loop_start : 0;       // GcAdpcmFormat.cs:19-22
-    L->looping = p->looping ? 1 : 0;
-    L->loop_start = loop_start + shift;
-    L->loop_end = loop_end + shift;
-    const int sc = L->looping ? L->loop_end : p->sample_count;                                       // SampleCount (:27)
-    L->sample_count = sc;
-    L->track_count = p->track_count ? p->track_count : div_round_up(nch, 2);
-    // the size math of BrstmWriter.cs:22-74 / BCFstmWriter.cs:23-83
-    L->samples_per_interleave = spi;
-    L->interleave_size = bytes_of(spi);
-    L->interleave_count = div_round_up(sc, spi);
-    L->last_block_samples = sc - (L->interleave_count - 1) * spi;
-    L->last_block_size_without_padding = bytes_of(L->last_block_samples);
-    L->last_block_size = (int)next_multiple(L->last_block_size_without_padding, 0x20);
-    L->samples_per_seek_table_entry = spe;
-    L->bytes_per_seek_table_entry = 4;
-    L->seek_table_entry_count = (p->target == VGA_NW_RSTM && p->seek_table_type == VGA_NW_SEEK_SHORT)
-        ? bytes_of(sc) / spe + 1 : div_round_up(sc, spe);
-    const int64_t audio_data_size = next_multiple(bytes_of(sc), 0x20);
-    const int T = L->track_count;
-    L->header_size = 0x40;
-    int64_t head;
-    if (p->target == VGA_NW_RSTM) {
-        L->head1_size = 0x34;
-        L->head2_size = 4 + 8 * T + (p->track_type == VGA_NW_TRACK_SHORT ? 4 : 0x0c) * T;
-        L->head3_size = 4 + 8 * nch + 0x38 * nch;
-    } else {
-        L->head1_size = 0x38 + (L->include_region_info ? 0xc : 0) + (L->include_unaligned_loop ? 8 : 0);
-        L->head2_size = L->include_track_info ? 4 + 8 * T : 0;
-        L->head3_size = 4 + 8 * nch + (L->include_track_info ? 0x14 * T : 0) + 8 * nch + 0x2e * nch;
-    }
-    head = next_multiple(8 + 24 + L->head1_size + L->head2_size + L->head3_size, 0x20);
-    const int64_t seek = next_multiple(8 + (int64_t)L->seek_table_entry_count * nch * 4, 0x20);
-    const int64_t data = 0x20 + audio_data_size * nch;
-    const int64_t file = 0x40 + head + seek + data;
-    if (file > 0x7FFFFFFF) { set_error("file would exceed 2 GiB (the reference's FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
-    L->head_block_offset = 0x40;
-    L->head_block_size = (int)head;
-    L->seek_block_offset = (int)(0x40 + head);
-    L->seek_block_size = (int)seek;
-    L->data_block_offset = (int)(0x40 + head + seek);
-    L->data_block_size = (int)data;
-    L->audio_data_offset = L->data_block_offset + 0x20;
-    L->audio_data_size = (int)audio_data_size;
-    L->file_size = (int)file;
-    return VGA_OK;
+    return nw_layout(p, kCodecGcAdpcm, nch, L);
 }
 
 int vga_nwstm_write_device(const vga_nwstm_params *p, int nch, int nfiles, const vga_nw_track *tracks, const uint8_t *d_adpcm,
@@ -492,13 +475,9 @@ int vga_nwstm_write_device(const vga_nwstm_params *p, int nch, int nfiles, const
         set_error("null device pointer");
         return VGA_ERR_ARGUMENT;
     }
-    if (file_pitch < L.file_size || (nfiles > 1 && (file_pitch & 15))) {
-        set_error("file pitch %lld: at least the file size %d and a multiple of 16", (long long)file_pitch, L.file_size);
-        return VGA_ERR_ARGUMENT;
-    }
     if (adpcm_len > 0 && adpcm_pitch < adpcm_len) { set_error("adpcm pitch < length"); return VGA_ERR_ARGUMENT; }
     if (seek_entries > 0 && seek_pitch < 2 * (int64_t)seek_entries) { set_error("seek pitch < 2 * entries"); return VGA_ERR_ARGUMENT; }
-    if ((int64_t)nfiles * nch > 0x7FFFFFFF / 16) { set_error("too many files in one call"); return VGA_ERR_ARGUMENT; }
+    if (int rc = check_write_files(nfiles, nch, file_pitch, L.file_size)) return rc;
     hipStream_t s = (hipStream_t)stream;
     nwstm::HeaderArgs a;
     header_args(L, p, nch, tracks, &a);
@@ -514,13 +493,8 @@ int vga_nwstm_write_device(const vga_nwstm_params *p, int nch, int nfiles, const
                            L.seek_block_offset, L.seek_block_size, d_files + (int64_t)f0 * file_pitch, file_pitch);
         VGA_HIP_TRY(hipGetLastError());
     }
-    const uint32_t out = (uint32_t)L.audio_data_size, il = (uint32_t)L.interleave_size;
-    if (out == 0) return VGA_OK;
-    const uint32_t out_blocks = (out + il - 1) / il, last_out = out - (out_blocks - 1) * il;
-    const uint64_t align = (uint64_t)(uintptr_t)d_adpcm | (uint64_t)adpcm_pitch | il | last_out |
-                           (uint64_t)(uintptr_t)(d_files + L.audio_data_offset) | (uint64_t)(nfiles > 1 ? file_pitch : 0);
-    return container::launch_interleave_files(align, d_adpcm, adpcm_pitch, nch, nfiles, (uint32_t)adpcm_len, il, out,
-                                              d_files + L.audio_data_offset, file_pitch, s);
+    return interleave_images(d_adpcm, adpcm_pitch, nch, nfiles, (uint32_t)adpcm_len, (uint32_t)L.interleave_size,
+                             (uint32_t)L.audio_data_size, d_files + L.audio_data_offset, file_pitch, s);
 }
 
 int vga_nwstm_write(const vga_nwstm_params *p, int nch, const vga_nw_track *tracks, const uint8_t *const *adpcm, int adpcm_len,
@@ -534,39 +508,22 @@ int vga_nwstm_write(const vga_nwstm_params *p, int nch, const vga_nw_track *trac
     if (!coefs || !file_out || (adpcm_len > 0 && !adpcm) || (seek_entries > 0 && !seek)) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     for (int c = 0; c < nch; c++)
         if ((adpcm_len > 0 && !adpcm[c]) || (seek_entries > 0 && !seek[c])) { set_error("channel %d: null pointer", c); return VGA_ERR_ARGUMENT; }
-    if (int rc = require_device()) return rc;
-    Stream st;
-    VGA_HIP_TRY(st.create());
-    const int64_t apitch = round_up(adpcm_len > 0 ? adpcm_len : 1, 16), spitch = round_up(2 * (seek_entries > 0 ? seek_entries : 1), 8);
-    DevBuf d_adpcm, d_coefs, d_gain, d_sc, d_lc, d_seek, d_file;
-    VGA_HIP_TRY(d_adpcm.alloc((size_t)nch * apitch));
-    VGA_HIP_TRY(d_coefs.alloc((size_t)nch * 32));
-    VGA_HIP_TRY(d_seek.alloc((size_t)nch * spitch * 2));
-    VGA_HIP_TRY(d_file.alloc((size_t)L.file_size));
-    for (int c = 0; c < nch; c++) {
-        if (adpcm_len > 0)
-            VGA_HIP_TRY(hipMemcpyAsync(d_adpcm.as<uint8_t>() + c * apitch, adpcm[c], (size_t)adpcm_len, hipMemcpyHostToDevice, st.s));
-        if (seek_entries > 0)
-            VGA_HIP_TRY(hipMemcpyAsync(d_seek.as<int16_t>() + c * spitch, seek[c], (size_t)seek_entries * 4, hipMemcpyHostToDevice, st.s));
-    }
-    VGA_HIP_TRY(hipMemcpyAsync(d_coefs.p, coefs, (size_t)nch * 32, hipMemcpyHostToDevice, st.s));
-    auto upload = [&](DevBuf &d, const int16_t *src, size_t shorts) -> int {
-        if (!src) return VGA_OK;
-        VGA_HIP_TRY(d.alloc(shorts * 2));
-        VGA_HIP_TRY(hipMemcpyAsync(d.p, src, shorts * 2, hipMemcpyHostToDevice, st.s));
-        return VGA_OK;
-    };
-    if (int rc = upload(d_gain, gain, (size_t)nch)) return rc;
-    if (int rc = upload(d_sc, start_context, (size_t)nch * 3)) return rc;
-    if (int rc = upload(d_lc, loop_context, (size_t)nch * 3)) return rc;
-    if (int rc = vga_nwstm_write_device(p, nch, 1, tracks, d_adpcm.as<uint8_t>(), apitch, adpcm_len, d_coefs.as<int16_t>(),
-                                        gain ? d_gain.as<int16_t>() : nullptr, start_context ? d_sc.as<int16_t>() : nullptr,
-                                        loop_context ? d_lc.as<int16_t>() : nullptr, d_seek.as<int16_t>(), spitch, seek_entries,
-                                        d_file.as<uint8_t>(), L.file_size, st.s))
-        return rc;
-    VGA_HIP_TRY(hipMemcpyAsync(file_out, d_file.p, (size_t)L.file_size, hipMemcpyDeviceToHost, st.s));
-    VGA_HIP_TRY(hipStreamSynchronize(st.s));
-    return VGA_OK;
+    HostStage h;
+    uint8_t *d_adpcm = nullptr;
+    int16_t *d_seek = nullptr;
+    const int16_t *d_coefs = nullptr, *d_gain = nullptr, *d_sc = nullptr, *d_lc = nullptr;
+    int64_t apitch = 0, spitch = 0;
+    if (int rc = h.open()) return rc;
+    if (int rc = h.rows(adpcm, nch, adpcm_len, &d_adpcm, &apitch)) return rc;
+    if (int rc = h.rows(seek, nch, 2 * seek_entries, &d_seek, &spitch)) return rc;
+    if (int rc = h.table(coefs, (size_t)nch * 16, &d_coefs)) return rc;
+    if (int rc = h.table(gain, (size_t)nch, &d_gain)) return rc;
+    if (int rc = h.table(start_context, (size_t)nch * 3, &d_sc)) return rc;
+    if (int rc = h.table(loop_context, (size_t)nch * 3, &d_lc)) return rc;
+    return h.write_image(file_out, (size_t)L.file_size, [&](uint8_t *d_file, hipStream_t s) {
+        return vga_nwstm_write_device(p, nch, 1, tracks, d_adpcm, apitch, adpcm_len, d_coefs, d_gain, d_sc, d_lc, d_seek, spitch,
+                                      seek_entries, d_file, L.file_size, s);
+    });
 }
 
 // BrstmReader.ReadFile / BCFstmReader.ReadFile up to the audio (host only): the checks of the reference readers,
@@ -578,7 +535,7 @@ static int parse_nw(const uint8_t *file, size_t size, vga_nwstm_info *out, bool 
     std::memset(out, 0, sizeof *out);
     const int64_t len = (int64_t)size;
     if (len < 4) return invalid("file is too short for a NintendoWare header");
-    Reader r{file, len, 0, true};
+    ByteReader r{file, len, 0, true};
     vga_nwstm_info &I = *out;
     if (!std::memcmp(file, "RSTM", 4)) {                    // BrstmReader.cs
         I.target = VGA_NW_RSTM;
@@ -597,7 +554,7 @@ static int parse_nw(const uint8_t *file, size_t size, vga_nwstm_info *out, bool 
         I.data_block_offset = r.i32(); I.data_block_size = r.i32();
         if (r.eof) return invalid("file ends inside the RSTM header");
         r.pos = I.head_block_offset;
-        if (!r.tag("HEAD")) return invalid("Unknown or invalid HEAD block");
+        if (!r.magic("HEAD", 4)) return invalid("Unknown or invalid HEAD block");
         if (r.i32() != I.head_block_size) return invalid("HEAD block size in RSTM header doesn't match size in HEAD header");
         const int base = (int)r.pos;
         const Ref si = read_ref(r, base), ti = read_ref(r, base), ci = read_ref(r, base);
@@ -663,7 +620,7 @@ static int parse_nw(const uint8_t *file, size_t size, vga_nwstm_info *out, bool 
         if (!pcm && found < I.channel_count) return invalid("fewer channel infos than channels");
         if (I.seek_block_offset != 0) {                     // ReadAdpcBlock
             r.pos = I.seek_block_offset;
-            if (!r.tag("ADPC")) return invalid("Unknown or invalid ADPC block");
+            if (!r.magic("ADPC", 4)) return invalid("Unknown or invalid ADPC block");
             if (r.i32() != I.seek_block_size) return invalid("ADPC block size in RSTM header doesn't match size in ADPC header");
             if (I.samples_per_seek_table_entry <= 0) return invalid("samples per seek table entry must be positive");
             const bool full = I.sample_count % I.samples_per_seek_table_entry == 0 && I.sample_count > 0;
@@ -680,7 +637,7 @@ static int parse_nw(const uint8_t *file, size_t size, vga_nwstm_info *out, bool 
             I.seek_table_offset = I.seek_block_offset + 8;
         }
         r.pos = I.data_block_offset;                        // ReadDataBlock
-        if (!r.tag("DATA")) return invalid("Unknown or invalid DATA block");
+        if (!r.magic("DATA", 4)) return invalid("Unknown or invalid DATA block");
         if (r.i32() != I.data_block_size) return invalid("DATA block size in main header doesn't match size in DATA header");
         I.audio_data_length = I.data_block_size - (I.audio_data_offset - I.data_block_offset);
     } else {                                                // BCFstmReader.cs
@@ -724,7 +681,7 @@ static int parse_nw(const uint8_t *file, size_t size, vga_nwstm_info *out, bool 
         if (!have_info) return invalid("File has no INFO block");
         if (info.type != kStreamInfoBlock || prefetch) { set_error("wave / prefetch blocks are not read here"); return VGA_ERR_INVALID_OP; }
         r.pos = info.abs();
-        if (!r.tag("INFO")) return invalid("Unknown or invalid INFO block");
+        if (!r.magic("INFO", 4)) return invalid("Unknown or invalid INFO block");
         if (r.i32() != info_size) return invalid("INFO block size in main header doesn't match size in INFO header");
         const int base = (int)r.pos;
         const Ref si = read_ref(r, base), ti = read_ref(r, base), ci = read_ref(r, base);
@@ -805,7 +762,7 @@ static int parse_nw(const uint8_t *file, size_t size, vga_nwstm_info *out, bool 
         I.head_block_size = info_size;
         if (have_seek) {                                    // ReadSeekBlock
             r.pos = seek.abs();
-            if (!r.tag("SEEK")) return invalid("Unknown or invalid SEEK block");
+            if (!r.magic("SEEK", 4)) return invalid("Unknown or invalid SEEK block");
             if (r.i32() != seek_size) return invalid("SEEK block size in main header doesn't match size in SEEK header");
             if (I.samples_per_seek_table_entry <= 0) return invalid("samples per seek table entry must be positive");
             I.seek_block_offset = seek.abs();
@@ -815,7 +772,7 @@ static int parse_nw(const uint8_t *file, size_t size, vga_nwstm_info *out, bool 
         }
         if (!have_data) return invalid("File has no DATA block");
         r.pos = data.abs();                                 // ReadDataBlock
-        if (!r.tag("DATA")) return invalid("Unknown or invalid DATA block");
+        if (!r.magic("DATA", 4)) return invalid("Unknown or invalid DATA block");
         if (r.i32() != data_size) return invalid("DATA block size in main header doesn't match size in DATA header");
         I.data_block_offset = data.abs();
         I.data_block_size = data_size;
@@ -858,14 +815,11 @@ int vga_nwstm_read_device(const vga_nwstm_info *I, const uint8_t *d_files, int64
     if (nfiles == 0 || I->adpcm_bytes == 0) return VGA_OK;
     const int nch = I->channel_count;
     if (nch < 1 || I->interleave_size <= 0 || I->audio_data_length < 0 || I->audio_data_length % nch) { set_error("info does not describe a stream"); return VGA_ERR_ARGUMENT; }
-    if (!d_files || !d_adpcm || adpcm_pitch < I->adpcm_bytes) { set_error("null pointer / adpcm pitch < %d", I->adpcm_bytes); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 1 && file_pitch < (int64_t)I->audio_data_offset + I->audio_data_length) { set_error("file pitch smaller than the stream"); return VGA_ERR_ARGUMENT; }
-    const uint32_t in = (uint32_t)(I->audio_data_length / nch), il = (uint32_t)I->interleave_size, out = (uint32_t)I->adpcm_bytes;
-    const uint32_t in_blocks = in ? (in + il - 1) / il : 0, last_in = in ? in - (in_blocks - 1) * il : 0;
-    const uint64_t align = (uint64_t)(uintptr_t)d_files | (uint64_t)(nfiles > 1 ? file_pitch : 0) | (uint64_t)I->audio_data_offset |
-                           il | last_in | (uint64_t)(uintptr_t)d_adpcm | (uint64_t)adpcm_pitch;
-    return container::launch_deinterleave(align, d_files, file_pitch, I->audio_data_offset, nch, nfiles * nch, in, il, out, d_adpcm,
-                                          adpcm_pitch, (hipStream_t)stream);
+    if (int rc = check_read_batch(d_files, d_adpcm, adpcm_pitch, I->adpcm_bytes, nfiles, file_pitch,
+                                  (int64_t)I->audio_data_offset + I->audio_data_length))
+        return rc;
+    return deinterleave_images(d_files, file_pitch, nfiles, I->audio_data_offset, nch, (uint32_t)(I->audio_data_length / nch),
+                               (uint32_t)I->interleave_size, (uint32_t)I->adpcm_bytes, d_adpcm, adpcm_pitch, (hipStream_t)stream);
 }
 
 int vga_nwstm_read(const uint8_t *file, size_t size, const vga_nwstm_info *I, uint8_t *const *adpcm_out, int16_t *const *seek_out)
@@ -885,20 +839,11 @@ int vga_nwstm_read(const uint8_t *file, size_t size, const vga_nwstm_info *I, ui
                 }
     }
     if (I->adpcm_bytes == 0) return VGA_OK;
-    if (int rc = require_device()) return rc;
-    Stream st;
-    VGA_HIP_TRY(st.create());
-    const int64_t apitch = round_up(I->adpcm_bytes, 16);
     const size_t bytes = (size_t)I->audio_data_offset + (size_t)I->audio_data_length;
-    DevBuf d_file, d_out;
-    VGA_HIP_TRY(d_file.alloc(bytes));
-    VGA_HIP_TRY(d_out.alloc((size_t)nch * apitch));
-    VGA_HIP_TRY(hipMemcpyAsync(d_file.p, file, bytes, hipMemcpyHostToDevice, st.s));
-    if (int rc = vga_nwstm_read_device(I, d_file.as<uint8_t>(), (int64_t)bytes, 1, d_out.as<uint8_t>(), apitch, st.s)) return rc;
-    for (int c = 0; c < nch; c++)
-        VGA_HIP_TRY(hipMemcpyAsync(adpcm_out[c], d_out.as<uint8_t>() + c * apitch, (size_t)I->adpcm_bytes, hipMemcpyDeviceToHost, st.s));
-    VGA_HIP_TRY(hipStreamSynchronize(st.s));
-    return VGA_OK;
+    HostStage h;
+    return h.read_rows(file, bytes, adpcm_out, nch, I->adpcm_bytes, 1, [&](const uint8_t *f, void *d, int64_t dp, hipStream_t s) {
+        return vga_nwstm_read_device(I, f, (int64_t)bytes, 1, static_cast<uint8_t *>(d), dp, s);
+    });
 }
 
 
@@ -913,82 +858,7 @@ int vga_nwstm_pcm_layout_for(const vga_nwstm_params *p, int codec, int nch, vga_
         set_error("codec %d: this call writes PCM8 (0) or PCM16 (1) streams (vga_nwstm_layout_for for GC-ADPCM)", codec);
         return VGA_ERR_ARGUMENT;
     }
-    if (p->target < VGA_NW_RSTM || p->target > VGA_NW_FSTM) { set_error("unknown NintendoWare target %d", p->target); return VGA_ERR_ARGUMENT; }
-    if (nch < 1 || nch > VGA_NW_MAX_CHANNELS) { set_error("channel count %d out of range (1..%d)", nch, VGA_NW_MAX_CHANNELS); return VGA_ERR_ARGUMENT; }
-    const int bps = codec == kCodecPcm16 ? 2 : 1;
-    const int def = 0x2000 / bps;                           // BytesToSamples(DefaultInterleave, Codec)
-    const int spi = p->samples_per_interleave ? p->samples_per_interleave : def;
-    if (spi < 1) return out_of_range("Number of samples per interleave must be positive");   // no divisible-by-14 rule
-    const int spe = p->samples_per_seek_table_entry ? p->samples_per_seek_table_entry : def;
-    if (spe < 2) return out_of_range("Number of samples per interleave must be 2 or greater");
-    if (p->sample_rate < 0 || p->sample_count < 0) return out_of_range("negative sample rate / sample count");
-    if (p->track_type != VGA_NW_TRACK_STANDARD && p->track_type != VGA_NW_TRACK_SHORT) { set_error("unknown BRSTM track type"); return VGA_ERR_ARGUMENT; }
-    if (p->seek_table_type != VGA_NW_SEEK_STANDARD && p->seek_table_type != VGA_NW_SEEK_SHORT) { set_error("unknown BRSTM seek table type"); return VGA_ERR_ARGUMENT; }
-    if (p->track_count < 0 || p->track_count > VGA_NW_MAX_TRACKS) {
-        set_error("track count %d out of range (0 = the default list, at most %d)", p->track_count, VGA_NW_MAX_TRACKS);
-        return VGA_ERR_OUT_OF_RANGE;
-    }
-    int loop_start = 0, loop_end = 0;
-    if (p->looping) {                                       // AudioFormatBaseBuilder.WithLoop (:30-43)
-        if (p->loop_start < 0 || p->loop_start > p->sample_count || p->loop_end < 0 || p->loop_end > p->sample_count)
-            return out_of_range("Loop points must be less than the number of samples and non-negative.");
-        if (p->loop_end < p->loop_start) return out_of_range("The loop end must be greater than the loop start");
-        loop_start = p->loop_start;
-        loop_end = p->loop_end;
-    }
-    if (int rc = target_and_version(p, L)) return rc;
-    if (L->include_unaligned_loop) {                        // BCFstmWriter.cs:250-254 reads Adpcm.LoopStart
-        set_error("BCSTM 2.3+ / BFSTM 0.4+ carry GC-ADPCM unaligned loop points, which a PCM stream does not have "
-                  "(the reference writer fails on a null GcAdpcmFormat): choose an earlier version");
-        return VGA_ERR_INVALID_OP;
-    }
-    const int64_t row = (int64_t)p->sample_count * bps;
-    if ((int64_t)spi * bps > 0x7FFFFFFF) return out_of_range("Number of samples per interleave too large for the interleave's int size");
-    if (row > 0x7FFFFFFF) { set_error("file would exceed 2 GiB (the reference's FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
-    L->channel_sample_count = p->sample_count;
-    L->channel_adpcm_bytes = (int)row;
-    L->looping = p->looping ? 1 : 0;
-    L->loop_start = loop_start;                              // no loop alignment for PCM
-    L->loop_end = loop_end;
-    const int sc = L->looping ? loop_end : p->sample_count;  // SampleCount = LoopEnd when looping
-    L->sample_count = sc;
-    L->track_count = p->track_count ? p->track_count : div_round_up(nch, 2);
-    L->samples_per_interleave = spi;
-    L->interleave_size = spi * bps;
-    L->interleave_count = div_round_up(sc, spi);
-    L->last_block_samples = sc - (L->interleave_count - 1) * spi;
-    L->last_block_size_without_padding = L->last_block_samples * bps;
-    L->last_block_size = (int)next_multiple(L->last_block_size_without_padding, 0x20);
-    const bool rstm = p->target == VGA_NW_RSTM;
-    L->samples_per_seek_table_entry = rstm ? 0 : spe;       // BrstmWriter.cs:51-52 vs BCFstmWriter.cs:51-52
-    L->bytes_per_seek_table_entry = rstm ? 0 : 4;
-    L->seek_table_entry_count = 0;
-    const int64_t audio_data_size = next_multiple((int64_t)sc * bps, 0x20);
-    const int T = L->track_count;
-    L->header_size = 0x40;
-    if (rstm) {
-        L->head1_size = 0x34;
-        L->head2_size = 4 + 8 * T + (p->track_type == VGA_NW_TRACK_SHORT ? 4 : 0x0c) * T;
-        L->head3_size = 4 + 8 * nch + 8 * nch;              // ChannelInfoSize 8
-    } else {
-        L->head1_size = 0x38 + (L->include_region_info ? 0xc : 0);
-        L->head2_size = L->include_track_info ? 4 + 8 * T : 0;
-        L->head3_size = 4 + 8 * nch + (L->include_track_info ? 0x14 * T : 0) + 8 * nch;   // ChannelInfoSize 0
-    }
-    const int64_t head = next_multiple(8 + 24 + L->head1_size + L->head2_size + L->head3_size, 0x20);
-    const int64_t data = 0x20 + audio_data_size * nch;
-    const int64_t file = 0x40 + head + data;
-    if (file > 0x7FFFFFFF) { set_error("file would exceed 2 GiB (the reference's FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
-    L->head_block_offset = 0x40;
-    L->head_block_size = (int)head;
-    L->seek_block_offset = 0;                               // no ADPC / SEEK block
-    L->seek_block_size = 0;
-    L->data_block_offset = (int)(0x40 + head);
-    L->data_block_size = (int)data;
-    L->audio_data_offset = L->data_block_offset + 0x20;
-    L->audio_data_size = (int)audio_data_size;
-    L->file_size = (int)file;
-    return VGA_OK;
+    return nw_layout(p, codec, nch, L);
 }
 
 int vga_nwstm_pcm_write_device(const vga_nwstm_params *p, int codec, int nch, int nfiles, const vga_nw_track *tracks,
@@ -998,17 +868,13 @@ int vga_nwstm_pcm_write_device(const vga_nwstm_params *p, int codec, int nch, in
     vga_nwstm_layout L;
     if (int rc = vga_nwstm_pcm_layout_for(p, codec, nch, &L)) return rc;
     if (int rc = check_track_list(p, tracks)) return rc;
-    if (sample_kind != VGA_SAMPLES_S16 && sample_kind != VGA_SAMPLES_8BIT) { set_error("unknown sample kind %d", sample_kind); return VGA_ERR_ARGUMENT; }
+    if (int rc = check_sample_kind(sample_kind)) return rc;
     if (codec == kCodecPcm16 && sample_kind != VGA_SAMPLES_S16) { set_error("a PCM16 stream is written from VGA_SAMPLES_S16 rows"); return VGA_ERR_ARGUMENT; }
     if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
     if (nfiles == 0) return VGA_OK;
     if (!d_files || (p->sample_count > 0 && !d_samples)) { set_error("null device pointer"); return VGA_ERR_ARGUMENT; }
-    if (file_pitch < L.file_size || (nfiles > 1 && (file_pitch & 15))) {
-        set_error("file pitch %lld: at least the file size %d and a multiple of 16", (long long)file_pitch, L.file_size);
-        return VGA_ERR_ARGUMENT;
-    }
     if (p->sample_count > 0 && pitch < p->sample_count) { set_error("pitch < sample count"); return VGA_ERR_ARGUMENT; }
-    if ((int64_t)nfiles * nch > 0x7FFFFFFF / 16) { set_error("too many files in one call"); return VGA_ERR_ARGUMENT; }
+    if (int rc = check_write_files(nfiles, nch, file_pitch, L.file_size)) return rc;
     hipStream_t s = (hipStream_t)stream;
     nwstm::HeaderArgs a;
     header_args(L, p, nch, tracks, &a, codec);
@@ -1018,15 +884,9 @@ int vga_nwstm_pcm_write_device(const vga_nwstm_params *p, int codec, int nch, in
     const uint32_t in = (uint32_t)L.channel_adpcm_bytes, il = (uint32_t)L.interleave_size, out = (uint32_t)L.audio_data_size;
     uint8_t *audio = d_files + L.audio_data_offset;
     if (out == 0) return VGA_OK;
-    if (sample_kind == VGA_SAMPLES_8BIT || (codec == kCodecPcm16 && L.endianness == VGA_NW_LITTLE_ENDIAN)) {
-        // the rows' bytes are the file's bytes: the GC-ADPCM interleave as it is
-        const int64_t bpitch = sample_kind == VGA_SAMPLES_S16 ? pitch * 2 : pitch;
-        const uint32_t out_blocks = (out + il - 1) / il, last_out = out - (out_blocks - 1) * il;
-        const uint64_t align = (uint64_t)(uintptr_t)d_samples | (uint64_t)bpitch | il | last_out | (uint64_t)(uintptr_t)audio |
-                               (uint64_t)(nfiles > 1 ? file_pitch : 0);
-        return container::launch_interleave_files(align, static_cast<const uint8_t *>(d_samples), bpitch, nch, nfiles, in, il, out,
-                                                  audio, file_pitch, s);
-    }
+    if (sample_kind == VGA_SAMPLES_8BIT || (codec == kCodecPcm16 && L.endianness == VGA_NW_LITTLE_ENDIAN))   // the rows' bytes are the file's
+        return interleave_images(static_cast<const uint8_t *>(d_samples), sample_kind == VGA_SAMPLES_S16 ? pitch * 2 : pitch, nch, nfiles,
+                                 in, il, out, audio, file_pitch, s);
     return pcm::launch_interleave_files(codec == kCodecPcm16 ? pcm::kSwap16 : pcm::kPcm8, static_cast<const int16_t *>(d_samples),
                                         pitch, nch, nfiles, in, il, out, audio, file_pitch, s);
 }
@@ -1037,25 +897,18 @@ int vga_nwstm_pcm_write(const vga_nwstm_params *p, int codec, int nch, const vga
     vga_nwstm_layout L;
     if (int rc = vga_nwstm_pcm_layout_for(p, codec, nch, &L)) return rc;
     if (int rc = check_track_list(p, tracks)) return rc;
-    if (sample_kind != VGA_SAMPLES_S16 && sample_kind != VGA_SAMPLES_8BIT) { set_error("unknown sample kind %d", sample_kind); return VGA_ERR_ARGUMENT; }
+    if (int rc = check_sample_kind(sample_kind)) return rc;
     if (!file_out || (p->sample_count > 0 && !samples)) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     for (int c = 0; c < nch && p->sample_count > 0; c++)
         if (!samples[c]) { set_error("channel %d: null pointer", c); return VGA_ERR_ARGUMENT; }
-    if (int rc = require_device()) return rc;
-    Stream st;
-    VGA_HIP_TRY(st.create());
-    const int es = sample_kind == VGA_SAMPLES_S16 ? 2 : 1;
-    const int64_t pitch = round_up(p->sample_count > 0 ? p->sample_count : 1, 16);
-    DevBuf d_in, d_file;
-    VGA_HIP_TRY(d_in.alloc((size_t)nch * pitch * es));
-    VGA_HIP_TRY(d_file.alloc((size_t)L.file_size));
-    for (int c = 0; c < nch && p->sample_count > 0; c++)
-        VGA_HIP_TRY(hipMemcpyAsync(d_in.as<uint8_t>() + c * pitch * es, samples[c], (size_t)p->sample_count * es, hipMemcpyHostToDevice, st.s));
-    if (int rc = vga_nwstm_pcm_write_device(p, codec, nch, 1, tracks, d_in.p, sample_kind, pitch, d_file.as<uint8_t>(), L.file_size, st.s))
-        return rc;
-    VGA_HIP_TRY(hipMemcpyAsync(file_out, d_file.p, (size_t)L.file_size, hipMemcpyDeviceToHost, st.s));
-    VGA_HIP_TRY(hipStreamSynchronize(st.s));
-    return VGA_OK;
+    HostStage h;
+    void *d_in = nullptr;
+    int64_t pitch = 0;
+    if (int rc = h.open()) return rc;
+    if (int rc = h.rows(samples, nch, p->sample_count, sample_kind == VGA_SAMPLES_S16 ? 2 : 1, &d_in, &pitch)) return rc;
+    return h.write_image(file_out, (size_t)L.file_size, [&](uint8_t *d_file, hipStream_t s) {
+        return vga_nwstm_pcm_write_device(p, codec, nch, 1, tracks, d_in, sample_kind, pitch, d_file, L.file_size, s);
+    });
 }
 
 // BrstmReader / BCFstmReader up to the audio for PCM8 / PCM16 streams (Common.ToPcm16Stream / ToPcm8Stream)
@@ -1066,7 +919,7 @@ int vga_nwstm_pcm_read_device(const vga_nwstm_info *I, const uint8_t *d_files, i
 {
     if (!I || nfiles < 0) { set_error("null / negative argument"); return VGA_ERR_ARGUMENT; }
     if (I->codec != kCodecPcm8 && I->codec != kCodecPcm16) { set_error("info is not a PCM8 / PCM16 stream (vga_nwstm_pcm_parse)"); return VGA_ERR_ARGUMENT; }
-    if (sample_kind != VGA_SAMPLES_S16 && sample_kind != VGA_SAMPLES_8BIT) { set_error("unknown sample kind %d", sample_kind); return VGA_ERR_ARGUMENT; }
+    if (int rc = check_sample_kind(sample_kind)) return rc;
     if (I->codec == kCodecPcm16 && sample_kind != VGA_SAMPLES_S16) { set_error("a PCM16 stream is read to VGA_SAMPLES_S16 rows"); return VGA_ERR_ARGUMENT; }
     const int bps = I->codec == kCodecPcm16 ? 2 : 1;
     if (nfiles == 0 || I->adpcm_bytes == 0) return VGA_OK;
@@ -1075,19 +928,14 @@ int vga_nwstm_pcm_read_device(const vga_nwstm_info *I, const uint8_t *d_files, i
         set_error("info does not describe a stream");
         return VGA_ERR_ARGUMENT;
     }
-    if (!d_files || !d_samples || pitch < I->sample_count) { set_error("null pointer / pitch < %d", I->sample_count); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 1 && file_pitch < (int64_t)I->audio_data_offset + I->audio_data_length) { set_error("file pitch smaller than the stream"); return VGA_ERR_ARGUMENT; }
+    if (int rc = check_read_batch(d_files, d_samples, pitch, I->sample_count, nfiles, file_pitch,
+                                  (int64_t)I->audio_data_offset + I->audio_data_length))
+        return rc;
     const uint32_t in = (uint32_t)(I->audio_data_length / nch), il = (uint32_t)I->interleave_size, out = (uint32_t)I->adpcm_bytes;
     hipStream_t s = (hipStream_t)stream;
-    if (sample_kind == VGA_SAMPLES_8BIT || (I->codec == kCodecPcm16 && I->endianness == VGA_NW_LITTLE_ENDIAN)) {
-        // the file's bytes are the rows' bytes: the GC-ADPCM de-interleave as it is
-        const int64_t bpitch = sample_kind == VGA_SAMPLES_S16 ? pitch * 2 : pitch;
-        const uint32_t in_blocks = in ? (in + il - 1) / il : 0, last_in = in ? in - (in_blocks - 1) * il : 0;
-        const uint64_t align = (uint64_t)(uintptr_t)d_files | (uint64_t)(nfiles > 1 ? file_pitch : 0) | (uint64_t)I->audio_data_offset |
-                               il | last_in | (uint64_t)(uintptr_t)d_samples | (uint64_t)bpitch;
-        return container::launch_deinterleave(align, d_files, file_pitch, I->audio_data_offset, nch, nfiles * nch, in, il, out,
-                                              static_cast<uint8_t *>(d_samples), bpitch, s);
-    }
+    if (sample_kind == VGA_SAMPLES_8BIT || (I->codec == kCodecPcm16 && I->endianness == VGA_NW_LITTLE_ENDIAN))   // the file's bytes are the rows'
+        return deinterleave_images(d_files, file_pitch, nfiles, I->audio_data_offset, nch, in, il, out, static_cast<uint8_t *>(d_samples),
+                                   sample_kind == VGA_SAMPLES_S16 ? pitch * 2 : pitch, s);
     return pcm::launch_deinterleave(I->codec == kCodecPcm16 ? pcm::kSwap16 : pcm::kPcm8, d_files, file_pitch, I->audio_data_offset, nch,
                                     nfiles * nch, in, il, out, static_cast<int16_t *>(d_samples), pitch, s);
 }
@@ -1095,27 +943,18 @@ int vga_nwstm_pcm_read_device(const vga_nwstm_info *I, const uint8_t *d_files, i
 int vga_nwstm_pcm_read(const uint8_t *file, size_t size, const vga_nwstm_info *I, void *const *out, int sample_kind)
 {
     if (!file || !I || !out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
-    if (sample_kind != VGA_SAMPLES_S16 && sample_kind != VGA_SAMPLES_8BIT) { set_error("unknown sample kind %d", sample_kind); return VGA_ERR_ARGUMENT; }
+    if (int rc = check_sample_kind(sample_kind)) return rc;
     const int nch = I->channel_count;
     if (I->audio_data_offset < 0 || (int64_t)I->audio_data_offset + I->audio_data_length > (int64_t)size) { set_error("info does not describe this file"); return VGA_ERR_ARGUMENT; }
     for (int c = 0; c < nch; c++)
         if (!out[c]) { set_error("channel %d: null pointer", c); return VGA_ERR_ARGUMENT; }
     if (I->sample_count == 0) return VGA_OK;
-    if (int rc = require_device()) return rc;
-    Stream st;
-    VGA_HIP_TRY(st.create());
-    const int es = sample_kind == VGA_SAMPLES_S16 ? 2 : 1;
-    const int64_t pitch = round_up(I->sample_count, 16);
     const size_t bytes = (size_t)I->audio_data_offset + (size_t)I->audio_data_length;
-    DevBuf d_file, d_out;
-    VGA_HIP_TRY(d_file.alloc(bytes));
-    VGA_HIP_TRY(d_out.alloc((size_t)nch * pitch * es));
-    VGA_HIP_TRY(hipMemcpyAsync(d_file.p, file, bytes, hipMemcpyHostToDevice, st.s));
-    if (int rc = vga_nwstm_pcm_read_device(I, d_file.as<uint8_t>(), (int64_t)bytes, 1, d_out.p, sample_kind, pitch, st.s)) return rc;
-    for (int c = 0; c < nch; c++)
-        VGA_HIP_TRY(hipMemcpyAsync(out[c], d_out.as<uint8_t>() + c * pitch * es, (size_t)I->sample_count * es, hipMemcpyDeviceToHost, st.s));
-    VGA_HIP_TRY(hipStreamSynchronize(st.s));
-    return VGA_OK;
+    HostStage h;
+    return h.read_rows(file, bytes, out, nch, I->sample_count, sample_kind == VGA_SAMPLES_S16 ? 2 : 1,
+                       [&](const uint8_t *f, void *d, int64_t dp, hipStream_t s) {
+                           return vga_nwstm_pcm_read_device(I, f, (int64_t)bytes, 1, d, sample_kind, dp, s);
+                       });
 }
 
 }  // extern "C"
