@@ -3,6 +3,9 @@
 times and the HBM traffic they stand for (bytes read + written / time).  Prints one JSON object.
 
     python tools/bench_containers.py          (--pcm: the copy ceiling and the PCM stream rows only)
+
+The bank read of wave and prefetch files (vga_nwwav_bank_read_device against one copy per channel) is timed by
+tools/bench_nwwav_bank.py, which prints its own JSON line.
 """
 import ctypes as C
 import json

@@ -211,6 +211,21 @@ SIGNATURES = {
     "vga_nwstm_pcm_parse": (ci, [u8p, C.c_size_t, vp]),
     "vga_nwstm_pcm_read_device": (ci, [vp, vp, i64, ci, vp, ci, i64, vp]),
     "vga_nwstm_pcm_read": (ci, [u8p, C.c_size_t, vp, vp, ci]),
+    # include/vgaudio_hip_nwwav.h
+    "vga_nwwav_parse": (ci, [u8p, C.c_size_t, vp]),
+    "vga_nwwav_read": (ci, [u8p, C.c_size_t, vp, u8pp]),
+    "vga_nwwav_bank_create": (ci, [vp, C.POINTER(i64), ci, C.POINTER(vp)]),
+    "vga_nwwav_bank_destroy": (None, [vp]),
+    "vga_nwwav_bank_channels": (ci, [vp]),
+    "vga_nwwav_bank_codec_channels": (ci, [vp, ci]),
+    "vga_nwwav_bank_rows": (ci, [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(i64)]),
+    "vga_nwwav_bank_gc_sample_counts": (ci, [vp, C.POINTER(ci)]),
+    "vga_nwwav_bank_gc_tables": (ci, [vp, i16p, i16p, i16p, i16p]),
+    "vga_nwwav_bank_adpcm_bytes": (i64, [vp]),
+    "vga_nwwav_bank_pcm16_samples": (i64, [vp]),
+    "vga_nwwav_bank_pcm8_bytes": (i64, [vp]),
+    "vga_nwwav_bank_source_bytes": (i64, [vp]),
+    "vga_nwwav_bank_read_device": (ci, [vp, vp, vp, vp, vp, vp]),
     "vga_wave_pcm8_file_size": (i64, [vp, ci]),
     "vga_wave_write_pcm8": (ci, [vp, ci, ci, vp, u8p]),
     "vga_wave_write_pcm8_device": (ci, [vp, ci, i64, ci, vp, vp, vp]),
@@ -372,6 +387,20 @@ class NwInfoC(C.Structure):
                     "seek_table_offset", "seek_entries", "seek_big_endian", "head_block_offset", "head_block_size",
                     "seek_block_offset", "seek_block_size", "data_block_offset", "data_block_size", "audio_data_offset",
                     "audio_data_length", "adpcm_bytes", "file_size")])
+
+
+class NwWavInfoC(C.Structure):
+    """vga_nwwav_info"""
+    _fields_ = ([("kind", C.c_int), ("endianness", C.c_int), ("version", C.c_uint32)]
+                + [(n, C.c_int) for n in (
+                    "file_size", "codec", "looping", "loop_start", "sample_count", "sample_rate", "channel_count",
+                    "channel_bytes", "has_loop_start_unaligned", "loop_start_unaligned", "prefetch_count",
+                    "prefetch_start_sample", "prefetch_size", "prefetch_audio_offset", "stream_looping",
+                    "stream_sample_count", "interleave_count", "interleave_size", "samples_per_interleave",
+                    "last_block_size_without_padding", "last_block_samples", "last_block_size")]
+                + [("audio_offset", C.c_int * NW_MAX_CHANNELS), ("coefs", (C.c_int16 * 16) * NW_MAX_CHANNELS),
+                   ("gain", C.c_int16 * NW_MAX_CHANNELS), ("start_context", (C.c_int16 * 3) * NW_MAX_CHANNELS),
+                   ("loop_context", (C.c_int16 * 3) * NW_MAX_CHANNELS)])
 
 
 GC_CONTAINER_MAX_CHANNELS = 255

@@ -1,10 +1,11 @@
-// container_host.hpp -- the host layer of the container files (nwstm.hip, gc_containers.hip, container_readers.hip,
-// capi_containers.hip): byte readers and writers over files in host memory, the reference's small helpers, the batch
+// container_host.hpp -- the host layer of the container files (nwstm.hip, nwwav.hip, gc_containers.hip,
+// container_readers.hip, capi_containers.hip): byte readers (byte_reader.hpp) and writers over files in host memory, the reference's small helpers, the batch
 // argument checks, the granule choice of the batched (de-)interleaves, and the staging of the host-pointer forms.
 // Host code only; the kernels stay in container_kernels.hpp / pcm_kernels.hpp.
 #pragma once
 #include "common.hpp"
 #include "container_kernels.hpp"
+#include "byte_reader.hpp"
 #include "../../include/vgaudio_hip_pcm.h"
 
 #include <algorithm>
@@ -39,29 +40,6 @@ inline int check_sample_kind(int kind)
     set_error("unknown sample kind %d", kind);
     return VGA_ERR_ARGUMENT;
 }
-
-// Big- or little-endian reads over a file in host memory (BinaryReader, BinaryReaderBE); a read past the end or at a
-// negative position sets `eof` (EndOfStreamException) and returns 0.
-struct ByteReader {
-    const uint8_t *p;
-    int64_t len, pos = 0;
-    bool big = false, eof = false;
-    bool has(int64_t n) { if (pos < 0 || pos + n > len) { eof = true; return false; } return true; }
-    int u8() { if (!has(1)) return 0; return p[pos++]; }
-    int u16() { if (!has(2)) return 0; const int v = big ? (p[pos] << 8 | p[pos + 1]) : (p[pos] | p[pos + 1] << 8); pos += 2; return v; }
-    int i16() { return (int16_t)u16(); }
-    int i32()
-    {
-        if (!has(4)) return 0;
-        const uint32_t b0 = p[pos], b1 = p[pos + 1], b2 = p[pos + 2], b3 = p[pos + 3];
-        pos += 4;
-        return (int)(big ? (b0 << 24 | b1 << 16 | b2 << 8 | b3) : (b3 << 24 | b2 << 16 | b1 << 8 | b0));
-    }
-    // the next n bytes equal `t` (they are consumed either way)
-    bool magic(const char *t, int n) { if (!has(n)) return false; const bool ok = std::memcmp(p + pos, t, n) == 0; pos += n; return ok; }
-    bool bytes(void *out, int n) { if (!has(n)) return false; std::memcpy(out, p + pos, n); pos += n; return true; }
-    void skip_to(int64_t target) { if (target > pos) pos = std::min(target, len); }   // ReadBytes(remaining) stops at the end
-};
 
 // Big- or little-endian writes into `size` bytes of host memory; what does not fit sets `overflow` and is dropped.
 struct ByteWriter {
