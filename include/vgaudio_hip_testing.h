@@ -126,6 +126,17 @@ int vga_testing_hca_device_info(const void *hca_info, void *out, int out_bytes);
  * change.  Returns the previous setting. */
 int vga_testing_adx_read_general_this_thread(int on);
 
+/* Poison mode for every allocation the library makes.  The device pool of the host-pointer entry points hands a parked block
+ * of 1 MiB or more to any later request of half its size or more with the last call's bytes in it, the page-locked pool any
+ * idle block that is large enough, and the stream-ordered scratch of the device entry points is recycled by the runtime's
+ * pool: in production no buffer starts out as zeros.  byte = 0..255: every block -- pooled or fresh device blocks, the
+ * stream-ordered scratch, page-locked blocks, and the tables of ragged batches, sound banks and the CRC -- is filled with
+ * that byte before it is handed out; results must not depend on it.  -1 (the default) switches the mode off; other values
+ * leave the setting unchanged.  PROCESS-WIDE (the pools are), host state only: the call itself touches no device and needs
+ * none.  Stream-ordered scratch is filled on the caller's stream, which is never waited for; a block without a stream is
+ * filled on the null stream and the fill has completed when the block is handed out.  Returns the previous setting. */
+int vga_testing_poison_allocations(int byte);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,7 +85,17 @@ inline const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "o
 inline int &mock_current_device() { static thread_local int d = 0; return d; }
 inline hipError_t hipSetDevice(int d) { if (d < 0 || d >= 4) return hipErrorInvalidValue; mock_current_device() = d; return hipSuccess; }
 inline hipError_t hipGetDevice(int *d) { *d = mock_current_device(); return hipSuccess; }
-inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = std::malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+// No allocation of the mock starts out as zeros: page-locked blocks, and the "device" buffers the test driver makes
+// (mock_device_buffer), come filled with kMockJunk -- as a pool's recycled blocks do on a device.
+static const unsigned char kMockJunk = 0xA5;
+inline hipError_t hipHostMalloc(void **p, size_t n, unsigned)
+{
+    *p = std::malloc(n ? n : 1);
+    if (*p) std::memset(*p, kMockJunk, n ? n : 1);
+    return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+inline hipError_t hipMalloc(void **p, size_t n) { return hipHostMalloc(p, n, 0); }
+inline hipError_t hipFree(void *p) { std::free(p); return hipSuccess; }
 inline hipError_t hipHostFree(void *p) { std::free(p); return hipSuccess; }
 static const unsigned hipHostRegisterDefault = 0, hipHostRegisterMapped = 2;
 // a page-locked row's device-visible address: the mock's "device" is the host

@@ -9,6 +9,16 @@
 
 using namespace vga::pipe;
 
+// a "device" buffer of the mock: hipMalloc memory, junk-filled like everything the mock allocates
+struct DeviceBuffer {
+    char *p = nullptr;
+    explicit DeviceBuffer(size_t n) { (void)hipMalloc(reinterpret_cast<void **>(&p), n); }
+    DeviceBuffer(const DeviceBuffer &) = delete;
+    ~DeviceBuffer() { (void)hipFree(p); }
+    char *data() { return p; }
+    char &operator[](size_t i) { return p[i]; }
+};
+
 static int g_taper = 0, g_tail = 0, g_head = 0;
 static bool g_direct = false, g_direct_out = false, g_shared = false;
 static int g_lanes = 1;
@@ -54,7 +64,7 @@ static int run_case(int units, int in_rpu, int out_rpu, size_t in_bytes, size_t 
     std::vector<void *> out_ptrs(out_rows);
     for (int r = 0; r < in_rows; r++) in_ptrs[r] = in[r].data();
     for (int r = 0; r < out_rows; r++) out_ptrs[r] = out[r].data();
-    std::vector<char> d_in((size_t)in_rows * in_pitch + 64, 0x11), d_out((size_t)out_rows * out_pitch + 64, 0x22);
+    DeviceBuffer d_in((size_t)in_rows * in_pitch + 64), d_out((size_t)out_rows * out_pitch + 64);
 
     Job job;
     job.units = units;
@@ -180,7 +190,7 @@ static int run_ragged_case(int units, int seed, int chunks_wanted, int feeders, 
     std::vector<const void *> in_ptrs(units);
     std::vector<void *> out_ptrs(units);
     for (int u = 0; u < units; u++) { in_ptrs[u] = in[u].data(); out_ptrs[u] = out[u].data(); }
-    std::vector<char> d_in(ia + 64, 0x11), d_out(oa + 64, 0x22);
+    DeviceBuffer d_in(ia + 64), d_out(oa + 64);
     Job job;
     job.units = units;
     job.in_rows = in_ptrs.data();
@@ -318,6 +328,13 @@ int main()
         g_lanes = m[3];
         bad += all_cases();
     }
+    // the staged and ragged shapes once more in poison mode (vga_testing_poison_allocations): the page-locked pool fills every
+    // block it hands out, and the bytes must not change
+    vga::poison_setting() = 0xFF;
+    g_direct = g_direct_out = g_shared = false;
+    g_lanes = 1;
+    bad += all_cases();
+    vga::poison_setting() = -1;
     // the same shapes with the rows moved by transfer launches (direct modes only use them), CU masks on and off, and a
     // transfer launch that refuses
     g_transfer = true;
@@ -341,7 +358,7 @@ int main()
         std::vector<const void *> ip(12);
         std::vector<void *> op(12);
         for (int r = 0; r < 12; r++) { ip[r] = in[r].data(); op[r] = out[r].data(); }
-        std::vector<char> d_in(12 * 9008 + 64), d_out(12 * 9008 + 64);
+        DeviceBuffer d_in(12 * 9008 + 64), d_out(12 * 9008 + 64);
         probe.units = 12; probe.chunk_units = 4; probe.in_rows = ip.data(); probe.in_row_bytes = 9000; probe.d_in = d_in.data(); probe.d_in_pitch = 9008;
         probe.out_rows = op.data(); probe.out_row_bytes = 9000; probe.d_out = d_out.data(); probe.d_out_pitch = 9008;
         probe.direct = probe.direct_out = probe.shared_streams = true;

@@ -19,6 +19,7 @@ wait turns step 6 into a failure.  The delay ends on its own, so a broken librar
 A second test runs two calls of one entry point at once on two streams (the second overtakes the first while it waits
 behind its delay): both outputs must be right.  The ragged `_v` forms share one vga_gcadpcm_ragged handle there.
 """
+import contextlib
 import ctypes as C
 import os
 import re
@@ -73,9 +74,34 @@ def _up(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def _rows(rows, pitch, dtype):
-    """list of 1-D arrays -> [len(rows), pitch] host array, zero padded"""
-    out = np.zeros((len(rows), pitch), dtype=dtype)
+JUNK = "junk"
+_PAD = {"fill": 0}                                          # what _rows / _packed put where no row lies, unless told otherwise
+
+
+@contextlib.contextmanager
+def pad_fill(fill):
+    """inside the block, rows are padded with `fill` instead of zeros (test_gpu_dirty_memory.py: JUNK)"""
+    old, _PAD["fill"] = _PAD["fill"], fill
+    try:
+        yield
+    finally:
+        _PAD["fill"] = old
+
+
+def _filled(shape, dtype, fill):
+    """an array of `fill`; JUNK: seeded random values over the whole range of dtype"""
+    if fill is None:
+        fill = _PAD["fill"]
+    if isinstance(fill, str):
+        assert fill == JUNK
+        info = np.iinfo(dtype)
+        return np.random.default_rng(0xD1).integers(info.min, info.max + 1, shape).astype(dtype)
+    return np.full(shape, fill, dtype=dtype)
+
+
+def _rows(rows, pitch, dtype, fill=None):
+    """list of 1-D arrays -> [len(rows), pitch] host array, padded with `fill` (default 0; see pad_fill)"""
+    out = _filled((len(rows), pitch), dtype, fill)
     for i, r in enumerate(rows):
         out[i, :len(r)] = r
     return out
@@ -111,8 +137,20 @@ class Case:
             t.view(-1).view(_torch().uint8).fill_(POISON_OUT)
 
     def load(self):
+        """the real inputs, padding included: what _rows put behind the rows (zeros or junk) is restored with them"""
         for t, r in zip(self.inputs, self.real):
             t.copy_(r)
+
+    inplace_cols = None                                     # rows that work in place: the columns of inputs[0] the call rewrites
+
+    def inputs_unchanged(self):
+        """every input byte the call may not write still holds what load() put there"""
+        for i, (t, r) in enumerate(zip(self.inputs, self.real)):
+            if i == 0 and self.inplace_cols is not None:
+                t, r = t[:, self.inplace_cols:], r[:, self.inplace_cols:]
+            if not bool((t == r).all()):
+                return False
+        return True
 
 
 def _ok(rc):
@@ -211,8 +249,8 @@ def _ragged_data(k):
     return chans, coefs, adpcm
 
 
-def _packed(r, rows, offsets, total, dtype):
-    host = np.zeros(total, dtype=dtype)
+def _packed(r, rows, offsets, total, dtype, fill=None):
+    host = _filled(total, dtype, fill)
     for o, a in zip(offsets, rows):
         host[int(o):int(o) + len(a)] = a
     return host
@@ -822,9 +860,11 @@ def row_adx_crypt(k, shared):
     key = _adx_keys()[2 + k]
     want = np.stack(po.adx_crypt(list(audio), _okey(key), 8))
     d = _up(_rows(audio, _pitch(18 * frames), np.uint8))
-    return Case([d], [],
+    case = Case([d], [],
                 lambda s: L.vga_adx_crypt_device(d.data_ptr(), d.shape[1], 18 * frames, nch, C.byref(key), 8, 18, s),
                 lambda: _eq(d[:, :18 * frames], want, "audio"))
+    case.inplace_cols = 18 * frames
+    return case
 
 
 def row_adx_find_key(k, shared):
@@ -860,9 +900,11 @@ def row_hca_crypt(k, shared):
     rc, dec, enc = po.hca_key_tables(56, 123456789 + k)
     want = np.stack([po.hca_crypt(frames[s], fs, enc) for s in range(ns)])
     d = _up(_rows(frames, _pitch(fc * fs), np.uint8))
-    return Case([d], [],
+    case = Case([d], [],
                 lambda s: L.vga_hca_crypt_device(d.data_ptr(), d.shape[1], ns, fc, fs, enc.ctypes.data_as(_lib.u8p), s),
                 lambda: _eq(d[:, :fc * fs], want, "frames"))
+    case.inplace_cols = fc * fs
+    return case
 
 
 def row_hca_find_key(k, shared):

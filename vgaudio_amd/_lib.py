@@ -177,6 +177,7 @@ SIGNATURES = {
     "vga_testing_host_transfer_piece_bytes_this_thread": (None, [ci]),
     "vga_testing_host_compute_lanes_this_thread": (None, [ci]),
     "vga_testing_fail_step_this_thread": (None, [ci, ci]),
+    "vga_testing_poison_allocations": (ci, [ci]),
     "vga_testing_plan_buckets": (ci, [C.POINTER(ci), C.POINTER(ci), ci, ci, C.c_longlong, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci),
                                  C.POINTER(ci), ci]),
     "vga_testing_hca_device_info": (ci, [vp, vp, ci]),

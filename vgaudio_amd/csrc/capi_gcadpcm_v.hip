@@ -214,7 +214,7 @@ int vga_gcadpcm_ragged_create(const int *sample_counts, int nch, vga_gcadpcm_rag
     const size_t tb = r->shape.table_bytes();
     std::vector<unsigned char> host(tb ? tb : 16);
     r->shape.write_tables(host.data());
-    hipError_t e = hipMalloc(&r->d_tables, host.size());
+    hipError_t e = device_malloc(&r->d_tables, host.size());
     if (e == hipSuccess) e = hipMemcpy(r->d_tables, host.data(), host.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         if (r->d_tables) (void)hipFree(r->d_tables);

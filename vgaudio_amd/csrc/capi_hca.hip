@@ -197,7 +197,7 @@ int vga::hca::crc_pow_table(const uint16_t **out)
             for (int j = 0; j < 8; j++) v = ((v << 1) ^ ((v & 0x8000u) ? 0x8005u : 0u)) & 0xFFFFu;
         }
         uint16_t *d = nullptr;
-        VGA_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof host));
+        VGA_HIP_TRY(device_malloc(reinterpret_cast<void **>(&d), sizeof host));
         VGA_HIP_TRY(hipMemcpy(d, host, sizeof host, hipMemcpyHostToDevice));
         g_crc_pow.dev[device] = d;
     }

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/vgaudio_hip.h"
+#include "poison.hpp"
 
 namespace vga {
 
@@ -28,6 +29,22 @@ bool take_error_pending();
         }                                                                              \
     } while (0)
 
+// Poison mode (vga_testing_poison_allocations): a block that has no stream is filled on the null stream, and the fill is
+// complete when this returns.  The library's own streams and a caller's non-blocking streams are not waited for.
+inline hipError_t poison_block(void *p, size_t bytes)
+{
+    const int byte = poison_byte();
+    if (byte < 0 || !p || !bytes) return hipSuccess;
+    const hipError_t e = hipMemset(p, byte, bytes);
+    return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
+// hipMalloc for the few tables that live outside the pool (ragged batches, sound banks, the CRC table)
+inline hipError_t device_malloc(void **out, size_t bytes)
+{
+    const hipError_t e = hipMalloc(out, bytes);
+    return e != hipSuccess ? e : poison_block(*out, bytes);
+}
+
 // Process-wide cache of the host-buffer entry points' device allocations.  hipMalloc maps memory at ~25 GB/s (1.4 s for
 // the 44 GB of a configs[1] call: more than the call's transfers and kernels together); a caller converting batch after
 // batch gets the previous call's buffers back instead.  Blocks of at least 1 MiB are parked on release (up to 64 GiB PER
@@ -43,36 +60,11 @@ public:
         static DevicePool pool;
         return pool;
     }
+    // a stale block keeps the last call's bytes: nothing clears it (poison mode fills it, pooled or not)
     hipError_t acquire(void **out, size_t bytes)
     {
-        if (bytes < kMinPooled) return hipMalloc(out, bytes ? bytes : 1);
-        int device = 0;
-        (void)hipGetDevice(&device);
-        {
-            std::lock_guard<std::mutex> g(m_);
-            int best = -1;
-            for (int i = 0; i < (int)blocks_.size(); i++) {
-                const Block &b = blocks_[i];
-                if (!b.busy && b.device == device && b.bytes >= bytes && b.bytes / 2 <= bytes &&
-                    (best < 0 || b.bytes < blocks_[best].bytes))
-                    best = i;
-            }
-            if (best >= 0) {
-                blocks_[best].busy = true;
-                *out = blocks_[best].p;
-                return hipSuccess;
-            }
-        }
-        hipError_t e = hipMalloc(out, bytes);
-        if (e != hipSuccess) {                             // out of memory with blocks parked: drop them and retry once
-            trim();
-            e = hipMalloc(out, bytes);
-        }
-        if (e == hipSuccess) {
-            std::lock_guard<std::mutex> g(m_);
-            blocks_.push_back({*out, bytes, device, true});
-        }
-        return e;
+        const hipError_t e = acquire_block(out, bytes);
+        return e != hipSuccess ? e : poison_block(*out, bytes ? bytes : 1);
     }
     void release(void *p)
     {
@@ -125,6 +117,37 @@ public:
 
 private:
     static constexpr size_t kMinPooled = (size_t)1 << 20;
+    hipError_t acquire_block(void **out, size_t bytes)
+    {
+        if (bytes < kMinPooled) return hipMalloc(out, bytes ? bytes : 1);
+        int device = 0;
+        (void)hipGetDevice(&device);
+        {
+            std::lock_guard<std::mutex> g(m_);
+            int best = -1;
+            for (int i = 0; i < (int)blocks_.size(); i++) {
+                const Block &b = blocks_[i];
+                if (!b.busy && b.device == device && b.bytes >= bytes && b.bytes / 2 <= bytes &&
+                    (best < 0 || b.bytes < blocks_[best].bytes))
+                    best = i;
+            }
+            if (best >= 0) {
+                blocks_[best].busy = true;
+                *out = blocks_[best].p;
+                return hipSuccess;
+            }
+        }
+        hipError_t e = hipMalloc(out, bytes);
+        if (e != hipSuccess) {                             // out of memory with blocks parked: drop them and retry once
+            trim();
+            e = hipMalloc(out, bytes);
+        }
+        if (e == hipSuccess) {
+            std::lock_guard<std::mutex> g(m_);
+            blocks_.push_back({*out, bytes, device, true});
+        }
+        return e;
+    }
     static size_t keep_bytes()
     {
         static const size_t v = [] {
@@ -180,7 +203,9 @@ struct AsyncBuf {
     ~AsyncBuf() { if (p) (void)hipFreeAsync(p, stream); }
     hipError_t alloc(size_t n, hipStream_t s) {
         stream = s;
-        return hipMallocAsync(&p, n ? n : 1, s);
+        const hipError_t e = hipMallocAsync(&p, n ? n : 1, s);
+        const int byte = poison_byte();                    // poison mode: filled in stream order, the caller's stream is not waited for
+        return e != hipSuccess || byte < 0 ? e : hipMemsetAsync(p, byte, n ? n : 1, s);
     }
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };

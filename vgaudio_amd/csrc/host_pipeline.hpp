@@ -40,6 +40,8 @@
 #include <thread>
 #include <vector>
 
+#include "poison.hpp"
+
 namespace vga {
 namespace pipe {
 
@@ -51,23 +53,13 @@ public:
         static PinnedPool pool;
         return pool;
     }
-    // a page-locked block of at least `bytes` (nullptr on failure)
+    // a page-locked block of at least `bytes` (nullptr on failure); an idle block comes back with its old bytes (poison
+    // mode, vga_testing_poison_allocations: filled first)
     void *acquire(size_t bytes)
     {
-        {
-            std::lock_guard<std::mutex> g(m_);
-            int best = -1;
-            for (int i = 0; i < (int)blocks_.size(); i++)
-                if (!blocks_[i].busy && blocks_[i].bytes >= bytes && (best < 0 || blocks_[i].bytes < blocks_[best].bytes)) best = i;
-            if (best >= 0) {
-                blocks_[best].busy = true;
-                return blocks_[best].p;
-            }
-        }
-        void *p = nullptr;
-        if (hipHostMalloc(&p, bytes, hipHostMallocPortable) != hipSuccess) return nullptr;
-        std::lock_guard<std::mutex> g(m_);
-        blocks_.push_back({p, bytes, true});
+        void *p = acquire_block(bytes);
+        const int byte = poison_byte();
+        if (p && byte >= 0) std::memset(p, byte, bytes);
         return p;
     }
     void release(void *p)
@@ -101,6 +93,24 @@ public:
 
 private:
     static constexpr size_t kKeepBytes = (size_t)1 << 30;
+    void *acquire_block(size_t bytes)
+    {
+        {
+            std::lock_guard<std::mutex> g(m_);
+            int best = -1;
+            for (int i = 0; i < (int)blocks_.size(); i++)
+                if (!blocks_[i].busy && blocks_[i].bytes >= bytes && (best < 0 || blocks_[i].bytes < blocks_[best].bytes)) best = i;
+            if (best >= 0) {
+                blocks_[best].busy = true;
+                return blocks_[best].p;
+            }
+        }
+        void *p = nullptr;
+        if (hipHostMalloc(&p, bytes, hipHostMallocPortable) != hipSuccess) return nullptr;
+        std::lock_guard<std::mutex> g(m_);
+        blocks_.push_back({p, bytes, true});
+        return p;
+    }
     struct Block { void *p; size_t bytes; bool busy; };
     std::mutex m_;
     std::vector<Block> blocks_;

@@ -239,7 +239,7 @@ int vga_nwwav_bank_create(const vga_nwwav_info *infos, const int64_t *file_offse
     b->groups = (int)groups.size() - 1;
     (void)hipGetDevice(&b->device);
     const size_t piece_bytes = pieces.size() * sizeof(Piece), bytes = piece_bytes + groups.size() * 4;
-    hipError_t e = hipMalloc(&b->d_tables, bytes);
+    hipError_t e = device_malloc(&b->d_tables, bytes);
     if (e == hipSuccess && piece_bytes) e = hipMemcpy(b->d_tables, pieces.data(), piece_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(static_cast<uint8_t *>(b->d_tables) + piece_bytes, groups.data(), groups.size() * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) {

@@ -195,6 +195,11 @@ void vga_testing_fail_step_this_thread(int kind, int nth)
     g_settings.fail = FailStep{on ? kind : 0, on ? nth : 0, 0};
 }
 void vga_testing_host_compute_lanes_this_thread(int lanes) { g_settings.pipe.compute_lanes = lanes > 0 ? lanes : 0; }
+int vga_testing_poison_allocations(int byte)
+{
+    if (byte < -1 || byte > 255) return poison_byte();
+    return poison_setting().exchange(byte, std::memory_order_relaxed);
+}
 
 int vga_testing_plan_buckets(const int *group, const int *length, int n, int max_units, long long max_volume, int longest_first,
                              int *order_out, int *chunk_begin_out, int *chunk_length_out, int *chunk_group_out, int max_chunks)
