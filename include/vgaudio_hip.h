@@ -778,8 +778,12 @@ void vga_hca_stream_destroy(vga_hca_stream *stream);
  * frames_out[s]: infos_out[s].frame_count * frame_size bytes.  Streams that differ in length only (not looping) share
  * their launches (zero-padded buckets a quarter wide: frame size and band counts follow from the bitrate,
  * CriHcaEncoder.cs:288-368, every frame is encoded on its own and the encoder's input past the PCM is silence, :234-240);
- * results are byte for byte those of one call per stream.  Decoding groups the streams by HcaInfo: streams of one shape
- * decode together, a batch of all-different lengths costs a call per stream. */
+ * results are byte for byte those of one call per stream.  Decoding shares launches the same way: streams whose frame
+ * size, band layout, channel types and ATH curve agree -- whatever their lengths, loop fields and lead-in -- are sorted into
+ * buckets a quarter wide, one pipelined job per channel count, and every stream of a bucket decodes to its own frame_count,
+ * sample_count and inserted_samples in one set of launches (nothing is decoded behind a stream's own last frame).  pcm_out:
+ * the streams' channels one after the other, infos[s].sample_count shorts each; results are byte for byte those of one
+ * vga_hca_decode_batch call per stream, a bad frame in any stream fails the call (VGA_ERR_INVALID_DATA). */
 int vga_hca_encode_batch_v(const int16_t *const *pcm, int nstreams, const vga_hca_params *configs,
                            vga_hca_info *infos_out, uint8_t *const *frames_out);
 int vga_hca_decode_batch_v(const vga_hca_info *infos, const uint8_t *const *frames, int nstreams,

@@ -121,6 +121,18 @@ int vga_testing_hca_frames_per_group_this_thread(int frames);
  * needs no GPU: the CPU suite feeds it to the lane emulator of the HCA decoder (tests/host/hca_decode_emulator.cpp). */
 int vga_testing_hca_device_info(const void *hca_info, void *out, int out_bytes);
 
+/* vga_hca_decode_batch_v sorts its streams into shape classes -- equality of the DeviceInfo above with frame_count,
+ * sample_count and inserted_samples ignored; the loop fields, comment_length and header_size of the HcaInfo are not part of
+ * it -- and the streams of one class and one length bucket share their launches.  infos: nstreams vga_hca_info;
+ * class_out[s]: the class of stream s, dense ids in order of first appearance.  Returns the number of classes, negative on
+ * bad arguments or an HcaInfo the decoder refuses.  Host code, needs no GPU. */
+int vga_testing_hca_decode_classes(const void *infos, int nstreams, int *class_out);
+/* The calling thread's last vga_hca_decode_batch_v call: [0] pipeline jobs run (one per channel count present and device
+ * share) [1] chunks = launch sets [2] shape classes [3] own frames (the sum of the streams' frame_count) [4] frame slots
+ * launched (the sum over the chunks of streams x the chunk's longest frame_count; a slot behind a stream's own frames does
+ * no work).  Writes min(n, 5) fields and returns 5. */
+int vga_testing_hca_decode_v_stats(long long *out, int n);
+
 /* The ADX file reader (vga_adx_read_device) moves 18-byte frames with a kernel of 16-byte vectors when the rows are 16-byte
  * aligned.  on != 0 sends calls made from the calling thread to the general de-interleave instead; the bytes must not
  * change.  Returns the previous setting. */

@@ -181,6 +181,8 @@ SIGNATURES = {
     "vga_testing_plan_buckets": (ci, [C.POINTER(ci), C.POINTER(ci), ci, ci, C.c_longlong, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci),
                                  C.POINTER(ci), ci]),
     "vga_testing_hca_device_info": (ci, [vp, vp, ci]),
+    "vga_testing_hca_decode_classes": (ci, [vp, ci, C.POINTER(ci)]),
+    "vga_testing_hca_decode_v_stats": (ci, [C.POINTER(C.c_longlong), ci]),
     "vga_hca_stream_create": (ci, [vp, vp, C.POINTER(vp)]),
     "vga_hca_stream_encode": (ci, [vp, vp, u8p, C.POINTER(ci)]),
     "vga_hca_stream_pending_frame_count": (ci, [vp]),

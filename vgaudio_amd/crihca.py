@@ -238,6 +238,34 @@ def encode_files(pcm16_list, configs=None):
     return result
 
 
+def decode_streams(streams):
+    """CriHcaDecoder.Decode (CriHcaDecoder.cs:11-29) of many streams of any shape in ONE ragged GPU call
+    (vga_hca_decode_batch_v).  streams: (HcaInfo, audio) pairs, audio = [FrameCount][FrameSize] bytes or flat.  Streams that
+    differ in length, lead-in or loop fields only share their launches.  Returns one list of ChannelCount int16 arrays
+    (SampleCount samples each) per stream."""
+    streams = list(streams)
+    ns = len(streams)
+    if not ns:
+        return []
+    infos = (_lib.HcaInfoC * ns)(*[_lib.HcaInfoC.from_buffer_copy(h.c if isinstance(h, HcaInfo) else h) for h, _ in streams])
+    flat = [np.ascontiguousarray(a, dtype=np.uint8).reshape(-1) for _, a in streams]
+    for s_, f in enumerate(flat):
+        if len(f) < max(infos[s_].frame_count, 0) * max(infos[s_].frame_size, 0):
+            raise _lib.ArgumentError("stream %d: audio shorter than FrameCount * FrameSize" % s_)
+        if not 1 <= infos[s_].channel_count <= 8:
+            raise _lib.ArgumentError("stream %d: bad channel count" % s_)       # (sizes the row list below)
+    outs = [[np.zeros(max(infos[s_].sample_count, 0), dtype=np.int16) for _ in range(infos[s_].channel_count)] for s_ in range(ns)]
+    check(_lib.lib().vga_hca_decode_batch_v(infos, _ptr_array(u8p, flat), ns, _ptr_array(i16p, [r for o in outs for r in o])))
+    return outs
+
+
+def decode_files(formats):
+    """CriHcaFormat.ToPcm16 (CriHcaFormat.cs:26-32) of many files in one ragged GPU call: one Pcm16Format per CriHcaFormat."""
+    formats = list(formats)
+    pcm = decode_streams([(f.Hca, f.AudioData) for f in formats])
+    return [Pcm16Format(p, f.Hca.SampleRate) for p, f in zip(pcm, formats)]
+
+
 class CriHcaKey:
     """Codecs/CriHca/CriHcaKey.cs:8-39: CriHcaKey(keyCode) (KeyType 56) | CriHcaKey.Type0 / Type1."""
     Type0, Type1 = "Type0", "Type1"

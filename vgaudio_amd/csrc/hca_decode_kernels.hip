@@ -24,6 +24,14 @@
 // decoder cannot reproduce -- such frames (corrupt streams only) are flagged in *status (bit 1), an
 // invalid sync word in bit 0 (the reference throws InvalidDataException), an intensity of 15 in bit 5 (the reference
 // throws IndexOutOfRangeException; the frames kernel's min(iq, 14) only keeps the table read inside the table).
+//
+// Streams of different lengths in one launch (vga_hca_decode_batch_v): both kernels are templates on RAGGED.  With a table
+// of one int4 per stream {frame_count, sample_count, inserted_samples, 0} the launch's info.frame_count is the LONGEST
+// stream's -- it sizes the grid and indexes the records -- and a stream runs to its own three values: a scan lane at or past
+// its stream's own frame count reads nothing and reports nothing (the rows are zero-padded behind a short stream; a zero
+// sync word would otherwise fail the call), its record slot stays unwritten and is never read; a frames workgroup whose run
+// begins there leaves before its first barrier.  RAGGED = false is the equal-length launch as it always was: the table is
+// a template parameter, not a null test, so that path pays nothing for it.
 #include "common.hpp"
 #include "hca_device.hpp"
 #include "hca_decode_core.hpp"
@@ -50,12 +58,16 @@ struct ScanTables {
     __device__ __forceinline__ const uint8_t *res_curve() const { return curve; }
 };
 
+template <bool RAGGED>
 struct GlobalSrc {
     const uint32_t *base;              // the frame's first aligned dword
-    int limit;                         // dwords readable from there (to the end of the stream's pitch)
+    int limit;                         // dwords readable from there (to the end of the stream's pitch); RAGGED: 0 = an idle lane
     __device__ __forceinline__ void quad(int k, uint32_t out[4]) const
     {
-        if (k + 3 < limit) {
+        if (RAGGED && limit <= 0) {    // past the stream's own last frame: zeros, no load
+#pragma unroll
+            for (int e = 0; e < 4; e++) out[e] = 0;
+        } else if (k + 3 < limit) {
             const Dwords4 v = *reinterpret_cast<const Dwords4 *>(base + k);
 #pragma unroll
             for (int e = 0; e < 4; e++) out[e] = v.v[e];
@@ -77,19 +89,22 @@ struct LdsRes {
 };
 // Record pieces (16 bytes each, in record order) are staged per lane and leave four at a time: 64 contiguous bytes per
 // record, four lanes per record (a lane's own 16-byte stores would touch 64 records 576 bytes apart per instruction).
+template <bool RAGGED>
 struct StagedOut {
     uint4 (*stage)[5];                 // [lane][piece], 80-byte rows
     uint8_t *records;                  // record of the wave's first frame
     size_t record_bytes;
     int lane, live_records;            // records [0, live_records) of this wave exist
+    uint64_t live_mask;                // RAGGED: bit r = record r of this wave exists (the lanes that hold a frame of their stream)
     int count;
+    __device__ __forceinline__ bool exists(int rr) const { return RAGGED ? ((live_mask >> rr) & 1) != 0 : rr < live_records; }
     __device__ __forceinline__ void flush(int group, int pieces)
     {
         wave_lds_sync();
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int rr = k * 16 + (lane >> 2), piece = lane & 3;
-            if (piece < pieces && rr < live_records)
+            if (piece < pieces && exists(rr))
                 *reinterpret_cast<uint4 *>(records + (size_t)rr * record_bytes + (size_t)group * 64 + piece * 16) = stage[rr][piece];
         }
         wave_lds_sync();
@@ -108,10 +123,17 @@ struct StagedOut {
 
 }  // namespace
 
+template <bool RAGGED>
 __global__ __launch_bounds__(64) void hca_scan_kernel(const uint8_t *__restrict__ frames, int64_t stream_pitch, int nstreams,
                                                       DeviceInfo info, DecodeLayout lay, uint8_t *__restrict__ records,
-                                                      int *__restrict__ status)
+                                                      int *__restrict__ status, const int4 *__restrict__ dims)
 {
+    if constexpr (RAGGED) {            // a wave whose 64 slots all lie behind their streams' own frames: nothing to do (one wave a block)
+        const int64_t g = (int64_t)blockIdx.x * 64 + threadIdx.x;
+        bool any = g < (int64_t)nstreams * info.frame_count;
+        if (any) any = (int)(g % info.frame_count) < dims[g / info.frame_count].x;
+        if (__ballot(any) == 0) return;
+    }
     extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];   // res[nch][16][64]
     __shared__ ScanTables T;
     __shared__ uint32_t s_ring[16 * 64];
@@ -134,23 +156,27 @@ __global__ __launch_bounds__(64) void hca_scan_kernel(const uint8_t *__restrict_
     const int64_t first = (int64_t)blockIdx.x * 64;
     const int64_t total = (int64_t)nstreams * info.frame_count;
     const int64_t gid = first + lane;
-    const bool live = gid < total;
+    bool live = gid < total;
     const int64_t id = live ? gid : total - 1;
     const int stream = (int)(id / info.frame_count);
     const int frame = (int)(id % info.frame_count);
+    if constexpr (RAGGED) live = live && frame < dims[stream].x;       // `stream` differs per lane: a load per lane
     const int64_t a0 = (int64_t)frame * info.frame_size;               // byte offset of the frame inside its stream
 
-    GlobalSrc src;
+    GlobalSrc<RAGGED> src;
     src.base = reinterpret_cast<const uint32_t *>(frames + (int64_t)stream * stream_pitch) + (a0 >> 2);
     src.limit = (int)(stream_pitch / 4 - (a0 >> 2));
+    if constexpr (RAGGED) src.limit = live ? src.limit : 0;            // an idle lane goes through the motions on zeros (the
+                                                                       // wave's lanes hand their records out together, StagedOut)
     LdsRing ring{s_ring + lane};
     LdsRes res{s_dyn + lane};
-    StagedOut out;
+    StagedOut<RAGGED> out;
     out.stage = s_stage;
     out.records = records + (size_t)first * lay.record_bytes;
     out.record_bytes = (size_t)lay.record_bytes;
     out.lane = lane;
     out.live_records = (int)min((int64_t)64, total - first);
+    out.live_mask = RAGGED ? __ballot(live) : 0;
     out.count = 0;
     ScanParams P;
     P.nch = info.nch;
@@ -206,11 +232,24 @@ struct Res16 {
 
 }  // namespace
 
+template <bool RAGGED>
 __global__ __launch_bounds__(FRAMES_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void hca_frames_kernel(
     const uint8_t *__restrict__ frames, int64_t frames_pitch, DeviceInfo info, DecodeLayout lay,
     const uint8_t *__restrict__ records, int frames_per_group, int groups_per_stream, int16_t *__restrict__ pcm,
-    int64_t stream_pitch, int64_t ch_pitch)
+    int64_t stream_pitch, int64_t ch_pitch, const int4 *__restrict__ dims)
 {
+    // the stream's own length, lead-in and sample count; RAGGED: from the table (the workgroup's stream is uniform: scalar
+    // loads), and a run that begins behind the stream's last frame ends here, all threads together, before any barrier
+    // (the equal-length form reads info's fields where it always did: the frames kernel sits at its register limit, and
+    // where those scalar loads are issued decides what it spills)
+    int own_frames = 0, own_samples = 0, own_inserted = 0;
+    if constexpr (RAGGED) {
+        const int4 d = dims[blockIdx.x / groups_per_stream];
+        own_frames = d.x;
+        own_samples = d.y;
+        own_inserted = d.z;
+        if ((int)(blockIdx.x % groups_per_stream) * frames_per_group >= own_frames) return;
+    }
     extern __shared__ __attribute__((aligned(16))) char s_mem[];
     __shared__ FramesTables T;
     const int nch = info.nch;
@@ -246,7 +285,7 @@ __global__ __launch_bounds__(FRAMES_THREADS) __attribute__((amdgpu_waves_per_eu(
 
     const int stream = blockIdx.x / groups_per_stream;
     const int f0 = (blockIdx.x % groups_per_stream) * frames_per_group;
-    const int f1 = min(f0 + frames_per_group, info.frame_count);
+    const int f1 = min(f0 + frames_per_group, RAGGED ? own_frames : info.frame_count);
     const uint32_t *sbase = reinterpret_cast<const uint32_t *>(frames + (int64_t)stream * frames_pitch);
     const int64_t last_word = frames_pitch / 4 - 1;
     const uint8_t *srec = records + (size_t)stream * info.frame_count * lay.record_bytes;
@@ -405,8 +444,8 @@ __global__ __launch_bounds__(FRAMES_THREADS) __attribute__((amdgpu_waves_per_eu(
                     const double cur = *reinterpret_cast<const double *>(chrows + slot * ROW_BYTES + cur_at);
                     const double prev = *reinterpret_cast<const double *>(chrows + pslot * ROW_BYTES + prev_at);
                     const int sample = imdct_sample(tid < 64, w_cur, w_prev, cur, prev);
-                    const int64_t tpos = (int64_t)f * SPF + sf * SPSF + tid - info.inserted_samples;
-                    if (tpos >= 0 && tpos < info.sample_count) dst[tpos] = (int16_t)sample;
+                    const int64_t tpos = (int64_t)f * SPF + sf * SPSF + tid - (RAGGED ? own_inserted : info.inserted_samples);
+                    if (tpos >= 0 && tpos < (RAGGED ? own_samples : info.sample_count)) dst[tpos] = (int16_t)sample;
                     pslot = slot;
                     slot = slot + 1 >= 9 ? 0 : slot + 1;
                 }
@@ -416,16 +455,17 @@ __global__ __launch_bounds__(FRAMES_THREADS) __attribute__((amdgpu_waves_per_eu(
 }
 
 int launch_decode(const uint8_t *d_frames, int64_t frames_pitch, int nstreams, const DeviceInfo &info, int16_t *d_pcm,
-                  int64_t stream_pitch, int64_t ch_pitch, void *d_workspace, int *d_status, hipStream_t stream)
+                  int64_t stream_pitch, int64_t ch_pitch, void *d_workspace, int *d_status, hipStream_t stream, const int4 *d_dims)
 {
     if (nstreams <= 0 || info.frame_count <= 0) return VGA_OK;
     const DecodeLayout lay = make_decode_layout(info);
     const int64_t total = (int64_t)nstreams * info.frame_count;
     uint8_t *records = reinterpret_cast<uint8_t *>(d_workspace);
     const size_t lds1 = (size_t)info.nch * 16 * 64 * sizeof(uint32_t);
-    if (lds1 > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_scan_kernel, lds1));
-    hipLaunchKernelGGL(hca_scan_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), lds1, stream, d_frames, frames_pitch,
-                       nstreams, info, lay, records, d_status);
+    const auto scan = d_dims ? hca_scan_kernel<true> : hca_scan_kernel<false>;
+    if (lds1 > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(scan, lds1));
+    hipLaunchKernelGGL(scan, dim3((unsigned)((total + 63) / 64)), dim3(64), lds1, stream, d_frames, frames_pitch, nstreams, info,
+                       lay, records, d_status, d_dims);
     // (test hook as in launch_encode: n > 0 = frames per group; 1000 + n means the same here.  A wave-per-frame form of this
     // launch, the encoder's scheme, was built and measured in round 6 and is not used: 20.0 ms against this kernel's 18.7 --
     // 7.5 G VALU instructions at 0.61 of the issue slots, 13.7 KB of LDS a wave = two waves per SIMD, and the 16-code chunks'
@@ -443,10 +483,11 @@ int launch_decode(const uint8_t *d_frames, int64_t frames_pitch, int nstreams, c
     const int groups = (info.frame_count + per_group - 1) / per_group;
     const size_t lds2 = (size_t)info.nch * 9 * ROW_BYTES + (size_t)info.nch * 128 * 9 +
                         (size_t)((lay.frame_dwords + 1 + 3) / 4 * 4) * 4 + (size_t)lay.record_bytes;
-    if (lds2 > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_frames_kernel, lds2));
-    hipLaunchKernelGGL(hca_frames_kernel, dim3((unsigned)((int64_t)nstreams * groups)), dim3(FRAMES_THREADS), lds2, stream,
-                       d_frames, frames_pitch, info, lay, reinterpret_cast<const uint8_t *>(records), per_group, groups, d_pcm,
-                       stream_pitch, ch_pitch);
+    const auto run_frames = d_dims ? hca_frames_kernel<true> : hca_frames_kernel<false>;
+    if (lds2 > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(run_frames, lds2));
+    hipLaunchKernelGGL(run_frames, dim3((unsigned)((int64_t)nstreams * groups)), dim3(FRAMES_THREADS), lds2, stream, d_frames,
+                       frames_pitch, info, lay, reinterpret_cast<const uint8_t *>(records), per_group, groups, d_pcm, stream_pitch,
+                       ch_pitch, d_dims);
     VGA_HIP_TRY(hipGetLastError());
     return VGA_OK;
 }
