@@ -8,7 +8,7 @@ Prints static instruction counts per block of the HOT path of one frame (lane = 
 = 8 channel-frames = 112 samples), the cold block's path for a plain third trip, the helper wave's loop per tile, and the
 resulting lane-operations per sample with the measured rates (cold-block rate, short-pass share) filled in.
 
-    python tools/isa_budget_gc.py > profiles/r06_gc_encode_isa_budget.md
+    python tools/isa_budget_gc.py > profiles/r07_gc_encode_isa_budget.md
 """
 import collections
 import os
@@ -97,11 +97,11 @@ def main():
         pre.append(t)
         if t.startswith("s_cbranch_execz"):
             skip_to = t.split()[1]
-    rows = [("row reads (12 x ds_read_b128) + pre-scan of the two history-dependent distances + first scale", count(pre)),
+    rows = [("row reads (8 x ds_read_b128) + pre-scan of the two history-dependent distances + first scale", count(pre)),
             ("passes B (s1 + 1) and A (s1) without the f32 detour, 28 sample steps", count(L[short_blk[0]:short_blk[1]])),
             ("the same with the conversions (30 % of the wave-frames take these instead)", count(L[normal_blk[0]:normal_blk[1]])),
             ("select the pass the reference ends on, 8-predictor argmin (DPP), winner's history, 4 x ds_write_b128", count(L[normal_blk[1]:tail_end + 1]))]
-    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 6)\n")
+    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 7)\n")
     print("`gc_encode_persistent_kernel<8, false>`, static counts from hipcc's gfx950 listing of `vgaudio_amd/csrc/gc_encode_kernel.hip`")
     print("(`tools/isa_budget_gc.py`).  One wave-frame = 64 lanes = 8 channels x 8 predictors = 112 input samples.\n")
     print("| block of the hot frame | total | VALU | SALU | LDS | wait / nop |")
@@ -126,32 +126,24 @@ def main():
                     ("cold block, %.3f x (third pass + ~45)" % COLD_RATE, COLD_RATE * (third_pass["VALU"] + 45)),
                     ("encoder wave, sum", per_frame)):
         print("| %s | %.0f | %.0f |" % (name, v, v * 64 / 112))
-    print("\nMeasured (profiles/r05_sq_counters.json, same kernel arithmetic): 75.4 G VALU wave-instructions per launch / 105.3 M "
-          "wave-frames = 716 per wave-frame = 409 lane-ops per sample.  The difference to the encoder wave's sum is the HELPER wave "
+    print("\nMeasured (profiles/r07_sq_counters_change.json): 70.37 G VALU wave-instructions per launch / 105.3 M "
+          "wave-frames = 668 per wave-frame = 382 lane-ops per sample (parent, same session: 74.69 G = 709).  The difference to the encoder wave's sum is the HELPER wave "
           "(one per two encoder waves: per tile of 4 frames x 16 channels it unpacks the frames, computes 96 pre-scan distances per "
           "frame with v_dot2 -- 576 of its ~950 instructions --, packs and stores the previous tile's winners) and the seams "
           "(0.3 % of the frames re-encoded).")
     print("""
-## What the budget says (round 6)
+## What the budget says (round 7)
 
-* The two passes are 226 of the 409 lane-operations per sample -- 13.7 VALU instructions per sample step and predictor (two
-  multiply-adds for the distance, three for the rounded shift, the nibble clamp, three for the reconstruction, its clamp, the
-  error and its square-accumulate, half a max3 / min3 for the overflow): nothing in them is bookkeeping.
-* The largest non-pass item is the HELPER's pre-scan: 96 distances per frame at 6 instructions each (v_dot2, the truncating
-  division by 2048 in three, the difference, half a max3 / min3) = ~72 VALU per encoder wave-frame, 10 % of the launch.  In
-  the numerator's domain (N = 2048 x - P: the distance is ceil(N / 2048) or floor(N / 2048) by the sign of P, both monotone)
-  the running extremes cost 3 instructions per distance and decide the first scale unless an extreme lies within one of a
-  power of two or of 9 x 2^j -- then the exact scan of that frame runs; costed at ~34 VALU per wave-frame (4.7 %) for a second
-  way through the first-scale logic and its emulator, not built.
-* The cold block is 53 lane-operations per sample for 1.25 lanes of work per visit.  Its entry was trimmed (385 -> ~290
-  instructions a visit: the resume point of the generic path worked out only where it is taken, the literal pass's set-up no
-  longer hoisted into every visit) with NO change in time (146.1 against 145.9 ms, same box): what a visit costs is the third
-  pass's own dependent chain, a single one where the hot pair interleaves two.  Deferring third trips (LABNOTES 9.5) or
-  batching them over a tile's frames was costed again with the roll-back's price: 67-74 instructions per frame against 78.
-* Select / argmin / commit: 45 VALU + 34 SALU.  Storing the winner's nibbles under its own mask instead of fourteen selects
-  in every lane removes 18 VALU and adds two exec-masked branches to the wave's critical path: 148.5 ms against 146.0.
-  The wave is bound by the latency of its own chain as much as by the SIMD's issue slots (0.86-0.88 busy): removing
-  instructions that are off the chain buys nothing, adding branches on it costs.
+* Round 6's table is `profiles/r06_gc_encode_isa_budget.md` (same tool, same options): passes 384 / 425 VALU, per wave-frame
+  396 + 77 + 45 + 92 = 610.  The pass body was 13.7 VALU per sample step and predictor with the history in two sign-extended
+  registers; on a packed pair (gc_encode_core.hpp P1-P6) it is 12.75 without the f32 rounding: v_dot2_i32_i16 (three-operand,
+  the 1024 from a scalar register), the distance, sign bit, add3, shift, nibble clamp, P >> 11, lshl_add, v_cvt_pk_i16_i32
+  (clamp and history shift), v_sub_u32_sdwa (the error from the packed half), the square-accumulate, half a max3 / min3.
+* The builtin without its clamp bit compiles to v_dot2c_i32_i16 with a v_mov of the constant in front of each: 340 VALU for
+  26 steps against the parent's 339 -- nothing gained.  With the bit (it cannot fire while |c0| + |c1| <= 32767): 357 per 28.
+* A dot instruction's result wants three wait states before another VALU reads it: `s_nop 2` behind every v_dot2 (28 in the
+  pass pair, column wait / nop) where the parent had `s_nop 0`.  They cost issue slots of this wave only.
+* The x * 2048 row is gone from LDS (the pass reads x * 2048 + 1024 alone): 8 ds_read_b128 per frame instead of 12.
 """)
 
 

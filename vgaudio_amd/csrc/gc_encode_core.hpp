@@ -25,11 +25,12 @@
 #define VGA_HD inline
 #endif
 
-// 24-bit multiply (operands are 16/17-bit here) and an optimisation barrier that keeps hipcc from
-// re-associating the negated coefficients back into "mad, then subtract" (one extra dependent op).
+// 24-bit multiply (operands are 16/17-bit here) and optimisation barriers: VGA_OPAQUE hides a value's range or origin from
+// hipcc (a 0/1 factor, a shift count it would otherwise fold per use), VGA_OPAQUE_S keeps a constant in a scalar register.
 #if defined(__HIP_DEVICE_COMPILE__)
 #define VGA_MUL24(a, b) __mul24((a), (b))
 #define VGA_OPAQUE(v) asm("" : "+v"(v))
+#define VGA_OPAQUE_S(v) asm("" : "+s"(v))
 // acc + e*e as ONE instruction (hipcc otherwise re-associates the 14 sums into mul, mul, add3)
 static __device__ __forceinline__ uint32_t vga_mad24_acc(int e, uint32_t acc)
 {
@@ -51,6 +52,7 @@ static __device__ __forceinline__ uint32_t vga_square24(int e)
 #define VGA_MAD24_ACC(e, acc) ((acc) + (uint32_t)(e) * (uint32_t)(e))
 #define VGA_MUL24(a, b) ((a) * (b))
 #define VGA_OPAQUE(v) ((void)0)
+#define VGA_OPAQUE_S(v) ((void)0)
 #endif
 
 namespace vga {
@@ -242,21 +244,73 @@ VGA_HD int round_through_f32(int d)
 #endif
 }
 
-// Fast quantise pass: integer-only, 15 VALU ops per sample of which 8 are on the dependent chain
-// (mad, cvt, cvt, add3, ashr, med3, lshl_add, med3) instead of the f32/f64 detour.
-//   d      = in*2048 - (o0*c1 + o1*c0)                       (two mads with negated coefs)
+// ---- packed pairs of 16-bit values (round 7) ------------------------------------------
+// The fast pass keeps the two newest reconstructed samples as ONE register, (older & 0xFFFF) | (newer << 16) -- the form
+// the kernel hands the history on in (PassOut::hist_pair) -- and the coefficients as (c1 & 0xFFFF) | (c0 << 16).  Two
+// operations work on such pairs; the device has an instruction for each, the host build (the lane emulator of the CPU
+// tests) spells out what the instruction does so that both run the same formulation.
+VGA_HD uint32_t pack16(int lo, int hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); }
+VGA_HD int pair_lo(uint32_t v) { return (int)(int16_t)(v & 0xFFFFu); }
+VGA_HD int pair_hi(uint32_t v) { return (int)v >> 16; }
+// a.lo * b.lo + a.hi * b.hi + acc, halves read as int16, the sum saturated to int32: v_dot2_i32_i16 with its clamp bit.
+// The bit is set for the ENCODING's sake, not for the saturation: without it hipcc takes the two-operand v_dot2c_i32_i16, whose
+// accumulator is its destination -- a v_mov of the constant in front of every one (counted in the listing: the instruction
+// the packed pair saves was spent again).  The three-operand form reads the constant from a scalar register.  The sum can
+// reach the rails only when |b.lo| + |b.hi| > 32767 (else |sum| < 2^30 + |acc|); the fast pass calls itself inexact for such
+// coefficients (S3) and the frame is encoded by pass_literal, so no product path sees a saturated sum.  The host build
+// saturates the exact 64-bit sum; whether the hardware clamps per term or once is therefore nobody's business.
+VGA_HD int dot2_i16(uint32_t a, uint32_t b, int acc)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef short s16x2 __attribute__((ext_vector_type(2)));
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b), acc, true);
+#else
+    const int64_t v = (int64_t)pair_lo(a) * pair_lo(b) + (int64_t)pair_hi(a) * pair_hi(b) + (int64_t)acc;
+    return v > 2147483647ll ? 2147483647 : (v < -2147483648ll ? (int)-2147483648ll : (int)v);
+#endif
+}
+// (clamp16(lo) & 0xFFFF) | (clamp16(hi) << 16)  (v_cvt_pk_i16_i32)
+VGA_HD uint32_t sat_pack16(int lo, int hi)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(lo, hi));
+#else
+    return pack16(clamp16i(lo), clamp16i(hi));
+#endif
+}
+
+// Fast quantise pass: integer-only, 12 VALU ops per sample (14 with the f32 rounding) instead of the f32/f64 detour.
+// With H = (o0, o1) the packed history and C = (c1, c0) the packed coefficients:
+//   P      = dot2(H, C, 1024)                                predicted + 1024, one instruction
+//   d      = in2048p - P                                     == in*2048 - predicted
 //   r      = (int)(float)d                                   the reference's float rounding
 //   u      = (r + 2^(k-1) - 1 + (d<0)) >> k                  unclamped nibble  (S2)
 //   q      = clamp(u, -8, 7)
-//   recon  = clamp16(((in*2048 + 1024 - d) >> 11) + (q << (k-11)))  (in*2048 + 1024 - d == predicted + 1024)
+//   w      = (P >> 11) + (q << (k-11))                       the reconstruction before its clamp
+//   H'     = sat_pack(w_prev, w)                             clamp AND history shift: (o1, recon) in one instruction
+//   e      = in - hi(H')                                     the error reads the packed half
+// Why this is the same arithmetic as the reference's (and as the pass in two 32-bit history registers it replaces):
+//  (P1) with |c0| + |c1| <= 32767 the dot product IS o0*c1 + o1*c0 + 1024: its operands are int16, every product is exact
+//       in 32 bits and |sum| <= 32768 * 32767 + 1024 < 2^30 -- nothing wraps in the reference's int arithmetic and nothing
+//       saturates here.  With larger coefficients the reference may wrap where dot2 saturates: the pass reports
+//       exact == false for them (as it always did: S3 needs the same bound) and pass_literal encodes the frame.  No
+//       coefficient is negated, so c = -32768 needs no 17th bit.
+//  (P2) d: in2048p = in*2048 + 1024, the 1024 in P cancels (mod 2^32).
+//  (P3) the reference reconstructs ((predicted + q * 2^k) + 1024) >> 11; q * 2^k is a multiple of 2^11 (k >= 11), so it passes
+//       through the floor: (P + q * 2^k) >> 11 = (P >> 11) + (q << (k - 11)).  |P >> 11| <= 2^20 and |q << (k-11)| <= 2^15: no
+//       overflow in w.
+//  (P4) sat_pack saturates each input to [-32768, 32767]: that is clamp16i, so hi(H') is the reference's clamped sample.
+//  (P5) the low half is w_prev saturated AGAIN, from the unclamped value of the step before: clamp16i of the same number, i.e.
+//       the previous step's hi(H) -- the history shift o0 = o1 at no cost.  (Step 0: w_prev = x[1], a 16-bit value.)
+//  (P6) S2, S3 and the `exact` test below are untouched: they speak about d, u and e, which are the same numbers.
 // The nibbles leave the pass unpacked (r.q): the kernel's helper wave packs the winner's frame (pack_frame).
 // The overflow is recovered from the running max/min of u (one max3/min3 per two samples).
 // r.exact == false (frame must be redone with pass_literal) when the 32-bit sum of squared
 // errors could overflow (S3): with |c0|+|c1| <= 32767 the predictor cannot wrap, and then
 // |in - recon| <= (ov + 1/2) * 2^(k-11) + 2 where ov is the pass's max overflow; we require that
 // bound to stay <= 17 500 (14 * 17500^2 < 2^32), which also rules out int32 overflow in u.
-// in2048v[s] = x[s + 2] * 2048 and in2048p[s] = x[s + 2] * 2048 + 1024 are supplied by the caller (the
-// kernel's helper wave precomputes them per tile).
+// in2048p[s] = x[s + 2] * 2048 + 1024 is supplied by the caller (the kernel's helper wave precomputes it per tile), hist
+// is the packed history (x[0], x[1]).
 // WIDE_TOTAL: the error sum in 64 bits (a multiply and an add with carry per sample instead of one mad) -- exact whatever
 // the overflow as long as the predictor cannot wrap (|c0| + |c1| <= 32767: then |d| < 2^30 + 2^26, u cannot leave int32, and
 // |in - recon| <= 65535 squares into 32 bits).  For the one case the 32-bit sum cannot serve: a pass at the cap (scale 12 ends
@@ -268,29 +322,28 @@ VGA_HD int round_through_f32(int d)
 // for nibble -- and one that does not must be run again with the conversions.  The kernel takes this form for a frame when
 // every lane of the wave quantises at scale 9 or below (70 % of the synthetic set's wave-frames).
 template <bool WIDE_TOTAL, bool NO_ROUND = false>
-VGA_HD PassOut pass_fast_core_t(const int (&x)[16], const int (&in2048v)[14], const int (&in2048p)[14], int c0, int c1,
-                                int scale_power)
+VGA_HD PassOut pass_fast_core_t(const int (&x)[16], uint32_t hist, const int (&in2048p)[14], int c0, int c1, int scale_power)
 {
     PassOut r;
     uint64_t total64 = 0;
     const int k = scale_power + 11;
     const int km11 = scale_power;
     int bias = (1 << (k - 1)) - 1;
-    int nc0 = -c0, nc1 = -c1;
     VGA_OPAQUE(bias);
-    VGA_OPAQUE(nc0);
-    VGA_OPAQUE(nc1);
+    const uint32_t cpair = pack16(c1, c0);
+    int k1024 = 1024;
+    VGA_OPAQUE_S(k1024);
     uint32_t total = 0;
     int umax = 0, umin = 0;
     int u_prev = 0;
-    int o0 = x[0], o1 = x[1];
+    uint32_t h = hist;                                              // (o0, o1)
+    int w_prev = pair_hi(hist);
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
     for (int s = 0; s < 14; s++) {
-        int base = VGA_MUL24(o0, nc1) + in2048v[s];                 // off the dependent chain (o0 is one step old)
-        VGA_OPAQUE(base);
-        const int d = VGA_MUL24(o1, nc0) + base;                    // == in2048 - predicted (mod 2^32)
+        const int P = dot2_i16(h, cpair, k1024);                    // predicted + 1024
+        const int d = (int)((uint32_t)in2048p[s] - (uint32_t)P);    // == in2048 - predicted
         const int rd = NO_ROUND ? d : round_through_f32(d);
         const int u = (int)((uint32_t)rd + (uint32_t)bias + ((uint32_t)d >> 31)) >> k;
         const int q = imin(imax(u, -8), 7);
@@ -300,61 +353,70 @@ VGA_HD PassOut pass_fast_core_t(const int (&x)[16], const int (&in2048v)[14], co
         }
         u_prev = u;
         r.q[s] = q;
-        // (predicted + 1024 + q * 2^k) >> 11 with the shift taken off the dependent chain: q * 2^k is a
-        // multiple of 2^11 (k >= 11), so it passes through the floor
-        const int pr11 = (int)((uint32_t)in2048p[s] - (uint32_t)d) >> 11;
-        const int recon = clamp16i(pr11 + (int)((uint32_t)q << km11));
-        const int e = x[s + 2] - recon;
+        const int w = (P >> 11) + (int)((uint32_t)q << km11);       // off the chain: P >> 11 waits for q
+        h = sat_pack16(w_prev, w);                                  // (o1, recon)
+        w_prev = w;
+        const int e = x[s + 2] - pair_hi(h);
 #if defined(__HIP_DEVICE_COMPILE__)
         if (WIDE_TOTAL) total64 += (uint64_t)vga_square24(e);           // |e| <= 65535: the product's low 32 bits are the square
 #else
         if (WIDE_TOTAL) total64 += (uint64_t)((int64_t)e * (int64_t)e);
 #endif
         else total = VGA_MAD24_ACC(e, total);                       // total += e * e, one v_mad_i32_i24
-        o0 = o1;
-        o1 = recon;
     }
-    r.hist_pair = (unsigned)(o0 & 0xFFFF) | ((unsigned)o1 << 16);
+    r.hist_pair = h;                                                // falls out of the last step
     const int ov = imax(imax(umax - 7, -8 - umin), 0);
     const int ac0 = c0 < 0 ? -c0 : c0, ac1 = c1 < 0 ? -c1 : c1;
     r.exact = ac0 + ac1 <= 32767 && (WIDE_TOTAL || (ov <= 17497 && (((2 * ov + 1) << (k - 11)) <= 34996)));
     r.total = WIDE_TOTAL ? total64 : (uint64_t)total;
     r.max_overflow = ov;
-    r.o12 = o0; r.o13 = o1;
+    r.o12 = pair_lo(h); r.o13 = pair_hi(h);
     return r;
 }
-VGA_HD PassOut pass_fast_core(const int (&x)[16], const int (&in2048v)[14], const int (&in2048p)[14], int c0, int c1,
-                              int scale_power)
+VGA_HD PassOut pass_fast_core(const int (&x)[16], uint32_t hist, const int (&in2048p)[14], int c0, int c1, int scale_power)
 {
-    return pass_fast_core_t<false>(x, in2048v, in2048p, c0, c1, scale_power);
+    return pass_fast_core_t<false>(x, hist, in2048p, c0, c1, scale_power);
 }
-VGA_HD PassOut pass_fast_core_no_round(const int (&x)[16], const int (&in2048v)[14], const int (&in2048p)[14], int c0, int c1,
+VGA_HD PassOut pass_fast_core_no_round(const int (&x)[16], uint32_t hist, const int (&in2048p)[14], int c0, int c1,
                                        int scale_power)
 {
-    return pass_fast_core_t<false, true>(x, in2048v, in2048p, c0, c1, scale_power);
+    return pass_fast_core_t<false, true>(x, hist, in2048p, c0, c1, scale_power);
 }
 // the bound under which a NO_ROUND pass is the exact pass (scale_power <= 12: the bound is positive up to scale 9)
 VGA_HD bool pass_no_round_is_exact(int scale_power, int max_overflow)
 {
     return scale_power <= 9 && max_overflow < (1 << (13 - scale_power)) - 8;
 }
-VGA_HD PassOut pass_fast_core_wide(const int (&x)[16], const int (&in2048v)[14], const int (&in2048p)[14], int c0, int c1,
+VGA_HD PassOut pass_fast_core_wide(const int (&x)[16], uint32_t hist, const int (&in2048p)[14], int c0, int c1,
                                    int scale_power)
 {
-    return pass_fast_core_t<true>(x, in2048v, in2048p, c0, c1, scale_power);
+    return pass_fast_core_t<true>(x, hist, in2048p, c0, c1, scale_power);
+}
+// The same three with the history taken from x[0], x[1] and with the row of x * 2048 the pass read until round 7 (callers
+// that still build one -- the lane emulator -- keep compiling; the pass does not look at it).
+VGA_HD PassOut pass_fast_core(const int (&x)[16], const int (&)[14], const int (&in2048p)[14], int c0, int c1, int scale_power)
+{
+    return pass_fast_core_t<false>(x, pack16(x[0], x[1]), in2048p, c0, c1, scale_power);
+}
+VGA_HD PassOut pass_fast_core_no_round(const int (&x)[16], const int (&)[14], const int (&in2048p)[14], int c0, int c1,
+                                       int scale_power)
+{
+    return pass_fast_core_t<false, true>(x, pack16(x[0], x[1]), in2048p, c0, c1, scale_power);
+}
+VGA_HD PassOut pass_fast_core_wide(const int (&x)[16], const int (&)[14], const int (&in2048p)[14], int c0, int c1,
+                                   int scale_power)
+{
+    return pass_fast_core_t<true>(x, pack16(x[0], x[1]), in2048p, c0, c1, scale_power);
 }
 
 VGA_HD PassOut pass_fast(const int (&x)[16], int c0, int c1, int scale_power)
 {
-    int in2048v[14], in2048p[14];
+    int in2048p[14];
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-    for (int s = 0; s < 14; s++) {
-        in2048v[s] = x[s + 2] * 2048;
-        in2048p[s] = in2048v[s] + 1024;
-    }
-    return pass_fast_core(x, in2048v, in2048p, c0, c1, scale_power);
+    for (int s = 0; s < 14; s++) in2048p[s] = x[s + 2] * 2048 + 1024;
+    return pass_fast_core(x, pack16(x[0], x[1]), in2048p, c0, c1, scale_power);
 }
 
 // ---- speculative two-candidate resolution --------------------------------------------
@@ -393,16 +455,16 @@ VGA_HD Resolve resolve_candidates_nobump(int s1, int ov_a, int ov_b)
     return z;
 }
 
-// Continue the reference's do-loop from `scale_power` (value before the ++), precomputed in*2048 arrays.
-VGA_HD PassOut resume_passes_core(const int (&x)[16], const int (&in2048v)[14], const int (&in2048p)[14], int c0,
-                                  int c1, int scale_power, int &final_sp)
+// Continue the reference's do-loop from `scale_power` (value before the ++), precomputed in*2048 + 1024 array.
+VGA_HD PassOut resume_passes_core(const int (&x)[16], const int (&in2048p)[14], int c0, int c1, int scale_power,
+                                  int &final_sp)
 {
     PassOut r;
     bool at_max;
     do {
         scale_power++;
         at_max = scale_power >= 12;
-        r = pass_fast_core(x, in2048v, in2048p, c0, c1, scale_power);
+        r = pass_fast_core(x, pack16(x[0], x[1]), in2048p, c0, c1, scale_power);
         if (!r.exact) r = pass_literal(x, c0, c1, scale_power);
         scale_power = apply_bumps(scale_power, r.max_overflow);
     } while (scale_power < 12 && r.max_overflow > 1 && !at_max);

@@ -15,8 +15,8 @@
 //    at scale s1 and candidate B at s1+1 IN PARALLEL LANES; two compares on the exchanged
 //    overflow values decide which one the reference ends on.  Third trips, overflow bumps
 //    and everything else that is rare sit behind ONE wave-uniform branch per frame.
-//  * The quantise pass is integer-only (16 VALU ops per sample, 8 on the dependent chain,
-//    instead of the float/double detour); exactness conditions in gc_encode_core.hpp S2/S3.
+//  * The quantise pass is integer-only on a packed pair of 16-bit history values (12 VALU ops per sample
+//    instead of the float/double detour); exactness conditions in gc_encode_core.hpp S2/S3, P1-P6.
 //  * 8-predictor argmin + winner-history broadcast: v_min_u32 / v_or_b32 with DPP operands
 //    (quad_perm, row_half_mirror, row_mirror) -- 8 VALU ops, no LDS.
 #include "common.hpp"
@@ -60,7 +60,7 @@ __device__ __forceinline__ unsigned row16_reduce(unsigned v, Op op)
 // Everything that does not depend on the reconstructed history is taken off the serial wave:
 //   helper wave (wave 1), one 16-frame tile AHEAD of the encoder:
 //     * coalesced global loads of the tile (lane = frame j of channel g: 28 contiguous bytes),
-//     * unpack to int32, x*2048, and for each of the 8 predictors the max/min pre-scan distance over the
+//     * unpack to int32, x*2048 + 1024, and for each of the 8 predictors the max/min pre-scan distance over the
 //       twelve samples s = 2..13 that involve input samples only (GcAdpcmEncoder.cs:107-115),
 //     * all of it into LDS (double-buffered), plus the coalesced flush of the previous tile's frames
 //       (the zero-padded partial last frame travels through the same path);
@@ -129,8 +129,7 @@ struct Lay {
 template <int CS, int TF>
 struct GcTileT {
     int x[CS][TF][16];         // [channel slot][frame][sample]  (14 used)
-    int in2048[CS][TF][16];    // x * 2048
-    int in2048p[CS][TF][16];   // x * 2048 + 1024
+    int in2048p[CS][TF][16];   // x * 2048 + 1024  (the pass needs no x * 2048 beside it since round 7: gc_encode_core.hpp P2)
     uint32_t pre[CS][TF][8];   // per predictor: clamp16(max d) & 0xFFFF | clamp16(min d) << 16, over s = 2..13
 };
 typedef short short2v __attribute__((ext_vector_type(2)));
@@ -157,7 +156,8 @@ VGA_COLD int prescan_sequential_cold(X16 xs, int c0, int c1)
 // path (a build with the block compiled in but never run: 172 ms vs 140 ms without it), which is why the
 // frame's tail is instantiated once per branch below instead of merging the two branches' results.
 struct ColdState {
-    int x[16], m[14], mp[14];
+    int x[16], mp[14];
+    uint32_t hist;             // (x[0], x[1]) packed
     int c0, c1, s1;
     // what this lane needs (any of them in any lane sends the wave here):
     //   generic: the reference's loop as written from `start` (the scalePower its loop continues from): the bump loop
@@ -176,11 +176,11 @@ struct ColdOut { PassOut r; int final_sp; int fin; };
 __device__ __forceinline__
 ColdOut encode_frame_cold(ColdState st, PassOut r, int final_sp, int fin)
 {
-    int x[16], m[14], mp[14];
+    int x[16], mp[14];
 #pragma unroll
     for (int i = 0; i < 16; i++) x[i] = st.x[i];
 #pragma unroll
-    for (int i = 0; i < 14; i++) { m[i] = st.m[i]; mp[i] = st.mp[i]; }
+    for (int i = 0; i < 14; i++) mp[i] = st.mp[i];
     if (st.drop) fin = 0;
     if (__any((st.generic | st.wide) != 0)) {      // (one test in front of both: the common visitor is a third trip)
     if (__any(st.generic != 0)) {                  // hostile input, and tones the first scale misjudges by 2^5 and more
@@ -202,7 +202,7 @@ ColdOut encode_frame_cold(ColdState st, PassOut r, int final_sp, int fin)
     // itself is right (gc_encode_core.hpp S2 holds for every int32 distance); only its 32-bit error sum may have wrapped.
     if (__any(st.wide != 0)) {
         if (st.wide) {
-            const PassOut w = pass_fast_core_wide(x, m, mp, st.c0, st.c1, final_sp);
+            const PassOut w = pass_fast_core_wide(x, st.hist, mp, st.c0, st.c1, final_sp);
             r.total = w.total;
             fin = 1;
         }
@@ -220,10 +220,10 @@ ColdOut encode_frame_cold(ColdState st, PassOut r, int final_sp, int fin)
                 bool short_pass = !__any(sp > 9);  // (over the lanes still in this loop) without the f32 detour, as the first two passes
 #endif
                 if (short_pass) {
-                    r = pass_fast_core_no_round(x, m, mp, st.c0, st.c1, sp);
+                    r = pass_fast_core_no_round(x, st.hist, mp, st.c0, st.c1, sp);
                     short_pass = !__any(!pass_no_round_is_exact(sp, r.max_overflow));
                 }
-                if (!short_pass) r = pass_fast_core(x, m, mp, st.c0, st.c1, sp);
+                if (!short_pass) r = pass_fast_core(x, st.hist, mp, st.c0, st.c1, sp);
                 const bool cap = sp >= 12;
                 if ((unsigned)r.max_overflow > (cap ? 3u : 248u)) {      // bump loop / inexact sum: generic
                     int xg[16];                                          // (opaque: see above)
@@ -352,15 +352,10 @@ __device__ __forceinline__ void gc_encode_piece(
             }
             GcTile &T = s_tile[tile & 1];
             int4 *xr = reinterpret_cast<int4 *>(&T.x[grp][hfr][0]);
-            int4 *mr = reinterpret_cast<int4 *>(&T.in2048[grp][hfr][0]);
             xr[0] = make_int4(in[0], in[1], in[2], in[3]);
             xr[1] = make_int4(in[4], in[5], in[6], in[7]);
             xr[2] = make_int4(in[8], in[9], in[10], in[11]);
             xr[3] = make_int4(in[12], in[13], 0, 0);
-            mr[0] = make_int4(in[0] * 2048, in[1] * 2048, in[2] * 2048, in[3] * 2048);
-            mr[1] = make_int4(in[4] * 2048, in[5] * 2048, in[6] * 2048, in[7] * 2048);
-            mr[2] = make_int4(in[8] * 2048, in[9] * 2048, in[10] * 2048, in[11] * 2048);
-            mr[3] = make_int4(in[12] * 2048, in[13] * 2048, 0, 0);
             int4 *qr = reinterpret_cast<int4 *>(&T.in2048p[grp][hfr][0]);
             qr[0] = make_int4(in[0] * 2048 + 1024, in[1] * 2048 + 1024, in[2] * 2048 + 1024, in[3] * 2048 + 1024);
             qr[1] = make_int4(in[4] * 2048 + 1024, in[5] * 2048 + 1024, in[6] * 2048 + 1024, in[7] * 2048 + 1024);
@@ -443,21 +438,18 @@ __device__ __forceinline__ void gc_encode_piece(
     }
     VGA_OPAQUE(h0);
     VGA_OPAQUE(h1);
+    uint32_t hpk = pack16(h0, h1);                     // the same history as the pass takes it: (h0, h1) in one register
 
     if (lane == 0) s_ncold[wave] = 0;                  // cold blocks this piece (diagnostics, g_vga_gc_stats)
-    struct Row { int x[16]; int m[14]; int mp[14]; uint32_t pre; };
+    struct Row { int x[16]; int mp[14]; uint32_t pre; };
     auto read_row = [&](const GcTile &T, int j, Row &R) {
         const int4 *xr = reinterpret_cast<const int4 *>(&T.x[grp][j][0]);
-        const int4 *mr = reinterpret_cast<const int4 *>(&T.in2048[grp][j][0]);
         const int4 a0 = xr[0], a1 = xr[1], a2 = xr[2], a3 = xr[3];
-        const int4 b0 = mr[0], b1 = mr[1], b2 = mr[2], b3 = mr[3];
         // keep the padding lanes "used": hipcc otherwise splits the 16-byte row reads into 7 odd-sized ones
-        asm volatile("" ::"v"(a3.z), "v"(a3.w), "v"(b3.z), "v"(b3.w));
-        int *x = R.x, *m = R.m;
+        asm volatile("" ::"v"(a3.z), "v"(a3.w));
+        int *x = R.x;
         x[2] = a0.x; x[3] = a0.y; x[4] = a0.z; x[5] = a0.w; x[6] = a1.x; x[7] = a1.y; x[8] = a1.z; x[9] = a1.w;
         x[10] = a2.x; x[11] = a2.y; x[12] = a2.z; x[13] = a2.w; x[14] = a3.x; x[15] = a3.y;
-        m[0] = b0.x; m[1] = b0.y; m[2] = b0.z; m[3] = b0.w; m[4] = b1.x; m[5] = b1.y; m[6] = b1.z; m[7] = b1.w;
-        m[8] = b2.x; m[9] = b2.y; m[10] = b2.z; m[11] = b2.w; m[12] = b3.x; m[13] = b3.y;
         const int4 *qr = reinterpret_cast<const int4 *>(&T.in2048p[grp][j][0]);
         const int4 e0 = qr[0], e1 = qr[1], e2 = qr[2], e3 = qr[3];
         asm volatile("" ::"v"(e3.z), "v"(e3.w));
@@ -493,7 +485,7 @@ __device__ __forceinline__ void gc_encode_piece(
         int final_sp = imin(s1 + (cand_b ? 1 : 0), 12);
         const bool at_cap = final_sp >= 12;            // the loop never goes past 12: this pass ends it
         const unsigned ov_limit = at_cap ? 3u : 248u;  // see `rare` below
-        PassOut r = pass_fast_core(x, R.m, R.mp, c0, c1, final_sp);
+        PassOut r = pass_fast_core(x, hpk, R.mp, c0, c1, final_sp);
         // Straight-line resolution, valid when no lane is `rare`:
         //   * no overflow can start the bump loop (:166-168 needs max_overflow + 8 > 256),
         //   * the 32-bit error sum of every lane that can become final is exact (gc_encode_core.hpp S3:
@@ -557,6 +549,7 @@ __device__ __forceinline__ void gc_encode_piece(
             if (!RAGGED || upd) {
                 h0 = (int)(int16_t)(pay & 0xFFFF);   // pcmBuffer[0] = pcmBuffer[14] (:40)
                 h1 = (int)pay >> 16;                 // pcmBuffer[1] = pcmBuffer[15] (:41)
+                hpk = pay;
             }
             VGA_OPAQUE(h0);                      // hide the 16-bit range: keeps the 24-bit multiplies the next frame
             VGA_OPAQUE(h1);                      // asks for (the compiler otherwise widens them to 64-bit mads)
@@ -572,7 +565,8 @@ __device__ __forceinline__ void gc_encode_piece(
 #pragma unroll
             for (int i = 0; i < 16; i++) st.x[i] = x[i];
 #pragma unroll
-            for (int i = 0; i < 14; i++) { st.m[i] = R.m[i]; st.mp[i] = R.mp[i]; }
+            for (int i = 0; i < 14; i++) st.mp[i] = R.mp[i];
+            st.hist = hpk;
             st.c0 = c0; st.c1 = c1; st.s1 = s1;
             const bool redo = __any(rare);             // (this layout: every pair's A lane walks the whole loop again, B lanes are out)
             st.generic = redo && !cand_b; st.start = s1 - 1; st.drop = redo && cand_b;
@@ -616,15 +610,15 @@ __device__ __forceinline__ void gc_encode_piece(
         bool short_passes = !__any(sp_b > 9);
 #endif
         if (short_passes) {
-            rb = pass_fast_core_no_round(x, R.m, R.mp, c0, c1, sp_b);
-            ra = pass_fast_core_no_round(x, R.m, R.mp, c0, c1, sp_a);
+            rb = pass_fast_core_no_round(x, hpk, R.mp, c0, c1, sp_b);
+            ra = pass_fast_core_no_round(x, hpk, R.mp, c0, c1, sp_a);
             // (hostile coefficients: the lane walks the reference's loop as written whatever these passes say)
             const bool trusted = !coef_ok || (pass_no_round_is_exact(sp_a, ra.max_overflow) && pass_no_round_is_exact(sp_b, rb.max_overflow));
             short_passes = !__any(!trusted);
         }
         if (!short_passes) {
-            rb = pass_fast_core(x, R.m, R.mp, c0, c1, sp_b);
-            ra = pass_fast_core(x, R.m, R.mp, c0, c1, sp_a);
+            rb = pass_fast_core(x, hpk, R.mp, c0, c1, sp_b);
+            ra = pass_fast_core(x, hpk, R.mp, c0, c1, sp_a);
         }
         const bool cap_a = sp_a >= 12, cap_b = sp_b >= 12;         // a pass at the cap ends the loop whatever it overflowed
         const int eff_a = cap_a ? 0 : ra.max_overflow, eff_b = cap_b ? 0 : rb.max_overflow;
@@ -700,6 +694,7 @@ __device__ __forceinline__ void gc_encode_piece(
             if (!RAGGED || upd) {                // (a slot past its last frame keeps the history it ended on)
                 h0 = (int)(int16_t)(pay & 0xFFFF);
                 h1 = (int)pay >> 16;
+                hpk = pay;
             }
             VGA_OPAQUE(h0);
             VGA_OPAQUE(h1);
@@ -714,7 +709,8 @@ __device__ __forceinline__ void gc_encode_piece(
 #pragma unroll
             for (int i = 0; i < 16; i++) st.x[i] = x[i];
 #pragma unroll
-            for (int i = 0; i < 14; i++) { st.m[i] = R.m[i]; st.mp[i] = R.mp[i]; }
+            for (int i = 0; i < 14; i++) st.mp[i] = R.mp[i];
+            st.hist = hpk;
             st.c0 = c0; st.c1 = c1; st.s1 = s1;
             st.generic = generic; st.drop = 0; st.wide = inexact; st.resume = resume;
             // where the reference's loop stands (the value of scalePower before its next ++): at its start for hostile
@@ -849,19 +845,17 @@ __device__ __forceinline__ void seam_run(const int16_t *__restrict__ src, uint8_
         const bool act = open && in_range;
         frames_run += act ? 1 : 0;
         fetch(f + 1, wn, oldn);                         // in flight during this frame
-        int x[16], m[14], mp[14];
+        int x[16], mp[14];
         x[0] = h0;
         x[1] = h1;
+        const uint32_t hpk = pack16(h0, h1);
 #pragma unroll
         for (int i = 0; i < 7; i++) {
             x[2 + 2 * i] = (int)(int16_t)(w[i] & 0xFFFF);
             x[3 + 2 * i] = (int)w[i] >> 16;
         }
 #pragma unroll
-        for (int i = 0; i < 14; i++) {
-            m[i] = x[2 + i] * 2048;
-            mp[i] = m[i] + 1024;
-        }
+        for (int i = 0; i < 14; i++) mp[i] = x[2 + i] * 2048 + 1024;
         // the guessed run's reconstruction of this frame (GcAdpcmDecoder.cs:25-45), from its bytes before they change
         {
             const int ps = (int)(old.x & 0xFFu);
@@ -893,8 +887,8 @@ __device__ __forceinline__ void seam_run(const int16_t *__restrict__ src, uint8_
         bool fin = true;                               // LPC = 16: this lane's pass is the one the reference ends on
         if (LPC == 8) {
         // (the passes as they always were: without the f32 detour -- tried in round 5 -- a seam run is no faster, LABNOTES 9.7)
-        const PassOut rb = pass_fast_core(x, m, mp, c0, c1, sp_b);
-        const PassOut ra = pass_fast_core(x, m, mp, c0, c1, sp_a);
+        const PassOut rb = pass_fast_core(x, hpk, mp, c0, c1, sp_b);
+        const PassOut ra = pass_fast_core(x, hpk, mp, c0, c1, sp_a);
         const bool cap_a = sp_a >= 12, cap_b = sp_b >= 12;
         const bool rare = !coef_ok || (unsigned)ra.max_overflow > (cap_a ? 3u : 248u) || (unsigned)rb.max_overflow > (cap_b ? 3u : 248u);
         const int eff_a = cap_a ? 0 : ra.max_overflow, eff_b = cap_b ? 0 : rb.max_overflow;
@@ -919,7 +913,7 @@ __device__ __forceinline__ void seam_run(const int16_t *__restrict__ src, uint8_
             // them the reference's loop ends on (encode_frame, CPW = 4); anything else -- both overflowed, a bump, an inexact
             // sum, hostile coefficients -- and the A lane walks the reference's loop as written, the B lane is out
             final_sp = cand_b ? sp_b : sp_a;
-            r = pass_fast_core(x, m, mp, c0, c1, final_sp);
+            r = pass_fast_core(x, hpk, mp, c0, c1, final_sp);
             const bool cap = final_sp >= 12;
             const bool rare_mine = !coef_ok || (unsigned)r.max_overflow > (cap ? 3u : 248u);
             const int eff = cap ? 0 : r.max_overflow;
@@ -985,16 +979,14 @@ __device__ __forceinline__ void encode_tail_frame(const int16_t *__restrict__ sr
                                                   bool coef_ok, int pr, int total_samples, int h0, int h1, bool act)
 {
     const int full_frames = total_samples / 14, tail = total_samples - full_frames * 14;
-    int x[16], m[14], mp[14];
+    int x[16], mp[14];
     x[0] = h0;
     x[1] = h1;
+    const uint32_t hpk = pack16(h0, h1);
 #pragma unroll
     for (int i = 0; i < 14; i++) x[2 + i] = i < tail ? (int)src[(int64_t)full_frames * 14 + i] : 0;
 #pragma unroll
-    for (int i = 0; i < 14; i++) {
-        m[i] = x[2 + i] * 2048;
-        mp[i] = m[i] + 1024;
-    }
+    for (int i = 0; i < 14; i++) mp[i] = x[2 + i] * 2048 + 1024;
     int s1;
     {
         int dmax = 0, dmin = 0;
@@ -1003,8 +995,8 @@ __device__ __forceinline__ void encode_tail_frame(const int16_t *__restrict__ sr
         if (s1 == -100) s1 = first_scale_power_from_md(prescan_sequential(x, c0, c1));
     }
     const int sp_a = imin(s1, 12), sp_b = imin(s1 + 1, 12);
-    const PassOut rb = pass_fast_core(x, m, mp, c0, c1, sp_b);
-    const PassOut ra = pass_fast_core(x, m, mp, c0, c1, sp_a);
+    const PassOut rb = pass_fast_core(x, hpk, mp, c0, c1, sp_b);
+    const PassOut ra = pass_fast_core(x, hpk, mp, c0, c1, sp_a);
     const bool cap_a = sp_a >= 12, cap_b = sp_b >= 12;
     const bool rare = !coef_ok || (unsigned)ra.max_overflow > (cap_a ? 3u : 248u) || (unsigned)rb.max_overflow > (cap_b ? 3u : 248u);
     const int eff_a = cap_a ? 0 : ra.max_overflow, eff_b = cap_b ? 0 : rb.max_overflow;
