@@ -2,13 +2,13 @@
 """Per-frame instruction budget of gc_encode_persistent_kernel<8, false> from hipcc's ISA listing: where do
 the ~409 lane-operations per input sample go against the ~240 the two passes x 8 predictors need?
 
-The frame loop's basic blocks are found from the listing itself: the fourteen `v_mad_i32_i24 v, e, e, acc` of a quantise pass
-(gc_encode_core.hpp: total += e * e) mark the passes; the blocks between the loop's labels are classified by what they hold.
+The frame loop's basic blocks are found from the listing itself: the seven `v_dot2_i32_i16 v, E, E, acc clamp` of a quantise pass
+(gc_encode_core.hpp E3: total += e0 * e0 + e1 * e1, once per two sample steps since round 8) mark the passes; the blocks between the loop's labels are classified by what they hold.
 Prints static instruction counts per block of the HOT path of one frame (lane = (channel, predictor), CPW = 8: one wave-frame
 = 8 channel-frames = 112 samples), the cold block's path for a plain third trip, the helper wave's loop per tile, and the
 resulting lane-operations per sample with the measured rates (cold-block rate, short-pass share) filled in.
 
-    python tools/isa_budget_gc.py > profiles/r07_gc_encode_isa_budget.md
+    python tools/isa_budget_gc.py > profiles/r08_gc_encode_isa_budget.md
 """
 import collections
 import os
@@ -68,11 +68,15 @@ def count(block):
 
 def main():
     L = kernel(listing(), "gc_encode_persistent_kernelILi8ELb0E")
-    sq = [i for i, l in enumerate(L) if re.search(r"v_mad_i32_i24 v\d+, (v\d+), \1, v\d+", l)]
-    assert len(sq) >= 56, "the listing does not look like the encoder's"
-    # first frame of the loop body (row set A): passes 0..55 = short pair (28) + normal pair (28)
-    short_a, short_b = sq[0], sq[27]
-    normal_a, normal_b = sq[28], sq[55]
+    sq = [i for i, l in enumerate(L) if re.search(r"v_dot2_i32_i16 v\d+, (v\d+), \1, (?:v\d+|0) clamp", l)]
+    assert len(sq) >= 28, "the listing does not look like the encoder's"
+    # first frame of the loop body (row set A): squares 0..27 = short pair (2 x 7) + normal pair (2 x 7)
+    # (hipcc sinks the short pair's squares behind the passes, into a block of their own: the passes' extent is taken from
+    # the fourteen v_cvt_pk_i16_i32 of each -- clamp and history shift, on the chain -- and stretched over the squares)
+    cv = [i for i, l in enumerate(L) if l.startswith("v_cvt_pk_i16_i32") and i > sq[0] - 700]
+    assert len(cv) >= 56, "the listing does not look like the encoder's"
+    short_a, short_b = min(cv[0], sq[0]), max(cv[27], sq[13])
+    normal_a, normal_b = min(cv[28], sq[14]), max(cv[55], sq[27])
     labels = [i for i, l in enumerate(L) if l.endswith(":")]
     prev_label = lambda i: max(j for j in labels if j <= i)
     next_label = lambda i: min(j for j in labels if j > i)
@@ -97,11 +101,11 @@ def main():
         pre.append(t)
         if t.startswith("s_cbranch_execz"):
             skip_to = t.split()[1]
-    rows = [("row reads (8 x ds_read_b128) + pre-scan of the two history-dependent distances + first scale", count(pre)),
+    rows = [("row reads (6 x ds_read_b128) + pre-scan of the two history-dependent distances + first scale", count(pre)),
             ("passes B (s1 + 1) and A (s1) without the f32 detour, 28 sample steps", count(L[short_blk[0]:short_blk[1]])),
             ("the same with the conversions (30 % of the wave-frames take these instead)", count(L[normal_blk[0]:normal_blk[1]])),
             ("select the pass the reference ends on, 8-predictor argmin (DPP), winner's history, 4 x ds_write_b128", count(L[normal_blk[1]:tail_end + 1]))]
-    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 7)\n")
+    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 8)\n")
     print("`gc_encode_persistent_kernel<8, false>`, static counts from hipcc's gfx950 listing of `vgaudio_amd/csrc/gc_encode_kernel.hip`")
     print("(`tools/isa_budget_gc.py`).  One wave-frame = 64 lanes = 8 channels x 8 predictors = 112 input samples.\n")
     print("| block of the hot frame | total | VALU | SALU | LDS | wait / nop |")
@@ -110,7 +114,7 @@ def main():
         print("| %s | %d | %d | %d | %d | %d |" % (name, c["total"], c["VALU"], c["SALU"], c["LDS"], c["wait/nop"]))
     hot_valu = rows[0][1]["VALU"] + SHORT_SHARE * rows[1][1]["VALU"] + (1 - SHORT_SHARE) * rows[2][1]["VALU"] + rows[3][1]["VALU"]
     # the cold block: the third pass (short form) is the next cluster of 14 squares behind the hot tail that is a single pass
-    third = [c for c in cluster(sq) if len(c) == 14]
+    third = [c for c in cluster(cv) if len(c) == 14]
     third_pass = count(L[prev_label(third[1][0]):next_label(third[1][-1])]) if len(third) > 1 else count([])
     print("\nCold block (third and later trips; %.3f of the wave-frames on the synthetic set): the third pass alone is %d VALU "
           "instructions for ~1.25 lanes of work; with its entry, loop and the frame's tail repeated behind it a plain visit executes "
@@ -126,25 +130,22 @@ def main():
                     ("cold block, %.3f x (third pass + ~45)" % COLD_RATE, COLD_RATE * (third_pass["VALU"] + 45)),
                     ("encoder wave, sum", per_frame)):
         print("| %s | %.0f | %.0f |" % (name, v, v * 64 / 112))
-    print("\nMeasured (profiles/r07_sq_counters_change.json): 70.37 G VALU wave-instructions per launch / 105.3 M "
-          "wave-frames = 668 per wave-frame = 382 lane-ops per sample (parent, same session: 74.69 G = 709).  The difference to the encoder wave's sum is the HELPER wave "
-          "(one per two encoder waves: per tile of 4 frames x 16 channels it unpacks the frames, computes 96 pre-scan distances per "
-          "frame with v_dot2 -- 576 of its ~950 instructions --, packs and stores the previous tile's winners) and the seams "
-          "(0.3 % of the frames re-encoded).")
-    print("""
-## What the budget says (round 7)
+    print(TEXT)
 
-* Round 6's table is `profiles/r06_gc_encode_isa_budget.md` (same tool, same options): passes 384 / 425 VALU, per wave-frame
-  396 + 77 + 45 + 92 = 610.  The pass body was 13.7 VALU per sample step and predictor with the history in two sign-extended
-  registers; on a packed pair (gc_encode_core.hpp P1-P6) it is 12.75 without the f32 rounding: v_dot2_i32_i16 (three-operand,
-  the 1024 from a scalar register), the distance, sign bit, add3, shift, nibble clamp, P >> 11, lshl_add, v_cvt_pk_i16_i32
-  (clamp and history shift), v_sub_u32_sdwa (the error from the packed half), the square-accumulate, half a max3 / min3.
-* The builtin without its clamp bit compiles to v_dot2c_i32_i16 with a v_mov of the constant in front of each: 340 VALU for
-  26 steps against the parent's 339 -- nothing gained.  With the bit (it cannot fire while |c0| + |c1| <= 32767): 357 per 28.
-* A dot instruction's result wants three wait states before another VALU reads it: `s_nop 2` behind every v_dot2 (28 in the
-  pass pair, column wait / nop) where the parent had `s_nop 0`.  They cost issue slots of this wave only.
-* The x * 2048 row is gone from LDS (the pass reads x * 2048 + 1024 alone): 8 ds_read_b128 per frame instead of 12.
-""")
+
+TEXT = """
+## What the budget says (round 8)
+
+* Round 7's table is `profiles/r07_gc_encode_isa_budget.md` (same tool, same options): passes 357 / 393 VALU, row block 82,
+  tail 45, third pass 204.
+* The pass takes the frame as the seven dwords of pairs it has in memory and forms the errors two at a time
+  (gc_encode_core.hpp E1-E5): `v_pk_sub_i16 E, xw, H clamp` and `v_dot2_i32_i16 total, E, E, total clamp` once per two sample
+  steps where round 7 had `v_sub_u32_sdwa` and `v_mad_i32_i24` in every step: -14 VALU per pass.
+* The row block reads 6 x ds_read_b128 (8 before) and keeps 7 + 14 registers per row set (16 + 14 before).  The two
+  history-dependent pre-scan distances take the history pair and one v_alignbit: the dot product without its clamp (v_dot2c
+  and a v_mov of the zero, as in the helper wave; hazards placed by the compiler) in place of v_mul_i32_i24 + v_mad_i32_i24.  The winner's history is no longer unpacked into two sign-extended registers a frame.
+* Each dot instruction still wants its wait states (`s_nop`): the accumulate chain's sit off the reconstruction chain.
+"""
 
 
 def cluster(idx):

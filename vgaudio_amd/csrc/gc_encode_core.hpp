@@ -15,7 +15,8 @@
 //       (r + 2^(k-1) - 1 + (d < 0)) >> k  (arithmetic shift) with r = (int)(float)d.
 //  (S3) totalDistance (:161-162) is an exact integer; 32-bit accumulation is exact under the
 //       overflow bound checked per frame (pass_fast); otherwise the pass is redone literally
-//       with a 64-bit sum.
+//       with a 64-bit sum.  Since round 8 the fast pass sums the squares of PAIRS of saturated 16-bit errors
+//       (E1-E5 below): its sum is the exact one below 2^28 and "at least 2^28" otherwise.
 #pragma once
 #include <cstdint>
 
@@ -31,14 +32,6 @@
 #define VGA_MUL24(a, b) __mul24((a), (b))
 #define VGA_OPAQUE(v) asm("" : "+v"(v))
 #define VGA_OPAQUE_S(v) asm("" : "+s"(v))
-// acc + e*e as ONE instruction (hipcc otherwise re-associates the 14 sums into mul, mul, add3)
-static __device__ __forceinline__ uint32_t vga_mad24_acc(int e, uint32_t acc)
-{
-    uint32_t r;
-    asm("v_mad_i32_i24 %0, %1, %1, %2" : "=v"(r) : "v"(e), "v"(acc));
-    return r;
-}
-#define VGA_MAD24_ACC(e, acc) vga_mad24_acc((e), (acc))
 // e * e for |e| <= 65535 as an unsigned 32-bit value.  NOT __mul24: the device library writes that one as a signed C product,
 // the compiler may then assume it stays below 2^31 -- it folded the first two squares of a 64-bit error sum into one 32-bit
 // mad (round 5: every frame of a full-scale square came out with the wrong predictor).
@@ -49,7 +42,6 @@ static __device__ __forceinline__ uint32_t vga_square24(int e)
     return r;
 }
 #else
-#define VGA_MAD24_ACC(e, acc) ((acc) + (uint32_t)(e) * (uint32_t)(e))
 #define VGA_MUL24(a, b) ((a) * (b))
 #define VGA_OPAQUE(v) ((void)0)
 #define VGA_OPAQUE_S(v) ((void)0)
@@ -161,6 +153,7 @@ struct PassOut {
     int o12, o13;        // reconstructed samples 12, 13
     unsigned hist_pair;  // (o12 & 0xFFFF) | (o13 << 16): the next frame's history, as the kernel hands it on
     bool exact;          // false: the fast pass could not prove itself exact -> redo with pass_literal
+                         // (true: `total` is the exact sum whatever its size; false: see E3)
 };
 
 VGA_HD uint32_t bswap32(uint32_t v)
@@ -278,6 +271,53 @@ VGA_HD uint32_t sat_pack16(int lo, int hi)
     return pack16(clamp16i(lo), clamp16i(hi));
 #endif
 }
+// ---- a frame's samples as packed pairs (round 8) ---------------------------------------
+// The fast pass takes the frame as the seven dwords it has in memory, xw[i] = (in[2i], in[2i + 1]) = (x[2 + 2i], x[3 + 2i]),
+// and forms its errors two at a time: one packed saturating subtract, one dot product of the pair with itself.
+// (clamp16(a.lo - b.lo) & 0xFFFF) | (clamp16(a.hi - b.hi) << 16): v_pk_sub_i16 with its clamp bit.  The bit is part of the
+// arithmetic here: a difference of two int16 needs 17 bits, unclamped 65535 would wrap to -1 (E2).
+VGA_HD uint32_t pk_sub_sat_i16(uint32_t a, uint32_t b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef short s16x2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
+#else
+    return pack16(clamp16i(pair_lo(a) - pair_lo(b)), clamp16i(pair_hi(a) - pair_hi(b)));
+#endif
+}
+// a.lo * b.lo + a.hi * b.hi in the reference's unchecked int arithmetic (mod 2^32): the dot product WITHOUT the clamp bit, as the
+// helper wave's pre-scan uses it.  For the pre-scan, whose predictor must wrap as the reference's does (only
+// (-32768, -32768) . (-32768, -32768) = 2^31 can).  hipcc makes the two-operand v_dot2c and a v_mov of the zero from it (see
+// dot2_i16) -- twice a frame, not fourteen times a pass.  (Round 8 first wrote the three-operand instruction with the inline
+// constant 0 as an asm statement and saved the copy; but hipcc does not look inside asm statements when it places the wait
+// states a dot product's result needs -- it left `s_nop 0` where its own get `s_nop 2` -- so the builtin it is.)
+VGA_HD int dot2_i16_wrap(uint32_t a, uint32_t b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef short s16x2 __attribute__((ext_vector_type(2)));
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b), 0, false);
+#else
+    return (int)((uint32_t)(pair_lo(a) * pair_lo(b)) + (uint32_t)(pair_hi(a) * pair_hi(b)));
+#endif
+}
+VGA_HD void pack_row(const int (&x)[16], uint32_t (&xw)[7])
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 7; i++) xw[i] = pack16(x[2 + 2 * i], x[3 + 2 * i]);
+}
+// x[0], x[1] = the history, x[2..15] = the frame: the form the literal pass, the sequential pre-scan and the reference's loop
+// as written (resume_passes) take -- the rare paths unpack where they run
+VGA_HD void unpack_row(const uint32_t (&xw)[7], uint32_t hist, int (&x)[16])
+{
+    x[0] = pair_lo(hist);
+    x[1] = pair_hi(hist);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 7; i++) { x[2 + 2 * i] = pair_lo(xw[i]); x[3 + 2 * i] = pair_hi(xw[i]); }
+}
 
 // Fast quantise pass: integer-only, 12 VALU ops per sample (14 with the f32 rounding) instead of the f32/f64 detour.
 // With H = (o0, o1) the packed history and C = (c1, c0) the packed coefficients:
@@ -288,7 +328,9 @@ VGA_HD uint32_t sat_pack16(int lo, int hi)
 //   q      = clamp(u, -8, 7)
 //   w      = (P >> 11) + (q << (k-11))                       the reconstruction before its clamp
 //   H'     = sat_pack(w_prev, w)                             clamp AND history shift: (o1, recon) in one instruction
-//   e      = in - hi(H')                                     the error reads the packed half
+//   every second step, H' = (o[s-1], o[s]) being the two newest outputs:
+//   E      = pk_sub_sat(xw[(s-1)/2], H')                     both errors, each saturated to int16
+//   total  = dot2(E, E, total)                               + e0*e0 + e1*e1, the sum saturated to int32
 // Why this is the same arithmetic as the reference's (and as the pass in two 32-bit history registers it replaces):
 //  (P1) with |c0| + |c1| <= 32767 the dot product IS o0*c1 + o1*c0 + 1024: its operands are int16, every product is exact
 //       in 32 bits and |sum| <= 32768 * 32767 + 1024 < 2^30 -- nothing wraps in the reference's int arithmetic and nothing
@@ -303,14 +345,34 @@ VGA_HD uint32_t sat_pack16(int lo, int hi)
 //  (P5) the low half is w_prev saturated AGAIN, from the unclamped value of the step before: clamp16i of the same number, i.e.
 //       the previous step's hi(H) -- the history shift o0 = o1 at no cost.  (Step 0: w_prev = x[1], a 16-bit value.)
 //  (P6) S2, S3 and the `exact` test below are untouched: they speak about d, u and e, which are the same numbers.
+// The error sum in pairs (round 8) -- what `total` means:
+//  (E1) step s reconstructs o[s] for the input x[s + 2]; after steps s - 1 and s (s odd) H' holds (o[s-1], o[s]) and the row
+//       dword xw[(s-1)/2] holds (x[s+1], x[s+2]): the inputs of exactly these two steps, halves in the same order.
+//  (E2) x and o are int16, so e = x - o lies in [-65535, 65535] and need not fit 16 bits; pk_sub_sat saturates each half to
+//       [-32768, 32767].  A half that did NOT saturate is e itself.
+//  (E3) dot2 with its clamp adds e0*e0 + e1*e1 to the running sum and saturates the result to [.., 2^31 - 1].  Every term is
+//       >= 0, so the running sum never decreases and, once saturated, stays at 2^31 - 1.  If no half saturated and the exact
+//       sum is below 2^31, `total` IS the exact sum.  If a half saturated, its term is >= 32767^2 > 2^29, and if the sum
+//       reached 2^31 it stays there: either way total >= 2^28 AND the exact sum >= 2^28.  Conversely an exact sum below
+//       2^28 has no term of 2^28 or more, so no |e| > 16384, nothing saturated: total == exact sum.  Hence
+//           exact sum <  2^28  =>  total == exact sum
+//           exact sum >= 2^28  =>  total >= 2^28, its value otherwise unspecified.
+//       This holds for ANY row and history (it is a statement about fourteen int16 pairs), whatever the overflow.
+//  (E4) the kernel's argmin folds every sum from 2^28 on into one 32-bit key and lets 64-bit keys decide only when a channel's
+//       best is that large; there, and only there, a lane at or above 2^28 needs its exact sum: the pass again with
+//       WIDE_TOTAL (scalar 17-bit errors, 64-bit sum).  A final lane at the cap may have |e| up to 14338 (overflow 3) and,
+//       if its sum came from a WIDE pass, up to 65535: all of them are above 2^28 when they matter and go that way.
+//  (E5) r.exact == true promises more: `total` is the exact sum whatever its size.  That needs 14 e^2 < 2^31, |e| <= 12385;
+//       the bound below ((2 ov + 1) << (k - 11) <= 24766, i.e. |e| <= 12385) is what pass_fast / resume_passes rely on when
+//       they hand `total` to a 64-bit comparison without looking at it again.
 // The nibbles leave the pass unpacked (r.q): the kernel's helper wave packs the winner's frame (pack_frame).
 // The overflow is recovered from the running max/min of u (one max3/min3 per two samples).
-// r.exact == false (frame must be redone with pass_literal) when the 32-bit sum of squared
-// errors could overflow (S3): with |c0|+|c1| <= 32767 the predictor cannot wrap, and then
+// r.exact == false (frame must be redone with pass_literal) when the saturating 32-bit sum of squared
+// errors could stop short (S3, E5): with |c0|+|c1| <= 32767 the predictor cannot wrap, and then
 // |in - recon| <= (ov + 1/2) * 2^(k-11) + 2 where ov is the pass's max overflow; we require that
-// bound to stay <= 17 500 (14 * 17500^2 < 2^32), which also rules out int32 overflow in u.
+// bound to stay <= 12 385 (14 * 12385^2 < 2^31), which also rules out int32 overflow in u.
 // in2048p[s] = x[s + 2] * 2048 + 1024 is supplied by the caller (the kernel's helper wave precomputes it per tile), hist
-// is the packed history (x[0], x[1]).
+// is the packed history (x[0], x[1]), xw the frame as packed pairs (E1).
 // WIDE_TOTAL: the error sum in 64 bits (a multiply and an add with carry per sample instead of one mad) -- exact whatever
 // the overflow as long as the predictor cannot wrap (|c0| + |c1| <= 32767: then |d| < 2^30 + 2^26, u cannot leave int32, and
 // |in - recon| <= 65535 squares into 32 bits).  For the one case the 32-bit sum cannot serve: a pass at the cap (scale 12 ends
@@ -322,7 +384,7 @@ VGA_HD uint32_t sat_pack16(int lo, int hi)
 // for nibble -- and one that does not must be run again with the conversions.  The kernel takes this form for a frame when
 // every lane of the wave quantises at scale 9 or below (70 % of the synthetic set's wave-frames).
 template <bool WIDE_TOTAL, bool NO_ROUND = false>
-VGA_HD PassOut pass_fast_core_t(const int (&x)[16], uint32_t hist, const int (&in2048p)[14], int c0, int c1, int scale_power)
+VGA_HD PassOut pass_fast_core_t(const uint32_t (&xw)[7], uint32_t hist, const int (&in2048p)[14], int c0, int c1, int scale_power)
 {
     PassOut r;
     uint64_t total64 = 0;
@@ -333,7 +395,7 @@ VGA_HD PassOut pass_fast_core_t(const int (&x)[16], uint32_t hist, const int (&i
     const uint32_t cpair = pack16(c1, c0);
     int k1024 = 1024;
     VGA_OPAQUE_S(k1024);
-    uint32_t total = 0;
+    int total = 0;
     int umax = 0, umin = 0;
     int u_prev = 0;
     uint32_t h = hist;                                              // (o0, o1)
@@ -356,57 +418,100 @@ VGA_HD PassOut pass_fast_core_t(const int (&x)[16], uint32_t hist, const int (&i
         const int w = (P >> 11) + (int)((uint32_t)q << km11);       // off the chain: P >> 11 waits for q
         h = sat_pack16(w_prev, w);                                  // (o1, recon)
         w_prev = w;
-        const int e = x[s + 2] - pair_hi(h);
+        if (WIDE_TOTAL) {
+            const int e = ((s & 1) ? pair_hi(xw[s >> 1]) : pair_lo(xw[s >> 1])) - pair_hi(h);      // x[s + 2] - o[s], 17 bits
 #if defined(__HIP_DEVICE_COMPILE__)
-        if (WIDE_TOTAL) total64 += (uint64_t)vga_square24(e);           // |e| <= 65535: the product's low 32 bits are the square
+            total64 += (uint64_t)vga_square24(e);                   // |e| <= 65535: the product's low 32 bits are the square
 #else
-        if (WIDE_TOTAL) total64 += (uint64_t)((int64_t)e * (int64_t)e);
+            total64 += (uint64_t)((int64_t)e * (int64_t)e);
 #endif
-        else total = VGA_MAD24_ACC(e, total);                       // total += e * e, one v_mad_i32_i24
+        } else if (s & 1) {
+            const uint32_t epk = pk_sub_sat_i16(xw[s >> 1], h);     // (x[s+1] - o[s-1], x[s+2] - o[s]), saturated (E1, E2)
+            total = dot2_i16(epk, epk, total);                      // total += e0*e0 + e1*e1, saturating (E3)
+        }
     }
     r.hist_pair = h;                                                // falls out of the last step
     const int ov = imax(imax(umax - 7, -8 - umin), 0);
     const int ac0 = c0 < 0 ? -c0 : c0, ac1 = c1 < 0 ? -c1 : c1;
-    r.exact = ac0 + ac1 <= 32767 && (WIDE_TOTAL || (ov <= 17497 && (((2 * ov + 1) << (k - 11)) <= 34996)));
-    r.total = WIDE_TOTAL ? total64 : (uint64_t)total;
+    r.exact = ac0 + ac1 <= 32767 && (WIDE_TOTAL || (ov <= 12383 && (((2 * ov + 1) << (k - 11)) <= 24766)));
+    r.total = WIDE_TOTAL ? total64 : (uint64_t)(uint32_t)total;     // (total >= 0: see E3)
     r.max_overflow = ov;
     r.o12 = pair_lo(h); r.o13 = pair_hi(h);
     return r;
 }
-VGA_HD PassOut pass_fast_core(const int (&x)[16], uint32_t hist, const int (&in2048p)[14], int c0, int c1, int scale_power)
+VGA_HD PassOut pass_fast_core(const uint32_t (&xw)[7], uint32_t hist, const int (&in2048p)[14], int c0, int c1, int scale_power)
 {
-    return pass_fast_core_t<false>(x, hist, in2048p, c0, c1, scale_power);
+    return pass_fast_core_t<false>(xw, hist, in2048p, c0, c1, scale_power);
 }
-VGA_HD PassOut pass_fast_core_no_round(const int (&x)[16], uint32_t hist, const int (&in2048p)[14], int c0, int c1,
+VGA_HD PassOut pass_fast_core_no_round(const uint32_t (&xw)[7], uint32_t hist, const int (&in2048p)[14], int c0, int c1,
                                        int scale_power)
 {
-    return pass_fast_core_t<false, true>(x, hist, in2048p, c0, c1, scale_power);
+    return pass_fast_core_t<false, true>(xw, hist, in2048p, c0, c1, scale_power);
 }
 // the bound under which a NO_ROUND pass is the exact pass (scale_power <= 12: the bound is positive up to scale 9)
 VGA_HD bool pass_no_round_is_exact(int scale_power, int max_overflow)
 {
     return scale_power <= 9 && max_overflow < (1 << (13 - scale_power)) - 8;
 }
+VGA_HD PassOut pass_fast_core_wide(const uint32_t (&xw)[7], uint32_t hist, const int (&in2048p)[14], int c0, int c1,
+                                   int scale_power)
+{
+    return pass_fast_core_t<true>(xw, hist, in2048p, c0, c1, scale_power);
+}
+// The exact-sum rule (E4) for one lane: a sum at or above 2^28 that is not known to be exact (r.exact) is taken again from
+// the pass with the 64-bit sum, at the scale the pass ran at.  The kernel's cold block applies it when a channel's best key
+// saturated; for coefficients that can wrap the wide pass is no authority and the caller has the literal pass's sum.
+constexpr uint64_t PACKED_SUM_CAP = 1ull << 28;
+VGA_HD bool needs_exact_sum(uint64_t total, bool known_exact) { return !known_exact && total >= PACKED_SUM_CAP; }
+// The same three for callers that hold the frame as sixteen ints, x[0], x[1] the history (the lane emulators of the CPU
+// tests): the row is packed here, the pass is the one above.
+VGA_HD PassOut pass_fast_core(const int (&x)[16], uint32_t hist, const int (&in2048p)[14], int c0, int c1, int scale_power)
+{
+    uint32_t xw[7];
+    pack_row(x, xw);
+    return pass_fast_core_t<false>(xw, hist, in2048p, c0, c1, scale_power);
+}
+VGA_HD PassOut pass_fast_core_no_round(const int (&x)[16], uint32_t hist, const int (&in2048p)[14], int c0, int c1,
+                                       int scale_power)
+{
+    uint32_t xw[7];
+    pack_row(x, xw);
+    return pass_fast_core_t<false, true>(xw, hist, in2048p, c0, c1, scale_power);
+}
 VGA_HD PassOut pass_fast_core_wide(const int (&x)[16], uint32_t hist, const int (&in2048p)[14], int c0, int c1,
                                    int scale_power)
 {
-    return pass_fast_core_t<true>(x, hist, in2048p, c0, c1, scale_power);
+    uint32_t xw[7];
+    pack_row(x, xw);
+    return pass_fast_core_t<true>(xw, hist, in2048p, c0, c1, scale_power);
 }
-// The same three with the history taken from x[0], x[1] and with the row of x * 2048 the pass read until round 7 (callers
-// that still build one -- the lane emulator -- keep compiling; the pass does not look at it).
+// ... and with the row of x * 2048 the pass read until round 7 (the pass does not look at it).  These hand `total` straight
+// to 64-bit comparisons, as the kernel did until round 8: they apply the exact-sum rule themselves.
+template <bool NO_ROUND>
+VGA_HD PassOut pass_fast_core_exact_sum(const int (&x)[16], const int (&in2048p)[14], int c0, int c1, int scale_power)
+{
+    uint32_t xw[7];
+    pack_row(x, xw);
+    const uint32_t hist = pack16(x[0], x[1]);
+    PassOut r = pass_fast_core_t<false, NO_ROUND>(xw, hist, in2048p, c0, c1, scale_power);
+    const int ac0 = c0 < 0 ? -c0 : c0, ac1 = c1 < 0 ? -c1 : c1;
+    if (ac0 + ac1 <= 32767 && needs_exact_sum(r.total, r.exact))
+        r.total = pass_fast_core_t<true>(xw, hist, in2048p, c0, c1, scale_power).total;
+    return r;
+}
 VGA_HD PassOut pass_fast_core(const int (&x)[16], const int (&)[14], const int (&in2048p)[14], int c0, int c1, int scale_power)
 {
-    return pass_fast_core_t<false>(x, pack16(x[0], x[1]), in2048p, c0, c1, scale_power);
+    return pass_fast_core_exact_sum<false>(x, in2048p, c0, c1, scale_power);
 }
 VGA_HD PassOut pass_fast_core_no_round(const int (&x)[16], const int (&)[14], const int (&in2048p)[14], int c0, int c1,
                                        int scale_power)
 {
-    return pass_fast_core_t<false, true>(x, pack16(x[0], x[1]), in2048p, c0, c1, scale_power);
+    return pass_fast_core_exact_sum<true>(x, in2048p, c0, c1, scale_power);
 }
 VGA_HD PassOut pass_fast_core_wide(const int (&x)[16], const int (&)[14], const int (&in2048p)[14], int c0, int c1,
                                    int scale_power)
 {
-    return pass_fast_core_t<true>(x, pack16(x[0], x[1]), in2048p, c0, c1, scale_power);
+    return pass_fast_core_wide(x, pack16(x[0], x[1]), in2048p, c0, c1, scale_power);
 }
 
 VGA_HD PassOut pass_fast(const int (&x)[16], int c0, int c1, int scale_power)

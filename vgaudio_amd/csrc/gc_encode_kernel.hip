@@ -64,7 +64,7 @@ __device__ __forceinline__ unsigned row16_reduce(unsigned v, Op op)
 //       twelve samples s = 2..13 that involve input samples only (GcAdpcmEncoder.cs:107-115),
 //     * all of it into LDS (double-buffered), plus the coalesced flush of the previous tile's frames
 //       (the zero-padded partial last frame travels through the same path);
-//   serial wave (wave 0): per frame 9 LDS reads, the two history-dependent pre-scan distances, the
+//   serial wave (wave 0): per frame 7 LDS reads, the two history-dependent pre-scan distances, the
 //     speculative quantise pass, candidate resolution, DPP argmin, one LDS write.
 // The hot loop is ONE copy of the frame body (a few KB of code): the reference's third-and-later
 // quantise passes re-enter the same pass code through a wave-uniform loop, and the never-on-audio
@@ -128,22 +128,21 @@ struct Lay {
 };
 template <int CS, int TF>
 struct GcTileT {
-    int x[CS][TF][16];         // [channel slot][frame][sample]  (14 used)
+    uint32_t xw[CS][TF][8];    // [channel slot][frame]: the frame as packed pairs (in[2i], in[2i + 1]), 7 used (round 8)
     int in2048p[CS][TF][16];   // x * 2048 + 1024  (the pass needs no x * 2048 beside it since round 7: gc_encode_core.hpp P2)
     uint32_t pre[CS][TF][8];   // per predictor: clamp16(max d) & 0xFFFF | clamp16(min d) << 16, over s = 2..13
 };
 typedef short short2v __attribute__((ext_vector_type(2)));
-struct X16 { int v[16]; };
+struct XW7 { uint32_t v[7]; };
 
 // inline: measured 267 ms out of line vs 260 ms inline at configs[1] (round 1)
 #define VGA_COLD __device__ __forceinline__
 
 // Rare +M/-M tie of the pre-scan (argument by value: the hot copy of the frame stays in registers).
-VGA_COLD int prescan_sequential_cold(X16 xs, int c0, int c1)
+VGA_COLD int prescan_sequential_cold(XW7 xs, uint32_t hist, int c0, int c1)
 {
     int x[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) x[i] = xs.v[i];
+    unpack_row(xs.v, hist, x);
     return prescan_sequential(x, c0, c1);
 }
 
@@ -156,14 +155,16 @@ VGA_COLD int prescan_sequential_cold(X16 xs, int c0, int c1)
 // path (a build with the block compiled in but never run: 172 ms vs 140 ms without it), which is why the
 // frame's tail is instantiated once per branch below instead of merging the two branches' results.
 struct ColdState {
-    int x[16], mp[14];
+    uint32_t xw[7];            // the frame as packed pairs; the paths that want ints unpack it where they run
+    int mp[14];
     uint32_t hist;             // (x[0], x[1]) packed
     int c0, c1, s1;
     // what this lane needs (any of them in any lane sends the wave here):
     //   generic: the reference's loop as written from `start` (the scalePower its loop continues from): the bump loop
     //            (:166-168) was entered, or the coefficients can wrap int32
     //   drop:    (lane-per-candidate layout) the pair's other lane redoes the whole loop: this lane is out
-    //   wide:    the final pass ran at the cap with an overflow above 3: same pass again with a 64-bit error sum
+    //   wide:    the final pass ran at the cap with an overflow above 3 (until round 8 its 32-bit error sum could have wrapped
+    //            and the pass ran again at once; the sum in pairs cannot wrap and the exact-sum rule below covers the lane)
     //   resume:  third and later trips
     // start: -100 = not known yet: the loop stands behind the bumps of the pass that started them (bump_a: the pass at s1
     // with overflow ov_a, else the pass at s1 + 1 with ov_b) -- worked out only by a lane that goes that way (round 6: the
@@ -171,43 +172,42 @@ struct ColdState {
     int generic, start, drop, wide, resume;
     int bump_a, ov_a, ov_b;
 };
-struct ColdOut { PassOut r; int final_sp; int fin; };
+// sum_exact: r.total came from the reference's loop as written (exact whatever its size); 0: from a fast pass at final_sp,
+// exact below 2^28 and "at least 2^28" otherwise (gc_encode_core.hpp E3)
+struct ColdOut { PassOut r; int final_sp; int fin; int sum_exact; };
 // inline: 370 ms out of line (the by-value state goes through scratch) vs 209 inline (round 1)
 __device__ __forceinline__
 ColdOut encode_frame_cold(ColdState st, PassOut r, int final_sp, int fin)
 {
-    int x[16], mp[14];
+    uint32_t xw[7];
+    int mp[14];
 #pragma unroll
-    for (int i = 0; i < 16; i++) x[i] = st.x[i];
+    for (int i = 0; i < 7; i++) xw[i] = st.xw[i];
 #pragma unroll
     for (int i = 0; i < 14; i++) mp[i] = st.mp[i];
+    int sum_exact = 0;
     if (st.drop) fin = 0;
-    if (__any((st.generic | st.wide) != 0)) {      // (one test in front of both: the common visitor is a third trip)
     if (__any(st.generic != 0)) {                  // hostile input, and tones the first scale misjudges by 2^5 and more
         if (st.generic) {
             // (the frame is made opaque here: hipcc otherwise hoists the literal pass's set-up -- fourteen shifts, 64-bit
             // mads -- out of this branch into every visit of the cold block)
             int xg[16];
+            unpack_row(xw, st.hist, xg);
 #pragma unroll
-            for (int i = 0; i < 16; i++) { xg[i] = x[i]; VGA_COLD_OPAQUE(xg[i]); }
+            for (int i = 0; i < 16; i++) VGA_COLD_OPAQUE(xg[i]);
             const int start = st.start != -100 ? st.start
                                                : (st.bump_a ? apply_bumps(st.s1, st.ov_a) : apply_bumps(st.s1 + 1, st.ov_b));
             r = resume_passes(xg, st.c0, st.c1, start, final_sp);
             fin = 1;
+            sum_exact = 1;
         }
     }
     // Round 5: until then any lane whose pass at the cap overflowed by more than 3 sent the whole wave through the
     // reference's loop from its start (three to four passes, the literal f32 / f64 one among them) -- 96 % of the wave-frames of
     // full-scale white noise and of a clipped square (bench.py signal_sensitivity: 316 and 343 ms against 146).  The pass
-    // itself is right (gc_encode_core.hpp S2 holds for every int32 distance); only its 32-bit error sum may have wrapped.
-    if (__any(st.wide != 0)) {
-        if (st.wide) {
-            const PassOut w = pass_fast_core_wide(x, st.hist, mp, st.c0, st.c1, final_sp);
-            r.total = w.total;
-            fin = 1;
-        }
-    }
-    }
+    // itself is right (gc_encode_core.hpp S2 holds for every int32 distance) and so is its error sum wherever the argmin
+    // looks at the value (E3); a `wide` lane stays final with the sum it has, the caller applies the exact-sum rule.
+    if (st.wide) fin = 1;
     if (__any(st.resume != 0)) {
         if (st.resume) {
             // third and later trips, same straight-line tests as the first trip
@@ -220,16 +220,18 @@ ColdOut encode_frame_cold(ColdState st, PassOut r, int final_sp, int fin)
                 bool short_pass = !__any(sp > 9);  // (over the lanes still in this loop) without the f32 detour, as the first two passes
 #endif
                 if (short_pass) {
-                    r = pass_fast_core_no_round(x, st.hist, mp, st.c0, st.c1, sp);
+                    r = pass_fast_core_no_round(xw, st.hist, mp, st.c0, st.c1, sp);
                     short_pass = !__any(!pass_no_round_is_exact(sp, r.max_overflow));
                 }
-                if (!short_pass) r = pass_fast_core(x, st.hist, mp, st.c0, st.c1, sp);
+                if (!short_pass) r = pass_fast_core(xw, st.hist, mp, st.c0, st.c1, sp);
                 const bool cap = sp >= 12;
                 if ((unsigned)r.max_overflow > (cap ? 3u : 248u)) {      // bump loop / inexact sum: generic
                     int xg[16];                                          // (opaque: see above)
+                    unpack_row(xw, st.hist, xg);
 #pragma unroll
-                    for (int i = 0; i < 16; i++) { xg[i] = x[i]; VGA_COLD_OPAQUE(xg[i]); }
+                    for (int i = 0; i < 16; i++) VGA_COLD_OPAQUE(xg[i]);
                     r = resume_passes(xg, st.c0, st.c1, sp - 1, final_sp);
+                    sum_exact = 1;
                     break;
                 }
                 final_sp = sp;
@@ -242,6 +244,7 @@ ColdOut encode_frame_cold(ColdState st, PassOut r, int final_sp, int fin)
     o.r = r;
     o.final_sp = final_sp;
     o.fin = fin;
+    o.sum_exact = sum_exact;
     return o;
 }
 
@@ -351,11 +354,9 @@ __device__ __forceinline__ void gc_encode_piece(
                 for (int i = 0; i < 7; i++) w[i] = (uint32_t)(in[2 * i] & 0xFFFF) | ((uint32_t)in[2 * i + 1] << 16);
             }
             GcTile &T = s_tile[tile & 1];
-            int4 *xr = reinterpret_cast<int4 *>(&T.x[grp][hfr][0]);
-            xr[0] = make_int4(in[0], in[1], in[2], in[3]);
-            xr[1] = make_int4(in[4], in[5], in[6], in[7]);
-            xr[2] = make_int4(in[8], in[9], in[10], in[11]);
-            xr[3] = make_int4(in[12], in[13], 0, 0);
+            uint4 *xr = reinterpret_cast<uint4 *>(&T.xw[grp][hfr][0]);   // the pairs as loaded (the ints: in2048p and the pre-scan)
+            xr[0] = make_uint4(w[0], w[1], w[2], w[3]);
+            xr[1] = make_uint4(w[4], w[5], w[6], 0u);
             int4 *qr = reinterpret_cast<int4 *>(&T.in2048p[grp][hfr][0]);
             qr[0] = make_int4(in[0] * 2048 + 1024, in[1] * 2048 + 1024, in[2] * 2048 + 1024, in[3] * 2048 + 1024);
             qr[1] = make_int4(in[4] * 2048 + 1024, in[5] * 2048 + 1024, in[6] * 2048 + 1024, in[7] * 2048 + 1024);
@@ -436,20 +437,17 @@ __device__ __forceinline__ void gc_encode_piece(
         h0 = src[-2];
         h1 = src[-1];
     }
-    VGA_OPAQUE(h0);
-    VGA_OPAQUE(h1);
-    uint32_t hpk = pack16(h0, h1);                     // the same history as the pass takes it: (h0, h1) in one register
+    uint32_t hpk = pack16(h0, h1);                     // the history as the pass and the pre-scan take it: (h0, h1) in one register
 
     if (lane == 0) s_ncold[wave] = 0;                  // cold blocks this piece (diagnostics, g_vga_gc_stats)
-    struct Row { int x[16]; int mp[14]; uint32_t pre; };
+    struct Row { uint32_t xw[7]; int mp[14]; uint32_t pre; };
     auto read_row = [&](const GcTile &T, int j, Row &R) {
-        const int4 *xr = reinterpret_cast<const int4 *>(&T.x[grp][j][0]);
-        const int4 a0 = xr[0], a1 = xr[1], a2 = xr[2], a3 = xr[3];
-        // keep the padding lanes "used": hipcc otherwise splits the 16-byte row reads into 7 odd-sized ones
-        asm volatile("" ::"v"(a3.z), "v"(a3.w));
-        int *x = R.x;
-        x[2] = a0.x; x[3] = a0.y; x[4] = a0.z; x[5] = a0.w; x[6] = a1.x; x[7] = a1.y; x[8] = a1.z; x[9] = a1.w;
-        x[10] = a2.x; x[11] = a2.y; x[12] = a2.z; x[13] = a2.w; x[14] = a3.x; x[15] = a3.y;
+        const uint4 *xr = reinterpret_cast<const uint4 *>(&T.xw[grp][j][0]);
+        const uint4 a0 = xr[0], a1 = xr[1];
+        // keep the padding lanes "used": hipcc otherwise splits the 16-byte row reads into odd-sized ones
+        asm volatile("" ::"v"(a1.w));
+        uint32_t *xw = R.xw;
+        xw[0] = a0.x; xw[1] = a0.y; xw[2] = a0.z; xw[3] = a0.w; xw[4] = a1.x; xw[5] = a1.y; xw[6] = a1.z;
         const int4 *qr = reinterpret_cast<const int4 *>(&T.in2048p[grp][j][0]);
         const int4 e0 = qr[0], e1 = qr[1], e2 = qr[2], e3 = qr[3];
         asm volatile("" ::"v"(e3.z), "v"(e3.w));
@@ -458,34 +456,40 @@ __device__ __forceinline__ void gc_encode_piece(
         mp[8] = e2.x; mp[9] = e2.y; mp[10] = e2.z; mp[11] = e2.w; mp[12] = e3.x; mp[13] = e3.y;
         R.pre = T.pre[grp][j][p];
     };
-    auto pack = [](const int (&x)[16]) {
-        X16 xs;
+    auto pack = [](const uint32_t (&xw)[7]) {
+        XW7 xs;
 #pragma unroll
-        for (int i = 0; i < 16; i++) xs.v[i] = x[i];
+        for (int i = 0; i < 7; i++) xs.v[i] = xw[i];
         return xs;
+    };
+    // The two history-dependent pre-scan distances (:107-115), operands taken from pairs: predicted(s = 0) is the dot product of
+    // the history pair (h0, h1) with (c1, c0), predicted(s = 1) that of (h1, x[2]) -- one v_alignbit across the history and the
+    // row's first dword.  Unclamped dot product: int32 wraps where the reference's unchecked sum does.
+    const uint32_t cpk = pack16(c1, c0);
+    auto prescan_head = [&](const Row &R, int &d0, int &d1) __attribute__((always_inline)) {
+        d0 = pair_lo(R.xw[0]) - div2048(dot2_i16_wrap(hpk, cpk));
+        d1 = pair_hi(R.xw[0]) - div2048(dot2_i16_wrap(__builtin_amdgcn_alignbit(R.xw[0], hpk, 16), cpk));
     };
 
     auto encode_frame = [&](Row &R, int buf, int j, bool upd) {
-        int (&x)[16] = R.x;
-        x[0] = h0;
-        x[1] = h1;
+        const uint32_t (&xw)[7] = R.xw;
         // ---- pre-scan (:107-124): two history-dependent distances + the helper's range for s = 2..13
         int s1;
         {
-            const int d0 = x[2] - div2048(VGA_MUL24(x[0], c1) + VGA_MUL24(x[1], c0));
-            const int d1 = x[3] - div2048(VGA_MUL24(x[1], c1) + VGA_MUL24(x[2], c0));
+            int d0, d1;
+            prescan_head(R, d0, d1);
             const int dmax = imax(imax((int)(int16_t)(R.pre & 0xFFFF), d0), d1);
             const int dmin = imin(imin((int)R.pre >> 16, d0), d1);
             s1 = first_scale_power_from_range(dmax, dmin);
             if (__any(s1 == -100)) {                   // +M and -M both present: first occurrence decides
-                if (s1 == -100) s1 = first_scale_power_from_md(prescan_sequential_cold(pack(x), c0, c1));
+                if (s1 == -100) s1 = first_scale_power_from_md(prescan_sequential_cold(pack(xw), hpk, c0, c1));
             }
         }
         // ---- first trip: candidate A at s1, B at s1+1 (speculation on the loop of :127-170)
         int final_sp = imin(s1 + (cand_b ? 1 : 0), 12);
         const bool at_cap = final_sp >= 12;            // the loop never goes past 12: this pass ends it
         const unsigned ov_limit = at_cap ? 3u : 248u;  // see `rare` below
-        PassOut r = pass_fast_core(x, hpk, R.mp, c0, c1, final_sp);
+        PassOut r = pass_fast_core(xw, hpk, R.mp, c0, c1, final_sp);
         // Straight-line resolution, valid when no lane is `rare`:
         //   * no overflow can start the bump loop (:166-168 needs max_overflow + 8 > 256),
         //   * the 32-bit error sum of every lane that can become final is exact (gc_encode_core.hpp S3:
@@ -517,8 +521,8 @@ __device__ __forceinline__ void gc_encode_piece(
             sat = __any((best >> 4) >= SAT);
             return (int)(best & 15u);
         };
-        auto argmin64 = [&](const PassOut &r, bool fin) __attribute__((always_inline)) -> int {
-            uint64_t key = fin ? ((r.total << 4) | (uint64_t)l16) : ~0ull;
+        auto argmin64 = [&](uint64_t total, bool fin) __attribute__((always_inline)) -> int {
+            uint64_t key = fin ? ((total << 4) | (uint64_t)l16) : ~0ull;
 #define VGA_MIN64_STAGE(CTRL)                                                          \
             {                                                                          \
                 const unsigned olo = (unsigned)dpp<CTRL>((int)(uint32_t)key);          \
@@ -546,13 +550,7 @@ __device__ __forceinline__ void gc_encode_piece(
                 rec[2] = make_int4(r.q[8], r.q[9], r.q[10], r.q[11]);
                 rec[3] = make_int4(r.q[12], r.q[13], p, final_sp);
             }
-            if (!RAGGED || upd) {
-                h0 = (int)(int16_t)(pay & 0xFFFF);   // pcmBuffer[0] = pcmBuffer[14] (:40)
-                h1 = (int)pay >> 16;                 // pcmBuffer[1] = pcmBuffer[15] (:41)
-                hpk = pay;
-            }
-            VGA_OPAQUE(h0);                      // hide the 16-bit range: keeps the 24-bit multiplies the next frame
-            VGA_OPAQUE(h1);                      // asks for (the compiler otherwise widens them to 64-bit mads)
+            if (!RAGGED || upd) hpk = pay;       // pcmBuffer[0] = pcmBuffer[14], pcmBuffer[1] = pcmBuffer[15] (:40-41), as the pair
         };
         bool sat = false;
         const int winner32 = argmin32(r, fin && !inexact, sat);      // (a lane whose sum is not to be trusted yet is not in it)
@@ -563,7 +561,7 @@ __device__ __forceinline__ void gc_encode_piece(
 #endif
             ColdState st;
 #pragma unroll
-            for (int i = 0; i < 16; i++) st.x[i] = x[i];
+            for (int i = 0; i < 7; i++) st.xw[i] = xw[i];
 #pragma unroll
             for (int i = 0; i < 14; i++) st.mp[i] = R.mp[i];
             st.hist = hpk;
@@ -575,7 +573,15 @@ __device__ __forceinline__ void gc_encode_piece(
             const ColdOut o = encode_frame_cold(st, r, final_sp, fin);
             bool sat2 = false;
             int winner = argmin32(o.r, o.fin != 0, sat2);
-            if (sat2) winner = argmin64(o.r, o.fin != 0);
+            if (sat2) {
+                // the exact-sum rule (gc_encode_core.hpp E4): a channel's best sum is 2^28 or more, 64-bit keys decide -- and a final
+                // lane up there whose sum came from a fast pass has "at least 2^28" for a sum: the pass at its scale again with the
+                // scalar 64-bit error term.  (Coefficients that can wrap went through the reference's loop: sum_exact.)
+                uint64_t total = o.r.total;
+                if (o.fin != 0 && needs_exact_sum(total, o.sum_exact != 0))
+                    total = pass_fast_core_wide(xw, hpk, R.mp, c0, c1, o.final_sp).total;
+                winner = argmin64(total, o.fin != 0);
+            }
             commit(o.r, o.final_sp, winner);
         } else
             commit(r, final_sp, winner32);
@@ -584,18 +590,16 @@ __device__ __forceinline__ void gc_encode_piece(
     // ---- CPW = 8: lane = (channel, predictor); candidate B (s1 + 1) and candidate A (s1) are two passes of the SAME lane,
     // inlined back to back (two independent dependent chains: the wave has instructions to issue while one waits).
     auto encode_frame8 = [&](Row &R, int buf, int j, bool upd) {
-        int (&x)[16] = R.x;
-        x[0] = h0;
-        x[1] = h1;
+        const uint32_t (&xw)[7] = R.xw;
         int s1;
         {
-            const int d0 = x[2] - div2048(VGA_MUL24(x[0], c1) + VGA_MUL24(x[1], c0));
-            const int d1 = x[3] - div2048(VGA_MUL24(x[1], c1) + VGA_MUL24(x[2], c0));
+            int d0, d1;
+            prescan_head(R, d0, d1);
             const int dmax = imax(imax((int)(int16_t)(R.pre & 0xFFFF), d0), d1);
             const int dmin = imin(imin((int)R.pre >> 16, d0), d1);
             s1 = first_scale_power_from_range(dmax, dmin);
             if (__any(s1 == -100)) {                   // +M and -M both present: first occurrence decides
-                if (s1 == -100) s1 = first_scale_power_from_md(prescan_sequential_cold(pack(x), c0, c1));
+                if (s1 == -100) s1 = first_scale_power_from_md(prescan_sequential_cold(pack(xw), hpk, c0, c1));
             }
         }
         const int sp_a = imin(s1, 12), sp_b = imin(s1 + 1, 12);
@@ -610,15 +614,15 @@ __device__ __forceinline__ void gc_encode_piece(
         bool short_passes = !__any(sp_b > 9);
 #endif
         if (short_passes) {
-            rb = pass_fast_core_no_round(x, hpk, R.mp, c0, c1, sp_b);
-            ra = pass_fast_core_no_round(x, hpk, R.mp, c0, c1, sp_a);
+            rb = pass_fast_core_no_round(xw, hpk, R.mp, c0, c1, sp_b);
+            ra = pass_fast_core_no_round(xw, hpk, R.mp, c0, c1, sp_a);
             // (hostile coefficients: the lane walks the reference's loop as written whatever these passes say)
             const bool trusted = !coef_ok || (pass_no_round_is_exact(sp_a, ra.max_overflow) && pass_no_round_is_exact(sp_b, rb.max_overflow));
             short_passes = !__any(!trusted);
         }
         if (!short_passes) {
-            rb = pass_fast_core(x, hpk, R.mp, c0, c1, sp_b);
-            ra = pass_fast_core(x, hpk, R.mp, c0, c1, sp_a);
+            rb = pass_fast_core(xw, hpk, R.mp, c0, c1, sp_b);
+            ra = pass_fast_core(xw, hpk, R.mp, c0, c1, sp_a);
         }
         const bool cap_a = sp_a >= 12, cap_b = sp_b >= 12;         // a pass at the cap ends the loop whatever it overflowed
         const int eff_a = cap_a ? 0 : ra.max_overflow, eff_b = cap_b ? 0 : rb.max_overflow;
@@ -663,8 +667,8 @@ __device__ __forceinline__ void gc_encode_piece(
             sat = __any((key >> 3) >= SAT);
             return (int)(key & 7u);
         };
-        auto argmin64 = [&](const PassOut &r, bool fin) __attribute__((always_inline)) -> int {
-            uint64_t key = fin ? ((r.total << 3) | (uint64_t)p) : ~0ull;
+        auto argmin64 = [&](uint64_t total, bool fin) __attribute__((always_inline)) -> int {
+            uint64_t key = fin ? ((total << 3) | (uint64_t)p) : ~0ull;
 #define VGA_MIN64_STAGE(CTRL)                                                          \
             {                                                                          \
                 const unsigned olo = (unsigned)dpp<CTRL>((int)(uint32_t)key);          \
@@ -691,13 +695,7 @@ __device__ __forceinline__ void gc_encode_piece(
                 rec[2] = make_int4(r.q[8], r.q[9], r.q[10], r.q[11]);
                 rec[3] = make_int4(r.q[12], r.q[13], p, final_sp);
             }
-            if (!RAGGED || upd) {                // (a slot past its last frame keeps the history it ended on)
-                h0 = (int)(int16_t)(pay & 0xFFFF);
-                h1 = (int)pay >> 16;
-                hpk = pay;
-            }
-            VGA_OPAQUE(h0);
-            VGA_OPAQUE(h1);
+            if (!RAGGED || upd) hpk = pay;       // (a slot past its last frame keeps the history it ended on)
         };
         bool sat = false;
         const int winner32 = argmin32(r, !(generic || resume || inexact), sat);
@@ -707,7 +705,7 @@ __device__ __forceinline__ void gc_encode_piece(
 #endif
             ColdState st;
 #pragma unroll
-            for (int i = 0; i < 16; i++) st.x[i] = x[i];
+            for (int i = 0; i < 7; i++) st.xw[i] = xw[i];
 #pragma unroll
             for (int i = 0; i < 14; i++) st.mp[i] = R.mp[i];
             st.hist = hpk;
@@ -724,7 +722,15 @@ __device__ __forceinline__ void gc_encode_piece(
             const ColdOut o = encode_frame_cold(st, r, final_sp, (generic || resume) ? 0 : 1);
             bool sat2 = false;
             int winner = argmin32(o.r, o.fin != 0, sat2);
-            if (sat2) winner = argmin64(o.r, o.fin != 0);
+            if (sat2) {
+                // the exact-sum rule (gc_encode_core.hpp E4): a channel's best sum is 2^28 or more, 64-bit keys decide -- and a final
+                // lane up there whose sum came from a fast pass has "at least 2^28" for a sum: the pass at its scale again with the
+                // scalar 64-bit error term.  (Coefficients that can wrap went through the reference's loop: sum_exact.)
+                uint64_t total = o.r.total;
+                if (o.fin != 0 && needs_exact_sum(total, o.sum_exact != 0))
+                    total = pass_fast_core_wide(xw, hpk, R.mp, c0, c1, o.final_sp).total;
+                winner = argmin64(total, o.fin != 0);
+            }
             commit(o.r, o.final_sp, winner);
         } else
             commit(r, final_sp, winner32);
@@ -769,8 +775,8 @@ __device__ __forceinline__ void gc_encode_piece(
     }
     if (seg_state && !repair && live && l16 == 0) {   // one lane per channel
         int16_t *st = seg_state + ((int64_t)by * nch + ch) * 2;
-        st[0] = (int16_t)h0;
-        st[1] = (int16_t)h1;
+        st[0] = (int16_t)pair_lo(hpk);
+        st[1] = (int16_t)pair_hi(hpk);
     }
     if (lane == 0) {
         atomicAdd(&g_vga_gc_stats[3], (unsigned long long)frames_wg);
@@ -887,10 +893,12 @@ __device__ __forceinline__ void seam_run(const int16_t *__restrict__ src, uint8_
         bool fin = true;                               // LPC = 16: this lane's pass is the one the reference ends on
         if (LPC == 8) {
         // (the passes as they always were: without the f32 detour -- tried in round 5 -- a seam run is no faster, LABNOTES 9.7)
-        const PassOut rb = pass_fast_core(x, hpk, mp, c0, c1, sp_b);
-        const PassOut ra = pass_fast_core(x, hpk, mp, c0, c1, sp_a);
+        // (at the cap from overflow 3 on, not 4 as until round 8: the sum in pairs is exact whatever its size only up to
+        // overflow 2 there -- gc_encode_core.hpp E5 -- and this loop hands it to a 64-bit argmin as it is)
+        const PassOut rb = pass_fast_core(w, hpk, mp, c0, c1, sp_b);
+        const PassOut ra = pass_fast_core(w, hpk, mp, c0, c1, sp_a);
         const bool cap_a = sp_a >= 12, cap_b = sp_b >= 12;
-        const bool rare = !coef_ok || (unsigned)ra.max_overflow > (cap_a ? 3u : 248u) || (unsigned)rb.max_overflow > (cap_b ? 3u : 248u);
+        const bool rare = !coef_ok || (unsigned)ra.max_overflow > (cap_a ? 2u : 248u) || (unsigned)rb.max_overflow > (cap_b ? 2u : 248u);
         const int eff_a = cap_a ? 0 : ra.max_overflow, eff_b = cap_b ? 0 : rb.max_overflow;
         const bool fin_a = eff_a < 2;
         const bool resume = !fin_a && eff_b >= 2;
@@ -913,9 +921,9 @@ __device__ __forceinline__ void seam_run(const int16_t *__restrict__ src, uint8_
             // them the reference's loop ends on (encode_frame, CPW = 4); anything else -- both overflowed, a bump, an inexact
             // sum, hostile coefficients -- and the A lane walks the reference's loop as written, the B lane is out
             final_sp = cand_b ? sp_b : sp_a;
-            r = pass_fast_core(x, hpk, mp, c0, c1, final_sp);
+            r = pass_fast_core(w, hpk, mp, c0, c1, final_sp);
             const bool cap = final_sp >= 12;
-            const bool rare_mine = !coef_ok || (unsigned)r.max_overflow > (cap ? 3u : 248u);
+            const bool rare_mine = !coef_ok || (unsigned)r.max_overflow > (cap ? 2u : 248u);
             const int eff = cap ? 0 : r.max_overflow;
             const int eff_other = dpp<DPP_QUAD_XOR1>(eff);
             // (the exchange on its own line: behind `rare_mine ||` it would run only in the lanes whose own flag is clear, and
@@ -995,10 +1003,12 @@ __device__ __forceinline__ void encode_tail_frame(const int16_t *__restrict__ sr
         if (s1 == -100) s1 = first_scale_power_from_md(prescan_sequential(x, c0, c1));
     }
     const int sp_a = imin(s1, 12), sp_b = imin(s1 + 1, 12);
-    const PassOut rb = pass_fast_core(x, hpk, mp, c0, c1, sp_b);
-    const PassOut ra = pass_fast_core(x, hpk, mp, c0, c1, sp_a);
+    uint32_t w[7];
+    pack_row(x, w);
+    const PassOut rb = pass_fast_core(w, hpk, mp, c0, c1, sp_b);
+    const PassOut ra = pass_fast_core(w, hpk, mp, c0, c1, sp_a);
     const bool cap_a = sp_a >= 12, cap_b = sp_b >= 12;
-    const bool rare = !coef_ok || (unsigned)ra.max_overflow > (cap_a ? 3u : 248u) || (unsigned)rb.max_overflow > (cap_b ? 3u : 248u);
+    const bool rare = !coef_ok || (unsigned)ra.max_overflow > (cap_a ? 2u : 248u) || (unsigned)rb.max_overflow > (cap_b ? 2u : 248u);   // (2: as seam_run)
     const int eff_a = cap_a ? 0 : ra.max_overflow, eff_b = cap_b ? 0 : rb.max_overflow;
     const bool fin_a = eff_a < 2;
     const bool resume = !fin_a && eff_b >= 2;
