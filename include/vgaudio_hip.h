@@ -160,7 +160,11 @@ void encodeFrame(int16_t *src, uint8_t *dst, int16_t *coefs, uint8_t one);
 /* ---- device-resident GC-ADPCM (inputs/outputs already in HBM) ----------
  * d_pcm: planar, channel c at d_pcm + c*pcm_pitch (pitch in samples, even,
  * base 4-byte aligned).  d_adpcm: channel c at d_adpcm + c*adpcm_pitch
- * (bytes, multiple of 8, base 8-byte aligned).  stream: hipStream_t. */
+ * (bytes, multiple of 8, base 8-byte aligned).  Nothing more is required
+ * (no 16-byte alignment: the kernels choose their forms by the alignment
+ * they find) and anything less is VGA_ERR_ARGUMENT.  d_coefs (nch*16) and
+ * d_hist1 / d_hist2 (nch or NULL): any short boundary.
+ * stream: hipStream_t. */
 size_t vga_gcadpcm_coefs_workspace_bytes(int nch, int length);
 int vga_gcadpcm_coefs_device(const int16_t *d_pcm, int64_t pcm_pitch, int nch, int length,
                              int16_t *d_coefs, void *d_workspace, size_t workspace_bytes,
@@ -285,7 +289,9 @@ int vga_dsp_layout_for(const vga_dsp_params *p, int nch, vga_dsp_layout *out);
 int vga_dsp_write(const uint8_t *const *adpcm, int adpcm_len, const int16_t *coefs, const int16_t *gain,
                   const int16_t *start_context, const int16_t *loop_context, int nch, const vga_dsp_params *p,
                   uint8_t *file_out);
-/* device-resident variant: the image is assembled in HBM (d_file 8-byte aligned, layout.file_size bytes) */
+/* device-resident variant: the image is assembled in HBM (d_file 8-byte aligned, layout.file_size bytes);
+ * d_adpcm / adpcm_pitch as vga_gcadpcm_encode_device takes them (base 8-byte aligned, pitch a multiple of 8,
+ * anything less is VGA_ERR_ARGUMENT), the per-channel arrays at any short boundary */
 int vga_dsp_write_device(const uint8_t *d_adpcm, int64_t adpcm_pitch, int adpcm_len, const int16_t *d_coefs,
                          const int16_t *d_gain, const int16_t *d_start_context, const int16_t *d_loop_context,
                          int nch, const vga_dsp_params *p, uint8_t *d_file, void *stream);
@@ -584,6 +590,8 @@ typedef struct {
 /* VGA_ERR_INVALID_DATA for a missing magic, 0 or more than 2 channels, a header that ends after the audio offset,
  * reads past the end, an interleave <= 0 (DeInterleave divides by it) */
 int vga_genh_parse(const uint8_t *file, size_t size, vga_genh_info *out);
+/* images at d_files + f*file_pitch, rows of info->adpcm_bytes at d_adpcm + r*adpcm_pitch: any byte, any pitch
+ * that holds an image / a row */
 int vga_genh_read_device(const vga_genh_info *info, const uint8_t *d_files, int64_t file_pitch, int nfiles, uint8_t *d_adpcm,
                          int64_t adpcm_pitch, void *stream);
 int vga_genh_read(const uint8_t *file, size_t size, const vga_genh_info *info, uint8_t *const *adpcm_out);
@@ -638,7 +646,20 @@ int vga_adx_encode_batch_v(const int16_t *const *pcm, const int *pcm_lengths, in
                            uint8_t *const *out, int16_t *history_out);
 int vga_adx_decode_batch_v(const uint8_t *const *adpcm, const int *adpcm_lengths, int nch, const int *sample_counts,
                            const vga_adx_params *params, int16_t *const *pcm_out);
-/* device-resident variants (pitches: pcm in samples, bytes for ADX data and even) */
+/* device-resident variants.  Layout contract (what the calls validate; tests/test_gpu_device_layouts.py
+ * runs it):
+ *   PCM rows (both calls): channel c at d_pcm + c*pcm_pitch, pitch in samples, >= the length; any sample
+ *     boundary, any pitch.
+ *   vga_adx_encode_device: d_out and out_pitch (bytes) even, out_pitch >= vga_adx_encoded_byte_count();
+ *     d_history_out: nch shorts or NULL.  An odd d_out or out_pitch -> VGA_ERR_ARGUMENT.
+ *   vga_adx_decode_device: d_adpcm and in_pitch (bytes, >= adpcm_length) at any byte.
+ * Which kernels run: 18-byte frames with a padding of 0..64 samples take the time-piece kernels (the ones
+ * bench.py measures) only when the PCM rows are 16-byte aligned (d_pcm % 16 == 0, pcm_pitch % 8 == 0) and
+ * the ADX rows 4-byte aligned (base and pitch % 4 == 0).  Every other layout -- like every other frame
+ * size -- is served by one lane per channel walking its stream serially: the same bytes, but about 60
+ * times slower at BASELINE configs[2] by DESIGN.md 4.3's figure for that kernel (measured for other frame
+ * sizes on aligned rows; NOT measured for a call that lands there by alignment).  A caller who slices rows
+ * out of a larger batch should keep pitches at multiples of 8 samples / 4 bytes. */
 int vga_adx_encode_device(const int16_t *d_pcm, int64_t pcm_pitch, int nch, int pcm_length,
                           const vga_adx_params *p, uint8_t *d_out, int64_t out_pitch,
                           int16_t *d_history_out, void *stream);
@@ -789,8 +810,13 @@ int vga_hca_encode_batch_v(const int16_t *const *pcm, int nstreams, const vga_hc
 int vga_hca_decode_batch_v(const vga_hca_info *infos, const uint8_t *const *frames, int nstreams,
                            int16_t *const *pcm_out);
 /* device-resident variants: pcm stream s / channel c at d_pcm + s*stream_pitch + c*ch_pitch (samples);
- * frames of stream s at d_frames + s*frames_pitch (even; decode: 4-byte aligned with >= 8 bytes of
- * slack after frame_count*frame_size).  *d_status receives flag bits (16 internal: cost table; 1 bad sync, 2 bad scale-factor
+ * any sample boundary, any ch_pitch >= the length, any stream_pitch >= channel_count*ch_pitch (it need
+ * not be a multiple of ch_pitch); frames of stream s at d_frames + s*frames_pitch.
+ * Encode: d_frames at ANY byte, frames_pitch even (an odd one -> VGA_ERR_ARGUMENT); frames then begin at
+ * any byte and are stored as aligned dwords plus lead and tail bytes.
+ * Decode: d_frames and frames_pitch multiples of 4 with >= 8 bytes of slack after frame_count*frame_size
+ * (anything else -> VGA_ERR_ARGUMENT; the slack's contents do not matter).
+ * *d_status receives flag bits (16 internal: cost table; 1 bad sync, 2 bad scale-factor
  * delta, 4 bitrate too low, 8 boundary search failed). */
 size_t vga_hca_decode_workspace_bytes(const vga_hca_info *info, int nstreams);
 int vga_hca_encode_device(const int16_t *d_pcm, int64_t stream_pitch, int64_t ch_pitch, int nstreams,
@@ -904,7 +930,8 @@ int vga_adx_key_from_code(uint64_t key_code, vga_adx_key *out);          /* CriA
 int vga_adx_key_from_string(const char *key_string, vga_adx_key *out);   /* CriAdxKey(string), ASCII */
 uint64_t vga_adx_key_code(const vga_adx_key *key);                       /* CriAdxKey.KeyCode */
 /* EncryptDecrypt (its own inverse for type 8; type 9 also masks the first header byte), in place.
- * audio_len must be whole frames. */
+ * audio_len must be whole frames.  The *_device forms of this section take their rows at any byte and
+ * any pitch >= the row's length; bytes behind a row's length are left alone. */
 int vga_adx_crypt(uint8_t *const *audio, int audio_len, int nch, const vga_adx_key *key, int encryption_type,
                   int frame_size);
 int vga_adx_crypt_device(uint8_t *d_audio, int64_t audio_pitch, int audio_len, int nch, const vga_adx_key *key,

@@ -138,6 +138,12 @@ int vga_testing_hca_decode_v_stats(long long *out, int n);
  * change.  Returns the previous setting. */
 int vga_testing_adx_read_general_this_thread(int on);
 
+/* Which kernel form the ADX launchers took for the last vga_adx_encode_device / vga_adx_decode_device call (or
+ * host-pointer chunk) made FROM THE CALLING THREAD: 0 = none yet, 1 = the time-piece kernels (18-byte frames on the
+ * layout include/vgaudio_hip.h names next to those calls), 2 = the general lane-per-channel kernel.  Either pointer
+ * may be null.  Host state only: the call allocates and launches nothing.  Returns 0. */
+int vga_testing_adx_last_path_this_thread(int *encode, int *decode);
+
 /* Poison mode for every allocation the library makes.  The device pool of the host-pointer entry points hands a parked block
  * of 1 MiB or more to any later request of half its size or more with the last call's bytes in it, the page-locked pool any
  * idle block that is large enough, and the stream-ordered scratch of the device entry points is recycled by the runtime's

@@ -260,6 +260,7 @@ SIGNATURES = {
     "vga_hca_read_device": (ci, [vp, vp, i64, ci, vp, i64, vp, vp]),
     "vga_hca_read": (ci, [u8p, C.c_size_t, vp, u8p, C.POINTER(ci)]),
     "vga_testing_adx_read_general_this_thread": (ci, [ci]),
+    "vga_testing_adx_last_path_this_thread": (ci, [C.POINTER(ci), C.POINTER(ci)]),
     "vga_gcadpcm_channel_layout_for": (ci, [vp, vp]),
     "vga_gcadpcm_build_channels_batch": (ci, [u8pp, i16p, ci, vp, u8pp, i16pp, i16pp, i16p]),
     "vga_gcadpcm_build_channels_workspace_bytes": (C.c_size_t, [ci, vp]),

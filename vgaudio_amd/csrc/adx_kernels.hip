@@ -1091,6 +1091,7 @@ int launch_encode(const int16_t *d_pcm, int64_t pcm_pitch, int nch, int pcm_leng
     const bool fast = p.frame_size == 18 && p.padding >= 0 && p.padding <= 64 && (pcm_pitch % 8) == 0 && ((uintptr_t)d_pcm % 16) == 0 &&
                       (out_pitch % 4) == 0 && ((uintptr_t)d_out % 4) == 0 && std::abs((int)p.coef0) <= 16384 &&
                       std::abs((int)p.coef1) <= 16384;
+    note_adx_encode_path(fast ? 1 : 2);
     if (fast) {
         d_pcm -= p.padding;                            // from here on d_pcm / pcm_length are the STREAM's
         pcm_length += p.padding;
@@ -1171,6 +1172,7 @@ int launch_decode(const uint8_t *d_adpcm, int64_t in_pitch, int nch, int sample_
     // (padded streams: up to two frames of padding, equal-length batches, at least two frames of output)
     const bool fast = p.frame_size == 18 && (p.padding == 0 || (p.padding > 0 && p.padding <= 64 && !d_own_samples && sample_count >= 64)) &&
                       (pcm_pitch % 8) == 0 && ((uintptr_t)d_pcm % 16) == 0 && (in_pitch % 4) == 0 && ((uintptr_t)d_adpcm % 4) == 0;
+    note_adx_decode_path(fast ? 1 : 2);
     if (fast) {
         if (p.padding > 0) {
             // The reference reads ceil(sampleCount / 32) frames from the frame the padding ends in and takes 32 - padding % 32

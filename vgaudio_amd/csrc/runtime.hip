@@ -50,6 +50,10 @@ int coefs_kernel_variant() { return g_settings.coefs_variant; }
 int encoder_segments_override() { return g_settings.encoder_segments; }
 int encoder_persistent_mode() { return g_settings.encoder_persistent; }
 int hca_frames_per_group_override() { return g_settings.hca_frames_per_group; }
+// not a setting but a record: what the calling thread's last ADX launches chose (0 = none yet)
+static thread_local int g_adx_encode_path = 0, g_adx_decode_path = 0;
+void note_adx_encode_path(int path) { g_adx_encode_path = path; }
+void note_adx_decode_path(int path) { g_adx_decode_path = path; }
 
 // The host pipeline runs an upload stream, a download stream and two lanes of kernels next to whatever streams the host
 // has; the HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (the runtime's default of four unless the
@@ -176,6 +180,12 @@ int vga_testing_hca_frames_per_group_this_thread(int frames)
     const int old = g_settings.hca_frames_per_group;
     g_settings.hca_frames_per_group = frames > 0 ? frames : 0;
     return old;
+}
+int vga_testing_adx_last_path_this_thread(int *encode, int *decode)
+{
+    if (encode) *encode = g_adx_encode_path;
+    if (decode) *decode = g_adx_decode_path;
+    return 0;
 }
 void vga_testing_host_pipeline_this_thread(int feeders, int drainers, int chunk_units, int slot_bytes)
 {
