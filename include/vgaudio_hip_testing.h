@@ -132,6 +132,12 @@ int vga_testing_hca_decode_classes(const void *infos, int nstreams, int *class_o
  * launched (the sum over the chunks of streams x the chunk's longest frame_count; a slot behind a stream's own frames does
  * no work).  Writes min(n, 5) fields and returns 5. */
 int vga_testing_hca_decode_v_stats(long long *out, int n);
+/* A packed batch (vgaudio_hip/hca_ragged.h; ragged: a vga_hca_ragged): [0] own frames (the sum of the streams' frame_count)
+ * [1] scan slots launched (own frames rounded up to the 64 lanes of a wave: no slot lies behind a stream's frames) [2]
+ * workgroups of the decoder's second kernel [3] runs in its table (one workgroup each; streams without samples have none).
+ * Host state of the object at the launcher's own frames per run: the call launches nothing.  Writes min(n, 4) fields and
+ * returns 4. */
+int vga_testing_hca_ragged_stats(const void *ragged, long long *out, int n);
 
 /* The ADX file reader (vga_adx_read_device) moves 18-byte frames with a kernel of 16-byte vectors when the rows are 16-byte
  * aligned.  on != 0 sends calls made from the calling thread to the general de-interleave instead; the bytes must not

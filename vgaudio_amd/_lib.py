@@ -183,6 +183,15 @@ SIGNATURES = {
     "vga_testing_hca_device_info": (ci, [vp, vp, ci]),
     "vga_testing_hca_decode_classes": (ci, [vp, ci, C.POINTER(ci)]),
     "vga_testing_hca_decode_v_stats": (ci, [C.POINTER(C.c_longlong), ci]),
+    "vga_testing_hca_ragged_stats": (ci, [vp, C.POINTER(C.c_longlong), ci]),
+    "vga_hca_ragged_layout_for": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), vp]),
+    "vga_hca_ragged_create": (ci, [vp, ci, C.POINTER(vp)]),
+    "vga_hca_ragged_destroy": (None, [vp]),
+    "vga_hca_ragged_streams": (ci, [vp]),
+    "vga_hca_ragged_totals_of": (ci, [vp, vp]),
+    "vga_hca_ragged_offsets": (ci, [vp, C.POINTER(i64), C.POINTER(i64)]),
+    "vga_hca_decode_device_v": (ci, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
+    "vga_hca_encode_device_v": (ci, [vp, vp, vp, vp, vp]),
     "vga_hca_stream_create": (ci, [vp, vp, C.POINTER(vp)]),
     "vga_hca_stream_encode": (ci, [vp, vp, u8p, C.POINTER(ci)]),
     "vga_hca_stream_pending_frame_count": (ci, [vp]),

@@ -48,8 +48,8 @@ def sources():
 
 def headers():
     inc = os.path.join(HERE, "..", "include")
-    return ([os.path.join(CSRC, f) for f in os.listdir(CSRC) if not f.endswith(".hip")] +
-            [os.path.join(inc, f) for f in os.listdir(inc)] + [os.path.abspath(__file__)])
+    public = [os.path.join(d, f) for d, _, files in os.walk(inc) for f in files]
+    return ([os.path.join(CSRC, f) for f in os.listdir(CSRC) if not f.endswith(".hip")] + public + [os.path.abspath(__file__)])
 
 
 def source_hashes():

@@ -259,6 +259,82 @@ def decode_streams(streams):
     return outs
 
 
+class RaggedTotalsC(C.Structure):
+    """vga_hca_ragged_totals (include/vgaudio_hip/hca_ragged.h)"""
+    _fields_ = [("frame_bytes", C.c_int64), ("pcm_samples", C.c_int64), ("rows", C.c_int), ("total_frames", C.c_int),
+                ("decode_workspace_bytes", C.c_size_t)]
+
+
+def _infos_array(infos):
+    infos = list(infos)
+    return (_lib.HcaInfoC * max(len(infos), 1))(*[_lib.HcaInfoC.from_buffer_copy(h.c if isinstance(h, HcaInfo) else h) for h in infos]), len(infos)
+
+
+class RaggedHca:
+    """Streams of ONE shape class and any lengths, resident on the device: packed frames, packed PCM, one set of launches per
+    call (vga_hca_ragged_create, vga_hca_decode_device_v, vga_hca_encode_device_v; include/vgaudio_hip/hca_ragged.h has the
+    layout).  The tensors are the caller's torch tensors on the current device; the calls run on torch's current stream
+    and do not synchronise it.  status: int32, one word per stream, zeroed by the caller."""
+
+    @staticmethod
+    def layout(infos):
+        """(frame_offsets int64[nstreams], pcm_row_offsets int64[rows], RaggedTotalsC): host only, needs no GPU"""
+        arr, ns = _infos_array(infos)
+        rows = sum(max(arr[s].channel_count, 0) for s in range(ns))
+        fo, ro, tot = np.zeros(max(ns, 1), dtype=np.int64), np.zeros(max(rows, 1), dtype=np.int64), RaggedTotalsC()
+        i64p = C.POINTER(C.c_int64)
+        check(_lib.lib().vga_hca_ragged_layout_for(arr, ns, fo.ctypes.data_as(i64p), ro.ctypes.data_as(i64p), C.byref(tot)))
+        return fo[:ns], ro[:rows], tot
+
+    def __init__(self, infos):
+        arr, ns = _infos_array(infos)
+        self._h = C.c_void_p()
+        check(_lib.lib().vga_hca_ragged_create(arr, ns, C.byref(self._h)))
+        self.streams = _lib.lib().vga_hca_ragged_streams(self._h)
+        self.totals = RaggedTotalsC()
+        check(_lib.lib().vga_hca_ragged_totals_of(self._h, C.byref(self.totals)))
+        self.frame_offsets = np.zeros(max(ns, 1), dtype=np.int64)
+        self.pcm_row_offsets = np.zeros(max(self.totals.rows, 1), dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        check(_lib.lib().vga_hca_ragged_offsets(self._h, self.frame_offsets.ctypes.data_as(i64p), self.pcm_row_offsets.ctypes.data_as(i64p)))
+        self.frame_offsets, self.pcm_row_offsets = self.frame_offsets[:ns], self.pcm_row_offsets[:self.totals.rows]
+
+    def close(self):
+        if self._h:
+            _lib.lib().vga_hca_ragged_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    @staticmethod
+    def _stream(stream):
+        import torch
+        return C.c_void_p((stream if stream is not None else torch.cuda.current_stream()).cuda_stream)
+
+    def _need(self, t, dtype, count, what):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() >= count):
+            raise _lib.ArgumentError("%s: a contiguous %s tensor on the device of at least %d elements" % (what, dtype, count))
+
+    def decode_device(self, frames, pcm, workspace, status, stream=None):
+        """frames: uint8[totals.frame_bytes] -> pcm: int16[totals.pcm_samples]; workspace: uint8[totals.decode_workspace_bytes]"""
+        import torch
+        self._need(frames, torch.uint8, self.totals.frame_bytes, "frames")
+        self._need(pcm, torch.int16, self.totals.pcm_samples, "pcm")
+        self._need(workspace, torch.uint8, self.totals.decode_workspace_bytes, "workspace")
+        self._need(status, torch.int32, self.streams, "status")
+        check(_lib.lib().vga_hca_decode_device_v(self._h, frames.data_ptr(), pcm.data_ptr(), workspace.data_ptr(),
+                                                 workspace.numel(), status.data_ptr(), self._stream(stream)))
+
+    def encode_device(self, pcm, frames, status, stream=None):
+        """pcm: int16[totals.pcm_samples] -> frames: uint8[totals.frame_bytes]; streams that do not loop"""
+        import torch
+        self._need(pcm, torch.int16, self.totals.pcm_samples, "pcm")
+        self._need(frames, torch.uint8, self.totals.frame_bytes, "frames")
+        self._need(status, torch.int32, self.streams, "status")
+        check(_lib.lib().vga_hca_encode_device_v(self._h, pcm.data_ptr(), frames.data_ptr(), status.data_ptr(), self._stream(stream)))
+
+
 def decode_files(formats):
     """CriHcaFormat.ToPcm16 (CriHcaFormat.cs:26-32) of many files in one ragged GPU call: one Pcm16Format per CriHcaFormat."""
     formats = list(formats)

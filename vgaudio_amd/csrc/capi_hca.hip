@@ -800,6 +800,14 @@ int hca_decode_classes(const hca::DeviceInfo *dev, int n, std::vector<int> &cls)
     return (int)ids.size();
 }
 
+}  // namespace
+// used by capi_hca_ragged.hip: one object holds one shape class, and its encoder the stream map of every stream
+namespace vga { namespace hca {
+int decode_classes(const DeviceInfo *dev, int n, std::vector<int> &cls) { return hca_decode_classes(dev, n, cls); }
+int pcm_map_from(const vga_hca_info &h, int pcm_length, PcmMap &m) { return make_pcm_map(h, pcm_length, m); }
+} }
+namespace {
+
 struct HcaDecodeVCall {
     const vga_hca_info *infos = nullptr;
     const uint8_t *const *frames = nullptr;

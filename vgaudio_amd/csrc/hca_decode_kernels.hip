@@ -32,6 +32,12 @@
 // sync word would otherwise fail the call), its record slot stays unwritten and is never read; a frames workgroup whose run
 // begins there leaves before its first barrier.  RAGGED = false is the equal-length launch as it always was: the table is
 // a template parameter, not a null test, so that path pays nothing for it.
+//
+// Packed streams (vga_hca_decode_device_v, hca_kernels.hpp): the third form, HCA_PACKED.  No pitch and no slot behind a
+// stream's frames: the scan's lane g IS frame g of the batch, and finds its stream by walking on from the stream that holds
+// its wave's first frame (a table entry per wave; at most the streams that begin inside the wave are walked); a frames
+// workgroup reads its run {stream's offsets and own values, first frame, length} from a table of exactly as many runs as
+// there are workgroups.  Status bits go to the stream's own word.
 #include "common.hpp"
 #include "hca_device.hpp"
 #include "hca_decode_core.hpp"
@@ -41,6 +47,8 @@ namespace vga {
 namespace hca {
 
 size_t decode_record_bytes(const DeviceInfo &info) { return (size_t)make_decode_layout(info).record_bytes; }
+
+enum { HCA_EQUAL = 0, HCA_RAGGED = 1, HCA_PACKED = 2 };   // the kernels' MODE
 
 namespace {
 
@@ -123,11 +131,12 @@ struct StagedOut {
 
 }  // namespace
 
-template <bool RAGGED>
+template <int MODE>
 __global__ __launch_bounds__(64) void hca_scan_kernel(const uint8_t *__restrict__ frames, int64_t stream_pitch, int nstreams,
                                                       DeviceInfo info, DecodeLayout lay, uint8_t *__restrict__ records,
                                                       int *__restrict__ status, const int4 *__restrict__ dims)
 {
+    constexpr bool RAGGED = MODE == HCA_RAGGED, PACKED = MODE == HCA_PACKED;
     if constexpr (RAGGED) {            // a wave whose 64 slots all lie behind their streams' own frames: nothing to do (one wave a block)
         const int64_t g = (int64_t)blockIdx.x * 64 + threadIdx.x;
         bool any = g < (int64_t)nstreams * info.frame_count;
@@ -168,6 +177,19 @@ __global__ __launch_bounds__(64) void hca_scan_kernel(const uint8_t *__restrict_
     src.limit = (int)(stream_pitch / 4 - (a0 >> 2));
     if constexpr (RAGGED) src.limit = live ? src.limit : 0;            // an idle lane goes through the motions on zeros (the
                                                                        // wave's lanes hand their records out together, StagedOut)
+    int first_bit = (int)(a0 & 3) * 8;
+    if constexpr (PACKED) {            // the launch is "one stream" of all the batch's frames: id is the frame among them
+        const PackedScanStream *streams = reinterpret_cast<const PackedScanStream *>(dims + 1);
+        const int *first_stream = reinterpret_cast<const int *>(streams + dims[0].x);
+        int s = first_stream[blockIdx.x];
+        while ((int)id >= streams[s].first_record + streams[s].frame_count) s++;     // (id < total: the last stream ends the walk)
+        const PackedScanStream own = streams[s];
+        const int64_t b0 = (int64_t)((int)id - own.first_record) * info.frame_size;
+        src.base = reinterpret_cast<const uint32_t *>(frames + own.frames_at) + (b0 >> 2);
+        src.limit = (int)min((int64_t)INT32_MAX, own.frames_room / 4 - (b0 >> 2));
+        first_bit = (int)(b0 & 3) * 8;
+        status += own.stream;
+    }
     LdsRing ring{s_ring + lane};
     LdsRes res{s_dyn + lane};
     StagedOut<RAGGED> out;
@@ -181,7 +203,7 @@ __global__ __launch_bounds__(64) void hca_scan_kernel(const uint8_t *__restrict_
     ScanParams P;
     P.nch = info.nch;
     P.frame_bits = info.frame_size * 8;
-    P.first_bit = (int)(a0 & 3) * 8;
+    P.first_bit = first_bit;
     P.hfr_group_count = info.hfr_group_count;
     P.coded_count = s_coded;
     P.channel_type = s_type;
@@ -232,7 +254,7 @@ struct Res16 {
 
 }  // namespace
 
-template <bool RAGGED>
+template <int MODE>
 __global__ __launch_bounds__(FRAMES_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void hca_frames_kernel(
     const uint8_t *__restrict__ frames, int64_t frames_pitch, DeviceInfo info, DecodeLayout lay,
     const uint8_t *__restrict__ records, int frames_per_group, int groups_per_stream, int16_t *__restrict__ pcm,
@@ -242,7 +264,15 @@ __global__ __launch_bounds__(FRAMES_THREADS) __attribute__((amdgpu_waves_per_eu(
     // loads), and a run that begins behind the stream's last frame ends here, all threads together, before any barrier
     // (the equal-length form reads info's fields where it always did: the frames kernel sits at its register limit, and
     // where those scalar loads are issued decides what it spills)
+    constexpr bool RAGGED = MODE == HCA_RAGGED, PACKED = MODE == HCA_PACKED, OWN = MODE != HCA_EQUAL;
     int own_frames = 0, own_samples = 0, own_inserted = 0;
+    PackedRun run = {};                // PACKED: this workgroup's run (uniform: scalar loads); the other forms never read it
+    if constexpr (PACKED) {
+        run = reinterpret_cast<const PackedRun *>(dims)[blockIdx.x];
+        own_frames = run.frame_count;
+        own_samples = run.sample_count;
+        own_inserted = run.inserted_samples;
+    }
     if constexpr (RAGGED) {
         const int4 d = dims[blockIdx.x / groups_per_stream];
         own_frames = d.x;
@@ -284,12 +314,13 @@ __global__ __launch_bounds__(FRAMES_THREADS) __attribute__((amdgpu_waves_per_eu(
     const int cur_at = 8 * imdct_cur_index(tid), prev_at = 8 * imdct_prev_index(tid);
 
     const int stream = blockIdx.x / groups_per_stream;
-    const int f0 = (blockIdx.x % groups_per_stream) * frames_per_group;
-    const int f1 = min(f0 + frames_per_group, RAGGED ? own_frames : info.frame_count);
-    const uint32_t *sbase = reinterpret_cast<const uint32_t *>(frames + (int64_t)stream * frames_pitch);
-    const int64_t last_word = frames_pitch / 4 - 1;
-    const uint8_t *srec = records + (size_t)stream * info.frame_count * lay.record_bytes;
-    int16_t *spcm = pcm + (int64_t)stream * stream_pitch;
+    const int f0 = PACKED ? run.f0 : (blockIdx.x % groups_per_stream) * frames_per_group;
+    const int f1 = PACKED ? run.f0 + run.len : min(f0 + frames_per_group, RAGGED ? own_frames : info.frame_count);
+    const uint32_t *sbase = reinterpret_cast<const uint32_t *>(frames + (PACKED ? run.frames_at : (int64_t)stream * frames_pitch));
+    const int64_t last_word = (PACKED ? run.frames_room : frames_pitch) / 4 - 1;
+    const uint8_t *srec = records + (PACKED ? (size_t)run.first_record : (size_t)stream * info.frame_count) * lay.record_bytes;
+    int16_t *spcm = pcm + (PACKED ? run.pcm_at : (int64_t)stream * stream_pitch);
+    if constexpr (PACKED) ch_pitch = run.ch_pitch;
     const int frame_bits = info.frame_size * 8;
 
     // the next frame's first dwords and record, loaded a frame ahead (unconditional loads at clamped positions)
@@ -444,14 +475,54 @@ __global__ __launch_bounds__(FRAMES_THREADS) __attribute__((amdgpu_waves_per_eu(
                     const double cur = *reinterpret_cast<const double *>(chrows + slot * ROW_BYTES + cur_at);
                     const double prev = *reinterpret_cast<const double *>(chrows + pslot * ROW_BYTES + prev_at);
                     const int sample = imdct_sample(tid < 64, w_cur, w_prev, cur, prev);
-                    const int64_t tpos = (int64_t)f * SPF + sf * SPSF + tid - (RAGGED ? own_inserted : info.inserted_samples);
-                    if (tpos >= 0 && tpos < (RAGGED ? own_samples : info.sample_count)) dst[tpos] = (int16_t)sample;
+                    const int64_t tpos = (int64_t)f * SPF + sf * SPSF + tid - (OWN ? own_inserted : info.inserted_samples);
+                    if (tpos >= 0 && tpos < (OWN ? own_samples : info.sample_count)) dst[tpos] = (int16_t)sample;
                     pslot = slot;
                     slot = slot + 1 >= 9 ? 0 : slot + 1;
                 }
             }
         }
     }
+}
+
+int decode_frames_per_group(int64_t total_frames, int override_value)
+{
+    // frames per workgroup: long runs amortise the table set-up and the recomputed sub-frame before the run, short ones
+    // keep small inputs spread over the chip
+    int per_group = (int)std::min<int64_t>(MAX_FRAMES_PER_GROUP, std::max<int64_t>(1, total_frames / 8192));
+    if (override_value > 0) per_group = std::min(override_value, 64);
+    return per_group;
+}
+
+static size_t scan_lds_bytes(const DeviceInfo &info) { return (size_t)info.nch * 16 * 64 * sizeof(uint32_t); }
+static size_t frames_lds_bytes(const DeviceInfo &info, const DecodeLayout &lay)
+{
+    return (size_t)info.nch * 9 * ROW_BYTES + (size_t)info.nch * 128 * 9 + (size_t)((lay.frame_dwords + 1 + 3) / 4 * 4) * 4 +
+           (size_t)lay.record_bytes;
+}
+
+int launch_decode_packed(const uint8_t *d_frames, const DeviceInfo &cls, int total_frames, const void *d_scan_table,
+                         const PackedRun *d_runs, int nruns, int16_t *d_pcm, void *d_workspace, int *d_status, hipStream_t stream)
+{
+    if (total_frames <= 0) return VGA_OK;
+    DeviceInfo info = cls;             // the scan indexes "one stream" of all the batch's frames
+    info.frame_count = total_frames;
+    info.sample_count = info.inserted_samples = 0;
+    const DecodeLayout lay = make_decode_layout(info);
+    uint8_t *records = reinterpret_cast<uint8_t *>(d_workspace);
+    const size_t lds1 = scan_lds_bytes(info);
+    if (lds1 > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_scan_kernel<HCA_PACKED>, lds1));
+    hipLaunchKernelGGL(hca_scan_kernel<HCA_PACKED>, dim3((unsigned)((total_frames + 63) / 64)), dim3(64), lds1, stream, d_frames,
+                       (int64_t)0, 1, info, lay, records, d_status, reinterpret_cast<const int4 *>(d_scan_table));
+    if (nruns > 0) {
+        const size_t lds2 = frames_lds_bytes(info, lay);
+        if (lds2 > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_frames_kernel<HCA_PACKED>, lds2));
+        hipLaunchKernelGGL(hca_frames_kernel<HCA_PACKED>, dim3((unsigned)nruns), dim3(FRAMES_THREADS), lds2, stream, d_frames,
+                           (int64_t)0, info, lay, reinterpret_cast<const uint8_t *>(records), 0, 1, d_pcm, (int64_t)0, (int64_t)0,
+                           reinterpret_cast<const int4 *>(d_runs));
+    }
+    VGA_HIP_TRY(hipGetLastError());
+    return VGA_OK;
 }
 
 int launch_decode(const uint8_t *d_frames, int64_t frames_pitch, int nstreams, const DeviceInfo &info, int16_t *d_pcm,
@@ -461,8 +532,8 @@ int launch_decode(const uint8_t *d_frames, int64_t frames_pitch, int nstreams, c
     const DecodeLayout lay = make_decode_layout(info);
     const int64_t total = (int64_t)nstreams * info.frame_count;
     uint8_t *records = reinterpret_cast<uint8_t *>(d_workspace);
-    const size_t lds1 = (size_t)info.nch * 16 * 64 * sizeof(uint32_t);
-    const auto scan = d_dims ? hca_scan_kernel<true> : hca_scan_kernel<false>;
+    const size_t lds1 = scan_lds_bytes(info);
+    const auto scan = d_dims ? hca_scan_kernel<HCA_RAGGED> : hca_scan_kernel<HCA_EQUAL>;
     if (lds1 > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(scan, lds1));
     hipLaunchKernelGGL(scan, dim3((unsigned)((total + 63) / 64)), dim3(64), lds1, stream, d_frames, frames_pitch, nstreams, info,
                        lay, records, d_status, d_dims);
@@ -475,15 +546,10 @@ int launch_decode(const uint8_t *d_frames, int64_t frames_pitch, int nstreams, c
     // the first half's frames launch -- 24.7 ms, the same as back to back: the frames launch leaves the scan's waves no room.
     const int hook = hca_frames_per_group_override();
     const int group_override = hook >= 1000 ? hook - 1000 : hook;
-    // frames per workgroup: long runs amortise the table set-up and the recomputed sub-frame before the run, short ones
-    // keep small inputs spread over the chip
-    int per_group = (int)std::min<int64_t>(MAX_FRAMES_PER_GROUP, std::max<int64_t>(1, total / 8192));
-    if (group_override > 0) per_group = std::min(group_override, 64);
-    per_group = std::min(per_group, info.frame_count);
+    const int per_group = std::min(decode_frames_per_group(total, group_override), info.frame_count);
     const int groups = (info.frame_count + per_group - 1) / per_group;
-    const size_t lds2 = (size_t)info.nch * 9 * ROW_BYTES + (size_t)info.nch * 128 * 9 +
-                        (size_t)((lay.frame_dwords + 1 + 3) / 4 * 4) * 4 + (size_t)lay.record_bytes;
-    const auto run_frames = d_dims ? hca_frames_kernel<true> : hca_frames_kernel<false>;
+    const size_t lds2 = frames_lds_bytes(info, lay);
+    const auto run_frames = d_dims ? hca_frames_kernel<HCA_RAGGED> : hca_frames_kernel<HCA_EQUAL>;
     if (lds2 > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(run_frames, lds2));
     hipLaunchKernelGGL(run_frames, dim3((unsigned)((int64_t)nstreams * groups)), dim3(FRAMES_THREADS), lds2, stream, d_frames,
                        frames_pitch, info, lay, reinterpret_cast<const uint8_t *>(records), per_group, groups, d_pcm, stream_pitch,

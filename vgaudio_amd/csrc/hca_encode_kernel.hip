@@ -45,11 +45,26 @@ constexpr int MAX_ENC_FRAMES_PER_GROUP = 16;
 }  // namespace
 
 // LDS gives six workgroups = three waves per SIMD; the hint keeps hipcc at the 168 VGPRs that fit (it takes 171 otherwise)
+// PACKED (vga_hca_encode_device_v, hca_kernels.hpp): the workgroup's run of frames, its stream's rows, length and status word
+// come from runs[blockIdx.x] instead of the pitches; the stream map is that of a stream that does not loop.
+template <bool PACKED>
 __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void hca_encode_kernel(
     const int16_t *__restrict__ pcm, int64_t stream_pitch, int64_t ch_pitch, int frames_per_group, int groups_per_stream, PcmMap map,
     DeviceInfo info, uint8_t *__restrict__ frames, int64_t frames_pitch, const uint16_t *__restrict__ crc_pow,
-    int *__restrict__ status, int first_frame, int end_frame)
+    int *__restrict__ status, int first_frame, int end_frame, const PackedRun *__restrict__ runs)
 {
+    PackedRun run = {};
+    if constexpr (PACKED) {
+        run = runs[blockIdx.x];
+        map.zero_pre = run.zero_pre;
+        map.pre_end = run.inserted_samples - SPSF;
+        map.main_end = map.pre_end + run.sample_count;
+        map.post_end = map.main_end;                           // (not looping: _postAudio is all zero)
+        map.loop_start = map.last_chunk = 0;
+        map.raw_len = run.sample_count;
+        ch_pitch = run.ch_pitch;
+        status += run.stream;
+    }
     extern __shared__ __attribute__((aligned(16))) double s_mem[];
     __shared__ EncTab T;
     __shared__ CostLut Q;
@@ -115,8 +130,8 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(3, 
     const double w_d = (double)__uint_as_float(HCA_MdctWindowF32Bits[127 - wi]);
 
     const int stream = blockIdx.x / groups_per_stream;
-    const int f0 = first_frame + (blockIdx.x % groups_per_stream) * frames_per_group;     // frames [first_frame, end_frame) of every stream
-    const int f1 = min(f0 + frames_per_group, end_frame);
+    const int f0 = PACKED ? run.f0 : first_frame + (blockIdx.x % groups_per_stream) * frames_per_group;     // frames [first_frame, end_frame) of every stream
+    const int f1 = PACKED ? run.f0 + run.len : min(f0 + frames_per_group, end_frame);
     const int available = info.frame_size * 8;
     const bool small = nch <= 2;
 
@@ -152,7 +167,7 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(3, 
     // both channels (k = 0..8), packed into nine registers -- and does so for the NEXT frame while this frame's bit
     // allocation and packing run, so that the HBM latency is off the frame's critical path.
     int16_t *xin = reinterpret_cast<int16_t *>(costs);                        // [nch][9 * 128]
-    const int16_t *spcm = pcm + (int64_t)stream * stream_pitch;
+    const int16_t *spcm = pcm + (PACKED ? run.pcm_at : (int64_t)stream * stream_pitch);
     // 9 x 128 int16 per channel = 576 dwords; lane `tid` moves dwords tid + 128 k of the [channel][576] array (k = 0..8 for
     // two channels, 0..4 for one): nine independent dword loads, nine registers, nothing to unpack
     uint32_t pk[9];
@@ -747,7 +762,7 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(3, 
         // ---- store the frame: whole aligned dwords (the frame starts at any byte: its k-th dword is a funnel shift of two
         // big-endian words of fbuf), the few bytes before the first and after the last aligned dword one by one
         {
-            uint8_t *dst = frames + (int64_t)stream * frames_pitch + (int64_t)frame * info.frame_size;
+            uint8_t *dst = frames + (PACKED ? run.frames_at : (int64_t)stream * frames_pitch) + (int64_t)frame * info.frame_size;
             const int lead = (int)((4 - (reinterpret_cast<uintptr_t>(dst) & 3)) & 3);       // bytes before the first aligned dword
             const int ndw = (info.frame_size - lead) / 4;
             auto byte_at = [&](int b) { return (fbuf[b >> 2] >> (24 - 8 * (b & 3))) & 0xFFu; };
@@ -766,6 +781,41 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(3, 
     }
 }
 
+static size_t encode_lds_bytes(const DeviceInfo &info)
+{
+    const int nch = info.nch;
+    const size_t doubles = (size_t)nch * 8 * RS + (size_t)nch * 16;
+    const size_t ints = 8 + 8 + 8 + 8 + 3 * (size_t)nch * 8;
+    return doubles * 8 + (size_t)nch * 128 * 16 + ints * 4 + (size_t)((((info.frame_size + 3) / 4 + 3) & ~1) * 4) + (size_t)nch * 256;
+}
+
+// frames per run of a launch of total_frames frames, and which kernel takes it.  hook: vga_testing_hca_frames_per_group_this_thread
+// (n > 0 = frames per run / group, 1000 + n = this file's workgroup-per-run kernel whatever the channel count)
+int encode_frames_per_run(const DeviceInfo &info, int64_t total_frames, int hook, bool *wave_kernel)
+{
+    *wave_kernel = hook < 1000 && encode_wave_kernel_takes(info);
+    if (*wave_kernel) return encode_wave_frames_per_run(total_frames, hook);
+    const int group_override = hook >= 1000 ? hook - 1000 : hook;
+    // frames per workgroup: long runs amortise the per-workgroup set-up (tables, twiddles), short ones keep small inputs
+    // spread over the chip
+    int per_group = (int)std::min<int64_t>(MAX_ENC_FRAMES_PER_GROUP, std::max<int64_t>(1, total_frames / 8192));
+    if (group_override > 0) per_group = std::min(group_override, 64);
+    return per_group;
+}
+
+int launch_encode_packed(const int16_t *d_pcm, const DeviceInfo &info, const PackedRun *d_runs, int nruns, bool wave_runs,
+                         uint8_t *d_frames, const uint16_t *d_crc_pow, int *d_status, hipStream_t stream)
+{
+    if (nruns <= 0) return VGA_OK;
+    if (wave_runs) return launch_encode_wave_packed(d_pcm, info, d_runs, nruns, d_frames, d_crc_pow, d_status, stream);
+    const size_t lds = encode_lds_bytes(info);
+    if (lds > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_encode_kernel<true>, lds));
+    hipLaunchKernelGGL(hca_encode_kernel<true>, dim3((unsigned)nruns), dim3(ENC_THREADS), lds, stream, d_pcm, (int64_t)0, (int64_t)0, 0,
+                       1, PcmMap{}, info, d_frames, (int64_t)0, d_crc_pow, d_status, 0, 0, d_runs);
+    VGA_HIP_TRY(hipGetLastError());
+    return VGA_OK;
+}
+
 int launch_encode(const int16_t *d_pcm, int64_t stream_pitch, int64_t ch_pitch, int nstreams, const PcmMap &map,
                   const DeviceInfo &info, uint8_t *d_frames, int64_t frames_pitch, const uint16_t *d_crc_pow,
                   int *d_status, hipStream_t stream, int first_frame, int frame_limit)
@@ -776,28 +826,20 @@ int launch_encode(const int16_t *d_pcm, int64_t stream_pitch, int64_t ch_pitch, 
     const int end_frame = frame_limit < 0 ? info.frame_count : std::min(info.frame_count, first_frame + frame_limit);
     if (nstreams <= 0 || first_frame < 0 || end_frame <= first_frame) return VGA_OK;
     const int frame_span = end_frame - first_frame;
-    const int nch = info.nch;
     // test hook (vga_testing_hca_frames_per_group_this_thread): n > 0 = frames per run / group, 1000 + n = this file's
     // workgroup-per-run kernel whatever the channel count (n = 0: its default run length)
     const int hook = hca_frames_per_group_override();
     if (hook < 1000 && encode_wave_kernel_takes(info))
         return launch_encode_wave(d_pcm, stream_pitch, ch_pitch, nstreams, map, info, d_frames, frames_pitch, d_crc_pow, d_status, stream,
                                   first_frame, end_frame, hook);
-    const int group_override = hook >= 1000 ? hook - 1000 : hook;
-    const size_t doubles = (size_t)nch * 8 * RS + (size_t)nch * 16;
-    const size_t ints = 8 + 8 + 8 + 8 + 3 * (size_t)nch * 8;
-    const size_t lds = doubles * 8 + (size_t)nch * 128 * 16 + ints * 4 + (size_t)((((info.frame_size + 3) / 4 + 3) & ~1) * 4) + (size_t)nch * 256;
-    if (lds > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_encode_kernel, lds));
-    // frames per workgroup: long runs amortise the per-workgroup set-up (tables, twiddles), short ones keep small inputs
-    // spread over the chip
-    const int64_t total = (int64_t)nstreams * frame_span;
-    int per_group = (int)std::min<int64_t>(MAX_ENC_FRAMES_PER_GROUP, std::max<int64_t>(1, total / 8192));
-    if (group_override > 0) per_group = std::min(group_override, 64);
-    per_group = std::min(per_group, frame_span);
+    const size_t lds = encode_lds_bytes(info);
+    if (lds > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_encode_kernel<false>, lds));
+    bool wave_kernel = false;
+    const int per_group = std::min(encode_frames_per_run(info, (int64_t)nstreams * frame_span, hook, &wave_kernel), frame_span);
     const int groups = (frame_span + per_group - 1) / per_group;
-    hipLaunchKernelGGL(hca_encode_kernel, dim3((unsigned)((int64_t)nstreams * groups)), dim3(ENC_THREADS), lds, stream,
+    hipLaunchKernelGGL(hca_encode_kernel<false>, dim3((unsigned)((int64_t)nstreams * groups)), dim3(ENC_THREADS), lds, stream,
                        d_pcm, stream_pitch, ch_pitch, per_group, groups, map, info, d_frames, frames_pitch, d_crc_pow, d_status,
-                       first_frame, end_frame);
+                       first_frame, end_frame, (const PackedRun *)nullptr);
     VGA_HIP_TRY(hipGetLastError());
     return VGA_OK;
 }

@@ -101,6 +101,7 @@ struct WaveArgs {
     int frames_per_run, runs_per_stream, total_runs, first_frame, end_frame, wave_bytes;
     PcmMap map;
     DeviceInfo info;
+    const PackedRun *runs;             // PACKED: total_runs entries, one per wave (hca_kernels.hpp); the pitches and map are unused
 };
 typedef const __attribute__((address_space(4))) WaveArgs *ColdArgs;
 __device__ __forceinline__ ColdArgs cold_args()
@@ -214,16 +215,28 @@ __device__ __forceinline__ int find_scale_factor_lut(const WaveShared &S, double
 
 }  // namespace
 
-template <int NCH>
+// the status word of the wave's stream (cold: the run is read again rather than kept through the frame loop)
+template <bool PACKED>
+__device__ __forceinline__ int *wave_status_word(int run)
+{
+    ColdArgs k = cold_args();
+    int *status = k->status;
+    if constexpr (PACKED)
+        if (status) status += k->runs[run].stream;
+    return status;
+}
+
+template <int NCH, bool PACKED>
 __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(VGA_HCA_WAVE_EU))) void hca_encode_wave_kernel(const WaveArgs args)
 {
     using Lay = Layout<NCH>;
     constexpr int PT = Lay::PT;
     const int16_t *__restrict__ pcm = args.pcm;
     uint8_t *__restrict__ frames = args.frames;
-    const int64_t stream_pitch = args.stream_pitch, ch_pitch = args.ch_pitch, frames_pitch = args.frames_pitch;
+    const int64_t stream_pitch = args.stream_pitch, frames_pitch = args.frames_pitch;
+    int64_t ch_pitch = args.ch_pitch;
     const int frame_size = args.info.frame_size, hfr_group_count = args.info.hfr_group_count;
-    const int map_pre_end = args.map.pre_end, map_main_end = args.map.main_end;
+    int map_pre_end = args.map.pre_end, map_main_end = args.map.main_end;
     extern __shared__ __attribute__((aligned(16))) char s_dyn[];
     __shared__ WaveShared S;
     const int tid = threadIdx.x;
@@ -270,7 +283,10 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(VGA_
     }
     __syncthreads();
     if (S.bad || !cost_lut_build<WG_THREADS>(S.Q, reinterpret_cast<double *>(s_dyn), tid)) {       // (s_dyn: nothing lives there before the first frame)
-        if (tid == 0 && cold_args()->status) atomicOr(cold_args()->status, 16);
+        if constexpr (PACKED) {                             // every stream of the launch that has a run in this workgroup
+            const int r = blockIdx.x * WG_WAVES + wave;
+            if (lane0 == 0 && r < args.total_runs && wave_status_word<true>(r)) atomicOr(wave_status_word<true>(r), 16);
+        } else if (tid == 0 && cold_args()->status) atomicOr(cold_args()->status, 16);
         return;
     }
     __syncthreads();
@@ -279,9 +295,20 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(VGA_
 
     const int run = blockIdx.x * WG_WAVES + wave;
     if (run >= args.total_runs) return;
-    const int stream = run / args.runs_per_stream;
-    const int f0 = args.first_frame + (run % args.runs_per_stream) * args.frames_per_run;   // frames [first_frame, end_frame) of every stream
-    const int f1 = min(f0 + args.frames_per_run, args.end_frame);
+    const int stream = PACKED ? 0 : run / args.runs_per_stream;
+    int f0 = args.first_frame + (run % args.runs_per_stream) * args.frames_per_run;   // frames [first_frame, end_frame) of every stream
+    int f1 = min(f0 + args.frames_per_run, args.end_frame);
+    int64_t packed_pcm_at = 0, packed_frames_at = 0;
+    if constexpr (PACKED) {            // the wave's own run: uniform, read once
+        const PackedRun *r = args.runs + __builtin_amdgcn_readfirstlane(run);
+        f0 = r->f0;
+        f1 = r->f0 + r->len;
+        packed_pcm_at = r->pcm_at;
+        packed_frames_at = r->frames_at;
+        ch_pitch = r->ch_pitch;
+        map_pre_end = r->inserted_samples - SPSF;
+        map_main_end = map_pre_end + r->sample_count;
+    }
 
     char *rows = s_dyn + (size_t)wave * args.wave_bytes;                 // eight transform rows; later the turned codes + the frame's bits
     uint32_t *fbuf = reinterpret_cast<uint32_t *>(rows + Lay::CODES_BYTES);
@@ -300,7 +327,7 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(VGA_
     // x^(8 k) mod P for the k bytes that follow this lane's chunk of the frame
     const unsigned crc_shift = lane0 * crc_chunk < nbytes ? args.crc_pow[nbytes - min(lane0 * crc_chunk + crc_chunk, nbytes)] : 0u;
 
-    const int16_t *spcm = pcm + (int64_t)stream * stream_pitch;
+    const int16_t *spcm = pcm + (PACKED ? packed_pcm_at : (int64_t)stream * stream_pitch);
     for (int frame = f0; frame < f1; frame++) {
         // sample 64 k + lane of the frame's window (its 1024 samples and the 128 before them), k = 0..17: channel 0 in the low
         // half, channel 1 in the high half -- straight from the caller's PCM when the whole window lies inside it (every
@@ -331,6 +358,15 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(VGA_
                 map.loop_start = k->map.loop_start;
                 map.last_chunk = k->map.last_chunk;
                 map.raw_len = k->map.raw_len;
+                if constexpr (PACKED) {                    // a stream that does not loop: _postAudio is all zero
+                    const PackedRun *r = k->runs + __builtin_amdgcn_readfirstlane(run);
+                    map.zero_pre = r->zero_pre;
+                    map.pre_end = r->inserted_samples - SPSF;
+                    map.main_end = map.pre_end + r->sample_count;
+                    map.post_end = map.main_end;
+                    map.loop_start = map.last_chunk = 0;
+                    map.raw_len = r->sample_count;
+                }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll 1
@@ -651,7 +687,7 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(VGA_
             header_lengths();
         }
         if (too_low) {                                 // InvalidDataException("Bitrate is set too low.")
-            if (ln_se == 0 && cold_args()->status) atomicOr(cold_args()->status, 4);
+            if (ln_se == 0 && wave_status_word<PACKED>(run)) atomicOr(wave_status_word<PACKED>(run), 4);
             level = 255;
         }
         if (level > 0 && !too_low) {
@@ -695,7 +731,7 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(VGA_
         }
         WAVE_STOP_AFTER(5, [&] { double t = 0; for (int c = 0; c < NCH; c++) for (int h = 0; h < 2; h++) for (int sf = 0; sf < 8; sf++) t += x[c][h][sf]; return __double2loint(t); }() + level + boundary);
         if (boundary < 0) {                            // NotImplementedException in the reference
-            if (ln_se == 0 && cold_args()->status) atomicOr(cold_args()->status, 8);
+            if (ln_se == 0 && wave_status_word<PACKED>(run)) atomicOr(wave_status_word<PACKED>(run), 8);
             boundary = 0;
         }
 
@@ -886,7 +922,7 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(VGA_
         // ---- store the frame: whole aligned dwords (the frame starts at any byte: its k-th dword is a funnel shift of two
         // big-endian words of fbuf), the few bytes before the first and after the last aligned dword one by one
         {
-            uint8_t *dst = frames + (int64_t)stream * frames_pitch + (int64_t)frame * frame_size;
+            uint8_t *dst = frames + (PACKED ? packed_frames_at : (int64_t)stream * frames_pitch) + (int64_t)frame * frame_size;
             const int lead = (int)((4 - (reinterpret_cast<uintptr_t>(dst) & 3)) & 3);       // bytes before the first aligned dword
             const int ndw = (frame_size - lead) / 4;
             auto byte_at = [&](int b) { return (fbuf[b >> 2] >> (24 - 8 * (b & 3))) & 0xFFu; };
@@ -919,6 +955,41 @@ bool encode_wave_kernel_takes(const DeviceInfo &info)
     return (info.nch == 1 || info.nch == 2) && WG_WAVES * wave_lds_bytes(info) + sizeof(WaveShared) + 64 <= (WG_WAVES > 4 ? 80 : 64) * 1024;
 }
 
+int encode_wave_frames_per_run(int64_t total_frames, int override_value)
+{
+    // frames per wave: long runs amortise the per-workgroup set-up (tables), short ones keep small inputs spread over the chip
+    int per_run = (int)std::min<int64_t>(MAX_WAVE_FRAMES, std::max<int64_t>(1, total_frames / 16384));
+    if (override_value > 0) per_run = std::min(override_value, 64);
+    return per_run;
+}
+
+int launch_encode_wave_packed(const int16_t *d_pcm, const DeviceInfo &info, const PackedRun *d_runs, int nruns, uint8_t *d_frames,
+                              const uint16_t *d_crc_pow, int *d_status, hipStream_t stream)
+{
+    const size_t wave_bytes = wave_lds_bytes(info);
+    const size_t lds = WG_WAVES * wave_bytes;
+    const unsigned grid = (unsigned)((nruns + WG_WAVES - 1) / WG_WAVES);
+    WaveArgs args{};
+    args.pcm = d_pcm;
+    args.frames = d_frames;
+    args.crc_pow = d_crc_pow;
+    args.status = d_status;
+    args.runs_per_stream = 1;
+    args.total_runs = nruns;
+    args.wave_bytes = (int)wave_bytes;
+    args.info = info;
+    args.runs = d_runs;
+    if (info.nch == 2) {
+        if (lds > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_encode_wave_kernel<2, true>, lds));
+        hipLaunchKernelGGL((hca_encode_wave_kernel<2, true>), dim3(grid), dim3(WG_THREADS), lds, stream, args);
+    } else {
+        if (lds > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_encode_wave_kernel<1, true>, lds));
+        hipLaunchKernelGGL((hca_encode_wave_kernel<1, true>), dim3(grid), dim3(WG_THREADS), lds, stream, args);
+    }
+    VGA_HIP_TRY(hipGetLastError());
+    return VGA_OK;
+}
+
 int launch_encode_wave(const int16_t *d_pcm, int64_t stream_pitch, int64_t ch_pitch, int nstreams, const PcmMap &map,
                        const DeviceInfo &info, uint8_t *d_frames, int64_t frames_pitch, const uint16_t *d_crc_pow,
                        int *d_status, hipStream_t stream, int first_frame, int end_frame, int frames_per_run_override)
@@ -926,11 +997,8 @@ int launch_encode_wave(const int16_t *d_pcm, int64_t stream_pitch, int64_t ch_pi
     const int frame_span = end_frame - first_frame;
     const size_t wave_bytes = wave_lds_bytes(info);
     const size_t lds = WG_WAVES * wave_bytes;
-    // frames per wave: long runs amortise the per-workgroup set-up (tables), short ones keep small inputs spread over the chip
     const int64_t total = (int64_t)nstreams * frame_span;
-    int per_run = (int)std::min<int64_t>(MAX_WAVE_FRAMES, std::max<int64_t>(1, total / 16384));
-    if (frames_per_run_override > 0) per_run = std::min(frames_per_run_override, 64);
-    per_run = std::min(per_run, frame_span);
+    const int per_run = std::min(encode_wave_frames_per_run(total, frames_per_run_override), frame_span);
     const int runs = (frame_span + per_run - 1) / per_run;
     const int64_t total_runs = (int64_t)nstreams * runs;
     const unsigned grid = (unsigned)((total_runs + WG_WAVES - 1) / WG_WAVES);
@@ -951,11 +1019,11 @@ int launch_encode_wave(const int16_t *d_pcm, int64_t stream_pitch, int64_t ch_pi
     args.map = map;
     args.info = info;
     if (info.nch == 2) {
-        if (lds > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_encode_wave_kernel<2>, lds));
-        hipLaunchKernelGGL(hca_encode_wave_kernel<2>, dim3(grid), dim3(WG_THREADS), lds, stream, args);
+        if (lds > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_encode_wave_kernel<2, false>, lds));
+        hipLaunchKernelGGL((hca_encode_wave_kernel<2, false>), dim3(grid), dim3(WG_THREADS), lds, stream, args);
     } else {
-        if (lds > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_encode_wave_kernel<1>, lds));
-        hipLaunchKernelGGL(hca_encode_wave_kernel<1>, dim3(grid), dim3(WG_THREADS), lds, stream, args);
+        if (lds > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_encode_wave_kernel<1, false>, lds));
+        hipLaunchKernelGGL((hca_encode_wave_kernel<1, false>), dim3(grid), dim3(WG_THREADS), lds, stream, args);
     }
     VGA_HIP_TRY(hipGetLastError());
     return VGA_OK;
