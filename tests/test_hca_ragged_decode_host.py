@@ -1,4 +1,4 @@
-"""vga_hca_decode_batch_v sorts its streams into shape classes before it buckets them by length (vgaudio_amd/csrc/capi_hca.hip):
+"""vga_hca_decode_batch_v sorts its streams into shape classes before it buckets them by length (vgaudio_amd/csrc/capi_hca_v.hip):
 two streams share their launches exactly when the kernels' view of them -- the DeviceInfo that make_device_info() builds --
 agrees once frame_count, sample_count and inserted_samples are ignored.  vga_testing_hca_decode_classes returns those classes;
 host code, no GPU.  The infos come from vga_hca_encoder_initialize (CriHcaEncoder.cs:61-114), which needs none either."""

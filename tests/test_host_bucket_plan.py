@@ -37,7 +37,7 @@ def check(group, length, order, begin, clen, cgrp, max_units, max_volume):
         units = order[begin[k]:begin[k + 1]]
         ls = np.asarray(length)[units]
         assert set(np.asarray(group)[units].tolist()) == {int(cgrp[k])}  # one parameter group
-        assert int(ls.max()) == int(clen[k]) == int(ls[-1])              # the chunk's longest is its last unit (capi_hca.hip reads it there)
+        assert int(ls.max()) == int(clen[k]) == int(ls[-1])              # the chunk's longest is its last unit (capi_hca_v.hip reads it there)
         assert np.all(np.diff(ls) >= 0)
         assert int(ls.max()) <= int(ls.min()) + int(ls.min()) // 4 + 1024   # within a quarter of each other
         assert len(units) <= max_units

@@ -1,5 +1,5 @@
 // capi_crypt.hip -- C ABI of the ADX / HCA encryption passes and key derivations.
-#include "common.hpp"
+#include "hca_capi.hpp"
 #include "crypt_kernels.hpp"
 
 #include <algorithm>
@@ -9,8 +9,6 @@
 #include <vector>
 
 using namespace vga;
-
-namespace vga { namespace hca { int crc_pow_table(const uint16_t **out); int device_info_from(const vga_hca_info &h, DeviceInfo &d); } }
 
 namespace {
 
@@ -359,7 +357,7 @@ int vga_hca_find_key_device(const vga_hca_info *h, const uint8_t *d_frames, int 
     if (!h || !index_out || nkeys < 0 || frame_count < 0 || (nkeys > 0 && !decryption_tables)) { set_error("null / negative argument"); return VGA_ERR_ARGUMENT; }
     *index_out = -1;
     hca::DeviceInfo d;
-    if (int rc = hca::device_info_from(*h, d)) return rc;
+    if (int rc = hca::make_device_info(*h, d)) return rc;
     if (nkeys == 0) return VGA_OK;
     if (frame_count == 0) { *index_out = 0; return VGA_OK; }            // no frame to refute the first key
     if (!d_frames) { set_error("null frames"); return VGA_ERR_ARGUMENT; }

@@ -1,9 +1,7 @@
 // capi_hca_ragged.hip -- device-resident CRI HCA batches of streams of different lengths (include/vgaudio_hip/hca_ragged.h).
 // Host side only: the packed layout, the shape-class check and the tables the PACKED instantiations of the kernels read
 // (hca_kernels.hpp: PackedRun, PackedScanStream), made once at create; a call checks its pointers and launches.
-#include "common.hpp"
-#include "../../include/vgaudio_hip/hca_ragged.h"
-#include "hca_kernels.hpp"
+#include "hca_capi.hpp"
 
 #include <algorithm>
 #include <map>
@@ -12,39 +10,21 @@
 
 using namespace vga;
 
-namespace vga { namespace hca {            // capi_hca.hip
-int crc_pow_table(const uint16_t **out);
-int device_info_from(const vga_hca_info &h, DeviceInfo &d);
-int decode_classes(const DeviceInfo *dev, int n, std::vector<int> &cls);
-int pcm_map_from(const vga_hca_info &h, int pcm_length, PcmMap &m);
-} }
+using hca::RaggedLayout;
 
-namespace {
-
-struct RaggedLayout {
-    std::vector<vga_hca_info> infos;
-    hca::DeviceInfo cls;                   // the class: the first stream's DeviceInfo
-    std::vector<int64_t> frame_at, row_at; // [nstreams], [rows]
-    std::vector<size_t> first_row;         // stream -> its first row
-    std::vector<int> first_record;         // stream -> its frame 0 among all frames
-    vga_hca_ragged_totals totals;
-    int first_looping = -1;
-};
-
-// the one place the layout is made: vga_hca_ragged_layout_for and vga_hca_ragged_create
-int make_layout(const vga_hca_info *infos, int nstreams, RaggedLayout &L)
+int vga::hca::make_layout(const vga_hca_info *infos, int nstreams, RaggedLayout &L)
 {
     if (nstreams < 0) { set_error("negative stream count"); return VGA_ERR_ARGUMENT; }
     if (nstreams > 0 && !infos) { set_error("null HcaInfo array"); return VGA_ERR_ARGUMENT; }
     L.infos.assign(infos, infos + nstreams);
     std::vector<hca::DeviceInfo> dev(nstreams);
     for (int s = 0; s < nstreams; s++) {   // every stream's own checks, as vga_hca_decode_device makes them
-        if (int rc = hca::device_info_from(infos[s], dev[s])) return rc;
+        if (int rc = make_device_info(infos[s], dev[s])) return rc;
         if (infos[s].sample_count < 0) { set_error("stream %d: negative sample count", s); return VGA_ERR_ARGUMENT; }
         if (infos[s].looping && L.first_looping < 0) L.first_looping = s;
     }
     std::vector<int> cls;
-    if (hca::decode_classes(dev.data(), nstreams, cls) > 1) {
+    if (decode_classes(dev.data(), nstreams, cls) > 1) {
         int bad = 0;
         while (cls[bad] == 0) bad++;
         set_error("stream %d is of another shape class than stream 0 (channels, frame size, bands or ATH curve differ): "
@@ -52,8 +32,7 @@ int make_layout(const vga_hca_info *infos, int nstreams, RaggedLayout &L)
         return VGA_ERR_ARGUMENT;
     }
     memset(&L.cls, 0, sizeof L.cls);
-    if (nstreams > 0) L.cls = dev[0];
-    L.cls.frame_count = L.cls.sample_count = L.cls.inserted_samples = 0;
+    if (nstreams > 0) L.cls = shape_class_of(dev[0]);
     L.frame_at.resize(nstreams);
     L.first_row.resize(nstreams);
     L.first_record.resize(nstreams);
@@ -78,6 +57,8 @@ int make_layout(const vga_hca_info *infos, int nstreams, RaggedLayout &L)
     L.totals.decode_workspace_bytes = nstreams > 0 ? hca::decode_record_bytes(L.cls) * (size_t)frames : 0;
     return VGA_OK;
 }
+
+namespace {
 
 struct RunTable {
     hca::PackedRun *d = nullptr;
@@ -106,11 +87,7 @@ struct vga_hca_ragged {
     }
 };
 
-namespace {
-
-// the runs {stream, first frame, length} of one launch: every stream's frames cut at per_run, never across a stream's end.
-// The decoder's second kernel has nothing to do for a stream without samples; the encoder writes such a stream's frames.
-std::vector<hca::PackedRun> cut_runs(const RaggedLayout &L, int per_run, bool encoder)
+std::vector<hca::PackedRun> vga::hca::cut_runs(const RaggedLayout &L, int per_run, bool encoder)
 {
     std::vector<hca::PackedRun> runs;
     for (int s = 0; s < (int)L.infos.size(); s++) {
@@ -127,7 +104,7 @@ std::vector<hca::PackedRun> cut_runs(const RaggedLayout &L, int per_run, bool en
         r.inserted_samples = h.inserted_samples;
         if (encoder) {
             hca::PcmMap m;
-            if (hca::pcm_map_from(h, h.sample_count, m) == VGA_OK) r.zero_pre = m.zero_pre;
+            if (make_pcm_map(h, h.sample_count, m) == VGA_OK) r.zero_pre = m.zero_pre;
         }
         r.stream = s;
         for (int f = 0; f < h.frame_count; f += per_run) {
@@ -138,6 +115,10 @@ std::vector<hca::PackedRun> cut_runs(const RaggedLayout &L, int per_run, bool en
     }
     return runs;
 }
+
+namespace {
+
+using hca::cut_runs;
 
 int upload_runs(const std::vector<hca::PackedRun> &runs, RunTable &t)
 {
@@ -158,9 +139,9 @@ int encoder_checks(const RaggedLayout &L)
     }
     for (int s = 0; s < (int)L.infos.size(); s++) {
         const vga_hca_info &h = L.infos[s];
-        if (h.frame_size * 8 < 48 + 3 * h.channel_count + 16) { set_error("Bitrate is set too low."); return VGA_ERR_INVALID_DATA; }
+        if (hca::bitrate_too_low(h)) { set_error("Bitrate is set too low."); return VGA_ERR_INVALID_DATA; }
         hca::PcmMap m;
-        if (int rc = hca::pcm_map_from(h, h.sample_count, m)) return rc;
+        if (int rc = hca::make_pcm_map(h, h.sample_count, m)) return rc;
     }
     return VGA_OK;
 }
@@ -242,7 +223,7 @@ int vga_hca_ragged_layout_for(const vga_hca_info *infos, int nstreams, int64_t *
 {
     if (!frame_offsets_out && !pcm_row_offsets_out && !totals_out) { set_error("vga_hca_ragged_layout_for: no output"); return VGA_ERR_ARGUMENT; }
     RaggedLayout L;
-    if (int rc = make_layout(infos, nstreams, L)) return rc;
+    if (int rc = hca::make_layout(infos, nstreams, L)) return rc;
     if (frame_offsets_out) std::copy(L.frame_at.begin(), L.frame_at.end(), frame_offsets_out);
     if (pcm_row_offsets_out) std::copy(L.row_at.begin(), L.row_at.end(), pcm_row_offsets_out);
     if (totals_out) *totals_out = L.totals;
@@ -254,7 +235,7 @@ int vga_hca_ragged_create(const vga_hca_info *infos, int nstreams, vga_hca_ragge
     if (!out) { set_error("null output"); return VGA_ERR_ARGUMENT; }
     *out = nullptr;
     vga_hca_ragged *r = new vga_hca_ragged;
-    int rc = make_layout(infos, nstreams, r->L);
+    int rc = hca::make_layout(infos, nstreams, r->L);
     if (!rc) rc = require_device();
     if (!rc) {
         (void)hipGetDevice(&r->device);

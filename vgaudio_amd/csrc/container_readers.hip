@@ -3,12 +3,11 @@
 // in HBM, in the row layouts the decoders take.  Keys and decryption stay with the caller, who composes them from the
 // existing key-search and crypt calls exactly as the reference's ToAudioStream does.
 #include "container_host.hpp"
+#include "hca_capi.hpp"
 #include "hca_frame_crc.hpp"
 
 using namespace vga;
 using namespace vga::container;
-
-namespace vga { namespace hca { int crc_pow_table(const uint16_t **out); } }   // capi_hca.hip
 
 // ---------------------------------------------------------------- device side
 namespace vga {
@@ -511,7 +510,7 @@ int vga_hca_read(const uint8_t *file, size_t size, const vga_hca_file_info *I, u
     HostStage h;
     const uint8_t *d_file = nullptr;
     void *d_out = nullptr, *d_bad = nullptr;
-    const int64_t pitch = round_up(bytes + 8, 16);
+    const int64_t pitch = hca::frames_pitch_for(H);
     int bad = 0;
     if (int rc = h.open()) return rc;
     if (int rc = h.image(file, (size_t)(I->frames_offset + bytes), &d_file)) return rc;
