@@ -294,6 +294,22 @@ def test_device_resident_ragged_batch():
     rb.close()
 
 
+def test_the_ragged_objects_layout_is_the_host_headers():
+    """vga_gcadpcm_ragged_create lays its rows out with csrc/gc_host.hpp: the offsets and sizes it reports are what the header
+    alone computes (tests/host/gc_host_driver.cpp, built with g++)"""
+    import torch
+    import test_gc_host_layer as H
+    from vgaudio_amd import device as vdev
+    lens = [0, 1, 13, 14, 15, 16, 897, 2880, 2880, 100000]
+    _, pcm_off, adpcm_off, _, totals = H.header_ragged_layout(H.load_host(), lens)
+    rb = vdev.GcRaggedBatch(lens, torch.device("cuda", 0))
+    assert _lib.lib().vga_gcadpcm_ragged_channels(rb.handle) == len(lens)
+    assert rb.pcm_offsets.tolist() == pcm_off and rb.adpcm_offsets.tolist() == adpcm_off
+    guard = H.load_host().gh_guard_bytes()
+    assert (rb.pcm_samples, rb.adpcm_bytes) == (totals[0] + guard // 2, totals[1] + guard)
+    rb.close()
+
+
 # ---------------------------------------------------------------------------------------------- CRI ADX, CRI HCA
 def _adx_param_sets():
     """(reference-side parameters for the oracle, the same as vga_adx_params) -- different files, different parameters"""

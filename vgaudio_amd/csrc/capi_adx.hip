@@ -148,16 +148,6 @@ int vga_adx_decode_device(const uint8_t *d_adpcm, int64_t in_pitch, int adpcm_le
 static constexpr int ADX_MIN_SHARE_CHANNELS = 128;     // channels per share of a call spread over several GPUs (vga_set_devices)
 
 static int adx_encode_batch_one(const int16_t *const *pcm, int nch, int pcm_length, const vga_adx_params *p, uint8_t *const *out,
-                                int16_t *history_out);
-int vga_adx_encode_batch(const int16_t *const *pcm, int nch, int pcm_length, const vga_adx_params *p,
-                         uint8_t *const *out, int16_t *history_out)
-{
-    if (nch <= 0 || !pcm || !out) return adx_encode_batch_one(pcm, nch, pcm_length, p, out, history_out);
-    return for_each_device_share(nch, ADX_MIN_SHARE_CHANNELS, [&](int first, int count) {
-        return adx_encode_batch_one(pcm + first, count, pcm_length, p, out + first, history_out ? history_out + first : nullptr);
-    });
-}
-static int adx_encode_batch_one(const int16_t *const *pcm, int nch, int pcm_length, const vga_adx_params *p, uint8_t *const *out,
                                 int16_t *history_out)
 {
     if (int rc = validate(p)) return rc;
@@ -181,18 +171,8 @@ static int adx_encode_batch_one(const int16_t *const *pcm, int nch, int pcm_leng
     const adx::AdxDeviceParams dp = device_params(p, true);
     pipe::Job job;
     job.units = nch;
-    if (pcm_length > 0) {
-        job.in_rows = (const void *const *)pcm;
-        job.in_row_bytes = (size_t)pcm_length * 2;
-        job.d_in = d_pcm.as<char>();
-        job.d_in_pitch = (size_t)pcm_pitch * 2;
-    }
-    if (nbytes > 0) {
-        job.out_rows = (void *const *)out;
-        job.out_row_bytes = (size_t)nbytes;
-        job.d_out = d_out.as<char>();
-        job.d_out_pitch = (size_t)out_pitch;
-    }
+    if (pcm_length > 0) bind_in(job, (const void *const *)pcm, (size_t)pcm_length * 2, d_pcm.as<char>(), (size_t)pcm_pitch * 2);
+    if (nbytes > 0) bind_out(job, (void *const *)out, (size_t)nbytes, d_out.as<char>(), (size_t)out_pitch);
     job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         return adx::launch_encode(d_pcm.as<int16_t>() + (int64_t)first * pcm_pitch, pcm_pitch, count, pcm_length, dp,
@@ -203,16 +183,15 @@ static int adx_encode_batch_one(const int16_t *const *pcm, int nch, int pcm_leng
     return VGA_OK;
 }
 
-static int adx_decode_batch_one(const uint8_t *const *adpcm, int adpcm_length, int nch, int sample_count, const vga_adx_params *p,
-                                int16_t *const *pcm_out);
-int vga_adx_decode_batch(const uint8_t *const *adpcm, int adpcm_length, int nch, int sample_count,
-                         const vga_adx_params *p, int16_t *const *pcm_out)
+int vga_adx_encode_batch(const int16_t *const *pcm, int nch, int pcm_length, const vga_adx_params *p,
+                         uint8_t *const *out, int16_t *history_out)
 {
-    if (nch <= 0 || !adpcm || !pcm_out) return adx_decode_batch_one(adpcm, adpcm_length, nch, sample_count, p, pcm_out);
+    if (nch <= 0 || !pcm || !out) return adx_encode_batch_one(pcm, nch, pcm_length, p, out, history_out);
     return for_each_device_share(nch, ADX_MIN_SHARE_CHANNELS, [&](int first, int count) {
-        return adx_decode_batch_one(adpcm + first, adpcm_length, count, sample_count, p, pcm_out + first);
+        return adx_encode_batch_one(pcm + first, count, pcm_length, p, out + first, history_out ? history_out + first : nullptr);
     });
 }
+
 static int adx_decode_batch_one(const uint8_t *const *adpcm, int adpcm_length, int nch, int sample_count, const vga_adx_params *p,
                                 int16_t *const *pcm_out)
 {
@@ -240,14 +219,8 @@ static int adx_decode_batch_one(const uint8_t *const *adpcm, int adpcm_length, i
     const adx::AdxDeviceParams dp = device_params(p, false);
     pipe::Job job;
     job.units = nch;
-    job.in_rows = (const void *const *)adpcm;
-    job.in_row_bytes = (size_t)adpcm_length;
-    job.d_in = d_in.as<char>();
-    job.d_in_pitch = (size_t)in_pitch;
-    job.out_rows = (void *const *)pcm_out;
-    job.out_row_bytes = (size_t)sample_count * 2;
-    job.d_out = d_pcm.as<char>();
-    job.d_out_pitch = (size_t)pcm_pitch * 2;
+    bind_in(job, (const void *const *)adpcm, (size_t)adpcm_length, d_in.as<char>(), (size_t)in_pitch);
+    bind_out(job, (void *const *)pcm_out, (size_t)sample_count * 2, d_pcm.as<char>(), (size_t)pcm_pitch * 2);
     job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         return adx::launch_decode(d_in.as<uint8_t>() + (int64_t)first * in_pitch, in_pitch, count, sample_count, dp,
@@ -261,6 +234,15 @@ static int adx_decode_batch_one(const uint8_t *const *adpcm, int adpcm_length, i
         return VGA_ERR_ARGUMENT;
     }
     return VGA_OK;
+}
+
+int vga_adx_decode_batch(const uint8_t *const *adpcm, int adpcm_length, int nch, int sample_count,
+                         const vga_adx_params *p, int16_t *const *pcm_out)
+{
+    if (nch <= 0 || !adpcm || !pcm_out) return adx_decode_batch_one(adpcm, adpcm_length, nch, sample_count, p, pcm_out);
+    return for_each_device_share(nch, ADX_MIN_SHARE_CHANNELS, [&](int first, int count) {
+        return adx_decode_batch_one(adpcm + first, adpcm_length, count, sample_count, p, pcm_out + first);
+    });
 }
 
 }  // extern "C"

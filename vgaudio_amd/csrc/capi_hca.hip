@@ -145,17 +145,9 @@ static int hca_encode_batch_one(const int16_t *const *pcm, int nstreams, const v
     job.units = nstreams;
     if (n > 0) {
         job.in_rows_per_unit = nch;
-        job.in_rows = (const void *const *)pcm;
-        job.in_row_bytes = (size_t)n * 2;
-        job.d_in = d_pcm.as<char>();
-        job.d_in_pitch = (size_t)ch_pitch * 2;
+        bind_in(job, (const void *const *)pcm, (size_t)n * 2, d_pcm.as<char>(), (size_t)ch_pitch * 2);
     }
-    if (fbytes > 0) {
-        job.out_rows = (void *const *)frames_out;
-        job.out_row_bytes = (size_t)fbytes;
-        job.d_out = d_frames.as<char>();
-        job.d_out_pitch = (size_t)frames_pitch;
-    }
+    if (fbytes > 0) bind_out(job, (void *const *)frames_out, (size_t)fbytes, d_frames.as<char>(), (size_t)frames_pitch);
     job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         return vga_hca_encode_device(d_pcm.as<int16_t>() + (int64_t)first * stream_pitch, stream_pitch, ch_pitch, count, n, &h,
@@ -205,18 +197,10 @@ static int hca_decode_batch_one(const vga_hca_info *h, const uint8_t *const *fra
     const size_t ws_per_stream = nstreams > 0 ? wsb / (size_t)nstreams : 0;
     pipe::Job job;
     job.units = nstreams;
-    if (fbytes > 0) {
-        job.in_rows = (const void *const *)frames;
-        job.in_row_bytes = (size_t)fbytes;
-        job.d_in = d_frames.as<char>();
-        job.d_in_pitch = (size_t)frames_pitch;
-    }
+    if (fbytes > 0) bind_in(job, (const void *const *)frames, (size_t)fbytes, d_frames.as<char>(), (size_t)frames_pitch);
     if (n > 0) {
         job.out_rows_per_unit = nch;
-        job.out_rows = (void *const *)pcm_out;
-        job.out_row_bytes = (size_t)n * 2;
-        job.d_out = d_pcm.as<char>();
-        job.d_out_pitch = (size_t)ch_pitch * 2;
+        bind_out(job, (void *const *)pcm_out, (size_t)n * 2, d_pcm.as<char>(), (size_t)ch_pitch * 2);
     }
     job.compute_lanes = planned_compute_lanes(1);                       // (nothing per lane)
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {

@@ -364,6 +364,22 @@ inline void bind_out(pipe::Job &job, void *const *rows, const RaggedRows &r, con
     job.d_out = d;
 }
 
+// equal-length rows: row_bytes each, `pitch` bytes apart on the device
+inline void bind_in(pipe::Job &job, const void *const *rows, size_t row_bytes, char *d, size_t pitch)
+{
+    job.in_rows = rows;
+    job.in_row_bytes = row_bytes;
+    job.d_in = d;
+    job.d_in_pitch = pitch;
+}
+inline void bind_out(pipe::Job &job, void *const *rows, size_t row_bytes, const char *d, size_t pitch)
+{
+    job.out_rows = rows;
+    job.out_row_bytes = row_bytes;
+    job.d_out = d;
+    job.d_out_pitch = pitch;
+}
+
 // The device image of a bucketed call (plan_buckets): chunk k's rows lie pitch[k] bytes apart behind the chunks before it,
 // a unit's rows next to each other.  A chunk's kernels run every row to the chunk's longest length, on into its padding.
 struct BucketLayout {
