@@ -8,7 +8,10 @@ Prints static instruction counts per block of the HOT path of one frame (lane = 
 = 8 channel-frames = 112 samples), the cold block's path for a plain third trip, the helper wave's loop per tile, and the
 resulting lane-operations per sample with the measured rates (cold-block rate, short-pass share) filled in.
 
-    python tools/isa_budget_gc.py > profiles/r08_gc_encode_isa_budget.md
+    python tools/isa_budget_gc.py > profiles/rNN_gc_encode_isa_budget.md
+
+(Tables up to profiles/r08_gc_encode_isa_budget.md were made with an earlier frame-start rule that counted the tile head into
+the frame's first row -- 87 VALU where this version says 53 for the same source; they cannot be reproduced with this version.)
 """
 import collections
 import os
@@ -80,12 +83,10 @@ def main():
     labels = [i for i, l in enumerate(L) if l.endswith(":")]
     prev_label = lambda i: max(j for j in labels if j <= i)
     next_label = lambda i: min(j for j in labels if j > i)
-    frame_start = prev_label(prev_label(short_a) - 1)
-    # walk back over the small blocks in front of the passes (s1 select, the rare sequential pre-scan) to the frame's first label
-    k = labels.index(prev_label(short_a))
-    while k > 0 and short_a - labels[k - 1] < 420:
-        k -= 1
-    frame_start = labels[k]
+    # the frame's first label: the nearest one in front of the passes whose block opens with the row reads of the NEXT frame
+    # (six ds_read_b128) -- the small blocks between it and the passes are the pre-scan head, the first scale and the
+    # rare sequential pre-scan
+    frame_start = max(j for j in labels if j < short_a and sum(l.startswith("ds_read_b128") for l in L[j:j + 20]) >= 6)
     short_blk = (prev_label(short_a), next_label(short_b))
     normal_blk = (prev_label(normal_a), next_label(normal_b))
     tail_end = normal_blk[1]
@@ -105,7 +106,7 @@ def main():
             ("passes B (s1 + 1) and A (s1) without the f32 detour, 28 sample steps", count(L[short_blk[0]:short_blk[1]])),
             ("the same with the conversions (30 % of the wave-frames take these instead)", count(L[normal_blk[0]:normal_blk[1]])),
             ("select the pass the reference ends on, 8-predictor argmin (DPP), winner's history, 4 x ds_write_b128", count(L[normal_blk[1]:tail_end + 1]))]
-    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 8)\n")
+    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 9)\n")
     print("`gc_encode_persistent_kernel<8, false>`, static counts from hipcc's gfx950 listing of `vgaudio_amd/csrc/gc_encode_kernel.hip`")
     print("(`tools/isa_budget_gc.py`).  One wave-frame = 64 lanes = 8 channels x 8 predictors = 112 input samples.\n")
     print("| block of the hot frame | total | VALU | SALU | LDS | wait / nop |")
@@ -134,17 +135,19 @@ def main():
 
 
 TEXT = """
-## What the budget says (round 8)
+## What the budget says (round 9)
 
-* Round 7's table is `profiles/r07_gc_encode_isa_budget.md` (same tool, same options): passes 357 / 393 VALU, row block 82,
-  tail 45, third pass 204.
-* The pass takes the frame as the seven dwords of pairs it has in memory and forms the errors two at a time
-  (gc_encode_core.hpp E1-E5): `v_pk_sub_i16 E, xw, H clamp` and `v_dot2_i32_i16 total, E, E, total clamp` once per two sample
-  steps where round 7 had `v_sub_u32_sdwa` and `v_mad_i32_i24` in every step: -14 VALU per pass.
-* The row block reads 6 x ds_read_b128 (8 before) and keeps 7 + 14 registers per row set (16 + 14 before).  The two
-  history-dependent pre-scan distances take the history pair and one v_alignbit: the dot product without its clamp (v_dot2c
-  and a v_mov of the zero, as in the helper wave; hazards placed by the compiler) in place of v_mul_i32_i24 + v_mad_i32_i24.  The winner's history is no longer unpacked into two sign-extended registers a frame.
-* Each dot instruction still wants its wait states (`s_nop`): the accumulate chain's sit off the reconstruction chain.
+* Round 8's table is `profiles/r08_gc_encode_isa_budget.md`.  Its first row (87 VALU) took the frame to begin at the TILE's
+  first label: the tool walked back a fixed number of lines and so counted the tile head (lane addresses, the first row's
+  reads), which runs once per four frames.  The tool now takes the frame to begin at the label whose block opens with the next
+  frame's six row reads; with that rule the parent of this round has 53 VALU in the row block and 519 per wave-frame.
+* Row block 53 -> 41: the two history-dependent distances in the numerator domain (gc_encode_core.hpp N1: `v_sub` for the
+  sign of D, `v_lshrrev`, `v_mad_i32_i24`, `v_ashrrev` on `in * 2048 + 1024 - P`, no unpacking of `in`, no quotient), both dot
+  products in the clamped three-operand form (no `v_mov` of the zero), and the first scale from ONE bit length (F1-F4: two
+  `v_med3`, `v_add`, `v_mul_i32_i24`, compare, `v_cndmask` with the shift folded in as SDWA, `v_or`, `v_ffbh`, `v_sub`; the
+  +M / -M tie is one compare and a scalar branch).
+* Passes 332 -> 328 / 365 -> 361: step 0 of both passes takes P0 and `in * 2048 + 1024 - P0` from the head.
+* The helper wave's pre-scan is as it was (the numerator-domain form was measured and taken out: LABNOTES 14).
 """
 
 

@@ -117,19 +117,47 @@ VGA_HD void prescan_range(const int (&x)[16], int c0, int c1, int s_begin, int s
 // Scale power of the FIRST quantise pass (value after the do-loop's first ++), given the
 // frame-wide max/min of the unclamped distances.  Returns -100 when the signed maximum is
 // ambiguous (+M and -M both present, M > 0): caller must use prescan_sequential().
+// Round 9: one bit length instead of two.  With pos = clamp(dmax, 0, 32767) (but see F5), neg = clamp(-dmin, 0, 32768):
+//  (F1) a positive maximum halves until pos < 8 * 2^n: n = max(bl(pos) - 3, 0), and the value after the first ++ is
+//       max(n - 1, 0) = max(bl(pos) - 4, 0) = bl(pos | 15) - 4.
+//  (F2) a negative one halves (its magnitude truncating) until neg < 9 * 2^n; the value wanted is the smallest m >= 0 with
+//       neg < 9 * 2^(m + 1).  g(a) = (a * 58255) >> 16 is monotone and crosses 8 * 2^j exactly where a crosses 9 * 2^j, for
+//       every j = 0..12: 58255 / 65536 = 8/9 + d with d = 0.778 / 65536, so g(9 * 2^j) >= 8 * 2^j, and g(9 * 2^j - 1) < 8 * 2^j
+//       because 9 * 2^j * d <= 0.44 < 58255 / 65536 (the step the last unit of a is worth).  Hence neg < 9 * 2^(m+1) <=> g(neg) < 16 * 2^m,
+//       and the value is bl(g(neg) | 15) - 4: the same expression as F1 on g(neg).  neg <= 32768: the product fits 31 bits.
+//  (F3) the larger magnitude decides (the positive one only when strictly larger: on equal magnitudes with equal halving
+//       counts either sign gives the same value); sum = pos - neg carries that sign.
+//  (F4) the ambiguous case: pos == neg and the two halving counts differ, i.e. 8 * 2^j <= pos < 9 * 2^j for some j >= 0 --
+//       the four leading bits of pos (of pos | 15) are 1000.  It needs sum == 0 first, so the kernel looks at it only behind
+//       a wave-uniform test of sum (first_scale_power_nt + first_scale_tie); first_scale_power_from_range is the two together.
+//  (F5) pos is floored at 1, not 0: a frame without a positive distance -- silence and every perfectly predicted frame have
+//       dmax = dmin = 0 -- would otherwise have sum == 0 and send its wave to the tie test on every frame.  Nothing else sees
+//       the difference: F1 reads pos | 15, F3 picks the negative side for dmin <= -1 either way (sum <= 0) and the positive
+//       side for dmin = 0, both with the value 0, and F4 needs pos >= 8.
+// Checked against the round-1 form (kept in tests/host/gc_first_scale_driver.cpp) on every pair of the callers' domain.
+VGA_HD int first_scale_power_nt(int dmax, int dmin, int &sum, int &pos)
+{
+    pos = imin(imax(dmax, 1), 32767);                                 // F5: 1, not 0
+    const int nd = imax(imin(dmin, 0), -32768);                       // -neg
+    sum = pos + nd;
+    const int gneg = (int)((uint32_t)VGA_MUL24(nd, -58255) >> 16);    // F2
+    const int v = sum > 0 ? pos : gneg;
+    return bit_length((unsigned)v | 15u) - 4;
+}
+// F4, for a lane with sum == 0
+VGA_HD bool first_scale_tie(int pos)
+{
+    const int e = bit_length((unsigned)pos | 15u) - 4;
+    return (pos >> e) == 8;
+}
 VGA_HD int first_scale_power_from_range(int dmax, int dmin)
 {
-    // straight-line version of halvings() for both signs (|1 keeps clz defined; bit_length(0|1) - 3 < 0 -> 0)
-    const int pos = imax(clamp16i(dmax), 0);
-    const int neg = imax(-clamp16i(dmin), 0);
-    const int hp = imax(bit_length((unsigned)pos | 1u) - 3, 0);
-    const int nn = imax(bit_length((unsigned)neg | 1u) - 4, 0);
-    const int hn = nn + ((((unsigned)neg >> nn) > 8u) ? 1 : 0);
+    int sum, pos;
+    const int s = first_scale_power_nt(dmax, dmin, sum, pos);
     // equal magnitudes with different halving counts: the sign of the reference's maxDistance depends on
     // which of +M / -M came first
-    if (pos == neg && hp != hn) return -100;
-    const int n = pos > neg ? hp : hn;
-    return imax(n - 1, 0);                          // (n<=1 ? -1 : n-2) + 1
+    if (sum == 0 && first_scale_tie(pos)) return -100;
+    return s;
 }
 
 VGA_HD int first_scale_power_from_md(int md)
@@ -300,6 +328,30 @@ VGA_HD int dot2_i16_wrap(uint32_t a, uint32_t b)
     return (int)((uint32_t)(pair_lo(a) * pair_lo(b)) + (uint32_t)(pair_hi(a) * pair_hi(b)));
 #endif
 }
+// ---- pre-scan distances in the numerator domain (round 9) --------------------------------
+// The pre-scan distance of a sample is in - D / 2048 with D = a * c1 + b * c0 and C#'s division (toward zero).  With
+// N = in * 2048 - D it is
+//       d = floor((N + (D > 0 ? 2047 : 0)) / 2048)                                                          (N1)
+//  * D > 0: D / 2048 = floor(D / 2048), so d = in + ceil(-D / 2048) = ceil(N / 2048) = floor((N + 2047) / 2048).
+//  * D < 0: D / 2048 = ceil(D / 2048), so d = in + floor(-D / 2048) = floor(N / 2048).
+//  * D = 0: N = in * 2048 is a multiple of 2048 and both forms give in (so "D >= 0" would do as well).
+// This is the same number as in - div2048(D), without forming the quotient and without unpacking `in`.
+//  (N2) for coefficients that cannot wrap (|c0| + |c1| <= 32767) |D| <= 32768 * 32767 < 2^30 and |in * 2048| <= 2^26, so
+//       |N| < 2^30 + 2^27 and |N + 2047| likewise: nothing overflows, and the clamped dot product that delivers D + 1024
+//       cannot saturate (P1).  Coefficients that can wrap keep the reference's unchecked sum (dot2_i16_wrap) and the quotient.
+VGA_HD int numer_adjust(int N, int D_is_pos)
+{
+    VGA_OPAQUE(D_is_pos);                                                   // a 0/1 factor, as in div2048: v_mad_u32_u24
+    return (int)((uint32_t)N + (uint32_t)VGA_MUL24(D_is_pos, 2047));
+}
+// A history-dependent distance of the pre-scan from P = predicted + 1024 as the pass forms it (dot2_i16 with 1024 as the
+// accumulator) and the row's in * 2048 + 1024: N = in2048p - P (the 1024 cancels -- this IS the pass's d of the same
+// sample, P2), D = P - 1024.  Valid where P is: |c0| + |c1| <= 32767 (P1).
+VGA_HD int head_distance_numer(int in2048p, int P)
+{
+    const int N = (int)((uint32_t)in2048p - (uint32_t)P);
+    return numer_adjust(N, (int)((uint32_t)(1024 - P) >> 31)) >> 11;                        // 1024 - P < 0  <=>  D > 0
+}
 VGA_HD void pack_row(const int (&x)[16], uint32_t (&xw)[7])
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -383,8 +435,18 @@ VGA_HD void unpack_row(const uint32_t (&xw)[7], uint32_t hist, int (&x)[16])
 // (pass_no_round_is_exact) therefore never met such a sample -- by induction over the samples it is the exact pass, nibble
 // for nibble -- and one that does not must be run again with the conversions.  The kernel takes this form for a frame when
 // every lane of the wave quantises at scale 9 or below (70 % of the synthetic set's wave-frames).
-template <bool WIDE_TOTAL, bool NO_ROUND = false>
-VGA_HD PassOut pass_fast_core_t(const uint32_t (&xw)[7], uint32_t hist, const int (&in2048p)[14], int c0, int c1, int scale_power)
+// HAVE_P0 (round 9): step 0's P = dot2(hist, C, 1024) handed in by a caller that has formed it already (the kernel's pre-scan
+// head takes its first distance from it, head_distance_numer) -- the same value, one dot product a pass less.
+// predicted_p1024 is that dot product as the pass writes it.
+VGA_HD int predicted_p1024(uint32_t h, uint32_t cpair)
+{
+    int k1024 = 1024;
+    VGA_OPAQUE_S(k1024);
+    return dot2_i16(h, cpair, k1024);
+}
+template <bool WIDE_TOTAL, bool NO_ROUND = false, bool HAVE_P0 = false>
+VGA_HD PassOut pass_fast_core_t(const uint32_t (&xw)[7], uint32_t hist, const int (&in2048p)[14], int c0, int c1, int scale_power,
+                                int P0 = 0)
 {
     PassOut r;
     uint64_t total64 = 0;
@@ -404,7 +466,7 @@ VGA_HD PassOut pass_fast_core_t(const uint32_t (&xw)[7], uint32_t hist, const in
 #pragma unroll
 #endif
     for (int s = 0; s < 14; s++) {
-        const int P = dot2_i16(h, cpair, k1024);                    // predicted + 1024
+        const int P = (HAVE_P0 && s == 0) ? P0 : dot2_i16(h, cpair, k1024);   // predicted + 1024
         const int d = (int)((uint32_t)in2048p[s] - (uint32_t)P);    // == in2048 - predicted
         const int rd = NO_ROUND ? d : round_through_f32(d);
         const int u = (int)((uint32_t)rd + (uint32_t)bias + ((uint32_t)d >> 31)) >> k;

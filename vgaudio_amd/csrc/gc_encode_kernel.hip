@@ -465,31 +465,50 @@ __device__ __forceinline__ void gc_encode_piece(
     // The two history-dependent pre-scan distances (:107-115), operands taken from pairs: predicted(s = 0) is the dot product of
     // the history pair (h0, h1) with (c1, c0), predicted(s = 1) that of (h1, x[2]) -- one v_alignbit across the history and the
     // row's first dword.  Unclamped dot product: int32 wraps where the reference's unchecked sum does.
+    // Round 9, when no lane of the wave has coefficients that can wrap (wave-uniform, decided once per piece): both distances in
+    // the numerator domain (gc_encode_core.hpp N1, head_distance_numer) from the clamped three-operand dot product with 1024 as
+    // its accumulator.  The first one is P0, the dot product step 0 of both passes needs anyway: formed once here and handed to
+    // them.  A wave with a hostile lane keeps the unchecked sum and the quotient for all its lanes (such a lane's first scale is
+    // where the reference's loop as written starts from).
     const uint32_t cpk = pack16(c1, c0);
-    auto prescan_head = [&](const Row &R, int &d0, int &d1) __attribute__((always_inline)) {
-        d0 = pair_lo(R.xw[0]) - div2048(dot2_i16_wrap(hpk, cpk));
-        d1 = pair_hi(R.xw[0]) - div2048(dot2_i16_wrap(__builtin_amdgcn_alignbit(R.xw[0], hpk, 16), cpk));
+    const bool head_numer = __builtin_amdgcn_ballot_w64(!coef_ok) == 0;
+    auto prescan_head = [&](const Row &R, int &d0, int &d1, int &P0) __attribute__((always_inline)) {
+        P0 = predicted_p1024(hpk, cpk);
+        if (__builtin_expect(head_numer, 1)) {
+            d0 = head_distance_numer(R.mp[0], P0);
+            d1 = head_distance_numer(R.mp[1], predicted_p1024(__builtin_amdgcn_alignbit(R.xw[0], hpk, 16), cpk));
+        } else {
+            d0 = pair_lo(R.xw[0]) - div2048(dot2_i16_wrap(hpk, cpk));
+            d1 = pair_hi(R.xw[0]) - div2048(dot2_i16_wrap(__builtin_amdgcn_alignbit(R.xw[0], hpk, 16), cpk));
+        }
+    };
+    // the first scale from the frame's range: the tie of +M and -M (gc_encode_core.hpp F4) needs pos == neg, looked at behind
+    // one wave-uniform test
+    auto first_scale = [&](const Row &R, int d0, int d1) __attribute__((always_inline)) -> int {
+        const int dmax = imax(imax((int)(int16_t)(R.pre & 0xFFFF), d0), d1);
+        const int dmin = imin(imin((int)R.pre >> 16, d0), d1);
+        int sum, pos;
+        int s1 = first_scale_power_nt(dmax, dmin, sum, pos);
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(sum == 0) != 0, 0)) {   // +M and -M both present (silence has sum == 1: F5): first occurrence decides
+            if (sum == 0 && first_scale_tie(pos)) s1 = first_scale_power_from_md(prescan_sequential_cold(pack(R.xw), hpk, c0, c1));
+        }
+        return s1;
     };
 
     auto encode_frame = [&](Row &R, int buf, int j, bool upd) {
         const uint32_t (&xw)[7] = R.xw;
         // ---- pre-scan (:107-124): two history-dependent distances + the helper's range for s = 2..13
-        int s1;
+        int s1, P0;
         {
             int d0, d1;
-            prescan_head(R, d0, d1);
-            const int dmax = imax(imax((int)(int16_t)(R.pre & 0xFFFF), d0), d1);
-            const int dmin = imin(imin((int)R.pre >> 16, d0), d1);
-            s1 = first_scale_power_from_range(dmax, dmin);
-            if (__any(s1 == -100)) {                   // +M and -M both present: first occurrence decides
-                if (s1 == -100) s1 = first_scale_power_from_md(prescan_sequential_cold(pack(xw), hpk, c0, c1));
-            }
+            prescan_head(R, d0, d1, P0);
+            s1 = first_scale(R, d0, d1);
         }
         // ---- first trip: candidate A at s1, B at s1+1 (speculation on the loop of :127-170)
         int final_sp = imin(s1 + (cand_b ? 1 : 0), 12);
         const bool at_cap = final_sp >= 12;            // the loop never goes past 12: this pass ends it
         const unsigned ov_limit = at_cap ? 3u : 248u;  // see `rare` below
-        PassOut r = pass_fast_core(xw, hpk, R.mp, c0, c1, final_sp);
+        PassOut r = pass_fast_core_t<false, false, true>(xw, hpk, R.mp, c0, c1, final_sp, P0);
         // Straight-line resolution, valid when no lane is `rare`:
         //   * no overflow can start the bump loop (:166-168 needs max_overflow + 8 > 256),
         //   * the 32-bit error sum of every lane that can become final is exact (gc_encode_core.hpp S3:
@@ -591,16 +610,11 @@ __device__ __forceinline__ void gc_encode_piece(
     // inlined back to back (two independent dependent chains: the wave has instructions to issue while one waits).
     auto encode_frame8 = [&](Row &R, int buf, int j, bool upd) {
         const uint32_t (&xw)[7] = R.xw;
-        int s1;
+        int s1, P0;
         {
             int d0, d1;
-            prescan_head(R, d0, d1);
-            const int dmax = imax(imax((int)(int16_t)(R.pre & 0xFFFF), d0), d1);
-            const int dmin = imin(imin((int)R.pre >> 16, d0), d1);
-            s1 = first_scale_power_from_range(dmax, dmin);
-            if (__any(s1 == -100)) {                   // +M and -M both present: first occurrence decides
-                if (s1 == -100) s1 = first_scale_power_from_md(prescan_sequential_cold(pack(xw), hpk, c0, c1));
-            }
+            prescan_head(R, d0, d1, P0);
+            s1 = first_scale(R, d0, d1);
         }
         const int sp_a = imin(s1, 12), sp_b = imin(s1 + 1, 12);
         // Round 5: when every lane of the wave quantises at scale 9 or below (70 % of the synthetic set's wave-frames) the two
@@ -614,15 +628,15 @@ __device__ __forceinline__ void gc_encode_piece(
         bool short_passes = !__any(sp_b > 9);
 #endif
         if (short_passes) {
-            rb = pass_fast_core_no_round(xw, hpk, R.mp, c0, c1, sp_b);
-            ra = pass_fast_core_no_round(xw, hpk, R.mp, c0, c1, sp_a);
+            rb = pass_fast_core_t<false, true, true>(xw, hpk, R.mp, c0, c1, sp_b, P0);
+            ra = pass_fast_core_t<false, true, true>(xw, hpk, R.mp, c0, c1, sp_a, P0);
             // (hostile coefficients: the lane walks the reference's loop as written whatever these passes say)
             const bool trusted = !coef_ok || (pass_no_round_is_exact(sp_a, ra.max_overflow) && pass_no_round_is_exact(sp_b, rb.max_overflow));
             short_passes = !__any(!trusted);
         }
         if (!short_passes) {
-            rb = pass_fast_core(xw, hpk, R.mp, c0, c1, sp_b);
-            ra = pass_fast_core(xw, hpk, R.mp, c0, c1, sp_a);
+            rb = pass_fast_core_t<false, false, true>(xw, hpk, R.mp, c0, c1, sp_b, P0);
+            ra = pass_fast_core_t<false, false, true>(xw, hpk, R.mp, c0, c1, sp_a, P0);
         }
         const bool cap_a = sp_a >= 12, cap_b = sp_b >= 12;         // a pass at the cap ends the loop whatever it overflowed
         const int eff_a = cap_a ? 0 : ra.max_overflow, eff_b = cap_b ? 0 : rb.max_overflow;
