@@ -149,6 +149,13 @@ int vga_testing_adx_read_general_this_thread(int on);
  * layout include/vgaudio_hip.h names next to those calls), 2 = the general lane-per-channel kernel.  Either pointer
  * may be null.  Host state only: the call allocates and launches nothing.  Returns 0. */
 int vga_testing_adx_last_path_this_thread(int *encode, int *decode);
+/* A packed ADX batch (vgaudio_hip/adx_ragged.h; ragged: a vga_adx_ragged): [0] own frames (the sum of the channels' encoded
+ * frames) [1] groups of 64 work slots [2] the encoder's time pieces [3] their length in frames [4] the (group, piece) items
+ * its first kernel is launched over -- one wave each, none wholly behind its group's longest channel -- [5] [6] [7] the same
+ * for the decoder [8] the encoder's path [9] the decoder's (1 = the time-piece kernels, 2 = the general lane-per-channel
+ * kernel, as vga_testing_adx_last_path_this_thread, which the *_device_v calls record in as well; 0 = an empty batch).
+ * Host state of the object: the call launches nothing.  Writes min(n, 10) fields and returns 10. */
+int vga_testing_adx_ragged_stats(const void *ragged, long long *out, int n);
 
 /* Poison mode for every allocation the library makes.  The device pool of the host-pointer entry points hands a parked block
  * of 1 MiB or more to any later request of half its size or more with the last call's bytes in it, the page-locked pool any

@@ -190,6 +190,15 @@ SIGNATURES = {
     "vga_hca_ragged_streams": (ci, [vp]),
     "vga_hca_ragged_totals_of": (ci, [vp, vp]),
     "vga_hca_ragged_offsets": (ci, [vp, C.POINTER(i64), C.POINTER(i64)]),
+    "vga_testing_adx_ragged_stats": (ci, [vp, C.POINTER(C.c_longlong), ci]),
+    "vga_adx_ragged_layout_for": (ci, [vp, C.POINTER(ci), ci, C.POINTER(i64), C.POINTER(i64), vp]),
+    "vga_adx_ragged_create": (ci, [vp, C.POINTER(ci), ci, C.POINTER(vp)]),
+    "vga_adx_ragged_destroy": (None, [vp]),
+    "vga_adx_ragged_channels": (ci, [vp]),
+    "vga_adx_ragged_totals_of": (ci, [vp, vp]),
+    "vga_adx_ragged_offsets": (ci, [vp, C.POINTER(i64), C.POINTER(i64)]),
+    "vga_adx_encode_device_v": (ci, [vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "vga_adx_decode_device_v": (ci, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
     "vga_hca_decode_device_v": (ci, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
     "vga_hca_encode_device_v": (ci, [vp, vp, vp, vp, vp]),
     "vga_hca_stream_create": (ci, [vp, vp, C.POINTER(vp)]),

@@ -302,3 +302,87 @@ class GuessAdx:
         check(_lib.lib().vga_adx_guess_keys(scales.ctypes.data, len(scales), adxFile.StartFrame, encryptionType, mp, nm, ip, ni,
                                             out, maxKeys, C.byref(n)))
         return [CriAdxKey(out[k].seed, out[k].mult, out[k].inc) for k in range(n.value)]
+
+
+class RaggedAdxTotalsC(C.Structure):
+    """vga_adx_ragged_totals (include/vgaudio_hip/adx_ragged.h)"""
+    _fields_ = [("pcm_samples", C.c_int64), ("adx_bytes", C.c_int64), ("channels", C.c_int), ("total_frames", C.c_int64),
+                ("encode_workspace_bytes", C.c_size_t), ("decode_workspace_bytes", C.c_size_t)]
+
+
+def _adx_params_c(params):
+    return params._c() if isinstance(params, CriAdxParameters) else _lib.AdxParams.from_buffer_copy(params)
+
+
+def _counts_array(sample_counts):
+    counts = [int(n) for n in sample_counts]
+    return (C.c_int * max(len(counts), 1))(*counts), len(counts)
+
+
+class RaggedAdx:
+    """Channels of ONE parameter set and any lengths, resident on the device: packed PCM rows, packed ADX rows, one set of
+    launches per call (vga_adx_ragged_create, vga_adx_encode_device_v, vga_adx_decode_device_v; include/vgaudio_hip/adx_ragged.h
+    has the layout).  The tensors are the caller's torch tensors on the current device; the calls run on torch's current
+    stream and do not synchronise it.  status: int32, one word per channel, zeroed by the caller."""
+
+    @staticmethod
+    def layout(params, sample_counts):
+        """(pcm_offsets int64[nch], adx_offsets int64[nch], RaggedAdxTotalsC): host only, needs no GPU"""
+        cp = _adx_params_c(params)
+        arr, nch = _counts_array(sample_counts)
+        po, ao, tot = np.zeros(max(nch, 1), dtype=np.int64), np.zeros(max(nch, 1), dtype=np.int64), RaggedAdxTotalsC()
+        i64p = C.POINTER(C.c_int64)
+        check(_lib.lib().vga_adx_ragged_layout_for(C.byref(cp), arr, nch, po.ctypes.data_as(i64p), ao.ctypes.data_as(i64p), C.byref(tot)))
+        return po[:nch], ao[:nch], tot
+
+    def __init__(self, params, sample_counts):
+        cp = _adx_params_c(params)
+        arr, nch = _counts_array(sample_counts)
+        self._h = C.c_void_p()
+        check(_lib.lib().vga_adx_ragged_create(C.byref(cp), arr, nch, C.byref(self._h)))
+        self.channels = _lib.lib().vga_adx_ragged_channels(self._h)
+        self.totals = RaggedAdxTotalsC()
+        check(_lib.lib().vga_adx_ragged_totals_of(self._h, C.byref(self.totals)))
+        po, ao = np.zeros(max(nch, 1), dtype=np.int64), np.zeros(max(nch, 1), dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        check(_lib.lib().vga_adx_ragged_offsets(self._h, po.ctypes.data_as(i64p), ao.ctypes.data_as(i64p)))
+        self.pcm_offsets, self.adx_offsets = po[:nch], ao[:nch]
+
+    def close(self):
+        if self._h:
+            _lib.lib().vga_adx_ragged_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    @staticmethod
+    def _stream(stream):
+        import torch
+        return C.c_void_p((stream if stream is not None else torch.cuda.current_stream()).cuda_stream)
+
+    def _need(self, t, dtype, count, what):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() >= count):
+            raise _lib.ArgumentError("%s: a contiguous %s tensor on the device of at least %d elements" % (what, dtype, count))
+
+    def encode_device(self, pcm, adx, workspace, history=None, stream=None):
+        """pcm: int16[totals.pcm_samples] -> adx: uint8[totals.adx_bytes]; workspace: uint8[totals.encode_workspace_bytes];
+        history: int16[channels] or None"""
+        import torch
+        self._need(pcm, torch.int16, self.totals.pcm_samples, "pcm")
+        self._need(adx, torch.uint8, self.totals.adx_bytes, "adx")
+        self._need(workspace, torch.uint8, self.totals.encode_workspace_bytes, "workspace")
+        if history is not None:
+            self._need(history, torch.int16, self.channels, "history")
+        check(_lib.lib().vga_adx_encode_device_v(self._h, pcm.data_ptr(), adx.data_ptr(), history.data_ptr() if history is not None else None,
+                                                 workspace.data_ptr(), workspace.numel(), self._stream(stream)))
+
+    def decode_device(self, adx, pcm, workspace, status, stream=None):
+        """adx: uint8[totals.adx_bytes] -> pcm: int16[totals.pcm_samples]; workspace: uint8[totals.decode_workspace_bytes]"""
+        import torch
+        self._need(adx, torch.uint8, self.totals.adx_bytes, "adx")
+        self._need(pcm, torch.int16, self.totals.pcm_samples, "pcm")
+        self._need(workspace, torch.uint8, self.totals.decode_workspace_bytes, "workspace")
+        self._need(status, torch.int32, self.channels, "status")
+        check(_lib.lib().vga_adx_decode_device_v(self._h, adx.data_ptr(), pcm.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                                 status.data_ptr(), self._stream(stream)))

@@ -2,6 +2,7 @@
 #include "common.hpp"
 #include "host_batch.hpp"
 #include "adx_kernels.hpp"
+#include "adx_host.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -27,22 +28,7 @@ void calculate_coefficients(int highpass_freq, int sample_rate, int16_t coefs[2]
     coefs[1] = (int16_t)(int)(c * c * -4096);
 }
 
-int validate(const vga_adx_params *p)
-{
-    if (!p) { set_error("null ADX parameters"); return VGA_ERR_ARGUMENT; }
-    if (p->frame_size < 4 || (p->frame_size & 1) || p->frame_size > 255) {
-        set_error("ADX frame size %d unsupported (even, 4..254)", p->frame_size);
-        return VGA_ERR_ARGUMENT;
-    }
-    if (p->type != 2 && p->type != 3 && p->type != 4) { set_error("ADX type %d unknown", p->type); return VGA_ERR_ARGUMENT; }
-    if (p->type == 2 && (p->filter < 0 || p->filter > 3)) {
-        set_error("ADX fixed filter %d out of range", p->filter);       // Coefs[c.Filter] throws
-        return VGA_ERR_ARGUMENT;
-    }
-    if (p->padding < 0) { set_error("negative padding"); return VGA_ERR_ARGUMENT; }
-    if (p->type != 2 && p->sample_rate <= 0) { set_error("sample rate must be positive"); return VGA_ERR_ARGUMENT; }
-    return VGA_OK;
-}
+using adx::validate;                                   // (adx_host.hpp)
 
 adx::AdxDeviceParams device_params(const vga_adx_params *p, bool encode)
 {
@@ -62,6 +48,8 @@ adx::AdxDeviceParams device_params(const vga_adx_params *p, bool encode)
 }
 
 }  // namespace
+
+adx::AdxDeviceParams vga::adx::make_device_params(const vga_adx_params *p, bool encode) { return device_params(p, encode); }
 
 // channels per chunk of the host pipeline (host_pipeline.hpp): the piece-wise kernels fill the chip from 1024 channels on
 static constexpr int ADX_CHUNK_CHANNELS = 1024;
