@@ -396,7 +396,10 @@ int vga_nwstm_layout_for(const vga_nwstm_params *p, int nch, vga_nwstm_layout *o
  *            loop: zeros); a file that does not loop carries its start context as loop context;
  *   d_seek   the builder's seek tables, seek_entries entries (2 shorts each) per row, seek_pitch in shorts.
  * tracks: params.track_count entries, or NULL for the default list.  Image f goes to d_files + f*file_pitch
- * (file_pitch >= layout.file_size and a multiple of 16 when nfiles > 1); every byte of each image is written. */
+ * (file_pitch >= layout.file_size and a multiple of 16 when nfiles > 1); every byte of each image is written.
+ * Layout: d_adpcm and d_files at any byte, adpcm_pitch anything >= adpcm_len; the int16 arrays at any short boundary,
+ * seek_pitch anything >= 2*seek_entries; a smaller pitch or a file_pitch off 16 is VGA_ERR_ARGUMENT and writes nothing.
+ * No byte outside the images is written: not between two images, not behind the last. */
 int vga_nwstm_write_device(const vga_nwstm_params *p, int nch, int nfiles, const vga_nw_track *tracks,
                            const uint8_t *d_adpcm, int64_t adpcm_pitch, int adpcm_len, const int16_t *d_coefs,
                            const int16_t *d_gain, const int16_t *d_start_context, const int16_t *d_loop_context,
@@ -434,7 +437,9 @@ typedef struct {
  * PCM16 streams (vga_nwstm_pcm_parse in vgaudio_hip_pcm.h reads those), CWAV / FWAV and CSTP / FSTP files. */
 int vga_nwstm_parse(const uint8_t *file, size_t size, vga_nwstm_info *out);
 /* nfiles images that share one parsed geometry at d_files + f*file_pitch -> row f*channel_count+c of d_adpcm
- * (info->adpcm_bytes per row), the layout vga_gcadpcm_decode_device takes */
+ * (info->adpcm_bytes per row), the layout vga_gcadpcm_decode_device takes.  Layout: images and rows at any byte,
+ * file_pitch anything that holds an image (audio_data_offset + audio_data_length; checked when nfiles > 1),
+ * adpcm_pitch anything >= info->adpcm_bytes (less: VGA_ERR_ARGUMENT); the bytes behind a row are left alone */
 int vga_nwstm_read_device(const vga_nwstm_info *info, const uint8_t *d_files, int64_t file_pitch, int nfiles,
                           uint8_t *d_adpcm, int64_t adpcm_pitch, void *stream);
 /* host form: adpcm_out[c] info->adpcm_bytes bytes; seek_out[c] (or NULL) 2*info->seek_entries shorts as stored */
@@ -487,7 +492,9 @@ int vga_hps_block_map(const vga_hps_params *p, int nch, vga_hps_block *blocks, i
  *            row, pcm_pitch in samples) or NULL for zeros.  A block whose hist index falls at or past pcm_len
  *            returns VGA_ERR_OUT_OF_RANGE (the reference's IndexOutOfRangeException).
  * Image f goes to d_files + f*file_pitch (file_pitch >= layout.file_size, a multiple of 16 when nfiles > 1); every
- * byte is written.  Stream-ordered: the block map reaches the device as kernel arguments, nothing synchronises. */
+ * byte is written.  Stream-ordered: the block map reaches the device as kernel arguments, nothing synchronises.
+ * Layout: d_adpcm and d_files at any byte, adpcm_pitch anything >= adpcm_len; d_pcm and the int16 arrays at any short
+ * boundary, pcm_pitch anything >= pcm_len; a smaller pitch or a file_pitch off 16 is VGA_ERR_ARGUMENT and writes nothing. */
 int vga_hps_write_device(const vga_hps_params *p, int nch, int nfiles, const uint8_t *d_adpcm, int64_t adpcm_pitch,
                          int adpcm_len, const int16_t *d_coefs, const int16_t *d_gain, const int16_t *d_start_context,
                          const int16_t *d_pcm, int64_t pcm_pitch, int pcm_len, uint8_t *d_files, int64_t file_pitch,
@@ -520,7 +527,9 @@ typedef struct {
  * info->block_count).  VGA_ERR_INVALID_DATA for a missing magic, reads past the end, channel sample counts that
  * differ, no channels, audio shorter than the sample count; VGA_ERR_INVALID_OP for more than 255 channels. */
 int vga_hps_parse(const uint8_t *file, size_t size, vga_hps_info *info, vga_hps_block_info *blocks, int capacity);
-/* nfiles images that share one parsed geometry -> row f*channel_count+c of d_adpcm (info->adpcm_bytes per row) */
+/* nfiles images that share one parsed geometry -> row f*channel_count+c of d_adpcm (info->adpcm_bytes per row).
+ * Layout: images and rows at any byte, file_pitch anything that holds an image (checked when nfiles > 1), adpcm_pitch
+ * anything >= info->adpcm_bytes (less: VGA_ERR_ARGUMENT); the bytes behind a row are left alone */
 int vga_hps_read_device(const vga_hps_info *info, const vga_hps_block_info *blocks, const uint8_t *d_files,
                         int64_t file_pitch, int nfiles, uint8_t *d_adpcm, int64_t adpcm_pitch, void *stream);
 int vga_hps_read(const uint8_t *file, size_t size, const vga_hps_info *info, const vga_hps_block_info *blocks,
@@ -549,7 +558,8 @@ typedef struct {
 /* VGA_ERR_OUT_OF_RANGE for a negative block size or one not divisible by 8 (the BlockSize setter) and for loop
  * points WithLoop rejects; VGA_ERR_INVALID_OP for a block size of 0 with no audio (the reference divides by 0). */
 int vga_idsp_layout_for(const vga_idsp_params *p, int nch, vga_idsp_layout *out);
-/* as vga_hps_write_device without the PCM rows, plus d_loop_context (3 shorts per row or NULL for zeros) */
+/* as vga_hps_write_device without the PCM rows, plus d_loop_context (3 shorts per row or NULL for zeros); the same
+ * layout rules: rows and images at any byte, any adpcm_pitch >= adpcm_len, file_pitch a multiple of 16 when nfiles > 1 */
 int vga_idsp_write_device(const vga_idsp_params *p, int nch, int nfiles, const uint8_t *d_adpcm, int64_t adpcm_pitch,
                           int adpcm_len, const int16_t *d_coefs, const int16_t *d_gain, const int16_t *d_start_context,
                           const int16_t *d_loop_context, uint8_t *d_files, int64_t file_pitch, void *stream);
@@ -573,6 +583,7 @@ typedef struct {
 /* VGA_ERR_INVALID_DATA for a missing magic, reads past the end, no channels, a zero interleave, audio past the end;
  * VGA_ERR_INVALID_OP for more than 255 channels */
 int vga_idsp_parse(const uint8_t *file, size_t size, vga_idsp_info *out);
+/* layout as vga_hps_read_device: images and rows at any byte, any pitch that holds an image / a row */
 int vga_idsp_read_device(const vga_idsp_info *info, const uint8_t *d_files, int64_t file_pitch, int nfiles, uint8_t *d_adpcm,
                          int64_t adpcm_pitch, void *stream);
 int vga_idsp_read(const uint8_t *file, size_t size, const vga_idsp_info *info, uint8_t *const *adpcm_out);
@@ -697,7 +708,9 @@ int vga_adx_file_layout_for(const vga_adx_file_params *p, int nch, vga_adx_file_
  * file_out: layout.file_size bytes */
 int vga_adx_write(const uint8_t *const *audio, int audio_len, const int16_t *history, int nch,
                   const vga_adx_file_params *p, uint8_t *file_out);
-/* device-resident: d_audio rows audio_pitch bytes apart and d_history as vga_adx_encode_device leaves them */
+/* device-resident: d_audio rows audio_pitch bytes apart and d_history as vga_adx_encode_device leaves them.  Layout:
+ * d_audio and d_file (layout.file_size bytes, all written) at any byte, audio_pitch anything >= audio_len (less:
+ * VGA_ERR_ARGUMENT), d_history at any short boundary */
 int vga_adx_write_device(const uint8_t *d_audio, int64_t audio_pitch, int audio_len, const int16_t *d_history, int nch,
                          const vga_adx_file_params *p, uint8_t *d_file, void *stream);
 
@@ -830,6 +843,9 @@ int vga_hca_decode_device(const vga_hca_info *info, const uint8_t *d_frames, int
  * Synthetic PCM16 source for benchmarks/tests: integer-only,
  * counter-based; bit-identical to vgaudio_amd/synth.py.  d_params: nch x 4
  * uint32 {f_inc, phi, amp, lfo_inc}; channel ids first_channel..+nch.
+ * Layout: d_pcm at any sample boundary, pcm_pitch anything >= length
+ * (less: VGA_ERR_ARGUMENT), d_params at any uint32 boundary; the samples
+ * behind a row are left alone.
  * ====================================================================== */
 int vga_synth_pcm16_device(int16_t *d_pcm, int64_t pcm_pitch, int nch, int length,
                            int first_channel, const uint32_t *d_params, void *stream);
@@ -847,7 +863,9 @@ int vga_hca_file_header(const vga_hca_info *info, const char *comment, float vol
                         int encrypted_ids, uint8_t *header_out /* info->header_size bytes */);   /* WriteHeader (:57-82); host only */
 int vga_hca_write(const vga_hca_info *info, const uint8_t *frames, const char *comment, float volume,
                   int encryption_type, int encrypted_ids, uint8_t *file_out);   /* host memory; header + copy */
-/* nstreams equally shaped streams: image s (file_pitch apart) = header + the frames of stream s (frames_pitch apart) */
+/* nstreams equally shaped streams: image s (file_pitch apart) = header + the frames of stream s (frames_pitch apart).
+ * Layout: d_frames and d_files at any byte; frames_pitch anything >= frame_size * frame_count and file_pitch anything >=
+ * vga_hca_file_size (no multiple-of-16 rule here; less: VGA_ERR_ARGUMENT); no byte between two images is written */
 int vga_hca_write_device(const vga_hca_info *info, const uint8_t *d_frames, int64_t frames_pitch, int nstreams,
                          const char *comment, float volume, int encryption_type, int encrypted_ids, uint8_t *d_files,
                          int64_t file_pitch, void *stream);

@@ -69,8 +69,9 @@ int vga_nwwav_read(const uint8_t *file, size_t size, const vga_nwwav_info *info,
  *   d_pcm16  PCM16 rows as int16 in HOST order (ToShortArray(structure.Endianness)), rows rounded up to 8 samples.
  *   d_pcm8   PCM8 rows as stored (signed), rows rounded up to 16 bytes; vga_pcm8_decode_device with signed_ = 1 over
  *            the whole buffer as one row gives PCM16 at the same offsets.
- * Round-up bytes are written as zeros.  All three buffers must be 16-byte aligned and hold what the size calls say
- * (0: the pointer may be null).  create needs a device (the tables live in its memory); the object may be used by any
+ * Round-up bytes are written as zeros.  All three buffers must be 16-byte aligned (else VGA_ERR_ARGUMENT, nothing is
+ * written) and hold what the size calls say (0: the pointer may be null); no byte outside them is written.  d_files
+ * may lie at any byte.  create needs a device (the tables live in its memory); the object may be used by any
  * number of reads.
  * -------------------------------------------------------------------- */
 typedef struct vga_nwwav_bank vga_nwwav_bank;

@@ -27,6 +27,8 @@ extern "C" {
  * Pcm8Codec (VGAudio/Codecs/Pcm8/Pcm8Codec.cs) over nrows pitched planar rows of n samples.
  * signed_ = 0: Encode (s + 0x8000) >> 8 / Decode (b - 0x80) << 8 (Pcm8Format, WAVE);
  * signed_ = 1: EncodeSigned s >> 8 / DecodeSigned (sbyte)b << 8 (Pcm8SignedFormat, NW streams).
+ * Layout: byte rows at any byte, int16 rows at any short boundary, both pitches (in elements) anything >= n (less:
+ * VGA_ERR_ARGUMENT); the elements behind a row are left alone.
  * -------------------------------------------------------------------- */
 int vga_pcm8_encode_device(const int16_t *d_pcm, int64_t pcm_pitch, int n, int nrows, int signed_, uint8_t *d_out,
                            int64_t out_pitch, void *stream);
@@ -54,7 +56,9 @@ int vga_pcm8_decode_device(const uint8_t *d_in, int64_t in_pitch, int n, int nro
 int vga_nwstm_pcm_layout_for(const vga_nwstm_params *p, int codec, int nch, vga_nwstm_layout *out);
 /* nfiles equally shaped images; file f's channel c is row f*nch+c of d_samples (params.sample_count samples each,
  * pitch in elements of sample_kind); image f at d_files + f*file_pitch (file_pitch >= layout.file_size and a
- * multiple of 16 when nfiles > 1); every byte of each image is written */
+ * multiple of 16 when nfiles > 1); every byte of each image is written.  Layout: d_files at any byte, d_samples at any
+ * element boundary, pitch anything >= params.sample_count; a smaller pitch or a file_pitch off 16 is VGA_ERR_ARGUMENT
+ * and writes nothing; no byte between two images is written */
 int vga_nwstm_pcm_write_device(const vga_nwstm_params *p, int codec, int nch, int nfiles, const vga_nw_track *tracks,
                                const void *d_samples, int sample_kind, int64_t pitch, uint8_t *d_files,
                                int64_t file_pitch, void *stream);
@@ -66,7 +70,9 @@ int vga_nwstm_pcm_write(const vga_nwstm_params *p, int codec, int nch, const vga
  * stream (read it with vga_nwstm_parse) and any other codec give VGA_ERR_INVALID_OP. */
 int vga_nwstm_pcm_parse(const uint8_t *file, size_t size, vga_nwstm_info *out);
 /* nfiles images sharing one parsed geometry -> row f*channel_count+c of d_samples (info->sample_count elements of
- * sample_kind per row, pitch in elements) */
+ * sample_kind per row, pitch in elements).  Layout: images at any byte on any file_pitch that holds one (checked
+ * when nfiles > 1), rows at any element boundary, pitch anything >= info->sample_count (less: VGA_ERR_ARGUMENT); the
+ * elements behind a row are left alone */
 int vga_nwstm_pcm_read_device(const vga_nwstm_info *info, const uint8_t *d_files, int64_t file_pitch, int nfiles,
                               void *d_samples, int sample_kind, int64_t pitch, void *stream);
 /* host form: out[c] info->sample_count elements of sample_kind */
@@ -77,6 +83,8 @@ int vga_nwstm_pcm_read(const uint8_t *file, size_t size, const vga_nwstm_info *i
  * the 16-bit one with 8-bit fields (block align nch, nch bytes per second per hertz, 8 valid bits in the extensible
  * fmt chunk above 2 channels); the data chunk holds nch * sample_count bytes, odd sizes included.  Samples are
  * unsigned: from VGA_SAMPLES_S16 rows the writer applies Pcm8Codec.Encode and the reader Pcm8Codec.Decode.
+ * Layout of the _device calls: d_file / d_data at any byte, rows at any element boundary, pitch (in elements) anything
+ * >= the sample count (less: VGA_ERR_ARGUMENT); the elements behind a row are left alone.
  * -------------------------------------------------------------------- */
 int64_t vga_wave_pcm8_file_size(const vga_wave_params *p, int nch);        /* < 0 = error */
 int vga_wave_write_pcm8(const void *const *samples, int sample_kind, int nch, const vga_wave_params *p, uint8_t *file_out);
