@@ -82,7 +82,7 @@ def test_volume_bound_and_empty_units():
     order, begin, clen, cgrp = plan(group, length)
     assert np.all(np.diff(begin) <= 512)
     check(group, length, order, begin, clen, cgrp, 1024, 1024 * 2880000)
-    # empty units (an ADX channel with no samples keeps a group of its own, capi_adx.hip) and an empty batch
+    # empty units (an ADX channel with no samples keeps a group of its own, capi_adx_v.hip) and an empty batch
     length = np.array([0, 5, 0, 48000, 0], dtype=np.int32)
     group = np.array([1, 0, 1, 0, 1], dtype=np.int32)
     order, begin, clen, cgrp = plan(group, length)

@@ -1,12 +1,15 @@
-// adx_host.hpp -- the host side of CRI ADX without HIP: the parameter check of every entry point, the encoded size, and for a
-// ragged device-resident batch (include/vgaudio_hip/adx_ragged.h) the packed layout, the longest-first work slots, the time
-// pieces and the table of (group, piece) items the kernels are launched over, and how the caller's workspace is cut.
+// adx_host.hpp -- the host side of CRI ADX without HIP: the predictor coefficients and the kernels' parameters, the
+// CriAdxHelpers conversions, the sizes, every entry point's argument checks, the time pieces and their figures, and for a
+// ragged device-resident batch (include/vgaudio_hip/adx_ragged.h) the packed layout, the longest-first work slots, the table
+// of (group, piece) items the kernels are launched over, and how the caller's workspace is cut.
 // Header-only and free of <hip/hip_runtime.h>, so that a stand-alone host program can include it
-// (tests/host/adx_host_driver.cpp) as the C-ABI files do; whoever includes it supplies vga::set_error.
+// (tests/host/adx_host_driver.cpp) as the kernel and C-ABI files do (adx_kernels.hpp); whoever includes it supplies vga::set_error.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <numeric>
 #include <vector>
 
@@ -38,21 +41,166 @@ inline int validate(const vga_adx_params *p)
     return VGA_OK;
 }
 
-// frames / bytes of CriAdxCodec.Encode's output (CriAdxCodec.cs:59-62) for valid parameters
+// ---- the predictor coefficients (CriAdxCodec.cs:173-191; host side: libm cos / sqrt, as the reference uses Math.Cos / Math.Sqrt)
+constexpr int16_t FIXED_COEFS[4][2] = {{0, 0}, {0x0F00, 0}, {0x1CC0, (int16_t)0xF300}, {0x1880, (int16_t)0xF240}};
+inline void calculate_coefficients(int highpass_freq, int sample_rate, int16_t coefs[2])
+{
+    const double sqrt2 = std::sqrt(2.0);
+    const double a = sqrt2 - std::cos(2.0 * M_PI * highpass_freq / sample_rate);
+    const double b = sqrt2 - 1;
+    const double c = (a - std::sqrt((a + b) * (a - b))) / b;
+    coefs[0] = (int16_t)(int)(c * 8192);
+    coefs[1] = (int16_t)(int)(c * c * -4096);
+}
+// What the kernels take: CriAdxParameters (Codecs/CriAdx/CriAdxParameters.cs:5-12) with the two predictor coefficients
+// resolved on the host (Fixed: Coefs[Filter]; else CalculateCoefficients).  Eight ints without padding: equal values are equal bytes.
+struct AdxDeviceParams {
+    int frame_size, version, type, filter, padding, history;   // type: 2 Fixed, 3 Linear, 4 Exponential
+    int coef0, coef1;
+};
+// ... of valid parameters: the encoder's high-pass is 500 Hz (CriAdxCodec.cs:64), the decoder takes the stream's (:13)
+inline AdxDeviceParams make_device_params(const vga_adx_params *p, bool encode)
+{
+    int16_t c[2] = {FIXED_COEFS[p->filter & 3][0], FIXED_COEFS[p->filter & 3][1]};
+    if (p->type != 2) calculate_coefficients(encode ? 500 : p->highpass_frequency, p->sample_rate, c);
+    return {p->frame_size, p->version, p->type, p->filter, p->padding, p->history, c[0], c[1]};
+}
+
+// ---- Formats/CriAdx/CriAdxHelpers.cs:7-31
+inline int nibble_count_to_sample_count(int nibble_count, int frame_size)
+{
+    const int npf = frame_size * 2, spf = npf - 4;
+    const int frames = nibble_count / npf, extra = nibble_count % npf;
+    return spf * frames + (extra < 4 ? 0 : extra - 4);
+}
+inline int sample_count_to_nibble_count(int sample_count, int frame_size)
+{
+    const int npf = frame_size * 2, spf = npf - 4;
+    const int frames = sample_count / spf, extra = sample_count % spf;
+    return npf * frames + (extra == 0 ? 0 : extra + 4);
+}
+inline int sample_count_to_byte_count(int sample_count, int frame_size)
+{
+    const int n = sample_count_to_nibble_count(sample_count, frame_size);
+    return (n / 2) + (n & 1);
+}
+
+// ---- sizes
+// Extensions.cs:145, (int)Math.Ceiling((double)v / d), for every int v and d > 0: the quotient truncates towards zero, so
+// only a positive remainder rounds up (-7 / 2 is -3 and stays -3)
+inline int divide_by_round_up(int v, int d) { return v / d + (v % d > 0 ? 1 : 0); }
+// Bytes of CriAdxCodec.Encode's output (CriAdxCodec.cs:59-62) as the reference computes them and vga_adx_encoded_byte_count
+// returns them: in ints, so pcm_length + padding wraps above 2^31 - 1 and so does the product -- where encoded_bytes() parts.
+inline int encoded_byte_count(int pcm_length, const vga_adx_params &p) { return divide_by_round_up(pcm_length + p.padding, (p.frame_size - 2) * 2) * p.frame_size; }
+// ... and without the wrap, for make_layout, which refuses a stream above 2 GiB: equal while pcm_length + padding and the bytes fit an int
 inline int64_t encoded_frames(int pcm_length, const vga_adx_params &p)
 {
     const int spf = (p.frame_size - 2) * 2;
     return ((int64_t)pcm_length + p.padding + spf - 1) / spf;
 }
 inline int64_t encoded_bytes(int pcm_length, const vga_adx_params &p) { return encoded_frames(pcm_length, p) * p.frame_size; }
+// bytes CriAdxCodec.Decode reads (CriAdxCodec.cs:18-24): up to the frame the padding ends in, then ceil(sample_count / spf) frames
+inline int64_t decode_bytes_read(int sample_count, const vga_adx_params &p)
+{
+    const int spf = (p.frame_size - 2) * 2;
+    return (int64_t)(p.padding / spf) * p.frame_size + (int64_t)divide_by_round_up(sample_count, spf) * p.frame_size;
+}
+
+// a channel's own frames of the padded stream in a bucket of the ragged host encoder (d_own_frames): the 18-byte kernels', of 32 samples
+constexpr int OWN_FRAME_SAMPLES = 32;
+inline int own_frames(int pcm_length, const vga_adx_params &p) { return divide_by_round_up(pcm_length + p.padding, OWN_FRAME_SAMPLES); }
+
+// ---- argument checks, each list in the order its entry point applies it: of two bad arguments the first one's message is
+// the call's.  A call with nothing to do (no channels, no samples) passes: the caller asks again.
+inline int check_pcm_not_empty(int pcm_length, const vga_adx_params &p, int channel = -1)   // channel >= 0: of a ragged call
+{
+    if (pcm_length != 0 || p.version != 4 || p.padding != 0) return VGA_OK;
+    char who[32] = "";
+    if (channel >= 0) snprintf(who, sizeof who, "channel %d: ", channel);
+    set_error("%sempty PCM: the reference reads pcm[0] (CriAdxCodec.cs:71)", who);
+    return VGA_ERR_ARGUMENT;
+}
+// the row arrays of an equal-length call, if it is one of host rows (in_needed: the input rows hold something)
+inline int check_rows(bool host_rows, const void *const *in, const void *const *out, int nch, bool in_needed)
+{
+    if (!host_rows) return VGA_OK;
+    if (!in || !out) { set_error("null channel array"); return VGA_ERR_ARGUMENT; }
+    for (int c = 0; c < nch; c++)
+        if ((!in[c] && in_needed) || !out[c]) { set_error("channel %d is null", c); return VGA_ERR_ARGUMENT; }
+    return VGA_OK;
+}
+// an equal-length encode; host_rows: of the host rows (pcm, out), else of device rows: check_encode_device_layout follows
+inline int check_encode(const vga_adx_params *p, int nch, int pcm_length, bool host_rows = false, const int16_t *const *pcm = nullptr, uint8_t *const *out = nullptr)
+{
+    if (int rc = validate(p)) return rc;
+    if (nch < 0 || pcm_length < 0) { set_error("negative size"); return VGA_ERR_ARGUMENT; }
+    if (nch == 0) return VGA_OK;
+    if (int rc = check_rows(host_rows, (const void *const *)pcm, (const void *const *)out, nch, pcm_length > 0)) return rc;
+    return check_pcm_not_empty(pcm_length, *p);
+}
+inline int check_encode_device_layout(int64_t pcm_pitch, int pcm_length, const void *d_out, int64_t out_pitch, int nbytes)
+{
+    if (pcm_pitch >= pcm_length && out_pitch >= nbytes && !(out_pitch & 1) && !((uintptr_t)d_out & 1)) return VGA_OK;
+    set_error("bad pitch/alignment (pcm_pitch=%lld, out_pitch=%lld, need >= %d and even)", (long long)pcm_pitch, (long long)out_pitch, nbytes);
+    return VGA_ERR_ARGUMENT;
+}
+// the stream holds what the decoder reads (IndexOutOfRange in C#) and the device rows their lengths: one refusal
+inline int check_decode_device_layout(int adpcm_length, int64_t in_pitch, int sample_count, int64_t pcm_pitch, const vga_adx_params &p)
+{
+    const long long need = decode_bytes_read(sample_count, p);
+    if (adpcm_length >= need && in_pitch >= adpcm_length && pcm_pitch >= sample_count) return VGA_OK;
+    set_error("ADX stream too short: %d bytes, decoder reads %lld", adpcm_length, need);
+    return VGA_ERR_ARGUMENT;
+}
+// an equal-length decode of device rows at (in_pitch, pcm_pitch), or of the host rows (adpcm, pcm_out): their pitches are their lengths
+inline int check_decode(const vga_adx_params *p, int adpcm_length, int nch, int sample_count, int64_t in_pitch, int64_t pcm_pitch,
+                        bool host_rows = false, const uint8_t *const *adpcm = nullptr, int16_t *const *pcm_out = nullptr)
+{
+    if (int rc = validate(p)) return rc;
+    if (nch < 0 || sample_count < 0 || adpcm_length < 0) { set_error("negative size"); return VGA_ERR_ARGUMENT; }
+    if (nch == 0 || sample_count == 0) return VGA_OK;
+    if (int rc = check_rows(host_rows, (const void *const *)adpcm, (const void *const *)pcm_out, nch, true)) return rc;
+    return check_decode_device_layout(adpcm_length, in_pitch, sample_count, pcm_pitch, *p);
+}
+// the ragged host calls: the arrays, then channel by channel
+inline int check_encode_v(const int16_t *const *pcm, const int *lengths, int nch, const vga_adx_params *params, uint8_t *const *out)
+{
+    if (nch < 0) { set_error("negative channel count"); return VGA_ERR_ARGUMENT; }
+    if (nch == 0) return VGA_OK;
+    if (!pcm || !lengths || !params || !out) { set_error("null array"); return VGA_ERR_ARGUMENT; }
+    for (int c = 0; c < nch; c++) {
+        if (int rc = validate(&params[c])) return rc;
+        if (lengths[c] < 0) { set_error("channel %d: negative length", c); return VGA_ERR_ARGUMENT; }
+        if (int rc = check_pcm_not_empty(lengths[c], params[c], c)) return rc;
+        if ((!pcm[c] && lengths[c] > 0) || !out[c]) { set_error("channel %d is null", c); return VGA_ERR_ARGUMENT; }
+    }
+    return VGA_OK;
+}
+inline size_t decode_bytes_read_v(int sample_count, const vga_adx_params &p) { return sample_count == 0 ? 0 : (size_t)decode_bytes_read(sample_count, p); }
+inline int check_decode_v(const uint8_t *const *adpcm, const int *adpcm_lengths, int nch, const int *sample_counts,
+                          const vga_adx_params *params, int16_t *const *pcm_out)
+{
+    if (nch < 0) { set_error("negative channel count"); return VGA_ERR_ARGUMENT; }
+    if (nch == 0) return VGA_OK;
+    if (!adpcm || !adpcm_lengths || !sample_counts || !params || !pcm_out) { set_error("null array"); return VGA_ERR_ARGUMENT; }
+    for (int c = 0; c < nch; c++) {
+        if (int rc = validate(&params[c])) return rc;
+        if (sample_counts[c] < 0 || adpcm_lengths[c] < 0) { set_error("channel %d: negative size", c); return VGA_ERR_ARGUMENT; }
+        const size_t need = decode_bytes_read_v(sample_counts[c], params[c]);
+        if ((size_t)adpcm_lengths[c] < need) {
+            set_error("channel %d: ADX stream too short: %d bytes, decoder reads %zu", c, adpcm_lengths[c], need);
+            return VGA_ERR_ARGUMENT;
+        }
+        if (sample_counts[c] > 0 && (!adpcm[c] || !pcm_out[c])) { set_error("channel %d is null", c); return VGA_ERR_ARGUMENT; }
+    }
+    return VGA_OK;
+}
 
 // ---- time pieces (seams.hpp's plan_pieces with the test hook's count as an argument): `want` pieces of a stream of
 // `frames` frames, each at least `min_frames` long, at most MAX_PIECES; hook > 0 wins, down to pieces of `hook_floor`
 // frames.  seg_frames is a multiple of `align`.
 constexpr int MAX_PIECES = 64;
-struct Pieces {
-    int segments = 1, seg_frames = 2;
-};
+struct Pieces { int segments = 1, seg_frames = 2; };
 inline Pieces cut_pieces(int frames, int want, int min_frames, int hook_floor, int align, int hook)
 {
     int segments = want;
@@ -61,14 +209,12 @@ inline Pieces cut_pieces(int frames, int want, int min_frames, int hook_floor, i
     if (segments > MAX_PIECES) segments = MAX_PIECES;
     if (hook > 0) segments = std::min(std::max(frames / hook_floor, 1), hook);
     if (segments > MAX_PIECES) segments = MAX_PIECES;
-    Pieces out;
-    out.segments = segments;
-    out.seg_frames = std::max(((frames + segments - 1) / segments + align - 1) / align * align, align);
-    return out;
+    return {segments, std::max(((frames + segments - 1) / segments + align - 1) / align * align, align)};
 }
-// the launchers' figures (adx_kernels.hip: launch_encode / launch_decode)
+// The pieces' figures, of the equal-length launchers (adx_kernels.hip, which says what was measured) and of the ragged plan
+// below alike: waves per SIMD, a piece's least frames, the same under the test hook; a piece is a multiple of PIECE_ALIGN_FRAMES
 constexpr int ENCODE_WAVES_PER_SIMD = 2, ENCODE_MIN_PIECE_FRAMES = 2560, ENCODE_HOOK_FLOOR = 64;
-constexpr int DECODE_WAVES_PER_SIMD = 1, DECODE_MIN_PIECE_FRAMES = 512, DECODE_HOOK_FLOOR = 8;
+constexpr int DECODE_WAVES_PER_SIMD = 1, DECODE_MIN_PIECE_FRAMES = 512, DECODE_HOOK_FLOOR = 8, PIECE_ALIGN_FRAMES = 2;
 
 // ---- ragged batches
 constexpr int64_t GUARD_BYTES = 256;      // after the last row of a packed buffer (gc::GUARD_BYTES): clamped loads of short rows stay inside
@@ -197,8 +343,8 @@ inline RaggedPlan make_plan(const RaggedLayout &L, int cus, int hook, bool encod
     const int frames = L.group_frames[0];
     const int64_t waves = (int64_t)cus * 4 * (encode ? ENCODE_WAVES_PER_SIMD : DECODE_WAVES_PER_SIMD);
     const int want = (int)std::min<int64_t>(MAX_PIECES, frames > 0 ? waves * frames / (L.lane_frames / GROUP_SLOTS) : waves / groups);
-    plan.pieces = encode ? cut_pieces(frames, want, ENCODE_MIN_PIECE_FRAMES, ENCODE_HOOK_FLOOR, 2, hook)
-                         : cut_pieces(frames, want, DECODE_MIN_PIECE_FRAMES, DECODE_HOOK_FLOOR, 2, hook);
+    plan.pieces = encode ? cut_pieces(frames, want, ENCODE_MIN_PIECE_FRAMES, ENCODE_HOOK_FLOOR, PIECE_ALIGN_FRAMES, hook)
+                         : cut_pieces(frames, want, DECODE_MIN_PIECE_FRAMES, DECODE_HOOK_FLOOR, PIECE_ALIGN_FRAMES, hook);
     for (int g = 0; g < groups; g++)
         for (int k = 0; k < plan.pieces.segments && (int64_t)k * plan.pieces.seg_frames < L.group_frames[g]; k++) {
             plan.items.push_back(g);

@@ -651,9 +651,8 @@ __global__ __launch_bounds__(64) void adx_encode_fs18_tail_kernel(
 // The one-wave encoder's pieces: two waves on every SIMD, each piece at least this long (a seam takes 200 frames to close on
 // average and 2500 for the longest of configs[2]'s 127 000, tests/host/analysis/adx_seam_stats.c; one still open at the end
 // of its piece carries on in the tail kernel).  The fix-up's lanes take seams from a queue: one persistent wave per SIMD
-// (profiles/r04_e_adx_parts.log: 512 / 1024 / 2048 waves 5.8 / 5.4 / 6.4 ms).
-constexpr int ADX_DIRECT_WAVES_PER_SIMD = 2;
-constexpr int ADX_DIRECT_MIN_PIECE_FRAMES = 2560;
+// (profiles/r04_e_adx_parts.log: 512 / 1024 / 2048 waves 5.8 / 5.4 / 6.4 ms).  The pieces' figures are adx_host.hpp's
+// ENCODE_* and DECODE_*, which the ragged plan reads too.
 constexpr int ADX_FIXUP_WAVES_PER_SIMD = 1;
 
 int launch_encode(const int16_t *d_pcm, int64_t pcm_pitch, int nch, int pcm_length, const AdxDeviceParams &p,
@@ -673,12 +672,12 @@ int launch_encode(const int16_t *d_pcm, int64_t pcm_pitch, int nch, int pcm_leng
         d_pcm -= p.padding;                            // from here on d_pcm / pcm_length are the STREAM's
         pcm_length += p.padding;
         const bool v4 = p.version == 4, ex = p.type == 4;
-        // as many time segments as put ADX_DIRECT_WAVES_PER_SIMD waves on every SIMD, each an even number of frames and at
-        // least ADX_DIRECT_MIN_PIECE_FRAMES long
+        // as many time segments as put ENCODE_WAVES_PER_SIMD waves on every SIMD, each an even number of frames and at
+        // least ENCODE_MIN_PIECE_FRAMES long
         const int groups64 = (nch + 63) / 64;
         const int cus = device_cu_count();
         const int frames = (pcm_length + 31) / 32;
-        const PiecePlan plan = plan_pieces(frames, cus * 4 * ADX_DIRECT_WAVES_PER_SIMD / groups64, ADX_DIRECT_MIN_PIECE_FRAMES, 64, 2);
+        const PiecePlan plan = plan_pieces(frames, cus * 4 * ENCODE_WAVES_PER_SIMD / groups64, ENCODE_MIN_PIECE_FRAMES, ENCODE_HOOK_FLOOR, PIECE_ALIGN_FRAMES);
         const int segments = plan.segments, seg_frames = plan.seg_frames;
         AsyncBuf scratch;                              // freed (stream-ordered) on every exit path
         int16_t *seg_state = nullptr;                  // [segments][nch][2] final histories, then [nch] first open seam
@@ -763,13 +762,13 @@ int launch_decode(const uint8_t *d_adpcm, int64_t in_pitch, int nch, int sample_
             d_pcm -= p.padding;
             sample_count = decoded + p.padding;
         }
-        // as many time pieces as put ONE wave on every SIMD (a wave = 64 channels of one piece), each at least 512 frames long
-        // and an even number of frames.  The kernel is bound by its stores, and what the memory system holds open is one
+        // as many time pieces as put ONE wave on every SIMD (DECODE_WAVES_PER_SIMD; a wave = 64 channels of one piece), each at
+        // least DECODE_MIN_PIECE_FRAMES (512) frames long and an even number of frames.  The kernel is bound by its stores, and what the memory system holds open is one
         // row position per (channel, piece): at configs[2] 8 / 16 / 32 / 64 pieces take 8.5 / 8.0 / 13.1 / 12.1 ms (and 12 or
         // 24, which leave some SIMDs with two waves and some with one, 11 ms)
         const int groups = (nch + 63) / 64;
         const int frames = (sample_count + 31) / 32;
-        const PiecePlan plan = plan_pieces(frames, device_cu_count() * 4 / groups, 512, 8, 2);
+        const PiecePlan plan = plan_pieces(frames, device_cu_count() * 4 * DECODE_WAVES_PER_SIMD / groups, DECODE_MIN_PIECE_FRAMES, DECODE_HOOK_FLOOR, PIECE_ALIGN_FRAMES);
         const int segments = plan.segments, seg_frames = plan.seg_frames;
         DecodeSeams ds;
         if (segments > 1)

@@ -1,28 +1,11 @@
 // adx_kernels.hpp -- launchers for the CRI ADX kernels (device pointers).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <cstdint>
 
-#include "../../include/vgaudio_hip.h"
+#include "adx_host.hpp"                    // AdxDeviceParams and make_device_params, the pieces' figures
 
 namespace vga {
 namespace adx {
-
-// CriAdxParameters (Codecs/CriAdx/CriAdxParameters.cs:5-12) with the two predictor
-// coefficients already resolved on the host (Fixed: Coefs[Filter]; else CalculateCoefficients).
-struct AdxDeviceParams {
-    int frame_size;
-    int version;
-    int type;       // 2 Fixed, 3 Linear, 4 Exponential
-    int filter;
-    int padding;
-    int history;
-    int coef0, coef1;
-};
-
-// the kernels' parameters of a valid vga_adx_params (capi_adx.hip): the encoder's high-pass is 500 Hz (CriAdxCodec.cs:64), the
-// decoder takes the stream's (:13)
-AdxDeviceParams make_device_params(const vga_adx_params *p, bool encode);
 
 // d_own_frames / d_own_samples (device, one int per channel; nullptr: every channel is pcm_length / sample_count long): the
 // channels are shorter streams zero-padded to the launch's length (the ragged entry points' length buckets) -- what lies past

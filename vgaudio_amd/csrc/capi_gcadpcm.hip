@@ -279,7 +279,7 @@ static int decode_batch_one(const uint8_t *const *adpcm, const int16_t *coefs, i
                                  b.h1.p ? b.h1.as<int16_t>() + first : nullptr, b.h2.p ? b.h2.as<int16_t>() + first : nullptr,
                                  b.pcm.as<int16_t>() + (int64_t)first * b.pcm_pitch, b.pcm_pitch, b.status.as<int>(), s);
     });
-    return gc::run_status_job(job, 2 * GC_CHUNK_CHANNELS, b.status);
+    return run_status_job(job, 2 * GC_CHUNK_CHANNELS, b.status, gc::BAD_PREDICTOR);
 }
 
 int vga_gcadpcm_decode_batch(const uint8_t *const *adpcm, const int16_t *coefs, int nch, int sample_count,

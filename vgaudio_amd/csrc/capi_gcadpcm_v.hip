@@ -247,7 +247,7 @@ int decode_batch_v_rows(const uint8_t *const *adpcm, const int16_t *coefs, const
                                          call.pcm.as<int16_t>(), call.status.as<int>(), s);
         return rc;
     });
-    return gc::run_status_job(job, nch, call.status);
+    return run_status_job(job, nch, call.status, gc::BAD_PREDICTOR);
 }
 
 // the rows longest first (gc::LongestFirst); results go back to the caller's rows

@@ -36,18 +36,8 @@ inline int upload_hist(DevBuf &d_h1, DevBuf &d_h2, int nch, const int16_t *h1, c
     return VGA_OK;
 }
 
-// the tail of a decode job: the pipeline, then the decoder's status word as the call's error
-inline int run_status_job(pipe::Job &job, int chunk_units, DevBuf &d_status)
-{
-    if (int rc = run_batch_pipeline(job, chunk_units)) return rc;
-    int status = 0;
-    VGA_HIP_TRY(hipMemcpy(&status, d_status.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (status != 0) {
-        set_error("a frame header names predictor > 7 (the reference throws IndexOutOfRangeException)");
-        return VGA_ERR_ARGUMENT;
-    }
-    return VGA_OK;
-}
+// a decode job's status word as the call's error (run_status_job, host_batch.hpp)
+constexpr const char *BAD_PREDICTOR = "a frame header names predictor > 7 (the reference throws IndexOutOfRangeException)";
 
 // Shapes of one group of channels as the kernels index them: the rows' layout (gc_host.hpp) and the work plan, which asks
 // the kernel files (coefficient records, five-wave channels, the encoder's pieces).

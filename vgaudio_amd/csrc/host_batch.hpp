@@ -276,6 +276,19 @@ inline int run_batch_pipeline(pipe::Job &job, int default_chunk_units)
     return VGA_OK;
 }
 
+// the tail of a decode job (GC-ADPCM, ADX): the pipeline, then the decoders' status word as the call's error, `message`
+inline int run_status_job(pipe::Job &job, int chunk_units, DevBuf &d_status, const char *message)
+{
+    if (int rc = run_batch_pipeline(job, chunk_units)) return rc;
+    int status = 0;
+    VGA_HIP_TRY(hipMemcpy(&status, d_status.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (status != 0) {
+        set_error("%s", message);
+        return VGA_ERR_ARGUMENT;
+    }
+    return VGA_OK;
+}
+
 // ---------------------------------------------------------------- ragged calls by length buckets
 // The `_v` entry points of codecs whose kernels take one length per launch (ADX, HCA): units are sorted by (parameter
 // group, length) and cut into chunks whose lengths differ by at most a quarter; a chunk's rows are zero-padded on the
