@@ -199,6 +199,17 @@ SIGNATURES = {
     "vga_adx_ragged_offsets": (ci, [vp, C.POINTER(i64), C.POINTER(i64)]),
     "vga_adx_encode_device_v": (ci, [vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "vga_adx_decode_device_v": (ci, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
+    # include/vgaudio_hip/gc_files.h
+    "vga_gc_files_layout_for": (ci, [vp, ci, vp, C.POINTER(ci), C.POINTER(i64), C.POINTER(i64), vp]),
+    "vga_gc_files_create": (ci, [vp, ci, vp, C.POINTER(vp)]),
+    "vga_gc_files_create_from_dsp": (ci, [C.POINTER(vp), ci, C.POINTER(i64), C.POINTER(vp)]),
+    "vga_gc_files_destroy": (None, [vp]),
+    "vga_gc_files_totals_of": (ci, [vp, vp]),
+    "vga_gc_files_offsets": (ci, [vp, C.POINTER(ci), C.POINTER(i64), C.POINTER(i64)]),
+    "vga_gc_files_ragged": (vp, [vp]),
+    "vga_gcadpcm_build_channels_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "vga_dsp_write_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "vga_dsp_read_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "vga_hca_decode_device_v": (ci, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
     "vga_hca_encode_device_v": (ci, [vp, vp, vp, vp, vp]),
     "vga_hca_stream_create": (ci, [vp, vp, C.POINTER(vp)]),
@@ -358,6 +369,22 @@ class GcChannelLayoutC(C.Structure):
     """vga_gcadpcm_channel_layout"""
     _fields_ = [(n, C.c_int) for n in ("alignment_needed", "loop_start_aligned", "sample_count_aligned",
                                        "seek_table_entries")]
+
+
+class GcFileC(C.Structure):
+    """vga_gc_file (include/vgaudio_hip/gc_files.h)"""
+    _fields_ = [("channels", C.c_int), ("sample_rate", C.c_int), ("channel", GcChannelParamsC)]
+
+
+class DspFileConfigC(C.Structure):
+    """vga_dsp_file_config"""
+    _fields_ = [(n, C.c_int) for n in ("samples_per_interleave", "loop_point_alignment", "trim_file")]
+
+
+class GcFilesTotalsC(C.Structure):
+    """vga_gc_files_totals"""
+    _fields_ = [("files", C.c_int), ("channels", C.c_int), ("pcm_samples", C.c_int64), ("adpcm_bytes", C.c_int64),
+                ("seek_shorts", C.c_int64), ("image_bytes", C.c_int64), ("build_workspace_bytes", C.c_size_t)]
 
 
 NW_MAX_CHANNELS = NW_MAX_TRACKS = 255

@@ -429,14 +429,57 @@ class GcAdpcmFormat:
         return out.astype(">i2" if bigEndian else "<i2").tobytes()
 
 
-def encode_files(pcm16_list, configs=None):
+def _encode_files_to_dsp(files, configs, dsp):
+    """WAV set -> vga_gcadpcm_encode_device_v -> vga_gcadpcm_build_channels_device_v -> vga_dsp_write_device_v: the rows stay in
+    HBM from the upload of the PCM to the download of the packed images; no launch per file"""
+    import torch
+    from .dsp import file_set
+    L = _lib.lib()
+    s = file_set(files, dsp)
+    try:
+        if s.files == 0:
+            return []
+        t, nch = s.totals, s.channels
+        po = np.zeros(nch, dtype=np.int64)
+        check(L.vga_gcadpcm_ragged_offsets(s.ragged, po.ctypes.data_as(C.POINTER(C.c_int64)), None))
+        host = np.zeros(t.pcm_samples, dtype=np.int16)
+        h1, h2, c = np.zeros(nch, np.int16), np.zeros(nch, np.int16), 0
+        for f, cfg in zip(files, configs):
+            for ch in f.Channels:
+                host[po[c]:po[c] + f.SampleCount] = np.asarray(ch, dtype=np.int16)[:f.SampleCount]
+                h1[c], h2[c] = (cfg.History1, cfg.History2) if cfg else (0, 0)
+                c += 1
+        dev = lambda a: torch.from_numpy(a).cuda()
+        pcm, d_h1, d_h2 = dev(host), dev(h1), dev(h2)
+        coefs = torch.zeros(nch * 16, dtype=torch.int16, device="cuda")
+        adpcm = torch.zeros(t.adpcm_bytes, dtype=torch.uint8, device="cuda")
+        ws = torch.empty(max(L.vga_gcadpcm_ragged_coefs_workspace_bytes(s.ragged), t.build_workspace_bytes, 16), dtype=torch.uint8, device="cuda")
+        ctx = torch.zeros(nch * 3, dtype=torch.int16, device="cuda")
+        images = torch.empty(t.image_bytes, dtype=torch.uint8, device="cuda")
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(L.vga_gcadpcm_coefs_device_v(s.ragged, pcm.data_ptr(), coefs.data_ptr(), ws.data_ptr(), ws.numel(), st))
+        check(L.vga_gcadpcm_encode_device_v(s.ragged, pcm.data_ptr(), coefs.data_ptr(), d_h1.data_ptr(), d_h2.data_ptr(), adpcm.data_ptr(), st))
+        s.build_channels(adpcm, coefs, loop_context=ctx, workspace=ws)     # GcAdpcmChannel's loop context (DspWriter.cs:74-76)
+        s.write_images(adpcm, coefs, images, loop_context=ctx)
+        return s.split_images(images)
+    finally:
+        s.close()
+
+
+def encode_files(pcm16_list, configs=None, dsp=None):
     """The reference's batch conversion (VGAudio.Cli/Batch.cs:24-25: Parallel.ForEach over files, each file
     GcAdpcmFormat.EncodeFromPcm16) as ONE ragged GPU call (vga_gcadpcm_encode_batch_v): `pcm16_list` holds one
     Pcm16Format per file, of any length and channel count; returns one GcAdpcmFormat per file, each what
     GcAdpcmFormat().EncodeFromPcm16(file) returns.  configs: None or one GcAdpcmParameters (or None) per file
-    (History1 / History2; a SampleCount override takes the per-file path)."""
+    (History1 / History2; a SampleCount override takes the per-file path).
+    dsp: a DspConfiguration -- the call then returns one DSP file (`bytes`) per input file, each what
+    DspWriter(dsp).GetFile(GcAdpcmFormat().EncodeFromPcm16(file)) returns, assembled on the device (vgaudio_amd.dsp.DspFileSet)."""
     files = list(pcm16_list)
     configs = list(configs) if configs is not None else [None] * len(files)
+    if dsp is not None:
+        if any(c is not None and c.SampleCount != -1 for c in configs):
+            raise _lib.ArgumentError("encode_files(dsp=...): a SampleCount override is not supported")
+        return _encode_files_to_dsp(files, configs, dsp)
     if any(c is not None and c.SampleCount != -1 for c in configs):
         return [GcAdpcmFormat().EncodeFromPcm16(f, c) for f, c in zip(files, configs)]
     chans, counts, h1, h2 = [], [], [], []
