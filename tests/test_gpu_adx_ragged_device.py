@@ -26,10 +26,10 @@ CASES = {
     "vga_adx_ragged_offsets": ["test_layout_of_the_object_is_the_host_layout"],
     "vga_adx_encode_device_v": ["test_encode_and_decode_match_oracle", "test_channel_counts_around_a_group", "test_own_calls_agree",
                                 "test_general_path_for_other_frame_sizes_and_padded_streams", "test_uniform_object",
-                                "test_bytes_do_not_depend_on_poison", "test_round_trip_on_a_busy_stream_and_two_streams_at_once",
+                                "test_uniform_object_with_seams", "test_bytes_do_not_depend_on_poison", "test_round_trip_on_a_busy_stream_and_two_streams_at_once",
                                 "test_zero_length_channel_under_v4_without_padding", "test_refused_layouts_launch_nothing"],
     "vga_adx_decode_device_v": ["test_encode_and_decode_match_oracle", "test_channel_counts_around_a_group", "test_own_calls_agree",
-                                "test_general_path_for_other_frame_sizes_and_padded_streams",
+                                "test_general_path_for_other_frame_sizes_and_padded_streams", "test_uniform_object_with_seams",
                                 "test_bytes_do_not_depend_on_poison", "test_round_trip_on_a_busy_stream_and_two_streams_at_once",
                                 "test_bad_filter_index_marks_its_channel_only", "test_zero_length_channel_under_v4_without_padding",
                                 "test_refused_layouts_launch_nothing"],
@@ -357,6 +357,48 @@ def test_uniform_object():
         t.cuda.synchronize()
         assert np.array_equal(out.cpu().numpy(), adx.cpu().numpy()[:nch * out_pitch])
         assert np.array_equal(h.cpu().numpy(), hist.cpu().numpy()[:nch])
+
+
+def test_uniform_object_with_seams():
+    """70 channels of 24 589 samples -- 769 frames: twelve pieces under the hook (the encoder's at its 64-frame floor) and a
+    partial last frame -- under seam modes 0, 1 and 3: the packed object and ONE vga_adx_encode_device / vga_adx_decode_device
+    call on the same rounded pitches run their direct, fix-up, tail and REPAIR kernels on the same rows.  The kernels of the
+    two calls are shells over the same bodies, so both must write the same ADX bytes, histories, PCM and status words, and the
+    packed result is the oracle's"""
+    t, n, nch = torch(), 24589, 70
+    with hooks(12):
+        b = Batch("default", [n] * nch)                                # (the plan is made at create)
+    try:
+        v = stats(b.r)
+        assert (v[2], v[3], v[5], v[6]) == (12, 66, 12, 66)
+        pitch, nbytes = (n + 7) // 8 * 8, L().vga_adx_encoded_byte_count(n, C.byref(b.p))
+        out_pitch = (nbytes + 15) // 16 * 16
+        assert list(b.po) == [c * pitch for c in range(nch)] and list(b.ao) == [c * out_pitch for c in range(nch)]
+        for force in (0, 1, 3):
+            with hooks(12, force):                                     # (the equal-length call plans when it is called)
+                _, adx, hist = b.encode()
+                _, pcm, st = b.decode()
+                src = up(b.pcm_image())
+                out = t.full((nch * out_pitch,), JUNK, dtype=t.uint8, device="cuda")
+                h = t.zeros(nch, dtype=t.int16, device="cuda")
+                _lib.check(L().vga_adx_encode_device(src.data_ptr(), pitch, nch, n, C.byref(b.p), out.data_ptr(), out_pitch,
+                                                     h.data_ptr(), None))
+                back = t.full((nch * pitch,), SENTINEL, dtype=t.int16, device="cuda")
+                one = t.zeros(1, dtype=t.int32, device="cuda")
+                _lib.check(L().vga_adx_decode_device(out.data_ptr(), out_pitch, nbytes, nch, n, C.byref(b.p), back.data_ptr(), pitch,
+                                                     one.data_ptr(), None))
+                t.cuda.synchronize()
+            adx, hist, pcm, st = adx.cpu().numpy(), hist.cpu().numpy(), pcm.cpu().numpy(), st.cpu().numpy()
+            assert np.array_equal(out.cpu().numpy(), adx[:nch * out_pitch]), force
+            assert np.array_equal(h.cpu().numpy(), hist[:nch]), force
+            assert np.array_equal(back.cpu().numpy(), pcm[:nch * pitch]), force
+            assert np.all(st[:nch] == int(one.item())) and st[nch] == 0, force
+            b.check_adx(adx, ("uniform", force), hist)
+            b.check_pcm(pcm, ("uniform", force))
+            assert np.all(st == 0), force
+    finally:
+        torch().cuda.synchronize()
+        b.close()
 
 
 # ---------------------------------------------------------------- poison mode

@@ -15,10 +15,6 @@
 #include <cstdlib>
 #include <type_traits>
 
-#ifndef VGA_ADX_ABLATE
-#define VGA_ADX_ABLATE 0
-#endif
-
 namespace vga {
 namespace adx {
 
@@ -106,52 +102,16 @@ __global__ __launch_bounds__(64) void adx_decode_fs18_direct_kernel(
         const int c = blockIdx.x * 64 + lane / LPR + RPI * i;
         return pcm + (int64_t)(c < nch ? c : nch - 1) * pcm_pitch + first_frame * 32 + (lane % LPR) * 8;
     };
-    // one frame whose 18 bytes are w[0 .. 4] (little-endian dwords, two bytes of slack)
+    // one frame whose 18 bytes are w[0 .. 4] (adx_decode_frame), and where its samples go
     auto decode_frame = [&](const uint32_t (&w)[5], auto mode_tag, int frame, int valid, int skip = 0) {
-        constexpr int MODE = decltype(mode_tag)::value;          // 0: whole frame, stored turned; 1: whole frame, stored by its lane; 2: partial; 3: not stored (warm-up)
+        constexpr int MODE = decltype(mode_tag)::value;          // 0: whole frame, stored turned; 1: whole frame, stored by its lane; 2: partial
                                                                  // 4: samples [skip, valid) only: the frame in which a padded stream's samples begin
-        const int hb0 = w[0] & 0xff, hb1 = (w[0] >> 8) & 0xff;
-        int filter_num = ((hb0 >> 4) & 0xF) >> 1;
-        int cf0, cf1;
-        if (p.type == 2) {
-            if (filter_num > 3) { bad = true; filter_num = 3; }
-            cf0 = filter_num == 0 ? 0 : (filter_num == 1 ? 0x0F00 : (filter_num == 2 ? 0x1CC0 : 0x1880));
-            cf1 = filter_num == 0 ? 0 : (filter_num == 1 ? 0 : (filter_num == 2 ? (int)(int16_t)0xF300 : (int)(int16_t)0xF240));
-        } else {
-            if (filter_num > 0) bad = true;
-            cf0 = p.coef0;
-            cf1 = p.coef1;
-        }
-        int scale = (int)(int16_t)(((hb0 << 8) | hb1) & 0x1FFF);
-        scale = (int)(int16_t)(p.type == 4 ? (1 << ((12 - scale) & 31)) : scale + 1);
         int o[32];
-#pragma unroll
-        for (int s = 0; s < 32; s++) {
-            const int b = 2 + (s >> 1);                                    // the byte that holds sample s: high nibble first
-            const int nib = __builtin_amdgcn_sbfe((int)w[b >> 2], 8 * (b & 3) + ((s & 1) ? 0 : 4), 4);
-            int sample;
-            if (V4) {                                  // :38-39
-                int rest = __mul24(hist2, cf1);
-                asm("" : "+v"(rest));
-                sample = __mul24(scale, nib) + ((__mul24(hist1, cf0) + rest) >> 12);
-            } else {                                   // :41-42
-                int rest = (__mul24(hist2, cf1) >> 12) + __mul24(scale, nib);
-                asm("" : "+v"(rest));
-                sample = (__mul24(hist1, cf0) >> 12) + rest;
-            }
-            const int fin = clamp16(sample);
-            if (MODE != 4 || s >= skip) {              // (a padded stream's first samples are not decoded at all, :21-33)
-                hist2 = hist1;                         // a partial last frame runs on: nothing reads the history after it
-                hist1 = fin;
-            }
-            o[s] = fin;
-        }
+        adx_decode_frame<V4, MODE == 4>(w, p, hist1, hist2, bad, o, skip);
         if (MODE == 0) {
             int4 *mine = s_turn + lane * (LPR + 1) + (frame % TURN) * 4;
 #pragma unroll
-            for (int q = 0; q < 4; q++)
-                mine[q] = make_int4((o[8 * q] & 0xFFFF) | (o[8 * q + 1] << 16), (o[8 * q + 2] & 0xFFFF) | (o[8 * q + 3] << 16),
-                                    (o[8 * q + 4] & 0xFFFF) | (o[8 * q + 5] << 16), (o[8 * q + 6] & 0xFFFF) | (o[8 * q + 7] << 16));
+            for (int q = 0; q < 4; q++) mine[q] = adx_pack8(o, q);
             if (frame % TURN == TURN - 1) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -161,34 +121,12 @@ __global__ __launch_bounds__(64) void adx_decode_fs18_direct_kernel(
                 asm volatile("" ::: "memory");
             }
         } else if (MODE == 1) {
-            if (live) {
-                int16_t *d = dst + (int64_t)frame * 32;
-#pragma unroll
-                for (int q = 0; q < 4; q++)
-                    adx_store16(d + 8 * q,
-                                make_int4((o[8 * q] & 0xFFFF) | (o[8 * q + 1] << 16), (o[8 * q + 2] & 0xFFFF) | (o[8 * q + 3] << 16),
-                                          (o[8 * q + 4] & 0xFFFF) | (o[8 * q + 5] << 16), (o[8 * q + 6] & 0xFFFF) | (o[8 * q + 7] << 16)));
-            }
+            if (live) adx_store_frame(dst + (int64_t)frame * 32, o);
         } else if ((MODE == 2 || MODE == 4) && live) {
             int16_t *d = dst + (int64_t)frame * 32;
 #pragma unroll
             for (int s2 = 0; s2 < 32; s2++)
                 if (s2 >= skip && s2 < valid) d[s2] = (int16_t)o[s2];
-        }
-    };
-    // one frame of the row by its index (it starts on a dword for even i, two bytes after one for odd i)
-    auto load_frame = [&](int i, uint32_t (&w)[5]) {
-        const uint32_t *f = reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint16_t *>(src) + (int64_t)i * 9 - (i & 1));
-        uint32_t t[5];
-#pragma unroll
-        for (int q = 0; q < 5; q++) t[q] = f[q];
-        if (i & 1) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) w[q] = (t[q] >> 16) | (t[q + 1] << 16);
-            w[4] = t[4] >> 16;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 5; q++) w[q] = t[q];
         }
     };
     // ---- Round 6: the head of a PADDED stream (launch_decode: `pcm` arrives moved back by the padding and total_samples counts
@@ -203,30 +141,13 @@ __global__ __launch_bounds__(64) void adx_decode_fs18_direct_kernel(
 #pragma unroll 1
         for (int i = fp; i < head_frames; i++) {
             uint32_t w[5];
-            load_frame(i, w);
+            adx_load_frame(src, i, w);
             const int valid = min(32, sample_count - i * 32);
             decode_frame(w, std::integral_constant<int, 4>{}, i, valid, i == fp ? p.padding % 32 : 0);
         }
     }
-    // ---- warm-up of a later piece: the WARM frames before it are decoded from the guess (0, 0) and not stored, so that the
-    // piece itself starts from a history that has, as a rule, already fallen into step with the true run (the decoder
-    // forgets a wrong history within 2000 samples on audio): its seam then closes on the first frame the fix-up launch
-    // checks (15 seams per channel at configs[2]: 3.7 ms of fix-up without this, against 7.9 ms for the decode itself)
-    if (!repair && blockIdx.y > 0) {
-        const int warm = (int)(first_frame < ADX_DECODE_WARM_FRAMES ? first_frame : ADX_DECODE_WARM_FRAMES);      // even
-        const uint32_t *wsrc = src - (int64_t)warm / 2 * 9;
-#pragma unroll 1
-        for (int k = 0; k < warm / 2; k++) {
-            uint32_t c9[9];
-#pragma unroll
-            for (int q = 0; q < 9; q++) c9[q] = wsrc[(int64_t)k * 9 + q];
-            const uint32_t a[5] = {c9[0], c9[1], c9[2], c9[3], c9[4]};
-            const uint32_t b[5] = {(c9[4] >> 16) | (c9[5] << 16), (c9[5] >> 16) | (c9[6] << 16), (c9[6] >> 16) | (c9[7] << 16),
-                                   (c9[7] >> 16) | (c9[8] << 16), c9[8] >> 16};
-            decode_frame(a, std::integral_constant<int, 3>{}, 0, 32);
-            decode_frame(b, std::integral_constant<int, 3>{}, 0, 32);
-        }
-    }
+    // ---- warm-up of a later piece
+    if (!repair && blockIdx.y > 0) adx_decode_warm_up<V4>(src, first_frame, p, hist1, hist2, bad);
     // ---- whole pairs of full frames: 36 bytes from a dword boundary, the next pair's loads in flight meanwhile
     const int full_pairs = (sample_count / 32) / TURN * (TURN / 2);          // whole blocks of TURN full frames
     uint32_t cur[9], nxt[9];
@@ -246,10 +167,8 @@ __global__ __launch_bounds__(64) void adx_decode_fs18_direct_kernel(
         const uint32_t *f = src + (int64_t)min(k + 1, full_pairs - 1) * 9;
 #pragma unroll
         for (int q = 0; q < 9; q++) nxt[q] = f[q];
-        const uint32_t a[5] = {cur[0], cur[1], cur[2], cur[3], cur[4]};
-        // the second frame starts two bytes into cur[4]
-        const uint32_t b[5] = {(cur[4] >> 16) | (cur[5] << 16), (cur[5] >> 16) | (cur[6] << 16), (cur[6] >> 16) | (cur[7] << 16),
-                               (cur[7] >> 16) | (cur[8] << 16), cur[8] >> 16};
+        uint32_t a[5], b[5];
+        adx_split_pair(cur, a, b);
         decode_frame(a, std::integral_constant<int, 0>{}, 2 * k, 32);
         decode_frame(b, std::integral_constant<int, 0>{}, 2 * k + 1, 32);
 #pragma unroll
@@ -259,7 +178,7 @@ __global__ __launch_bounds__(64) void adx_decode_fs18_direct_kernel(
 #pragma unroll 1
     for (int i = max(2 * full_pairs, head_frames); i < frame_count; i++) {
         uint32_t w[5];
-        load_frame(i, w);
+        adx_load_frame(src, i, w);
         const int valid = min(32, sample_count - i * 32);
         if (valid == 32) decode_frame(w, std::integral_constant<int, 1>{}, i, 32);
         else decode_frame(w, std::integral_constant<int, 2>{}, i, valid);
@@ -338,165 +257,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     uint8_t *__restrict__ out, int64_t out_pitch, int16_t *__restrict__ history_out, int16_t *__restrict__ seg_state,
     uint2 *__restrict__ crumbs, const int *__restrict__ first_open, const int *__restrict__ open_seams, int many)
 {
-    const int ch_raw = blockIdx.x * 64 + threadIdx.x;
+    const int ch = blockIdx.x * 64 + threadIdx.x;
     int k = blockIdx.y;
     if (REPAIR) {
         if (open_seams[0] < many) return;              // few: adx_encode_fs18_tail_kernel has chained them
-        const int ko = wave_first_open(first_open, ch_raw < nch, ch_raw);
+        const int ko = wave_first_open(first_open, ch < nch, ch);
         if (!is_open(ko)) return;                      // no open seam among this wave's channels
         k = ko;
     }
-    const int ch = ch_raw;
     const int64_t f0 = (int64_t)k * seg_frames;
     if (ch >= nch || (k > 0 && f0 * 32 >= total_length)) return;
-    if (REPAIR) {
-        seg_frames = 0x7fffff00 / 32 - (int)f0;        // ... to the end of the stream
-        crumbs = nullptr;
-    }
-    const int16_t *src = pcm + (int64_t)ch * pcm_pitch;
-    uint8_t *dst = out + (int64_t)ch * out_pitch;
-    const int c0 = p.coef0, c1 = p.coef1;
-    const int filter_bits = p.type == 2 ? ((p.filter << 5) & 0xff) : 0;
+    AdxPitchedRows r{pcm, pcm_pitch, out, out_pitch, nch, total_length, p.padding, nullptr, crumbs};
+    r.open(ch);
     int a = 0, b = 0;
     if (REPAIR) {                                      // the true history at the start of piece k
-        a = seg_state[((int64_t)(k - 1) * nch + ch) * 2];
-        b = seg_state[((int64_t)(k - 1) * nch + ch) * 2 + 1];
+        const int16_t *st = seg_state + r.state(k - 1) * 2;
+        a = st[0];
+        b = st[1];
     } else if (k > 0) {                                // the guess: the input just before this piece
-        a = src[f0 * 32 - 2];
-        b = src[f0 * 32 - 1];
+        a = r.src[f0 * 32 - 2];
+        b = r.src[f0 * 32 - 1];
     } else {
         int hist = p.history;
-        if (V4 && total_length > 0 && p.padding == 0) { a = b = src[0]; hist = a; }    // :69-74
+        if (V4 && total_length > 0 && p.padding == 0) { a = b = r.src[0]; hist = a; }    // :69-74
         if (history_out) history_out[ch] = (int16_t)hist;
     }
-    const int64_t frames = ((int64_t)total_length + 31) / 32, full_frames = total_length / 32;
-    const int64_t fe = f0 + seg_frames < frames ? f0 + seg_frames : frames;
-    // Two frames (one 128-byte line of the lane's row) are loaded together, the pair after them in flight meanwhile: the
-    // halves of a line loaded a frame apart did not survive in the L1 between the two (30.5 GB fetched for 23.6).
-    auto fetch2 = [&](int64_t f, uint4 (&px)[8]) {     // unconditional, clamped to the last full frames
-        const int64_t fc = f + 1 < full_frames ? f : (full_frames >= 2 ? full_frames - 2 : 0);
-        if (full_frames >= 2) {
-#pragma unroll
-            for (int i = 0; i < 8; i++) px[i] = adx_load16(src + fc * 32 + 8 * i);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; i++) px[i] = make_uint4(0, 0, 0, 0);
-        }
-    };
-    auto encode_x = [&](int64_t f, const uint32_t (&xw)[16], uint32_t &hdr, uint32_t (&nib)[4]) {
-#if VGA_ADX_ABLATE & 4                                  // (timing-only builds: tools/build_variants.sh)
-        const int pm30 = (int)(xw[5] & 0x7FFFu);
-#else
-        const int pm30 = adx_prescan30(xw, c0, c1);
-#endif
-        adx_encode_frame_packed<V4, EXPONENTIAL>(xw, a, b, c0, c1, filter_bits, pm30, hdr, nib);
-        // the crumb of this frame, for the seam that may run over it: the history this run leaves it with and the part
-        // of the pre-scan that does not depend on any history (a wave's 64 crumbs are 512 contiguous bytes)
-#if !(VGA_ADX_ABLATE & 3)
-        if (crumbs && k > 0) crumbs[f * nch + ch] = make_uint2(((uint32_t)a & 0xFFFFu) | ((uint32_t)b << 16), (uint32_t)pm30);
-#endif
-    };
-    auto encode = [&](int64_t f, const uint4 (&px)[8], auto half_c, uint32_t &hdr, uint32_t (&nib)[4]) {   // the pair's first or second frame
-        constexpr int H = decltype(half_c)::value * 4;
-        uint32_t xw[16];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            xw[4 * i] = px[H + i].x; xw[4 * i + 1] = px[H + i].y; xw[4 * i + 2] = px[H + i].z; xw[4 * i + 3] = px[H + i].w;
-        }
-        encode_x(f, xw, hdr, nib);
-    };
-    // Eight frames at a time: their 144 bytes leave as nine 16-byte stores (whole lines for the L2 to write back, where 36
-    // bytes per pair of frames left partial ones: 17.0 GB written for 9.6)
-    const int64_t fe8 = fe < full_frames ? fe : full_frames;                           // groups of eight need full frames
-    auto encode_slow = [&](int64_t f) {                 // a frame loaded a sample at a time (zero outside the stream's samples)
-        uint32_t xw[16], hdr, nib[4];
-        adx_load_frame_slow(src, f, total_length, xw, p.padding);
-        encode_x(f, xw, hdr, nib);
-        uint16_t *d = reinterpret_cast<uint16_t *>(dst + f * 18);
-        d[0] = (uint16_t)hdr;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            d[1 + 2 * i] = (uint16_t)(nib[i] & 0xFFFFu);
-            d[2 + 2 * i] = (uint16_t)(nib[i] >> 16);
-        }
-    };
-    uint4 cur[8], nxt[8];
-    int64_t f = f0;
-    if (!REPAIR && k == 0 && p.padding > 0) {
-        // the head of a padded stream: frames up to the first even one that lies wholly behind the padding
-        int64_t fh = ((int64_t)p.padding + 31) / 32;
-        fh += fh & 1;
-        for (; f < fh && f < fe; f++) {
-            const int64_t end = (f + 1) * 32 < total_length ? (f + 1) * 32 : total_length;
-            if (end <= p.padding) {                     // wholly inside the padding: skipped, its bytes stay zero (:84-86)
-                uint16_t *d = reinterpret_cast<uint16_t *>(dst + f * 18);
-#pragma unroll
-                for (int i = 0; i < 9; i++) d[i] = 0;
-            } else
-                encode_slow(f);
-        }
-    }
-    if (f + 8 <= fe8) fetch2(f, cur);
-    for (; f + 8 <= fe8; f += 8) {
-        uint32_t w[36];
-        auto pair = [&](auto pr_c) __attribute__((always_inline)) {                    // (a lambda per pair: constant indices into w)
-            constexpr int pr = decltype(pr_c)::value;
-            uint32_t he, ho, ne[4], no[4];
-#if VGA_ADX_ABLATE & 8                                  // no loads after the first: the same frames over and over
-            if (f == f0 && pr == 0) fetch2(f + 2, nxt);
-#else
-            fetch2(f + 2 * pr + 2, nxt);
-#endif
-            encode(f + 2 * pr, cur, std::integral_constant<int, 0>{}, he, ne);
-            encode(f + 2 * pr + 1, cur, std::integral_constant<int, 1>{}, ho, no);
-            // 36 bytes: header, 16 bytes of nibbles, header, 16 bytes of nibbles
-            uint32_t *d = w + 9 * pr;
-            d[0] = he | (ne[0] << 16);
-            d[1] = (ne[0] >> 16) | (ne[1] << 16);
-            d[2] = (ne[1] >> 16) | (ne[2] << 16);
-            d[3] = (ne[2] >> 16) | (ne[3] << 16);
-            d[4] = (ne[3] >> 16) | (ho << 16);
-            d[5] = no[0]; d[6] = no[1]; d[7] = no[2]; d[8] = no[3];
-#if !(VGA_ADX_ABLATE & 8)
-#pragma unroll
-            for (int i = 0; i < 8; i++) cur[i] = nxt[i];
-#endif
-            __builtin_amdgcn_sched_barrier(0);          // (the next pair's work stays behind this one: registers)
-        };
-        pair(std::integral_constant<int, 0>{});
-        pair(std::integral_constant<int, 1>{});
-        pair(std::integral_constant<int, 2>{});
-        pair(std::integral_constant<int, 3>{});
-#if VGA_ADX_ABLATE & 2
-        if (w[0] == 0x12345678u && w[35] == 0x9abcdef0u && w[17] == 77u) dst[f * 18] = 1;
-#else
-        adx_u32x4_a4 *d = reinterpret_cast<adx_u32x4_a4 *>(dst + f * 18);              // f - f0 is a multiple of 8, f0 even
-#pragma unroll
-        for (int i = 0; i < 9; i++) {
-            adx_u32x4_a4 v;
-            v.x = w[4 * i]; v.y = w[4 * i + 1]; v.z = w[4 * i + 2]; v.w = w[4 * i + 3];
-            d[i] = v;
-        }
-#endif
-    }
-    for (; f < fe; f++) encode_slow(f);                 // what is left of the piece, the zero-padded last frame included
-    if (seg_state && !REPAIR) {
-        int16_t *st = seg_state + ((int64_t)k * nch + ch) * 2;
-        st[0] = (int16_t)a;
-        st[1] = (int16_t)b;
-    }
+    adx_encode_piece<V4, EXPONENTIAL, REPAIR>(r, k, seg_frames, p, a, b, seg_state);
 }
 
-// The fix-up launch: every seam of the batch -- (channel, piece) pairs, `items` of them -- from a queue, a LANE at a time.
-// A seam is a serial run of unknown length (at configs[2]: 200 frames on average, 2500 for the longest of 127 000; the
-// lengths are close to exponentially distributed, tests/host/analysis/adx_seam_stats.c), so a wave that kept 64 seams
-// until the last of them closed would run 1000 frames for 200 frames of work per lane.  Here a lane whose seam has closed
-// takes the next one (the wave asks the queue when ADX_FIXUP_REFILL lanes are idle), and the launch lasts about as long as
-// its longest seam run by a wave that has its SIMD to itself.
-// The guessed run's crumbs stand in for a replay of its bytes (adx_encode_seam_run, which the tail kernel keeps): per frame
-// one 8-byte load replaces nine 16-bit loads and the 32-sample decode, and the pre-scan is down to the two distances
-// that see the history -- 650 instructions per frame instead of 1100.
-// A lane's frame is loaded an iteration ahead (a lane that has just taken a seam sits its first iteration out).
+// The fix-up launch (adx_encode_fixup) over (channel, seam) pairs.  own_frames (the ragged entry points' length buckets,
+// capi_adx.hip): channel ch is a shorter stream zero-padded to total_length and only its first own_frames[ch] frames are
+// anybody's output.
 template <bool V4, bool EXPONENTIAL>
 __global__ __launch_bounds__(64) void adx_encode_fs18_fixup_kernel(
     const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_length, int seg_frames, int segments, AdxDeviceParams p,
@@ -504,111 +295,12 @@ __global__ __launch_bounds__(64) void adx_encode_fs18_fixup_kernel(
     int *__restrict__ first_open, int *__restrict__ seam_open, int *__restrict__ seam_end, int force_open, int *__restrict__ queue,
     const int *__restrict__ own_frames, int *__restrict__ open_seams)
 {
-    const int lane = threadIdx.x;
-    const int c0 = p.coef0, c1 = p.coef1;
-    const int filter_bits = p.type == 2 ? ((p.filter << 5) & 0xff) : 0;
-    const int64_t frames = ((int64_t)total_length + 31) / 32;
-    const int64_t full_frames = total_length / 32;     // frames with all 32 samples (>= 64 here: pieces are that long at least)
-    // own_frames (the ragged entry points' length buckets, capi_adx.hip): channel ch is a shorter stream zero-padded to
-    // total_length and only its first own_frames[ch] frames are anybody's output.  What a seam does past them is nobody's
-    // business -- and in digital silence the two runs need never meet (the run from the true history settles on a small
-    // non-zero fixed point of the predictor's floors, the guessed run on zero): round 5's ragged call of 10 008 files spent
-    // 100 ms per bucket chaining such seams through the padding of the bucket's shortest file.
-    // the pieces that exist: seam k (1 .. pieces - 1) starts piece k
-    const int pieces = (int)((frames + seg_frames - 1) / seg_frames) < segments ? (int)((frames + seg_frames - 1) / seg_frames) : segments;
-    const int items = nch * (pieces - 1);
-    bool active = false, have = false, drained = false;
-    int ch = 0, k = 0, ta = 0, tb = 0;
-    int64_t f = 0, fend = 0, own_end = 0;
-    const int16_t *src = pcm;
-    uint8_t *dst = out;
-    uint4 cur[4], nxt[4];
-    uint2 ccr = make_uint2(0, 0), ncr = make_uint2(0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; i++) cur[i] = nxt[i] = make_uint4(0, 0, 0, 0);
-    for (;;) {
-        const uint64_t idle = __ballot(!active);
-        const int n_idle = __popcll(idle);
-        if (!drained && (n_idle >= ADX_FIXUP_REFILL || n_idle == 64)) {
-            int base = 0;
-            if (lane == __ffsll((long long)idle) - 1) base = atomicAdd(queue, n_idle);
-            base = __shfl(base, __ffsll((long long)idle) - 1);
-            if (!active) {
-                const int idx = base + (int)__popcll(idle & ((1ull << lane) - 1ull));
-                if (idx < items) {                      // channel-fastest: neighbouring lanes start on neighbouring crumbs
-                    k = 1 + idx / nch;
-                    ch = idx - (k - 1) * nch;
-                    f = (int64_t)k * seg_frames;
-                    fend = f + seg_frames < frames ? f + seg_frames : frames;
-                    own_end = own_frames ? (int64_t)own_frames[ch] : frames;
-                    src = pcm + (int64_t)ch * pcm_pitch;
-                    dst = out + (int64_t)ch * out_pitch;
-                    ta = seg_state[((int64_t)(k - 1) * nch + ch) * 2];
-                    tb = seg_state[((int64_t)(k - 1) * nch + ch) * 2 + 1];
-                    active = f < own_end;               // a seam in the channel's padding: nothing to do
-                    have = false;
-                }
-            }
-            if (base + n_idle >= items) drained = true;
-        }
-        if (!__any(active)) {
-            if (drained) return;
-            continue;
-        }
-        if (active) {                                   // the frame after this one (a new seam: its first), clamped
-            const int64_t fl = have ? f + 1 : f;
-            const int64_t fc = fl < full_frames ? fl : full_frames - 1;
-#pragma unroll
-            for (int i = 0; i < 4; i++) nxt[i] = adx_load16(src + fc * 32 + 8 * i);
-            ncr = crumbs[fc * nch + ch];
-        }
-        if (active && have) {
-            uint32_t xw[16];
-            if (f < full_frames) {
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    xw[4 * i] = cur[i].x; xw[4 * i + 1] = cur[i].y; xw[4 * i + 2] = cur[i].z; xw[4 * i + 3] = cur[i].w;
-                }
-            } else {                                    // the zero-padded last frame: its own loads
-                adx_load_frame_slow(src, f, total_length, xw);
-                ccr = crumbs[f * nch + ch];
-            }
-            uint32_t fw[9];
-            adx_encode_frame_words<V4, EXPONENTIAL>(xw, ta, tb, c0, c1, filter_bits, (int)ccr.y, fw);
-            uint16_t *o = reinterpret_cast<uint16_t *>(dst + f * 18);
-#pragma unroll
-            for (int i = 0; i < 9; i++) o[i] = (uint16_t)fw[i];
-            const int sa = (int)(int16_t)(ccr.x & 0xFFFFu), sb = (int)ccr.x >> 16;       // the guessed run's history after this frame
-            f++;
-            if (ta == sa && tb == sb && !seam_forced_open(force_open, ch, k)) {
-                active = false;                         // closed: the rest of the piece stands
-            } else if (f >= own_end) {
-                active = false;                         // the channel's own frames are all written: the rest is padding
-            } else if (f >= fend) {
-                // still open at the end of its piece: the chain launch carries on from the history reached here
-                seam_open[(int64_t)(k - 1) * nch + ch] = 1;
-                seam_end[(int64_t)(k - 1) * nch + ch] = (int)(((unsigned)tb << 16) | ((unsigned)ta & 0xFFFFu));
-                atomicMin(&first_open[ch], k);
-                // (seams the test hook holds open count only in its REPAIR mode, 3: the chained tail has tests of its own)
-                if (!seam_forced_open(force_open, ch, k) || force_open == 3) atomicAdd(open_seams, 1);
-                active = false;
-            }
-        }
-        if (active) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) cur[i] = nxt[i];
-            ccr = ncr;
-            have = true;
-        }
-    }
+    adx_encode_fixup<V4, EXPONENTIAL>(AdxPitchedRows{pcm, pcm_pitch, out, out_pitch, nch, total_length, p.padding, own_frames,
+                                                     const_cast<uint2 *>(crumbs), pcm, out},
+                                      seg_frames, segments, p, seg_state, first_open, seam_open, seam_end, force_open, queue, open_seams);
 }
 
-// The channels with an open seam, piece after piece (one lane per channel; lanes without one leave at once) -- the
-// encoder's counterpart of the decoders' chained tail kernels and of gc_encode_chain_kernel: where the true history at
-// the start of piece k is not seg_state[k - 1], which the fix-up launch assumed, the piece holds the run from
-// seg_state[k - 1]; the same seam run from the true history finds where the two meet.  A run that does not meet by the
-// end of the piece carries on; a later open seam of the channel starts again from its recorded end.  (Round 1 encoded
-// the rest of the channel serially: 0.7 s for a 60 s channel.)
+// The chained tail (adx_encode_tail): one lane per channel
 template <bool V4, bool EXPONENTIAL>
 __global__ __launch_bounds__(64) void adx_encode_fs18_tail_kernel(
     const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_length, int seg_frames, int segments, AdxDeviceParams p,
@@ -618,34 +310,8 @@ __global__ __launch_bounds__(64) void adx_encode_fs18_tail_kernel(
 {
     const int ch = blockIdx.x * 64 + threadIdx.x;
     if (ch >= nch) return;
-    if (open_seams[0] >= many) return;                 // many seams that would not close: the REPAIR launch takes them all
-    const int k0 = first_open[ch];
-    if (k0 <= 0 || k0 >= SEAM_OPEN_LIMIT) return;      // (!is_open(k0), spelt out: the call compiles to another compare)
-    const int64_t own_end = own_frames ? (int64_t)own_frames[ch] : ((int64_t)total_length + 31) / 32;   // (see the fix-up kernel)
-    const int16_t *src = pcm + (int64_t)ch * pcm_pitch;
-    uint8_t *dst = out + (int64_t)ch * out_pitch;
-    const int c0 = p.coef0, c1 = p.coef1;
-    const int filter_bits = p.type == 2 ? ((p.filter << 5) & 0xff) : 0;
-    bool carry = false;
-    int ta = 0, tb = 0;
-    for (int k = k0; k < segments; k++) {
-        const int64_t f0 = (int64_t)k * seg_frames;
-        if (f0 * 32 >= total_length || f0 >= own_end) break;
-        const int64_t idx = (int64_t)(k - 1) * nch + ch;
-        bool apart = false;
-        if (carry)
-            apart = adx_encode_seam_run<V4, EXPONENTIAL>(src, dst, f0, seg_frames, total_length, c0, c1, filter_bits, ta, tb,
-                                                         seg_state[idx * 2], seg_state[idx * 2 + 1], ch, k, force_open);
-        if (apart) {
-            carry = true;                              // (ta, tb): the true history at the end of this piece
-        } else if (seam_open[idx] != 0) {
-            carry = true;                              // this piece's own seam ran out of frames: its recorded end is the truth
-            const int e = seam_end[idx];
-            ta = (int)(int16_t)(e & 0xFFFF);
-            tb = e >> 16;
-        } else
-            carry = false;
-    }
+    adx_encode_tail<V4, EXPONENTIAL>(AdxPitchedRows{pcm, pcm_pitch, out, out_pitch, nch, total_length, p.padding, own_frames, nullptr}, ch,
+                                     seg_frames, segments, p, seg_state, first_open, seam_open, seam_end, force_open, open_seams, many);
 }
 
 // The one-wave encoder's pieces: two waves on every SIMD, each piece at least this long (a seam takes 200 frames to close on
@@ -708,31 +374,28 @@ int launch_encode(const int16_t *d_pcm, int64_t pcm_pitch, int nch, int pcm_leng
 #endif
         fixup_waves = (int)std::min<int64_t>(fixup_waves, ((int64_t)nch * (segments - 1) + 63) / 64);
         if (fixup_waves < 1) fixup_waves = 1;
-#define VGA_ADX_ENC_T(V, E)                                                                                              \
-        {                                                                                                                \
-            hipLaunchKernelGGL((adx_encode_fs18_direct_kernel<V, E>), dim3(groups64, segments), dim3(64), 0, stream, d_pcm, \
-                               pcm_pitch, nch, pcm_length, seg_frames, p, d_out, out_pitch, d_history_out, seg_state, crumbs, \
-                               (const int *)nullptr, (const int *)nullptr, 0);                                          \
-            VGA_HIP_TRY(hipGetLastError());                                                                              \
-            if (segments > 1) {                                                                                          \
-                hipLaunchKernelGGL((adx_encode_fs18_fixup_kernel<V, E>), dim3(fixup_waves), dim3(64), 0, stream,         \
-                                   d_pcm, pcm_pitch, nch, pcm_length, seg_frames, segments, p, d_out, out_pitch, seg_state, crumbs, \
-                                   first_open, seam_open, seam_end, force_open_seams(), queue, d_own_frames, open_seams); \
-                VGA_HIP_TRY(hipGetLastError());                                                                          \
-                hipLaunchKernelGGL((adx_encode_fs18_tail_kernel<V, E>), dim3(groups64), dim3(64), 0, stream, d_pcm,     \
-                                   pcm_pitch, nch, pcm_length, seg_frames, segments, p, d_out, out_pitch, seg_state,    \
-                                   first_open, seam_open, seam_end, force_open_seams(), d_own_frames, open_seams, many); \
-                VGA_HIP_TRY(hipGetLastError());                                                                          \
-                hipLaunchKernelGGL((adx_encode_fs18_direct_kernel<V, E, true>), dim3(groups64, 1), dim3(64), 0, stream, d_pcm, \
-                                   pcm_pitch, nch, pcm_length, seg_frames, p, d_out, out_pitch, (int16_t *)nullptr, seg_state, \
-                                   (uint2 *)nullptr, (const int *)first_open, (const int *)open_seams, many);           \
-            }                                                                                                            \
-        }
-        if (v4 && ex) VGA_ADX_ENC_T(true, true)
-        else if (v4) VGA_ADX_ENC_T(true, false)
-        else if (ex) VGA_ADX_ENC_T(false, true)
-        else VGA_ADX_ENC_T(false, false)
-#undef VGA_ADX_ENC_T
+        const int rc = adx_with_version_and_type(v4, ex, [&](auto v, auto e) -> int {
+            constexpr bool V = decltype(v)::value, E = decltype(e)::value;
+            hipLaunchKernelGGL((adx_encode_fs18_direct_kernel<V, E>), dim3(groups64, segments), dim3(64), 0, stream, d_pcm, pcm_pitch, nch,
+                               pcm_length, seg_frames, p, d_out, out_pitch, d_history_out, seg_state, crumbs, (const int *)nullptr,
+                               (const int *)nullptr, 0);
+            VGA_HIP_TRY(hipGetLastError());
+            if (segments > 1) {
+                hipLaunchKernelGGL((adx_encode_fs18_fixup_kernel<V, E>), dim3(fixup_waves), dim3(64), 0, stream, d_pcm, pcm_pitch, nch,
+                                   pcm_length, seg_frames, segments, p, d_out, out_pitch, seg_state, crumbs, first_open, seam_open,
+                                   seam_end, force_open_seams(), queue, d_own_frames, open_seams);
+                VGA_HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL((adx_encode_fs18_tail_kernel<V, E>), dim3(groups64), dim3(64), 0, stream, d_pcm, pcm_pitch, nch,
+                                   pcm_length, seg_frames, segments, p, d_out, out_pitch, seg_state, first_open, seam_open, seam_end,
+                                   force_open_seams(), d_own_frames, open_seams, many);
+                VGA_HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL((adx_encode_fs18_direct_kernel<V, E, true>), dim3(groups64, 1), dim3(64), 0, stream, d_pcm, pcm_pitch,
+                                   nch, pcm_length, seg_frames, p, d_out, out_pitch, (int16_t *)nullptr, seg_state, (uint2 *)nullptr,
+                                   (const int *)first_open, (const int *)open_seams, many);
+            }
+            return VGA_OK;
+        });
+        if (rc) return rc;
     } else {                                           // other frame sizes, padded (looping) streams, odd alignments
         hipLaunchKernelGGL(adx_encode_kernel, grid, block, 0, stream, d_pcm, pcm_pitch, nch, pcm_length, p, d_out, out_pitch,
                            d_history_out);
@@ -773,29 +436,27 @@ int launch_decode(const uint8_t *d_adpcm, int64_t in_pitch, int nch, int sample_
         DecodeSeams ds;
         if (segments > 1)
             if (const int rc = ds.init(nch, segments, stream)) return rc;
-#define VGA_ADX_DEC_T(V)                                                                                                 \
-        {                                                                                                                \
-            hipLaunchKernelGGL((adx_decode_fs18_direct_kernel<V, false>), dim3(groups, segments), dim3(64), 0, stream,   \
-                               d_adpcm, in_pitch, nch, sample_count, seg_frames, p, d_pcm, pcm_pitch, d_status,          \
-                               (const int *)nullptr, (const int *)nullptr);                                              \
-            VGA_HIP_TRY(hipGetLastError());                                                                              \
-            if (segments > 1) {                                                                                          \
-                hipLaunchKernelGGL(adx_decode_fs18_fixup_kernel<V>, dim3(groups, segments - 1), dim3(64), 0, stream,    \
-                                   d_adpcm, in_pitch, nch, sample_count, seg_frames, p, d_pcm, pcm_pitch, ds.first_open, \
-                                   ds.seam_open, force_open_seams(), ds.slow_seams, d_own_samples);                     \
-                VGA_HIP_TRY(hipGetLastError());                                                                          \
-                hipLaunchKernelGGL(adx_decode_fs18_tail_kernel<V>, dim3(groups), dim3(64), 0, stream, d_adpcm, in_pitch, \
-                                   nch, sample_count, seg_frames, segments, p, d_pcm, pcm_pitch, ds.first_open,          \
-                                   ds.seam_open, force_open_seams(), ds.slow_seams, d_own_samples);                     \
-                VGA_HIP_TRY(hipGetLastError());                                                                          \
-                hipLaunchKernelGGL((adx_decode_fs18_direct_kernel<V, true>), dim3(groups, 1), dim3(64), 0, stream,       \
-                                   d_adpcm, in_pitch, nch, sample_count, seg_frames, p, d_pcm, pcm_pitch, d_status,      \
-                                   (const int *)ds.first_open, (const int *)ds.slow_seams);                             \
-            }                                                                                                            \
-        }
-        if (p.version == 4) VGA_ADX_DEC_T(true)
-        else VGA_ADX_DEC_T(false)
-#undef VGA_ADX_DEC_T
+        const int rc = adx_with_version(p.version == 4, [&](auto v) -> int {
+            constexpr bool V = decltype(v)::value;
+            hipLaunchKernelGGL((adx_decode_fs18_direct_kernel<V, false>), dim3(groups, segments), dim3(64), 0, stream, d_adpcm, in_pitch,
+                               nch, sample_count, seg_frames, p, d_pcm, pcm_pitch, d_status, (const int *)nullptr, (const int *)nullptr);
+            VGA_HIP_TRY(hipGetLastError());
+            if (segments > 1) {
+                hipLaunchKernelGGL(adx_decode_fs18_fixup_kernel<V>, dim3(groups, segments - 1), dim3(64), 0, stream, d_adpcm, in_pitch,
+                                   nch, sample_count, seg_frames, p, d_pcm, pcm_pitch, ds.first_open, ds.seam_open, force_open_seams(),
+                                   ds.slow_seams, d_own_samples);
+                VGA_HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL(adx_decode_fs18_tail_kernel<V>, dim3(groups), dim3(64), 0, stream, d_adpcm, in_pitch, nch,
+                                   sample_count, seg_frames, segments, p, d_pcm, pcm_pitch, ds.first_open, ds.seam_open,
+                                   force_open_seams(), ds.slow_seams, d_own_samples);
+                VGA_HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL((adx_decode_fs18_direct_kernel<V, true>), dim3(groups, 1), dim3(64), 0, stream, d_adpcm, in_pitch, nch,
+                                   sample_count, seg_frames, p, d_pcm, pcm_pitch, d_status, (const int *)ds.first_open,
+                                   (const int *)ds.slow_seams);
+            }
+            return VGA_OK;
+        });
+        if (rc) return rc;
     } else {
         hipLaunchKernelGGL(adx_decode_kernel, dim3((nch + 63) / 64), dim3(64), 0, stream, d_adpcm, in_pitch, nch, sample_count, p,
                            d_pcm, pcm_pitch, d_status);
