@@ -72,14 +72,24 @@ def count(block):
 def main():
     L = kernel(listing(), "gc_encode_persistent_kernelILi8ELb0E")
     sq = [i for i, l in enumerate(L) if re.search(r"v_dot2_i32_i16 v\d+, (v\d+), \1, (?:v\d+|0) clamp", l)]
-    assert len(sq) >= 28, "the listing does not look like the encoder's"
-    # first frame of the loop body (row set A): squares 0..27 = short pair (2 x 7) + normal pair (2 x 7)
-    # (hipcc sinks the short pair's squares behind the passes, into a block of their own: the passes' extent is taken from
-    # the fourteen v_cvt_pk_i16_i32 of each -- clamp and history shift, on the chain -- and stretched over the squares)
-    cv = [i for i, l in enumerate(L) if l.startswith("v_cvt_pk_i16_i32") and i > sq[0] - 700]
-    assert len(cv) >= 56, "the listing does not look like the encoder's"
-    short_a, short_b = min(cv[0], sq[0]), max(cv[27], sq[13])
-    normal_a, normal_b = min(cv[28], sq[14]), max(cv[55], sq[27])
+    # first frame of the loop body (row set A): short pair of passes (2 x 14 sample steps), then the normal pair.  The passes'
+    # extent is taken from the fourteen v_cvt_pk_i16_i32 of each -- clamp and history shift, on the chain.
+    if any(l.startswith("v_addc_co_u32") for l in L):
+        # round 10: the frame's passes are the first code with an add with carry (the seam code inside the kernel keeps the
+        # old pass); the hot passes form no squares any more -- one error block of seven stands in the frame's tail
+        first = next(i for i, l in enumerate(L) if l.startswith("v_addc_co_u32"))
+        cv = [i for i, l in enumerate(L) if l.startswith("v_cvt_pk_i16_i32") and i > first - 40]
+        assert len(cv) >= 56, "the listing does not look like the encoder's"
+        inside = lambda a, b: [i for i in sq if a <= i <= b + 60]
+        short_a, short_b = cv[0], max([cv[27]] + (inside(cv[0], cv[27]) if len(inside(cv[0], cv[55])) >= 28 else []))
+        normal_a, normal_b = cv[28], max([cv[55]] + (inside(cv[28], cv[55]) if len(inside(cv[0], cv[55])) >= 28 else []))
+    else:
+        assert len(sq) >= 28, "the listing does not look like the encoder's"
+        # (hipcc sinks the short pair's squares behind the passes, into a block of their own: stretched over the squares)
+        cv = [i for i, l in enumerate(L) if l.startswith("v_cvt_pk_i16_i32") and i > sq[0] - 700]
+        assert len(cv) >= 56, "the listing does not look like the encoder's"
+        short_a, short_b = min(cv[0], sq[0]), max(cv[27], sq[13])
+        normal_a, normal_b = min(cv[28], sq[14]), max(cv[55], sq[27])
     labels = [i for i, l in enumerate(L) if l.endswith(":")]
     prev_label = lambda i: max(j for j in labels if j <= i)
     next_label = lambda i: min(j for j in labels if j > i)
@@ -106,7 +116,7 @@ def main():
             ("passes B (s1 + 1) and A (s1) without the f32 detour, 28 sample steps", count(L[short_blk[0]:short_blk[1]])),
             ("the same with the conversions (30 % of the wave-frames take these instead)", count(L[normal_blk[0]:normal_blk[1]])),
             ("select the pass the reference ends on, 8-predictor argmin (DPP), winner's history, 4 x ds_write_b128", count(L[normal_blk[1]:tail_end + 1]))]
-    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 9)\n")
+    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 10)\n")
     print("`gc_encode_persistent_kernel<8, false>`, static counts from hipcc's gfx950 listing of `vgaudio_amd/csrc/gc_encode_kernel.hip`")
     print("(`tools/isa_budget_gc.py`).  One wave-frame = 64 lanes = 8 channels x 8 predictors = 112 input samples.\n")
     print("| block of the hot frame | total | VALU | SALU | LDS | wait / nop |")
@@ -135,20 +145,23 @@ def main():
 
 
 TEXT = """
-## What the budget says (round 9)
+## What the budget says (round 10)
 
-* Round 8's table is `profiles/r08_gc_encode_isa_budget.md`.  Its first row (87 VALU) took the frame to begin at the TILE's
-  first label: the tool walked back a fixed number of lines and so counted the tile head (lane addresses, the first row's
-  reads), which runs once per four frames.  The tool now takes the frame to begin at the label whose block opens with the next
-  frame's six row reads; with that rule the parent of this round has 53 VALU in the row block and 519 per wave-frame.
-* Row block 53 -> 41: the two history-dependent distances in the numerator domain (gc_encode_core.hpp N1: `v_sub` for the
-  sign of D, `v_lshrrev`, `v_mad_i32_i24`, `v_ashrrev` on `in * 2048 + 1024 - P`, no unpacking of `in`, no quotient), both dot
-  products in the clamped three-operand form (no `v_mov` of the zero), and the first scale from ONE bit length (F1-F4: two
-  `v_med3`, `v_add`, `v_mul_i32_i24`, compare, `v_cndmask` with the shift folded in as SDWA, `v_or`, `v_ffbh`, `v_sub`; the
-  +M / -M tie is one compare and a scalar branch).
-* Passes 332 -> 328 / 365 -> 361: step 0 of both passes takes P0 and `in * 2048 + 1024 - P0` from the head.
-* The helper wave's pre-scan is as it was (the numerator-domain form was measured and taken out: LABNOTES 14).
+* Round 9's table is `profiles/r09_gc_encode_isa_budget.md` (same tool, parent of this round): row block 41, passes 328 / 361,
+  tail 43, cold block 81, encoder wave 503 VALU per wave-frame.
+* Passes 328 -> 277 / 361 -> 307.  Step 1 (gc_encode_core.hpp B1-B5): the sample step is `v_dot2`, `v_sub_co`, `v_addc_co`,
+  shift, `v_med3`, `P >> 11`, `v_lshl_add`, `v_cvt_pk` -- 8 where it was 9 (`v_sub`, `v_lshrrev`, `v_add3`), -23 / -26 per pair
+  of passes (step 0 keeps a `v_cndmask` of the borrow the two passes share).  hipcc puts `s_nop 1` between the carry pair
+  (a VALU write of an SGPR read by the next VALU): 66 / 51 wait / nop lines against 27 / 28.  Step 2: the passes form no
+  squares (-28: 2 x 7 `v_pk_sub_i16` + `v_dot2`).
+* Tail 43 -> 62: seven selects of the history pairs (the seventh is the winner's history: one select it had already) and one
+  error block of 7 + 7.  Steps 1 + 2 together: -51 in the passes, +19 in the tail.
+* Row block 41 -> 50: per pass one shift for -Z and two adds for the clamp bounds (6), the borrow of the shared step 0.  The
+  tool counts the block in front of the conversions pair (10 VALU: its copy of the pass constants) into this row although
+  the short path jumps over it, so a frame of the short kind executes about 5 fewer than the table says.
+* Cold block 81 -> 77: the third pass 190 -> 178.
 """
+
 
 
 def cluster(idx):

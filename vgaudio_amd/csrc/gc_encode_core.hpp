@@ -520,6 +520,182 @@ VGA_HD PassOut pass_fast_core_wide(const uint32_t (&xw)[7], uint32_t hist, const
 {
     return pass_fast_core_t<true>(xw, hist, in2048p, c0, c1, scale_power);
 }
+// ---- the rounding sign from the subtract's borrow (round 10) --------------------------------
+// pass_fast_core_t spends three instructions of the sample step's dependent chain on d = in2048p - P, sign = d >>> 31 and
+// t = rd + bias + sign.  pass_fast_core_b runs the same step on numbers moved up by OFF = 2^30: both operands of the subtract are
+// then non-negative, its unsigned borrow IS the sign, and an add with carry consumes it (v_sub_co_u32 + v_addc_co_u32: one
+// instruction and one link of the chain less per sample step).  With Z = 2^(19 - scale_power) = OFF / 2^k:
+//   P'     = dot2(H, C, 1024 + OFF)                          P + OFF; the accumulator constant in a scalar register as before
+//   d, b   = usub_overflow(in', P')                          in' = in*2048 + 1024 + OFF (the caller's row); b = borrow
+//   t      = rd + (bias - OFF) + b                           rd = d or (int)(float)d as in pass_fast_core_t; one add with carry
+//   u2     = t >> k                                          = u - Z
+//   q2     = med3(u2, -8 - Z, 7 - Z)                         = q - Z
+//   w      = (P' >> 11) + (q2 << scale_power)                the true w
+//   H', E, total                                             as in pass_fast_core_t
+// The overflow comes from the running max / min of u2 against the shifted bounds; they start at -Z, the old 0.
+//  (B1) |c0| + |c1| <= 30720: |predicted| <= 32768 * 30720 = 2^30 - 2^26, so P' = predicted + 1024 + 2^30 lies in
+//       [2^26 + 1024, 2^31 - 2^26 + 1024], inside [0, 2^31): the dot product's clamp cannot fire (P1 carries over) and P' is
+//       non-negative as an unsigned AND as a signed number.  in' = in * 2048 + 1024 + 2^30 lies in
+//       [2^30 - 2^26 + 1024, 2^30 + 2^26 - 1024], inside [0, 2^31) as well.
+//  (B2) both operands of in' - P' are non-negative and below 2^31: the difference is the true d = in * 2048 - predicted (the
+//       1024 + OFF cancels, P2) without wrapping, and the unsigned subtract borrows exactly when in' < P', i.e. when d < 0.
+//  (B3) t does not leave int32.  d >= -2^26 - (2^30 - 2^26) = -2^30, which f32 represents, so rd >= -2^30 (rounding is monotone)
+//       and t >= -2^30 + bias - 2^30 >= -2^31 + 1023; upwards t < 2^30 + 2^26 + 2^22 - 2^30.  THIS is what sets the bound at 30720
+//       = 32768 - 2048 and not at 32767: there d could reach -2^30 - 2^26 + 32768 and t would wrap below -2^31 at small scales.
+//  (B4) OFF = Z * 2^k exactly (k <= 23 < 30), and an arithmetic shift commutes with subtracting a multiple of 2^k:
+//       u2 = (rd + bias + b - Z * 2^k) >> k = u - Z.  Clamping u - Z to [-8 - Z, 7 - Z] gives q - Z; max / min likewise, so
+//       max(umax2 - (7 - Z), (-8 - Z) - umin2, 0) is the old overflow.  Z is a multiple of 128 (scale_power <= 12): q2 & 15 == q & 15.
+//  (B5) w: P' >> 11 = (P >> 11) + 2^19 (OFF is a multiple of 2^11) and q2 << scale_power = (q << scale_power) - 2^19: the two
+//       cancel, w is pass_fast_core_t's w bit for bit.  Hence H, the errors and everything S2 / S3 / E1-E5 / NO_ROUND say speak
+//       about the same numbers.
+// The nibbles leave the pass as q2 (PassOutB::q2); whoever packs them takes them & 15 (pack_frame_mod16) or adds Z.
+// Coefficients with |c0| + |c1| > 30720 get exact == false: the callers send them the way coefficients that can wrap go (the
+// reference's loop as written, exact for any coefficients).  Real coefficient sets have |c0| + |c1| of a few thousand.
+// pass_fast_core_t stays for the seam, tail and chain code and for the WIDE pass (bound 32767).
+constexpr int PASS_B_OFF = 1 << 30;
+constexpr int PASS_B_COEF_SUM_MAX = 30720;                             // B3
+struct PassOutB {
+    int q2[14];          // q - Z, Z = pass_b_z(scale_power); congruent to the nibble mod 16
+    uint64_t total;
+    int max_overflow;
+    unsigned hist_pair;
+    bool exact;          // as PassOut::exact, with the bound of B3 on the coefficients
+    uint32_t pairs[7];   // WITH_SUM == false only: the seven history pairs (o[2i], o[2i + 1]) the error sum is formed from (E1)
+};
+VGA_HD bool pass_b_coef_ok(int c0, int c1)
+{
+    return (c0 < 0 ? -c0 : c0) + (c1 < 0 ? -c1 : c1) <= PASS_B_COEF_SUM_MAX;
+}
+VGA_HD int pass_b_z(int scale_power) { return 1 << (19 - scale_power); }
+VGA_HD int pass_b_row(int in) { return in * 2048 + 1024 + PASS_B_OFF; }      // in' (the kernel's helper wave writes it per tile)
+// P' of a history pair: the dot product as the pass writes it
+VGA_HD int predicted_b(uint32_t h, uint32_t cpair)
+{
+    int kacc = 1024 + PASS_B_OFF;
+    VGA_OPAQUE_S(kacc);
+    return dot2_i16(h, cpair, kacc);
+}
+// head_distance_numer on the moved numbers: N = in' - P' is the same N, and 1024 + OFF - P' = 1024 - P without wrapping (B1)
+VGA_HD int head_distance_numer_b(int in_b, int P_b)
+{
+    const int N = (int)((uint32_t)in_b - (uint32_t)P_b);
+    return numer_adjust(N, (int)((uint32_t)(1024 + PASS_B_OFF - P_b) >> 31)) >> 11;
+}
+// median of three signed values (v_med3_i32): with lo <= hi, clamp(v, lo, hi).  hipcc makes v_max + v_min of a clamp whose
+// bounds are registers; the asm statement's operands here come from a shift and registers that are set once per pass, never
+// straight from a dot product, so no wait states are missing behind it (see dot2_i16_wrap).
+VGA_HD int med3_i32(int v, int lo, int hi)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    int r;
+    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(v), "v"(lo), "v"(hi));
+    return r;
+#else
+    return imin(imax(v, lo), hi);
+#endif
+}
+// d = a - b (mod 2^32) and the unsigned borrow; t = x + y + carry (mod 2^32).  The device build leaves both to hipcc
+// (v_sub_co_u32 / v_addc_co_u32 from these very expressions); the host build computes the same.
+VGA_HD uint32_t sub_borrow_u32(uint32_t a, uint32_t b, uint32_t &borrow)
+{
+    uint32_t d;
+    borrow = __builtin_usub_overflow(a, b, &d) ? 1u : 0u;
+    return d;
+}
+// WITH_SUM == false (round 10, step 2): the pass returns its seven history pairs and total = 0; a caller that runs two passes
+// in one lane picks the pairs of the pass the reference ends on and forms ONE sum from them (error_sum_pairs) -- E1-E5 are
+// statements about the pairs and hold for the sum formed there.
+VGA_HD uint32_t error_sum_pairs(const uint32_t (&xw)[7], const uint32_t (&pairs)[7])
+{
+    int total = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 7; i++) {
+        const uint32_t epk = pk_sub_sat_i16(xw[i], pairs[i]);       // (E1, E2)
+        total = dot2_i16(epk, epk, total);                          // (E3)
+    }
+    return (uint32_t)total;
+}
+template <bool NO_ROUND, bool HAVE_P0 = false, bool WITH_SUM = true>
+VGA_HD PassOutB pass_fast_core_b(const uint32_t (&xw)[7], uint32_t hist, const int (&in_b)[14], int c0, int c1, int scale_power,
+                                 int P0_b = 0)
+{
+    PassOutB r;
+    const int k = scale_power + 11;
+    const int km11 = scale_power;
+    int bias2 = (1 << (k - 1)) - 1 - PASS_B_OFF;
+    VGA_OPAQUE(bias2);
+    const int nz = -(1 << 19) >> scale_power;                       // -Z in one shift
+    const int q_lo = nz - 8, q_hi = nz + 7;
+    const uint32_t cpair = pack16(c1, c0);
+    int kacc = 1024 + PASS_B_OFF;
+    VGA_OPAQUE_S(kacc);
+    int total = 0;
+    int umax = nz, umin = nz;
+    int u_prev = nz;
+    uint32_t h = hist;                                              // (o0, o1)
+    int w_prev = pair_hi(hist);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int s = 0; s < 14; s++) {
+        const int P = (HAVE_P0 && s == 0) ? P0_b : dot2_i16(h, cpair, kacc);  // predicted + 1024 + OFF
+        uint32_t b;
+        const int d = (int)sub_borrow_u32((uint32_t)in_b[s], (uint32_t)P, b);  // the true distance; b = (d < 0)  (B2)
+        const int rd = NO_ROUND ? d : round_through_f32(d);
+        const int u2 = (int)((uint32_t)rd + (uint32_t)bias2 + b) >> k;       // u - Z  (B3, B4)
+        const int q2 = med3_i32(u2, q_lo, q_hi);
+        if (s & 1) {
+            umax = imax(imax(umax, u_prev), u2);
+            umin = imin(imin(umin, u_prev), u2);
+        }
+        u_prev = u2;
+        r.q2[s] = q2;
+        const int w = (P >> 11) + (int)((uint32_t)q2 << km11);      // (B5)
+        h = sat_pack16(w_prev, w);
+        w_prev = w;
+        if (s & 1) {
+            if (WITH_SUM) {
+                const uint32_t epk = pk_sub_sat_i16(xw[s >> 1], h);
+                total = dot2_i16(epk, epk, total);
+            } else
+                r.pairs[s >> 1] = h;
+        }
+    }
+    r.hist_pair = h;
+    const int ov = imax(imax(umax - q_hi, q_lo - umin), 0);
+    r.exact = pass_b_coef_ok(c0, c1) && ov <= 12383 && (((2 * ov + 1) << (k - 11)) <= 24766);
+    r.total = (uint64_t)(uint32_t)total;
+    r.max_overflow = ov;
+    return r;
+}
+// The 8 frame bytes (pack_frame) from nibbles known mod 16 only: q, q2 = q - Z, or the biased nibble all pack alike.
+VGA_HD void pack_frame_mod16(const int (&q)[14], int predictor, int scale_power, uint32_t &d0, uint32_t &d1)
+{
+    uint32_t wa = 0, wb = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int s = 0; s < 14; s++) {
+        if (s < 6) wa = (wa << 4) | ((uint32_t)q[s] & 15u);
+        else       wb = (wb << 4) | ((uint32_t)q[s] & 15u);
+    }
+    const uint32_t header = (uint32_t)((predictor << 4) | (scale_power & 0xF));
+    d0 = bswap32((header << 24) | wa);
+    d1 = bswap32(wb);
+}
+// a PassOut (nibbles as they are) in the form the kernel's frame tail takes
+VGA_HD PassOutB as_pass_b(const PassOut &r)
+{
+    PassOutB o;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int s = 0; s < 14; s++) o.q2[s] = r.q[s];
+    o.total = r.total; o.max_overflow = r.max_overflow; o.hist_pair = r.hist_pair; o.exact = r.exact;
+    return o;
+}
 // The exact-sum rule (E4) for one lane: a sum at or above 2^28 that is not known to be exact (r.exact) is taken again from
 // the pass with the 64-bit sum, at the scale the pass ran at.  The kernel's cold block applies it when a channel's best key
 // saturated; for coefficients that can wrap the wide pass is no authority and the caller has the literal pass's sum.

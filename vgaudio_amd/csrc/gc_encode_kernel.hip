@@ -16,7 +16,9 @@
 //    overflow values decide which one the reference ends on.  Third trips, overflow bumps
 //    and everything else that is rare sit behind ONE wave-uniform branch per frame.
 //  * The quantise pass is integer-only on a packed pair of 16-bit history values (12 VALU ops per sample
-//    instead of the float/double detour); exactness conditions in gc_encode_core.hpp S2/S3, P1-P6.
+//    instead of the float/double detour); exactness conditions in gc_encode_core.hpp S2/S3, P1-P6.  Since round 10 the
+//    piece kernels run it on numbers moved up by 2^30 (pass_fast_core_b, B1-B5): the rounding sign is the subtract's
+//    borrow, one op a sample less; the seam, tail and chain code keeps pass_fast_core_t.
 //  * 8-predictor argmin + winner-history broadcast: v_min_u32 / v_or_b32 with DPP operands
 //    (quad_perm, row_half_mirror, row_mirror) -- 8 VALU ops, no LDS.
 #include "common.hpp"
@@ -60,7 +62,7 @@ __device__ __forceinline__ unsigned row16_reduce(unsigned v, Op op)
 // Everything that does not depend on the reconstructed history is taken off the serial wave:
 //   helper wave (wave 1), one 16-frame tile AHEAD of the encoder:
 //     * coalesced global loads of the tile (lane = frame j of channel g: 28 contiguous bytes),
-//     * unpack to int32, x*2048 + 1024, and for each of the 8 predictors the max/min pre-scan distance over the
+//     * unpack to int32, x*2048 + 1024 + 2^30 (pass_b_row), and for each of the 8 predictors the max/min pre-scan distance over the
 //       twelve samples s = 2..13 that involve input samples only (GcAdpcmEncoder.cs:107-115),
 //     * all of it into LDS (double-buffered), plus the coalesced flush of the previous tile's frames
 //       (the zero-padded partial last frame travels through the same path);
@@ -129,7 +131,7 @@ struct Lay {
 template <int CS, int TF>
 struct GcTileT {
     uint32_t xw[CS][TF][8];    // [channel slot][frame]: the frame as packed pairs (in[2i], in[2i + 1]), 7 used (round 8)
-    int in2048p[CS][TF][16];   // x * 2048 + 1024  (the pass needs no x * 2048 beside it since round 7: gc_encode_core.hpp P2)
+    int in2048p[CS][TF][16];   // x * 2048 + 1024 + 2^30: the row of pass_fast_core_b (round 10, gc_encode_core.hpp B1)
     uint32_t pre[CS][TF][8];   // per predictor: clamp16(max d) & 0xFFFF | clamp16(min d) << 16, over s = 2..13
 };
 typedef short short2v __attribute__((ext_vector_type(2)));
@@ -156,7 +158,7 @@ VGA_COLD int prescan_sequential_cold(XW7 xs, uint32_t hist, int c0, int c1)
 // frame's tail is instantiated once per branch below instead of merging the two branches' results.
 struct ColdState {
     uint32_t xw[7];            // the frame as packed pairs; the paths that want ints unpack it where they run
-    int mp[14];
+    int mp[14];                // the row moved up by 2^30 (pass_b_row)
     uint32_t hist;             // (x[0], x[1]) packed
     int c0, c1, s1;
     // what this lane needs (any of them in any lane sends the wave here):
@@ -174,10 +176,10 @@ struct ColdState {
 };
 // sum_exact: r.total came from the reference's loop as written (exact whatever its size); 0: from a fast pass at final_sp,
 // exact below 2^28 and "at least 2^28" otherwise (gc_encode_core.hpp E3)
-struct ColdOut { PassOut r; int final_sp; int fin; int sum_exact; };
+struct ColdOut { PassOutB r; int final_sp; int fin; int sum_exact; };
 // inline: 370 ms out of line (the by-value state goes through scratch) vs 209 inline (round 1)
 __device__ __forceinline__
-ColdOut encode_frame_cold(ColdState st, PassOut r, int final_sp, int fin)
+ColdOut encode_frame_cold(ColdState st, PassOutB r, int final_sp, int fin)
 {
     uint32_t xw[7];
     int mp[14];
@@ -197,7 +199,7 @@ ColdOut encode_frame_cold(ColdState st, PassOut r, int final_sp, int fin)
             for (int i = 0; i < 16; i++) VGA_COLD_OPAQUE(xg[i]);
             const int start = st.start != -100 ? st.start
                                                : (st.bump_a ? apply_bumps(st.s1, st.ov_a) : apply_bumps(st.s1 + 1, st.ov_b));
-            r = resume_passes(xg, st.c0, st.c1, start, final_sp);
+            r = as_pass_b(resume_passes(xg, st.c0, st.c1, start, final_sp));
             fin = 1;
             sum_exact = 1;
         }
@@ -220,17 +222,17 @@ ColdOut encode_frame_cold(ColdState st, PassOut r, int final_sp, int fin)
                 bool short_pass = !__any(sp > 9);  // (over the lanes still in this loop) without the f32 detour, as the first two passes
 #endif
                 if (short_pass) {
-                    r = pass_fast_core_no_round(xw, st.hist, mp, st.c0, st.c1, sp);
+                    r = pass_fast_core_b<true>(xw, st.hist, mp, st.c0, st.c1, sp);
                     short_pass = !__any(!pass_no_round_is_exact(sp, r.max_overflow));
                 }
-                if (!short_pass) r = pass_fast_core(xw, st.hist, mp, st.c0, st.c1, sp);
+                if (!short_pass) r = pass_fast_core_b<false>(xw, st.hist, mp, st.c0, st.c1, sp);
                 const bool cap = sp >= 12;
                 if ((unsigned)r.max_overflow > (cap ? 3u : 248u)) {      // bump loop / inexact sum: generic
                     int xg[16];                                          // (opaque: see above)
                     unpack_row(xw, st.hist, xg);
 #pragma unroll
                     for (int i = 0; i < 16; i++) VGA_COLD_OPAQUE(xg[i]);
-                    r = resume_passes(xg, st.c0, st.c1, sp - 1, final_sp);
+                    r = as_pass_b(resume_passes(xg, st.c0, st.c1, sp - 1, final_sp));
                     sum_exact = 1;
                     break;
                 }
@@ -358,10 +360,10 @@ __device__ __forceinline__ void gc_encode_piece(
             xr[0] = make_uint4(w[0], w[1], w[2], w[3]);
             xr[1] = make_uint4(w[4], w[5], w[6], 0u);
             int4 *qr = reinterpret_cast<int4 *>(&T.in2048p[grp][hfr][0]);
-            qr[0] = make_int4(in[0] * 2048 + 1024, in[1] * 2048 + 1024, in[2] * 2048 + 1024, in[3] * 2048 + 1024);
-            qr[1] = make_int4(in[4] * 2048 + 1024, in[5] * 2048 + 1024, in[6] * 2048 + 1024, in[7] * 2048 + 1024);
-            qr[2] = make_int4(in[8] * 2048 + 1024, in[9] * 2048 + 1024, in[10] * 2048 + 1024, in[11] * 2048 + 1024);
-            qr[3] = make_int4(in[12] * 2048 + 1024, in[13] * 2048 + 1024, 0, 0);
+            qr[0] = make_int4(pass_b_row(in[0]), pass_b_row(in[1]), pass_b_row(in[2]), pass_b_row(in[3]));
+            qr[1] = make_int4(pass_b_row(in[4]), pass_b_row(in[5]), pass_b_row(in[6]), pass_b_row(in[7]));
+            qr[2] = make_int4(pass_b_row(in[8]), pass_b_row(in[9]), pass_b_row(in[10]), pass_b_row(in[11]));
+            qr[3] = make_int4(pass_b_row(in[12]), pass_b_row(in[13]), 0, 0);
             // pre-scan distances of samples 2..13 (:107-115): predicted = (in[k]*c1 + in[k+1]*c0) / 2048 for the
             // pair starting at k = s - 2.  One v_dot2c_i32_i16 per (predictor, sample): the pairs at even k are
             // the loaded dwords, the pairs at odd k one v_alignbit each (shared by the 8 predictors); the
@@ -400,7 +402,7 @@ __device__ __forceinline__ void gc_encode_piece(
             const int4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
             const int q[14] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, r3.x, r3.y};
             uint2 v;
-            pack_frame(q, r3.z, r3.w, v.x, v.y);
+            pack_frame_mod16(q, r3.z, r3.w, v.x, v.y);   // the record holds q - Z from the hot pass, q from the reference's loop: alike mod 16
             if (fr < full_frames) {
                 *reinterpret_cast<uint2 *>(dst + (int64_t)fr * 8) = v;
             } else {
@@ -427,7 +429,9 @@ __device__ __forceinline__ void gc_encode_piece(
     const bool cand_b = CPW == 4 && (l16 & 1) != 0;
     const int c0 = coefs[ch * 16 + 2 * p];
     const int c1 = coefs[ch * 16 + 2 * p + 1];
-    const bool coef_ok = (c0 < 0 ? -c0 : c0) + (c1 < 0 ? -c1 : c1) <= 32767;   // predictor cannot wrap int32
+    // the bound of pass_fast_core_b (gc_encode_core.hpp B3: 30720, below the 32767 at which the predictor can wrap int32); a lane
+    // above it takes the reference's loop as written
+    const bool coef_ok = pass_b_coef_ok(c0, c1);
     int h0 = hist2 ? hist2[ch] : 0;   // pcmBuffer[0] = History2 (GcAdpcmEncoder.cs:24)
     int h1 = hist1 ? hist1[ch] : 0;   // pcmBuffer[1] = History1 (:25)
     if (repair) {
@@ -466,17 +470,24 @@ __device__ __forceinline__ void gc_encode_piece(
     // the history pair (h0, h1) with (c1, c0), predicted(s = 1) that of (h1, x[2]) -- one v_alignbit across the history and the
     // row's first dword.  Unclamped dot product: int32 wraps where the reference's unchecked sum does.
     // Round 9, when no lane of the wave has coefficients that can wrap (wave-uniform, decided once per piece): both distances in
-    // the numerator domain (gc_encode_core.hpp N1, head_distance_numer) from the clamped three-operand dot product with 1024 as
+    // the numerator domain (gc_encode_core.hpp N1, head_distance_numer_b) from the clamped three-operand dot product with 1024 + 2^30 as
     // its accumulator.  The first one is P0, the dot product step 0 of both passes needs anyway: formed once here and handed to
     // them.  A wave with a hostile lane keeps the unchecked sum and the quotient for all its lanes (such a lane's first scale is
     // where the reference's loop as written starts from).
     const uint32_t cpk = pack16(c1, c0);
+    // the rare pass with the 64-bit error sum keeps the old form (bound 32767) and takes the row as it was: 2^30 off again
+    auto wide_total = [&](const uint32_t (&xw)[7], const int (&mp)[14], int sp) -> uint64_t {
+        int row[14];
+#pragma unroll
+        for (int i = 0; i < 14; i++) row[i] = mp[i] - PASS_B_OFF;
+        return pass_fast_core_wide(xw, hpk, row, c0, c1, sp).total;
+    };
     const bool head_numer = __builtin_amdgcn_ballot_w64(!coef_ok) == 0;
     auto prescan_head = [&](const Row &R, int &d0, int &d1, int &P0) __attribute__((always_inline)) {
-        P0 = predicted_p1024(hpk, cpk);
+        P0 = predicted_b(hpk, cpk);
         if (__builtin_expect(head_numer, 1)) {
-            d0 = head_distance_numer(R.mp[0], P0);
-            d1 = head_distance_numer(R.mp[1], predicted_p1024(__builtin_amdgcn_alignbit(R.xw[0], hpk, 16), cpk));
+            d0 = head_distance_numer_b(R.mp[0], P0);
+            d1 = head_distance_numer_b(R.mp[1], predicted_b(__builtin_amdgcn_alignbit(R.xw[0], hpk, 16), cpk));
         } else {
             d0 = pair_lo(R.xw[0]) - div2048(dot2_i16_wrap(hpk, cpk));
             d1 = pair_hi(R.xw[0]) - div2048(dot2_i16_wrap(__builtin_amdgcn_alignbit(R.xw[0], hpk, 16), cpk));
@@ -508,7 +519,7 @@ __device__ __forceinline__ void gc_encode_piece(
         int final_sp = imin(s1 + (cand_b ? 1 : 0), 12);
         const bool at_cap = final_sp >= 12;            // the loop never goes past 12: this pass ends it
         const unsigned ov_limit = at_cap ? 3u : 248u;  // see `rare` below
-        PassOut r = pass_fast_core_t<false, false, true>(xw, hpk, R.mp, c0, c1, final_sp, P0);
+        PassOutB r = pass_fast_core_b<false, true>(xw, hpk, R.mp, c0, c1, final_sp, P0);
         // Straight-line resolution, valid when no lane is `rare`:
         //   * no overflow can start the bump loop (:166-168 needs max_overflow + 8 > 256),
         //   * the 32-bit error sum of every lane that can become final is exact (gc_encode_core.hpp S3:
@@ -533,7 +544,7 @@ __device__ __forceinline__ void gc_encode_piece(
         // several wild ones); only when a channel's BEST is that large (`sat`, wave-uniform) do the 64-bit keys decide -- in
         // the cold block: the hot copy of the frame's tail holds no 64-bit code.
         constexpr unsigned SAT = (1u << 28) - 1;
-        auto argmin32 = [&](const PassOut &r, bool fin, bool &sat) __attribute__((always_inline)) -> int {
+        auto argmin32 = [&](const PassOutB &r, bool fin, bool &sat) __attribute__((always_inline)) -> int {
             const unsigned tot = umin32((unsigned)(r.total >> 32) ? SAT : (unsigned)r.total, SAT);
             const unsigned key = fin ? ((tot << 4) | (unsigned)l16) : 0xFFFFFFFFu;
             const unsigned best = row16_reduce(key, [](unsigned a, unsigned b) { return a < b ? a : b; });
@@ -558,16 +569,16 @@ __device__ __forceinline__ void gc_encode_piece(
         };
         // ---- the frame's tail: winner's history broadcast, winner's record to LDS.  A lambda so that the hot and the cold
         // branch each get their own copy: merging the two branches' PassOut registers instead put the copies on the hot path.
-        auto commit = [&](const PassOut &r, int final_sp, int winner) __attribute__((always_inline)) {
+        auto commit = [&](const PassOutB &r, int final_sp, int winner) __attribute__((always_inline)) {
             const bool won = l16 == winner;
             const unsigned pay = row16_reduce(won ? r.hist_pair : 0u,
                                               [](unsigned a, unsigned b) { return a | b; });
             if (won) {                                           // packed and flushed by the helper, a tile at a time
                 int4 *rec = &s_out[buf][grp][j][0];
-                rec[0] = make_int4(r.q[0], r.q[1], r.q[2], r.q[3]);
-                rec[1] = make_int4(r.q[4], r.q[5], r.q[6], r.q[7]);
-                rec[2] = make_int4(r.q[8], r.q[9], r.q[10], r.q[11]);
-                rec[3] = make_int4(r.q[12], r.q[13], p, final_sp);
+                rec[0] = make_int4(r.q2[0], r.q2[1], r.q2[2], r.q2[3]);
+                rec[1] = make_int4(r.q2[4], r.q2[5], r.q2[6], r.q2[7]);
+                rec[2] = make_int4(r.q2[8], r.q2[9], r.q2[10], r.q2[11]);
+                rec[3] = make_int4(r.q2[12], r.q2[13], p, final_sp);
             }
             if (!RAGGED || upd) hpk = pay;       // pcmBuffer[0] = pcmBuffer[14], pcmBuffer[1] = pcmBuffer[15] (:40-41), as the pair
         };
@@ -598,7 +609,7 @@ __device__ __forceinline__ void gc_encode_piece(
                 // scalar 64-bit error term.  (Coefficients that can wrap went through the reference's loop: sum_exact.)
                 uint64_t total = o.r.total;
                 if (o.fin != 0 && needs_exact_sum(total, o.sum_exact != 0))
-                    total = pass_fast_core_wide(xw, hpk, R.mp, c0, c1, o.final_sp).total;
+                    total = wide_total(xw, R.mp, o.final_sp);
                 winner = argmin64(total, o.fin != 0);
             }
             commit(o.r, o.final_sp, winner);
@@ -621,22 +632,22 @@ __device__ __forceinline__ void gc_encode_piece(
         // passes run without the detour through f32 -- (int)(float)d is d below 2^24, two conversions a sample less -- and each
         // lane checks from its overflow that no distance reached 2^24 (gc_encode_core.hpp: NO_ROUND); a lane that cannot
         // tell sends the wave through the passes as they always were.
-        PassOut ra, rb;
+        PassOutB ra, rb;
 #ifdef VGA_GC_NO_FAST_PASSES                                        // (timing-only switch, tools/build_variants.sh)
         bool short_passes = false;
 #else
         bool short_passes = !__any(sp_b > 9);
 #endif
         if (short_passes) {
-            rb = pass_fast_core_t<false, true, true>(xw, hpk, R.mp, c0, c1, sp_b, P0);
-            ra = pass_fast_core_t<false, true, true>(xw, hpk, R.mp, c0, c1, sp_a, P0);
+            rb = pass_fast_core_b<true, true, false>(xw, hpk, R.mp, c0, c1, sp_b, P0);
+            ra = pass_fast_core_b<true, true, false>(xw, hpk, R.mp, c0, c1, sp_a, P0);
             // (hostile coefficients: the lane walks the reference's loop as written whatever these passes say)
             const bool trusted = !coef_ok || (pass_no_round_is_exact(sp_a, ra.max_overflow) && pass_no_round_is_exact(sp_b, rb.max_overflow));
             short_passes = !__any(!trusted);
         }
         if (!short_passes) {
-            rb = pass_fast_core_t<false, false, true>(xw, hpk, R.mp, c0, c1, sp_b, P0);
-            ra = pass_fast_core_t<false, false, true>(xw, hpk, R.mp, c0, c1, sp_a, P0);
+            rb = pass_fast_core_b<false, true, false>(xw, hpk, R.mp, c0, c1, sp_b, P0);
+            ra = pass_fast_core_b<false, true, false>(xw, hpk, R.mp, c0, c1, sp_a, P0);
         }
         const bool cap_a = sp_a >= 12, cap_b = sp_b >= 12;         // a pass at the cap ends the loop whatever it overflowed
         const int eff_a = cap_a ? 0 : ra.max_overflow, eff_b = cap_b ? 0 : rb.max_overflow;
@@ -659,20 +670,26 @@ __device__ __forceinline__ void gc_encode_piece(
 #endif
         // (Round 6, measured and taken out again: the winning lanes storing the right pass's nibbles under their own masks
         // instead of fourteen selects in every lane -- 18 VALU instructions a frame less, two more exec-masked branches on
-        // the wave's critical path: 148.5 ms against 146.0, profiles/r06_e_encode_variants.log.)
-        PassOut r;
+        // the wave's critical path: 148.5 ms against 146.0, profiles/r06_e_encode_variants.log.
+        // Round 10, the same end without a branch, measured and taken out as well: every lane issuing the record writes of
+        // BOTH passes, each to the record or to a dummy slot of the lane's own by two address selects -- 8 VALU instructions
+        // a frame less, four LDS writes more: 118.3-118.7 ms against 117.8-118.5, profiles/r10_encode_ab.log.)
+        PassOutB r;
 #pragma unroll
-        for (int i = 0; i < 14; i++) r.q[i] = fin_a ? ra.q[i] : rb.q[i];
-        r.total = fin_a ? ra.total : rb.total;
-        r.hist_pair = fin_a ? ra.hist_pair : rb.hist_pair;
+        for (int i = 0; i < 14; i++) r.q2[i] = fin_a ? ra.q2[i] : rb.q2[i];   // (each Z its own: only the value mod 16 is used)
+        // one error block behind the choice (round 10): the passes hand over their history pairs, the sum is formed once
+        uint32_t sel[7];
+#pragma unroll
+        for (int i = 0; i < 7; i++) sel[i] = fin_a ? ra.pairs[i] : rb.pairs[i];
+        r.total = error_sum_pairs(xw, sel);
+        r.hist_pair = sel[6];
         r.max_overflow = fin_a ? ra.max_overflow : rb.max_overflow;
-        r.o12 = r.o13 = 0;
         r.exact = true;
         const int final_sp = fin_a ? sp_a : sp_b;
         // 32-bit keys: error sums from 2^28 on share one key (such a predictor loses to any below); only when a channel's BEST
         // is that large (`sat`, wave-uniform) do the 64-bit keys decide -- in the cold block
         constexpr unsigned SAT = (1u << 28) - 1;
-        auto argmin32 = [&](const PassOut &r, bool fin, bool &sat) __attribute__((always_inline)) -> int {
+        auto argmin32 = [&](const PassOutB &r, bool fin, bool &sat) __attribute__((always_inline)) -> int {
             const unsigned tot = umin32((unsigned)(r.total >> 32) ? SAT : (unsigned)r.total, SAT);
             unsigned key = fin ? ((tot << 3) | (unsigned)p) : 0xFFFFFFFFu;
             key = umin32(key, (unsigned)dpp<DPP_QUAD_XOR1>((int)key));
@@ -696,7 +713,7 @@ __device__ __forceinline__ void gc_encode_piece(
 #undef VGA_MIN64_STAGE
             return (int)(key & 7u);
         };
-        auto commit = [&](const PassOut &r, int final_sp, int winner) __attribute__((always_inline)) {
+        auto commit = [&](const PassOutB &r, int final_sp, int winner) __attribute__((always_inline)) {
             const bool won = p == winner;
             unsigned pay = won ? r.hist_pair : 0u;
             pay |= (unsigned)dpp<DPP_QUAD_XOR1>((int)pay);
@@ -704,10 +721,10 @@ __device__ __forceinline__ void gc_encode_piece(
             pay |= (unsigned)dpp<DPP_ROW_HALF_MIRROR>((int)pay);
             if (won) {
                 int4 *rec = &s_out[buf][grp][j][0];
-                rec[0] = make_int4(r.q[0], r.q[1], r.q[2], r.q[3]);
-                rec[1] = make_int4(r.q[4], r.q[5], r.q[6], r.q[7]);
-                rec[2] = make_int4(r.q[8], r.q[9], r.q[10], r.q[11]);
-                rec[3] = make_int4(r.q[12], r.q[13], p, final_sp);
+                rec[0] = make_int4(r.q2[0], r.q2[1], r.q2[2], r.q2[3]);
+                rec[1] = make_int4(r.q2[4], r.q2[5], r.q2[6], r.q2[7]);
+                rec[2] = make_int4(r.q2[8], r.q2[9], r.q2[10], r.q2[11]);
+                rec[3] = make_int4(r.q2[12], r.q2[13], p, final_sp);
             }
             if (!RAGGED || upd) hpk = pay;       // (a slot past its last frame keeps the history it ended on)
         };
@@ -742,7 +759,7 @@ __device__ __forceinline__ void gc_encode_piece(
                 // scalar 64-bit error term.  (Coefficients that can wrap went through the reference's loop: sum_exact.)
                 uint64_t total = o.r.total;
                 if (o.fin != 0 && needs_exact_sum(total, o.sum_exact != 0))
-                    total = pass_fast_core_wide(xw, hpk, R.mp, c0, c1, o.final_sp).total;
+                    total = wide_total(xw, R.mp, o.final_sp);
                 winner = argmin64(total, o.fin != 0);
             }
             commit(o.r, o.final_sp, winner);
