@@ -210,6 +210,15 @@ SIGNATURES = {
     "vga_gcadpcm_build_channels_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "vga_dsp_write_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "vga_dsp_read_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    # include/vgaudio_hip/gc_files_aligned.h
+    "vga_gc_aligned_layout_for": (ci, [vp, ci, C.POINTER(ci), C.POINTER(i64), vp]),
+    "vga_gc_aligned_create": (ci, [vp, ci, C.POINTER(vp)]),
+    "vga_gc_aligned_destroy": (None, [vp]),
+    "vga_gc_aligned_totals_of": (ci, [vp, vp]),
+    "vga_gc_aligned_offsets": (ci, [vp, C.POINTER(ci), C.POINTER(i64)]),
+    "vga_gc_aligned_ragged_in": (vp, [vp]),
+    "vga_gc_aligned_ragged_out": (vp, [vp]),
+    "vga_gcadpcm_align_channels_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "vga_hca_decode_device_v": (ci, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
     "vga_hca_encode_device_v": (ci, [vp, vp, vp, vp, vp]),
     "vga_hca_stream_create": (ci, [vp, vp, C.POINTER(vp)]),
@@ -385,6 +394,13 @@ class GcFilesTotalsC(C.Structure):
     """vga_gc_files_totals"""
     _fields_ = [("files", C.c_int), ("channels", C.c_int), ("pcm_samples", C.c_int64), ("adpcm_bytes", C.c_int64),
                 ("seek_shorts", C.c_int64), ("image_bytes", C.c_int64), ("build_workspace_bytes", C.c_size_t)]
+
+
+class GcAlignedTotalsC(C.Structure):
+    """vga_gc_aligned_totals (include/vgaudio_hip/gc_files_aligned.h)"""
+    _fields_ = [("files", C.c_int), ("channels", C.c_int), ("aligned_channels", C.c_int), ("pcm_samples", C.c_int64),
+                ("adpcm_bytes", C.c_int64), ("out_pcm_samples", C.c_int64), ("out_adpcm_bytes", C.c_int64), ("seek_shorts", C.c_int64),
+                ("workspace_bytes", C.c_size_t)]
 
 
 NW_MAX_CHANNELS = NW_MAX_TRACKS = 255

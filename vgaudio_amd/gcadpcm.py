@@ -531,3 +531,128 @@ def decode_files(formats):
         out.append(p)
         at += k
     return out
+
+
+class AlignedFileSet:
+    """A set of GC-ADPCM files whose loop starts may need the GcAdpcmAlignment re-encode, resident on the device
+    (include/vgaudio_hip/gc_files_aligned.h has the layout): the channels of all files are the packed rows of two ragged
+    batches, `ragged_in` over the files' sample counts (what the _device_v codec calls wrote) and `ragged_out` over their
+    aligned sample counts; the seek tables are one packed buffer.
+    `files`: one (channels, sample_rate, sample_count, looping, loop_start, loop_end[, alignment[, samples_per_seek_entry]])
+    tuple or _lib.GcFileC per file.  The tensors are the caller's torch tensors on the current device; the call runs on
+    torch's current stream and does not synchronise it."""
+
+    def __init__(self, files=None):
+        self._h = C.c_void_p()
+        arr, n = self._files_array(files)
+        check(_lib.lib().vga_gc_aligned_create(arr, n, C.byref(self._h)))
+        self.totals = _lib.GcAlignedTotalsC()
+        check(_lib.lib().vga_gc_aligned_totals_of(self._h, C.byref(self.totals)))
+        nf, nch = self.totals.files, self.totals.channels
+        fc, so = np.zeros(max(nf, 1), np.int32), np.zeros(max(nch, 1), np.int64)
+        check(_lib.lib().vga_gc_aligned_offsets(self._h, fc.ctypes.data_as(C.POINTER(C.c_int)), so.ctypes.data_as(C.POINTER(C.c_int64))))
+        self.first_channel, self.seek_offsets = fc[:nf], so[:nch]
+        self.files, self.channels = nf, nch
+        self.ragged_in = C.c_void_p(_lib.lib().vga_gc_aligned_ragged_in(self._h))      # borrowed: live as long as this object
+        self.ragged_out = C.c_void_p(_lib.lib().vga_gc_aligned_ragged_out(self._h))
+        self.layouts = []                                                      # per file: vga_gcadpcm_channel_layout_for's numbers
+        for f in arr[:n]:
+            lay = _lib.GcChannelLayoutC()
+            check(_lib.lib().vga_gcadpcm_channel_layout_for(C.byref(f.channel), C.byref(lay)))
+            self.layouts.append(lay)
+
+    @staticmethod
+    def _files_array(files):
+        from .dsp import _gc_file
+        files = [f if isinstance(f, _lib.GcFileC) else _gc_file(*f) for f in (files or [])]
+        return (_lib.GcFileC * max(len(files), 1))(*files), len(files)
+
+    @classmethod
+    def layout(cls, files):
+        """(first_channel int32[files], seek_offsets int64[channels], GcAlignedTotalsC): host only, needs no GPU"""
+        arr, n = cls._files_array(files)
+        nch = sum(arr[i].channels for i in range(n) if arr[i].channels > 0)
+        fc, so, tot = np.zeros(max(n, 1), np.int32), np.zeros(max(nch, 1), np.int64), _lib.GcAlignedTotalsC()
+        check(_lib.lib().vga_gc_aligned_layout_for(arr, n, fc.ctypes.data_as(C.POINTER(C.c_int)), so.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   C.byref(tot)))
+        return fc[:n], so[:tot.channels], tot
+
+    def close(self):
+        if self._h:
+            _lib.lib().vga_gc_aligned_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def offsets(self, which):
+        """(pcm offsets, adpcm offsets) int64[channels] of `ragged_in` ("in") or `ragged_out` ("out")"""
+        po, ao = np.zeros(max(self.channels, 1), np.int64), np.zeros(max(self.channels, 1), np.int64)
+        i64p = C.POINTER(C.c_int64)
+        check(_lib.lib().vga_gcadpcm_ragged_offsets(self.ragged_in if which == "in" else self.ragged_out, po.ctypes.data_as(i64p),
+                                                    ao.ctypes.data_as(i64p)))
+        return po[:self.channels], ao[:self.channels]
+
+    def align_channels(self, adpcm, coefs, adpcm_out, pcm=None, seek=None, loop_context=None, status=None, workspace=None, stream=None):
+        """vga_gcadpcm_align_channels_device_v.  adpcm: uint8[totals.adpcm_bytes], coefs: int16[channels*16], adpcm_out:
+        uint8[totals.out_adpcm_bytes]; outputs that may be None: pcm int16[totals.out_pcm_samples], seek
+        int16[totals.seek_shorts], loop_context int16[channels*3]; status: int32[1] or None; workspace:
+        uint8[totals.workspace_bytes]"""
+        import torch
+        from .dsp import DspFileSet
+        ptr, t = DspFileSet._ptr, self.totals
+        check(_lib.lib().vga_gcadpcm_align_channels_device_v(
+            self._h, ptr(adpcm, torch.uint8, t.adpcm_bytes, "adpcm"), ptr(coefs, torch.int16, self.channels * 16, "coefs"),
+            ptr(adpcm_out, torch.uint8, t.out_adpcm_bytes, "adpcm_out"), ptr(pcm, torch.int16, t.out_pcm_samples, "pcm"),
+            ptr(seek, torch.int16, t.seek_shorts, "seek"), ptr(loop_context, torch.int16, self.channels * 3, "loop_context"),
+            ptr(status, torch.int32, 1, "status"), ptr(workspace, torch.uint8, 0, "workspace"),
+            workspace.numel() if workspace is not None else 0, DspFileSet._stream(stream)))
+
+
+def build_files(pcm16_list, per_file_channel_params):
+    """GcAdpcmFormat().EncodeFromPcm16(file)._clone(alignmentMultiple=, samplesPerSeekTableEntry=) for a list of files -- the
+    coefficient search, the encode, the alignment re-encode, the seek tables and the loop contexts -- on the device and
+    without a launch per file (AlignedFileSet).  `per_file_channel_params`: one (alignmentMultiple, samplesPerSeekTableEntry)
+    per file.  Returns per file a dict of numpy arrays, each a list with one entry per channel: "adpcm" (the aligned
+    stream), "seek" (int16[2 * entries]), "context" (int16[3]), "coefs" (int16[16]); and "sample_count" (the aligned one)."""
+    import torch
+    files, params = list(pcm16_list), list(per_file_channel_params)
+    if len(files) != len(params):
+        raise _lib.ArgumentError("build_files: one (alignmentMultiple, samplesPerSeekTableEntry) per file")
+    L = _lib.lib()
+    s = AlignedFileSet([(f.ChannelCount, f.SampleRate, f.SampleCount, f.Looping, f.LoopStart if f.Looping else 0,
+                         f.LoopEnd if f.Looping else 0, a, e) for f, (a, e) in zip(files, params)])
+    try:
+        if s.files == 0:
+            return []
+        t, nch = s.totals, s.channels
+        pin, _ = s.offsets("in")
+        _, aout = s.offsets("out")
+        host, c = np.zeros(t.pcm_samples, dtype=np.int16), 0
+        for f in files:
+            for ch in f.Channels:
+                host[pin[c]:pin[c] + f.SampleCount] = np.asarray(ch, dtype=np.int16)[:f.SampleCount]
+                c += 1
+        new = lambda n, dtype: torch.zeros(max(int(n), 16), dtype=dtype, device="cuda")
+        pcm = torch.from_numpy(host).cuda()
+        coefs, adpcm, out = new(nch * 16, torch.int16), new(t.adpcm_bytes, torch.uint8), new(t.out_adpcm_bytes, torch.uint8)
+        seek, ctx = new(t.seek_shorts, torch.int16), new(nch * 3, torch.int16)
+        ws = torch.empty(max(L.vga_gcadpcm_ragged_coefs_workspace_bytes(s.ragged_in), t.workspace_bytes, 16), dtype=torch.uint8, device="cuda")
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(L.vga_gcadpcm_coefs_device_v(s.ragged_in, pcm.data_ptr(), coefs.data_ptr(), ws.data_ptr(), ws.numel(), st))
+        check(L.vga_gcadpcm_encode_device_v(s.ragged_in, pcm.data_ptr(), coefs.data_ptr(), None, None, adpcm.data_ptr(), st))
+        s.align_channels(adpcm, coefs, out, seek=seek, loop_context=ctx, workspace=ws)
+        out, seek, ctx, coefs = out.cpu().numpy(), seek.cpu().numpy(), ctx.cpu().numpy(), coefs.cpu().numpy()      # synchronises
+        result, c = [], 0
+        for f, lay in zip(files, s.layouts):
+            nbytes = GcAdpcmMath.SampleCountToByteCount(lay.sample_count_aligned)
+            r = {"adpcm": [], "seek": [], "context": [], "coefs": [], "sample_count": lay.sample_count_aligned}
+            for _ in range(f.ChannelCount):
+                r["adpcm"].append(out[aout[c]:aout[c] + nbytes].copy())
+                r["seek"].append(seek[s.seek_offsets[c]:s.seek_offsets[c] + 2 * lay.seek_table_entries].copy())
+                r["context"].append(ctx[3 * c:3 * c + 3].copy())
+                r["coefs"].append(coefs[16 * c:16 * c + 16].copy())
+                c += 1
+            result.append(r)
+        return result
+    finally:
+        s.close()
