@@ -219,6 +219,17 @@ SIGNATURES = {
     "vga_gc_aligned_ragged_in": (vp, [vp]),
     "vga_gc_aligned_ragged_out": (vp, [vp]),
     "vga_gcadpcm_align_channels_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    # include/vgaudio_hip/nw_files.h
+    "vga_nw_files_layout_for": (ci, [vp, ci, vp, C.POINTER(ci), C.POINTER(i64), C.POINTER(i64), vp]),
+    "vga_nw_files_create": (ci, [vp, ci, vp, C.POINTER(vp)]),
+    "vga_nw_files_create_from_infos": (ci, [C.POINTER(vp), ci, C.POINTER(i64), C.POINTER(vp)]),
+    "vga_nw_files_destroy": (None, [vp]),
+    "vga_nw_files_totals_of": (ci, [vp, vp]),
+    "vga_nw_files_offsets": (ci, [vp, C.POINTER(ci), C.POINTER(i64), C.POINTER(i64)]),
+    "vga_nw_files_gc_files": (ci, [vp, vp]),
+    "vga_nw_files_ragged": (vp, [vp]),
+    "vga_nwstm_write_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "vga_nwstm_read_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "vga_hca_decode_device_v": (ci, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
     "vga_hca_encode_device_v": (ci, [vp, vp, vp, vp, vp]),
     "vga_hca_stream_create": (ci, [vp, vp, C.POINTER(vp)]),
@@ -452,6 +463,24 @@ class NwInfoC(C.Structure):
                     "seek_table_offset", "seek_entries", "seek_big_endian", "head_block_offset", "head_block_size",
                     "seek_block_offset", "seek_block_size", "data_block_offset", "data_block_size", "audio_data_offset",
                     "audio_data_length", "adpcm_bytes", "file_size")])
+
+
+class NwFileC(C.Structure):
+    """vga_nw_file (include/vgaudio_hip/nw_files.h)"""
+    _fields_ = [(n, C.c_int) for n in ("channels", "sample_rate", "sample_count", "looping", "loop_start", "loop_end")]
+
+
+class NwFileConfigC(C.Structure):
+    """vga_nw_file_config"""
+    _fields_ = ([(n, C.c_int) for n in ("target", "samples_per_interleave", "samples_per_seek_table_entry", "loop_point_alignment",
+                                        "track_type", "seek_table_type")]
+                + [("version", C.c_uint32), ("endianness", C.c_int)])
+
+
+class NwFilesTotalsC(C.Structure):
+    """vga_nw_files_totals"""
+    _fields_ = [("files", C.c_int), ("channels", C.c_int), ("pcm_samples", C.c_int64), ("adpcm_bytes", C.c_int64),
+                ("seek_shorts", C.c_int64), ("image_bytes", C.c_int64)]
 
 
 class NwWavInfoC(C.Structure):

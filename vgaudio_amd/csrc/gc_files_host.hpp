@@ -61,37 +61,41 @@ inline bool writer_granule16(const FileGeom &g, bool last_block)
 // (file, chunk) items over the audio region of every image: the region of file f is output_size * nch bytes; its full
 // blocks and its last block are cut separately (the last block's rows are packed more tightly and may allow only the
 // smaller granule), each into chunks of CHUNK_GRANULES granules.  No item lies wholly outside its image.
-inline void cut_writer_items(FilesLayout &L)
+// granule16(geom, last_block): may that part of the file move 16-byte granules (the container's rule)
+template <class Rule>
+inline void cut_writer_items(std::vector<FileGeom> &geom, std::vector<Item> &items, Rule granule16)
 {
-    for (size_t f = 0; f < L.geom.size(); f++) {
-        FileGeom &g = L.geom[f];
+    for (size_t f = 0; f < geom.size(); f++) {
+        FileGeom &g = geom[f];
         const uint64_t total = (uint64_t)g.output_size * g.channels;
         if (total == 0) continue;
         const uint32_t out_blocks = (g.output_size + g.interleave - 1) / g.interleave;
         const uint64_t boundary = (uint64_t)(out_blocks - 1) * g.interleave * g.channels;
-        g.granule16 = (writer_granule16(g, false) ? 1u : 0u) | (writer_granule16(g, true) ? 2u : 0u);
+        g.granule16 = (granule16(g, false) ? 1u : 0u) | (granule16(g, true) ? 2u : 0u);
         const uint64_t from[2] = {0, boundary}, to[2] = {boundary, total};
         for (int part = 0; part < 2; part++) {
             const bool g16 = (g.granule16 >> part) & 1;
             const uint64_t step = (uint64_t)CHUNK_GRANULES * (g16 ? 16 : 8);
             for (uint64_t at = from[part]; at < to[part]; at += step)
-                L.audio_items.push_back({(int)f, (uint32_t)(at >> 3) | (g16 ? 0x80000000u : 0u)});
+                items.push_back({(int)f, (uint32_t)(at >> 3) | (g16 ? 0x80000000u : 0u)});
         }
     }
 }
+inline void cut_writer_items(FilesLayout &L) { cut_writer_items(L.geom, L.audio_items, writer_granule16); }
 
 // (channel, chunk) items over the rows the reader fills: output_size bytes each
-inline void cut_reader_items(FilesLayout &L)
+inline void cut_reader_items(const std::vector<FileGeom> &geom, std::vector<Item> &items)
 {
-    for (size_t f = 0; f < L.geom.size(); f++) {
-        const FileGeom &g = L.geom[f];
+    for (size_t f = 0; f < geom.size(); f++) {
+        const FileGeom &g = geom[f];
         const bool g16 = g.granule16 & 1;
         const uint64_t step = (uint64_t)CHUNK_GRANULES * (g16 ? 16 : 8);
         for (int i = 0; i < g.channels; i++)
             for (uint64_t at = 0; at < g.output_size; at += step)
-                L.audio_items.push_back({g.first_channel + i, (uint32_t)(at >> 3) | (g16 ? 0x80000000u : 0u)});
+                items.push_back({g.first_channel + i, (uint32_t)(at >> 3) | (g16 ? 0x80000000u : 0u)});
     }
 }
+inline void cut_reader_items(FilesLayout &L) { cut_reader_items(L.geom, L.audio_items); }
 
 inline void cut_meta_items(FilesLayout &L)
 {

@@ -3,235 +3,44 @@
 // and taken apart in HBM, nfiles equally shaped files per launch.  Everything on the device is byte movement:
 // HBM-bound, every byte of an image read or written once.
 #include "container_host.hpp"
+#include "nw_header_body.hpp"
 #include "pcm_kernels.hpp"
 
 using namespace vga;
 using namespace vga::container;
-
-namespace {
-
-constexpr int kDefaultSamples = 14336;                      // BytesToSamples(0x2000) (BxstmConfiguration.cs:17,48)
-constexpr int kOffsetMarker = 0x01000000, kOffsetMarkerV2 = 0x01010000;   // BrstmWriter.cs:76-80
-// Structures/ReferenceType.cs
-enum : int {
-    kByteTable = 0x0100, kReferenceTable = 0x0101, kGcAdpcmInfo = 0x0300, kSampleData = 0x1F00, kStreamInfoBlock = 0x4000,
-    kStreamSeekBlock = 0x4001, kStreamDataBlock = 0x4002, kStreamRegionBlock = 0x4003, kStreamPrefetchDataBlock = 0x4004,
-    kStreamInfo = 0x4100, kTrackInfo = 0x4101, kChannelInfo = 0x4102
-};
-constexpr int kCodecPcm8 = 0, kCodecPcm16 = 1, kCodecGcAdpcm = 2;   // NwCodec.cs
-
-// Common.cs:103-140 on a packed NwVersion
-bool include_track_info(uint32_t v) { const int major = v >> 24; return (major == 0 && v <= 0x00020000u) || (major >= 2 && v <= 0x02010000u); }
-bool include_region_info(uint32_t v) { const int major = v >> 24; return (major >= 2 && v >= 0x02010000u) || major == 0; }
-bool include_unaligned_loop(uint32_t v) { const int major = v >> 24; return (major == 0 && v >= 0x00040000u) || (major >= 2 && v >= 0x02030000u); }
-bool include_checksum(uint32_t v) { return (v >> 24) == 0 && v >= 0x00050000u; }
-
-}  // namespace
+using namespace vga::nw;                                    // the formats' constants, the size math (nw_host.hpp)
 
 // ---------------------------------------------------------------- device side
 namespace vga {
 namespace nwstm {
 
-struct TrackK { int channel_count; uint8_t left, right, volume, panning; };
+using nw::TrackK;
 
 // everything the header kernel writes that is not per channel; passed by value (< 4 KiB of kernel arguments)
-struct HeaderArgs {
-    int target, big, nch, looping, sample_rate, loop_start, loop_end, sample_count;
-    int interleave_count, interleave_size, samples_per_interleave, last_block_size_without_padding, last_block_samples;
-    int last_block_size, samples_per_seek_table_entry, track_short, track_info, region_info, unaligned_loop, version_word;
-    int head_offset, head_size, head1_size, head2_size, seek_offset, seek_size, data_offset, data_size, audio_offset;
-    int file_size, track_count;
-    int codec, bytes_per_seek_table_entry;                  // NwCodec: GC-ADPCM, or PCM8 / PCM16 (no seek block)
+struct HeaderArgs : nw::HeaderGeom {
     TrackK tracks[VGA_NW_MAX_TRACKS];
 };
 
-// A positioned, endian-aware writer over one image, as the reference's BinaryWriter over MemoryStream(byte[FileSize])
-// (Utilities/BinaryWriterBE.cs for big-endian files).
-struct Cursor {
-    uint8_t *buf;
-    int pos;
-    bool big;
-    __device__ void put8(int v) { buf[pos++] = (uint8_t)v; }
-    __device__ void put16(int v) { if (big) { put8(v >> 8); put8(v); } else { put8(v); put8(v >> 8); } }
-    __device__ void put32(int v) { if (big) { put16(v >> 16); put16(v); } else { put16(v); put16(v >> 16); } }
-    __device__ void tag(const char *t) { for (int k = 0; k < 4; k++) put8(t[k]); }   // WriteUTF8: bytes as they are
+// equally shaped files: file f's channel c is row f * nch + c of the pitched inputs, the tracks are the launch's
+struct PitchedRows {
+    const HeaderArgs &a;
+    const uint8_t *adpcm;
+    int64_t adpcm_pitch;
+    int adpcm_len, row0;
+    __device__ int row(int ch) const { return row0 + ch; }
+    __device__ int first_byte(int ch) const { return adpcm_len > 0 ? adpcm[(int64_t)(row0 + ch) * adpcm_pitch] : 0; }
+    __device__ TrackK track(int i) const { return a.tracks[i]; }
 };
 
-// One workgroup per image: the threads zero everything in front of the seek block (of the DATA block for PCM, which
-// has none) and between the DATA header and the audio, then lane 0 writes the file header and HEAD
-// (BrstmWriter.cs:130-260) or INFO (BCFstmWriter.cs:171-333).  PCM streams take the writers' Codec != GcAdpcm branches.
+// One workgroup per image (nw_header_body.hpp)
 __global__ __launch_bounds__(64) void nw_header_kernel(HeaderArgs a, const uint8_t *__restrict__ adpcm, int64_t adpcm_pitch,
                                                        int adpcm_len, const int16_t *__restrict__ coefs,
                                                        const int16_t *__restrict__ gain, const int16_t *__restrict__ start_ctx,
                                                        const int16_t *__restrict__ loop_ctx, uint8_t *__restrict__ files,
                                                        int64_t file_pitch)
 {
-    uint8_t *img = files + (int64_t)blockIdx.x * file_pitch;
-    const bool gc = a.codec == kCodecGcAdpcm;
-    for (int k = threadIdx.x, end = gc ? a.seek_offset : a.data_offset; k < end; k += 64) img[k] = 0;
-    for (int k = a.data_offset + threadIdx.x; k < a.audio_offset; k += 64) img[k] = 0;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const int nch = a.nch, row0 = blockIdx.x * nch;
-    // GcAdpcmChannel.StartContext: (Adpcm[0], 0, 0) for a fresh channel (GcAdpcmChannel.cs:45)
-    auto ctx = [&](Cursor &c, int ch, bool loop) {
-        const int r = row0 + ch;
-        // the loop context written for a file that does not loop is the start context (BrstmWriter.cs:250, BCFstmWriter.cs:325)
-        if (loop && a.looping) {
-            for (int k = 0; k < 3; k++) c.put16(loop_ctx ? loop_ctx[r * 3 + k] : 0);
-        } else if (start_ctx) {
-            for (int k = 0; k < 3; k++) c.put16(start_ctx[r * 3 + k]);
-        } else {
-            c.put16(adpcm_len > 0 ? adpcm[(int64_t)r * adpcm_pitch] : 0);
-            c.put16(0);
-            c.put16(0);
-        }
-    };
-    auto coef = [&](Cursor &c, int ch) { for (int k = 0; k < 16; k++) c.put16(coefs[(row0 + ch) * 16 + k]); };
-    Cursor c{img, 0, a.big != 0};
-    const int T = a.track_count;
-    if (a.target == VGA_NW_RSTM) {
-        c.tag("RSTM");                                      // WriteRstmHeader (:130-145)
-        c.put16(0xfeff);
-        c.put16(0x0100);
-        c.put32(a.file_size);
-        c.put16(0x40);
-        c.put16(2);
-        c.put32(a.head_offset); c.put32(a.head_size);
-        c.put32(a.seek_offset); c.put32(a.seek_size);
-        c.put32(a.data_offset); c.put32(a.data_size);
-        c.pos = a.head_offset;                              // WriteHeadBlock (:147-162)
-        c.tag("HEAD");
-        c.put32(a.head_size);
-        c.put32(kOffsetMarker); c.put32(24);
-        c.put32(kOffsetMarker); c.put32(24 + a.head1_size);
-        c.put32(kOffsetMarker); c.put32(24 + a.head1_size + a.head2_size);
-        c.put8(a.codec);                                    // WriteHeadBlock1 (:164-183)
-        c.put8(a.looping);
-        c.put8(nch);                                        // (byte)ChannelCount
-        c.put8(0);
-        c.put16(a.sample_rate);                             // (ushort)SampleRate
-        c.put16(0);
-        c.put32(a.loop_start);
-        c.put32(a.sample_count);
-        c.put32(a.audio_offset);
-        c.put32(a.interleave_count);
-        c.put32(a.interleave_size);
-        c.put32(a.samples_per_interleave);
-        c.put32(a.last_block_size_without_padding);
-        c.put32(a.last_block_samples);
-        c.put32(a.last_block_size);
-        c.put32(a.samples_per_seek_table_entry);
-        c.put32(a.bytes_per_seek_table_entry);
-        const int tinfo = a.track_short ? 4 : 0x0c;         // WriteHeadBlock2 (:185-216)
-        c.put8(T);
-        c.put8(a.track_short ? 0 : 1);
-        c.put16(0);
-        int base = 24 + 0x34 + 4;
-        for (int i = 0; i < T; i++) { c.put32(a.track_short ? kOffsetMarker : kOffsetMarkerV2); c.put32(base + T * 8 + tinfo * i); }
-        for (int i = 0; i < T; i++) {
-            const TrackK &t = a.tracks[i];
-            if (!a.track_short) { c.put8(t.volume); c.put8(t.panning); c.put16(0); c.put32(0); }
-            c.put8(t.channel_count);
-            c.put8(t.left);
-            c.put8(t.right);
-            c.put8(0);
-        }
-        c.put8(nch);                                        // WriteHeadBlock3 (:218-256)
-        c.put8(0);
-        c.put16(0);
-        base = 24 + 0x34 + a.head2_size + 4;
-        const int cinfo = gc ? 0x38 : 8;                    // ChannelInfoSize
-        for (int i = 0; i < nch; i++) { c.put32(kOffsetMarker); c.put32(base + nch * 8 + cinfo * i); }
-        for (int i = 0; i < nch; i++) {
-            c.put32(kOffsetMarker);
-            if (!gc) { c.put32(0); continue; }
-            c.put32(base + nch * 8 + 0x38 * i + 8);
-            coef(c, i);
-            c.put16(gain ? gain[row0 + i] : 0);
-            ctx(c, i, false);
-            ctx(c, i, true);
-            c.put16(0);
-        }
-        if (gc) {
-            c.pos = a.seek_offset;                          // WriteAdpcBlock (:258-267)
-            c.tag("ADPC");
-            c.put32(a.seek_size);
-        }
-        c.pos = a.data_offset;                              // WriteDataBlock (:270-274)
-        c.tag("DATA");
-        c.put32(a.data_size);
-        c.put32(0x18);
-        return;
-    }
-    c.tag(a.target == VGA_NW_CSTM ? "CSTM" : "FSTM");       // WriteHeader (:171-197)
-    c.put16(0xfeff);
-    c.put16(0x40);
-    c.put32(a.version_word);
-    c.put32(a.file_size);
-    c.put16(gc ? 3 : 2);
-    c.put16(0);
-    c.put16(kStreamInfoBlock); c.put16(0); c.put32(a.head_offset); c.put32(a.head_size);
-    if (gc) { c.put16(kStreamSeekBlock); c.put16(0); c.put32(a.seek_offset); c.put32(a.seek_size); }
-    c.put16(kStreamDataBlock); c.put16(0); c.put32(a.data_offset); c.put32(a.data_size);
-    c.pos = a.head_offset;                                  // WriteInfoBlock (:199-223)
-    c.tag("INFO");
-    c.put32(a.head_size);
-    c.put16(kStreamInfo); c.put16(0); c.put32(24);
-    if (a.track_info) { c.put16(kReferenceTable); c.put16(0); c.put32(24 + a.head1_size); }
-    else { c.put32(0); c.put32(-1); }
-    c.put16(kReferenceTable); c.put16(0); c.put32(24 + a.head1_size + a.head2_size);
-    c.put8(a.codec);                                        // WriteInfoBlock1 (:225-258)
-    c.put8(a.looping);
-    c.put8(nch);
-    c.put8(0);
-    c.put32(a.sample_rate);
-    c.put32(a.loop_start);
-    c.put32(a.sample_count);
-    c.put32(a.interleave_count);
-    c.put32(a.interleave_size);
-    c.put32(a.samples_per_interleave);
-    c.put32(a.last_block_size_without_padding);
-    c.put32(a.last_block_samples);
-    c.put32(a.last_block_size);
-    c.put32(a.bytes_per_seek_table_entry);
-    c.put32(a.samples_per_seek_table_entry);
-    c.put16(kSampleData); c.put16(0); c.put32(0x18);
-    if (a.region_info) { c.put16(kByteTable); c.put16(0); c.put32(0); c.put32(-1); }
-    if (a.unaligned_loop) { c.put32(a.loop_start); c.put32(a.loop_end); }   // Adpcm.LoopStart / LoopEnd
-    if (a.track_info) {                                     // WriteInfoBlock2 (:260-275)
-        c.put32(T);
-        for (int i = 0; i < T; i++) { c.put16(kTrackInfo); c.put16(0); c.put32(4 + 8 * T + 4 + 8 * nch + 0x14 * i); }
-    }
-    const int tts = a.track_info ? 0x14 * T : 0;            // WriteInfoBlock3 (:277-333)
-    c.put32(nch);
-    for (int i = 0; i < nch; i++) { c.put16(kChannelInfo); c.put16(0); c.put32(4 + 8 * nch + tts + 8 * i); }
-    if (a.track_info)
-        for (int i = 0; i < T; i++) {
-            const TrackK &t = a.tracks[i];
-            c.put8(t.volume); c.put8(t.panning); c.put16(0);
-            c.put16(kByteTable); c.put16(0); c.put32(0xc);
-            c.put32(t.channel_count);
-            c.put8(t.left); c.put8(t.right); c.put16(0);
-        }
-    for (int i = 0; i < nch; i++) {
-        if (gc) { c.put16(kGcAdpcmInfo); c.put16(0); c.put32(8 * nch - 8 * i + 0x2e * i); }
-        else { c.put32(0); c.put32(-1); }                   // a null reference: PCM has no channel info body
-    }
-    if (gc) {
-        for (int i = 0; i < nch; i++) {
-            coef(c, i);
-            ctx(c, i, false);
-            ctx(c, i, true);
-            c.put16(0);
-        }
-        c.pos = a.seek_offset;                              // WriteSeekBlock (:335-344)
-        c.tag("SEEK");
-        c.put32(a.seek_size);
-    }
-    c.pos = a.data_offset;                                  // WriteDataBlock (:346-352): bytes 8..0x20 stay zero
-    c.tag("DATA");
-    c.put32(a.data_size);
+    const PitchedRows rows{a, adpcm, adpcm_pitch, adpcm_len, (int)blockIdx.x * a.nch};
+    nw::write_header(a, rows, coefs, gain, start_ctx, loop_ctx, files + (int64_t)blockIdx.x * file_pitch);
 }
 
 // GcAdpcmFormat.BuildSeekTable (GcAdpcmFormat.cs:100-113): the channels' tables interleaved by 2 shorts, resized to
@@ -290,18 +99,7 @@ void header_args(const vga_nwstm_layout &L, const vga_nwstm_params *p, int nch, 
                  int codec = kCodecGcAdpcm)
 {
     std::memset(a, 0, sizeof *a);
-    a->target = L.target; a->big = L.endianness; a->nch = nch; a->looping = L.looping; a->sample_rate = p->sample_rate;
-    a->loop_start = L.loop_start; a->loop_end = L.loop_end; a->sample_count = L.sample_count;
-    a->interleave_count = L.interleave_count; a->interleave_size = L.interleave_size;
-    a->samples_per_interleave = L.samples_per_interleave; a->last_block_size_without_padding = L.last_block_size_without_padding;
-    a->last_block_samples = L.last_block_samples; a->last_block_size = L.last_block_size;
-    a->samples_per_seek_table_entry = L.samples_per_seek_table_entry; a->track_short = p->track_type == VGA_NW_TRACK_SHORT;
-    a->track_info = L.include_track_info; a->region_info = L.include_region_info; a->unaligned_loop = L.include_unaligned_loop;
-    a->version_word = L.version_word; a->head_offset = L.head_block_offset; a->head_size = L.head_block_size;
-    a->head1_size = L.head1_size; a->head2_size = L.head2_size; a->seek_offset = L.seek_block_offset;
-    a->seek_size = L.seek_block_size; a->data_offset = L.data_block_offset; a->data_size = L.data_block_size;
-    a->audio_offset = L.audio_data_offset; a->file_size = L.file_size; a->track_count = L.track_count;
-    a->codec = codec; a->bytes_per_seek_table_entry = L.bytes_per_seek_table_entry;
+    nw::header_geom(L, p, nch, codec, a);
     fill_tracks(L, tracks, a);
 }
 
@@ -314,140 +112,6 @@ int pcm_codec_check(int codec)
     if (codec == kCodecGcAdpcm) set_error("the stream is GC-ADPCM (codec 2): read it with vga_nwstm_parse");
     else set_error("stream codec %d is neither PCM8 (0) nor PCM16 (1)", codec);
     return VGA_ERR_INVALID_OP;
-}
-
-// the target's byte order and the version fields (BrstmWriter.cs:119, BCFstmWriter.cs:27,57-65,147-162)
-int target_and_version(const vga_nwstm_params *p, vga_nwstm_layout *L)
-{
-    L->target = p->target;
-    if (p->target == VGA_NW_RSTM) {
-        L->endianness = VGA_NW_BIG_ENDIAN;                  // BrstmWriter.cs:119
-        L->version = 0x01000000u;
-    } else {
-        L->endianness = p->endianness < 0 ? (p->target == VGA_NW_CSTM ? VGA_NW_LITTLE_ENDIAN : VGA_NW_BIG_ENDIAN) : (p->endianness != 0);
-        uint32_t v = p->version ? p->version : (p->target == VGA_NW_CSTM ? 0x02010000u : 0x00030000u);
-        const int major = v >> 24, minor = (v >> 16) & 0xff;
-        if ((v & 0xffff) != 0 || (p->target == VGA_NW_CSTM ? (major != 2 || minor > 3) : (major != 0 || minor < 2 || minor > 5))) {
-            set_error("version %u.%u.%u is not one this writer produces (BCSTM 2.0-2.3, BFSTM 0.2-0.5)", major, minor, (v >> 8) & 0xff);
-            return VGA_ERR_OUT_OF_RANGE;
-        }
-        L->version = v;
-        L->include_track_info = include_track_info(v);
-        L->include_region_info = include_region_info(v);
-        L->include_unaligned_loop = include_unaligned_loop(v);
-        // BCFstmWriter.GetVersion (:147-162): the configured Version only selects which fields exist
-        const int word = p->target == VGA_NW_FSTM ? (L->include_unaligned_loop ? 4 : 3)
-                         : (L->include_track_info && L->include_region_info) ? 0x201
-                         : (!L->include_track_info && L->include_region_info) ? 0x202 : 0x200;
-        L->version_word = word << 16;
-    }
-    return VGA_OK;
-}
-
-// BxstmConfiguration.cs:42-100 and the size math of BrstmWriter.cs:22-74 / BCFstmWriter.cs:23-83 for a GC-ADPCM, PCM8 or
-// PCM16 stream (L zeroed by the caller).  PCM has no divisible-by-14 rule, no loop alignment, no seek block and no
-// channel info body, and no version with unaligned loop points.
-int nw_layout(const vga_nwstm_params *p, int codec, int nch, vga_nwstm_layout *L)
-{
-    const bool gc = codec == kCodecGcAdpcm;
-    const int bps = codec == kCodecPcm16 ? 2 : 1;           // PCM bytes per sample
-    auto bytes = [&](int samples) { return gc ? bytes_of(samples) : samples * bps; };
-    if (p->target < VGA_NW_RSTM || p->target > VGA_NW_FSTM) { set_error("unknown NintendoWare target %d", p->target); return VGA_ERR_ARGUMENT; }
-    if (nch < 1 || nch > VGA_NW_MAX_CHANNELS) { set_error("channel count %d out of range (1..%d)", nch, VGA_NW_MAX_CHANNELS); return VGA_ERR_ARGUMENT; }
-    if (gc && (p->keep_seek_table || p->keep_loop_context)) {
-        set_error("only RecalculateSeekTable = RecalculateLoopContext = true is supported: the tables come from the channel builder");
-        return VGA_ERR_ARGUMENT;
-    }
-    const int def = gc ? kDefaultSamples : 0x2000 / bps;    // BytesToSamples(DefaultInterleave, Codec)
-    const int spi = p->samples_per_interleave ? p->samples_per_interleave : def;
-    if (spi < 1) return out_of_range("Number of samples per interleave must be positive");
-    if (gc && spi % 14 != 0) return out_of_range("Number of samples per interleave must be divisible by 14");
-    const int spe = p->samples_per_seek_table_entry ? p->samples_per_seek_table_entry : def;
-    if (spe < 2) return out_of_range("Number of samples per interleave must be 2 or greater");
-    const int align = p->loop_point_alignment ? p->loop_point_alignment : kDefaultSamples;
-    if (gc && align < 0) return out_of_range("negative loop point alignment");
-    if (p->sample_rate < 0 || p->sample_count < 0) return out_of_range("negative sample rate / sample count");
-    if (p->track_type != VGA_NW_TRACK_STANDARD && p->track_type != VGA_NW_TRACK_SHORT) { set_error("unknown BRSTM track type"); return VGA_ERR_ARGUMENT; }
-    if (p->seek_table_type != VGA_NW_SEEK_STANDARD && p->seek_table_type != VGA_NW_SEEK_SHORT) { set_error("unknown BRSTM seek table type"); return VGA_ERR_ARGUMENT; }
-    if (p->track_count < 0 || p->track_count > VGA_NW_MAX_TRACKS) {
-        set_error("track count %d out of range (0 = the default list, at most %d)", p->track_count, VGA_NW_MAX_TRACKS);
-        return VGA_ERR_OUT_OF_RANGE;
-    }
-    if (int rc = check_loop(p->looping, p->loop_start, p->loop_end, p->sample_count)) return rc;
-    const int loop_start = p->looping ? p->loop_start : 0, loop_end = p->looping ? p->loop_end : 0;
-    if (int rc = target_and_version(p, L)) return rc;
-    int shift = 0;
-    if (gc) {
-        // SetupWriter (BrstmWriter.cs:88-103): WithAlignment when the loop start is not aligned; every channel is then
-        // rebuilt with LoopAlignmentMultiple and SamplesPerSeekTableEntry -- vga_gcadpcm_build_channels_* does both
-        L->channel.sample_count = p->sample_count;
-        L->channel.looping = p->looping ? 1 : 0;
-        L->channel.loop_start = loop_start;
-        L->channel.loop_end = loop_end;
-        L->channel.loop_alignment_multiple = align;
-        L->channel.samples_per_seek_table_entry = spe;
-        vga_gcadpcm_channel_layout cl;
-        if (int rc = vga_gcadpcm_channel_layout_for(&L->channel, &cl)) return rc;
-        L->alignment_needed = cl.alignment_needed;
-        L->channel_sample_count = cl.sample_count_aligned;
-        L->channel_adpcm_bytes = bytes_of(cl.sample_count_aligned);
-        L->channel_seek_entries = cl.seek_table_entries;
-        shift = cl.alignment_needed ? cl.loop_start_aligned - loop_start : 0;          // GcAdpcmFormat.cs:19-22
-    } else {
-        if (L->include_unaligned_loop) {                    // BCFstmWriter.cs:250-254 reads Adpcm.LoopStart
-            set_error("BCSTM 2.3+ / BFSTM 0.4+ carry GC-ADPCM unaligned loop points, which a PCM stream does not have "
-                      "(the reference writer fails on a null GcAdpcmFormat): choose an earlier version");
-            return VGA_ERR_INVALID_OP;
-        }
-        const int64_t row = (int64_t)p->sample_count * bps;
-        if ((int64_t)spi * bps > 0x7FFFFFFF) return out_of_range("Number of samples per interleave too large for the interleave's int size");
-        if (row > 0x7FFFFFFF) { set_error("file would exceed 2 GiB (the reference's FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
-        L->channel_sample_count = p->sample_count;
-        L->channel_adpcm_bytes = (int)row;
-    }
-    L->looping = p->looping ? 1 : 0;
-    L->loop_start = loop_start + shift;
-    L->loop_end = loop_end + shift;
-    const int sc = L->looping ? L->loop_end : p->sample_count;                                       // SampleCount (:27)
-    L->sample_count = sc;
-    L->track_count = p->track_count ? p->track_count : div_round_up(nch, 2);
-    const bool rstm = p->target == VGA_NW_RSTM;
-    L->samples_per_interleave = spi;
-    L->interleave_size = bytes(spi);
-    L->interleave_count = div_round_up(sc, spi);
-    L->last_block_samples = sc - (L->interleave_count - 1) * spi;
-    L->last_block_size_without_padding = bytes(L->last_block_samples);
-    L->last_block_size = (int)next_multiple(L->last_block_size_without_padding, 0x20);
-    L->samples_per_seek_table_entry = gc || !rstm ? spe : 0;  // a PCM BRSTM writes zeros (BrstmWriter.cs:51-52)
-    L->bytes_per_seek_table_entry = gc || !rstm ? 4 : 0;
-    if (gc) L->seek_table_entry_count = rstm && p->seek_table_type == VGA_NW_SEEK_SHORT ? bytes_of(sc) / spe + 1 : div_round_up(sc, spe);
-    const int64_t audio_data_size = next_multiple(bytes(sc), 0x20);
-    const int T = L->track_count;
-    L->header_size = 0x40;
-    if (rstm) {
-        L->head1_size = 0x34;
-        L->head2_size = 4 + 8 * T + (p->track_type == VGA_NW_TRACK_SHORT ? 4 : 0x0c) * T;
-        L->head3_size = 4 + 8 * nch + (gc ? 0x38 : 8) * nch;                              // ChannelInfoSize
-    } else {
-        L->head1_size = 0x38 + (L->include_region_info ? 0xc : 0) + (L->include_unaligned_loop ? 8 : 0);
-        L->head2_size = L->include_track_info ? 4 + 8 * T : 0;
-        L->head3_size = 4 + 8 * nch + (L->include_track_info ? 0x14 * T : 0) + 8 * nch + (gc ? 0x2e : 0) * nch;
-    }
-    const int64_t head = next_multiple(8 + 24 + L->head1_size + L->head2_size + L->head3_size, 0x20);
-    const int64_t seek = gc ? next_multiple(8 + (int64_t)L->seek_table_entry_count * nch * 4, 0x20) : 0;   // PCM: no ADPC / SEEK
-    const int64_t data = 0x20 + audio_data_size * nch;
-    const int64_t file = 0x40 + head + seek + data;
-    if (file > 0x7FFFFFFF) { set_error("file would exceed 2 GiB (the reference's FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
-    L->head_block_offset = 0x40;
-    L->head_block_size = (int)head;
-    L->seek_block_offset = gc ? (int)(0x40 + head) : 0;
-    L->seek_block_size = (int)seek;
-    L->data_block_offset = (int)(0x40 + head + seek);
-    L->data_block_size = (int)data;
-    L->audio_data_offset = L->data_block_offset + 0x20;
-    L->audio_data_size = (int)audio_data_size;
-    L->file_size = (int)file;
-    return VGA_OK;
 }
 
 }  // namespace

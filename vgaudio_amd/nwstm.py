@@ -395,3 +395,184 @@ def configuration_of(info):
         c.Endianness = Endianness(info.endianness)
         c.Version = NwVersion.FromPacked(info.version)
     return c
+
+
+# ---------------------------------------------------------------- sets of files on the device (include/vgaudio_hip/nw_files.h)
+def _nw_file(channels, sample_rate, sample_count, looping=False, loop_start=0, loop_end=0):
+    if not looping:
+        loop_start = loop_end = 0
+    return _lib.NwFileC(int(channels), int(sample_rate), int(sample_count), int(bool(looping)), int(loop_start), int(loop_end))
+
+
+def _file_config(target, configuration=None):
+    """vga_nw_file_config of a target and a BxstmConfiguration (None: the defaults)"""
+    if isinstance(configuration, _lib.NwFileConfigC):
+        return configuration
+    c = configuration or BxstmConfiguration()
+    if c.Codec != NwCodec.GcAdpcm:
+        raise _lib.ArgumentError("sets of NintendoWare files hold GC-ADPCM streams (PCM streams go through the per-file writers)")
+    if not (c.RecalculateSeekTable and c.RecalculateLoopContext):
+        raise _lib.ArgumentError("only RecalculateSeekTable = RecalculateLoopContext = true is supported")
+    if c.LoopPointAlignment < 0:
+        raise _lib.ArgumentOutOfRangeError("negative loop point alignment")
+    return _lib.NwFileConfigC(int(NwTarget(target)), c.SamplesPerInterleave, c.SamplesPerSeekTableEntry, c.LoopPointAlignment,
+                              int(c.TrackType), int(c.SeekTableType), c.Version.Version if c.Version is not None else 0,
+                              -1 if c.Endianness is None else int(c.Endianness))
+
+
+class NwFileSet:
+    """A set of BRSTM / BCSTM / BFSTM files of different shapes, resident on the device (include/vgaudio_hip/nw_files.h has the
+    layout): the channels of all files are the packed rows gcadpcm.AlignedFileSet leaves as its output, the seek tables one
+    packed buffer, the images another.  `files`: one (channels, sample_rate, sample_count, looping, loop_start, loop_end) tuple or
+    _lib.NwFileC per file, the loop the format's, before the writer aligns it; `target`: NwTarget; `configuration`: the
+    BxstmConfiguration of the whole set (as VGAudio.Cli/Batch.cs applies one to every file).  The tensors are the caller's
+    torch tensors on the current device; the calls run on torch's current stream and do not synchronise it."""
+
+    def __init__(self, files=None, target=NwTarget.Revolution, configuration=None, _handle=None):
+        self._h, self.image_sizes = C.c_void_p(), None
+        if _handle is not None:
+            self._h = _handle
+        else:
+            arr, n = self._files_array(files)
+            cfg = _file_config(target, configuration)
+            check(_lib.lib().vga_nw_files_create(arr, n, C.byref(cfg), C.byref(self._h)))
+            self.image_sizes = [self.file_layout(arr[i], cfg).file_size for i in range(n)]
+        self.totals = _lib.NwFilesTotalsC()
+        check(_lib.lib().vga_nw_files_totals_of(self._h, C.byref(self.totals)))
+        nf, nch = self.totals.files, self.totals.channels
+        fc, so, io = np.zeros(max(nf, 1), np.int32), np.zeros(max(nch, 1), np.int64), np.zeros(max(nf, 1), np.int64)
+        i64p = C.POINTER(C.c_int64)
+        check(_lib.lib().vga_nw_files_offsets(self._h, fc.ctypes.data_as(C.POINTER(C.c_int)), so.ctypes.data_as(i64p), io.ctypes.data_as(i64p)))
+        self.first_channel, self.seek_offsets, self.image_offsets = fc[:nf], so[:nch], io[:nf]
+        self.files, self.channels = nf, nch
+        self.ragged = C.c_void_p(_lib.lib().vga_nw_files_ragged(self._h))        # borrowed: lives as long as this object
+
+    @staticmethod
+    def _files_array(files):
+        files = [f if isinstance(f, _lib.NwFileC) else _nw_file(*f) for f in (files or [])]
+        return (_lib.NwFileC * max(len(files), 1))(*files), len(files)
+
+    @staticmethod
+    def file_layout(f, cfg):
+        """vga_nwstm_layout_for of one file of a set: the configuration plus the file's numbers"""
+        p = _lib.NwParamsC()
+        p.target, p.sample_rate, p.sample_count = cfg.target, f.sample_rate, f.sample_count
+        p.looping, p.loop_start, p.loop_end = f.looping, f.loop_start, f.loop_end
+        p.samples_per_interleave, p.samples_per_seek_table_entry = cfg.samples_per_interleave, cfg.samples_per_seek_table_entry
+        p.loop_point_alignment, p.track_type, p.seek_table_type = cfg.loop_point_alignment, cfg.track_type, cfg.seek_table_type
+        p.version, p.endianness = cfg.version, cfg.endianness
+        L = _lib.NwLayoutC()
+        check(_lib.lib().vga_nwstm_layout_for(C.byref(p), f.channels, C.byref(L)))
+        return L
+
+    @classmethod
+    def layout(cls, files, target=NwTarget.Revolution, configuration=None):
+        """(first_channel int32[files], seek_offsets int64[channels], image_offsets int64[files], NwFilesTotalsC): host only,
+        needs no GPU"""
+        arr, n = cls._files_array(files)
+        cfg = _file_config(target, configuration)
+        nch = sum(arr[i].channels for i in range(n) if arr[i].channels > 0)
+        fc, so, io = np.zeros(max(n, 1), np.int32), np.zeros(max(nch, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        tot, i64p = _lib.NwFilesTotalsC(), C.POINTER(C.c_int64)
+        check(_lib.lib().vga_nw_files_layout_for(arr, n, C.byref(cfg), fc.ctypes.data_as(C.POINTER(C.c_int)), so.ctypes.data_as(i64p),
+                                                 io.ctypes.data_as(i64p), C.byref(tot)))
+        return fc[:n], so[:tot.channels], io[:n], tot
+
+    @classmethod
+    def from_infos(cls, infos, image_offsets=None):
+        """A set for reading, from the vga_nwstm_info of every file (parse()); image_offsets: multiples of 8, or None for images
+        packed as write() packs them"""
+        infos = list(infos)
+        n = len(infos)
+        ptrs = (C.c_void_p * max(n, 1))(*[C.addressof(i) for i in infos])
+        offs = np.ascontiguousarray(image_offsets, dtype=np.int64) if image_offsets is not None else None
+        h = C.c_void_p()
+        check(_lib.lib().vga_nw_files_create_from_infos(ptrs, n, offs.ctypes.data_as(C.POINTER(C.c_int64)) if offs is not None else None,
+                                                        C.byref(h)))
+        s = cls(_handle=h)
+        s.image_sizes = [i.audio_data_offset + i.audio_data_length for i in infos]
+        return s
+
+    def close(self):
+        if self._h:
+            _lib.lib().vga_nw_files_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def gc_files(self):
+        """the _lib.GcFileC of every file (channel = vga_nwstm_layout_for(...).channel): what gcadpcm.AlignedFileSet takes"""
+        arr = (_lib.GcFileC * max(self.files, 1))()
+        check(_lib.lib().vga_nw_files_gc_files(self._h, arr))
+        return list(arr[:self.files])
+
+    def write(self, adpcm, coefs, images, gain=None, start_context=None, loop_context=None, seek=None, stream=None):
+        """vga_nwstm_write_device_v.  adpcm: uint8[totals.adpcm_bytes] (the aligned rows), coefs: int16[channels*16], seek:
+        int16[totals.seek_shorts]; images: uint8[totals.image_bytes]"""
+        import torch
+        from .dsp import DspFileSet
+        ptr, t, n = DspFileSet._ptr, self.totals, self.channels
+        check(_lib.lib().vga_nwstm_write_device_v(
+            self._h, ptr(adpcm, torch.uint8, t.adpcm_bytes, "adpcm"), ptr(coefs, torch.int16, n * 16, "coefs"),
+            ptr(gain, torch.int16, n, "gain"), ptr(start_context, torch.int16, n * 3, "start_context"),
+            ptr(loop_context, torch.int16, n * 3, "loop_context"), ptr(seek, torch.int16, t.seek_shorts, "seek"),
+            ptr(images, torch.uint8, t.image_bytes, "images"), DspFileSet._stream(stream)))
+
+    def read(self, images, adpcm, coefs=None, gain=None, start_context=None, loop_context=None, stream=None):
+        """vga_nwstm_read_device_v (a set from from_infos): images -> the rows of adpcm and the parsed per-channel arrays"""
+        import torch
+        from .dsp import DspFileSet
+        ptr, t, n = DspFileSet._ptr, self.totals, self.channels
+        check(_lib.lib().vga_nwstm_read_device_v(
+            self._h, ptr(images, torch.uint8, t.image_bytes, "images"), ptr(adpcm, torch.uint8, t.adpcm_bytes, "adpcm"),
+            ptr(coefs, torch.int16, n * 16, "coefs"), ptr(gain, torch.int16, n, "gain"),
+            ptr(start_context, torch.int16, n * 3, "start_context"), ptr(loop_context, torch.int16, n * 3, "loop_context"),
+            DspFileSet._stream(stream)))
+
+    def images(self, host_buffer):
+        """one `bytes` per file from the packed images (a device tensor or a numpy array); synchronises"""
+        host = host_buffer.cpu().numpy() if hasattr(host_buffer, "cpu") else np.asarray(host_buffer, dtype=np.uint8)
+        return [host[int(at):int(at) + int(size)].tobytes() for at, size in zip(self.image_offsets, self.image_sizes)]
+
+
+def write_files(pcm16_list, target, configuration=None):
+    """BrstmWriter / BCFstmWriter(target)(configuration).GetFile(GcAdpcmFormat().EncodeFromPcm16(file)) for a list of Pcm16Format
+    files -- with NwTarget.Revolution the whole of VGAudio.Cli/Batch.cs -- on the device and without a launch per file: one
+    upload, vga_gcadpcm_coefs_device_v, vga_gcadpcm_encode_device_v, the alignment re-encode of gcadpcm.AlignedFileSet,
+    vga_nwstm_write_device_v, one download.  Returns one `bytes` per file."""
+    import torch
+    from .gcadpcm import AlignedFileSet
+    files = list(pcm16_list)
+    L = _lib.lib()
+    s = NwFileSet([(f.ChannelCount, f.SampleRate, f.SampleCount, f.Looping, f.LoopStart if f.Looping else 0,
+                    f.LoopEnd if f.Looping else 0) for f in files], target, configuration)
+    a = None
+    try:
+        if s.files == 0:
+            return []
+        a = AlignedFileSet(s.gc_files())
+        t, nch = a.totals, a.channels
+        if t.out_adpcm_bytes != s.totals.adpcm_bytes or list(a.seek_offsets) != list(s.seek_offsets):
+            raise _lib.VgaError("internal: the aligned set's output is not the file set's input")
+        pin, _ = a.offsets("in")
+        host, c = np.zeros(t.pcm_samples, dtype=np.int16), 0
+        for f in files:
+            for ch in f.Channels:
+                host[pin[c]:pin[c] + f.SampleCount] = np.asarray(ch, dtype=np.int16)[:f.SampleCount]
+                c += 1
+        new = lambda n, dtype: torch.zeros(max(int(n), 16), dtype=dtype, device="cuda")
+        pcm = torch.from_numpy(host).cuda()
+        coefs, adpcm, out = new(nch * 16, torch.int16), new(t.adpcm_bytes, torch.uint8), new(t.out_adpcm_bytes, torch.uint8)
+        seek, ctx = new(t.seek_shorts, torch.int16), new(nch * 3, torch.int16)
+        images = torch.empty(s.totals.image_bytes, dtype=torch.uint8, device="cuda")
+        ws = torch.empty(max(L.vga_gcadpcm_ragged_coefs_workspace_bytes(a.ragged_in), t.workspace_bytes, 16), dtype=torch.uint8, device="cuda")
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(L.vga_gcadpcm_coefs_device_v(a.ragged_in, pcm.data_ptr(), coefs.data_ptr(), ws.data_ptr(), ws.numel(), st))
+        check(L.vga_gcadpcm_encode_device_v(a.ragged_in, pcm.data_ptr(), coefs.data_ptr(), None, None, adpcm.data_ptr(), st))
+        a.align_channels(adpcm, coefs, out, seek=seek, loop_context=ctx, workspace=ws)
+        s.write(out, coefs, images, loop_context=ctx, seek=seek)
+        return s.images(images)
+    finally:
+        if a is not None:
+            a.close()
+        s.close()
