@@ -2,8 +2,9 @@
 """Per-frame instruction budget of gc_encode_persistent_kernel<8, false> from hipcc's ISA listing: where do
 the ~409 lane-operations per input sample go against the ~240 the two passes x 8 predictors need?
 
-The frame loop's basic blocks are found from the listing itself: the seven `v_dot2_i32_i16 v, E, E, acc clamp` of a quantise pass
-(gc_encode_core.hpp E3: total += e0 * e0 + e1 * e1, once per two sample steps since round 8) mark the passes; the blocks between the loop's labels are classified by what they hold.
+The frame loop's basic blocks are found from the listing itself: a pair of quantise passes is the one block of the frame that
+holds two passes' `v_cvt_pk_i16_i32` (clamp and history shift, one per sample step), with or without `v_cvt_f32_i32`; the
+blocks between the loop's labels are classified by what they hold.
 Prints static instruction counts per block of the HOT path of one frame (lane = (channel, predictor), CPW = 8: one wave-frame
 = 8 channel-frames = 112 samples), the cold block's path for a plain third trip, the helper wave's loop per tile, and the
 resulting lane-operations per sample with the measured rates (cold-block rate, short-pass share) filled in.
@@ -15,7 +16,6 @@ the frame's first row -- 87 VALU where this version says 53 for the same source;
 """
 import collections
 import os
-import re
 import subprocess
 import sys
 import tempfile
@@ -71,40 +71,39 @@ def count(block):
 
 def main():
     L = kernel(listing(), "gc_encode_persistent_kernelILi8ELb0E")
-    sq = [i for i, l in enumerate(L) if re.search(r"v_dot2_i32_i16 v\d+, (v\d+), \1, (?:v\d+|0) clamp", l)]
-    # first frame of the loop body (row set A): short pair of passes (2 x 14 sample steps), then the normal pair.  The passes'
-    # extent is taken from the fourteen v_cvt_pk_i16_i32 of each -- clamp and history shift, on the chain.
-    if any(l.startswith("v_addc_co_u32") for l in L):
-        # round 10: the frame's passes are the first code with an add with carry (the seam code inside the kernel keeps the
-        # old pass); the hot passes form no squares any more -- one error block of seven stands in the frame's tail
-        first = next(i for i, l in enumerate(L) if l.startswith("v_addc_co_u32"))
-        cv = [i for i, l in enumerate(L) if l.startswith("v_cvt_pk_i16_i32") and i > first - 40]
-        assert len(cv) >= 56, "the listing does not look like the encoder's"
-        inside = lambda a, b: [i for i in sq if a <= i <= b + 60]
-        short_a, short_b = cv[0], max([cv[27]] + (inside(cv[0], cv[27]) if len(inside(cv[0], cv[55])) >= 28 else []))
-        normal_a, normal_b = cv[28], max([cv[55]] + (inside(cv[28], cv[55]) if len(inside(cv[0], cv[55])) >= 28 else []))
-    else:
-        assert len(sq) >= 28, "the listing does not look like the encoder's"
-        # (hipcc sinks the short pair's squares behind the passes, into a block of their own: stretched over the squares)
-        cv = [i for i, l in enumerate(L) if l.startswith("v_cvt_pk_i16_i32") and i > sq[0] - 700]
-        assert len(cv) >= 56, "the listing does not look like the encoder's"
-        short_a, short_b = min(cv[0], sq[0]), max(cv[27], sq[13])
-        normal_a, normal_b = min(cv[28], sq[14]), max(cv[55], sq[27])
+    cv = [i for i, l in enumerate(L) if l.startswith("v_cvt_pk_i16_i32")]
     labels = [i for i, l in enumerate(L) if l.endswith(":")]
     prev_label = lambda i: max(j for j in labels if j <= i)
     next_label = lambda i: min(j for j in labels if j > i)
-    # the frame's first label: the nearest one in front of the passes whose block opens with the row reads of the NEXT frame
-    # (six ds_read_b128) -- the small blocks between it and the passes are the pre-scan head, the first scale and the
-    # rare sequential pre-scan
-    frame_start = max(j for j in labels if j < short_a and sum(l.startswith("ds_read_b128") for l in L[j:j + 20]) >= 6)
-    short_blk = (prev_label(short_a), next_label(short_b))
-    normal_blk = (prev_label(normal_a), next_label(normal_b))
+    # the frame's passes are the first code with an add with carry (round 10; the seam code inside the kernel keeps the old
+    # pass).  The frame's first label: the nearest one in front of them whose block opens with the row reads of the NEXT
+    # frame (six ds_read_b128); the frame's copy ends where the next block of that kind begins (the loop body holds two).
+    first = next(i for i, l in enumerate(L) if l.startswith("v_addc_co_u32"))
+    opens_frame = lambda j: sum(l.startswith("ds_read_b128") for l in L[j:j + 20]) >= 6
+    frame_start = max(j for j in labels if j < first and opens_frame(j))
+    frame_end = min(j for j in labels if j > first and opens_frame(j))
+    # A pair of passes is the one basic block of the frame with two passes' clamp-and-shift instructions (v_cvt_pk_i16_i32: 28,
+    # or a few less where the overflow-only pass drops its last; the cold block's passes come one to a block, 14): the pair with the f32 detour holds v_cvt_f32_i32, the short pair does not.  Found by
+    # what the blocks hold, not by where they stand: since round 11 hipcc puts the short pair out of line behind the cold block.
+    pairs = [(a, next_label(a)) for a in labels if frame_start <= a < frame_end
+             and sum(l.startswith("v_cvt_pk_i16_i32") for l in L[a:next_label(a)]) >= 20]
+    assert len(pairs) >= 2, "the listing does not look like the encoder's"
+    has_cvt = lambda blk: any(l.startswith("v_cvt_f32_i32") for l in L[blk[0]:blk[1]])
+    normal_blk = next(blk for blk in pairs if has_cvt(blk))
+    short_blk = next(blk for blk in pairs if not has_cvt(blk))
+    # the short pair's row runs on through the test of what the pair vouches for, to where it rejoins: the other pair's label
+    # or the block's own s_branch
+    end = short_blk[1]
+    while end != normal_blk[0] and not L[end - 1].startswith("s_branch"):
+        end = next_label(end)
+    short_blk = (short_blk[0], end)
+    # the tail ends with the jump to the next frame: an s_branch, or the conditional branch to the next frame's first label
     tail_end = normal_blk[1]
-    while not L[tail_end].startswith("s_branch"):
+    while not (L[tail_end].startswith("s_branch") or (L[tail_end].startswith("s_cbranch") and L[tail_end].split()[1] + ":" == L[frame_end])):
         tail_end += 1
     # (what an execz branch jumps over -- the rare +M / -M tie's sequential pre-scan -- is not on the hot path)
     pre, skip_to = [], None
-    for t in L[frame_start:short_blk[0]]:
+    for t in L[frame_start:min(short_blk[0], normal_blk[0])]:
         if skip_to:
             if t == skip_to + ":":
                 skip_to = None
@@ -113,10 +112,10 @@ def main():
         if t.startswith("s_cbranch_execz"):
             skip_to = t.split()[1]
     rows = [("row reads (6 x ds_read_b128) + pre-scan of the two history-dependent distances + first scale", count(pre)),
-            ("passes B (s1 + 1) and A (s1) without the f32 detour, 28 sample steps", count(L[short_blk[0]:short_blk[1]])),
+            ("the frame's two passes without the f32 detour, 28 sample steps, and the test of what they vouch for", count(L[short_blk[0]:short_blk[1]])),
             ("the same with the conversions (30 % of the wave-frames take these instead)", count(L[normal_blk[0]:normal_blk[1]])),
-            ("select the pass the reference ends on, 8-predictor argmin (DPP), winner's history, 4 x ds_write_b128", count(L[normal_blk[1]:tail_end + 1]))]
-    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 10)\n")
+            ("the flags, the error block, 8-predictor argmin (DPP), winner's history, 4 x ds_write_b128", count(L[normal_blk[1]:tail_end + 1]))]
+    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 11)\n")
     print("`gc_encode_persistent_kernel<8, false>`, static counts from hipcc's gfx950 listing of `vgaudio_amd/csrc/gc_encode_kernel.hip`")
     print("(`tools/isa_budget_gc.py`).  One wave-frame = 64 lanes = 8 channels x 8 predictors = 112 input samples.\n")
     print("| block of the hot frame | total | VALU | SALU | LDS | wait / nop |")
@@ -145,22 +144,24 @@ def main():
 
 
 TEXT = """
-## What the budget says (round 10)
+## What the budget says (round 11)
 
-* Round 9's table is `profiles/r09_gc_encode_isa_budget.md` (same tool, parent of this round): row block 41, passes 328 / 361,
-  tail 43, cold block 81, encoder wave 503 VALU per wave-frame.
-* Passes 328 -> 277 / 361 -> 307.  Step 1 (gc_encode_core.hpp B1-B5): the sample step is `v_dot2`, `v_sub_co`, `v_addc_co`,
-  shift, `v_med3`, `P >> 11`, `v_lshl_add`, `v_cvt_pk` -- 8 where it was 9 (`v_sub`, `v_lshrrev`, `v_add3`), -23 / -26 per pair
-  of passes (step 0 keeps a `v_cndmask` of the borrow the two passes share).  hipcc puts `s_nop 1` between the carry pair
-  (a VALU write of an SGPR read by the next VALU): 66 / 51 wait / nop lines against 27 / 28.  Step 2: the passes form no
-  squares (-28: 2 x 7 `v_pk_sub_i16` + `v_dot2`).
-* Tail 43 -> 62: seven selects of the history pairs (the seventh is the winner's history: one select it had already) and one
-  error block of 7 + 7.  Steps 1 + 2 together: -51 in the passes, +19 in the tail.
-* Row block 41 -> 50: per pass one shift for -Z and two adds for the clamp bounds (6), the borrow of the shared step 0.  The
-  tool counts the block in front of the conversions pair (10 VALU: its copy of the pass constants) into this row although
-  the short path jumps over it, so a frame of the short kind executes about 5 fewer than the table says.
-* Cold block 81 -> 77: the third pass 190 -> 178.
+* The parent's table, made with this version of the tool, is round 10's (`profiles/r10_gc_encode_isa_budget.md`): row block 50,
+  passes 277 / 307, tail 62, cold block 77, encoder wave 475 VALU per wave-frame; tail 34 SALU.
+* Tail 62 -> 40: the 21 selects between two result sets (14 nibbles, 7 history pairs) and the select of the overflow are gone --
+  the final pass's registers ARE the frame's result (gc_encode_core.hpp T1, T2).  SALU 34 -> 38: the flags as before.
+* Row block 50 -> 34: one pass's constants (shift, bias, -Z, two clamp bounds) are formed in front of the pair instead of two.
+* Passes 277 -> 276 / 307 -> 321: the second pass builds its constants from sp2 behind the first (select of the scale, shift for
+  -Z, two adds, the bias), the overflow-only pass drops its last clamp-and-shift and every register copy of its nibbles.
+* Encoder wave 475 -> 440: **-35 VALU per wave-frame** (-39 on a short frame, -24 on one with the conversions).  As in round 10
+  the tool counts the block in front of the conversions pair into the row block although the short path jumps over it
+  (parent: 20 VALU there, now 4), so a short frame saves about 8 fewer than the table says.
+* hipcc now places the short pair out of line (behind the cold block, a branch there and one back); the tool finds the pairs
+  by what their blocks hold.
+* Step 2 of the round (the flags as compares and lane-mask logic, one bit for the branch; measured, not kept -- LABNOTES 16.3):
+  tail 40 -> 36 VALU and 38 -> 12 SALU, both exec-mask diamonds gone.
 """
+
 
 
 

@@ -617,7 +617,9 @@ VGA_HD uint32_t error_sum_pairs(const uint32_t (&xw)[7], const uint32_t (&pairs)
     }
     return (uint32_t)total;
 }
-template <bool NO_ROUND, bool HAVE_P0 = false, bool WITH_SUM = true>
+// OV_ONLY (round 11): the pass for its overflow alone -- neither the nibbles nor the history pairs become outputs (q2, pairs,
+// total are left unset); see final_pass_pair.
+template <bool NO_ROUND, bool HAVE_P0 = false, bool WITH_SUM = true, bool OV_ONLY = false>
 VGA_HD PassOutB pass_fast_core_b(const uint32_t (&xw)[7], uint32_t hist, const int (&in_b)[14], int c0, int c1, int scale_power,
                                  int P0_b = 0)
 {
@@ -651,11 +653,11 @@ VGA_HD PassOutB pass_fast_core_b(const uint32_t (&xw)[7], uint32_t hist, const i
             umin = imin(imin(umin, u_prev), u2);
         }
         u_prev = u2;
-        r.q2[s] = q2;
+        if (!OV_ONLY) r.q2[s] = q2;
         const int w = (P >> 11) + (int)((uint32_t)q2 << km11);      // (B5)
         h = sat_pack16(w_prev, w);
         w_prev = w;
-        if (s & 1) {
+        if ((s & 1) && !OV_ONLY) {
             if (WITH_SUM) {
                 const uint32_t epk = pk_sub_sat_i16(xw[s >> 1], h);
                 total = dot2_i16(epk, epk, total);
@@ -669,6 +671,48 @@ VGA_HD PassOutB pass_fast_core_b(const uint32_t (&xw)[7], uint32_t hist, const i
     r.total = (uint64_t)(uint32_t)total;
     r.max_overflow = ov;
     return r;
+}
+// ---- one lane, both trips: the pass at s1 for its overflow, then ONE final pass (round 11) -------------------------------
+// A lane of the (channel, predictor) layout ran the pass at sp_b = s1 + 1 and the pass at sp_a = s1, kept the nibbles and the
+// history pairs of both and picked one set with 21 selects.  Nothing needs both sets: the overflow of the pass at s1 alone
+// says whether the reference's loop stops there (pass_a_is_final).  So the first pass runs for its overflow only (OV_ONLY) and
+// the second at the lane's own scale sp2 = fin_a ? sp_a : sp_b:
+//  (T1) fin_a: the second pass IS the pass at sp_a again -- same row, history, coefficients and scale, hence the same nibbles,
+//       pairs and overflow (ov_2 == ov_a).
+//  (T2) otherwise it is the pass at sp_b, ov_2 == ov_b.
+// Either way its q2, pairs and hist_pair are what the selects delivered.  Every flag below reads ov_b only for a lane that is
+// not fin_a (frame_flags: bump_b and resume carry !fin_a, inexact reads the side fin_a names), so ov_2 stands in for ov_b.
+// A NO_ROUND pair vouches for itself when the pass at sp_a and the pass at sp2 both do (pass_no_round_is_exact): an exact
+// first pass has the true ov_a, hence the true fin_a and sp2.
+VGA_HD bool pass_a_is_final(int sp_a, int ov_a) { return sp_a >= 12 || ov_a <= 1; }
+template <bool NO_ROUND>
+VGA_HD PassOutB final_pass_pair(const uint32_t (&xw)[7], uint32_t hist, const int (&in_b)[14], int c0, int c1, int sp_a, int sp_b,
+                                int P0_b, int &ov_a, int &sp2)
+{
+    ov_a = pass_fast_core_b<NO_ROUND, true, false, true>(xw, hist, in_b, c0, c1, sp_a, P0_b).max_overflow;
+    sp2 = pass_a_is_final(sp_a, ov_a) ? sp_a : sp_b;
+    return pass_fast_core_b<NO_ROUND, true, false>(xw, hist, in_b, c0, c1, sp2, P0_b);
+}
+// What can stand between the two passes and the frame's result, per lane (round 5; sp_a = min(s1, 12), sp_b = min(s1 + 1, 12)):
+//   * bump_a / bump_b: the pass the loop has reached overflowed by more than 248, the bump loop (:166-168) moves the scale by
+//     more than one step -- the reference's loop as written, from the scale it moves to;
+//   * hostile coefficients (!coef_ok): the whole loop as written;      (generic = any of these)
+//   * inexact: the final pass ran at the cap and overflowed by more than 3: its lane's sum goes by the exact-sum rule (E4);
+//   * resume: both passes overflowed, on to s1 + 2.
+// A pass at the cap ends the loop whatever it overflowed.  ov_b may be ov_2 of final_pass_pair (T1, T2).
+struct FrameFlags { bool fin_a, bump_a, bump_b, generic, inexact, resume; };
+VGA_HD FrameFlags frame_flags(int sp_a, int sp_b, int ov_a, int ov_b, bool coef_ok)
+{
+    FrameFlags f;
+    const bool cap_a = sp_a >= 12, cap_b = sp_b >= 12;
+    const int eff_a = cap_a ? 0 : ov_a, eff_b = cap_b ? 0 : ov_b;
+    f.fin_a = eff_a < 2;
+    f.bump_a = !cap_a && (unsigned)ov_a > 248u;
+    f.bump_b = !f.fin_a && !cap_b && (unsigned)ov_b > 248u;
+    f.generic = !coef_ok || f.bump_a || f.bump_b;
+    f.inexact = !f.generic && (f.fin_a ? (cap_a && (unsigned)ov_a > 3u) : (cap_b && (unsigned)ov_b > 3u));
+    f.resume = !f.generic && !f.fin_a && eff_b >= 2;
+    return f;
 }
 // The 8 frame bytes (pack_frame) from nibbles known mod 16 only: q, q2 = q - Z, or the biased nibble all pack alike.
 VGA_HD void pack_frame_mod16(const int (&q)[14], int predictor, int scale_power, uint32_t &d0, uint32_t &d1)

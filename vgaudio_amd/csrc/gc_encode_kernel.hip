@@ -617,8 +617,8 @@ __device__ __forceinline__ void gc_encode_piece(
             commit(r, final_sp, winner32);
     };
 
-    // ---- CPW = 8: lane = (channel, predictor); candidate B (s1 + 1) and candidate A (s1) are two passes of the SAME lane,
-    // inlined back to back (two independent dependent chains: the wave has instructions to issue while one waits).
+    // ---- CPW = 8: lane = (channel, predictor); both trips of the reference's loop are passes of the SAME lane, one behind
+    // the other: the pass at s1 for its overflow, then the final pass at the scale that overflow names (round 11).
     auto encode_frame8 = [&](Row &R, int buf, int j, bool upd) {
         const uint32_t (&xw)[7] = R.xw;
         int s1, P0;
@@ -632,41 +632,32 @@ __device__ __forceinline__ void gc_encode_piece(
         // passes run without the detour through f32 -- (int)(float)d is d below 2^24, two conversions a sample less -- and each
         // lane checks from its overflow that no distance reached 2^24 (gc_encode_core.hpp: NO_ROUND); a lane that cannot
         // tell sends the wave through the passes as they always were.
-        PassOutB ra, rb;
+        // Round 11: the pass at s1 runs for its overflow alone; it tells the lane which scale the reference ends on (or that the
+        // lane goes to the cold block), and ONE final pass at that scale, sp2, delivers the nibbles, the history pairs and the
+        // overflow the flags read where they read pass B's (gc_encode_core.hpp T1, T2: final_pass_pair).
+        PassOutB r;
+        int ov_a, sp2;
 #ifdef VGA_GC_NO_FAST_PASSES                                        // (timing-only switch, tools/build_variants.sh)
         bool short_passes = false;
 #else
         bool short_passes = !__any(sp_b > 9);
 #endif
         if (short_passes) {
-            rb = pass_fast_core_b<true, true, false>(xw, hpk, R.mp, c0, c1, sp_b, P0);
-            ra = pass_fast_core_b<true, true, false>(xw, hpk, R.mp, c0, c1, sp_a, P0);
+            r = final_pass_pair<true>(xw, hpk, R.mp, c0, c1, sp_a, sp_b, P0, ov_a, sp2);
             // (hostile coefficients: the lane walks the reference's loop as written whatever these passes say)
-            const bool trusted = !coef_ok || (pass_no_round_is_exact(sp_a, ra.max_overflow) && pass_no_round_is_exact(sp_b, rb.max_overflow));
+            const bool trusted = !coef_ok || (pass_no_round_is_exact(sp_a, ov_a) && pass_no_round_is_exact(sp2, r.max_overflow));
             short_passes = !__any(!trusted);
         }
-        if (!short_passes) {
-            rb = pass_fast_core_b<false, true, false>(xw, hpk, R.mp, c0, c1, sp_b, P0);
-            ra = pass_fast_core_b<false, true, false>(xw, hpk, R.mp, c0, c1, sp_a, P0);
-        }
-        const bool cap_a = sp_a >= 12, cap_b = sp_b >= 12;         // a pass at the cap ends the loop whatever it overflowed
-        const int eff_a = cap_a ? 0 : ra.max_overflow, eff_b = cap_b ? 0 : rb.max_overflow;
-        const bool fin_a = eff_a < 2;                              // the reference stops after the pass at s1
-        // Which of the two passes the reference ends on, and what can stand in the way (each lane for itself; round 5 --
-        // until then any of these in any lane redid the whole wave's frame from scratch):
-        //   * bump_a / bump_b: the pass the loop has reached overflowed by more than 248, the bump loop (:166-168) moves the
-        //     scale by more than one step -- the reference's loop as written, from the scale it moves to;
-        //   * hostile coefficients (they can wrap int32): the whole loop as written;
-        //   * inexact: the final pass ran at the cap and overflowed by more than 3 -- its 32-bit error sum may have wrapped
-        //     (gc_encode_core.hpp S3); the pass again with a 64-bit sum.  (B's overflow is nobody's business when A is final.)
-        const bool bump_a = !cap_a && (unsigned)ra.max_overflow > 248u;
-        const bool bump_b = !fin_a && !cap_b && (unsigned)rb.max_overflow > 248u;
-        const bool generic = !coef_ok || bump_a || bump_b;
-        const bool inexact = !generic && (fin_a ? (cap_a && (unsigned)ra.max_overflow > 3u) : (cap_b && (unsigned)rb.max_overflow > 3u));
+        if (!short_passes) r = final_pass_pair<false>(xw, hpk, R.mp, c0, c1, sp_a, sp_b, P0, ov_a, sp2);
+        const int ov_2 = r.max_overflow;
+        // Which of the two passes the reference ends on, and what can stand in the way (each lane for itself, round 5):
+        // gc_encode_core.hpp frame_flags.
+        const FrameFlags ff = frame_flags(sp_a, sp_b, ov_a, ov_2, coef_ok);
+        const bool bump_a = ff.bump_a, generic = ff.generic, inexact = ff.inexact;
 #ifdef VGA_GC_ABLATE_THIRD_TRIPS                                     // timing only (tools/build_variants.sh): what the cold block costs
         const bool resume = false;
 #else
-        const bool resume = !generic && !fin_a && eff_b >= 2;      // both overflowed: on to s1 + 2 in the cold block
+        const bool resume = ff.resume;                             // both overflowed: on to s1 + 2 in the cold block
 #endif
         // (Round 6, measured and taken out again: the winning lanes storing the right pass's nibbles under their own masks
         // instead of fourteen selects in every lane -- 18 VALU instructions a frame less, two more exec-masked branches on
@@ -674,18 +665,10 @@ __device__ __forceinline__ void gc_encode_piece(
         // Round 10, the same end without a branch, measured and taken out as well: every lane issuing the record writes of
         // BOTH passes, each to the record or to a dummy slot of the lane's own by two address selects -- 8 VALU instructions
         // a frame less, four LDS writes more: 118.3-118.7 ms against 117.8-118.5, profiles/r10_encode_ab.log.)
-        PassOutB r;
-#pragma unroll
-        for (int i = 0; i < 14; i++) r.q2[i] = fin_a ? ra.q2[i] : rb.q2[i];   // (each Z its own: only the value mod 16 is used)
-        // one error block behind the choice (round 10): the passes hand over their history pairs, the sum is formed once
-        uint32_t sel[7];
-#pragma unroll
-        for (int i = 0; i < 7; i++) sel[i] = fin_a ? ra.pairs[i] : rb.pairs[i];
-        r.total = error_sum_pairs(xw, sel);
-        r.hist_pair = sel[6];
-        r.max_overflow = fin_a ? ra.max_overflow : rb.max_overflow;
+        // one error block (round 10): the final pass hands over its history pairs, the sum is formed here
+        r.total = error_sum_pairs(xw, r.pairs);
         r.exact = true;
-        const int final_sp = fin_a ? sp_a : sp_b;
+        const int final_sp = sp2;
         // 32-bit keys: error sums from 2^28 on share one key (such a predictor loses to any below); only when a channel's BEST
         // is that large (`sat`, wave-uniform) do the 64-bit keys decide -- in the cold block
         constexpr unsigned SAT = (1u << 28) - 1;
@@ -745,11 +728,11 @@ __device__ __forceinline__ void gc_encode_piece(
             // where the reference's loop stands (the value of scalePower before its next ++): at its start for hostile
             // coefficients; behind the bumps of the pass that started them otherwise (encode_frame_cold works that out)
 #ifdef VGA_GC_R05_COLD                                                // (timing only: the cold block's entry as it was in round 5)
-            st.start = !coef_ok ? s1 - 1 : (bump_a ? apply_bumps(s1, ra.max_overflow) : apply_bumps(s1 + 1, rb.max_overflow));
+            st.start = !coef_ok ? s1 - 1 : (bump_a ? apply_bumps(s1, ov_a) : apply_bumps(s1 + 1, ov_2));
 #else
             st.start = !coef_ok ? s1 - 1 : -100;
 #endif
-            st.bump_a = bump_a; st.ov_a = ra.max_overflow; st.ov_b = rb.max_overflow;
+            st.bump_a = bump_a; st.ov_a = ov_a; st.ov_b = ov_2;      // (ov_2 is pass B's wherever the cold block reads it: not fin_a)
             const ColdOut o = encode_frame_cold(st, r, final_sp, (generic || resume) ? 0 : 1);
             bool sat2 = false;
             int winner = argmin32(o.r, o.fin != 0, sat2);
