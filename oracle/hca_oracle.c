@@ -571,6 +571,12 @@ int vgo_hca_encoder_init(const vgo_hca_params *c, vgo_hca_info *h, int *post_sam
 }
 
 /* ------------------------------------------------------------------ encoder: frame stages */
+/* path counters (oracle.h): filled by the stages below, read back with vgo_hca_encode_paths_get */
+static __thread vgo_hca_encode_paths g_paths;
+static __thread int g_frame_hit_255;
+
+void vgo_hca_encode_paths_get(vgo_hca_encode_paths *out) { *out = g_paths; }
+
 /* :691-709 */
 static int find_scale_factor(double value)
 {
@@ -612,6 +618,7 @@ static void encode_intensity_stereo(hca_frame *f)
                 energy_ratio = 1;
             }
             f->ch[c + 1].intensity[sf] = quantized;
+            g_paths.intensity[quantized]++;
             for (int b = f->hca.base_band_count; b < f->hca.total_band_count; b++) {
                 l[b] = (l[b] + r[b]) * energy_ratio;
                 r[b] = 0;
@@ -697,7 +704,8 @@ static void calculate_hfr_scale(hca_frame *f)
             if (average > 0.0) {
                 double inv = 1.0 / average, s2 = sqrt(2);
                 group_spectra[group] *= inv < s2 ? inv : s2;
-            }
+                if (inv < s2) g_paths.hfr_inverse++; else g_paths.hfr_sqrt2++;
+            } else g_paths.hfr_zero++;
             ch->hfr_scales[group] = find_scale_factor(group_spectra[group]);
         }
     }
@@ -778,6 +786,7 @@ static int binary_search_level(hca_frame *f, int available_bits, int low, int hi
         if (mid_value > available_bits) low = mid + 1;
         else if (mid_value <= available_bits) high = mid;
     }
+    if (low == max) g_frame_hit_255 = 1;
     return low == max && mid_value > available_bits ? -1 : low;
 }
 
@@ -791,7 +800,8 @@ static int binary_search_boundary(hca_frame *f, int available_bits, int noise_le
         if (available_bits < mid_value) high = mid - 1;
         else if (available_bits >= mid_value) low = mid;
     }
-    if (low == high) return low < max ? low : -1;
+    if (low == high) { g_paths.boundary_exit_equal++; return low < max ? low : -1; }
+    g_paths.boundary_exit_probe++;
     int hi_value = calculate_used_bits(f, noise_level, high);
     return hi_value > available_bits ? low : high;
 }
@@ -801,10 +811,13 @@ static int calculate_noise_level(hca_frame *f)
 {
     int highest_band = f->hca.base_band_count + f->hca.stereo_band_count - 1;
     int available_bits = f->hca.frame_size * 8;
+    uint64_t drops = 0;
+    g_frame_hit_255 = 0;
     int level = binary_search_level(f, available_bits, 0, 255);
     while (level < 0) {
         highest_band -= 2;
-        if (highest_band < 0) return -3;
+        if (highest_band < 0) break;
+        drops++;
         for (int c = 0; c < f->nch; c++) {
             f->ch[c].scale_factors[highest_band + 1] = 0;
             f->ch[c].scale_factors[highest_band + 2] = 0;
@@ -812,6 +825,12 @@ static int calculate_noise_level(hca_frame *f)
         calculate_frame_header_length(f);
         level = binary_search_level(f, available_bits, 0, 255);
     }
+    g_paths.band_drops += drops;
+    if (drops > g_paths.band_drops_frame_max) g_paths.band_drops_frame_max = drops;
+    g_paths.frames_with_band_drops += drops > 0;
+    g_paths.frames_with_repeated_band_drops += drops > 1;
+    g_paths.frames_level_search_hit_255 += g_frame_hit_255;
+    if (level < 0) { g_paths.error_minus3++; return -3; }
     f->acceptable_noise_level = level;
     return 0;
 }
@@ -819,10 +838,10 @@ static int calculate_noise_level(hca_frame *f)
 /* :487-500; -4 where the reference throws NotImplementedException */
 static int calculate_evaluation_boundary(hca_frame *f)
 {
-    if (f->acceptable_noise_level == 0) { f->evaluation_boundary = 0; return 0; }
+    if (f->acceptable_noise_level == 0) { g_paths.frames_level_zero++; f->evaluation_boundary = 0; return 0; }
     int available_bits = f->hca.frame_size * 8;
     int level = binary_search_boundary(f, available_bits, f->acceptable_noise_level, 0, 127);
-    if (level < 0) return -4;
+    if (level < 0) { g_paths.error_minus4++; return -4; }
     f->evaluation_boundary = level;
     return 0;
 }
@@ -862,6 +881,7 @@ static void write_scale_factors(bit_writer *w, const hca_channel *ch)
     int delta_bits = ch->sf_delta_bits;
     const int *scales = ch->scale_factors;
     bw_write(w, delta_bits, 3);
+    g_paths.sf_delta_bits[delta_bits]++;
     if (delta_bits == 0) return;
     if (delta_bits == 6) {
         for (int i = 0; i < ch->coded_sf_count; i++) bw_write(w, scales[i], 6);
@@ -931,6 +951,7 @@ static void pack_frame(hca_frame *f, uint8_t *out)
 /* CriHcaEncoder.EncodeFrame :271-286 (+ PcmToFloat :845-858, RunMdct :834-843) */
 static int encode_frame(hca_frame *f, int16_t *const *pcm, uint8_t *out)
 {
+    g_paths.frames++;
     for (int c = 0; c < f->nch; c++) {
         int idx = 0;
         for (int sf = 0; sf < SUBFRAMES; sf++)
@@ -1059,6 +1080,7 @@ int vgo_hca_encode(const int16_t *pcm, long pitch, const vgo_hca_params *c, vgo_
     pthread_once(&g_scale_once, init_scale);
     hca_encoder e;
     memset(&e, 0, sizeof e);
+    memset(&g_paths, 0, sizeof g_paths);
     int rc = vgo_hca_encoder_init(c, &e.hca, &e.post_samples, &e.buffer_pre_samples);
     if (rc) return rc;
     const int nch = e.hca.channel_count;

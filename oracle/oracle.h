@@ -200,6 +200,23 @@ int vgo_hca_encode_batch(const int16_t *pcm, long stream_pitch, long ch_pitch, i
                          uint8_t *frames, long frames_pitch, int threads);
 int vgo_hca_decode_batch(const vgo_hca_info *info, const uint8_t *frames, long frames_pitch, int nstreams,
                          int16_t *pcm_out, long stream_pitch, long ch_pitch, int threads);
+/* Which way the data-dependent decisions of CriHcaEncoder.EncodeFrame went during this thread's last vgo_hca_encode
+ * (zeroed at its start; counting changes no output byte).  Frames that end in an error are counted up to the error. */
+typedef struct {
+    uint64_t frames;                    /* EncodeFrame calls */
+    uint64_t sf_delta_bits[7];          /* channel headers written, by CriHcaChannel.ScaleFactorDeltaBits (6: raw) */
+    uint64_t intensity[14];             /* primary sub-frames by the intensity index stored (:741-755; 13: the bound) */
+    uint64_t hfr_zero, hfr_sqrt2, hfr_inverse;   /* HFR groups: average 0, scale sqrt(2), scale 1 / average (:824-827) */
+    uint64_t band_drops;                /* iterations of CalculateNoiseLevel's retry loop (:466-482) */
+    uint64_t band_drops_frame_max;      /* the most of them in one frame */
+    uint64_t frames_with_band_drops, frames_with_repeated_band_drops;
+    uint64_t frames_level_zero;         /* CalculateEvaluationBoundary returns early (:489-493) */
+    uint64_t boundary_exit_equal;       /* BinarySearchBoundary ends at low == high (:544-547) */
+    uint64_t boundary_exit_probe;       /* ... or at the final probe of `high` (:549-551) */
+    uint64_t frames_level_search_hit_255;   /* a BinarySearchLevel of the frame ended at low == 255 */
+    uint64_t error_minus3, error_minus4;    /* frames that ended in "Bitrate is set too low" / NotImplementedException */
+} vgo_hca_encode_paths;
+void vgo_hca_encode_paths_get(vgo_hca_encode_paths *out);
 /* test hooks */
 int vgo_hca_table(const char *name, double *out, int cap);
 uint16_t vgo_crc16(const uint8_t *data, int size);                       /* Utilities/Crc16.cs:12-18 */

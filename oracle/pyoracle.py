@@ -97,6 +97,15 @@ class HcaParams(C.Structure):
                                        "sample_count", "looping", "loop_start", "loop_end")]
 
 
+class HcaEncodePaths(C.Structure):
+    """vgo_hca_encode_paths"""
+    _fields_ = [("frames", C.c_uint64), ("sf_delta_bits", C.c_uint64 * 7), ("intensity", C.c_uint64 * 14)] + [
+        (n, C.c_uint64) for n in ("hfr_zero", "hfr_sqrt2", "hfr_inverse", "band_drops", "band_drops_frame_max",
+                                  "frames_with_band_drops", "frames_with_repeated_band_drops", "frames_level_zero",
+                                  "boundary_exit_equal", "boundary_exit_probe", "frames_level_search_hit_255",
+                                  "error_minus3", "error_minus4")]
+
+
 def _declare_hca(L):
     i16p, u8p, i, dp = C.POINTER(C.c_int16), C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_double)
     ip = C.POINTER(C.c_int)
@@ -113,6 +122,8 @@ def _declare_hca(L):
     L.vgo_mdct_run.argtypes = [dp, i, dp, i]
     L.vgo_mdct_run.restype = None
     L.vgo_hca_debug_last_frame.argtypes = [i16p, C.c_long, pp, i, ip, ip, ip, ip, ip, dp]
+    L.vgo_hca_encode_paths_get.argtypes = [C.POINTER(HcaEncodePaths)]
+    L.vgo_hca_encode_paths_get.restype = None
 
 
 def _i16(a):
@@ -723,6 +734,15 @@ def hca_encode(pcm2d, params):
     frames = np.zeros((info.frame_count, info.frame_size), dtype=np.uint8)
     rc = lib().vgo_hca_encode(_i16(pcm2d), pcm2d.shape[1], C.byref(params), C.byref(info), _u8(frames))
     return rc, info, frames
+
+
+def hca_encode_paths():
+    """which way the encoder's data-dependent decisions went in this thread's last hca_encode: a dict of ints, the
+    histograms (sf_delta_bits 0..6, intensity 0..13) as lists"""
+    p = HcaEncodePaths()
+    lib().vgo_hca_encode_paths_get(C.byref(p))
+    return {n: (list(getattr(p, n)) if n in ("sf_delta_bits", "intensity") else int(getattr(p, n)))
+            for n, _ in HcaEncodePaths._fields_}
 
 
 def hca_decode(info, frames):
