@@ -9,7 +9,13 @@ Prints static instruction counts per block of the HOT path of one frame (lane = 
 = 8 channel-frames = 112 samples), the cold block's path for a plain third trip, the helper wave's loop per tile, and the
 resulting lane-operations per sample with the measured rates (cold-block rate, short-pass share) filled in.
 
-    python tools/isa_budget_gc.py > profiles/rNN_gc_encode_isa_budget.md
+    python tools/isa_budget_gc.py [--src other/gc_encode_kernel.hip] [-DNAME=VALUE ...] > profiles/rNN_gc_encode_isa_budget.md
+
+Since round 12 the listing is made with the product's own options for the file (vgaudio_amd/build.py FILE_FLAGS; until then
+with the common ones only), and the tool also counts the scratch instructions (spill stores and reloads) per block of the
+frame, for the uniform and the ragged instantiation: the blocks of the frame loop are the ones hipcc's loop comments put under
+the first depth-3 loop header of the kernel, wherever they stand in the listing.  --src: the same for another copy of the
+kernel file (a parent's, say), compiled against this tree's headers.
 
 (Tables up to profiles/r08_gc_encode_isa_budget.md were made with an earlier frame-start rule that counted the tile head into
 the frame's first row -- 87 VALU where this version says 53 for the same source; they cannot be reproduced with this version.)
@@ -28,8 +34,13 @@ SHORT_SHARE = 0.70          # wave-frames whose two passes run without the f32 d
 
 
 def listing():
+    sys.path.insert(0, ROOT)
+    from vgaudio_amd.build import FILE_FLAGS                  # the product's per-file code generation options
+    src = os.path.abspath(sys.argv[sys.argv.index("--src") + 1]) if "--src" in sys.argv else SRC
     with tempfile.TemporaryDirectory() as tmp:
-        subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["--save-temps=obj", "-c", SRC, "-o", os.path.join(tmp, "k.o")], check=True, cwd=tmp,
+        subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + FILE_FLAGS.get("gc_encode_kernel.hip", []) + ["-I", os.path.dirname(SRC)] +
+                       [a for a in sys.argv[1:] if a.startswith("-D")] +
+                       ["--save-temps=obj", "-c", src, "-o", os.path.join(tmp, "k.o")], check=True, cwd=tmp,
                        stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         s = [f for f in os.listdir(tmp) if f.endswith(".s") and "gfx950" in f][0]
         return open(os.path.join(tmp, s)).read().split("\n")
@@ -44,6 +55,67 @@ def kernel(lines, name):
         if not t.strip() or t.strip().startswith((".p2align", ".", "//")) and not t.strip().endswith(":"):
             continue
         out.append(t.strip())
+    return out
+
+
+def scratch_by_block(raw, name):
+    """Scratch instructions of one kernel by where they stand: {region: count}, and the in-loop ones one by one.  The frame loop
+    is the kernel's first depth-3 loop (piece queue > tiles > frames); hipcc's comments name every block's innermost loop."""
+    import re
+    a = next(i for i, l in enumerate(raw) if l.startswith("_Z") and name in l and l.split(";")[0].rstrip().endswith(":"))
+    b = next(i for i in range(a, len(raw)) if "s_endpgm" in raw[i])
+    frame_hdr, tile_hdr, nested, tile_nested, where, lab = None, None, set(), set(), "prologue, seams, epilogue", None
+    regions, inside = collections.OrderedDict(), []
+    for key in ("frame loop: the frame's pairs of passes", "frame loop: the cold block's passes", "frame loop: row reads, first scale, flags, tail, the cold block's other code",
+                "tile head (once per tile, outside the frame loop)", "prologue, seams, epilogue"):
+        regions[key] = 0
+    i = a + 1
+    while i < b:
+        m = re.match(r"^(\.LBB\d+_\d+):", raw[i])
+        if m:
+            lab = m.group(1)[2:]
+            j, com = i + 1, raw[i]
+            while j < b and raw[j].lstrip().startswith(";"):
+                com += raw[j]
+                j += 1
+            if frame_hdr is None and "This Loop Header: Depth=2" in com:
+                tile_hdr = lab                                       # (the last depth-2 header in front of the frame loop)
+                tile_nested = {lab}
+            if frame_hdr is None and "This Loop Header: Depth=3" in com:
+                frame_hdr = lab
+            if frame_hdr and (lab == frame_hdr or re.search(r"Parent Loop %s\b" % frame_hdr, com)):
+                nested.add(lab)
+            inner = re.search(r"in Loop: Header=(BB\d+_\d+)", com)
+            in_frame = lab in nested or (inner is not None and inner.group(1) in nested)
+            in_tile = not in_frame and (lab in tile_nested or (inner is not None and inner.group(1) in tile_nested))
+            end = next((k for k in range(j, b) if re.match(r"^\.LBB\d+_\d+:", raw[k])), b)
+            cvt = sum(l.lstrip().startswith("v_cvt_pk_i16_i32") for l in raw[j:end])
+            if in_frame:
+                where = ("frame loop: the frame's pairs of passes" if cvt >= 20 else "frame loop: the cold block's passes" if cvt >= 13
+                         else "frame loop: row reads, first scale, flags, tail, the cold block's other code")
+            elif in_tile:
+                where = "tile head (once per tile, outside the frame loop)"
+            else:
+                where = "prologue, seams, epilogue"
+        elif raw[i].lstrip().startswith("scratch_"):
+            regions[where] += 1
+            if where.startswith("frame loop"):
+                inside.append("%s: %s" % (lab, raw[i].split(";")[0].strip()))
+        i += 1
+    return regions, inside, frame_hdr
+
+
+def resources(raw, name):
+    """VGPRs, spill slots and scratch bytes per lane from the kernel's .amdhsa / metadata comment block."""
+    import re
+    a = next(i for i, l in enumerate(raw) if l.startswith("_Z") and name in l and l.split(";")[0].rstrip().endswith(":"))
+    out = {}
+    for l in raw[a:]:
+        m = re.match(r"^; (NumVgprs|ScratchSize|Occupancy|LDSByteSize): (\d+)", l)
+        if m:
+            out[m.group(1)] = int(m.group(2))
+            if m.group(1) == "Occupancy":
+                break
     return out
 
 
@@ -70,7 +142,8 @@ def count(block):
 
 
 def main():
-    L = kernel(listing(), "gc_encode_persistent_kernelILi8ELb0E")
+    RAW = listing()
+    L = kernel(RAW, "gc_encode_persistent_kernelILi8ELb0E")
     cv = [i for i, l in enumerate(L) if l.startswith("v_cvt_pk_i16_i32")]
     labels = [i for i, l in enumerate(L) if l.endswith(":")]
     prev_label = lambda i: max(j for j in labels if j <= i)
@@ -115,7 +188,7 @@ def main():
             ("the frame's two passes without the f32 detour, 28 sample steps, and the test of what they vouch for", count(L[short_blk[0]:short_blk[1]])),
             ("the same with the conversions (30 % of the wave-frames take these instead)", count(L[normal_blk[0]:normal_blk[1]])),
             ("the flags, the error block, 8-predictor argmin (DPP), winner's history, 4 x ds_write_b128", count(L[normal_blk[1]:tail_end + 1]))]
-    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 11)\n")
+    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 12)\n")
     print("`gc_encode_persistent_kernel<8, false>`, static counts from hipcc's gfx950 listing of `vgaudio_amd/csrc/gc_encode_kernel.hip`")
     print("(`tools/isa_budget_gc.py`).  One wave-frame = 64 lanes = 8 channels x 8 predictors = 112 input samples.\n")
     print("| block of the hot frame | total | VALU | SALU | LDS | wait / nop |")
@@ -140,27 +213,46 @@ def main():
                     ("cold block, %.3f x (third pass + ~45)" % COLD_RATE, COLD_RATE * (third_pass["VALU"] + 45)),
                     ("encoder wave, sum", per_frame)):
         print("| %s | %.0f | %.0f |" % (name, v, v * 64 / 112))
-    print(TEXT)
+    # scratch (spill stores and reloads) by where it stands, uniform and ragged instantiation
+    print("\n## Registers and scratch instructions by block\n")
+    for nice, mangled in (("gc_encode_persistent_kernel<8, false>", "gc_encode_persistent_kernelILi8ELb0E"),
+                          ("gc_encode_persistent_kernel<8, true>", "gc_encode_persistent_kernelILi8ELb1E")):
+        regions, inside, hdr = scratch_by_block(RAW, mangled)
+        res = resources(RAW, mangled)
+        print("`%s`: %d VGPRs, %d waves per SIMD, %d B of scratch per lane, %d B of LDS per workgroup; frame loop header `.L%s`.\n"
+              % (nice, res.get("NumVgprs", -1), res.get("Occupancy", -1), res.get("ScratchSize", -1), res.get("LDSByteSize", -1), hdr))
+        print("| where | scratch instructions |")
+        print("|---|---:|")
+        for k, v in regions.items():
+            print("| %s | %d |" % (k, v))
+        print("| **frame loop, header to back edge, cold block included** | **%d** |\n" % len(inside))
+        for t in inside:
+            print("* in the frame loop: `%s`" % t)
+    if "--src" not in sys.argv and not any(a.startswith("-D") for a in sys.argv[1:]):
+        print(TEXT)
 
 
 TEXT = """
-## What the budget says (round 11)
+## What the budget says (round 12)
 
-* The parent's table, made with this version of the tool, is round 10's (`profiles/r10_gc_encode_isa_budget.md`): row block 50,
-  passes 277 / 307, tail 62, cold block 77, encoder wave 475 VALU per wave-frame; tail 34 SALU.
-* Tail 62 -> 40: the 21 selects between two result sets (14 nibbles, 7 history pairs) and the select of the overflow are gone --
-  the final pass's registers ARE the frame's result (gc_encode_core.hpp T1, T2).  SALU 34 -> 38: the flags as before.
-* Row block 50 -> 34: one pass's constants (shift, bias, -Z, two clamp bounds) are formed in front of the pair instead of two.
-* Passes 277 -> 276 / 307 -> 321: the second pass builds its constants from sp2 behind the first (select of the scale, shift for
-  -Z, two adds, the bias), the overflow-only pass drops its last clamp-and-shift and every register copy of its nibbles.
-* Encoder wave 475 -> 440: **-35 VALU per wave-frame** (-39 on a short frame, -24 on one with the conversions).  As in round 10
-  the tool counts the block in front of the conversions pair into the row block although the short path jumps over it
-  (parent: 20 VALU there, now 4), so a short frame saves about 8 fewer than the table says.
-* hipcc now places the short pair out of line (behind the cold block, a branch there and one back); the tool finds the pairs
-  by what their blocks hold.
-* Step 2 of the round (the flags as compares and lane-mask logic, one bit for the branch; measured, not kept -- LABNOTES 16.3):
-  tail 40 -> 36 VALU and 38 -> 12 SALU, both exec-mask diamonds gone.
+* The parent's table (`profiles/r11_gc_encode_isa_budget.md`, made with the common options only): row block 34, passes 276 / 321,
+  tail 40 VALU and 38 SALU, cold block 77, encoder wave 440 VALU per wave-frame.  With the product's per-file options, which
+  this version of the tool uses, the parent's rows and passes read the same; the rule that finds the end of the tail runs
+  past the parent's flag diamonds there (`--src` on the parent's file), so the parent's tail is quoted from round 11.
+* The flags as one bit (`frame_goes_cold`): the tail's two exec-mask diamonds are gone, the single flags are formed inside the
+  cold branch: tail 40 -> 37 VALU, 38 -> 12 SALU.
+* One LDS slot per (channel slot, frame) -- row, pre-scan words, record -- reached from ONE address register with immediate
+  offsets: the row block forms one address where it formed three (34 -> 33 VALU with the `v_mov` that keeps the pre-scan
+  word's index opaque per frame); the tile head derives the address from the hardware's lane number.
+* Prediction, written down before the GPU run: encoder wave 440 -> 436 VALU per wave-frame (437 in the four-waves build), SALU -26 in the tail; at three
+  waves per SIMD that is worth what round 11's step 2 measured (about 1 ms) plus whatever the row reads gain from landing in
+  disjoint banks.  Measured: LABNOTES 17.
+* The build at four waves per SIMD (`-DVGA_GC_PERSISTENT_WAVES_PER_EU=4,4`; table below the kept build's when given): 128 VGPRs,
+  no scratch instruction between the frame loop's header and its back edge in either instantiation, none in the tile head;
+  what is left stands in the piece prologue and the seam code.  Measured and not kept.
 """
+
+
 
 
 

@@ -714,6 +714,27 @@ VGA_HD FrameFlags frame_flags(int sp_a, int sp_b, int ov_a, int ov_b, bool coef_
     f.resume = !f.generic && !f.fin_a && eff_b >= 2;
     return f;
 }
+// "Does the lane go to the cold block", and fin_a, as four compares and lane-mask logic -- no select, no branch (round 12;
+// measured in round 11, LABNOTES 16.3).  thr = 1 below the cap, 3 at it: what a pass may overflow by and still end the loop
+// with a sum the 32-bit key can trust.  With a_bad = ov_a > thr(sp_a), b_bad = ov_2 > thr(sp_b):
+//   * cap_a: the pass at sp_a ends the loop; the lane is cold exactly when a_bad (inexact).
+//   * !cap_a, !a_bad: fin_a, hot.
+//   * !cap_a, a_bad: not fin_a, ov_2 is pass B's; cold when ov_a > 248 (bump_a) or b_bad -- below the cap that is resume or
+//     bump_b, at it inexact.
+// Hence cold = !coef_ok | (a_bad & (cap_a | ov_a > 248 | b_bad)), and cold == generic || resume || inexact of frame_flags
+// (tests/test_host_gc_flag_masks.py, by enumeration).  The frame code branches on the ballot of `cold` and asks frame_flags
+// for the single flags inside the cold branch only.
+VGA_HD int frame_flag_limit(int sp) { return sp >= 12 ? 3 : 1; }
+struct FrameCold { bool cold, fin_a; };
+VGA_HD FrameCold frame_goes_cold(int sp_a, int sp_b, int ov_a, int ov_2, bool coef_ok)
+{
+    const bool cap_a = sp_a >= 12;
+    const bool a_bad = ov_a > frame_flag_limit(sp_a), b_bad = ov_2 > frame_flag_limit(sp_b);
+    FrameCold f;
+    f.fin_a = cap_a | !a_bad;
+    f.cold = !coef_ok | (a_bad & (cap_a | (ov_a > 248) | b_bad));
+    return f;
+}
 // The 8 frame bytes (pack_frame) from nibbles known mod 16 only: q, q2 = q - Z, or the biased nibble all pack alike.
 VGA_HD void pack_frame_mod16(const int (&q)[14], int predictor, int scale_power, uint32_t &d0, uint32_t &d1)
 {

@@ -118,6 +118,11 @@ constexpr int ENC_THREADS = 64 * (SW + 1);
 #ifndef VGA_GC_HELPER_PRIO
 #define VGA_GC_HELPER_PRIO 0
 #endif
+// waves per SIMD gc_encode_persistent_kernel is compiled for (tools/build_variants.sh: 4,4 is the 128-VGPR build of round 12,
+// measured and not kept: see persistent_wgs_per_cu)
+#ifndef VGA_GC_PERSISTENT_WAVES_PER_EU
+#define VGA_GC_PERSISTENT_WAVES_PER_EU 3, 3
+#endif
 // Two lane layouts of the encoder wave (template parameter CPW = channels per encoder wave):
 //   CPW = 4: lane = (channel, predictor, scale candidate A/B) -- the candidates of the retry loop run side by side;
 //   CPW = 8: lane = (channel, predictor) -- candidate B (s1 + 1) and candidate A (s1) run one after the other in the
@@ -128,11 +133,20 @@ struct Lay {
     static constexpr int CS = CPW * SW;    // channel slots per workgroup
     static constexpr int TF = 64 / CS;     // frames per tile: one helper lane per (channel slot, frame)
 };
+// Round 12: everything a (channel slot, frame) owns in LDS -- the helper's row, its pre-scan words and the winner's record --
+// is ONE 192-byte slot, so that an encoder lane reaches all of it from one address register with immediate offsets (the
+// four arrays of before cost four address registers, which a 128-VGPR frame loop spilled).  A channel slot's frames are
+// padded by 16 bytes: the eight channel slots of an encoder wave then read their 16-byte pieces from disjoint LDS banks.
 template <int CS, int TF>
 struct GcTileT {
-    uint32_t xw[CS][TF][8];    // [channel slot][frame]: the frame as packed pairs (in[2i], in[2i + 1]), 7 used (round 8)
-    int in2048p[CS][TF][16];   // x * 2048 + 1024 + 2^30: the row of pass_fast_core_b (round 10, gc_encode_core.hpp B1)
-    uint32_t pre[CS][TF][8];   // per predictor: clamp16(max d) & 0xFFFF | clamp16(min d) << 16, over s = 2..13
+    struct Slot {
+        uint32_t xw[8];        // the frame as packed pairs (in[2i], in[2i + 1]), 7 used (round 8)
+        int in2048p[16];       // x * 2048 + 1024 + 2^30: the row of pass_fast_core_b (round 10, gc_encode_core.hpp B1)
+        uint32_t pre[8];       // per predictor: clamp16(max d) & 0xFFFF | clamp16(min d) << 16, over s = 2..13
+        int4 out[4];           // the winner's frame, unpacked: q[0..13], predictor, scale; the helper packs it when it flushes
+    };
+    struct Group { Slot f[TF]; uint32_t pad[4]; };
+    Group g[CS];               // [channel slot][frame]
 };
 typedef short short2v __attribute__((ext_vector_type(2)));
 struct XW7 { uint32_t v[7]; };
@@ -302,9 +316,12 @@ __device__ __forceinline__ void gc_encode_piece(
     };
     pcm += first_frame * 14;
     adpcm += first_frame * 8;
-    __shared__ GcTile s_tile[2];
-    // the winner's frame, unpacked: q[0..13], predictor, scale; the helper packs it (pack_frame) when it flushes
-    __shared__ int4 s_out[2][CS][TF][4];
+    using Slot = typename GcTile::Slot;
+    static_assert(TF % 2 == 0, "the frame loop takes a tile's frames in pairs");
+    // (`end`: what the row reads one frame past the last channel slot's last pair land in; see the frame loop)
+    struct Tiles { GcTile t[2]; Slot end; };
+    __shared__ Tiles s_tiles;
+    GcTile (&s_tile)[2] = s_tiles.t;
     __shared__ int s_ncold[SW];
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
@@ -355,11 +372,11 @@ __device__ __forceinline__ void gc_encode_piece(
 #pragma unroll
                 for (int i = 0; i < 7; i++) w[i] = (uint32_t)(in[2 * i] & 0xFFFF) | ((uint32_t)in[2 * i + 1] << 16);
             }
-            GcTile &T = s_tile[tile & 1];
-            uint4 *xr = reinterpret_cast<uint4 *>(&T.xw[grp][hfr][0]);   // the pairs as loaded (the ints: in2048p and the pre-scan)
+            Slot &T = s_tile[tile & 1].g[grp].f[hfr];
+            uint4 *xr = reinterpret_cast<uint4 *>(&T.xw[0]);   // the pairs as loaded (the ints: in2048p and the pre-scan)
             xr[0] = make_uint4(w[0], w[1], w[2], w[3]);
-            xr[1] = make_uint4(w[4], w[5], w[6], 0u);
-            int4 *qr = reinterpret_cast<int4 *>(&T.in2048p[grp][hfr][0]);
+            xr[1] = make_uint4(w[4], w[5], w[6], (!RAGGED || tile * TF + hfr < frames) ? 1u : 0u);   // (the spare dword: slot_has_frame)
+            int4 *qr = reinterpret_cast<int4 *>(&T.in2048p[0]);
             qr[0] = make_int4(pass_b_row(in[0]), pass_b_row(in[1]), pass_b_row(in[2]), pass_b_row(in[3]));
             qr[1] = make_int4(pass_b_row(in[4]), pass_b_row(in[5]), pass_b_row(in[6]), pass_b_row(in[7]));
             qr[2] = make_int4(pass_b_row(in[8]), pass_b_row(in[9]), pass_b_row(in[10]), pass_b_row(in[11]));
@@ -391,14 +408,14 @@ __device__ __forceinline__ void gc_encode_piece(
 #endif
                 pre[p] = (uint32_t)(clamp16i(dmax) & 0xFFFF) | ((uint32_t)clamp16i(dmin) << 16);
             }
-            uint4 *pr = reinterpret_cast<uint4 *>(&T.pre[grp][hfr][0]);
+            uint4 *pr = reinterpret_cast<uint4 *>(&T.pre[0]);
             pr[0] = make_uint4(pre[0], pre[1], pre[2], pre[3]);
             pr[1] = make_uint4(pre[4], pre[5], pre[6], pre[7]);
         };
         auto flush = [&](int tile) {
             const int fr = tile * TF + hfr;
             if (!live || fr >= frames) return;
-            const int4 *rec = &s_out[tile & 1][grp][hfr][0];
+            const int4 *rec = &s_tile[tile & 1].g[grp].f[hfr].out[0];
             const int4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
             const int q[14] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, r3.x, r3.y};
             uint2 v;
@@ -425,6 +442,7 @@ __device__ __forceinline__ void gc_encode_piece(
 
     // -------------------------------------------------------------------- serial (encoder) wave
     __builtin_amdgcn_s_setprio(VGA_GC_ENCODER_PRIO);   // its latency is the kernel's run time: win every issue arbitration
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);   // (wave-uniform: a scalar register, for the tile heads)
     int p = CPW == 4 ? l16 >> 1 : l16;
     const bool cand_b = CPW == 4 && (l16 & 1) != 0;
     const int c0 = coefs[ch * 16 + 2 * p];
@@ -444,21 +462,35 @@ __device__ __forceinline__ void gc_encode_piece(
     uint32_t hpk = pack16(h0, h1);                     // the history as the pass and the pre-scan take it: (h0, h1) in one register
 
     if (lane == 0) s_ncold[wave] = 0;                  // cold blocks this piece (diagnostics, g_vga_gc_stats)
-    struct Row { uint32_t xw[7]; int mp[14]; uint32_t pre; };
-    auto read_row = [&](const GcTile &T, int j, Row &R) {
-        const uint4 *xr = reinterpret_cast<const uint4 *>(&T.xw[grp][j][0]);
+    // (the pre-scan word is not part of the row: it is read at the head of its own frame, a dot product and the head distances
+    // ahead of its use, and not a frame ahead -- one register less across the passes of the frame before)
+    struct Row { uint32_t xw[7]; int mp[14]; };
+    auto read_row = [&](const Slot &T, Row &R) {
+        const uint4 *xr = reinterpret_cast<const uint4 *>(&T.xw[0]);
         const uint4 a0 = xr[0], a1 = xr[1];
         // keep the padding lanes "used": hipcc otherwise splits the 16-byte row reads into odd-sized ones
         asm volatile("" ::"v"(a1.w));
         uint32_t *xw = R.xw;
         xw[0] = a0.x; xw[1] = a0.y; xw[2] = a0.z; xw[3] = a0.w; xw[4] = a1.x; xw[5] = a1.y; xw[6] = a1.z;
-        const int4 *qr = reinterpret_cast<const int4 *>(&T.in2048p[grp][j][0]);
+        const int4 *qr = reinterpret_cast<const int4 *>(&T.in2048p[0]);
         const int4 e0 = qr[0], e1 = qr[1], e2 = qr[2], e3 = qr[3];
         asm volatile("" ::"v"(e3.z), "v"(e3.w));
         int *mp = R.mp;
         mp[0] = e0.x; mp[1] = e0.y; mp[2] = e0.z; mp[3] = e0.w; mp[4] = e1.x; mp[5] = e1.y; mp[6] = e1.z; mp[7] = e1.w;
         mp[8] = e2.x; mp[9] = e2.y; mp[10] = e2.z; mp[11] = e2.w; mp[12] = e3.x; mp[13] = e3.y;
-        R.pre = T.pre[grp][j][p];
+    };
+    // the lane's pre-scan word of the frame.  Its byte offset is made opaque per frame: hipcc otherwise forms slot + 4 p once
+    // for the two frames of a loop trip and keeps that second address alive across the first frame (spilled at 128 VGPRs).
+    auto read_pre = [&](const Slot &T) __attribute__((always_inline)) -> uint32_t {
+        int pp = p;
+        asm volatile("" : "+v"(pp));
+        return T.pre[pp];
+    };
+    // RAGGED: is this frame one of the slot's own (else the slot's history stays frozen)?  The helper says so in the row's spare
+    // dword, read where the frame's tail needs it: a per-lane frame count kept across the loop was one register too many.
+    auto slot_has_frame = [&](const Slot &T) __attribute__((always_inline)) -> bool {
+        if constexpr (RAGGED) return T.xw[7] != 0u;
+        else return true;
     };
     auto pack = [](const uint32_t (&xw)[7]) {
         XW7 xs;
@@ -495,9 +527,9 @@ __device__ __forceinline__ void gc_encode_piece(
     };
     // the first scale from the frame's range: the tie of +M and -M (gc_encode_core.hpp F4) needs pos == neg, looked at behind
     // one wave-uniform test
-    auto first_scale = [&](const Row &R, int d0, int d1) __attribute__((always_inline)) -> int {
-        const int dmax = imax(imax((int)(int16_t)(R.pre & 0xFFFF), d0), d1);
-        const int dmin = imin(imin((int)R.pre >> 16, d0), d1);
+    auto first_scale = [&](const Row &R, uint32_t pre, int d0, int d1) __attribute__((always_inline)) -> int {
+        const int dmax = imax(imax((int)(int16_t)(pre & 0xFFFF), d0), d1);
+        const int dmin = imin(imin((int)pre >> 16, d0), d1);
         int sum, pos;
         int s1 = first_scale_power_nt(dmax, dmin, sum, pos);
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(sum == 0) != 0, 0)) {   // +M and -M both present (silence has sum == 1: F5): first occurrence decides
@@ -506,14 +538,14 @@ __device__ __forceinline__ void gc_encode_piece(
         return s1;
     };
 
-    auto encode_frame = [&](Row &R, int buf, int j, bool upd) {
+    auto encode_frame = [&](Row &R, Slot &S, uint32_t pre) {
         const uint32_t (&xw)[7] = R.xw;
         // ---- pre-scan (:107-124): two history-dependent distances + the helper's range for s = 2..13
         int s1, P0;
         {
             int d0, d1;
             prescan_head(R, d0, d1, P0);
-            s1 = first_scale(R, d0, d1);
+            s1 = first_scale(R, pre, d0, d1);
         }
         // ---- first trip: candidate A at s1, B at s1+1 (speculation on the loop of :127-170)
         int final_sp = imin(s1 + (cand_b ? 1 : 0), 12);
@@ -574,13 +606,13 @@ __device__ __forceinline__ void gc_encode_piece(
             const unsigned pay = row16_reduce(won ? r.hist_pair : 0u,
                                               [](unsigned a, unsigned b) { return a | b; });
             if (won) {                                           // packed and flushed by the helper, a tile at a time
-                int4 *rec = &s_out[buf][grp][j][0];
+                int4 *rec = &S.out[0];
                 rec[0] = make_int4(r.q2[0], r.q2[1], r.q2[2], r.q2[3]);
                 rec[1] = make_int4(r.q2[4], r.q2[5], r.q2[6], r.q2[7]);
                 rec[2] = make_int4(r.q2[8], r.q2[9], r.q2[10], r.q2[11]);
                 rec[3] = make_int4(r.q2[12], r.q2[13], p, final_sp);
             }
-            if (!RAGGED || upd) hpk = pay;       // pcmBuffer[0] = pcmBuffer[14], pcmBuffer[1] = pcmBuffer[15] (:40-41), as the pair
+            if (slot_has_frame(S)) hpk = pay;    // pcmBuffer[0] = pcmBuffer[14], pcmBuffer[1] = pcmBuffer[15] (:40-41), as the pair
         };
         bool sat = false;
         const int winner32 = argmin32(r, fin && !inexact, sat);      // (a lane whose sum is not to be trusted yet is not in it)
@@ -619,13 +651,13 @@ __device__ __forceinline__ void gc_encode_piece(
 
     // ---- CPW = 8: lane = (channel, predictor); both trips of the reference's loop are passes of the SAME lane, one behind
     // the other: the pass at s1 for its overflow, then the final pass at the scale that overflow names (round 11).
-    auto encode_frame8 = [&](Row &R, int buf, int j, bool upd) {
+    auto encode_frame8 = [&](Row &R, Slot &S, uint32_t pre) {
         const uint32_t (&xw)[7] = R.xw;
         int s1, P0;
         {
             int d0, d1;
             prescan_head(R, d0, d1, P0);
-            s1 = first_scale(R, d0, d1);
+            s1 = first_scale(R, pre, d0, d1);
         }
         const int sp_a = imin(s1, 12), sp_b = imin(s1 + 1, 12);
         // Round 5: when every lane of the wave quantises at scale 9 or below (70 % of the synthetic set's wave-frames) the two
@@ -637,7 +669,7 @@ __device__ __forceinline__ void gc_encode_piece(
         // overflow the flags read where they read pass B's (gc_encode_core.hpp T1, T2: final_pass_pair).
         PassOutB r;
         int ov_a, sp2;
-#ifdef VGA_GC_NO_FAST_PASSES                                        // (timing-only switch, tools/build_variants.sh)
+#ifdef VGA_GC_NO_FAST_PASSES                                       // (timing-only switch, tools/build_variants.sh)
         bool short_passes = false;
 #else
         bool short_passes = !__any(sp_b > 9);
@@ -651,13 +683,13 @@ __device__ __forceinline__ void gc_encode_piece(
         if (!short_passes) r = final_pass_pair<false>(xw, hpk, R.mp, c0, c1, sp_a, sp_b, P0, ov_a, sp2);
         const int ov_2 = r.max_overflow;
         // Which of the two passes the reference ends on, and what can stand in the way (each lane for itself, round 5):
-        // gc_encode_core.hpp frame_flags.
-        const FrameFlags ff = frame_flags(sp_a, sp_b, ov_a, ov_2, coef_ok);
-        const bool bump_a = ff.bump_a, generic = ff.generic, inexact = ff.inexact;
+        // gc_encode_core.hpp frame_flags.  Round 12: the hot path forms ONE bit from them, as compares and lane-mask logic
+        // (frame_goes_cold); the single flags are worked out inside the cold branch, by the lanes that got there.
 #ifdef VGA_GC_ABLATE_THIRD_TRIPS                                     // timing only (tools/build_variants.sh): what the cold block costs
-        const bool resume = false;
+        const FrameFlags ff0 = frame_flags(sp_a, sp_b, ov_a, ov_2, coef_ok);
+        const bool cold = ff0.generic || ff0.inexact;
 #else
-        const bool resume = ff.resume;                             // both overflowed: on to s1 + 2 in the cold block
+        const bool cold = frame_goes_cold(sp_a, sp_b, ov_a, ov_2, coef_ok).cold;
 #endif
         // (Round 6, measured and taken out again: the winning lanes storing the right pass's nibbles under their own masks
         // instead of fourteen selects in every lane -- 18 VALU instructions a frame less, two more exec-masked branches on
@@ -703,19 +735,27 @@ __device__ __forceinline__ void gc_encode_piece(
             pay |= (unsigned)dpp<DPP_QUAD_XOR2>((int)pay);
             pay |= (unsigned)dpp<DPP_ROW_HALF_MIRROR>((int)pay);
             if (won) {
-                int4 *rec = &s_out[buf][grp][j][0];
+                int4 *rec = &S.out[0];
                 rec[0] = make_int4(r.q2[0], r.q2[1], r.q2[2], r.q2[3]);
                 rec[1] = make_int4(r.q2[4], r.q2[5], r.q2[6], r.q2[7]);
                 rec[2] = make_int4(r.q2[8], r.q2[9], r.q2[10], r.q2[11]);
                 rec[3] = make_int4(r.q2[12], r.q2[13], p, final_sp);
             }
-            if (!RAGGED || upd) hpk = pay;       // (a slot past its last frame keeps the history it ended on)
+            if (slot_has_frame(S)) hpk = pay;    // (a slot past its last frame keeps the history it ended on)
         };
         bool sat = false;
-        const int winner32 = argmin32(r, !(generic || resume || inexact), sat);
-        if (__builtin_expect(__any(generic || resume || inexact) || sat, 0)) {
+        const int winner32 = argmin32(r, !cold, sat);
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(cold) != 0 || sat, 0)) {
 #ifdef VGA_GC_STATS                                                  // (a -DVGA_GC_STATS build only: five instructions per cold block = 1 ms of the launch)
             if (lane == 0) atomicAdd(&s_ncold[wave], 1);
+#endif
+            // what this lane needs there (a lane that is not cold has none of them set)
+            const FrameFlags ff = frame_flags(sp_a, sp_b, ov_a, ov_2, coef_ok);
+            const bool bump_a = ff.bump_a, generic = ff.generic, inexact = ff.inexact;
+#ifdef VGA_GC_ABLATE_THIRD_TRIPS
+            const bool resume = false;
+#else
+            const bool resume = ff.resume;                         // both overflowed: on to s1 + 2 in the cold block
 #endif
             ColdState st;
 #pragma unroll
@@ -749,9 +789,9 @@ __device__ __forceinline__ void gc_encode_piece(
         } else
             commit(r, final_sp, winner32);
     };
-    auto encode_one = [&](Row &R, int buf, int j, bool upd) __attribute__((always_inline)) {
-        if constexpr (CPW == 4) encode_frame(R, buf, j, upd);
-        else encode_frame8(R, buf, j, upd);
+    auto encode_one = [&](Row &R, Slot &S, uint32_t pre) __attribute__((always_inline)) {
+        if constexpr (CPW == 4) encode_frame(R, S, pre);
+        else encode_frame8(R, S, pre);
     };
 
 #ifdef VGA_DEBUG_TIMESTAMPS
@@ -761,28 +801,36 @@ __device__ __forceinline__ void gc_encode_piece(
     for (int tile = 0; tile < tiles; tile++) {
         const int buf = tile & 1;
         const int nf = imin(TF, frames_wg - tile * TF);
-        const int left = frames - tile * TF;           // RAGGED: this slot's own frames in the tile
 #ifndef VGA_GC_NO_TILE_REDERIVE                        // (timing-only switch, tools/build_variants.sh)
         {
-            // the lane's LDS addresses follow from its slot and predictor: derived again for every tile (three VALU ops) --
-            // kept across the piece they were spilled and came back through scratch loads the tile had to wait for
-            int l = lane;
-            asm volatile("" : "+v"(l));
-            grp = wave * CPW + l / LPC;
+            // the lane's LDS address follows from its slot and predictor: derived again for every tile -- kept across the piece
+            // they were spilled and came back through scratch loads the tile had to wait for.  Round 12: from the hardware's
+            // lane number and the wave's number in a scalar register; at 128 VGPRs `lane` itself is a spilled value.
+            // (the count's start value is opaque, or hipcc forms the lane number once per piece and spills THAT)
+            unsigned zero = 0;
+            asm volatile("" : "+s"(zero));
+            const int l = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
+            grp = wave_u * CPW + l / LPC;
             p = CPW == 4 ? (l & (LPC - 1)) >> 1 : (l & (LPC - 1));
         }
 #endif
-        const GcTile &T = s_tile[buf];
+        // The lane's one LDS address: rows, pre-scan words and records are immediate offsets from it, and it moves on by two
+        // frames per trip (TF is even and j is: S[1] is a frame of the tile; S[2] behind the tile's last pair is the padding
+        // and the next channel slot's first frame, or s_tiles.end -- read, never used).
+        Slot *S = &s_tile[buf].g[grp].f[0];
         // two row register sets, ping-pong: the LDS reads of frame j+1 are in flight during frame j
         Row RA, RB;
-        read_row(T, 0, RA);
+        read_row(S[0], RA);
 #pragma unroll 1
-        for (int j = 0; j < nf; j += 2) {
-            read_row(T, imin(j + 1, TF - 1), RB);
-            encode_one(RA, buf, j, j < left);
+        for (int j = 0; j < nf; j += 2, S += 2) {
+            // (LDS answers in order: the frame's own pre-scan word is asked for BEFORE the next frame's six row reads)
+            const uint32_t pre_a = read_pre(S[0]);
+            read_row(S[1], RB);
+            encode_one(RA, S[0], pre_a);
             if (j + 1 < nf) {
-                read_row(T, imin(j + 2, TF - 1), RA);
-                encode_one(RB, buf, j + 1, j + 1 < left);
+                const uint32_t pre_b = read_pre(S[1]);
+                read_row(S[2], RA);
+                encode_one(RB, S[1], pre_b);
             }
         }
         __syncthreads();                               // tile done: helper may flush it and refill this buffer later
@@ -1129,7 +1177,7 @@ __global__ __launch_bounds__(64) void gc_encode_seam_kernel(
 // the other workgroups' items.  A seam reads what two other workgroups wrote (the piece state before it, the bytes
 // after it): both sides put a device-scope fence between their stores / loads and the counter.
 template <int CPW, bool RAGGED>
-__global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void gc_encode_persistent_kernel(
+__global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(VGA_GC_PERSISTENT_WAVES_PER_EU))) void gc_encode_persistent_kernel(
     const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const Pieces seg,
     const int16_t *__restrict__ coefs, const int16_t *__restrict__ hist1,
     const int16_t *__restrict__ hist2, uint8_t *adpcm, int64_t adpcm_pitch, int16_t *seg_state,
@@ -1307,11 +1355,17 @@ constexpr int MAX_PIECES = 1024;               // what encode_scratch_bytes() an
 // PERSISTENT_BIG_ROUNDS big items followed by PERSISTENT_SMALL_ROUNDS rounds of short ones -- with items of one size d
 // the workgroups end spread over the last d of the launch (152 ms at configs[1] with 16 pieces of 35 ms: mean life
 // 136 ms + d / 2).
-// persistent workgroups per compute unit: four (two encoder waves and a helper on every SIMD)
+// persistent workgroups per compute unit: four.  What the number rests on: the kernel is built for three waves per SIMD
+// (amdgpu_waves_per_eu(3, 3), 166 VGPRs), a workgroup is three waves, so four workgroups put exactly two encoder waves and a
+// helper on every SIMD -- the wave slots themselves force the even placement.  Round 12 built the kernel for four waves per
+// SIMD (128 VGPRs, no scratch instruction in the frame loop; -DVGA_GC_PERSISTENT_WAVES_PER_EU=4,4) and ran it at four and at
+// five workgroups: all five start together, but the launch takes 122-125 ms against 113.5 -- most workgroups end near 104 ms,
+// a few near 121 (four) or 134 (five): with a free fourth slot nothing keeps three or four encoder waves off one SIMD, and the
+// launch lasts as long as its slowest workgroup (LABNOTES 17).
 static int persistent_wgs_per_cu()
 {
-#ifdef VGA_TUNING   // tools/time_corun.py: fewer workgroups leave registers and LDS for another kernel's waves
-    if (const char *e = std::getenv("VGA_HIP_GC_WGS_PER_CU")) return imin(imax(std::atoi(e), 1), 4);
+#ifdef VGA_TUNING   // tools/time_corun.py: fewer workgroups leave registers and LDS for another kernel's waves; 5: for a four-waves build
+    if (const char *e = std::getenv("VGA_HIP_GC_WGS_PER_CU")) return imin(imax(std::atoi(e), 1), 5);
 #endif
     return 4;
 }
