@@ -334,6 +334,19 @@ SIGNATURES = {
     "vga_hca_decode_workspace_bytes": (C.c_size_t, [vp, ci]),
     "vga_hca_encode_device": (ci, [vp, i64, i64, ci, ci, vp, vp, i64, vp, vp]),
     "vga_hca_decode_device": (ci, [vp, vp, i64, ci, vp, i64, i64, vp, C.c_size_t, vp, vp]),
+    # include/vgaudio_hip/adx_files.h
+    "vga_adx_files_layout_for": (ci, [vp, ci, C.POINTER(i64), C.POINTER(ci), C.POINTER(i64), C.POINTER(i64), vp]),
+    "vga_adx_files_create": (ci, [vp, ci, C.POINTER(i64), C.POINTER(vp)]),
+    "vga_adx_files_create_from_infos": (ci, [vp, ci, C.POINTER(i64), C.POINTER(vp)]),
+    "vga_adx_files_destroy": (None, [vp]),
+    "vga_adx_files_totals_of": (ci, [vp, vp]),
+    "vga_adx_files_offsets": (ci, [vp, C.POINTER(ci), C.POINTER(i64), C.POINTER(i64)]),
+    "vga_adx_write_device_v": (ci, [vp, vp, vp, vp, vp]),
+    "vga_adx_read_device_v": (ci, [vp, vp, vp, vp, vp]),
+    "vga_adx_files_write_items_for": (ci, [vp, ci, C.POINTER(i64), ci, vp, i64, C.POINTER(i64)]),
+    "vga_adx_files_read_items_for": (ci, [vp, ci, C.POINTER(i64), ci, vp, i64, C.POINTER(i64)]),
+    "vga_adx_files_stats": (ci, [vp, C.POINTER(i64)]),
+    "vga_adx_files_force_general_this_thread": (ci, [ci]),
 }
 
 
@@ -348,6 +361,22 @@ class AdxFileLayoutC(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("sample_count", "frame_count", "base_header_size", "alignment_bytes", "header_size",
                                        "audio_offset", "audio_size", "footer_offset", "footer_size", "loop_start_offset",
                                        "loop_end_offset", "file_size")]
+
+
+class AdxFileC(C.Structure):
+    """vga_adx_file (include/vgaudio_hip/adx_files.h)"""
+    _fields_ = [("channels", C.c_int), ("params", AdxFileParamsC)]
+
+
+class AdxFilesTotalsC(C.Structure):
+    """vga_adx_files_totals"""
+    _fields_ = [("files", C.c_int), ("channels", C.c_int), ("audio_bytes", C.c_int64), ("image_bytes", C.c_int64)]
+
+
+class AdxFilesItemC(C.Structure):
+    """vga_adx_files_item"""
+    _fields_ = [("form", C.c_int), ("file", C.c_int), ("x", C.c_int), ("y", C.c_uint32), ("granule", C.c_int),
+                ("begin", C.c_int64), ("end", C.c_int64), ("keep_end", C.c_int64)]
 
 
 class WaveInfoC(C.Structure):

@@ -111,3 +111,245 @@ class AdxReader:
         chans = [CriAdxChannel(audio[c], int(info.history[c][0]), info.version) for c in range(info.channel_count)]
         return CriAdxFormat(chans, info.sample_count - ins, info.sample_rate, info.frame_size, info.highpass_frequency, ins,
                             info.type, info.version, bool(info.looping), info.loop_start_sample - ins, info.loop_end_sample - ins)
+
+
+# ---------------------------------------------------------------- sets of files on the device (include/vgaudio_hip/adx_files.h)
+def _adx_file(f):
+    if isinstance(f, _lib.AdxFileC):
+        return f
+    channels, params = f
+    return _lib.AdxFileC(int(channels), params if isinstance(params, _lib.AdxFileParamsC) else _lib.AdxFileParamsC(*params))
+
+
+def _i64_or_none(values):
+    if values is None:
+        return None, None
+    a = np.ascontiguousarray(values, dtype=np.int64)
+    return a, a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+class AdxFileSet:
+    """A set of ADX files of different shapes, resident on the device (include/vgaudio_hip/adx_files.h has the layout): the
+    channels of all files are packed rows -- as criadx.RaggedAdx leaves its output, or at the caller's `audio_offsets` --, the
+    images one packed buffer.  `files`: one _lib.AdxFileC or (channels, _lib.AdxFileParamsC) per file, the params what
+    vga_adx_write_device takes.  The tensors are the caller's torch tensors on the current device; the calls run on torch's
+    current stream and do not synchronise it."""
+
+    def __init__(self, files=None, audio_offsets=None, _handle=None):
+        self._h, self.image_sizes = C.c_void_p(), None
+        if _handle is not None:
+            self._h = _handle
+        else:
+            arr, n = self._files_array(files)
+            keep, offs = _i64_or_none(audio_offsets)
+            check(_lib.lib().vga_adx_files_create(arr, n, offs, C.byref(self._h)))
+            self.image_sizes = [self.file_layout(arr[i]).file_size for i in range(n)]
+        self.totals = _lib.AdxFilesTotalsC()
+        check(_lib.lib().vga_adx_files_totals_of(self._h, C.byref(self.totals)))
+        nf, nch = self.totals.files, self.totals.channels
+        fc, ao, io = np.zeros(max(nf, 1), np.int32), np.zeros(max(nch, 1), np.int64), np.zeros(max(nf, 1), np.int64)
+        i64p = C.POINTER(C.c_int64)
+        check(_lib.lib().vga_adx_files_offsets(self._h, fc.ctypes.data_as(C.POINTER(C.c_int)), ao.ctypes.data_as(i64p), io.ctypes.data_as(i64p)))
+        self.first_channel, self.audio_offsets, self.image_offsets = fc[:nf], ao[:nch], io[:nf]
+        self.files, self.channels = nf, nch
+
+    @staticmethod
+    def _files_array(files):
+        files = [_adx_file(f) for f in (files or [])]
+        return (_lib.AdxFileC * max(len(files), 1))(*files), len(files)
+
+    @staticmethod
+    def file_layout(f):
+        """vga_adx_file_layout_for of one file of a set"""
+        L = _lib.AdxFileLayoutC()
+        check(_lib.lib().vga_adx_file_layout_for(C.byref(f.params), f.channels, C.byref(L)))
+        return L
+
+    @classmethod
+    def layout(cls, files, audio_offsets=None):
+        """(first_channel int32[files], audio_offsets int64[channels], image_offsets int64[files], AdxFilesTotalsC): host only,
+        needs no GPU"""
+        arr, n = cls._files_array(files)
+        nch = sum(arr[i].channels for i in range(n) if arr[i].channels > 0)
+        fc, ao, io = np.zeros(max(n, 1), np.int32), np.zeros(max(nch, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        tot, i64p = _lib.AdxFilesTotalsC(), C.POINTER(C.c_int64)
+        keep, offs = _i64_or_none(audio_offsets)
+        check(_lib.lib().vga_adx_files_layout_for(arr, n, offs, fc.ctypes.data_as(C.POINTER(C.c_int)), ao.ctypes.data_as(i64p),
+                                                  io.ctypes.data_as(i64p), C.byref(tot)))
+        return fc[:n], ao[:tot.channels], io[:n], tot
+
+    @classmethod
+    def from_infos(cls, infos, image_offsets=None):
+        """A set for reading, from the vga_adx_file_info of every file (parse()); image_offsets: any byte offsets, or None for
+        images packed as write_device packs them"""
+        infos = list(infos)
+        n = len(infos)
+        ptrs = (C.c_void_p * max(n, 1))(*[C.addressof(i) for i in infos])
+        keep, offs = _i64_or_none(image_offsets)
+        h = C.c_void_p()
+        check(_lib.lib().vga_adx_files_create_from_infos(ptrs, n, offs, C.byref(h)))
+        s = cls(_handle=h)
+        s.image_sizes = [i.audio_offset + i.audio_bytes * i.channel_count for i in infos]
+        return s
+
+    @staticmethod
+    def _items(call, first, n, offsets, general):
+        keep, offs = _i64_or_none(offsets)
+        count = C.c_int64()
+        check(call(first, n, offs, int(general), None, 0, C.byref(count)))
+        items = (_lib.AdxFilesItemC * max(count.value, 1))()
+        check(call(first, n, offs, int(general), items, count.value, C.byref(count)))
+        return list(items[:count.value])
+
+    @classmethod
+    def write_items(cls, files, audio_offsets=None, general=False):
+        """the work items of vga_adx_write_device_v on such a set (_lib.AdxFilesItemC), host only"""
+        arr, n = cls._files_array(files)
+        return cls._items(_lib.lib().vga_adx_files_write_items_for, arr, n, audio_offsets, general)
+
+    @classmethod
+    def read_items(cls, infos, image_offsets=None, general=False):
+        """the work items of vga_adx_read_device_v on a set of such infos, host only"""
+        infos = list(infos)
+        ptrs = (C.c_void_p * max(len(infos), 1))(*[C.addressof(i) for i in infos])
+        return cls._items(_lib.lib().vga_adx_files_read_items_for, ptrs, len(infos), image_offsets, general)
+
+    def close(self):
+        if self._h:
+            _lib.lib().vga_adx_files_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def stats(self):
+        """(span files, general files, span items, general items) of a call made by this thread now"""
+        out = (C.c_int64 * 4)()
+        check(_lib.lib().vga_adx_files_stats(self._h, out))
+        return tuple(out)
+
+    def write_device(self, audio, images, history=None, stream=None):
+        """vga_adx_write_device_v.  audio: uint8[totals.audio_bytes] (the rows), history: int16[channels] (needed if any file is
+        version 4); images: uint8[totals.image_bytes]"""
+        import torch
+        from .dsp import DspFileSet
+        ptr, t = DspFileSet._ptr, self.totals
+        check(_lib.lib().vga_adx_write_device_v(self._h, ptr(audio, torch.uint8, t.audio_bytes, "audio"),
+                                                ptr(history, torch.int16, self.channels, "history"),
+                                                ptr(images, torch.uint8, t.image_bytes, "images"), DspFileSet._stream(stream)))
+
+    def read_device(self, images, audio, history=None, stream=None):
+        """vga_adx_read_device_v (a set from from_infos): images -> the rows of audio and, if given, the start history of
+        every row"""
+        import torch
+        from .dsp import DspFileSet
+        ptr, t = DspFileSet._ptr, self.totals
+        check(_lib.lib().vga_adx_read_device_v(self._h, ptr(images, torch.uint8, t.image_bytes, "images"),
+                                               ptr(audio, torch.uint8, t.audio_bytes, "audio"),
+                                               ptr(history, torch.int16, self.channels, "history"), DspFileSet._stream(stream)))
+
+    def images(self, host_buffer):
+        """one `bytes` per file from the packed images (a device tensor or a numpy array); synchronises"""
+        host = host_buffer.cpu().numpy() if hasattr(host_buffer, "cpu") else np.asarray(host_buffer, dtype=np.uint8)
+        return [host[int(at):int(at) + int(size)].tobytes() for at, size in zip(self.image_offsets, self.image_sizes)]
+
+
+def write_files(pcm16_list, configuration=None):
+    """AdxWriter(configuration).GetFile(file) for a list of Pcm16Format files, on the device and without a launch per file: the
+    files are grouped by the codec parameter set they need (sample rate, loop padding), one criadx.RaggedAdx per group encodes
+    into one buffer, one AdxFileSet over all of them writes the images.  Returns one `bytes` per file, in the caller's order.
+    A file the encoder refuses (no samples with version 4 and no padding) raises, naming the file."""
+    import torch
+    from .criadx import RaggedAdx, _get_next_multiple
+    cfg = configuration or AdxConfiguration()
+    if cfg.EncryptionKey is not None:
+        raise _lib.ArgumentError("write_files: keyed encryption is not part of file sets; AdxWriter encrypts file by file")
+    files = list(pcm16_list)
+    spf = (cfg.FrameSize - 2) * 2
+    groups, align = {}, []
+    for i, f in enumerate(files):
+        loop_start = f.LoopStart if f.Looping else 0
+        a = _get_next_multiple(loop_start, spf * 2 if f.ChannelCount == 1 else spf) - loop_start      # CriAdxFormat.cs:59-62
+        align.append(a)
+        if f.SampleCount == 0 and cfg.Version == 4 and a == 0:
+            raise _lib.ArgumentError("file %d: empty PCM: the reference reads pcm[0] (CriAdxCodec.cs:71)" % i)
+        groups.setdefault((f.SampleRate, a), []).append(i)
+    order = [i for members in groups.values() for i in members]
+    described = []
+    for i in order:
+        f, a = files[i], align[i]
+        looping = bool(f.Looping)
+        described.append(_lib.AdxFileC(f.ChannelCount, _lib.AdxFileParamsC(
+            f.SampleRate, f.SampleCount + a, int(looping), (f.LoopStart if looping else 0) + a, (f.LoopEnd if looping else 0) + a, a,
+            cfg.FrameSize, cfg.Version, cfg.Type, 500, cfg.EncryptionType, int(bool(cfg.TrimFile)))))
+    AdxFileSet.layout(described)                                   # every refusal of a file, before anything is allocated
+    if not files:
+        return []
+    ragged, s = [], None
+    try:
+        pcm_at = adx_at = 0
+        offsets, pcm_parts = [], []
+        for (rate, a), members in groups.items():
+            params = CriAdxParameters(SampleRate=rate, FrameSize=cfg.FrameSize, Padding=a, Filter=cfg.Filter, Type=cfg.Type, Version=cfg.Version)
+            r = RaggedAdx(params, [files[i].SampleCount for i in members for _ in range(files[i].ChannelCount)])
+            ragged.append((r, pcm_at, adx_at, len(offsets)))
+            host, c = np.zeros(r.totals.pcm_samples, dtype=np.int16), 0
+            for i in members:
+                for ch in files[i].Channels:
+                    n = files[i].SampleCount
+                    host[r.pcm_offsets[c]:r.pcm_offsets[c] + n] = np.asarray(ch, dtype=np.int16)[:n]
+                    c += 1
+            pcm_parts.append(host)
+            offsets += [adx_at + int(o) for o in r.adx_offsets]
+            pcm_at += r.totals.pcm_samples                           # multiples of 8 samples / 16 bytes: every base stays aligned
+            adx_at += r.totals.adx_bytes
+        s = AdxFileSet(described, audio_offsets=offsets if len(ragged) > 1 else None)
+        if [int(o) for o in s.audio_offsets] != offsets:
+            raise _lib.VgaError("internal: the ragged batches' rows are not the file set's")
+        pcm = torch.from_numpy(np.concatenate(pcm_parts)).cuda()
+        adx = torch.zeros(max(adx_at, s.totals.audio_bytes), dtype=torch.uint8, device="cuda")
+        history = torch.zeros(max(s.channels, 1), dtype=torch.int16, device="cuda")
+        ws = torch.empty(max(max(r.totals.encode_workspace_bytes for r, _, _, _ in ragged), 16), dtype=torch.uint8, device="cuda")
+        images = torch.empty(s.totals.image_bytes, dtype=torch.uint8, device="cuda")
+        for r, p0, a0, c0 in ragged:
+            if r.channels:
+                r.encode_device(pcm[p0:], adx[a0:], ws, history=history[c0:])
+        s.write_device(adx, images, history=history)
+        out = s.images(images)
+        result = [None] * len(files)
+        for k, i in enumerate(order):
+            result[i] = out[k]
+        return result
+    finally:
+        for r, _, _, _ in ragged:
+            r.close()
+        if s is not None:
+            s.close()
+
+
+def read_files(list_of_bytes):
+    """AdxReader().ReadFormat(file) for a list of files: the headers are parsed on the host, all audio is taken out of the
+    images in one vga_adx_read_device_v call.  Returns one CriAdxFormat per file; an encrypted file's audio stays encrypted, as
+    AdxReader leaves it when it has no key."""
+    import torch
+    datas = [bytes(d) for d in list_of_bytes]
+    infos = [parse(d) for d in datas]
+    s = AdxFileSet.from_infos(infos)
+    try:
+        if s.files == 0:
+            return []
+        host = np.zeros(s.totals.image_bytes, dtype=np.uint8)
+        for d, at, size in zip(datas, s.image_offsets, s.image_sizes):
+            host[int(at):int(at) + size] = np.frombuffer(d, dtype=np.uint8)[:size]
+        images = torch.from_numpy(host).cuda()
+        audio = torch.zeros(s.totals.audio_bytes, dtype=torch.uint8, device="cuda")
+        s.read_device(images, audio)
+        rows = audio.cpu().numpy()
+        out = []
+        for f, info in enumerate(infos):
+            first = int(s.first_channel[f])
+            chans = [rows[int(s.audio_offsets[first + c]):int(s.audio_offsets[first + c]) + info.audio_bytes].copy()
+                     for c in range(info.channel_count)]
+            out.append(AdxReader._to_format(info, chans))
+        return out
+    finally:
+        s.close()

@@ -1,6 +1,7 @@
 // container_kernels.hip -- file images assembled in HBM.  All of this is byte movement:
 // HBM-bound, every byte read once and written once.
 #include "container_kernels.hpp"
+#include "adx_header_body.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -62,55 +63,17 @@ int launch_interleave(const uint8_t *src, int64_t pitch, int input_size, int cou
     return VGA_OK;
 }
 
-// A positioned big-endian writer over the image, as the reference's BinaryWriter over MemoryStream(byte[FileSize]).
-struct Cursor {
-    uint8_t *buf;
-    int size, pos;
-    __device__ void put8(int v) { if (pos < size) buf[pos] = (uint8_t)v; pos++; }
-    __device__ void put16(int v) { put8(v >> 8); put8(v); }
-    __device__ void put32(int v) { put16(v >> 16); put16(v); }
-};
-
-// AdxWriter.WriteHeader (:81-117).  Fields are written one after the other whatever HeaderSize is; "(c)CRI" and
-// then the audio overwrite what ran past it -- the later launches on the same stream reproduce that order.
+// AdxWriter.WriteHeader (:81-117) and the footer (:133-138): adx_header_body.hpp's bodies, one thread each
 __global__ void adx_header_kernel(AdxHeaderArgs a, const int16_t *__restrict__ history, uint8_t *__restrict__ file)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    Cursor c{file, a.file_size, 0};
-    c.put16(0x8000);
-    c.put16(a.header_size);
-    c.put8(a.type);
-    c.put8(a.frame_size);
-    c.put8(4);                                             // bit depth
-    c.put8(a.nch);
-    c.put32(a.sample_rate);
-    c.put32(a.sample_count);
-    c.put16(a.type != 2 ? a.highpass_frequency : 0);       // CriAdxType.Fixed
-    c.put8(a.version);
-    c.put8(a.encryption_type);
-    if (a.version == 4) {
-        c.put32(0);
-        for (int i = 0; i < a.nch; i++) { c.put16(history[i]); c.put16(history[i]); }
-        if (a.nch == 1) c.put32(0);
-    }
-    c.put16(a.alignment_samples);
-    c.put16(a.looping ? 1 : 0);
-    c.put32(a.looping ? 1 : 0);
-    c.put32(a.loop_start);
-    c.put32(a.loop_start_offset);
-    c.put32(a.loop_end);
-    c.put32(a.loop_end_offset);
-    c.pos = a.header_size - 2;
-    const char sig[6] = {'(', 'c', ')', 'C', 'R', 'I'};
-    for (int k = 0; k < 6; k++) c.put8(sig[k]);
+    adx_write_header(a, history, file);
 }
 
 __global__ void adx_footer_kernel(AdxHeaderArgs a, uint8_t *__restrict__ file)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    Cursor c{file, a.file_size, a.footer_pos};
-    c.put16(0x8001);
-    c.put16(a.footer_size - 4);
+    adx_write_footer(a, file);
 }
 
 int launch_adx_header(const AdxHeaderArgs &a, const int16_t *d_history, uint8_t *d_file, hipStream_t stream)

@@ -1,6 +1,7 @@
 // container_kernels.hpp -- launchers for the container-image kernels
 #pragma once
 #include "common.hpp"
+#include "adx_file_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -50,11 +51,7 @@ inline int upload_bytes(const uint8_t *host, int n, uint8_t *dst, hipStream_t s)
 int launch_interleave(const uint8_t *src, int64_t pitch, int input_size, int count, int interleave, int output_size,
                       uint8_t *dst, hipStream_t stream);
 
-struct AdxHeaderArgs {
-    int header_size, type, frame_size, nch, sample_rate, sample_count, highpass_frequency, version, encryption_type;
-    int alignment_samples, looping, loop_start, loop_start_offset, loop_end, loop_end_offset;
-    int footer_pos, footer_size, file_size;
-};
+// (AdxHeaderArgs: adx_file_host.hpp, with the host code that fills it)
 // AdxWriter.WriteHeader (:81-117); the footer (:133-138) is a second launch AFTER the audio, as in the reference
 int launch_adx_header(const AdxHeaderArgs &a, const int16_t *d_history, uint8_t *d_file, hipStream_t stream);
 int launch_adx_footer(const AdxHeaderArgs &a, uint8_t *d_file, hipStream_t stream);

@@ -3,6 +3,7 @@
 // in HBM, in the row layouts the decoders take.  Keys and decryption stay with the caller, who composes them from the
 // existing key-search and crypt calls exactly as the reference's ToAudioStream does.
 #include "container_host.hpp"
+#include "adx_span.hpp"
 #include "hca_capi.hpp"
 #include "hca_frame_crc.hpp"
 
@@ -14,63 +15,20 @@ namespace vga {
 namespace readers {
 
 // ADX frames of 18 bytes, interleaved one frame per channel (AdxReader.ReadData :116-124 -> DeInterleave(audioSize,
-// FrameSize, ChannelCount)).  18 does not divide 16 and the audio offset has any alignment, so a gather straight from
-// the image moves 2-byte granules at best (the general path).  Here a workgroup takes a span of frame groups of one file:
-// aligned 16-byte loads of the span into LDS (the ragged ends byte by byte), then every thread assembles 16-byte output
-// granules of one channel's row from LDS and stores them aligned.  A span holds a multiple of 8 frames per channel, so
-// every span starts its rows on a 16-byte boundary (8 * 18 = 144 = 9 * 16).
-constexpr int kAdxFrame = 18;
-constexpr int kAdxSpanBytes = 16384;          // LDS per workgroup for the span (plus 32 bytes of alignment slack)
-constexpr int kAdxMaxFastChannels = kAdxSpanBytes / (kAdxFrame * 8);   // 113: a span must hold 8 frames per channel
+// FrameSize, ChannelCount)): a workgroup takes a span of frame groups of one file through LDS with 16-byte vectors both
+// ways.  The body is adx_span.hpp's, shared with the reader of a set of files (adx_files_kernels.hip).
+constexpr int kAdxFrame = adxspan::kFrame;
+constexpr int kAdxSpanBytes = adxspan::kSpanBytes;
+constexpr int kAdxMaxFastChannels = adxspan::kMaxChannels;
 
 __global__ __launch_bounds__(256) void adx18_deinterleave_kernel(const uint8_t *__restrict__ files, int64_t file_pitch,
                                                                  int audio_offset, int nch, int frame_count, int span_frames,
                                                                  uint8_t *__restrict__ dst, int64_t dst_pitch, int file0)
 {
-    __shared__ __align__(16) uint8_t lds[kAdxSpanBytes + 32];
+    __shared__ __align__(16) uint8_t lds[adxspan::kLdsBytes];
     const int f = file0 + blockIdx.y;
-    const uint8_t *base = files + (int64_t)f * file_pitch + audio_offset;
-    const int64_t audio = (int64_t)frame_count * kAdxFrame * nch;      // the image's audio bytes: nothing outside is read
-    const int k0 = blockIdx.x * span_frames;
-    const int nk = min(span_frames, frame_count - k0);
-    const int64_t span0 = (int64_t)k0 * kAdxFrame * nch, span1 = span0 + (int64_t)nk * kAdxFrame * nch;
-    const int mis = (int)((uintptr_t)(base + span0) & 15);            // LDS byte 0 is audio byte span0 - mis
-    const int64_t x0 = span0 - mis;
-    const int granules = (int)((span1 - x0 + 15) >> 4);
-    for (int g = threadIdx.x; g < granules; g += 256) {
-        const int64_t x = x0 + 16 * (int64_t)g;
-        uint4 v;
-        if (x >= 0 && x + 16 <= audio) {
-            v = *reinterpret_cast<const uint4 *>(base + x);
-        } else {
-            uint8_t t[16];
-#pragma unroll
-            for (int k = 0; k < 16; k++) t[k] = x + k >= 0 && x + k < audio ? base[x + k] : 0;
-            memcpy(&v, t, 16);
-        }
-        *reinterpret_cast<uint4 *>(lds + 16 * g) = v;
-    }
-    __syncthreads();
-    const int row_bytes = nk * kAdxFrame;
-    const int per_row = (row_bytes + 15) >> 4;
-    for (int q = threadIdx.x; q < per_row * nch; q += 256) {
-        const int c = q / per_row, j0 = (q - c * per_row) * 16;
-        const int fr = j0 / kAdxFrame, w = j0 - fr * kAdxFrame;
-        const int n1 = min(16, kAdxFrame - w);                         // bytes from frame fr, the rest from frame fr + 1
-        const int o1 = mis + (fr * nch + c) * kAdxFrame + w, o2 = mis + ((fr + 1) * nch + c) * kAdxFrame - n1;
-        const int avail = min(16, row_bytes - j0);
-        uint8_t t[16];
-#pragma unroll
-        for (int k = 0; k < 16; k++) t[k] = k < avail ? lds[k < n1 ? o1 + k : o2 + k] : 0;
-        uint8_t *d = dst + (int64_t)(f * nch + c) * dst_pitch + (int64_t)k0 * kAdxFrame + j0;
-        if (avail == 16) {
-            uint4 v;
-            memcpy(&v, t, 16);
-            *reinterpret_cast<uint4 *>(d) = v;
-        } else {
-            for (int k = 0; k < avail; k++) d[k] = t[k];
-        }
-    }
+    adxspan::deinterleave_span(lds, files + (int64_t)f * file_pitch + audio_offset, nch, frame_count, blockIdx.x * span_frames, span_frames,
+                               [&](int c) { return dst + (int64_t)(f * nch + c) * dst_pitch; });
 }
 
 // ReadHcaData (HcaReader.cs:123-138): one wave per frame copies it from the image to the frames layout and checks its
