@@ -347,6 +347,19 @@ SIGNATURES = {
     "vga_adx_files_read_items_for": (ci, [vp, ci, C.POINTER(i64), ci, vp, i64, C.POINTER(i64)]),
     "vga_adx_files_stats": (ci, [vp, C.POINTER(i64)]),
     "vga_adx_files_force_general_this_thread": (ci, [ci]),
+    # include/vgaudio_hip/hca_files.h
+    "vga_hca_files_layout_for": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp]),
+    "vga_hca_files_create": (ci, [vp, ci, C.POINTER(i64), vp, ci, C.POINTER(vp)]),
+    "vga_hca_files_create_from_infos": (ci, [vp, ci, C.POINTER(i64), C.POINTER(ci), vp, ci, C.POINTER(i64), C.POINTER(vp)]),
+    "vga_hca_files_destroy": (None, [vp]),
+    "vga_hca_files_totals_of": (ci, [vp, vp]),
+    "vga_hca_files_offsets": (ci, [vp, C.POINTER(i64), C.POINTER(i64)]),
+    "vga_hca_write_device_v": (ci, [vp, vp, vp, vp]),
+    "vga_hca_read_device_v": (ci, [vp, vp, vp, vp, vp]),
+    "vga_hca_files_write_items_for": (ci, [vp, ci, C.POINTER(i64), ci, vp, i64, C.POINTER(i64)]),
+    "vga_hca_files_read_items_for": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), ci, vp, i64, C.POINTER(i64)]),
+    "vga_hca_files_stats": (ci, [vp, C.POINTER(i64)]),
+    "vga_hca_files_force_general_this_thread": (ci, [ci]),
 }
 
 
@@ -638,6 +651,23 @@ class HcaFileInfoC(C.Structure):
                 + [(n, C.c_int) for n in ("vbr_max_frame_size", "vbr_noise_level", "dec_stereo_type", "reserved1", "reserved2",
                                           "has_ath_chunk", "has_comment")]
                 + [("comment", C.c_char * 256), ("frames_offset", C.c_int)])
+
+
+class HcaFileC(C.Structure):
+    """vga_hca_file (include/vgaudio_hip/hca_files.h)"""
+    _fields_ = [("hca", HcaInfoC), ("comment", C.c_char_p), ("volume", C.c_float), ("encryption_type", C.c_int),
+                ("encrypted_ids", C.c_int), ("key", C.c_int)]
+
+
+class HcaFilesTotalsC(C.Structure):
+    """vga_hca_files_totals"""
+    _fields_ = [("files", C.c_int), ("total_frames", C.c_int64), ("frame_bytes", C.c_int64), ("image_bytes", C.c_int64)]
+
+
+class HcaFilesItemC(C.Structure):
+    """vga_hca_files_item"""
+    _fields_ = [("form", C.c_int), ("file", C.c_int), ("first_frame", C.c_int), ("frames", C.c_int), ("begin", C.c_int64),
+                ("end", C.c_int64)]
 
 
 class HcaParamsC(C.Structure):

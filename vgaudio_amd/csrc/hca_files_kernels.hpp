@@ -1,0 +1,25 @@
+// hca_files_kernels.hpp -- launchers of hca_files_kernels.hip over the device tables of a vga_hca_files object
+#pragma once
+#include "common.hpp"
+#include "hca_files_host.hpp"
+
+namespace vga {
+namespace hcaf {
+
+// the object's tables in device memory (hca_files_host.hpp has the element types)
+struct DeviceTables {
+    const FileTab *tab = nullptr;
+    const uint8_t *headers = nullptr;            // (a set for writing) every header, each at a multiple of 16
+    const uint8_t *tables = nullptr;             // the substitution tables, 256 bytes each
+    const uint16_t *crc_pow = nullptr;           // vga::hca::crc_pow_table
+    const Item *items[2] = {nullptr, nullptr};   // every file in its own form (span items in front); every file general
+    int files = 0;
+    int span_items = 0, item_count[2] = {0, 0};
+};
+
+// general: the force hook's table
+int launch_write_images(const DeviceTables &t, bool general, const uint8_t *d_frames, uint8_t *d_images, hipStream_t stream);
+int launch_read_images(const DeviceTables &t, bool general, const uint8_t *d_images, uint8_t *d_frames, int *d_bad_crc, hipStream_t stream);
+
+}  // namespace hcaf
+}  // namespace vga

@@ -128,3 +128,295 @@ class HcaReader:
             CriHcaEncryption.Crypt(hca, frames, key, True)
             hca.EncryptionType = 0
         return CriHcaFormat(frames, hca), HcaConfiguration(EncryptionKey=key)     # GetConfiguration (:51-57)
+
+
+# ---------------------------------------------------------------- sets of files on the device (include/vgaudio_hip/hca_files.h)
+def _i64_or_none(values):
+    if values is None:
+        return None, None
+    a = np.ascontiguousarray(values, dtype=np.int64)
+    return a, a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _tables_or_none(tables):
+    """ntables x 256 bytes -> (keep-alive, pointer, count)"""
+    if tables is None or len(tables) == 0:
+        return None, None, 0
+    a = np.ascontiguousarray(np.asarray(tables, dtype=np.uint8).reshape(-1, 256))
+    return a, a.ctypes.data_as(u8p), len(a)
+
+
+def _hca_file(f):
+    if isinstance(f, _lib.HcaFileC):
+        return f
+    info, comment, volume, encryption_type, encrypted_ids, key = f
+    c = _lib.HcaInfoC.from_buffer_copy(info.c if isinstance(info, HcaInfo) else info)
+    if isinstance(comment, str):
+        comment = comment.encode("utf-8")
+    return _lib.HcaFileC(c, comment, float(volume), int(encryption_type), int(encrypted_ids), int(key))
+
+
+class HcaFileSet:
+    """A set of HCA files of different shapes, resident on the device (include/vgaudio_hip/hca_files.h has the layout): the
+    frames of all files lie packed -- as crihca.RaggedHca leaves its output, or at the caller's `frame_offsets` --, the images
+    in one packed buffer.  `files`: one _lib.HcaFileC or (info, comment, volume, encryption_type, encrypted_ids, key) per file:
+    what vga_hca_write_device takes, and the index of the file's table in `tables` (ntables x 256 bytes; -1: no key).  The
+    tensors are the caller's torch tensors on the current device; the calls run on torch's current stream and do not
+    synchronise it."""
+
+    def __init__(self, files=None, frame_offsets=None, tables=None, _handle=None):
+        self._h, self.image_sizes = C.c_void_p(), None
+        if _handle is not None:
+            self._h = _handle
+        else:
+            arr, n = self._files_array(files)
+            keep, offs = _i64_or_none(frame_offsets)
+            keep_t, tp, nt = _tables_or_none(tables)
+            check(_lib.lib().vga_hca_files_create(arr, n, offs, tp, nt, C.byref(self._h)))
+            self.image_sizes = [arr[i].hca.header_size + arr[i].hca.frame_count * arr[i].hca.frame_size for i in range(n)]
+        self.totals = _lib.HcaFilesTotalsC()
+        check(_lib.lib().vga_hca_files_totals_of(self._h, C.byref(self.totals)))
+        nf = self.totals.files
+        fo, io = np.zeros(max(nf, 1), np.int64), np.zeros(max(nf, 1), np.int64)
+        i64p = C.POINTER(C.c_int64)
+        check(_lib.lib().vga_hca_files_offsets(self._h, fo.ctypes.data_as(i64p), io.ctypes.data_as(i64p)))
+        self.frame_offsets, self.image_offsets = fo[:nf], io[:nf]
+        self.files = nf
+
+    @staticmethod
+    def _files_array(files):
+        files = [_hca_file(f) for f in (files or [])]
+        return (_lib.HcaFileC * max(len(files), 1))(*files), len(files)
+
+    @classmethod
+    def layout(cls, files, frame_offsets=None):
+        """(frame_offsets int64[files], image_offsets int64[files], HcaFilesTotalsC): host only, needs no GPU"""
+        arr, n = cls._files_array(files)
+        fo, io = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        tot, i64p = _lib.HcaFilesTotalsC(), C.POINTER(C.c_int64)
+        keep, offs = _i64_or_none(frame_offsets)
+        check(_lib.lib().vga_hca_files_layout_for(arr, n, offs, fo.ctypes.data_as(i64p), io.ctypes.data_as(i64p), C.byref(tot)))
+        return fo[:n], io[:n], tot
+
+    @classmethod
+    def from_infos(cls, infos, image_offsets=None, keys=None, tables=None, frame_offsets=None):
+        """A set for reading, from the vga_hca_file_info of every file (parse()); image_offsets: any byte offsets, or None for
+        images packed as write_device packs them; keys: one index into `tables` (decryption tables) per file, -1 for none"""
+        infos = list(infos)
+        n = len(infos)
+        ptrs = (C.c_void_p * max(n, 1))(*[C.addressof(i) if i is not None else None for i in infos])
+        keep, offs = _i64_or_none(image_offsets)
+        keep_f, foffs = _i64_or_none(frame_offsets)
+        keep_t, tp, nt = _tables_or_none(tables)
+        kp = None
+        if keys is not None:
+            keep_k = np.ascontiguousarray(list(keys) + [0], dtype=np.int32)
+            kp = keep_k.ctypes.data_as(C.POINTER(C.c_int))
+        h = C.c_void_p()
+        check(_lib.lib().vga_hca_files_create_from_infos(ptrs, n, offs, kp, tp, nt, foffs, C.byref(h)))
+        s = cls(_handle=h)
+        s.image_sizes = [i.frames_offset + i.hca.frame_count * i.hca.frame_size for i in infos]
+        return s
+
+    @staticmethod
+    def _items(call, head, general):
+        count = C.c_int64()
+        check(call(*head, int(general), None, 0, C.byref(count)))
+        items = (_lib.HcaFilesItemC * max(count.value, 1))()
+        check(call(*head, int(general), items, count.value, C.byref(count)))
+        return list(items[:count.value])
+
+    @classmethod
+    def write_items(cls, files, frame_offsets=None, general=False):
+        """the work items of vga_hca_write_device_v on such a set (_lib.HcaFilesItemC), host only"""
+        arr, n = cls._files_array(files)
+        keep, offs = _i64_or_none(frame_offsets)
+        return cls._items(_lib.lib().vga_hca_files_write_items_for, (arr, n, offs), general)
+
+    @classmethod
+    def read_items(cls, infos, image_offsets=None, frame_offsets=None, general=False):
+        """the work items of vga_hca_read_device_v on a set of such infos, host only"""
+        infos = list(infos)
+        ptrs = (C.c_void_p * max(len(infos), 1))(*[C.addressof(i) for i in infos])
+        keep, offs = _i64_or_none(image_offsets)
+        keep_f, foffs = _i64_or_none(frame_offsets)
+        return cls._items(_lib.lib().vga_hca_files_read_items_for, (ptrs, len(infos), offs, foffs), general)
+
+    def close(self):
+        if self._h:
+            _lib.lib().vga_hca_files_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def stats(self):
+        """(span files, general files, span items, general items) of a call made by this thread now"""
+        out = (C.c_int64 * 4)()
+        check(_lib.lib().vga_hca_files_stats(self._h, out))
+        return tuple(out)
+
+    def write_device(self, frames, images, stream=None):
+        """vga_hca_write_device_v.  frames: uint8[totals.frame_bytes]; images: uint8[totals.image_bytes]"""
+        import torch
+        from .dsp import DspFileSet
+        ptr, t = DspFileSet._ptr, self.totals
+        check(_lib.lib().vga_hca_write_device_v(self._h, ptr(frames, torch.uint8, t.frame_bytes, "frames"),
+                                                ptr(images, torch.uint8, t.image_bytes, "images"), DspFileSet._stream(stream)))
+
+    def read_device(self, images, frames, bad_crc=None, stream=None):
+        """vga_hca_read_device_v (a set from from_infos): images -> the frames and, if given, the bad-CRC counts ADDED to
+        bad_crc (int32[files], zeroed by the caller)"""
+        import torch
+        from .dsp import DspFileSet
+        ptr, t = DspFileSet._ptr, self.totals
+        check(_lib.lib().vga_hca_read_device_v(self._h, ptr(images, torch.uint8, t.image_bytes, "images"),
+                                               ptr(frames, torch.uint8, t.frame_bytes, "frames"),
+                                               ptr(bad_crc, torch.int32, self.files, "bad_crc"), DspFileSet._stream(stream)))
+
+    def images(self, host_buffer):
+        """one `bytes` per file from the packed images (a device tensor or a numpy array); synchronises"""
+        host = host_buffer.cpu().numpy() if hasattr(host_buffer, "cpu") else np.asarray(host_buffer, dtype=np.uint8)
+        return [host[int(at):int(at) + int(size)].tobytes() for at, size in zip(self.image_offsets, self.image_sizes)]
+
+
+def _shape_class(h):
+    """what the streams of one crihca.RaggedHca must agree in (include/vgaudio_hip/hca_ragged.h)"""
+    return (h.channel_count, h.sample_rate, h.frame_size, h.min_resolution, h.max_resolution, h.track_count, h.channel_config,
+            h.total_band_count, h.base_band_count, h.stereo_band_count, h.bands_per_hfr_group, h.hfr_group_count, h.use_ath_curve)
+
+
+def write_files(pcm16_list, configuration=None):
+    """HcaWriter(configuration).GetFile(file) for a list of Pcm16Format files, on the device and without a launch per file or
+    per key: files that do not loop are grouped by shape class and one crihca.RaggedHca per class encodes them, a looping file
+    is encoded by vga_hca_encode_device into its own place, all of it at explicit offsets in one frames buffer; one HcaFileSet
+    over everything encrypts (configuration.EncryptionKey: every file gets its table, KeyType as encryption type and masked
+    chunk ids) and writes the images.  Returns one `bytes` per file, in the caller's order."""
+    import torch
+    from .crihca import RaggedHca
+    cfg = configuration or HcaConfiguration()
+    files = list(pcm16_list)
+    L = _lib.lib()
+    infos = []
+    for i, f in enumerate(files):
+        p = CriHcaParameters(Bitrate=cfg.Bitrate, LimitBitrate=cfg.LimitBitrate, ChannelCount=f.ChannelCount, SampleRate=f.SampleRate,
+                             SampleCount=f.SampleCount, Looping=bool(f.Looping), LoopStart=f.LoopStart if f.Looping else 0,
+                             LoopEnd=f.LoopEnd if f.Looping else 0)
+        if cfg.Quality != CriHcaQuality.NotSet:
+            p.Quality = cfg.Quality
+        c, h = p._c(), _lib.HcaInfoC()
+        try:
+            check(L.vga_hca_encoder_initialize(C.byref(c), C.byref(h)))
+        except _lib.VgaError as e:
+            raise type(e)("file %d: %s" % (i, e)) from None
+        infos.append(h)
+    key = cfg.EncryptionKey
+    enc_type, tables = (key.KeyType, [key.EncryptionTable]) if key is not None else (0, None)
+    groups, loops = {}, []
+    for i, h in enumerate(infos):
+        (loops.append(i) if h.looping else groups.setdefault(_shape_class(h), []).append(i))
+    order = [i for members in groups.values() for i in members] + loops
+    described = [_lib.HcaFileC(infos[i], None, 1.0, enc_type, int(key is not None), 0 if key is not None else -1) for i in order]
+    HcaFileSet.layout(described)                                      # every refusal of a file, before anything is allocated
+    if not files:
+        return []
+    ragged, s = [], None
+    try:
+        frames_at, offsets, jobs = 0, [], []
+        for members in groups.values():
+            r = RaggedHca([infos[i] for i in members])
+            host, row = np.zeros(max(r.totals.pcm_samples, 8), dtype=np.int16), 0
+            for i in members:
+                for ch in files[i].Channels:
+                    n = files[i].SampleCount
+                    host[r.pcm_row_offsets[row]:r.pcm_row_offsets[row] + n] = np.asarray(ch, dtype=np.int16)[:n]
+                    row += 1
+            ragged.append(r)
+            jobs.append((r, host, frames_at))
+            offsets += [frames_at + int(o) for o in r.frame_offsets]
+            frames_at += (r.totals.frame_bytes + 15) // 16 * 16
+        loop_jobs = []
+        for i in loops:
+            h, f = infos[i], files[i]
+            n = f.SampleCount
+            host = np.zeros((h.channel_count, max(n, 1)), dtype=np.int16)
+            for c, ch in enumerate(f.Channels):
+                host[c, :n] = np.asarray(ch, dtype=np.int16)[:n]
+            loop_jobs.append((h, host, n, frames_at))
+            offsets.append(frames_at)
+            frames_at += (h.frame_count * h.frame_size + 8 + 15) // 16 * 16
+        s = HcaFileSet(described, frame_offsets=offsets, tables=tables)
+        frames = torch.zeros(max(frames_at, s.totals.frame_bytes), dtype=torch.uint8, device="cuda")
+        images = torch.empty(s.totals.image_bytes, dtype=torch.uint8, device="cuda")
+        status = torch.zeros(len(files) + 1, dtype=torch.int32, device="cuda")
+        st, done, keep = C.c_void_p(torch.cuda.current_stream().cuda_stream), 0, []
+        for r, host, at in jobs:
+            pcm = torch.from_numpy(host).cuda()
+            keep.append(pcm)
+            if r.streams:
+                r.encode_device(pcm, frames[at:], status[done:])
+            done += r.streams
+        for h, host, n, at in loop_jobs:
+            pcm = torch.from_numpy(host).cuda()
+            keep.append(pcm)
+            check(L.vga_hca_encode_device(pcm.data_ptr(), pcm.numel(), pcm.shape[1], 1, n, C.byref(h), frames.data_ptr() + at,
+                                          (h.frame_count * h.frame_size + 8 + 1) // 2 * 2, status.data_ptr() + 4 * done, st))
+            done += 1
+        s.write_device(frames, images)
+        out = s.images(images)
+        flags = status.cpu().numpy()
+        for k, i in enumerate(order):
+            if flags[k]:
+                raise _lib.InvalidDataError("file %d: the encoder reports status %d" % (i, int(flags[k])))
+        result = [None] * len(files)
+        for k, i in enumerate(order):
+            result[i] = out[k]
+        return result
+    finally:
+        for r in ragged:
+            r.close()
+        if s is not None:
+            s.close()
+
+
+def read_files(list_of_bytes, Decrypt=True, EncryptionKey=None):
+    """HcaReader(Decrypt, EncryptionKey).ReadWithConfig(file) for a list of files: the headers are parsed on the host, all
+    frames are taken out of the images, CRC-checked and decrypted in one vga_hca_read_device_v call.  Returns
+    (formats, bad_crc): one CriHcaFormat per file, EncryptionType 0 where decrypted, and the bad-CRC frames per file.  A
+    type-56 file without a key is refused by name (FindKey synchronises and stays with the caller, HcaReader.Keys)."""
+    import torch
+    datas = [bytes(d) for d in list_of_bytes]
+    infos = [parse(d) for d in datas]
+    tables, keys, type1 = [], [], None
+    for i, info in enumerate(infos):
+        k = -1
+        if Decrypt and EncryptionKey is not None:
+            k = 0
+        elif Decrypt and info.encryption_type == 1:
+            k = type1 = len(tables) if type1 is None else type1
+        elif Decrypt and info.encryption_type == 56:
+            raise _lib.InvalidDataError("file %d: Cannot find key to decrypt HCA file." % i)
+        if k == len(tables):
+            tables.append((EncryptionKey if EncryptionKey is not None else CriHcaKey(CriHcaKey.Type1)).DecryptionTable)
+        keys.append(k)
+    s = HcaFileSet.from_infos(infos, keys=keys, tables=tables or None)
+    try:
+        if s.files == 0:
+            return [], []
+        host = np.zeros(s.totals.image_bytes, dtype=np.uint8)
+        for d, at, size in zip(datas, s.image_offsets, s.image_sizes):
+            host[int(at):int(at) + size] = np.frombuffer(d, dtype=np.uint8)[:size]
+        images = torch.from_numpy(host).cuda()
+        frames = torch.zeros(s.totals.frame_bytes, dtype=torch.uint8, device="cuda")
+        bad = torch.zeros(s.files, dtype=torch.int32, device="cuda")
+        s.read_device(images, frames, bad)
+        flat = frames.cpu().numpy()
+        out = []
+        for f, info in enumerate(infos):
+            hca = hca_info_of(info)
+            at, n = int(s.frame_offsets[f]), hca.FrameCount * hca.FrameSize
+            if keys[f] >= 0:
+                hca.EncryptionType = 0
+            out.append(CriHcaFormat(flat[at:at + n].copy().reshape(hca.FrameCount, hca.FrameSize), hca))
+        return out, [int(b) for b in bad.cpu().numpy()]
+    finally:
+        s.close()
