@@ -21,8 +21,12 @@ int vga_testing_force_open_seams_this_thread(int mode);
 
 /* GC-ADPCM encoder wave layout for calls made FROM THE CALLING THREAD: 0 = the launcher's choice (the product: 4 for
  * batches below ~512 channels, 8 from there on and for ragged batches); 8 = lane per (channel, predictor); 4 = lane per
- * (channel, predictor, scale candidate).  Both produce the same bytes.  Returns the previous value; other arguments leave
- * it unchanged. */
+ * (channel, predictor, scale candidate).  8 also names the workgroup shape: two encoder waves and a helper wave, sixteen
+ * channel slots.  1 = the (channel, predictor) lanes in the self-served shape -- one-wave workgroups of eight channel slots
+ * that take (group of eight, piece) items from a queue, each wave helper and encoder of its own channels -- which the
+ * launcher picks by itself from 2048 channels on and for ragged batches; it runs as persistent workgroups whatever
+ * vga_testing_gc_encoder_persistent_this_thread says.  All produce the same bytes.  Returns the previous value; other
+ * arguments leave it unchanged. */
 int vga_testing_gc_encoder_layout_this_thread(int channels_per_wave);
 /* GC-ADPCM coefficient-search kernel for calls made from the calling thread: 0 = the launcher's choice by channel count
  * (the product), 1 = one wave per channel, 2 = workgroups of four channels and a summing wave, 3 = the same five waves on
@@ -41,7 +45,9 @@ int vga_testing_gc_encoder_persistent_this_thread(int mode);
 /* The GC-ADPCM encoder's piece schedule (gc::plan_encode_pieces, vgaudio_amd/csrc/gc_encode_kernel.hip) for a device of
  * `cus` compute units: `groups` channel groups of sixteen whose longest channel has `frames` frames and whose longest
  * channels hold `group_frames` frames in all.  Host arithmetic, needs no GPU.  out5 = {pieces, big, nb, small, persistent}:
- * piece k begins at frame min(k, nb) * big + max(k - nb, 0) * small.  The pieces must cover `frames`.  Returns 0. */
+ * piece k begins at frame min(k, nb) * big + max(k - nb, 0) * small.  The pieces must cover `frames`.  With
+ * vga_testing_gc_encoder_layout_this_thread(1) in force: the schedule of the self-served shape (always persistent; the rounds
+ * of the two-size schedule counted in groups of eight on twelve workgroups per compute unit).  Returns 0. */
 int vga_testing_gc_plan_pieces(int cus, int groups, int frames, long long group_frames, int ragged, int *out5);
 
 /* Diagnostics of the GC-ADPCM encoder's data-dependent parts, summed over every launch of the process on the current

@@ -9,7 +9,11 @@ Prints static instruction counts per block of the HOT path of one frame (lane = 
 = 8 channel-frames = 112 samples), the cold block's path for a plain third trip, the helper wave's loop per tile, and the
 resulting lane-operations per sample with the measured rates (cold-block rate, short-pass share) filled in.
 
-    python tools/isa_budget_gc.py [--src other/gc_encode_kernel.hip] [-DNAME=VALUE ...] > profiles/rNN_gc_encode_isa_budget.md
+    python tools/isa_budget_gc.py [--src other/gc_encode_kernel.hip] [--shape self] [-DNAME=VALUE ...] > profiles/rNN_gc_encode_isa_budget.md
+
+--shape self (round 13): the same table for gc_encode_self_served_kernel<false> -- the one-wave workgroups that are helper and
+encoder of their eight channel slots -- and, in place of the helper wave's loop, the static counts of that kernel's tile
+boundary: the blocks of the tile loop outside the frame loop (next tile's loads, flush, the compute half of prepare).
 
 Since round 12 the listing is made with the product's own options for the file (vgaudio_amd/build.py FILE_FLAGS; until then
 with the common ones only), and the tool also counts the scratch instructions (spill stores and reloads) per block of the
@@ -66,6 +70,7 @@ def scratch_by_block(raw, name):
     b = next(i for i in range(a, len(raw)) if "s_endpgm" in raw[i])
     frame_hdr, tile_hdr, nested, tile_nested, where, lab = None, None, set(), set(), "prologue, seams, epilogue", None
     regions, inside = collections.OrderedDict(), []
+    tile_code = []                                                   # every instruction of the tile loop outside the frame loop
     for key in ("frame loop: the frame's pairs of passes", "frame loop: the cold block's passes", "frame loop: row reads, first scale, flags, tail, the cold block's other code",
                 "tile head (once per tile, outside the frame loop)", "prologue, seams, epilogue"):
         regions[key] = 0
@@ -101,7 +106,12 @@ def scratch_by_block(raw, name):
             regions[where] += 1
             if where.startswith("frame loop"):
                 inside.append("%s: %s" % (lab, raw[i].split(";")[0].strip()))
+        if where.startswith("tile head") and not m:
+            t = raw[i].split(";")[0].strip()
+            if t and not t.startswith(".") and not t.endswith(":"):
+                tile_code.append(t)
         i += 1
+    scratch_by_block.tile_code = tile_code
     return regions, inside, frame_hdr
 
 
@@ -143,7 +153,11 @@ def count(block):
 
 def main():
     RAW = listing()
-    L = kernel(RAW, "gc_encode_persistent_kernelILi8ELb0E")
+    self_shape = "--shape" in sys.argv and sys.argv[sys.argv.index("--shape") + 1] == "self"
+    uniform, ragged = (("gc_encode_self_served_kernelILb0E", "gc_encode_self_served_kernelILb1E") if self_shape
+                       else ("gc_encode_persistent_kernelILi8ELb0E", "gc_encode_persistent_kernelILi8ELb1E"))
+    nice_name = "gc_encode_self_served_kernel<%s>" if self_shape else "gc_encode_persistent_kernel<8, %s>"
+    L = kernel(RAW, uniform)
     cv = [i for i, l in enumerate(L) if l.startswith("v_cvt_pk_i16_i32")]
     labels = [i for i, l in enumerate(L) if l.endswith(":")]
     prev_label = lambda i: max(j for j in labels if j <= i)
@@ -188,8 +202,8 @@ def main():
             ("the frame's two passes without the f32 detour, 28 sample steps, and the test of what they vouch for", count(L[short_blk[0]:short_blk[1]])),
             ("the same with the conversions (30 % of the wave-frames take these instead)", count(L[normal_blk[0]:normal_blk[1]])),
             ("the flags, the error block, 8-predictor argmin (DPP), winner's history, 4 x ds_write_b128", count(L[normal_blk[1]:tail_end + 1]))]
-    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 12)\n")
-    print("`gc_encode_persistent_kernel<8, false>`, static counts from hipcc's gfx950 listing of `vgaudio_amd/csrc/gc_encode_kernel.hip`")
+    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 13)\n")
+    print("`" + nice_name % "false" + "`, static counts from hipcc's gfx950 listing of `vgaudio_amd/csrc/gc_encode_kernel.hip`")
     print("(`tools/isa_budget_gc.py`).  One wave-frame = 64 lanes = 8 channels x 8 predictors = 112 input samples.\n")
     print("| block of the hot frame | total | VALU | SALU | LDS | wait / nop |")
     print("|---|---:|---:|---:|---:|---:|")
@@ -215,9 +229,13 @@ def main():
         print("| %s | %.0f | %.0f |" % (name, v, v * 64 / 112))
     # scratch (spill stores and reloads) by where it stands, uniform and ragged instantiation
     print("\n## Registers and scratch instructions by block\n")
-    for nice, mangled in (("gc_encode_persistent_kernel<8, false>", "gc_encode_persistent_kernelILi8ELb0E"),
-                          ("gc_encode_persistent_kernel<8, true>", "gc_encode_persistent_kernelILi8ELb1E")):
+    for nice, mangled in ((nice_name % "false", uniform), (nice_name % "true", ragged)):
         regions, inside, hdr = scratch_by_block(RAW, mangled)
+        if self_shape:
+            c = count(scratch_by_block.tile_code)
+            print("`%s`, tile boundary (the blocks of the tile loop outside the frame loop, every branch counted once -- the partial last "
+                  "frame's byte loops among them): %d instructions, %d VALU, %d SALU, %d LDS, %d VMEM per tile of 8 frames x 8 channel slots.\n"
+                  % (nice, c["total"], c["VALU"], c["SALU"], c["LDS"], c["VMEM"]))
         res = resources(RAW, mangled)
         print("`%s`: %d VGPRs, %d waves per SIMD, %d B of scratch per lane, %d B of LDS per workgroup; frame loop header `.L%s`.\n"
               % (nice, res.get("NumVgprs", -1), res.get("Occupancy", -1), res.get("ScratchSize", -1), res.get("LDSByteSize", -1), hdr))
@@ -229,8 +247,28 @@ def main():
         for t in inside:
             print("* in the frame loop: `%s`" % t)
     if "--src" not in sys.argv and not any(a.startswith("-D") for a in sys.argv[1:]):
-        print(TEXT)
+        print(TEXT_SELF if self_shape else TEXT)
 
+
+TEXT_SELF = """
+## What the budget says (round 13, written before the GPU run)
+
+* The frame loop is the 2 + 1 shape's, instruction for instruction: row block 33, passes 276 / 321, tail 37 VALU, encoder role
+  436 VALU per wave-frame (`gc_encode_persistent_kernel<8, false>` from the same source reads the same, 166 VGPRs).
+* The tile boundary stands where the helper wave's loop stood.  A tile is 8 frames x 8 channel slots = 8 wave-frames; the helper's
+  tile of 4 frames x 16 slots is 8 wave-frames as well: 762 VALU there (95 per wave-frame), at most 871 here (109 per wave-frame;
+  the static count holds the partial last frame's byte loops and both sides of every branch, a full tile executes fewer).  What
+  is new in it: eight `ds_bpermute` for the coefficient pairs of the helper role, the lane's slot address once more, and the
+  clamped frame index formed twice (load and compute).
+* 167 VGPRs with the next tile's seven dwords held across the frame loop, no scratch anywhere in the kernel, 12 612 B of LDS
+  per workgroup: twelve workgroups are 151 344 B of the compute unit's 163 840 (13 312 B each if the allocation is in steps
+  of 512 B: 159 744).
+* Prediction, written down before the GPU run.  Instructions per launch: encoder role unchanged, helper role 95 -> 100-109 per
+  wave-frame, so SQ_INSTS_VALU +1 to +2.6 % (531 -> 536-545 per wave-frame).  Time goes as instructions / busy fraction: if three
+  like waves per SIMD lift SQ_ACTIVE_INST_VALU / issue slots from 0.90 to 0.97 the launch is 112 ms x 1.026 x 0.90 / 0.97 = 106.6 ms
+  at the worst instruction count (-5 ms) and 105 ms at the best; if the busy fraction does not move, the launch is 1-3 ms SLOWER
+  and the shape stays behind the test hook.  Measured: LABNOTES 18.
+"""
 
 TEXT = """
 ## What the budget says (round 12)

@@ -13,7 +13,8 @@ int vga_testing_gc_plan_pieces(int cus, int groups, int frames, long long group_
     if (!out5 || cus <= 0 || groups <= 0 || frames <= 0) return -1;
     bool persistent = false;
     gc::Pieces seg;
-    const int segments = gc::plan_encode_pieces_on(cus, groups, frames, group_frames, ragged != 0, &persistent, &seg);
+    const int segments = gc::plan_encode_pieces_on(cus, groups, frames, group_frames, ragged != 0, &persistent, &seg,
+                                                     encoder_layout() == 1 ? 1 : 8);   // (1: the schedule of the self-served shape)
     out5[0] = segments;
     out5[1] = seg.big;
     out5[2] = seg.nb;

@@ -69,7 +69,7 @@ struct RaggedShape : RaggedLayout {
             solo_channels = ragged_solo_count(by_length.data(), n, total_frames, device_cu_count(), &solo_usable);
             const int groups = (int)group_frames.size();
             const int64_t work = std::accumulate(group_frames.begin(), group_frames.end(), (int64_t)0);
-            segments = plan_encode_pieces(groups, (max_length + 13) / 14, work, true, &persistent, &seg);
+            segments = plan_encode_pieces(groups, (max_length + 13) / 14, work, true, &persistent, &seg, encoder_plan_layout(groups, true));
             if (persistent && groups < (1 << 20) && segments <= 4096) {
                 struct Item { int size, y, g; };
                 std::vector<Item> list;

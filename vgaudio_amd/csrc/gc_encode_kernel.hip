@@ -25,6 +25,7 @@
 #include "gc_encode_core.hpp"
 #include "gcadpcm_kernels.hpp"
 #include "seams.hpp"
+#include "gc_plan8.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -128,10 +129,18 @@ constexpr int ENC_THREADS = 64 * (SW + 1);
 //   CPW = 8: lane = (channel, predictor) -- candidate B (s1 + 1) and candidate A (s1) run one after the other in the
 //            same lane.  Twice the channels share every per-frame fixed cost (row reads, pre-scan, resolution,
 //            argmin, the cold block's pass), which is worth more than the second pass costs: LABNOTES.md 4.1.
-template <int CPW>
+// Round 13, SELF (CPW = 8 only): the self-served shape -- a workgroup is ONE wave that is encoder and helper of its eight
+// channel slots in turn: helper role lane = (slot = lane >> 3, frame = lane & 7), encoder role (slot = lane >> 3, predictor =
+// lane & 7); one tile buffer, no workgroup barrier, no issue priority.  All waves of a SIMD are then alike (three at 168
+// VGPRs, by counting: twelve workgroups per CU), and each has its tile boundary's work to issue where the others' chains wait.
+template <int CPW, bool SELF = false>
 struct Lay {
-    static constexpr int CS = CPW * SW;    // channel slots per workgroup
+    static_assert(!SELF || CPW == 8, "the self-served shape is the (channel, predictor) layout");
+    static constexpr int EW = SELF ? 1 : SW;   // encoder waves per workgroup
+    static constexpr int CS = CPW * EW;    // channel slots per workgroup
     static constexpr int TF = 64 / CS;     // frames per tile: one helper lane per (channel slot, frame)
+    static constexpr int THREADS = SELF ? 64 : ENC_THREADS;
+    static constexpr int BUFS = SELF ? 1 : 2;  // tile buffers: the wave that fills the one of SELF is the wave that drains it
 };
 // Round 12: everything a (channel slot, frame) owns in LDS -- the helper's row, its pre-scan words and the winner's record --
 // is ONE 192-byte slot, so that an encoder lane reaches all of it from one address register with immediate offsets (the
@@ -276,7 +285,7 @@ ColdOut encode_frame_cold(ColdState st, PassOutB r, int final_sp, int fin)
 // encoding (clamped loads, nothing flushed) with its history frozen.
 // One (channel group, time piece) = what a workgroup of the plain launch does: gc_encode_kernel calls it once with its
 // block indices, gc_encode_persistent_kernel once per item it takes from the queue.
-template <bool REPAIR, int CPW, bool RAGGED>
+template <bool REPAIR, int CPW, bool RAGGED, bool SELF = false>
 __device__ __forceinline__ void gc_encode_piece(
     const int bx, const int by,
     const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const Pieces seg,
@@ -289,7 +298,8 @@ __device__ __forceinline__ void gc_encode_piece(
     // starting from seg_state of the piece before, which is the real history for all four (every seam before it
     // closed).  Workgroups without such a channel leave at once.
     constexpr bool repair = REPAIR;
-    constexpr int CS = Lay<CPW>::CS, TF = Lay<CPW>::TF;
+    constexpr int CS = Lay<CPW, SELF>::CS, TF = Lay<CPW, SELF>::TF, BUFS = Lay<CPW, SELF>::BUFS;
+    static_assert(!(SELF && REPAIR), "the repair launch keeps the 2 + 1 shape");
     using GcTile = GcTileT<CS, TF>;
     int64_t first_frame = seg.first(by);
     int repair_piece = 0;
@@ -319,13 +329,13 @@ __device__ __forceinline__ void gc_encode_piece(
     using Slot = typename GcTile::Slot;
     static_assert(TF % 2 == 0, "the frame loop takes a tile's frames in pairs");
     // (`end`: what the row reads one frame past the last channel slot's last pair land in; see the frame loop)
-    struct Tiles { GcTile t[2]; Slot end; };
+    struct Tiles { GcTile t[BUFS]; Slot end; };
     __shared__ Tiles s_tiles;
-    GcTile (&s_tile)[2] = s_tiles.t;
-    __shared__ int s_ncold[SW];
+    GcTile (&s_tile)[BUFS] = s_tiles.t;
+    __shared__ int s_ncold[Lay<CPW, SELF>::EW];
     const int tid = threadIdx.x;
-    const int wave = tid >> 6;
-    const bool helper = wave == SW;
+    const int wave = SELF ? 0 : tid >> 6;
+    const bool helper = !SELF && wave == SW;
     const int lane = tid & 63;
     // encoder wave: CPW channels x 8 predictors (x 2 candidates when CPW = 4); helper wave: CS channel slots x TF frames
     constexpr int LPC = 64 / CPW;                          // lanes per channel: 16 or 8
@@ -346,6 +356,87 @@ __device__ __forceinline__ void gc_encode_piece(
     const int frames_wg = RAGGED ? (piece_samples_of(total_wg) + 13) / 14 : frames;
     const int tiles = (frames_wg + TF - 1) / TF;
 
+    // ---------------------------------------------------------------- the helper role (a wave of its own, or SELF: this wave)
+    // load_frame: the lane's frame of the tile from global memory, frame index clamped: as ints and as packed pairs
+    // (in[2i], in[2i+1]) -- the self-served shape keeps the pairs alone across a tile's frames and unpacks them again
+    auto load_frame = [&](int tile, uint32_t (&w)[7], int (&in)[14]) __attribute__((always_inline)) {
+        const int fr = RAGGED ? imax(imin(tile * TF + hfr, frames - 1), 0) : imin(tile * TF + hfr, frames - 1);
+        if (fr < full_frames) {
+            const uint32_t *p32 = reinterpret_cast<const uint32_t *>(src + (int64_t)fr * 14);
+#pragma unroll
+            for (int i = 0; i < 7; i++) w[i] = p32[i];
+#pragma unroll
+            for (int i = 0; i < 7; i++) {
+                in[2 * i] = (int)(int16_t)(w[i] & 0xFFFF);
+                in[2 * i + 1] = (int)w[i] >> 16;
+            }
+        } else {                                   // zero-padded partial last frame (:32-33)
+#pragma unroll
+            for (int s = 0; s < 14; s++) in[s] = (s < tail) ? (int)src[(int64_t)fr * 14 + s] : 0;
+#pragma unroll
+            for (int i = 0; i < 7; i++) w[i] = (uint32_t)(in[2 * i] & 0xFFFF) | ((uint32_t)in[2 * i + 1] << 16);
+        }
+    };
+    // prepare_from: everything of the frame that depends on input samples only, into the lane's LDS slot
+    // (cpk[p]: (c1, c0) of predictor p as a packed pair, low half c1)
+    auto prepare_from = [&](int tile, const uint32_t (&w)[7], const int (&in)[14], const uint32_t (&cpk)[8]) __attribute__((always_inline)) {
+        Slot &T = s_tile[tile & (BUFS - 1)].g[grp].f[hfr];
+        uint4 *xr = reinterpret_cast<uint4 *>(&T.xw[0]);   // the pairs as loaded (the ints: in2048p and the pre-scan)
+        xr[0] = make_uint4(w[0], w[1], w[2], w[3]);
+        xr[1] = make_uint4(w[4], w[5], w[6], (!RAGGED || tile * TF + hfr < frames) ? 1u : 0u);   // (the spare dword: slot_has_frame)
+        int4 *qr = reinterpret_cast<int4 *>(&T.in2048p[0]);
+        qr[0] = make_int4(pass_b_row(in[0]), pass_b_row(in[1]), pass_b_row(in[2]), pass_b_row(in[3]));
+        qr[1] = make_int4(pass_b_row(in[4]), pass_b_row(in[5]), pass_b_row(in[6]), pass_b_row(in[7]));
+        qr[2] = make_int4(pass_b_row(in[8]), pass_b_row(in[9]), pass_b_row(in[10]), pass_b_row(in[11]));
+        qr[3] = make_int4(pass_b_row(in[12]), pass_b_row(in[13]), 0, 0);
+        // pre-scan distances of samples 2..13 (:107-115): predicted = (in[k]*c1 + in[k+1]*c0) / 2048 for the
+        // pair starting at k = s - 2.  One v_dot2c_i32_i16 per (predictor, sample): the pairs at even k are
+        // the loaded dwords, the pairs at odd k one v_alignbit each (shared by the 8 predictors); the
+        // wrap of int32 is the reference's (unchecked arithmetic).
+        uint32_t pair[12];
+#pragma unroll
+        for (int k = 0; k < 12; k++)
+            pair[k] = (k & 1) ? __builtin_amdgcn_alignbit(w[(k + 1) / 2], w[(k - 1) / 2], 16) : w[k / 2];
+        uint32_t pre[8];
+#pragma unroll
+        for (int p = 0; p < 8; p++) {
+            int dmax = 0, dmin = 0;
+#ifdef VGA_GC_ABLATE_HELPER_PRESCAN                                  // timing only: what the helper's 96 distances per frame cost the launch
+            dmax = in[2 + p] & 1023;
+            dmin = -(in[3 + p] & 1023);
+#else
+#pragma unroll
+            for (int k = 0; k < 12; k++) {
+                const int predicted = div2048(__builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, pair[k]),
+                                                                     __builtin_bit_cast(short2v, cpk[p]), 0, false));
+                const int d = in[k + 2] - predicted;
+                dmax = imax(dmax, d);
+                dmin = imin(dmin, d);
+            }
+#endif
+            pre[p] = (uint32_t)(clamp16i(dmax) & 0xFFFF) | ((uint32_t)clamp16i(dmin) << 16);
+        }
+        uint4 *pr = reinterpret_cast<uint4 *>(&T.pre[0]);
+        pr[0] = make_uint4(pre[0], pre[1], pre[2], pre[3]);
+        pr[1] = make_uint4(pre[4], pre[5], pre[6], pre[7]);
+    };
+    auto flush = [&](int tile) __attribute__((always_inline)) {
+        const int fr = tile * TF + hfr;
+        if (!live || fr >= frames) return;
+        const int4 *rec = &s_tile[tile & (BUFS - 1)].g[grp].f[hfr].out[0];
+        const int4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+        const int q[14] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, r3.x, r3.y};
+        uint2 v;
+        pack_frame_mod16(q, r3.z, r3.w, v.x, v.y);   // the record holds q - Z from the hot pass, q from the reference's loop: alike mod 16
+        if (fr < full_frames) {
+            *reinterpret_cast<uint2 *>(dst + (int64_t)fr * 8) = v;
+        } else {
+            // partial last frame: SampleCountToByteCount(tail) bytes (:38)
+            const int nbytes = (tail + 2 + 1) / 2;
+            const uint64_t both = ((uint64_t)v.y << 32) | v.x;
+            for (int b = 0; b < nbytes; b++) dst[(int64_t)fr * 8 + b] = (uint8_t)(both >> (8 * b));
+        }
+    };
     if (helper) {
         // ---------------------------------------------------------------- helper wave
         __builtin_amdgcn_s_setprio(VGA_GC_HELPER_PRIO);
@@ -354,80 +445,10 @@ __device__ __forceinline__ void gc_encode_piece(
         for (int p = 0; p < 8; p++)
             cpk[p] = (uint32_t)(uint16_t)coefs[ch * 16 + 2 * p + 1] | ((uint32_t)(uint16_t)coefs[ch * 16 + 2 * p] << 16);
         auto prepare = [&](int tile) {
-            const int fr = RAGGED ? imax(imin(tile * TF + hfr, frames - 1), 0) : imin(tile * TF + hfr, frames - 1);
+            uint32_t w[7];
             int in[14];
-            uint32_t w[7];                             // the frame as packed pairs (in[2i], in[2i+1])
-            if (fr < full_frames) {
-                const uint32_t *p32 = reinterpret_cast<const uint32_t *>(src + (int64_t)fr * 14);
-#pragma unroll
-                for (int i = 0; i < 7; i++) w[i] = p32[i];
-#pragma unroll
-                for (int i = 0; i < 7; i++) {
-                    in[2 * i] = (int)(int16_t)(w[i] & 0xFFFF);
-                    in[2 * i + 1] = (int)w[i] >> 16;
-                }
-            } else {                                   // zero-padded partial last frame (:32-33)
-#pragma unroll
-                for (int s = 0; s < 14; s++) in[s] = (s < tail) ? (int)src[(int64_t)fr * 14 + s] : 0;
-#pragma unroll
-                for (int i = 0; i < 7; i++) w[i] = (uint32_t)(in[2 * i] & 0xFFFF) | ((uint32_t)in[2 * i + 1] << 16);
-            }
-            Slot &T = s_tile[tile & 1].g[grp].f[hfr];
-            uint4 *xr = reinterpret_cast<uint4 *>(&T.xw[0]);   // the pairs as loaded (the ints: in2048p and the pre-scan)
-            xr[0] = make_uint4(w[0], w[1], w[2], w[3]);
-            xr[1] = make_uint4(w[4], w[5], w[6], (!RAGGED || tile * TF + hfr < frames) ? 1u : 0u);   // (the spare dword: slot_has_frame)
-            int4 *qr = reinterpret_cast<int4 *>(&T.in2048p[0]);
-            qr[0] = make_int4(pass_b_row(in[0]), pass_b_row(in[1]), pass_b_row(in[2]), pass_b_row(in[3]));
-            qr[1] = make_int4(pass_b_row(in[4]), pass_b_row(in[5]), pass_b_row(in[6]), pass_b_row(in[7]));
-            qr[2] = make_int4(pass_b_row(in[8]), pass_b_row(in[9]), pass_b_row(in[10]), pass_b_row(in[11]));
-            qr[3] = make_int4(pass_b_row(in[12]), pass_b_row(in[13]), 0, 0);
-            // pre-scan distances of samples 2..13 (:107-115): predicted = (in[k]*c1 + in[k+1]*c0) / 2048 for the
-            // pair starting at k = s - 2.  One v_dot2c_i32_i16 per (predictor, sample): the pairs at even k are
-            // the loaded dwords, the pairs at odd k one v_alignbit each (shared by the 8 predictors); the
-            // wrap of int32 is the reference's (unchecked arithmetic).
-            uint32_t pair[12];
-#pragma unroll
-            for (int k = 0; k < 12; k++)
-                pair[k] = (k & 1) ? __builtin_amdgcn_alignbit(w[(k + 1) / 2], w[(k - 1) / 2], 16) : w[k / 2];
-            uint32_t pre[8];
-#pragma unroll
-            for (int p = 0; p < 8; p++) {
-                int dmax = 0, dmin = 0;
-#ifdef VGA_GC_ABLATE_HELPER_PRESCAN                                  // timing only: what the helper's 96 distances per frame cost the launch
-                dmax = in[2 + p] & 1023;
-                dmin = -(in[3 + p] & 1023);
-#else
-#pragma unroll
-                for (int k = 0; k < 12; k++) {
-                    const int predicted = div2048(__builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, pair[k]),
-                                                                         __builtin_bit_cast(short2v, cpk[p]), 0, false));
-                    const int d = in[k + 2] - predicted;
-                    dmax = imax(dmax, d);
-                    dmin = imin(dmin, d);
-                }
-#endif
-                pre[p] = (uint32_t)(clamp16i(dmax) & 0xFFFF) | ((uint32_t)clamp16i(dmin) << 16);
-            }
-            uint4 *pr = reinterpret_cast<uint4 *>(&T.pre[0]);
-            pr[0] = make_uint4(pre[0], pre[1], pre[2], pre[3]);
-            pr[1] = make_uint4(pre[4], pre[5], pre[6], pre[7]);
-        };
-        auto flush = [&](int tile) {
-            const int fr = tile * TF + hfr;
-            if (!live || fr >= frames) return;
-            const int4 *rec = &s_tile[tile & 1].g[grp].f[hfr].out[0];
-            const int4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
-            const int q[14] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, r3.x, r3.y};
-            uint2 v;
-            pack_frame_mod16(q, r3.z, r3.w, v.x, v.y);   // the record holds q - Z from the hot pass, q from the reference's loop: alike mod 16
-            if (fr < full_frames) {
-                *reinterpret_cast<uint2 *>(dst + (int64_t)fr * 8) = v;
-            } else {
-                // partial last frame: SampleCountToByteCount(tail) bytes (:38)
-                const int nbytes = (tail + 2 + 1) / 2;
-                const uint64_t both = ((uint64_t)v.y << 32) | v.x;
-                for (int b = 0; b < nbytes; b++) dst[(int64_t)fr * 8 + b] = (uint8_t)(both >> (8 * b));
-            }
+            load_frame(tile, w, in);
+            prepare_from(tile, w, in, cpk);
         };
         if (tiles > 0) prepare(0);
         __syncthreads();
@@ -441,7 +462,7 @@ __device__ __forceinline__ void gc_encode_piece(
     }
 
     // -------------------------------------------------------------------- serial (encoder) wave
-    __builtin_amdgcn_s_setprio(VGA_GC_ENCODER_PRIO);   // its latency is the kernel's run time: win every issue arbitration
+    if constexpr (!SELF) __builtin_amdgcn_s_setprio(VGA_GC_ENCODER_PRIO);   // its latency is the kernel's run time: win every issue arbitration
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);   // (wave-uniform: a scalar register, for the tile heads)
     int p = CPW == 4 ? l16 >> 1 : l16;
     const bool cand_b = CPW == 4 && (l16 & 1) != 0;
@@ -797,9 +818,9 @@ __device__ __forceinline__ void gc_encode_piece(
 #ifdef VGA_DEBUG_TIMESTAMPS
     if (!repair && tid == 0 && gridDim.y != 1) g_vga_enc_ts[2 * ((blockIdx.y * gridDim.x + blockIdx.x) & 32767)] = wall_clock64();
 #endif
-    __syncthreads();                                   // tile 0 prepared
-    for (int tile = 0; tile < tiles; tile++) {
-        const int buf = tile & 1;
+    // a tile's frames, by the encoder role
+    auto encode_tile = [&](int tile) __attribute__((always_inline)) {
+        const int buf = tile & (BUFS - 1);
         const int nf = imin(TF, frames_wg - tile * TF);
 #ifndef VGA_GC_NO_TILE_REDERIVE                        // (timing-only switch, tools/build_variants.sh)
         {
@@ -833,7 +854,50 @@ __device__ __forceinline__ void gc_encode_piece(
                 encode_one(RB, S[1], pre_b);
             }
         }
+    };
+    if constexpr (SELF) {
+        // ---- the self-served tile loop: no other wave touches this workgroup's LDS, and one wave's LDS operations complete
+        // in the order it issued them -- a fence of wavefront scope (no instruction: the compiler keeps its LDS accesses on
+        // either side) and s_waitcnt lgkmcnt(0) stand where the 2 + 1 shape has its workgroup barrier.
+        auto own_lds_done = [&]() __attribute__((always_inline)) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0); vmcnt and expcnt left alone
+        };
+        // the helper role's coefficient pairs: predictor q's pair is what the encoder role's lane (slot, q) holds
+        auto prepare_self = [&](int tile, const uint32_t (&w)[7]) __attribute__((always_inline)) {
+            uint32_t cp8[8];
+#pragma unroll
+            for (int q = 0; q < 8; q++) cp8[q] = (uint32_t)__shfl((int)cpk, (lane & 56) | q);
+            int in[14];
+#pragma unroll
+            for (int i = 0; i < 7; i++) {
+                in[2 * i] = (int)(int16_t)(w[i] & 0xFFFF);
+                in[2 * i + 1] = (int)w[i] >> 16;
+            }
+            prepare_from(tile, w, in, cp8);
+        };
+        uint32_t wn[7];                                    // the lane's frame of the NEXT tile, loaded a tile ahead
+        int unused[14];
+        if (tiles > 0) {
+            load_frame(0, wn, unused);
+            prepare_self(0, wn);
+            own_lds_done();
+        }
+        for (int tile = 0; tile < tiles; tile++) {
+            const bool more = tile + 1 < tiles;
+            if (more) load_frame(tile + 1, wn, unused);    // in flight during the tile's frames
+            encode_tile(tile);
+            own_lds_done();                                // the winners' records
+            flush(tile);
+            if (more) prepare_self(tile + 1, wn);
+            own_lds_done();
+        }
+    } else {
+    __syncthreads();                                   // tile 0 prepared
+    for (int tile = 0; tile < tiles; tile++) {
+        encode_tile(tile);
         __syncthreads();                               // tile done: helper may flush it and refill this buffer later
+    }
     }
     if (seg_state && !repair && live && l16 == 0) {   // one lane per channel
         int16_t *st = seg_state + ((int64_t)by * nch + ch) * 2;
@@ -1245,6 +1309,67 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(VGA
     }
 }
 
+// Round 13: the same queue for the self-served shape (Lay<8, true>): a workgroup is one wave, items are (group of EIGHT
+// channel slots, piece) -- gc_plan8.hpp -- and cus x 12 workgroups put three waves on every SIMD, all alike.  The piece
+// schedule is the one planned for groups of sixteen, so a channel has the seams it has with the 2 + 1 shape; they close on
+// the one wave (seam_piece<8> is per wave).  What was shared through LDS is a readfirstlane.  As there, no wave ever waits
+// for another workgroup.
+template <bool RAGGED>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void gc_encode_self_served_kernel(
+    const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const Pieces seg,
+    const int16_t *__restrict__ coefs, const int16_t *__restrict__ hist1,
+    const int16_t *__restrict__ hist2, uint8_t *adpcm, int64_t adpcm_pitch, int16_t *seg_state,
+    const Ragged rg, int groups, int items, int segments, int *__restrict__ queue, int *__restrict__ seam_count, int *first_open,
+    int *seam_flag, int *seam_end, int force_open)
+{
+    constexpr int CS = PLAN8_SLOTS;
+    static_assert(Lay<8, true>::CS == CS && Lay<8, true>::THREADS == 64, "one wave, eight channel slots");
+    const int lane = threadIdx.x;
+    const uint32_t *host_items = RAGGED ? rg.items : nullptr;
+#ifdef VGA_DEBUG_TIMESTAMPS
+    if (lane == 0) g_vga_enc_ts[2 * (blockIdx.x & 32767)] = wall_clock64();
+#endif
+    for (;;) {
+        int item = 0;
+        if (lane == 0) item = atomicAdd(queue, 1);
+        item = __builtin_amdgcn_readfirstlane(item);
+        if (item >= items) {
+#ifdef VGA_DEBUG_TIMESTAMPS
+            if (lane == 0) g_vga_enc_ts[2 * (blockIdx.x & 32767) + 1] = wall_clock64();
+#endif
+            return;
+        }
+        int g, y;
+        if (!plan8_item(item, groups, nch, host_items, g, y)) continue;
+        gc_encode_piece<false, 8, RAGGED, true>(g, y, pcm, pcm_pitch, nch, total_samples, seg, coefs, hist1, hist2, adpcm, adpcm_pitch,
+                                                seg_state, (const int *)nullptr, rg);
+        if (segments <= 1) continue;
+        // ---- the seams at this piece's ends
+        __threadfence();                               // this wave's bytes and piece state are out before it says so
+        int at_start = 0, at_end = 0;
+        if (lane == 0) {
+            // (pieces past the end of the group's longest channel do not exist: nobody waits for them)
+            const int total_wg = RAGGED ? rg.length[rg.order[g * CS]] : total_samples;
+            auto exists = [&](int piece) { return piece < segments && seg.first(piece) * 14 < total_wg; };
+            if (exists(y)) {
+                if (y >= 1 && atomicAdd(&seam_count[(int64_t)(y - 1) * groups + g], 1) == 1) at_start = y;
+                if (exists(y + 1) && atomicAdd(&seam_count[(int64_t)y * groups + g], 1) == 1) at_end = y + 1;
+            }
+        }
+        const int seam_a = __builtin_amdgcn_readfirstlane(at_start), seam_b = __builtin_amdgcn_readfirstlane(at_end);
+        if ((seam_a | seam_b) != 0) {
+            __threadfence();                           // the other workgroup's stores, before anything of them is read
+            const int slot = g * CS + (lane >> 3);
+            if (seam_a)
+                seam_piece<8>(slot, seam_a, lane, pcm, pcm_pitch, nch, total_samples, seg, coefs, adpcm, adpcm_pitch, seg_state,
+                           first_open, seam_flag, seam_end, force_open, rg);
+            if (seam_b)
+                seam_piece<8>(slot, seam_b, lane, pcm, pcm_pitch, nch, total_samples, seg, coefs, adpcm, adpcm_pitch, seg_state,
+                           first_open, seam_flag, seam_end, force_open, rg);
+        }
+    }
+}
+
 // The channels with an open seam, piece after piece: where the true history V at the start of piece k is not the one the
 // seam launch assumed there (T = seg_state[k - 1]), the piece's bytes are the run from T, so the same seam_run from V next
 // to a replay from T finds where the two meet -- as a rule a few frames in, and the chain ends unless a later seam of the
@@ -1348,6 +1473,12 @@ constexpr int PERSISTENT_ITEMS_PER_WORKGROUP = 4;      // uniform pieces (the te
 constexpr int PERSISTENT_BIG_ROUNDS = 3;       // a workgroup's share of the frames in this many big items ...
 constexpr int PERSISTENT_SMALL_ROUNDS = 2;     // ... followed by this many rounds of short items
 constexpr int PERSISTENT_SMALL_FRAMES = 4096;  // ... of this many frames
+// The self-served shape (uniform batches): four big rounds and ONE round of short items -- its items are half the size, and
+// every short piece more is a seam that a slow-closing channel can leave open for the chain launch (one sweep on the
+// synthetic set, profiles/r13_encode_ab.log: big,small rounds 4,1 108.4 ms; 2,1 108.8; 2,2 109.3; 3,1 109.4; 5,2 112.8;
+// 4,2 114.2; 4,3 116.5; 3,3 117.1; 3,2 115.7-117.7; the 2 + 1 shape's pieces as they are 110.5-110.8; parent 111.4-111.8).
+constexpr int SELF_SERVED_BIG_ROUNDS = 4;
+constexpr int SELF_SERVED_SMALL_ROUNDS = 1;
 constexpr int MAX_PIECES = 1024;               // what encode_scratch_bytes() and the ragged item list (capi_gcadpcm_v.hip) are sized for
 
 // The piece schedule (see Pieces, gcadpcm_kernels.hpp).  Plain grid: as many equal pieces as put two encoder waves on
@@ -1381,8 +1512,12 @@ int plan_encode_pieces_on(int cus, int groups, int frames, int64_t group_frames,
 {
     // persistent workgroups taking (channel group, piece) items from a queue (gc_encode_persistent_kernel) once the batch
     // has enough channel groups; test hook: 1 = never, 2 = always
+    // layout 1, the self-served shape (forced by the test hook or the launcher's choice): it exists as persistent workgroups
+    // only, and its queue holds groups of EIGHT channel slots for twelve workgroups per compute unit -- the rounds below are
+    // counted in those (`groups` stays the count of groups of sixteen)
+    const bool self = layout == 1;
     const int pmode = encoder_persistent_mode();
-    const bool persistent = layout != 4 && (pmode == 2 || (pmode == 0 && (ragged || groups * PERSISTENT_MIN_GROUPS_FACTOR >= cus * 4)));
+    const bool persistent = self || (layout != 4 && (pmode == 2 || (pmode == 0 && (ragged || groups * PERSISTENT_MIN_GROUPS_FACTOR >= cus * 4))));
     int segments = cus * 4 / (groups > 0 ? groups : 1);   // = SW encoder waves on every SIMD
     if (persistent && (pmode == 2 || ragged)) segments = (cus * 4 * PERSISTENT_ITEMS_PER_WORKGROUP + groups - 1) / groups;
     if (ragged) {
@@ -1404,14 +1539,16 @@ int plan_encode_pieces_on(int cus, int groups, int frames, int64_t group_frames,
         (ragged || groups * PERSISTENT_SCHEDULE_GROUPS_FACTOR >= cus * 4)) {
         // (ragged batches, mixed-lengths set of bench.py: 4 rounds 151.7 ms, 3: 158.2, 6: 154.5, 8: 169.5; profiles/r04_a_ragged_schedules.log)
         int big_rounds = ragged ? PERSISTENT_BIG_ROUNDS + 1 : PERSISTENT_BIG_ROUNDS, small_rounds = PERSISTENT_SMALL_ROUNDS, small = PERSISTENT_SMALL_FRAMES;
+        if (self && !ragged) { big_rounds = SELF_SERVED_BIG_ROUNDS; small_rounds = SELF_SERVED_SMALL_ROUNDS; }   // (ragged: not swept, kept)
 #ifdef VGA_TUNING   // tools/build_variants.sh only: the product never reads its schedule from the environment
         if (const char *e = std::getenv("VGA_HIP_GC_SCHEDULE")) std::sscanf(e, "%d,%d,%d", &big_rounds, &small_rounds, &small);
 #endif
         small = imax(small, MIN_PIECE_FRAMES);
         big_rounds = imax(big_rounds, 1);
-        const int wgs = cus * persistent_wgs_per_cu();
-        const int64_t per_wg = group_frames / wgs + 1;                                      // a workgroup's share of the frames
-        int ns = (small_rounds * wgs + groups / 2) / groups;                                // piece indices that make small_rounds rounds of items
+        const int wgs = cus * (self ? PLAN8_WGS_PER_CU : persistent_wgs_per_cu());
+        const int queue_groups = self ? 2 * groups : groups;
+        const int64_t per_wg = group_frames * (self ? 2 : 1) / wgs + 1;                     // a workgroup's share of the frames
+        int ns = (small_rounds * wgs + queue_groups / 2) / queue_groups;                    // piece indices that make small_rounds rounds of items
         if ((int64_t)ns * small > frames / 2) ns = frames / (2 * small);
         int big = (int)imax((int)((per_wg - (int64_t)small_rounds * small) / big_rounds), small);
         int nb = (int)((frames - (int64_t)ns * small + big - 1) / big);
@@ -1442,6 +1579,20 @@ int plan_encode_pieces_on(int cus, int groups, int frames, int64_t group_frames,
     return segments;
 }
 
+// Which batches the self-served shape encodes when nothing is forced: those of the two-size schedule (from one group of
+// sixteen per 8 workgroups of the 2 + 1 shape on: 2048 channels on an MI355X) and ragged batches.  LABNOTES 18.
+#ifndef VGA_GC_SELF_SERVED_DEFAULT
+#define VGA_GC_SELF_SERVED_DEFAULT 1
+#endif
+static bool self_served_shape(int layout_hook, int groups16, int cus, bool ragged)
+{
+    if (layout_hook == 1) return true;
+    if (layout_hook != 0 || encoder_persistent_mode() != 0) return false;    // (a forced layout or queue mode means the 2 + 1 shape)
+    return VGA_GC_SELF_SERVED_DEFAULT != 0 && (ragged || groups16 * PERSISTENT_SCHEDULE_GROUPS_FACTOR >= cus * 4);
+}
+// (for the host's plan of a ragged batch, gc_capi.hpp: the layout to hand to plan_encode_pieces)
+int encoder_plan_layout(int groups16, bool ragged) { return self_served_shape(encoder_layout(), groups16, device_cu_count(), ragged) ? 1 : 8; }
+
 template <int CPW, bool RAGGED>
 static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch, int sample_count, const int16_t *d_coefs,
                                 const int16_t *d_hist1, const int16_t *d_hist2, uint8_t *d_adpcm, int64_t adpcm_pitch,
@@ -1460,20 +1611,26 @@ static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch
     bool persistent = false;
     Pieces seg;
     int segments;
+    const bool want_self = CPW == 8 && self_served_shape(encoder_layout(), groups, cus, RAGGED);
     if (RAGGED && rg.items) {
         persistent = rg.persistent != 0;
         seg = rg.seg;
         segments = rg.segments;
     } else {
-        segments = plan_encode_pieces(groups, frames, RAGGED ? rg.total_frames / CS : (int64_t)groups * frames, RAGGED, &persistent, &seg, CPW);
+        segments = plan_encode_pieces(groups, frames, RAGGED ? rg.total_frames / CS : (int64_t)groups * frames, RAGGED, &persistent, &seg,
+                                      want_self ? 1 : CPW);
     }
+    // the self-served shape takes the pieces in groups of eight channel slots (gc_plan8.hpp)
+    const bool self = want_self && persistent;
+    const Plan8 p8 = self ? plan_groups_of_eight(cus, nch, segments, RAGGED && rg.items ? rg.n_items : -1) : Plan8{};
+    const int seam_groups = self ? p8.groups : groups;
     AsyncBuf scratch;                                  // freed (stream-ordered) on every exit path
     int16_t *seg_state = nullptr;
     int *first_open = nullptr, *seam_flag = nullptr, *seam_end = nullptr, *queue = nullptr, *seam_count = nullptr;
     if (segments > 1 || persistent) {
         const size_t state_bytes = segments > 1 ? (size_t)round_up((int64_t)segments * nch * 2 * (int64_t)sizeof(int16_t), 16) : 0;
         const size_t open_bytes = (size_t)round_up((int64_t)nch * (int64_t)sizeof(int), 16);
-        const size_t count_bytes = persistent && segments > 1 ? (size_t)round_up((int64_t)(segments - 1) * groups * (int64_t)sizeof(int), 16) : 0;
+        const size_t count_bytes = persistent && segments > 1 ? (size_t)round_up((int64_t)(segments - 1) * seam_groups * (int64_t)sizeof(int), 16) : 0;
         const size_t need = 3 * state_bytes + open_bytes + 16 + count_bytes;
         // the caller's scratch when it brought one (the host pipeline: hipMallocAsync next to busy copy streams stalled
         // its launching thread for up to 300 ms per call), a stream-ordered allocation otherwise
@@ -1494,7 +1651,12 @@ static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch
         seam_count = queue + 4;
         if (persistent) VGA_HIP_TRY(hipMemsetAsync(queue, 0, 16 + count_bytes, stream));    // the queue's head and every seam's counter
     }
-    if (persistent) {
+    if (self) {
+        if constexpr (CPW == 8)
+            hipLaunchKernelGGL((gc_encode_self_served_kernel<RAGGED>), dim3(p8.wgs), dim3(Lay<8, true>::THREADS), 0, stream, d_pcm, pcm_pitch,
+                               nch, sample_count, seg, d_coefs, d_hist1, d_hist2, d_adpcm, adpcm_pitch, seg_state, rg, p8.groups, p8.items,
+                               segments, queue, seam_count, first_open, seam_flag, seam_end, force_open_seams());
+    } else if (persistent) {
         const int items = RAGGED && rg.items ? rg.n_items : groups * segments;
         const int wgs = imin(items, cus * persistent_wgs_per_cu());
         if constexpr (CPW == 8)
@@ -1552,8 +1714,9 @@ static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch
 }
 
 // upper bound of what launch_encode wants as scratch for nch channels (1024 pieces x (state, flag, end) + 4 B per channel, + alignment)
-// (+ the persistent kernel's queue and seam counters: 4 B per channel group and seam)
-size_t encode_scratch_bytes(int nch) { return (size_t)(nch > 0 ? nch : 0) * (1024 * 12 + 4 + 256) + 8192; }
+// (+ the persistent kernels' queue and seam counters: 4 B per channel group and seam)
+// (groups of eight, the self-served shape: 4 B per seam and 8 channels = 512 B per channel)
+size_t encode_scratch_bytes(int nch) { return (size_t)(nch > 0 ? nch : 0) * (1024 * 12 + 4 + 512) + 8192; }
 
 int launch_encode(const int16_t *d_pcm, int64_t pcm_pitch, int nch, int sample_count, const int16_t *d_coefs,
                   const int16_t *d_hist1, const int16_t *d_hist2, uint8_t *d_adpcm, int64_t adpcm_pitch,

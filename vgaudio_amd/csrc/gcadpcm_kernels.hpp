@@ -22,8 +22,11 @@ struct Pieces {
 };
 // The encoder's piece schedule for `groups` channel groups (16 channels each) whose longest channel has `frames` frames and
 // which hold `group_frames` frames of work in all (sum over groups of the group's longest channel); persistent = workgroups
-// that take (group, piece) items from a queue (the (channel, predictor) layout only: layout == 8).  Returns the number of
-// pieces the longest channel has.
+// that take (group, piece) items from a queue (the (channel, predictor) layout only: layout == 8, or layout == 1: the
+// self-served shape, whose queue holds groups of eight for twelve workgroups per compute unit -- the two-size schedule counts
+// its rounds in those; encoder_plan_layout says which of the two a batch gets).  Returns the number of pieces the longest
+// channel has.
+int encoder_plan_layout(int groups, bool ragged);
 int plan_encode_pieces(int groups, int frames, int64_t group_frames, bool ragged, bool *persistent, Pieces *seg, int layout = 8);
 // ... on a device with `cus` compute units (host arithmetic only)
 int plan_encode_pieces_on(int cus, int groups, int frames, int64_t group_frames, bool ragged, bool *persistent, Pieces *seg, int layout = 8);

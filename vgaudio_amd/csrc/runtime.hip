@@ -154,7 +154,8 @@ int vga_testing_force_open_seams_this_thread(int mode)
 int vga_testing_gc_encoder_layout_this_thread(int channels_per_wave)
 {
     const int old = g_settings.encoder_layout;
-    if (channels_per_wave == 0 || channels_per_wave == 4 || channels_per_wave == 8) g_settings.encoder_layout = channels_per_wave;
+    if (channels_per_wave == 0 || channels_per_wave == 1 || channels_per_wave == 4 || channels_per_wave == 8)
+        g_settings.encoder_layout = channels_per_wave;
     return old;
 }
 int vga_testing_gc_coefs_variant_this_thread(int variant)
