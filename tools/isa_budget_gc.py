@@ -14,6 +14,9 @@ resulting lane-operations per sample with the measured rates (cold-block rate, s
 --shape self (round 13): the same table for gc_encode_self_served_kernel<false> -- the one-wave workgroups that are helper and
 encoder of their eight channel slots -- and, in place of the helper wave's loop, the static counts of that kernel's tile
 boundary: the blocks of the tile loop outside the frame loop (next tile's loads, flush, the compute half of prepare).
+Round 14: that boundary split by block -- load and unpack, row, pre-scan, flush and pack, bookkeeping -- by the source line of
+every instruction (the listing is made with -gline-tables-only; tile_blocks), the frame loop's instruction count with a digest
+of its mnemonics (to hold a change against its parent's, --src), and the kernel's instruction count.
 
 Since round 12 the listing is made with the product's own options for the file (vgaudio_amd/build.py FILE_FLAGS; until then
 with the common ones only), and the tool also counts the scratch instructions (spill stores and reloads) per block of the
@@ -42,11 +45,13 @@ def listing():
     from vgaudio_amd.build import FILE_FLAGS                  # the product's per-file code generation options
     src = os.path.abspath(sys.argv[sys.argv.index("--src") + 1]) if "--src" in sys.argv else SRC
     with tempfile.TemporaryDirectory() as tmp:
-        subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + FILE_FLAGS.get("gc_encode_kernel.hip", []) + ["-I", os.path.dirname(SRC)] +
+        # (line tables only: the .loc directives the tile boundary's split by block reads; they change no instruction)
+        subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-gline-tables-only"] + FILE_FLAGS.get("gc_encode_kernel.hip", []) + ["-I", os.path.dirname(SRC)] +
                        [a for a in sys.argv[1:] if a.startswith("-D")] +
                        ["--save-temps=obj", "-c", src, "-o", os.path.join(tmp, "k.o")], check=True, cwd=tmp,
                        stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         s = [f for f in os.listdir(tmp) if f.endswith(".s") and "gfx950" in f][0]
+        listing.src = src
         return open(os.path.join(tmp, s)).read().split("\n")
 
 
@@ -57,6 +62,8 @@ def kernel(lines, name):
     for l in lines[a + 1:b + 1]:
         t = l.split(";")[0].rstrip()
         if not t.strip() or t.strip().startswith((".p2align", ".", "//")) and not t.strip().endswith(":"):
+            continue
+        if t.strip().endswith(":") and not t.strip().startswith(".LBB"):   # (.Ltmp labels of the line tables are no block boundaries)
             continue
         out.append(t.strip())
     return out
@@ -71,6 +78,7 @@ def scratch_by_block(raw, name):
     frame_hdr, tile_hdr, nested, tile_nested, where, lab = None, None, set(), set(), "prologue, seams, epilogue", None
     regions, inside = collections.OrderedDict(), []
     tile_code = []                                                   # every instruction of the tile loop outside the frame loop
+    tile_loc, cur_loc, frame_ops = [], (0, 0), []                    # ... its (file number, line) by the .loc in force; the frame loop's mnemonics
     for key in ("frame loop: the frame's pairs of passes", "frame loop: the cold block's passes", "frame loop: row reads, first scale, flags, tail, the cold block's other code",
                 "tile head (once per tile, outside the frame loop)", "prologue, seams, epilogue"):
         regions[key] = 0
@@ -106,13 +114,75 @@ def scratch_by_block(raw, name):
             regions[where] += 1
             if where.startswith("frame loop"):
                 inside.append("%s: %s" % (lab, raw[i].split(";")[0].strip()))
-        if where.startswith("tile head") and not m:
+        loc = re.match(r"^\s*\.loc\s+(\d+)\s+(\d+)", raw[i])
+        if loc:
+            cur_loc = (int(loc.group(1)), int(loc.group(2)))
+        if not m:
             t = raw[i].split(";")[0].strip()
             if t and not t.startswith(".") and not t.endswith(":"):
-                tile_code.append(t)
+                if where.startswith("tile head"):
+                    tile_code.append(t)
+                    tile_loc.append(cur_loc)
+                elif where.startswith("frame loop"):
+                    frame_ops.append(t.split()[0])
         i += 1
     scratch_by_block.tile_code = tile_code
+    scratch_by_block.tile_loc = tile_loc
+    scratch_by_block.frame_ops = frame_ops
     return regions, inside, frame_hdr
+
+
+TILE_BLOCKS = ("load and unpack", "row", "pre-scan", "flush and pack", "bookkeeping")
+
+
+def tile_blocks(raw, tile_code, tile_loc):
+    """The tile boundary's instructions by the source line their .loc names (round 14): the helper role's lambdas of the kernel
+    file and the functions of gc_encode_core.hpp they call.  load and unpack: load_frame and prepare_self's unpack; row: the
+    pairs and the pass's row into the LDS slot (prepare_from up to the pre-scan's pairs); pre-scan: the rest of prepare_from
+    with the header's dot products, quotients, max / min and packing; flush and pack: flush and pack_frame_mod16; bookkeeping:
+    everything else (the loop, the fences and waits, the coefficient pairs' ds_bpermute, the item's end)."""
+    import re
+    files = {}
+    for l in raw:
+        m = re.match(r'^\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', l)
+        if m:
+            files[int(m.group(1))] = os.path.basename(m.group(3) or m.group(2))
+    src = open(listing.src).read().split("\n")
+
+    def extent(opening, closing="    };"):
+        a = next(i for i, l in enumerate(src) if opening in l)
+        pad = len(src[a]) - len(src[a].lstrip())
+        b = next(i for i in range(a + 1, len(src)) if src[i].rstrip() == " " * pad + "};")
+        return a + 1, b + 1                                          # 1-based, inclusive
+    load, prep, flush, pself = (extent("auto load_frame = "), extent("auto prepare_from = "), extent("auto flush = "),
+                                extent("auto prepare_self = "))
+    pairs = next(i for i in range(prep[0], prep[1]) if "uint32_t pair[12];" in src[i]) + 1
+    core = open(os.path.join(os.path.dirname(SRC), "gc_encode_core.hpp")).read().split("\n")
+
+    def core_fn(line):                                               # the function of the header a line stands in
+        for i in range(min(line, len(core)) - 1, -1, -1):
+            m = re.match(r"^VGA_HD\s+[\w:<> ]+?\b(\w+)\(", core[i])
+            if m:
+                return m.group(1)
+        return ""
+    out = {k: [] for k in TILE_BLOCKS}
+    for t, (fno, line) in zip(tile_code, tile_loc):
+        name = files.get(fno, "")
+        if name == os.path.basename(listing.src):
+            where = ("load and unpack" if load[0] <= line <= load[1] else
+                     "row" if prep[0] <= line < pairs else "pre-scan" if pairs <= line <= prep[1] else
+                     "flush and pack" if flush[0] <= line <= flush[1] else
+                     "load and unpack" if pself[0] <= line <= pself[1] and "__shfl" not in src[line - 1] and "prepare_from" not in src[line - 1]
+                     else "bookkeeping")
+        elif name == "gc_encode_core.hpp":
+            fn = core_fn(line)
+            where = ("pre-scan" if fn in ("prescan_numer_word", "numer_adjust", "dot2_i16", "dot2_i16_wrap", "div2048", "sat_pack16", "imax", "imin",
+                                          "clamp16i", "pk_sub_sat_i16", "med3_i32") else
+                     "row" if fn == "pass_b_row" else "flush and pack" if fn.startswith("pack_frame") else "bookkeeping")
+        else:
+            where = "bookkeeping"
+        out[where].append(t)
+    return out
 
 
 def resources(raw, name):
@@ -202,7 +272,7 @@ def main():
             ("the frame's two passes without the f32 detour, 28 sample steps, and the test of what they vouch for", count(L[short_blk[0]:short_blk[1]])),
             ("the same with the conversions (30 % of the wave-frames take these instead)", count(L[normal_blk[0]:normal_blk[1]])),
             ("the flags, the error block, 8-predictor argmin (DPP), winner's history, 4 x ds_write_b128", count(L[normal_blk[1]:tail_end + 1]))]
-    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 13)\n")
+    print("# GC-ADPCM encoder: instruction budget of one wave-frame (round 14)\n")
     print("`" + nice_name % "false" + "`, static counts from hipcc's gfx950 listing of `vgaudio_amd/csrc/gc_encode_kernel.hip`")
     print("(`tools/isa_budget_gc.py`).  One wave-frame = 64 lanes = 8 channels x 8 predictors = 112 input samples.\n")
     print("| block of the hot frame | total | VALU | SALU | LDS | wait / nop |")
@@ -236,6 +306,17 @@ def main():
             print("`%s`, tile boundary (the blocks of the tile loop outside the frame loop, every branch counted once -- the partial last "
                   "frame's byte loops among them): %d instructions, %d VALU, %d SALU, %d LDS, %d VMEM per tile of 8 frames x 8 channel slots.\n"
                   % (nice, c["total"], c["VALU"], c["SALU"], c["LDS"], c["VMEM"]))
+            print("| block of the tile boundary | total | VALU | SALU | LDS | VMEM | wait / nop |")
+            print("|---|---:|---:|---:|---:|---:|---:|")
+            for k, blk in tile_blocks(RAW, scratch_by_block.tile_code, scratch_by_block.tile_loc).items():
+                b = count(blk)
+                print("| %s | %d | %d | %d | %d | %d | %d |" % (k, b["total"], b["VALU"], b["SALU"], b["LDS"], b["VMEM"], b["wait/nop"]))
+            import hashlib
+            ops = scratch_by_block.frame_ops
+            print("\nFrame loop, header to back edge: %d instructions; SHA-1 of their mnemonics sorted `%s`, in listing order `%s`; the "
+                  "whole kernel: %d instructions.\n"
+                  % (len(ops), hashlib.sha1(" ".join(sorted(ops)).encode()).hexdigest()[:16], hashlib.sha1(" ".join(ops).encode()).hexdigest()[:16],
+                     sum(not l.endswith(":") for l in kernel(RAW, mangled))))
         res = resources(RAW, mangled)
         print("`%s`: %d VGPRs, %d waves per SIMD, %d B of scratch per lane, %d B of LDS per workgroup; frame loop header `.L%s`.\n"
               % (nice, res.get("NumVgprs", -1), res.get("Occupancy", -1), res.get("ScratchSize", -1), res.get("LDSByteSize", -1), hdr))
@@ -251,23 +332,32 @@ def main():
 
 
 TEXT_SELF = """
-## What the budget says (round 13, written before the GPU run)
+## What the budget says (round 14, written before the GPU runs it speaks of)
 
-* The frame loop is the 2 + 1 shape's, instruction for instruction: row block 33, passes 276 / 321, tail 37 VALU, encoder role
-  436 VALU per wave-frame (`gc_encode_persistent_kernel<8, false>` from the same source reads the same, 166 VGPRs).
-* The tile boundary stands where the helper wave's loop stood.  A tile is 8 frames x 8 channel slots = 8 wave-frames; the helper's
-  tile of 4 frames x 16 slots is 8 wave-frames as well: 762 VALU there (95 per wave-frame), at most 871 here (109 per wave-frame;
-  the static count holds the partial last frame's byte loops and both sides of every branch, a full tile executes fewer).  What
-  is new in it: eight `ds_bpermute` for the coefficient pairs of the helper role, the lane's slot address once more, and the
-  clamped frame index formed twice (load and compute).
-* 167 VGPRs with the next tile's seven dwords held across the frame loop, no scratch anywhere in the kernel, 12 612 B of LDS
-  per workgroup: twelve workgroups are 151 344 B of the compute unit's 163 840 (13 312 B each if the allocation is in steps
-  of 512 B: 159 744).
-* Prediction, written down before the GPU run.  Instructions per launch: encoder role unchanged, helper role 95 -> 100-109 per
-  wave-frame, so SQ_INSTS_VALU +1 to +2.6 % (531 -> 536-545 per wave-frame).  Time goes as instructions / busy fraction: if three
-  like waves per SIMD lift SQ_ACTIVE_INST_VALU / issue slots from 0.90 to 0.97 the launch is 112 ms x 1.026 x 0.90 / 0.97 = 106.6 ms
-  at the worst instruction count (-5 ms) and 105 ms at the best; if the busy fraction does not move, the launch is 1-3 ms SLOWER
-  and the shape stays behind the test hook.  Measured: LABNOTES 18.
+* The tile boundary by block (the table above; the split follows the `.loc` line of every instruction, so an instruction the
+  scheduler moved or merged counts where its line says).  Static VALU per tile of 8 wave-frames, both sides of every branch and
+  the partial last frame's byte loops counted: parent 871 (`--src` on the parent's file: pre-scan 703), the numerator form as
+  the issue words it -- dot product, subtract, sign bit, `v_mad_u32_u24`, `v_max3` / `v_min3` over pairs, 5 per term -- 682, the
+  form as committed -- dot product, add, `v_med3_i32` (gc_encode_core.hpp N7), 4 per term, one `v_cvt_pk_i16_i32` for both clamps
+  and the packing -- **586**: pre-scan 703 -> 418, the rolled fallback loop of a wave with a hostile channel among them, which a clean
+  wave never executes; the other blocks sum to 168 on both sides.  The whole kernel: 13 187 -> 12 584 instructions (the two forms side by side do
+  not grow it: the fallback is a loop rolled over the predictors).
+* What the issue's item 3 names does not survive in this listing: the row is formed from the loaded pairs ((w << 16) >> 5, and
+  an SDWA shift of the high half), there is no second unpack; the slot address is one `v_mad_u32_u24` shared by `flush` and
+  `prepare_from`; the clamped frame index is formed once per load (`v_lshl_or`, `v_min`), `flush` has the unclamped index of its
+  own tile.  Nothing was changed in the source for them.
+* Conditions: 167 VGPRs (168 in the ragged instantiation), three waves per SIMD, no scratch instruction anywhere in the kernel.
+  The frame loop holds the parent's 6406 instructions -- the same mnemonics with the same counts (the SHA-1 of the sorted list
+  is the parent's); hipcc schedules a few of them (`v_or_b32` / `v_lshlrev_b32` of the record's packing, the `s_nop` in front of a
+  dot product's reader) in another order, so the digest in listing order differs.
+* Prediction.  Static: 871 -> 586 VALU per tile, -285, that is -35.6 per wave-frame of about 561 (SQ_INSTS_VALU 59.07 G per
+  launch, round 13): **SQ_INSTS_VALU -6.3 %, to about 55.3 G**; executed instructions fall a little further (a clean wave runs
+  neither form's fallback).  At the parent's busy fraction (0.988) the 105.3 ms kernel would take about **98.6 ms (-6.7 ms)**.
+  (The form is compiled into the self-served shape only: every kernel with a helper wave compiles to the parent's
+  instruction count, `profiles/r14_kernel_resources_gc_encode.txt`.)
+  Session 1 of `profiles/r14_encode_ab.log` measured the issue's five-per-term form (-189 static) at -1.84 ms of the encode
+  call where the same reckoning gave -4.5: at that exchange rate the form as committed is worth about **-2.8 ms**.  Measured:
+  LABNOTES 19.
 """
 
 TEXT = """

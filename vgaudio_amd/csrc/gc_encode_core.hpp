@@ -352,6 +352,46 @@ VGA_HD int head_distance_numer(int in2048p, int P)
     const int N = (int)((uint32_t)in2048p - (uint32_t)P);
     return numer_adjust(N, (int)((uint32_t)(1024 - P) >> 31)) >> 11;                        // 1024 - P < 0  <=>  D > 0
 }
+// The range of samples 2..13 of ONE predictor in the numerator domain (round 14): the tile head's pre-scan word without a
+// quotient per term.  pair[k] = (in[k], in[k + 1]) are the operands of sample k + 2's prediction, a2048[k] = in[k + 2] * 2048,
+// ncpk = (-c1, -c0) as a packed pair (low half -c1).  Per term
+//       N = dot2(pair, ncpk, a2048) = in * 2048 - D,        X = clamp(a2048, N, N + 2047),        d = X >> 11        (N1, N7)
+// Returns clamp16(max d) & 0xFFFF | clamp16(min d) << 16 with max and min started at 0 -- the word
+// prescan_range(x, c0, c1, 2, 14, ...) and clamp16i give.
+//  (N3) the accumulator: |D| <= 32768 * (|c0| + |c1|) <= 32768 * 30720 = 2^30 - 2^26 under pass_b_coef_ok, |a2048| <= 2^26, so
+//       |N| <= 2^30 and N + 2047 < 2^31 - 2048: the clamped dot product cannot saturate (its clamp bit only selects the
+//       three-operand encoding, as in dot2_i16) and the add does not wrap.  The pass's row (a2048 + 1024 + 2^30) must NOT be the
+//       accumulator: N + 2^30 leaves int32.
+//  (N7) the sign test and the bias of N1 as one median.  a2048 = N + D, so clamp(a2048, N, N + 2047) = N + clamp(D, 0, 2047):
+//         D <= 0:         X = N, N1's numerator;
+//         D >= 2047:      X = N + 2047, N1's numerator;
+//         0 < D < 2047:   X = a2048, where N1 has N + 2047 = a2048 + (2047 - D): both lie in [a2048, a2048 + 2047) and a2048 is
+//                         a multiple of 2048, so both shift to the same d = in (the quotient D / 2048 is 0).
+//       The lower bound is not above the upper one, so the median of the three IS the clamp (v_med3_i32).  Its operand N + 2047
+//       is formed by the compiler from the dot product's result, so the median stands behind the wait states that result
+//       needs although it is an asm statement (see dot2_i16_wrap, med3_i32).
+//  (N4) x -> x >> 11 is monotone, so max_k (X_k >> 11) = (max_k X_k) >> 11 and likewise for the minimum; the start value 0 is
+//       0 >> 11.  One shift per predictor and side, the running max / min over the X (v_max3 / v_min3 over pairs of terms).
+//  (N5) the two clamps and the packing are sat_pack16 (one v_cvt_pk_i16_i32): |X >> 11| <= 2^19 + 1 needs them.
+//  (N6) -c must fit int16: c = -32768 cannot be negated.  pass_b_coef_ok bounds |c0| + |c1| by 30720, so wherever this form is
+//       valid no coefficient is below -30720.  Callers that cannot vouch for the bound keep prescan_range's form.
+VGA_HD int med3_i32(int v, int lo, int hi);
+VGA_HD uint32_t prescan_numer_word(const uint32_t (&pair)[12], const int (&a2048)[12], uint32_t ncpk)
+{
+    int xmax = 0, xmin = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < 12; k += 2) {
+        const int N0 = dot2_i16(pair[k], ncpk, a2048[k]);
+        const int N1 = dot2_i16(pair[k + 1], ncpk, a2048[k + 1]);
+        const int X0 = med3_i32(a2048[k], N0, N0 + 2047);
+        const int X1 = med3_i32(a2048[k + 1], N1, N1 + 2047);
+        xmax = imax(imax(xmax, X0), X1);
+        xmin = imin(imin(xmin, X0), X1);
+    }
+    return sat_pack16(xmax >> 11, xmin >> 11);
+}
 VGA_HD void pack_row(const int (&x)[16], uint32_t (&xw)[7])
 {
 #if defined(__HIP_DEVICE_COMPILE__)

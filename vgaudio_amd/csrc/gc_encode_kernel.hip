@@ -379,7 +379,14 @@ __device__ __forceinline__ void gc_encode_piece(
     };
     // prepare_from: everything of the frame that depends on input samples only, into the lane's LDS slot
     // (cpk[p]: (c1, c0) of predictor p as a packed pair, low half c1)
-    auto prepare_from = [&](int tile, const uint32_t (&w)[7], const int (&in)[14], const uint32_t (&cpk)[8]) __attribute__((always_inline)) {
+    // Round 14, the self-served shape only (the shapes with a helper wave measured no gain and a loss at 1024 channels: they keep
+    // the loop they had).  `numer` (wave-uniform, decided once per piece: no channel of the wave has coefficients above the
+    // bound of pass_b_coef_ok): the range of samples 2..13 in the numerator domain (gc_encode_core.hpp N1, N3-N7,
+    // prescan_numer_word) -- cpk[p] is then (-c1, -c0) of predictor p, low half -c1.  A wave with a hostile channel keeps the
+    // reference's unchecked sum and the quotient, as a loop rolled over the predictors (rare: it must be small, not fast);
+    // pair_of(p) hands it (c1, c0) of predictor p.
+    auto prepare_from = [&](int tile, const uint32_t (&w)[7], const int (&in)[14], const uint32_t (&cpk)[8], const bool numer,
+                            auto pair_of) __attribute__((always_inline)) {
         Slot &T = s_tile[tile & (BUFS - 1)].g[grp].f[hfr];
         uint4 *xr = reinterpret_cast<uint4 *>(&T.xw[0]);   // the pairs as loaded (the ints: in2048p and the pre-scan)
         xr[0] = make_uint4(w[0], w[1], w[2], w[3]);
@@ -397,28 +404,52 @@ __device__ __forceinline__ void gc_encode_piece(
 #pragma unroll
         for (int k = 0; k < 12; k++)
             pair[k] = (k & 1) ? __builtin_amdgcn_alignbit(w[(k + 1) / 2], w[(k - 1) / 2], 16) : w[k / 2];
-        uint32_t pre[8];
+        uint4 *pr = reinterpret_cast<uint4 *>(&T.pre[0]);
+        if constexpr (!SELF) {
+            uint32_t pre[8];
 #pragma unroll
-        for (int p = 0; p < 8; p++) {
-            int dmax = 0, dmin = 0;
+            for (int p = 0; p < 8; p++) {
+                int dmax = 0, dmin = 0;
 #ifdef VGA_GC_ABLATE_HELPER_PRESCAN                                  // timing only: what the helper's 96 distances per frame cost the launch
-            dmax = in[2 + p] & 1023;
-            dmin = -(in[3 + p] & 1023);
+                dmax = in[2 + p] & 1023;
+                dmin = -(in[3 + p] & 1023);
 #else
 #pragma unroll
-            for (int k = 0; k < 12; k++) {
-                const int predicted = div2048(__builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, pair[k]),
-                                                                     __builtin_bit_cast(short2v, cpk[p]), 0, false));
-                const int d = in[k + 2] - predicted;
-                dmax = imax(dmax, d);
-                dmin = imin(dmin, d);
-            }
+                for (int k = 0; k < 12; k++) {
+                    const int predicted = div2048(__builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, pair[k]),
+                                                                         __builtin_bit_cast(short2v, cpk[p]), 0, false));
+                    const int d = in[k + 2] - predicted;
+                    dmax = imax(dmax, d);
+                    dmin = imin(dmin, d);
+                }
 #endif
-            pre[p] = (uint32_t)(clamp16i(dmax) & 0xFFFF) | ((uint32_t)clamp16i(dmin) << 16);
+                pre[p] = (uint32_t)(clamp16i(dmax) & 0xFFFF) | ((uint32_t)clamp16i(dmin) << 16);
+            }
+            pr[0] = make_uint4(pre[0], pre[1], pre[2], pre[3]);
+            pr[1] = make_uint4(pre[4], pre[5], pre[6], pre[7]);
+        } else if (__builtin_expect(numer, 1)) {
+            int a2048[12];
+#pragma unroll
+            for (int k = 0; k < 12; k++) a2048[k] = in[k + 2] * 2048;
+            uint32_t pre[8];
+#pragma unroll
+            for (int q = 0; q < 8; q++) pre[q] = prescan_numer_word(pair, a2048, cpk[q]);
+            pr[0] = make_uint4(pre[0], pre[1], pre[2], pre[3]);
+            pr[1] = make_uint4(pre[4], pre[5], pre[6], pre[7]);
+        } else {
+#pragma unroll 1
+            for (int q = 0; q < 8; q++) {
+                const uint32_t cp = pair_of(q);
+                int dmax = 0, dmin = 0;
+#pragma unroll
+                for (int k = 0; k < 12; k++) {
+                    const int d = in[k + 2] - div2048(dot2_i16_wrap(pair[k], cp));
+                    dmax = imax(dmax, d);
+                    dmin = imin(dmin, d);
+                }
+                T.pre[q] = sat_pack16(dmax, dmin);
+            }
         }
-        uint4 *pr = reinterpret_cast<uint4 *>(&T.pre[0]);
-        pr[0] = make_uint4(pre[0], pre[1], pre[2], pre[3]);
-        pr[1] = make_uint4(pre[4], pre[5], pre[6], pre[7]);
     };
     auto flush = [&](int tile) __attribute__((always_inline)) {
         const int fr = tile * TF + hfr;
@@ -448,7 +479,7 @@ __device__ __forceinline__ void gc_encode_piece(
             uint32_t w[7];
             int in[14];
             load_frame(tile, w, in);
-            prepare_from(tile, w, in, cpk);
+            prepare_from(tile, w, in, cpk, false, [](int) { return 0u; });
         };
         if (tiles > 0) prepare(0);
         __syncthreads();
@@ -865,16 +896,18 @@ __device__ __forceinline__ void gc_encode_piece(
         };
         // the helper role's coefficient pairs: predictor q's pair is what the encoder role's lane (slot, q) holds
         auto prepare_self = [&](int tile, const uint32_t (&w)[7]) __attribute__((always_inline)) {
-            uint32_t cp8[8];
+            // (negated for the numerator form, one packed subtract per tile; head_numer is the flag over the same eight channels)
+            const uint32_t ncpk = pk_sub_sat_i16(0u, cpk);
+            uint32_t ncp8[8];
 #pragma unroll
-            for (int q = 0; q < 8; q++) cp8[q] = (uint32_t)__shfl((int)cpk, (lane & 56) | q);
+            for (int q = 0; q < 8; q++) ncp8[q] = (uint32_t)__shfl((int)ncpk, (lane & 56) | q);
             int in[14];
 #pragma unroll
             for (int i = 0; i < 7; i++) {
                 in[2 * i] = (int)(int16_t)(w[i] & 0xFFFF);
                 in[2 * i + 1] = (int)w[i] >> 16;
             }
-            prepare_from(tile, w, in, cp8);
+            prepare_from(tile, w, in, ncp8, head_numer, [&](int q) { return (uint32_t)__shfl((int)cpk, (lane & 56) | q); });
         };
         uint32_t wn[7];                                    // the lane's frame of the NEXT tile, loaded a tile ahead
         int unused[14];
