@@ -829,6 +829,8 @@ int vga_hca_decode_batch_v(const vga_hca_info *infos, const uint8_t *const *fram
  * any byte and are stored as aligned dwords plus lead and tail bytes.
  * Decode: d_frames and frames_pitch multiples of 4 with >= 8 bytes of slack after frame_count*frame_size
  * (anything else -> VGA_ERR_ARGUMENT; the slack's contents do not matter).
+ * The pitches have no upper bound: streams and rows may lie 8 GiB and more apart inside a larger buffer
+ * (tests/test_gpu_far_offsets.py; the decoder's scan clamps its count of readable dwords to INT32_MAX).
  * *d_status receives flag bits (16 internal: cost table; 1 bad sync, 2 bad scale-factor
  * delta, 4 bitrate too low, 8 boundary search failed). */
 size_t vga_hca_decode_workspace_bytes(const vga_hca_info *info, int nstreams);

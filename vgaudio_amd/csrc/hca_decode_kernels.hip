@@ -174,7 +174,7 @@ __global__ __launch_bounds__(64) void hca_scan_kernel(const uint8_t *__restrict_
 
     GlobalSrc<RAGGED> src;
     src.base = reinterpret_cast<const uint32_t *>(frames + (int64_t)stream * stream_pitch) + (a0 >> 2);
-    src.limit = (int)(stream_pitch / 4 - (a0 >> 2));
+    src.limit = (int)min((int64_t)INT32_MAX, stream_pitch / 4 - (a0 >> 2));    // (a pitch of 8 GiB is 2^31 dwords)
     if constexpr (RAGGED) src.limit = live ? src.limit : 0;            // an idle lane goes through the motions on zeros (the
                                                                        // wave's lanes hand their records out together, StagedOut)
     int first_bit = (int)(a0 & 3) * 8;
