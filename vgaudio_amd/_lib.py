@@ -347,6 +347,19 @@ SIGNATURES = {
     "vga_adx_files_read_items_for": (ci, [vp, ci, C.POINTER(i64), ci, vp, i64, C.POINTER(i64)]),
     "vga_adx_files_stats": (ci, [vp, C.POINTER(i64)]),
     "vga_adx_files_force_general_this_thread": (ci, [ci]),
+    # include/vgaudio_hip_files/wave_files.h
+    "vga_wave_files_layout_for": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), C.POINTER(ci), C.POINTER(i64), C.POINTER(i64), vp]),
+    "vga_wave_files_create": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), C.POINTER(vp)]),
+    "vga_wave_files_create_from_infos": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), C.POINTER(vp)]),
+    "vga_wave_files_destroy": (None, [vp]),
+    "vga_wave_files_totals_of": (ci, [vp, vp]),
+    "vga_wave_files_offsets": (ci, [vp, C.POINTER(ci), C.POINTER(i64), C.POINTER(i64)]),
+    "vga_wave_read_device_v": (ci, [vp, vp, vp, vp]),
+    "vga_wave_write_device_v": (ci, [vp, vp, vp, vp]),
+    "vga_wave_files_write_items_for": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), ci, vp, i64, C.POINTER(i64)]),
+    "vga_wave_files_read_items_for": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), ci, vp, i64, C.POINTER(i64)]),
+    "vga_wave_files_stats": (ci, [vp, C.POINTER(i64)]),
+    "vga_wave_files_force_general_this_thread": (ci, [ci]),
     # include/vgaudio_hip/hca_files.h
     "vga_hca_files_layout_for": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp]),
     "vga_hca_files_create": (ci, [vp, ci, C.POINTER(i64), vp, ci, C.POINTER(vp)]),
@@ -402,6 +415,22 @@ class WaveInfoC(C.Structure):
 class WaveParamsC(C.Structure):
     """vga_wave_params"""
     _fields_ = [(n, C.c_int) for n in ("sample_rate", "sample_count", "looping", "loop_start", "loop_end")]
+
+
+class WaveFileC(C.Structure):
+    """vga_wave_file (include/vgaudio_hip_files/wave_files.h)"""
+    _fields_ = [("channels", C.c_int), ("bits", C.c_int), ("params", WaveParamsC)]
+
+
+class WaveFilesTotalsC(C.Structure):
+    """vga_wave_files_totals"""
+    _fields_ = [("files", C.c_int), ("channels", C.c_int), ("pcm_samples", C.c_int64), ("image_bytes", C.c_int64)]
+
+
+class WaveFilesItemC(C.Structure):
+    """vga_wave_files_item"""
+    _fields_ = [("form", C.c_int), ("file", C.c_int), ("x", C.c_int), ("y", C.c_uint32), ("span", C.c_int),
+                ("begin", C.c_int64), ("end", C.c_int64)]
 
 
 class AdxKeyC(C.Structure):

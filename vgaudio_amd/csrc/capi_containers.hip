@@ -1,6 +1,7 @@
 // capi_containers.hip -- C ABI of the ADX and HCA container writers (DSP lives next to the
 // GC-ADPCM entry points).  Images are assembled in HBM; the host-pointer forms stage through the device.
 #include "container_host.hpp"
+#include "wave_file_host.hpp"
 
 #include <vector>
 
@@ -188,64 +189,8 @@ int vga_hca_write(const vga_hca_info *h, const uint8_t *frames, const char *comm
 }  // extern "C"
 
 // ---------------------------------------------------------------- WAVE, 16-bit PCM
-namespace {
-
-const uint8_t kSubtypePcm[16] = {0x01, 0x00, 0x00, 0x00, 0x00, 0x00, 0x10, 0x00, 0x80, 0x00, 0x00, 0xAA, 0x00, 0x38, 0x9B, 0x71};
-
-int wave_channel_mask(int n)                                // WaveWriter.cs:147-164
-{
-    switch (n) {
-    case 4: return 0x0033;
-    case 5: return 0x0133;
-    case 6: return 0x0633;
-    case 7: return 0x01f3;
-    case 8: return 0x06f3;
-    default: return (int)((1u << (n & 31)) - 1);
-    }
-}
-
-int wave_header_size(const vga_wave_params *p, int nch) { return 12 + 8 + (nch > 2 ? 40 : 16) + (p->looping ? 8 + 0x3c : 0) + 8; }
-
-// WriteRiffHeader / WriteFmtChunk / WriteSmplChunk / the data chunk's header (WaveWriter.cs:56-129); every chunk
-// size here is even, so the reference's 2-byte alignment steps never move the position
-void wave_header(const vga_wave_params *p, int nch, int64_t file_size, uint8_t *out, int bytes_per_sample = 2)
-{
-    const int bps = bytes_per_sample;
-    ByteWriter w{out, wave_header_size(p, nch)};
-    w.tag("RIFF");
-    w.put32((int)(file_size - 8));
-    w.tag("WAVE");
-    w.tag("fmt ");
-    w.put32(nch > 2 ? 40 : 16);
-    w.put16(nch > 2 ? 0xFFFE : 1);
-    w.put16(nch);
-    w.put32(p->sample_rate);
-    w.put32(p->sample_rate * bps * nch);
-    w.put16(bps * nch);
-    w.put16(8 * bps);
-    if (nch > 2) {
-        w.put16(22);
-        w.put16(8 * bps);
-        w.put32(wave_channel_mask(nch));
-        w.bytes(kSubtypePcm, 16);
-    }
-    if (p->looping) {
-        w.tag("smpl");
-        w.put32(0x3c);
-        for (int i = 0; i < 7; i++) w.put32(0);
-        w.put32(1);
-        for (int i = 0; i < 3; i++) w.put32(0);
-        w.put32(p->loop_start);
-        w.put32(p->loop_end);
-        w.put32(0);
-        w.put32(0);
-    }
-    w.tag("data");
-    w.put32(nch * p->sample_count * bps);
-}
-
-}  // namespace
-
+// The writers' size and header math and the readers' checks are wave_file_host.hpp's: one copy for these calls and for sets
+// of files (include/vgaudio_hip_files/wave_files.h).
 extern "C" {
 
 // WaveReader.ReadFile + ToAudioStream up to the audio itself (WaveReader.cs:13-68, RiffParser.cs:36-78): host only.
@@ -282,7 +227,7 @@ int vga_wave_parse(const uint8_t *file, int64_t file_len, vga_wave_info *w)
                 const int ext_size = r.i16();
                 r.i16();
                 r.i32();
-                if (r.has(16)) { ext_pcm = std::memcmp(file + r.pos, kSubtypePcm, 16) == 0; r.pos += 16; }
+                if (r.has(16)) { ext_pcm = std::memcmp(file + r.pos, kWaveSubtypePcm, 16) == 0; r.pos += 16; }
                 have_ext = true;
                 r.skip_to(ext_body + ext_size);
             }
@@ -354,9 +299,8 @@ int vga_wave_deinterleave_pcm16_device(const uint8_t *d_data, int sample_count, 
 int vga_wave_read_pcm16(const uint8_t *file, int64_t file_len, const vga_wave_info *w, int16_t *const *pcm_out)
 {
     if (!file || !w || !pcm_out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
-    if (w->bits_per_sample != 16) { set_error("only 16-bit PCM is converted here (Pcm8 is outside this path)"); return VGA_ERR_ARGUMENT; }
+    if (int rc = wave_read16_check(w, file_len)) return rc;
     const int64_t bytes = (int64_t)w->sample_count * w->channel_count * 2;
-    if (w->data_offset < 0 || w->data_offset + bytes > file_len) { set_error("info does not describe this file"); return VGA_ERR_ARGUMENT; }
     if (bytes == 0) return VGA_OK;
     for (int c = 0; c < w->channel_count; c++)
         if (!pcm_out[c]) { set_error("pcm_out[%d] is null", c); return VGA_ERR_ARGUMENT; }
@@ -370,10 +314,7 @@ int vga_wave_read_pcm16(const uint8_t *file, int64_t file_len, const vga_wave_in
 // WaveWriter.FileSize (WaveWriter.cs:25-30), 16-bit
 int64_t vga_wave_file_size(const vga_wave_params *p, int nch)
 {
-    if (!p || nch < 1 || nch > 0x7FFF || p->sample_count < 0) { set_error("bad WAVE parameters"); return VGA_ERR_ARGUMENT; }
-    const int64_t size = wave_header_size(p, nch) + (int64_t)nch * p->sample_count * 2;
-    if (size > 0x7FFFFFFF) { set_error("WAVE file would exceed 2 GiB (FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
-    return size;
+    return wave_file_size(p, nch, 2);
 }
 
 int vga_wave_write_pcm16_device(const int16_t *d_pcm, int64_t pcm_pitch, int nch, const vga_wave_params *p, uint8_t *d_file,
@@ -422,10 +363,7 @@ extern "C" {
 // WaveWriter.FileSize (WaveWriter.cs:25-30) with BytesPerSample 1: DataChunkSize = nch * samples, odd sizes included
 int64_t vga_wave_pcm8_file_size(const vga_wave_params *p, int nch)
 {
-    if (!p || nch < 1 || nch > 0x7FFF || p->sample_count < 0) { set_error("bad WAVE parameters"); return VGA_ERR_ARGUMENT; }
-    const int64_t size = wave_header_size(p, nch) + (int64_t)nch * p->sample_count;
-    if (size > 0x7FFFFFFF) { set_error("WAVE file would exceed 2 GiB (FileSize is an int)"); return VGA_ERR_OUT_OF_RANGE; }
-    return size;
+    return wave_file_size(p, nch, 1);
 }
 
 int vga_wave_write_pcm8_device(const void *d_samples, int sample_kind, int64_t pitch, int nch, const vga_wave_params *p,
@@ -479,14 +417,8 @@ int vga_wave_read_pcm8(const uint8_t *file, int64_t file_len, const vga_wave_inf
 {
     if (!file || !w || !out) { set_error("null argument"); return VGA_ERR_ARGUMENT; }
     if (int rc = check_sample_kind(sample_kind)) return rc;
-    if (w->bits_per_sample != 8) { set_error("only 8-bit PCM is read here (vga_wave_read_pcm16 reads 16-bit files)"); return VGA_ERR_ARGUMENT; }
-    if (w->channel_count < 1) { set_error("info does not describe this file"); return VGA_ERR_ARGUMENT; }
-    if (w->data_size % w->channel_count != 0) {                                                        // Interleave.cs:83-85
-        set_error("The input array length (%d) must be divisible by the number of outputs.", w->data_size);
-        return VGA_ERR_INVALID_DATA;
-    }
+    if (int rc = wave_read8_check(w, file_len)) return rc;
     const int64_t bytes = (int64_t)w->sample_count * w->channel_count;
-    if (w->data_offset < 0 || w->data_offset + bytes > file_len) { set_error("info does not describe this file"); return VGA_ERR_ARGUMENT; }
     for (int c = 0; c < w->channel_count; c++)
         if (!out[c]) { set_error("out[%d] is null", c); return VGA_ERR_ARGUMENT; }
     if (bytes == 0) return VGA_OK;

@@ -126,6 +126,22 @@ def _gc_file(channels, sample_rate, sample_count, looping=False, loop_start=0, l
                                               int(samples_per_entry)))
 
 
+def stream_handle(stream):
+    """the hipStream_t of a torch stream, or of torch's current stream: what every file set's device calls take"""
+    import torch
+    return C.c_void_p((stream if stream is not None else torch.cuda.current_stream()).cuda_stream)
+
+
+def device_ptr(t, dtype, count, what):
+    """the address of a file set's buffer: None, or a contiguous device tensor of `dtype` with at least `count` elements"""
+    import torch
+    if t is None:
+        return None
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() >= count):
+        raise _lib.ArgumentError("%s: a contiguous %s tensor on the device of at least %d elements" % (what, dtype, count))
+    return t.data_ptr()
+
+
 class DspFileSet:
     """A set of GC-ADPCM files of different shapes, resident on the device (include/vgaudio_hip/gc_files.h has the layout): the
     channels of all files are the packed rows of one ragged batch, the seek tables one packed buffer, the DSP images another.
@@ -215,19 +231,8 @@ class DspFileSet:
 
     __del__ = close
 
-    @staticmethod
-    def _stream(stream):
-        import torch
-        return C.c_void_p((stream if stream is not None else torch.cuda.current_stream()).cuda_stream)
-
-    @staticmethod
-    def _ptr(t, dtype, count, what):
-        import torch
-        if t is None:
-            return None
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() >= count):
-            raise _lib.ArgumentError("%s: a contiguous %s tensor on the device of at least %d elements" % (what, dtype, count))
-        return t.data_ptr()
+    _stream = staticmethod(lambda stream: stream_handle(stream))
+    _ptr = staticmethod(lambda t, dtype, count, what: device_ptr(t, dtype, count, what))
 
     def build_channels(self, adpcm, coefs, pcm=None, seek=None, loop_context=None, status=None, workspace=None, stream=None):
         """vga_gcadpcm_build_channels_device_v.  adpcm: uint8[totals.adpcm_bytes], coefs: int16[channels*16]; outputs (each may be
