@@ -1,0 +1,149 @@
+// idsp_files_host_driver.cpp -- vgaudio_amd/csrc/idsp_files_host.hpp (and the IDSP half of gc_stream_host.hpp under it; the HPS half: hps_files_host_driver.cpp) on its own
+// (tests/test_idsp_files_host.py): the headers with a set_error / last_error of this file's, no HIP and no product library,
+// built with g++ -fsanitize=address,undefined and run as a child process.  `idsp_files_host_driver cases.bin results.bin` runs
+// every case of cases.bin and writes what the headers answered:
+//   cases.bin    int32 n; n x { int32 kind;
+//                  kind 0 (vga_idsp_files_layout_for's arguments): int32 nfiles, block_size, trim_file; nfiles x int32[6] the
+//                         fields of vga_idsp_file
+//                  kind 1 (vga_idsp_files_create_from_infos's): int32 nfiles, has_offsets; nfiles x int32[7] (channel_count,
+//                         sample_count, adpcm_bytes, interleave, audio_data_offset, audio_data_length, sample_rate);
+//                         int64 offsets[nfiles] when has_offsets
+//                  kind 2 (vga_idsp_layout_for's): int32 nch; the bytes of a vga_idsp_params }
+//   results.bin  per case: int32 rc, message length, message bytes; when rc == 0
+//                  kind 2: the bytes of the vga_idsp_layout
+//                  kinds 0, 1: int32 nfiles, nch, first_channel[nfiles]; int64 image_off[nfiles]; int32 image_size[nfiles], counts[nch];
+//                  int64 adpcm_off[nch]; int32 file[nch]; int64 pcm_samples, adpcm_bytes, image_bytes;
+//                  nfiles x { uint32 input_size, interleave, output_size, granule16; int32 audio_offset, header_size, nch };
+//                  int32 regions; regions x { int32 kernel, index, granule; int64 begin, end }
+// Every array handed to the headers is a heap block of exactly its size.  Prints "<cases> ok".
+#include "../../vgaudio_amd/csrc/idsp_files_host.hpp"
+
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+namespace {
+char g_error[512];
+}
+
+void vga::set_error(const char *fmt, ...)
+{
+    char next[sizeof g_error];                             // the arguments may point into g_error
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(next, sizeof next, fmt, ap);
+    va_end(ap);
+    memcpy(g_error, next, sizeof g_error);
+}
+const char *vga::last_error() { return g_error; }
+
+using namespace vga;
+
+namespace {
+
+template <class T> bool read_n(FILE *f, T *out, size_t count) { return count == 0 || fread(out, sizeof(T), count, f) == count; }
+template <class T> void put(FILE *f, const T &v) { fwrite(&v, sizeof(T), 1, f); }
+
+void put_status(FILE *out, int rc)
+{
+    put(out, rc);
+    const int len = (int)strlen(g_error);
+    put(out, len);
+    fwrite(g_error, 1, (size_t)len, out);
+}
+
+void write_layout(FILE *out, const idf::FilesLayout &L)
+{
+    const int nfiles = L.totals.files, nch = L.totals.channels;
+    put(out, nfiles);
+    put(out, nch);
+    for (int f = 0; f < nfiles; f++) put(out, L.first_channel[f]);
+    for (int f = 0; f < nfiles; f++) put(out, L.image_off[f]);
+    for (int f = 0; f < nfiles; f++) put(out, L.image_size[f]);
+    for (int c = 0; c < nch; c++) put(out, L.counts[c]);
+    for (int c = 0; c < nch; c++) put(out, L.channel[c].adpcm_off);
+    for (int c = 0; c < nch; c++) put(out, L.channel[c].file);
+    const int64_t totals[3] = {L.totals.pcm_samples, L.totals.adpcm_bytes, L.totals.image_bytes};
+    fwrite(totals, sizeof totals, 1, out);
+    for (const idf::FileTab &t : L.tab) {
+        const uint32_t a[4] = {t.audio.input_size, t.audio.interleave, t.audio.output_size, t.audio.granule16};
+        const int v[3] = {t.audio_offset, t.h.header_size, t.audio.channels};
+        fwrite(a, sizeof a, 1, out);
+        fwrite(v, sizeof v, 1, out);
+    }
+    std::vector<vga_idsp_files_region> r;
+    idf::regions_of(L, r);
+    put(out, (int)r.size());
+    for (const vga_idsp_files_region &x : r) { put(out, x.kernel); put(out, x.index); put(out, x.granule); put(out, x.begin); put(out, x.end); }
+}
+
+}  // namespace
+
+int main(int argc, char **argv)
+{
+    FILE *in = argc > 2 ? fopen(argv[1], "rb") : nullptr;
+    FILE *out = in ? fopen(argv[2], "wb") : nullptr;
+    if (!in || !out) { printf("usage: idsp_files_host_driver cases.bin results.bin\n"); return 2; }
+    int n = 0;
+    if (!read_n(in, &n, 1)) return 2;
+    for (int i = 0; i < n; i++) {
+        int kind = 0, nfiles = 0;
+        if (!read_n(in, &kind, 1) || !read_n(in, &nfiles, 1)) return 2;
+        g_error[0] = 0;
+        int rc = 0;
+        if (kind == 2) {                                   // nfiles holds the channel count
+            vga_idsp_params *p = static_cast<vga_idsp_params *>(malloc(sizeof *p));
+            vga_idsp_layout *N = static_cast<vga_idsp_layout *>(malloc(sizeof *N));
+            if (!read_n(in, p, 1)) return 2;
+            rc = gcs::idsp_layout(p, nfiles, N);
+            put_status(out, rc);
+            if (rc == 0) fwrite(N, sizeof *N, 1, out);
+            free(N);
+            free(p);
+            continue;
+        }
+        const size_t count = nfiles > 0 ? (size_t)nfiles : 0;
+        idf::FilesLayout *L = new idf::FilesLayout;
+        if (kind == 0) {
+            int c[2];
+            if (!read_n(in, c, 2)) return 2;
+            vga_idsp_file_config *cfg = static_cast<vga_idsp_file_config *>(malloc(sizeof *cfg));
+            *cfg = {c[0], c[1]};
+            vga_idsp_file *files = static_cast<vga_idsp_file *>(malloc(count * sizeof(vga_idsp_file)));
+            for (size_t f = 0; f < count; f++) {
+                int v[6];
+                if (!read_n(in, v, 6)) return 2;
+                files[f] = {v[0], v[1], v[2], v[3], v[4], v[5]};
+            }
+            rc = idf::make_layout(count ? files : nullptr, nfiles, cfg, *L);
+            free(files);
+            free(cfg);
+        } else {
+            int has_offsets = 0;
+            if (!read_n(in, &has_offsets, 1)) return 2;
+            vga_idsp_info **infos = static_cast<vga_idsp_info **>(malloc(count * sizeof(vga_idsp_info *)));
+            for (size_t f = 0; f < count; f++) {
+                int v[7];
+                if (!read_n(in, v, 7)) return 2;
+                vga_idsp_info *I = static_cast<vga_idsp_info *>(calloc(1, sizeof(vga_idsp_info)));
+                I->channel_count = v[0]; I->sample_count = v[1]; I->adpcm_bytes = v[2]; I->interleave = v[3];
+                I->audio_data_offset = v[4]; I->audio_data_length = v[5]; I->sample_rate = v[6];
+                infos[f] = I;
+            }
+            int64_t *offsets = has_offsets ? static_cast<int64_t *>(malloc(count * sizeof(int64_t))) : nullptr;
+            if (has_offsets && !read_n(in, offsets, count)) return 2;
+            rc = idf::make_layout_from_infos(count ? infos : nullptr, nfiles, offsets, *L);
+            free(offsets);
+            for (size_t f = 0; f < count; f++) free(infos[f]);
+            free(infos);
+        }
+        put_status(out, rc);
+        if (rc == 0) write_layout(out, *L);
+        delete L;
+    }
+    fclose(in);
+    fclose(out);
+    printf("%d ok\n", n);
+    return 0;
+}

@@ -230,6 +230,34 @@ SIGNATURES = {
     "vga_nw_files_ragged": (vp, [vp]),
     "vga_nwstm_write_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "vga_nwstm_read_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    # include/vgaudio_hip_files/idsp_files.h
+    "vga_idsp_files_layout_for": (ci, [vp, ci, vp, C.POINTER(ci), C.POINTER(i64), vp]),
+    "vga_idsp_files_create": (ci, [vp, ci, vp, C.POINTER(vp)]),
+    "vga_idsp_files_create_from_infos": (ci, [C.POINTER(vp), ci, C.POINTER(i64), C.POINTER(vp)]),
+    "vga_idsp_files_destroy": (None, [vp]),
+    "vga_idsp_files_totals_of": (ci, [vp, vp]),
+    "vga_idsp_files_offsets": (ci, [vp, C.POINTER(ci), C.POINTER(i64)]),
+    "vga_idsp_files_gc_files": (ci, [vp, vp]),
+    "vga_idsp_files_ragged": (vp, [vp]),
+    "vga_idsp_write_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "vga_idsp_read_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "vga_idsp_files_write_regions_for": (ci, [vp, ci, vp, vp, i64, C.POINTER(i64)]),
+    "vga_idsp_files_read_regions_for": (ci, [C.POINTER(vp), ci, C.POINTER(i64), vp, i64, C.POINTER(i64)]),
+    "vga_idsp_files_stats": (ci, [vp, C.POINTER(i64)]),
+    # include/vgaudio_hip_files/hps_files.h
+    "vga_hps_files_layout_for": (ci, [vp, ci, C.POINTER(ci), C.POINTER(i64), C.POINTER(i64), vp]),
+    "vga_hps_files_create": (ci, [vp, ci, C.POINTER(vp)]),
+    "vga_hps_files_create_from_infos": (ci, [C.POINTER(vp), C.POINTER(vp), ci, C.POINTER(i64), C.POINTER(vp)]),
+    "vga_hps_files_destroy": (None, [vp]),
+    "vga_hps_files_totals_of": (ci, [vp, vp]),
+    "vga_hps_files_offsets": (ci, [vp, C.POINTER(ci), C.POINTER(i64), C.POINTER(i64)]),
+    "vga_hps_files_gc_files": (ci, [vp, vp]),
+    "vga_hps_files_ragged": (vp, [vp]),
+    "vga_hps_write_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "vga_hps_read_device_v": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "vga_hps_files_write_regions_for": (ci, [vp, ci, vp, i64, C.POINTER(i64)]),
+    "vga_hps_files_read_regions_for": (ci, [C.POINTER(vp), C.POINTER(vp), ci, C.POINTER(i64), vp, i64, C.POINTER(i64)]),
+    "vga_hps_files_stats": (ci, [vp, C.POINTER(i64)]),
     "vga_hca_decode_device_v": (ci, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
     "vga_hca_encode_device_v": (ci, [vp, vp, vp, vp, vp]),
     "vga_hca_stream_create": (ci, [vp, vp, C.POINTER(vp)]),
@@ -630,6 +658,43 @@ class IdspInfoC(C.Structure):
                    ("gain", C.c_int16 * _GCM), ("start_context", (C.c_int16 * 3) * _GCM),
                    ("loop_context", (C.c_int16 * 3) * _GCM)]
                 + [(n, C.c_int) for n in ("interleave", "adpcm_bytes")])
+
+
+class IdspFileC(C.Structure):
+    """vga_idsp_file (include/vgaudio_hip_files/idsp_files.h)"""
+    _fields_ = [(n, C.c_int) for n in ("channels", "sample_rate", "sample_count", "looping", "loop_start", "loop_end")]
+
+
+class IdspFileConfigC(C.Structure):
+    """vga_idsp_file_config"""
+    _fields_ = [("block_size", C.c_int), ("trim_file", C.c_int)]
+
+
+class IdspFilesTotalsC(C.Structure):
+    """vga_idsp_files_totals"""
+    _fields_ = [("files", C.c_int), ("channels", C.c_int), ("pcm_samples", C.c_int64), ("adpcm_bytes", C.c_int64),
+                ("image_bytes", C.c_int64)]
+
+
+class IdspFilesRegionC(C.Structure):
+    """vga_idsp_files_region"""
+    _fields_ = [("kernel", C.c_int), ("index", C.c_int), ("granule", C.c_int), ("begin", C.c_int64), ("end", C.c_int64)]
+
+
+class HpsFileC(C.Structure):
+    """vga_hps_file (include/vgaudio_hip_files/hps_files.h)"""
+    _fields_ = [(n, C.c_int) for n in ("channels", "sample_rate", "sample_count", "looping", "loop_start", "loop_end")]
+
+
+class HpsFilesTotalsC(C.Structure):
+    """vga_hps_files_totals"""
+    _fields_ = [("files", C.c_int), ("channels", C.c_int), ("pcm_samples", C.c_int64), ("adpcm_bytes", C.c_int64),
+                ("image_bytes", C.c_int64), ("blocks", C.c_int64)]
+
+
+class HpsFilesRegionC(C.Structure):
+    """vga_hps_files_region"""
+    _fields_ = [("kernel", C.c_int), ("index", C.c_int), ("granule", C.c_int), ("begin", C.c_int64), ("end", C.c_int64)]
 
 
 class GenhInfoC(C.Structure):

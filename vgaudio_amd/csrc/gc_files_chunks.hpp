@@ -11,6 +11,7 @@ namespace vga {
 namespace gcf {
 
 template <int G> struct Granule;                  // (container_kernels.hpp's; that header's launchers would instantiate their kernels in the includer)
+template <> struct Granule<1> { using type = uint8_t; };   // the general form of a read (idsp_files_kernels.hip)
 template <> struct Granule<8> { using type = uint2; };
 template <> struct Granule<16> { using type = uint4; };
 
