@@ -47,8 +47,9 @@
  * the guards.  The object keeps its tables in the memory of the device that was current at create, is immutable and
  * serves any number of calls, concurrent calls on different streams included.
  *
- * LEFT OUT: sets of HPS and IDSP files, host-pointer forms of the _v calls, PCM8 / PCM16 NintendoWare streams in sets, custom
- * track lists in sets, the seek tables on the read side (vga_nwstm_read delivers them per file). */
+ * LEFT OUT: sets of HPS and IDSP files, host-pointer forms of the _v calls, custom track lists in sets, the seek tables on the
+ * read side (vga_nwstm_read delivers them per file).  PCM8 / PCM16 NintendoWare streams in sets are
+ * ../vgaudio_hip_files/nw_pcm_files.h's. */
 #ifndef VGAUDIO_HIP_NW_FILES_H
 #define VGAUDIO_HIP_NW_FILES_H
 

@@ -388,6 +388,19 @@ SIGNATURES = {
     "vga_wave_files_read_items_for": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), ci, vp, i64, C.POINTER(i64)]),
     "vga_wave_files_stats": (ci, [vp, C.POINTER(i64)]),
     "vga_wave_files_force_general_this_thread": (ci, [ci]),
+    # include/vgaudio_hip_files/nw_pcm_files.h
+    "vga_nw_pcm_files_layout_for": (ci, [vp, ci, vp, ci, C.POINTER(i64), C.POINTER(i64), C.POINTER(ci), C.POINTER(i64), C.POINTER(i64), vp]),
+    "vga_nw_pcm_files_create": (ci, [vp, ci, vp, ci, C.POINTER(i64), C.POINTER(i64), C.POINTER(vp)]),
+    "vga_nw_pcm_files_create_from_infos": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), C.POINTER(vp)]),
+    "vga_nw_pcm_files_destroy": (None, [vp]),
+    "vga_nw_pcm_files_totals_of": (ci, [vp, vp]),
+    "vga_nw_pcm_files_offsets": (ci, [vp, C.POINTER(ci), C.POINTER(i64), C.POINTER(i64)]),
+    "vga_nwstm_pcm_write_device_v": (ci, [vp, vp, vp, vp]),
+    "vga_nwstm_pcm_read_device_v": (ci, [vp, vp, vp, vp]),
+    "vga_nw_pcm_files_write_items_for": (ci, [vp, ci, vp, ci, C.POINTER(i64), C.POINTER(i64), ci, vp, i64, C.POINTER(i64)]),
+    "vga_nw_pcm_files_read_items_for": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), ci, vp, i64, C.POINTER(i64)]),
+    "vga_nw_pcm_files_stats": (ci, [vp, C.POINTER(i64)]),
+    "vga_nw_pcm_files_force_general_this_thread": (ci, [ci]),
     # include/vgaudio_hip/hca_files.h
     "vga_hca_files_layout_for": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp]),
     "vga_hca_files_create": (ci, [vp, ci, C.POINTER(i64), vp, ci, C.POINTER(vp)]),
@@ -580,6 +593,17 @@ class NwFilesTotalsC(C.Structure):
     """vga_nw_files_totals"""
     _fields_ = [("files", C.c_int), ("channels", C.c_int), ("pcm_samples", C.c_int64), ("adpcm_bytes", C.c_int64),
                 ("seek_shorts", C.c_int64), ("image_bytes", C.c_int64)]
+
+
+class NwPcmFilesTotalsC(C.Structure):
+    """vga_nw_pcm_files_totals (include/vgaudio_hip_files/nw_pcm_files.h)"""
+    _fields_ = [("files", C.c_int), ("channels", C.c_int), ("pcm_samples", C.c_int64), ("image_bytes", C.c_int64)]
+
+
+class NwPcmFilesItemC(C.Structure):
+    """vga_nw_pcm_files_item"""
+    _fields_ = [("form", C.c_int), ("file", C.c_int), ("x", C.c_int), ("y", C.c_uint32), ("conv", C.c_int),
+                ("begin", C.c_int64), ("end", C.c_int64)]
 
 
 class NwWavInfoC(C.Structure):

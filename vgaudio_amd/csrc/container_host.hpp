@@ -16,13 +16,6 @@
 namespace vga {
 namespace container {
 
-inline int check_sample_kind(int kind)
-{
-    if (kind == VGA_SAMPLES_S16 || kind == VGA_SAMPLES_8BIT) return VGA_OK;
-    set_error("unknown sample kind %d", kind);
-    return VGA_ERR_ARGUMENT;
-}
-
 // Big- or little-endian writes into `size` bytes of host memory; what does not fit sets `overflow` and is dropped.
 struct ByteWriter {
     uint8_t *buf;

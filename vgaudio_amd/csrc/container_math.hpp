@@ -3,6 +3,7 @@
 // that stand-alone host programs include (nw_host.hpp) use them as container_host.hpp does.
 #pragma once
 #include "gc_host.hpp"
+#include "../../include/vgaudio_hip_pcm.h"
 
 namespace vga {
 namespace container {
@@ -14,6 +15,14 @@ inline int64_t next_multiple(int64_t v, int64_t m) { return m <= 0 || v % m == 0
 // Extensions.cs:145, (int)Math.Ceiling((double)v / d): a negative quotient rounds towards zero (-1 / 8 -> 0)
 inline int div_round_up(int v, int d) { return v / d + (v % d != 0 && (v < 0) == (d < 0) ? 1 : 0); }
 inline int bytes_of(int samples) { return gc::sample_count_to_byte_count(samples); }
+
+// the kind of pitched planar rows a PCM call takes or gives (vgaudio_hip_pcm.h)
+inline int check_sample_kind(int kind)
+{
+    if (kind == VGA_SAMPLES_S16 || kind == VGA_SAMPLES_8BIT) return VGA_OK;
+    set_error("unknown sample kind %d", kind);
+    return VGA_ERR_ARGUMENT;
+}
 
 // AudioFormatBaseBuilder.WithLoop (:30-43)
 inline int check_loop(int looping, int loop_start, int loop_end, int sample_count)

@@ -1,7 +1,8 @@
 // nw_host.hpp -- the host side of the NintendoWare streams (nwstm.hip, nw_files_host.hpp) without HIP: the constants of the
 // formats, the version predicates, BxstmConfiguration's rules and the size math of BrstmWriter.cs / BCFstmWriter.cs
-// (nw_layout), and the numbers the header kernels write (HeaderGeom).  Header-only and free of <hip/hip_runtime.h>, so that a
-// stand-alone host program can include it (tests/host/nw_files_host_driver.cpp); whoever includes it supplies vga::set_error.
+// (nw_layout), the PCM readers' check of a parsed info, and the numbers the header kernels write (HeaderGeom).  Header-only
+// and free of <hip/hip_runtime.h>, so that a stand-alone host program can include it (tests/host/nw_files_host_driver.cpp);
+// whoever includes it supplies vga::set_error.
 #pragma once
 #include "container_math.hpp"
 
@@ -159,6 +160,23 @@ inline int nw_layout(const vga_nwstm_params *p, int codec, int nch, vga_nwstm_la
     L->audio_data_offset = L->data_block_offset + 0x20;
     L->audio_data_size = (int)audio_data_size;
     L->file_size = (int)file;
+    return VGA_OK;
+}
+
+// What vga_nwstm_pcm_read_device checks of a parsed info before it looks at a pointer, for that call and for every file of a
+// set for reading (nw_pcm_files_host.hpp) alike.  moves: the call has images to read; the geometry is looked at only then, and
+// only of a stream that has samples.
+inline int pcm_read_info_check(const vga_nwstm_info *I, int sample_kind, bool moves)
+{
+    if (I->codec != kCodecPcm8 && I->codec != kCodecPcm16) { set_error("info is not a PCM8 / PCM16 stream (vga_nwstm_pcm_parse)"); return VGA_ERR_ARGUMENT; }
+    if (int rc = check_sample_kind(sample_kind)) return rc;
+    if (I->codec == kCodecPcm16 && sample_kind != VGA_SAMPLES_S16) { set_error("a PCM16 stream is read to VGA_SAMPLES_S16 rows"); return VGA_ERR_ARGUMENT; }
+    if (!moves || I->adpcm_bytes == 0) return VGA_OK;
+    const int nch = I->channel_count, bps = I->codec == kCodecPcm16 ? 2 : 1;
+    if (nch < 1 || I->interleave_size <= 0 || I->audio_data_length < 0 || I->audio_data_length % nch || I->adpcm_bytes != I->sample_count * bps) {
+        set_error("info does not describe a stream");
+        return VGA_ERR_ARGUMENT;
+    }
     return VGA_OK;
 }
 

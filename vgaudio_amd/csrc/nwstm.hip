@@ -582,16 +582,9 @@ int vga_nwstm_pcm_read_device(const vga_nwstm_info *I, const uint8_t *d_files, i
                               int sample_kind, int64_t pitch, void *stream)
 {
     if (!I || nfiles < 0) { set_error("null / negative argument"); return VGA_ERR_ARGUMENT; }
-    if (I->codec != kCodecPcm8 && I->codec != kCodecPcm16) { set_error("info is not a PCM8 / PCM16 stream (vga_nwstm_pcm_parse)"); return VGA_ERR_ARGUMENT; }
-    if (int rc = check_sample_kind(sample_kind)) return rc;
-    if (I->codec == kCodecPcm16 && sample_kind != VGA_SAMPLES_S16) { set_error("a PCM16 stream is read to VGA_SAMPLES_S16 rows"); return VGA_ERR_ARGUMENT; }
-    const int bps = I->codec == kCodecPcm16 ? 2 : 1;
+    if (int rc = nw::pcm_read_info_check(I, sample_kind, nfiles > 0)) return rc;
     if (nfiles == 0 || I->adpcm_bytes == 0) return VGA_OK;
     const int nch = I->channel_count;
-    if (nch < 1 || I->interleave_size <= 0 || I->audio_data_length < 0 || I->audio_data_length % nch || I->adpcm_bytes != I->sample_count * bps) {
-        set_error("info does not describe a stream");
-        return VGA_ERR_ARGUMENT;
-    }
     if (int rc = check_read_batch(d_files, d_samples, pitch, I->sample_count, nfiles, file_pitch,
                                   (int64_t)I->audio_data_offset + I->audio_data_length))
         return rc;

@@ -539,10 +539,13 @@ def write_files(pcm16_list, target, configuration=None):
     """BrstmWriter / BCFstmWriter(target)(configuration).GetFile(GcAdpcmFormat().EncodeFromPcm16(file)) for a list of Pcm16Format
     files -- with NwTarget.Revolution the whole of VGAudio.Cli/Batch.cs -- on the device and without a launch per file: one
     upload, vga_gcadpcm_coefs_device_v, vga_gcadpcm_encode_device_v, the alignment re-encode of gcadpcm.AlignedFileSet,
-    vga_nwstm_write_device_v, one download.  Returns one `bytes` per file."""
+    vga_nwstm_write_device_v, one download.  Returns one `bytes` per file.  With configuration.Codec Pcm16Bit or Pcm8Bit the
+    files are what GetFile(file) gives for that configuration, through vga_nwstm_pcm_write_device_v (NwPcmFileSet)."""
     import torch
     from .gcadpcm import AlignedFileSet
     files = list(pcm16_list)
+    if isinstance(configuration, BxstmConfiguration) and configuration.Codec in (NwCodec.Pcm16Bit, NwCodec.Pcm8Bit):
+        return _write_pcm_files(files, target, configuration)
     L = _lib.lib()
     s = NwFileSet([(f.ChannelCount, f.SampleRate, f.SampleCount, f.Looping, f.LoopStart if f.Looping else 0,
                     f.LoopEnd if f.Looping else 0) for f in files], target, configuration)
@@ -576,3 +579,218 @@ def write_files(pcm16_list, target, configuration=None):
         if a is not None:
             a.close()
         s.close()
+
+
+# ------------------------------------------------ sets of PCM files on the device (include/vgaudio_hip_files/nw_pcm_files.h)
+def _pcm_file_config(target, configuration):
+    """(vga_nw_file_config, codec) of a target and a BxstmConfiguration whose Codec is Pcm16Bit or Pcm8Bit"""
+    c = configuration or BxstmConfiguration(Codec=NwCodec.Pcm16Bit)
+    if c.Codec not in (NwCodec.Pcm16Bit, NwCodec.Pcm8Bit):
+        raise _lib.ArgumentError("sets of PCM NintendoWare files hold Pcm16Bit or Pcm8Bit streams (NwFileSet for GC-ADPCM)")
+    cfg = _lib.NwFileConfigC(int(NwTarget(target)), c.SamplesPerInterleave, c.SamplesPerSeekTableEntry, c.LoopPointAlignment,
+                             int(c.TrackType), int(c.SeekTableType), c.Version.Version if c.Version is not None else 0,
+                             -1 if c.Endianness is None else int(c.Endianness))
+    return cfg, int(c.Codec)
+
+
+def _i64_or_none(values):
+    if values is None:
+        return None, None
+    a = np.ascontiguousarray(values, dtype=np.int64)
+    return a, a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+class NwPcmFileSet:
+    """A set of PCM16 / PCM8 BRSTM / BCSTM / BFSTM files of different shapes, resident on the device
+    (include/vgaudio_hip_files/nw_pcm_files.h has the layout): the channels of all files are packed int16 rows of ONE buffer,
+    as wave.read_files_device leaves them, or at the caller's `pcm_offsets` (samples); the images one buffer, packed or at the
+    caller's `image_offsets`.  `files`: one (channels, sample_rate, sample_count, looping, loop_start, loop_end) tuple or
+    _lib.NwFileC per file; `target`: NwTarget; `configuration`: the BxstmConfiguration of the whole set, its Codec Pcm16Bit
+    or Pcm8Bit.  The tensors are the caller's torch tensors on the current device; the calls run on torch's current stream
+    and do not synchronise it."""
+
+    def __init__(self, files=None, target=NwTarget.Revolution, configuration=None, pcm_offsets=None, image_offsets=None, _handle=None):
+        self._h, self.image_sizes = C.c_void_p(), None
+        if _handle is not None:
+            self._h = _handle
+        else:
+            arr, n = NwFileSet._files_array(files)
+            cfg, codec = _pcm_file_config(target, configuration)
+            keep_p, po = _i64_or_none(pcm_offsets)
+            keep_i, io = _i64_or_none(image_offsets)
+            check(_lib.lib().vga_nw_pcm_files_create(arr, n, C.byref(cfg), codec, po, io, C.byref(self._h)))
+            self.image_sizes = [self.file_layout(arr[i], cfg, codec).file_size for i in range(n)]
+        self.totals = _lib.NwPcmFilesTotalsC()
+        check(_lib.lib().vga_nw_pcm_files_totals_of(self._h, C.byref(self.totals)))
+        nf, nch = self.totals.files, self.totals.channels
+        fc, po, io = np.zeros(max(nf, 1), np.int32), np.zeros(max(nch, 1), np.int64), np.zeros(max(nf, 1), np.int64)
+        i64p = C.POINTER(C.c_int64)
+        check(_lib.lib().vga_nw_pcm_files_offsets(self._h, fc.ctypes.data_as(C.POINTER(C.c_int)), po.ctypes.data_as(i64p), io.ctypes.data_as(i64p)))
+        self.first_channel, self.pcm_offsets, self.image_offsets = fc[:nf], po[:nch], io[:nf]
+        self.files, self.channels = nf, nch
+
+    @staticmethod
+    def file_params(f, cfg):
+        """vga_nwstm_params of one file of a set: the configuration plus the file's numbers"""
+        p = _lib.NwParamsC()
+        p.target, p.sample_rate, p.sample_count = cfg.target, f.sample_rate, f.sample_count
+        p.looping, p.loop_start, p.loop_end = f.looping, f.loop_start, f.loop_end
+        p.samples_per_interleave, p.samples_per_seek_table_entry = cfg.samples_per_interleave, cfg.samples_per_seek_table_entry
+        p.loop_point_alignment, p.track_type, p.seek_table_type = cfg.loop_point_alignment, cfg.track_type, cfg.seek_table_type
+        p.version, p.endianness = cfg.version, cfg.endianness
+        return p
+
+    @classmethod
+    def file_layout(cls, f, cfg, codec):
+        """vga_nwstm_pcm_layout_for of one file of a set"""
+        p, L = cls.file_params(f, cfg), _lib.NwLayoutC()
+        check(_lib.lib().vga_nwstm_pcm_layout_for(C.byref(p), int(codec), f.channels, C.byref(L)))
+        return L
+
+    @classmethod
+    def layout(cls, files, target=NwTarget.Revolution, configuration=None, pcm_offsets=None, image_offsets=None):
+        """(first_channel int32[files], pcm_offsets int64[channels], image_offsets int64[files], NwPcmFilesTotalsC): host only,
+        needs no GPU"""
+        arr, n = NwFileSet._files_array(files)
+        cfg, codec = _pcm_file_config(target, configuration)
+        nch = sum(arr[i].channels for i in range(n) if arr[i].channels > 0)
+        fc, po, io = np.zeros(max(n, 1), np.int32), np.zeros(max(nch, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        tot, i64p = _lib.NwPcmFilesTotalsC(), C.POINTER(C.c_int64)
+        keep_p, pin = _i64_or_none(pcm_offsets)
+        keep_i, iin = _i64_or_none(image_offsets)
+        check(_lib.lib().vga_nw_pcm_files_layout_for(arr, n, C.byref(cfg), codec, pin, iin, fc.ctypes.data_as(C.POINTER(C.c_int)),
+                                                     po.ctypes.data_as(i64p), io.ctypes.data_as(i64p), C.byref(tot)))
+        return fc[:n], po[:tot.channels], io[:n], tot
+
+    @classmethod
+    def from_infos(cls, infos, pcm_offsets=None, image_offsets=None):
+        """A set for reading, from the vga_nwstm_info of every file (parse_pcm()); image_offsets: any byte offsets, or None
+        for images packed as a set for writing packs them"""
+        infos = list(infos)
+        n = len(infos)
+        ptrs = (C.c_void_p * max(n, 1))(*[C.addressof(i) for i in infos])
+        keep_p, po = _i64_or_none(pcm_offsets)
+        keep_i, io = _i64_or_none(image_offsets)
+        h = C.c_void_p()
+        check(_lib.lib().vga_nw_pcm_files_create_from_infos(ptrs, n, po, io, C.byref(h)))
+        s = cls(_handle=h)
+        s.image_sizes = [i.audio_data_offset + i.audio_data_length for i in infos]
+        return s
+
+    @staticmethod
+    def _items(call, args, pcm_offsets, image_offsets, general):
+        keep_p, po = _i64_or_none(pcm_offsets)
+        keep_i, io = _i64_or_none(image_offsets)
+        count = C.c_int64()
+        check(call(*args, po, io, int(general), None, 0, C.byref(count)))
+        items = (_lib.NwPcmFilesItemC * max(count.value, 1))()
+        check(call(*args, po, io, int(general), items, count.value, C.byref(count)))
+        return list(items[:count.value])
+
+    @classmethod
+    def write_items(cls, files, target=NwTarget.Revolution, configuration=None, pcm_offsets=None, image_offsets=None, general=False):
+        """the work items of vga_nwstm_pcm_write_device_v on such a set (_lib.NwPcmFilesItemC), host only"""
+        arr, n = NwFileSet._files_array(files)
+        cfg, codec = _pcm_file_config(target, configuration)
+        return cls._items(_lib.lib().vga_nw_pcm_files_write_items_for, (arr, n, C.byref(cfg), codec), pcm_offsets, image_offsets, general)
+
+    @classmethod
+    def read_items(cls, infos, pcm_offsets=None, image_offsets=None, general=False):
+        """the work items of vga_nwstm_pcm_read_device_v on a set of such infos, host only"""
+        infos = list(infos)
+        ptrs = (C.c_void_p * max(len(infos), 1))(*[C.addressof(i) for i in infos])
+        return cls._items(_lib.lib().vga_nw_pcm_files_read_items_for, (ptrs, len(infos)), pcm_offsets, image_offsets, general)
+
+    def close(self):
+        if self._h:
+            _lib.lib().vga_nw_pcm_files_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def offsets(self):
+        """(first_channel, pcm_offsets, image_offsets) of the object"""
+        return self.first_channel, self.pcm_offsets, self.image_offsets
+
+    def stats(self):
+        """(vector files, general files, vector items, general items) of a call made by this thread now"""
+        out = (C.c_int64 * 4)()
+        check(_lib.lib().vga_nw_pcm_files_stats(self._h, out))
+        return tuple(out)
+
+    def write(self, pcm, images, stream=None):
+        """vga_nwstm_pcm_write_device_v.  pcm: int16[totals.pcm_samples] (the rows); images: uint8[totals.image_bytes]"""
+        import torch
+        from .dsp import device_ptr as ptr, stream_handle
+        t = self.totals
+        check(_lib.lib().vga_nwstm_pcm_write_device_v(self._h, ptr(pcm, torch.int16, t.pcm_samples, "pcm"),
+                                                      ptr(images, torch.uint8, t.image_bytes, "images"), stream_handle(stream)))
+
+    def read(self, images, pcm, stream=None):
+        """vga_nwstm_pcm_read_device_v (a set from from_infos).  images: uint8[totals.image_bytes]; pcm: int16[totals.pcm_samples]"""
+        import torch
+        from .dsp import device_ptr as ptr, stream_handle
+        t = self.totals
+        check(_lib.lib().vga_nwstm_pcm_read_device_v(self._h, ptr(images, torch.uint8, t.image_bytes, "images"),
+                                                     ptr(pcm, torch.int16, t.pcm_samples, "pcm"), stream_handle(stream)))
+
+    def images(self, host_buffer):
+        """one `bytes` per file from the images' buffer (a device tensor or a numpy array); synchronises"""
+        host = host_buffer.cpu().numpy() if hasattr(host_buffer, "cpu") else np.asarray(host_buffer, dtype=np.uint8)
+        return [host[int(at):int(at) + int(size)].tobytes() for at, size in zip(self.image_offsets, self.image_sizes)]
+
+
+def _write_pcm_files(files, target, configuration):
+    """write_files for a configuration whose Codec is Pcm16Bit or Pcm8Bit: one upload into the packed rows,
+    vga_nwstm_pcm_write_device_v, one download"""
+    import torch
+    for i, f in enumerate(files):
+        if not isinstance(f, Pcm16Format):
+            raise _lib.ArgumentError("file %d: write_files takes Pcm16Format files (decode with ToPcm16 first)" % i)
+    described = [(f.ChannelCount, f.SampleRate, f.SampleCount, f.Looping, f.LoopStart if f.Looping else 0, f.LoopEnd if f.Looping else 0)
+                 for f in files]
+    _, offsets, _, totals = NwPcmFileSet.layout(described, target, configuration)   # every refusal of a file, before anything is allocated
+    if not files:
+        return []
+    host, c = np.zeros(totals.pcm_samples, dtype=np.int16), 0
+    for f in files:
+        for ch in f.Channels:
+            host[int(offsets[c]):int(offsets[c]) + f.SampleCount] = np.asarray(ch, dtype=np.int16)[:f.SampleCount]
+            c += 1
+    s = NwPcmFileSet(described, target, configuration)
+    try:
+        images = torch.empty(s.totals.image_bytes, dtype=torch.uint8, device="cuda")
+        s.write(torch.from_numpy(host).cuda(), images)
+        return s.images(images)
+    finally:
+        s.close()
+
+
+def read_pcm_files(list_of_bytes):
+    """BrstmReader / BCFstmReader.ReadFormat(file) for a list of PCM16 / PCM8 streams, without a launch per file: one upload,
+    one vga_nwstm_pcm_read_device_v, one download.  One Pcm16Format per file with the stream's loop and tracks; a PCM8 stream
+    comes as its Pcm8SignedFormat's ToPcm16() would give it (the set's rows are int16)."""
+    import torch
+    datas = [bytes(d) for d in list_of_bytes]
+    if not datas:
+        return []
+    infos = [parse_pcm(d) for d in datas]
+    s = NwPcmFileSet.from_infos(infos)
+    try:
+        host = np.zeros(s.totals.image_bytes, dtype=np.uint8)
+        for d, at, size in zip(datas, s.image_offsets, s.image_sizes):
+            host[int(at):int(at) + size] = np.frombuffer(d, dtype=np.uint8)[:size]
+        pcm = torch.zeros(s.totals.pcm_samples, dtype=torch.int16, device="cuda")
+        s.read(torch.from_numpy(host).cuda(), pcm)
+        rows, offsets = pcm.cpu().numpy(), s.pcm_offsets
+    finally:
+        s.close()
+    out, c = [], 0
+    for info in infos:
+        chans = [rows[int(offsets[c + i]):int(offsets[c + i]) + info.sample_count].copy() for i in range(info.channel_count)]
+        c += info.channel_count
+        fmt = Pcm16Format(chans, info.sample_rate).WithLoop(bool(info.looping), info.loop_start, info.sample_count)
+        tracks = [AudioTrack(t.channel_count, t.left, t.right, t.volume, t.panning) for t in info.tracks[:info.track_count]]
+        fmt.Tracks = tracks if tracks else AudioTrack.GetDefaultTrackList(info.channel_count)
+        out.append(fmt)
+    return out
