@@ -57,6 +57,23 @@ int vga_testing_gc_plan_pieces(int cus, int groups, int frames, long long group_
  * walked, pieces encoded, 1 if this build counts the cold blocks}.
  * reset != 0 clears the counters afterwards.  Returns 0, or -1 when the device cannot be read. */
 int vga_testing_gc_encode_stats(unsigned long long *out8, int reset);
+/* ... the same with n <= 9 fields: [8] = channels with an open seam whose chain the self-served encoder walked inside its own
+ * launch (the hand-over below) -- the channels the chain kernel counts in [5] when the hand-over is switched off. */
+int vga_testing_gc_encode_stats_n(unsigned long long *out, int n, int reset);
+
+/* The self-served GC-ADPCM encoder (layout 1) on uniform batches continues an open seam into the next piece inside its own
+ * launch, as soon as that piece and its own seam run are finished, and leaves the chain kernel a record per channel; the chain
+ * kernel then walks nothing but the partial last frame of a run that never met.  on = 0: calls made from the calling thread
+ * leave every open seam to the chain kernel, as ragged batches and the other shapes do; on != 0 (the default): normal
+ * operation.  Same bytes.  Returns the previous setting. */
+int vga_testing_gc_seam_handover_this_thread(int on);
+/* With the hand-over in force the same launch takes the groups of eight channels whose seams are likely to close slowly --
+ * a predictor with complex poles next to the unit circle, vgaudio_amd/csrc/gc_plan8.hpp -- from its queue first.  The order
+ * of the groups for nch channels' coefficients (16 per channel): order[(nch + 7) / 8] = the flagged groups, ascending, then
+ * the others, ascending; returns the number of flagged groups, or -1.  _host: coefs in host memory, host code, needs no GPU;
+ * _device: d_coefs in device memory, the table built by the kernel the encoder launches (null stream; the call waits). */
+int vga_testing_gc_slow_order_host(const short *coefs, int nch, int *order);
+int vga_testing_gc_slow_order_device(const void *d_coefs, int nch, int *order);
 
 /* The host-pointer entry points (vga_*_batch) move data through a pipeline of feeder threads, pinned rings, per-chunk
  * kernel launches and drainer threads (vgaudio_amd/csrc/host_pipeline.hpp); its shape normally follows the volume of

@@ -170,6 +170,10 @@ SIGNATURES = {
     "vga_testing_gc_coefs_variant_this_thread": (ci, [ci]),
     "vga_testing_gc_encoder_segments_this_thread": (ci, [ci]),
     "vga_testing_gc_encoder_persistent_this_thread": (ci, [ci]),
+    "vga_testing_gc_seam_handover_this_thread": (ci, [ci]),
+    "vga_testing_gc_slow_order_host": (ci, [vp, ci, vp]),
+    "vga_testing_gc_slow_order_device": (ci, [vp, ci, vp]),
+    "vga_testing_gc_encode_stats_n": (ci, [C.POINTER(C.c_ulonglong), ci, ci]),
     "vga_testing_last_pipeline_stats": (ci, [vp, ci]),
     "vga_testing_host_pipeline_tail_this_thread": (None, [ci]),
     "vga_testing_buckets_order_this_thread": (None, [ci]),

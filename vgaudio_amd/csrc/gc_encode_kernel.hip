@@ -29,6 +29,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 namespace vga {
 namespace gc {
@@ -92,22 +93,27 @@ extern "C" int vga_debug_encode_timestamps(unsigned long long *out, int n)
 //   [3] wave-frames encoded by the piece kernels   [4] ... of which took the cold block (third trips, bump loop, inexact sums;
 //   counted by -DVGA_GC_STATS builds only -- tools/build_variants.sh stats:"-DVGA_GC_STATS" -- 0 otherwise, [7] says which)
 //   [5] channels gc_encode_chain_kernel had to walk   [6] pieces encoded   [7] 1 = this build counts [4]
-__device__ unsigned long long g_vga_gc_stats[8];
-extern "C" int vga_testing_gc_encode_stats(unsigned long long *out8, int reset)
+//   [8] (vga_testing_gc_encode_stats_n only) channels with an open seam whose chain the self-served kernel walked itself (round
+//   15, the hand-over below): what [5] counts when the hand-over is switched off
+constexpr int GC_STATS = 9;
+__device__ unsigned long long g_vga_gc_stats[GC_STATS];
+extern "C" int vga_testing_gc_encode_stats_n(unsigned long long *out, int n, int reset)
 {
+    if (n < 0 || n > GC_STATS) return -1;
     if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_vga_gc_stats), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (out && n > 0 && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_vga_gc_stats), (size_t)n * sizeof(unsigned long long)) != hipSuccess) return -1;
 #ifdef VGA_GC_STATS
-    if (out8) out8[7] = 1;
+    if (out && n > 7) out[7] = 1;
 #else
-    if (out8) out8[7] = 0;
+    if (out && n > 7) out[7] = 0;
 #endif
     if (reset) {
-        const unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const unsigned long long zero[GC_STATS] = {};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_vga_gc_stats), zero, sizeof zero) != hipSuccess) return -1;
     }
     return 0;
 }
+extern "C" int vga_testing_gc_encode_stats(unsigned long long *out8, int reset) { return vga_testing_gc_encode_stats_n(out8, 8, reset); }
 constexpr int SW = 2;              // encoder (serial) waves per workgroup; one helper wave serves them all
 constexpr int ENC_THREADS = 64 * (SW + 1);
 // issue priorities (s_setprio) of the encoder waves and of the helper wave.  Round 6 (profiles/r06_t_encode_priority*.log):
@@ -1246,6 +1252,139 @@ __device__ __forceinline__ void seam_piece(
     }
 }
 
+// Round 15, the self-served shape on uniform batches: open seams handed on inside the launch.  What gc_encode_chain_kernel
+// does piece after piece in a launch of its own -- one wave per group of eight, alone on the chip, for as long as its
+// slowest channel's runs take to meet -- happens here as soon as its inputs exist, underneath the other waves' items.
+//
+// The chain is serial in the pieces for a reason: the history a seam's own run starts from (T = seg_state[k - 1]) is the
+// true one only when everything before it has been settled, so a seam's recorded end is "the truth provided a true run
+// has met mine".  So a TOKEN walks every group's pieces in order, 2, 3, ...: per channel either "nothing enters piece p"
+// or "V enters piece p: the true history there, which the piece's bytes were not encoded from".  The token for piece 2
+// comes from seam 1's own run (piece 0 starts from the caller's history: that run is the true one).  Piece p then needs
+// two things, and they arrive in either order on word[(p - 1) * groups + group]:
+//   a) the own run of seam p has finished: its flag and end are written, the piece's bytes are its run from T;
+//   b) the token for piece p has arrived: token / v[(p - 1) * nch + channel] are written.
+// Whoever arrives second runs the continuation for the group's eight channels -- seam_run from V next to the replay from
+// T for the channels that have a V, the others' lanes idle -- applies the chain launch's three rules (still apart: carry V
+// on; met a run that was itself flagged: its recorded end is the truth; else nothing), and takes the token to piece p + 1
+// by the same rule: it finds a) there and continues, or leaves b) and returns to the queue.  Nobody ever waits.  The
+// fences are seam_count's: a device-scope fence between a party's stores and its add, another before the second party
+// reads.  Behind the last piece the token becomes the channel's record (row segments - 1 of the same arrays): the chain
+// launch then runs no seam_run for the channel, and encodes the partial last frame from V when a run was still apart
+// there -- the one case that stays with it.  Nothing is written into seam_flag or first_open on the way (other waves read
+// the one and atomicMin the other); the chain launch clears first_open as it always did.
+constexpr int HAND_ARRIVED = 1;                // a token (or record) has been written
+constexpr int HAND_V = 2;                      // ... and it carries a V
+constexpr int HAND_EVER = 4;                   // ... the channel had an open seam somewhere before (statistics, [8])
+struct Handover {
+    int *word = nullptr;                       // null: no hand-over (the chain launch does it all)
+    int *token = nullptr, *v = nullptr;
+};
+
+// The seams at the ends of the piece a wave of the self-served kernel has just encoded (seam_a, seam_b: 0 = not this wave's),
+// and whatever continuations the hand-over brings it.  ONE copy of seam_run: the runs are steps of a loop.
+__device__ __forceinline__ void self_served_seams(
+    const int g, const int seam_a, const int seam_b, const int lane, const int groups, const int segments,
+    const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const Pieces seg,
+    const int16_t *__restrict__ coefs, uint8_t *adpcm, int64_t adpcm_pitch,
+    const int16_t *seg_state, int *first_open, int *seam_flag, int *seam_end, int force_open, const Handover hand)
+{
+    const int pr = lane & 7;                            // this lane's predictor
+    const bool lead = pr == 0;                          // one lane per channel: flags, statistics, tokens
+    const int slot_raw = g * PLAN8_SLOTS + (lane >> 3);
+    const bool live = slot_raw < nch;
+    const int ch = live ? slot_raw : nch - 1;
+    const int16_t *src = pcm + (int64_t)ch * pcm_pitch;
+    uint8_t *dst = adpcm + (int64_t)ch * adpcm_pitch;
+    const int16_t *cf = coefs + ch * 16;
+    const int c0 = cf[2 * pr], c1 = cf[2 * pr + 1];
+    const bool coef_ok = (c0 < 0 ? -c0 : c0) + (c1 < 0 ? -c1 : c1) <= 32767;
+    auto second_on = [&](int piece) {                   // announce on piece's word; true: the other party was there first
+        __threadfence();                                // this wave's stores are out before it says so
+        int old = 0;
+        if (lane == 0) old = atomicAdd(&hand.word[(int64_t)(piece - 1) * groups + g], 1);
+        const bool second = __builtin_amdgcn_readfirstlane(old) == 1;
+        if (second) __threadfence();                    // the other party's stores, before anything of them is read
+        return second;
+    };
+    int own = 0;                                        // own runs taken so far
+    int p = 0;                                          // != 0: both parties of piece p are here: continue into it
+    int state = 0, v0 = 0, v1 = 0;                      // the token this wave carries: what enters piece p (then: piece k + 1)
+    for (;;) {
+        const bool cont = p != 0;
+        int k;
+        if (cont) k = p;
+        else if (own == 0) { own = 1; k = seam_a; }
+        else if (own == 1) { own = 2; k = seam_b; }
+        else break;
+        p = 0;
+        if (k == 0) continue;
+        const int64_t f0 = seg.first(k);
+        const bool valid = live && f0 * 14 < total_samples;
+        const int64_t idx = (int64_t)(k - 1) * nch + ch;
+        const int t0 = valid ? seg_state[idx * 2] : 0, t1 = valid ? seg_state[idx * 2 + 1] : 0;   // T
+        // own run: from T next to the guessed run (the two input samples before the piece); continuation: from V next to T
+        int h0 = cont ? v0 : t0, h1 = cont ? v1 : t1;
+        const int g2 = cont ? t0 : (valid ? src[f0 * 14 - 2] : 0), g1 = cont ? t1 : (valid ? src[f0 * 14 - 1] : 0);
+        bool open = cont ? valid && (state & HAND_V) != 0 : valid;
+        const bool ran = open;
+        int frames_run = 0;
+        if (__any(open))
+            seam_run<8>(src, dst, c0, c1, coef_ok, pr, ch, k, f0, total_samples, seg.frames(k), seg.frames(k), force_open, h0, h1, g2, g1, open, frames_run);
+        if (!cont) {                                    // (as seam_piece)
+            if (valid && lead) {
+                atomicAdd(&g_vga_gc_stats[open ? 1 : 0], 1ull);
+                atomicAdd(&g_vga_gc_stats[2], (unsigned long long)frames_run);
+                seam_flag[idx] = open ? 1 : 0;
+                if (open) {
+                    seam_end[idx] = (int)(((unsigned)h1 << 16) | ((unsigned)h0 & 0xFFFFu));
+                    atomicMin(&first_open[ch], k);
+                }
+            }
+            if (!hand.word) continue;
+            if (k == 1) {                               // the run from the caller's history: the true one
+                state = HAND_ARRIVED | (open ? HAND_V | HAND_EVER : 0);
+                v0 = h0;
+                v1 = h1;
+            } else {
+                if (second_on(k)) {                     // a): the token was waiting
+                    state = hand.token[idx];
+                    const int v = hand.v[idx];
+                    v0 = (int)(int16_t)(v & 0xFFFF);
+                    v1 = v >> 16;
+                    p = k;
+                }
+                continue;
+            }
+        } else {
+            if (valid && lead && frames_run) atomicAdd(&g_vga_gc_stats[2], (unsigned long long)frames_run);
+            const bool flagged = valid && seam_flag[idx] != 0;
+            if (ran && open) {                          // still apart at the piece's end: carry on into the next one
+                v0 = h0;
+                v1 = h1;
+            } else if (flagged) {                       // met the run from T, whose own seam ran out of frames: its end is the truth
+                const int ended = seam_end[idx];
+                state |= HAND_V | HAND_EVER;
+                v0 = (int)(int16_t)(ended & 0xFFFF);
+                v1 = ended >> 16;
+            } else
+                state &= ~HAND_V;
+        }
+        // (state, v0, v1): what enters piece k + 1 -- or, behind the stream's last piece, the channel's record in row
+        // segments - 1 (the test hook's equal pieces can leave piece indices behind the end of the stream: nobody encodes
+        // those, and no token waits for them)
+        const bool last = k + 1 >= segments || seg.first(k + 1) * 14 >= total_samples;
+        const int64_t nidx = (int64_t)(last ? segments - 1 : k) * nch + ch;
+        if (live && lead) {
+            hand.v[nidx] = (int)(((unsigned)v1 << 16) | ((unsigned)v0 & 0xFFFFu));
+            hand.token[nidx] = state;
+            if (last && (state & HAND_EVER) != 0) atomicAdd(&g_vga_gc_stats[8], 1ull);
+        }
+        if (last) continue;
+        if (second_on(k + 1)) p = k + 1;                // b): the piece's own run has finished
+    }
+}
+
 template <int LPC>
 __global__ __launch_bounds__(64) void gc_encode_seam_kernel(
     const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const Pieces seg,
@@ -1342,6 +1481,61 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(VGA
     }
 }
 
+// Round 15: the order of the self-served queue on uniform batches (gc_plan8.hpp: plan8_slow_channel, plan8_slow_order) from
+// the coefficients where they are -- on the device, on the encode's stream, never synchronised to the host.  One wave:
+// order[0 .. S) = the flagged groups of eight, ascending, order[S .. groups8) = the others, order[groups8] = S.
+__global__ __launch_bounds__(64) void gc_slow_groups_kernel(const int16_t *__restrict__ coefs, int nch, int groups8, int *__restrict__ order)
+{
+    const int lane = threadIdx.x;
+    auto flagged = [&](int g) {
+        bool slow = false;
+        if (g < groups8)
+            for (int s = 0; s < PLAN8_SLOTS; s++) {
+                const int ch = g * PLAN8_SLOTS + s;
+                if (ch < nch) slow = plan8_slow_channel(coefs + (int64_t)ch * 16) || slow;
+            }
+        return slow;
+    };
+    int total = 0;
+    for (int base = 0; base < groups8; base += 64) total += __popcll(__ballot(flagged(base + lane)));
+    int s = 0, r = total;
+    const unsigned long long lower = (1ull << lane) - 1;
+    for (int base = 0; base < groups8; base += 64) {
+        const int g = base + lane;
+        const bool f = flagged(g);
+        const unsigned long long m = __ballot(f), rest = __ballot(!f && g < groups8);
+        if (g < groups8) order[f ? s + __popcll(m & lower) : r + __popcll(rest & lower)] = g;
+        s += __popcll(m);
+        r += __popcll(rest);
+    }
+    if (lane == 0) order[groups8] = total;
+}
+// (test-only exports, include/vgaudio_hip_testing.h)
+extern "C" int vga_testing_gc_slow_order_host(const int16_t *coefs, int nch, int *order)
+{
+    if (!coefs || !order || nch <= 0) return -1;
+    const int groups8 = (nch + PLAN8_SLOTS - 1) / PLAN8_SLOTS;
+    std::vector<unsigned char> flagged((size_t)groups8, 0);
+    for (int ch = 0; ch < nch; ch++)
+        if (plan8_slow_channel(coefs + (int64_t)ch * 16)) flagged[(size_t)(ch / PLAN8_SLOTS)] = 1;
+    return plan8_slow_order(flagged.data(), groups8, order);
+}
+extern "C" int vga_testing_gc_slow_order_device(const void *d_coefs, int nch, int *order)
+{
+    if (!d_coefs || !order || nch <= 0) return -1;
+    const int groups8 = (nch + PLAN8_SLOTS - 1) / PLAN8_SLOTS;
+    int *d_order = nullptr;
+    if (hipMalloc(&d_order, (size_t)(groups8 + 1) * sizeof(int)) != hipSuccess) return -1;
+    hipLaunchKernelGGL(gc_slow_groups_kernel, dim3(1), dim3(64), 0, (hipStream_t)0, static_cast<const int16_t *>(d_coefs), nch, groups8, d_order);
+    std::vector<int> host((size_t)groups8 + 1);
+    const bool ok = hipGetLastError() == hipSuccess &&
+                    hipMemcpy(host.data(), d_order, host.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d_order);
+    if (!ok) return -1;
+    for (int g = 0; g < groups8; g++) order[g] = host[(size_t)g];
+    return host[(size_t)groups8];
+}
+
 // Round 13: the same queue for the self-served shape (Lay<8, true>): a workgroup is one wave, items are (group of EIGHT
 // channel slots, piece) -- gc_plan8.hpp -- and cus x 12 workgroups put three waves on every SIMD, all alike.  The piece
 // schedule is the one planned for groups of sixteen, so a channel has the seams it has with the 2 + 1 shape; they close on
@@ -1353,12 +1547,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
     const int16_t *__restrict__ coefs, const int16_t *__restrict__ hist1,
     const int16_t *__restrict__ hist2, uint8_t *adpcm, int64_t adpcm_pitch, int16_t *seg_state,
     const Ragged rg, int groups, int items, int segments, int *__restrict__ queue, int *__restrict__ seam_count, int *first_open,
-    int *seam_flag, int *seam_end, int force_open)
+    int *seam_flag, int *seam_end, int force_open, const Handover hand, const int *__restrict__ slow_order)
 {
     constexpr int CS = PLAN8_SLOTS;
     static_assert(Lay<8, true>::CS == CS && Lay<8, true>::THREADS == 64, "one wave, eight channel slots");
     const int lane = threadIdx.x;
     const uint32_t *host_items = RAGGED ? rg.items : nullptr;
+    // (uniform batches: the groups likely to close their seams slowly first, gc_slow_groups_kernel)
+    const int *order = RAGGED ? nullptr : slow_order;
+    const int slow = order ? order[groups] : 0;
 #ifdef VGA_DEBUG_TIMESTAMPS
     if (lane == 0) g_vga_enc_ts[2 * (blockIdx.x & 32767)] = wall_clock64();
 #endif
@@ -1373,7 +1570,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
             return;
         }
         int g, y;
-        if (!plan8_item(item, groups, nch, host_items, g, y)) continue;
+        if (!plan8_item(item, groups, nch, host_items, order, slow, segments, g, y)) continue;
         gc_encode_piece<false, 8, RAGGED, true>(g, y, pcm, pcm_pitch, nch, total_samples, seg, coefs, hist1, hist2, adpcm, adpcm_pitch,
                                                 seg_state, (const int *)nullptr, rg);
         if (segments <= 1) continue;
@@ -1392,13 +1589,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         const int seam_a = __builtin_amdgcn_readfirstlane(at_start), seam_b = __builtin_amdgcn_readfirstlane(at_end);
         if ((seam_a | seam_b) != 0) {
             __threadfence();                           // the other workgroup's stores, before anything of them is read
-            const int slot = g * CS + (lane >> 3);
-            if (seam_a)
-                seam_piece<8>(slot, seam_a, lane, pcm, pcm_pitch, nch, total_samples, seg, coefs, adpcm, adpcm_pitch, seg_state,
-                           first_open, seam_flag, seam_end, force_open, rg);
-            if (seam_b)
-                seam_piece<8>(slot, seam_b, lane, pcm, pcm_pitch, nch, total_samples, seg, coefs, adpcm, adpcm_pitch, seg_state,
-                           first_open, seam_flag, seam_end, force_open, rg);
+            if constexpr (RAGGED) {
+                const int slot = g * CS + (lane >> 3);
+                if (seam_a)
+                    seam_piece<8>(slot, seam_a, lane, pcm, pcm_pitch, nch, total_samples, seg, coefs, adpcm, adpcm_pitch, seg_state,
+                               first_open, seam_flag, seam_end, force_open, rg);
+                if (seam_b)
+                    seam_piece<8>(slot, seam_b, lane, pcm, pcm_pitch, nch, total_samples, seg, coefs, adpcm, adpcm_pitch, seg_state,
+                               first_open, seam_flag, seam_end, force_open, rg);
+            } else                                     // (uniform batches: with the hand-over of open seams, round 15)
+                self_served_seams(g, seam_a, seam_b, lane, groups, segments, pcm, pcm_pitch, nch, total_samples, seg, coefs, adpcm,
+                                  adpcm_pitch, seg_state, first_open, seam_flag, seam_end, force_open, hand);
         }
     }
 }
@@ -1414,7 +1615,8 @@ __global__ __launch_bounds__(64) void gc_encode_chain_kernel(
     const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const Pieces seg, int segments,
     const int16_t *__restrict__ coefs, uint8_t *__restrict__ adpcm, int64_t adpcm_pitch,
     int16_t *__restrict__ seg_state, int *__restrict__ first_open, const int *__restrict__ seam_flag,
-    const int *__restrict__ seam_end, int force_open, const Ragged rg)
+    const int *__restrict__ seam_end, int force_open, const Ragged rg, const int *__restrict__ hand_token,
+    const int *__restrict__ hand_v)
 {
     const int lane = threadIdx.x;
     const int pr = LPC == 16 ? (lane >> 1) & 7 : lane & 7;
@@ -1424,12 +1626,23 @@ __global__ __launch_bounds__(64) void gc_encode_chain_kernel(
     const int slot = live ? slot_raw : nch - 1;
     const int ch = rg.order ? rg.order[slot] : slot;
     if (rg.order) total_samples = rg.length[ch];        // ragged: per lane from here on
-    const int mine = live ? first_open[ch] : SEAM_NONE;
-    int kmin = mine;
+    // Round 15: a channel whose chain the self-served kernel has walked itself (self_served_seams) has a record behind the last
+    // piece: nothing of it is walked here -- only first_open is cleared, and the partial last frame encoded when the record
+    // carries a V (a run still apart at the very end).  hand_token == nullptr, or a record of 0: as ever.
+    const int64_t rec_idx = (int64_t)(segments - 1) * nch + ch;
+    const int record = hand_token && live ? hand_token[rec_idx] : 0;
+    const bool resolved = record != 0;
+    const int mine_raw = live ? first_open[ch] : SEAM_NONE;
+    const int mine = resolved ? SEAM_NONE : mine_raw;
+    int kmin = mine, kmin_raw = mine_raw;
 #pragma unroll
-    for (int o = LPC; o < 64; o <<= 1) kmin = imin(kmin, __shfl_xor(kmin, o));
-    if (kmin >= segments) return;                       // no open seam among this wave's channels
-    if (live && lead && mine < segments) atomicAdd(&g_vga_gc_stats[5], 1ull);
+    for (int o = LPC; o < 64; o <<= 1) {
+        kmin = imin(kmin, __shfl_xor(kmin, o));
+        kmin_raw = imin(kmin_raw, __shfl_xor(kmin_raw, o));
+    }
+    if (kmin_raw >= segments) return;                   // no open seam among this wave's channels
+    const bool tail_left = resolved && (record & HAND_V) != 0 && total_samples % 14 != 0;
+    if (live && lead && (mine < segments || tail_left)) atomicAdd(&g_vga_gc_stats[5], 1ull);
     int frames_run = 0;
     const int16_t *src = pcm + (rg.order ? rg.pcm_off[ch] : (int64_t)ch * pcm_pitch);
     uint8_t *dst = adpcm + (rg.order ? rg.adpcm_off[ch] : (int64_t)ch * adpcm_pitch);
@@ -1448,7 +1661,7 @@ __global__ __launch_bounds__(64) void gc_encode_chain_kernel(
         last_k = k;
         const bool is_last = seg.first(k + 1) * 14 >= total_samples || k == segments - 1;
         const int64_t idx = (int64_t)(k - 1) * nch + ch;
-        const bool flagged = live && exists && seam_flag[idx] != 0;
+        const bool flagged = live && !resolved && exists && seam_flag[idx] != 0;
         const int ended = seam_end[idx];
         const bool ran = live && have && exists;
         bool open = ran;
@@ -1471,6 +1684,12 @@ __global__ __launch_bounds__(64) void gc_encode_chain_kernel(
             v1 = ended >> 16;
         } else
             have = false;
+    }
+    if (tail_left) {                                    // (the kernel's record: its run arrived at the stream's end with this V)
+        const int v = hand_v[rec_idx];
+        have = true;
+        v0 = (int)(int16_t)(v & 0xFFFF);
+        v1 = v >> 16;
     }
     // apart to the very end: only the partial last frame is left to encode from V -- here, by the channel's eight lanes (the
     // serial repair launch that used to take over re-ran the whole last piece: 4.9 ms of a 256-channel encode's 31)
@@ -1660,11 +1879,17 @@ static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch
     AsyncBuf scratch;                                  // freed (stream-ordered) on every exit path
     int16_t *seg_state = nullptr;
     int *first_open = nullptr, *seam_flag = nullptr, *seam_end = nullptr, *queue = nullptr, *seam_count = nullptr;
+    // open seams handed on inside the self-served kernel (self_served_seams): uniform batches; the test hook switches it off
+    const bool handover = self && !RAGGED && segments > 1 && !gc_seam_handover_off();
+    Handover hand;
+    int *slow_order = nullptr;
     if (segments > 1 || persistent) {
         const size_t state_bytes = segments > 1 ? (size_t)round_up((int64_t)segments * nch * 2 * (int64_t)sizeof(int16_t), 16) : 0;
         const size_t open_bytes = (size_t)round_up((int64_t)nch * (int64_t)sizeof(int), 16);
         const size_t count_bytes = persistent && segments > 1 ? (size_t)round_up((int64_t)(segments - 1) * seam_groups * (int64_t)sizeof(int), 16) : 0;
-        const size_t need = 3 * state_bytes + open_bytes + 16 + count_bytes;
+        // (the hand-over: a word per seam and group behind seam_count's, then a token and a V per piece and channel)
+        const size_t order_bytes = handover ? (size_t)round_up((int64_t)(seam_groups + 1) * (int64_t)sizeof(int), 16) : 0;   // (gc_slow_groups_kernel's table)
+        const size_t need = 3 * state_bytes + open_bytes + 16 + count_bytes + (handover ? count_bytes + 2 * state_bytes + order_bytes : 0);
         // the caller's scratch when it brought one (the host pipeline: hipMallocAsync next to busy copy streams stalled
         // its launching thread for up to 300 ms per call), a stream-ordered allocation otherwise
         unsigned char *base = static_cast<unsigned char *>(d_scratch);
@@ -1682,13 +1907,24 @@ static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch
         } else
             seg_state = nullptr;
         seam_count = queue + 4;
-        if (persistent) VGA_HIP_TRY(hipMemsetAsync(queue, 0, 16 + count_bytes, stream));    // the queue's head and every seam's counter
+        if (persistent) VGA_HIP_TRY(hipMemsetAsync(queue, 0, 16 + count_bytes * (handover ? 2 : 1), stream));    // the queue's head and every seam's counter (and word)
+        if (handover) {
+            unsigned char *words = base + 3 * state_bytes + open_bytes + 16 + count_bytes;
+            hand.word = reinterpret_cast<int *>(words);
+            hand.token = reinterpret_cast<int *>(words + count_bytes);
+            hand.v = reinterpret_cast<int *>(words + count_bytes + state_bytes);
+            slow_order = reinterpret_cast<int *>(words + count_bytes + 2 * state_bytes);
+            // (the channels' records, the row behind the last piece: "not walked" unless the kernel says otherwise)
+            VGA_HIP_TRY(hipMemsetAsync(hand.token + (size_t)(segments - 1) * nch, 0, (size_t)nch * sizeof(int), stream));
+        }
     }
     if (self) {
-        if constexpr (CPW == 8)
+        if constexpr (CPW == 8) {
+            if (slow_order) hipLaunchKernelGGL(gc_slow_groups_kernel, dim3(1), dim3(64), 0, stream, d_coefs, nch, p8.groups, slow_order);
             hipLaunchKernelGGL((gc_encode_self_served_kernel<RAGGED>), dim3(p8.wgs), dim3(Lay<8, true>::THREADS), 0, stream, d_pcm, pcm_pitch,
                                nch, sample_count, seg, d_coefs, d_hist1, d_hist2, d_adpcm, adpcm_pitch, seg_state, rg, p8.groups, p8.items,
-                               segments, queue, seam_count, first_open, seam_flag, seam_end, force_open_seams());
+                               segments, queue, seam_count, first_open, seam_flag, seam_end, force_open_seams(), hand, (const int *)slow_order);
+        }
     } else if (persistent) {
         const int items = RAGGED && rg.items ? rg.n_items : groups * segments;
         const int wgs = imin(items, cus * persistent_wgs_per_cu());
@@ -1731,11 +1967,11 @@ static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch
 #endif
             hipLaunchKernelGGL(gc_encode_chain_kernel<16>, dim3((nch + 3) / 4), dim3(64), 0, stream, d_pcm, pcm_pitch, nch, sample_count,
                                seg, segments, d_coefs, d_adpcm, adpcm_pitch, seg_state, first_open, seam_flag, seam_end,
-                               force_open_seams(), rg);
+                               force_open_seams(), rg, (const int *)hand.token, (const int *)hand.v);
         else
             hipLaunchKernelGGL(gc_encode_chain_kernel<8>, dim3((nch + 7) / 8), dim3(64), 0, stream, d_pcm, pcm_pitch, nch, sample_count,
                                seg, segments, d_coefs, d_adpcm, adpcm_pitch, seg_state, first_open, seam_flag, seam_end,
-                               force_open_seams(), rg);
+                               force_open_seams(), rg, (const int *)hand.token, (const int *)hand.v);
         VGA_HIP_TRY(hipGetLastError());
         // repair: the same encoder, serially over the last piece, for a channel the chain could not finish (a partial
         // last frame after a run that never met; none: every workgroup returns)
@@ -1749,7 +1985,8 @@ static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch
 // upper bound of what launch_encode wants as scratch for nch channels (1024 pieces x (state, flag, end) + 4 B per channel, + alignment)
 // (+ the persistent kernels' queue and seam counters: 4 B per channel group and seam)
 // (groups of eight, the self-served shape: 4 B per seam and 8 channels = 512 B per channel)
-size_t encode_scratch_bytes(int nch) { return (size_t)(nch > 0 ? nch : 0) * (1024 * 12 + 4 + 512) + 8192; }
+// (the hand-over of the self-served shape: a token and a V per piece and channel, 8 B, and a second word per seam and group)
+size_t encode_scratch_bytes(int nch) { return (size_t)(nch > 0 ? nch : 0) * (1024 * 20 + 4 + 1024 + 1) + 8192 + 32; }
 
 int launch_encode(const int16_t *d_pcm, int64_t pcm_pitch, int nch, int sample_count, const int16_t *d_coefs,
                   const int16_t *d_hist1, const int16_t *d_hist2, uint8_t *d_adpcm, int64_t adpcm_pitch,

@@ -41,19 +41,77 @@ inline Plan8 plan_groups_of_eight(int cus, int nch, int segments, int host_items
     return p;
 }
 
+// Round 15: groups whose seams are likely to close slowly are taken from the queue first (uniform batches).  A seam that
+// outlives its piece is continued into the next one by a single wave, frame after frame (self_served_seams,
+// gc_encode_kernel.hip); started with the launch, that walk runs underneath the other groups' items, started with the last
+// round of short items it is what the launch ends on.
+//
+// Which channels: the reconstruction error of a run obeys the predictor's recurrence, so two runs from different histories
+// approach each other at the rate of its poles -- complex poles of z^2 = (c0 z + c1) / 2048 have radius^2 = -c1 / 2048 --
+// and only a predictor next to the unit circle keeps them apart for thousands of frames.  tools/gc_slow_seam_table.py
+// (LABNOTES round 15, gate 0) holds the closing times of a host model next to the radius: every channel whose seams need more
+// than 1024 frames has a predictor with complex poles and -c1 >= PLAN8_SLOW_C1.  A false positive costs nothing (its
+// group's items are as long as any, they only run early); a pure tone's seams close at once (it is coded without loss) and
+// it is flagged all the same.
+#ifndef VGA_PLAN8_SLOW_C1                      // (timing variants only, tools/build_variants.sh: 4096 = no group is ever flagged)
+#define VGA_PLAN8_SLOW_C1 2040
+#endif
+constexpr int PLAN8_SLOW_C1 = VGA_PLAN8_SLOW_C1;   // radius^2 >= 0.996
+VGA_PLAN8_HD inline bool plan8_slow_predictor(int c0, int c1)
+{
+    return -c1 >= PLAN8_SLOW_C1 && (int64_t)c0 * c0 < (int64_t)-8192 * c1;      // (c0 / 2048)^2 + 4 c1 / 2048 < 0: complex poles
+}
+// ... a channel: any of its eight predictors (coefs16: c0, c1 of predictor 0, of predictor 1, ...)
+VGA_PLAN8_HD inline bool plan8_slow_channel(const int16_t *coefs16)
+{
+    bool slow = false;
+    for (int p = 0; p < 8; p++) slow = slow || plan8_slow_predictor(coefs16[2 * p], coefs16[2 * p + 1]);
+    return slow;
+}
+// The order of the groups: order[0 .. S) = the flagged groups, ascending, order[S .. groups8) = the others, ascending.
+// Returns S.  (The device builds the same table from the coefficients where they are: gc_slow_groups_kernel.)
+inline int plan8_slow_order(const unsigned char *flagged, int groups8, int *order)
+{
+    int s = 0;
+    for (int g = 0; g < groups8; g++)
+        if (flagged[g]) order[s++] = g;
+    int r = s;
+    for (int g = 0; g < groups8; g++)
+        if (!flagged[g]) order[r++] = g;
+    return s;
+}
+
 // queue item -> (group of eight, piece).  Piece-major without a host list, else the list's order (biggest first), a host
 // item's two halves next to each other.  false: nothing to encode (the half lies behind the batch's last channel).
-VGA_PLAN8_HD inline bool plan8_item(int item, int groups8, int nch, const uint32_t *host_items, int &g, int &y)
+// order / slow (uniform batches, plan8_slow_order; order == nullptr: none): the first slow x segments items are all pieces
+// of the flagged groups, piece-major among them, the rest is the piece-major order over the other groups; with no flagged
+// group or with every group flagged the order is the plain one.
+VGA_PLAN8_HD inline bool plan8_item(int item, int groups8, int nch, const uint32_t *host_items, const int *order, int slow, int segments,
+                                    int &g, int &y)
 {
     if (host_items) {
         const uint32_t v = host_items[item >> 1];
         g = 2 * (int)(v & 0xFFFFFu) + (item & 1);
         y = (int)(v >> 20);
+    } else if (order && slow > 0 && slow < groups8) {
+        const int front = slow * segments;
+        if (item < front) {
+            g = order[item % slow];
+            y = item / slow;
+        } else {
+            const int rest = groups8 - slow;
+            g = order[slow + (item - front) % rest];
+            y = (item - front) / rest;
+        }
     } else {
         g = item % groups8;
         y = item / groups8;
     }
     return g * PLAN8_SLOTS < nch;
+}
+VGA_PLAN8_HD inline bool plan8_item(int item, int groups8, int nch, const uint32_t *host_items, int &g, int &y)
+{
+    return plan8_item(item, groups8, nch, host_items, nullptr, 0, 0, g, y);
 }
 
 }  // namespace gc

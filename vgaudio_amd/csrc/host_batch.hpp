@@ -39,6 +39,7 @@ struct ThreadSettings {
     int encoder_segments = 0;
     int encoder_persistent = 0;
     int hca_frames_per_group = 0;
+    int gc_seam_handover_off = 0;
     PipeOverride pipe;
     FailStep fail;
 };

@@ -50,6 +50,7 @@ int coefs_kernel_variant() { return g_settings.coefs_variant; }
 int encoder_segments_override() { return g_settings.encoder_segments; }
 int encoder_persistent_mode() { return g_settings.encoder_persistent; }
 int hca_frames_per_group_override() { return g_settings.hca_frames_per_group; }
+bool gc_seam_handover_off() { return g_settings.gc_seam_handover_off != 0; }
 // not a setting but a record: what the calling thread's last ADX launches chose (0 = none yet)
 static thread_local int g_adx_encode_path = 0, g_adx_decode_path = 0;
 void note_adx_encode_path(int path) { g_adx_encode_path = path; }
@@ -174,6 +175,12 @@ int vga_testing_gc_encoder_persistent_this_thread(int mode)
 {
     const int old = g_settings.encoder_persistent;
     g_settings.encoder_persistent = mode >= 0 && mode <= 2 ? mode : 0;
+    return old;
+}
+int vga_testing_gc_seam_handover_this_thread(int on)
+{
+    const int old = g_settings.gc_seam_handover_off ? 0 : 1;
+    g_settings.gc_seam_handover_off = on ? 0 : 1;
     return old;
 }
 int vga_testing_hca_frames_per_group_this_thread(int frames)

@@ -60,6 +60,30 @@ def host(cls, nch, n, first_channel=0):
     raise ValueError(cls)
 
 
+def tones_in_noise(nch, n, first_channel=0):
+    """[nch, n] int16 on the host (not one of CLASSES: the seam tests and tools/gc_slow_seam_table.py).  Channel c by c % 4:
+    0 a square whose period is the GC-ADPCM frame (14 samples), 1 a sine of that period, 2 the 440 Hz sine at half scale,
+    each on a floor of white noise (1/64, 1/64, 1/256 of full scale), 3 white noise at an eighth of full scale.  A pure tone
+    is coded without loss and its encoder seams close at once; on a noise floor the sines' runs stay apart for hundreds to
+    thousands of frames (kind 1: as a rule for good), while the square's and the noise's meet within a few frames."""
+    i = np.arange(n, dtype=np.int64)[None, :]
+    rows = []
+    for c in range(first_channel, first_channel + nch):
+        noise = host("white_full_scale", 1, n, first_channel=c)[0].astype(np.int64)
+        kind = c % 4
+        if kind == 0:
+            amp = 12000 + 100 * (c % 50)
+            row = np.where(((i[0] + c) % 14) < 7, amp, -amp) + noise // 64
+        elif kind == 1:
+            row = (20000.0 * np.sin(2.0 * np.pi * (i[0] + c) / 14.0)).astype(np.int64) + noise // 64
+        elif kind == 2:
+            row = host("sine440", 1, n, first_channel=c)[0].astype(np.int64) // 2 + noise // 256
+        else:
+            row = noise // 8
+        rows.append(row.astype(np.int16))
+    return np.stack(rows)
+
+
 def device(cls, nch, n, dev, first_channel=0, out=None, chunk=32):
     """[nch, pitch] int16 on the GPU (pitch as device.alloc_pcm), the same bits as host()"""
     import torch
