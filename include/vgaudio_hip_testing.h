@@ -47,8 +47,14 @@ int vga_testing_gc_encoder_persistent_this_thread(int mode);
  * channels hold `group_frames` frames in all.  Host arithmetic, needs no GPU.  out5 = {pieces, big, nb, small, persistent}:
  * piece k begins at frame min(k, nb) * big + max(k - nb, 0) * small.  The pieces must cover `frames`.  With
  * vga_testing_gc_encoder_layout_this_thread(1) in force: the schedule of the self-served shape (always persistent; the rounds
- * of the two-size schedule counted in groups of eight on twelve workgroups per compute unit).  Returns 0. */
+ * of the two-size schedule counted in groups of eight on twelve workgroups per compute unit; on uniform batches whose tail
+ * descends this is the schedule of the groups that keep the coarse tail, see vga_testing_gc_plan_pieces_n).  Returns 0. */
 int vga_testing_gc_plan_pieces(int cus, int groups, int frames, long long group_frames, int ragged, int *out5);
+/* ... the same with the whole schedule: out10 = {pieces, big, nb, small, n1, s2, n2, s3, persistent, 0} -- behind the nb big
+ * pieces come n1 pieces of `small` frames, then n2 of s2, then pieces of s3 (n1 or n2 = 1 << 30: that level has no end and the
+ * later ones are unused).  coarse != 0: the schedule of the groups of eight whose seams are likely to close slowly (the
+ * self-served shape on uniform batches: one tail level, of pieces no shorter than 4096 frames). */
+int vga_testing_gc_plan_pieces_n(int cus, int groups, int frames, long long group_frames, int ragged, int coarse, int *out10);
 
 /* Diagnostics of the GC-ADPCM encoder's data-dependent parts, summed over every launch of the process on the current
  * device since the last reset (the call synchronises the device first): out8 = {seams closed inside their piece, seams left
@@ -67,6 +73,12 @@ int vga_testing_gc_encode_stats_n(unsigned long long *out, int n, int reset);
  * leave every open seam to the chain kernel, as ragged batches and the other shapes do; on != 0 (the default): normal
  * operation.  Same bytes.  Returns the previous setting. */
 int vga_testing_gc_seam_handover_this_thread(int on);
+/* The schedule of the self-served GC-ADPCM encoder on uniform batches, for calls made from the calling thread, at any batch
+ * size: the workgroups' share of the frames in big_rounds rounds of big items, then tail_counts[i] pieces per channel of
+ * tail_frames[i] frames, i = 0, 1, 2 (descending; a count of 0 skips the level), none shorter than min_tail_frames (at least
+ * 64).  The groups flagged as slow-closing take tail_counts[0] pieces of max(tail_frames[0], min(4096, 4 * min_tail_frames))
+ * frames instead.  big_rounds = 0 (or null arrays) restores the default.  Same bytes.  Returns the previous big_rounds. */
+int vga_testing_gc_schedule_this_thread(int big_rounds, const int *tail_counts, const int *tail_frames, int min_tail_frames);
 /* With the hand-over in force the same launch takes the groups of eight channels whose seams are likely to close slowly --
  * a predictor with complex poles next to the unit circle, vgaudio_amd/csrc/gc_plan8.hpp -- from its queue first.  The order
  * of the groups for nch channels' coefficients (16 per channel): order[(nch + 7) / 8] = the flagged groups, ascending, then
@@ -74,6 +86,13 @@ int vga_testing_gc_seam_handover_this_thread(int on);
  * _device: d_coefs in device memory, the table built by the kernel the encoder launches (null stream; the call waits). */
 int vga_testing_gc_slow_order_host(const short *coefs, int nch, int *order);
 int vga_testing_gc_slow_order_device(const void *d_coefs, int nch, int *order);
+/* The one launch in front of the self-served encoder on uniform batches (gc_self_served_prologue_kernel): it builds that table
+ * with a flag per group behind it and fills the scratch the encoder's queue starts from -- zero_ints words of zeros (the queue's
+ * head, the seams' counters and words), a zero per channel (the channels' records) and "no open seam" per channel.  Runs it
+ * (null stream; the call waits) on buffers of its own whose every byte was 0xFF: order_flags[2 * ((nch + 7) / 8) + 1] = the
+ * order, the number of flagged groups, the flags; *bad_words = the words of the fills, and of a guard behind them, that do
+ * not hold what they should.  Returns the number of flagged groups, or -1. */
+int vga_testing_gc_prologue_device(const void *d_coefs, int nch, int zero_ints, int *order_flags, int *bad_words);
 
 /* The host-pointer entry points (vga_*_batch) move data through a pipeline of feeder threads, pinned rings, per-chunk
  * kernel launches and drainer threads (vgaudio_amd/csrc/host_pipeline.hpp); its shape normally follows the volume of

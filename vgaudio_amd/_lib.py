@@ -171,8 +171,10 @@ SIGNATURES = {
     "vga_testing_gc_encoder_segments_this_thread": (ci, [ci]),
     "vga_testing_gc_encoder_persistent_this_thread": (ci, [ci]),
     "vga_testing_gc_seam_handover_this_thread": (ci, [ci]),
+    "vga_testing_gc_schedule_this_thread": (ci, [ci, C.POINTER(ci), C.POINTER(ci), ci]),
     "vga_testing_gc_slow_order_host": (ci, [vp, ci, vp]),
     "vga_testing_gc_slow_order_device": (ci, [vp, ci, vp]),
+    "vga_testing_gc_prologue_device": (ci, [vp, ci, ci, vp, vp]),
     "vga_testing_gc_encode_stats_n": (ci, [C.POINTER(C.c_ulonglong), ci, ci]),
     "vga_testing_last_pipeline_stats": (ci, [vp, ci]),
     "vga_testing_host_pipeline_tail_this_thread": (None, [ci]),
@@ -273,6 +275,7 @@ SIGNATURES = {
     "vga_hca_stream_destroy": (None, [vp]),
     "vga_testing_gc_encode_stats": (ci, [C.POINTER(C.c_ulonglong), ci]),
     "vga_testing_gc_plan_pieces": (ci, [ci, ci, ci, C.c_longlong, ci, C.POINTER(ci)]),
+    "vga_testing_gc_plan_pieces_n": (ci, [ci, ci, ci, C.c_longlong, ci, ci, C.POINTER(ci)]),
     "vga_set_devices": (ci, [vp, ci]),
     "vga_set_progress_callback": (ci, [vp, vp]),
     "vga_get_devices": (ci, [vp, ci]),

@@ -13,13 +13,27 @@ int vga_testing_gc_plan_pieces(int cus, int groups, int frames, long long group_
     if (!out5 || cus <= 0 || groups <= 0 || frames <= 0) return -1;
     bool persistent = false;
     gc::Pieces seg;
+    // (1: the schedule of the self-served shape -- out5 holds two sizes: on uniform batches the schedule of the groups that keep
+    // the coarse tail, which is the only one wherever the tail does not descend; vga_testing_gc_plan_pieces_n has both)
     const int segments = gc::plan_encode_pieces_on(cus, groups, frames, group_frames, ragged != 0, &persistent, &seg,
-                                                     encoder_layout() == 1 ? 1 : 8);   // (1: the schedule of the self-served shape)
+                                                     encoder_layout() == 1 ? 1 : 8);
     out5[0] = segments;
     out5[1] = seg.big;
     out5[2] = seg.nb;
     out5[3] = seg.small;
     out5[4] = persistent ? 1 : 0;
+    return 0;
+}
+
+int vga_testing_gc_plan_pieces_n(int cus, int groups, int frames, long long group_frames, int ragged, int coarse, int *out10)
+{
+    if (!out10 || cus <= 0 || groups <= 0 || frames <= 0) return -1;
+    bool persistent = false;
+    gc::TailPieces seg;
+    const int segments = gc::plan_encode_tail_pieces_on(cus, groups, frames, group_frames, ragged != 0, &persistent, &seg,
+                                                          encoder_layout() == 1 ? 1 : 8, coarse != 0);
+    const int out[10] = {segments, seg.big, seg.nb, seg.small, seg.n1, seg.s2, seg.n2, seg.s3, persistent ? 1 : 0, 0};
+    for (int i = 0; i < 10; i++) out10[i] = out[i];
     return 0;
 }
 

@@ -262,6 +262,7 @@ int coefs_kernel_variant();               // 0: four channels + summing wave per
 int encoder_segments_override();   // > 0: time pieces per channel forced by the test hook
 int encoder_persistent_mode();     // 0: the launcher decides; 1: one workgroup per (channel group, piece); 2: persistent workgroups + queue
 int hca_frames_per_group_override();   // > 0: frames per workgroup of hca_frames_kernel forced by the test hook
+const int *gc_schedule_override(); // test hook: null, or {big rounds, tail counts[3], tail frames[3], floor} of the self-served schedule
 bool gc_seam_handover_off();       // test hook: the self-served encoder leaves every open seam to the chain launch
 // which kernel form the calling thread's last adx::launch_encode / launch_decode took (vga_testing_adx_last_path_this_thread):
 // 1 = the time-piece kernels, 2 = the general lane-per-channel kernel

@@ -291,10 +291,10 @@ ColdOut encode_frame_cold(ColdState st, PassOutB r, int final_sp, int fin)
 // encoding (clamped loads, nothing flushed) with its history frozen.
 // One (channel group, time piece) = what a workgroup of the plain launch does: gc_encode_kernel calls it once with its
 // block indices, gc_encode_persistent_kernel once per item it takes from the queue.
-template <bool REPAIR, int CPW, bool RAGGED, bool SELF = false>
+template <bool REPAIR, int CPW, bool RAGGED, bool SELF = false, class P = Pieces>
 __device__ __forceinline__ void gc_encode_piece(
     const int bx, const int by,
-    const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const Pieces seg,
+    const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const P seg,
     const int16_t *__restrict__ coefs, const int16_t *__restrict__ hist1,
     const int16_t *__restrict__ hist2, uint8_t *__restrict__ adpcm, int64_t adpcm_pitch, int16_t *__restrict__ seg_state,
     const int *__restrict__ first_open, const Ragged &rg)
@@ -1283,9 +1283,10 @@ struct Handover {
 
 // The seams at the ends of the piece a wave of the self-served kernel has just encoded (seam_a, seam_b: 0 = not this wave's),
 // and whatever continuations the hand-over brings it.  ONE copy of seam_run: the runs are steps of a loop.
+template <class P>
 __device__ __forceinline__ void self_served_seams(
-    const int g, const int seam_a, const int seam_b, const int lane, const int groups, const int segments,
-    const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const Pieces seg,
+    const int g, const int seam_a, const int seam_b, const int lane, const int groups, const int segments, const int rec_row,
+    const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const P seg,
     const int16_t *__restrict__ coefs, uint8_t *adpcm, int64_t adpcm_pitch,
     const int16_t *seg_state, int *first_open, int *seam_flag, int *seam_end, int force_open, const Handover hand)
 {
@@ -1371,10 +1372,11 @@ __device__ __forceinline__ void self_served_seams(
                 state &= ~HAND_V;
         }
         // (state, v0, v1): what enters piece k + 1 -- or, behind the stream's last piece, the channel's record in row
-        // segments - 1 (the test hook's equal pieces can leave piece indices behind the end of the stream: nobody encodes
+        // rec_row (segments - 1; round 16: of the longer of the batch's two schedules) (the test hook's equal pieces can leave
+        // piece indices behind the end of the stream: nobody encodes
         // those, and no token waits for them)
         const bool last = k + 1 >= segments || seg.first(k + 1) * 14 >= total_samples;
-        const int64_t nidx = (int64_t)(last ? segments - 1 : k) * nch + ch;
+        const int64_t nidx = (int64_t)(last ? rec_row : k) * nch + ch;
         if (live && lead) {
             hand.v[nidx] = (int)(((unsigned)v1 << 16) | ((unsigned)v0 & 0xFFFFu));
             hand.token[nidx] = state;
@@ -1482,33 +1484,75 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(VGA
 }
 
 // Round 15: the order of the self-served queue on uniform batches (gc_plan8.hpp: plan8_slow_channel, plan8_slow_order) from
-// the coefficients where they are -- on the device, on the encode's stream, never synchronised to the host.  One wave:
+// the coefficients where they are -- on the device, on the encode's stream, never synchronised to the host:
 // order[0 .. S) = the flagged groups of eight, ascending, order[S .. groups8) = the others, order[groups8] = S.
-__global__ __launch_bounds__(64) void gc_slow_groups_kernel(const int16_t *__restrict__ coefs, int nch, int groups8, int *__restrict__ order)
+// Behind it a flag per group, order[groups8 + 1 + g] (round 16: flagged groups keep the coarse tail, plan_encode_pieces_on).
+//
+// Round 16: ONE launch in front of the self-served kernel does this and what three memsets did -- the queue's head with the
+// seams' counters and words behind it (`zero`, zero_ints), the channels' records (`token_row`, nch) and first_open (nch x
+// SEAM_NONE).  The table was one wave with 64 dependent loads per lane (127.7 us at 4096 channels); here workgroup 0 takes a
+// lane per (group, predictor), 128 groups at a time, leaves the flags, and orders them with one scan.  Every workgroup
+// shares the fills.
+constexpr int PROLOGUE_THREADS = 1024;
+__global__ __launch_bounds__(PROLOGUE_THREADS) void gc_self_served_prologue_kernel(
+    const int16_t *__restrict__ coefs, int nch, int groups8, int *__restrict__ order, int *__restrict__ zero, int64_t zero_ints,
+    int *__restrict__ token_row, int *__restrict__ first_open)
 {
-    const int lane = threadIdx.x;
-    auto flagged = [&](int g) {
+    const int64_t step = (int64_t)gridDim.x * PROLOGUE_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * PROLOGUE_THREADS + threadIdx.x; i < zero_ints; i += step) zero[i] = 0;
+    for (int64_t i = (int64_t)blockIdx.x * PROLOGUE_THREADS + threadIdx.x; i < nch; i += step) {
+        token_row[i] = 0;
+        first_open[i] = SEAM_NONE;
+    }
+    if (blockIdx.x != 0 || order == nullptr) return;
+    __shared__ int s_wave[PROLOGUE_THREADS / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int *flag = order + groups8 + 1;
+    // the flags: a lane per (group, predictor), a wave holds eight groups
+    for (int base = 0; base < groups8; base += PROLOGUE_THREADS / 8) {
+        const int g = base + (t >> 3), pr = t & 7;
         bool slow = false;
         if (g < groups8)
-            for (int s = 0; s < PLAN8_SLOTS; s++) {
-                const int ch = g * PLAN8_SLOTS + s;
-                if (ch < nch) slow = plan8_slow_channel(coefs + (int64_t)ch * 16) || slow;
+            for (int sl = 0; sl < PLAN8_SLOTS; sl++) {
+                const int ch = g * PLAN8_SLOTS + sl;
+                if (ch < nch) slow = plan8_slow_predictor(coefs[(int64_t)ch * 16 + 2 * pr], coefs[(int64_t)ch * 16 + 2 * pr + 1]) || slow;
             }
-        return slow;
-    };
-    int total = 0;
-    for (int base = 0; base < groups8; base += 64) total += __popcll(__ballot(flagged(base + lane)));
-    int s = 0, r = total;
-    const unsigned long long lower = (1ull << lane) - 1;
-    for (int base = 0; base < groups8; base += 64) {
-        const int g = base + lane;
-        const bool f = flagged(g);
-        const unsigned long long m = __ballot(f), rest = __ballot(!f && g < groups8);
-        if (g < groups8) order[f ? s + __popcll(m & lower) : r + __popcll(rest & lower)] = g;
-        s += __popcll(m);
-        r += __popcll(rest);
+        const unsigned long long m = __ballot(slow);
+        if (g < groups8 && pr == 0) flag[g] = ((m >> (lane & 56)) & 0xFFull) != 0 ? 1 : 0;
     }
-    if (lane == 0) order[groups8] = total;
+    __syncthreads();                                    // (this workgroup's own stores: visible to it from here on)
+    // the order: every thread a run of consecutive groups, an exclusive scan of the runs' counts
+    const int run = (groups8 + PROLOGUE_THREADS - 1) / PROLOGUE_THREADS;
+    const int g0 = imin(t * run, groups8), g1 = imin(g0 + run, groups8);
+    int mine = 0;
+    for (int g = g0; g < g1; g++) mine += flag[g];
+    int inc = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(inc, o);
+        if (lane >= o) inc += up;
+    }
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < PROLOGUE_THREADS / 64; w++) {
+        const int c = s_wave[w];
+        before += w < wave ? c : 0;
+        total += c;
+    }
+    int s = before + inc - mine;                        // flagged groups below g0
+    for (int g = g0; g < g1; g++) {
+        const int f = flag[g];
+        order[f ? s : total + (g - s)] = g;
+        s += f;
+    }
+    if (t == 0) order[groups8] = total;
+}
+// how many workgroups: one per 16 KiB of fills, at most 64
+static int prologue_workgroups(int64_t zero_ints, int nch)
+{
+    const int64_t want = (zero_ints + 2 * (int64_t)nch + 4 * PROLOGUE_THREADS - 1) / (4 * PROLOGUE_THREADS);
+    return want < 1 ? 1 : want > 64 ? 64 : (int)want;
 }
 // (test-only exports, include/vgaudio_hip_testing.h)
 extern "C" int vga_testing_gc_slow_order_host(const int16_t *coefs, int nch, int *order)
@@ -1520,20 +1564,42 @@ extern "C" int vga_testing_gc_slow_order_host(const int16_t *coefs, int nch, int
         if (plan8_slow_channel(coefs + (int64_t)ch * 16)) flagged[(size_t)(ch / PLAN8_SLOTS)] = 1;
     return plan8_slow_order(flagged.data(), groups8, order);
 }
+// The prologue on buffers of its own, every byte of them 0xFF beforehand: order_flags = the table, S and the flags
+// (2 * groups8 + 1), *bad_words = the words of the fills that do not hold what the memsets left.  Returns S, or -1.
+extern "C" int vga_testing_gc_prologue_device(const void *d_coefs, int nch, int zero_ints, int *order_flags, int *bad_words)
+{
+    if (!d_coefs || !order_flags || nch <= 0 || zero_ints < 0) return -1;
+    const int groups8 = (nch + PLAN8_SLOTS - 1) / PLAN8_SLOTS;
+    const size_t n_order = (size_t)2 * groups8 + 1, n_all = n_order + (size_t)zero_ints + 2 * (size_t)nch + 4;   // (+ 4 guard words)
+    int *d = nullptr;
+    if (hipMalloc(&d, n_all * sizeof(int)) != hipSuccess) return -1;
+    std::vector<int> host(n_all);
+    bool ok = hipMemset(d, 0xFF, n_all * sizeof(int)) == hipSuccess;
+    int *d_zero = d + n_order, *d_token = d_zero + zero_ints, *d_open = d_token + nch;
+    if (ok) {
+        hipLaunchKernelGGL(gc_self_served_prologue_kernel, dim3(prologue_workgroups(zero_ints, nch)), dim3(PROLOGUE_THREADS), 0, (hipStream_t)0,
+                           static_cast<const int16_t *>(d_coefs), nch, groups8, d, d_zero, (int64_t)zero_ints, d_token, d_open);
+        ok = hipGetLastError() == hipSuccess && hipMemcpy(host.data(), d, n_all * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    (void)hipFree(d);
+    if (!ok) return -1;
+    for (size_t i = 0; i < n_order; i++) order_flags[i] = host[i];
+    int bad = 0;
+    for (size_t i = 0; i < (size_t)zero_ints + (size_t)nch; i++) bad += host[n_order + i] != 0;
+    for (int i = 0; i < nch; i++) bad += host[n_order + (size_t)zero_ints + (size_t)nch + (size_t)i] != SEAM_NONE;
+    for (int i = 0; i < 4; i++) bad += host[n_all - 4 + (size_t)i] != -1;                  // (nothing written behind the end)
+    if (bad_words) *bad_words = bad;
+    return host[(size_t)groups8];
+}
 extern "C" int vga_testing_gc_slow_order_device(const void *d_coefs, int nch, int *order)
 {
     if (!d_coefs || !order || nch <= 0) return -1;
     const int groups8 = (nch + PLAN8_SLOTS - 1) / PLAN8_SLOTS;
-    int *d_order = nullptr;
-    if (hipMalloc(&d_order, (size_t)(groups8 + 1) * sizeof(int)) != hipSuccess) return -1;
-    hipLaunchKernelGGL(gc_slow_groups_kernel, dim3(1), dim3(64), 0, (hipStream_t)0, static_cast<const int16_t *>(d_coefs), nch, groups8, d_order);
-    std::vector<int> host((size_t)groups8 + 1);
-    const bool ok = hipGetLastError() == hipSuccess &&
-                    hipMemcpy(host.data(), d_order, host.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(d_order);
-    if (!ok) return -1;
-    for (int g = 0; g < groups8; g++) order[g] = host[(size_t)g];
-    return host[(size_t)groups8];
+    std::vector<int> table((size_t)2 * groups8 + 1);
+    const int s = vga_testing_gc_prologue_device(d_coefs, nch, 0, table.data(), nullptr);
+    if (s < 0) return -1;
+    for (int g = 0; g < groups8; g++) order[g] = table[(size_t)g];
+    return s;
 }
 
 // Round 13: the same queue for the self-served shape (Lay<8, true>): a workgroup is one wave, items are (group of EIGHT
@@ -1543,19 +1609,27 @@ extern "C" int vga_testing_gc_slow_order_device(const void *d_coefs, int nch, in
 // for another workgroup.
 template <bool RAGGED>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void gc_encode_self_served_kernel(
-    const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const Pieces seg,
+    const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const std::conditional_t<RAGGED, Pieces, TailPieces> seg,
     const int16_t *__restrict__ coefs, const int16_t *__restrict__ hist1,
     const int16_t *__restrict__ hist2, uint8_t *adpcm, int64_t adpcm_pitch, int16_t *seg_state,
     const Ragged rg, int groups, int items, int segments, int *__restrict__ queue, int *__restrict__ seam_count, int *first_open,
-    int *seam_flag, int *seam_end, int force_open, const Handover hand, const int *__restrict__ slow_order)
+    int *seam_flag, int *seam_end, int force_open, const Handover hand, const int *__restrict__ slow_order, const TailPieces segc,
+    int segments_c)
 {
     constexpr int CS = PLAN8_SLOTS;
     static_assert(Lay<8, true>::CS == CS && Lay<8, true>::THREADS == 64, "one wave, eight channel slots");
     const int lane = threadIdx.x;
     const uint32_t *host_items = RAGGED ? rg.items : nullptr;
-    // (uniform batches: the groups likely to close their seams slowly first, gc_slow_groups_kernel)
+    // (uniform batches: the groups likely to close their seams slowly first, gc_self_served_prologue_kernel)
     const int *order = RAGGED ? nullptr : slow_order;
     const int slow = order ? order[groups] : 0;
+    // Round 16 (segments_c > 0): the flagged groups have pieces of their own, segc -- the coarse tail -- and come first in the
+    // queue as they did; a group's seams, counters, words and tokens are all indexed by the pieces of ITS schedule, and the
+    // channel records stay in the row behind the last piece of the longer of the two
+    const bool two = !RAGGED && order != nullptr && segments_c > 0;
+    const int front = two ? slow * segments_c : 0;
+    if (two) items = front + (groups - slow) * segments;
+    const int rec_row = (two && segments_c > segments ? segments_c : segments) - 1;
 #ifdef VGA_DEBUG_TIMESTAMPS
     if (lane == 0) g_vga_enc_ts[2 * (blockIdx.x & 32767)] = wall_clock64();
 #endif
@@ -1570,17 +1644,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
             return;
         }
         int g, y;
-        if (!plan8_item(item, groups, nch, host_items, order, slow, segments, g, y)) continue;
-        gc_encode_piece<false, 8, RAGGED, true>(g, y, pcm, pcm_pitch, nch, total_samples, seg, coefs, hist1, hist2, adpcm, adpcm_pitch,
+        const bool coarse = two && item < front;
+        if (!plan8_item(item, groups, nch, host_items, order, slow, two ? segments_c : segments, g, y)) continue;
+        std::conditional_t<RAGGED, Pieces, TailPieces> sg = seg;
+        int ns = segments;
+        if constexpr (!RAGGED)
+            if (coarse) {                               // (wave-uniform: a select of scalars)
+                sg = segc;
+                ns = segments_c;
+            }
+        gc_encode_piece<false, 8, RAGGED, true, std::conditional_t<RAGGED, Pieces, TailPieces>>(g, y, pcm, pcm_pitch, nch, total_samples, sg, coefs, hist1, hist2, adpcm, adpcm_pitch,
                                                 seg_state, (const int *)nullptr, rg);
-        if (segments <= 1) continue;
+        if (ns <= 1) continue;
         // ---- the seams at this piece's ends
         __threadfence();                               // this wave's bytes and piece state are out before it says so
         int at_start = 0, at_end = 0;
         if (lane == 0) {
             // (pieces past the end of the group's longest channel do not exist: nobody waits for them)
             const int total_wg = RAGGED ? rg.length[rg.order[g * CS]] : total_samples;
-            auto exists = [&](int piece) { return piece < segments && seg.first(piece) * 14 < total_wg; };
+            auto exists = [&](int piece) { return piece < ns && sg.first(piece) * 14 < total_wg; };
             if (exists(y)) {
                 if (y >= 1 && atomicAdd(&seam_count[(int64_t)(y - 1) * groups + g], 1) == 1) at_start = y;
                 if (exists(y + 1) && atomicAdd(&seam_count[(int64_t)y * groups + g], 1) == 1) at_end = y + 1;
@@ -1598,7 +1680,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
                     seam_piece<8>(slot, seam_b, lane, pcm, pcm_pitch, nch, total_samples, seg, coefs, adpcm, adpcm_pitch, seg_state,
                                first_open, seam_flag, seam_end, force_open, rg);
             } else                                     // (uniform batches: with the hand-over of open seams, round 15)
-                self_served_seams(g, seam_a, seam_b, lane, groups, segments, pcm, pcm_pitch, nch, total_samples, seg, coefs, adpcm,
+                self_served_seams(g, seam_a, seam_b, lane, groups, ns, rec_row, pcm, pcm_pitch, nch, total_samples, sg, coefs, adpcm,
                                   adpcm_pitch, seg_state, first_open, seam_flag, seam_end, force_open, hand);
         }
     }
@@ -1610,13 +1692,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 // channel was left open too (then V is that seam's recorded end).  Only a run that is still apart at the very end of a
 // stream with a partial last frame goes to the serial repair launch (first_open[channel] = last piece; seg_state gets
 // that piece's true start), which also remains the fall-back when the scratch cannot hold the flags.
-template <int LPC>
-__global__ __launch_bounds__(64) void gc_encode_chain_kernel(
-    const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const Pieces seg, int segments,
+template <int LPC, class P>
+__device__ __forceinline__ void chain_walk(
+    const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const P seg, int segments,
     const int16_t *__restrict__ coefs, uint8_t *__restrict__ adpcm, int64_t adpcm_pitch,
     int16_t *__restrict__ seg_state, int *__restrict__ first_open, const int *__restrict__ seam_flag,
-    const int *__restrict__ seam_end, int force_open, const Ragged rg, const int *__restrict__ hand_token,
-    const int *__restrict__ hand_v)
+    const int *__restrict__ seam_end, int force_open, const Ragged &rg, const int *__restrict__ hand_token,
+    const int *__restrict__ hand_v, const int rec_row)
 {
     const int lane = threadIdx.x;
     const int pr = LPC == 16 ? (lane >> 1) & 7 : lane & 7;
@@ -1629,7 +1711,7 @@ __global__ __launch_bounds__(64) void gc_encode_chain_kernel(
     // Round 15: a channel whose chain the self-served kernel has walked itself (self_served_seams) has a record behind the last
     // piece: nothing of it is walked here -- only first_open is cleared, and the partial last frame encoded when the record
     // carries a V (a run still apart at the very end).  hand_token == nullptr, or a record of 0: as ever.
-    const int64_t rec_idx = (int64_t)(segments - 1) * nch + ch;
+    const int64_t rec_idx = (int64_t)rec_row * nch + ch;
     const int record = hand_token && live ? hand_token[rec_idx] : 0;
     const bool resolved = record != 0;
     const int mine_raw = live ? first_open[ch] : SEAM_NONE;
@@ -1699,12 +1781,41 @@ __global__ __launch_bounds__(64) void gc_encode_chain_kernel(
     if (live && lead && frames_run) atomicAdd(&g_vga_gc_stats[2], (unsigned long long)frames_run);
     if (live && lead) first_open[ch] = SEAM_NONE;
 }
+template <int LPC>
+__global__ __launch_bounds__(64) void gc_encode_chain_kernel(
+    const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const Pieces seg, int segments,
+    const int16_t *__restrict__ coefs, uint8_t *__restrict__ adpcm, int64_t adpcm_pitch,
+    int16_t *__restrict__ seg_state, int *__restrict__ first_open, const int *__restrict__ seam_flag,
+    const int *__restrict__ seam_end, int force_open, const Ragged rg, const int *__restrict__ hand_token,
+    const int *__restrict__ hand_v)
+{
+    chain_walk<LPC, Pieces>(pcm, pcm_pitch, nch, total_samples, seg, segments, coefs, adpcm, adpcm_pitch, seg_state, first_open, seam_flag, seam_end,
+                            force_open, rg, hand_token, hand_v, segments - 1);
+}
+// Round 16, behind the self-served kernel on a uniform batch whose tail descends: a wave here is a group of eight, and a
+// flagged group (slow_flag, the prologue kernel's; nullptr: nobody has the flags, one schedule for all) has the coarse
+// pieces.  The channels' records are in row rec_row, behind the last piece of the longer schedule.
+__global__ __launch_bounds__(64) void gc_encode_chain_tail_kernel(
+    const int16_t *__restrict__ pcm, int64_t pcm_pitch, int nch, int total_samples, const TailPieces seg, int segments,
+    const int16_t *__restrict__ coefs, uint8_t *__restrict__ adpcm, int64_t adpcm_pitch,
+    int16_t *__restrict__ seg_state, int *__restrict__ first_open, const int *__restrict__ seam_flag,
+    const int *__restrict__ seam_end, int force_open, const int *__restrict__ hand_token,
+    const int *__restrict__ hand_v, int rec_row, const int *__restrict__ slow_flag, const TailPieces segc, int segments_c)
+{
+    const bool coarse = slow_flag != nullptr && slow_flag[blockIdx.x] != 0;
+    chain_walk<8, TailPieces>(pcm, pcm_pitch, nch, total_samples, coarse ? segc : seg, coarse ? segments_c : segments, coefs, adpcm, adpcm_pitch,
+                              seg_state, first_open, seam_flag, seam_end, force_open, Ragged{}, hand_token, hand_v, rec_row);
+}
 
 // A piece must be longer than the slowest seam of the batch takes to close, or that channel's seams all stay open and the
 // chain kernel ends up walking the whole channel serially: channels 64..95 of the synthetic set hold one whose seams need
 // ~3000 frames (profiles/r03_b_encode_pieces.log: 96 channels x 60 s in 20.9 ms with 64 pieces of 3214 frames, 60.8 ms
 // with 128, 150 ms with 256; without such a channel more pieces only help: 64 channels 6.7 / 5.5 / 4.0 ms).  Round 2 cut
 // pieces down to 512 frames.
+// Round 15 / 16: this is the floor of every shape whose open seams go to the chain launch -- the plain grid, the 2 + 1 shape,
+// ragged batches.  The self-served shape on uniform batches continues an open seam inside its launch (self_served_seams) and
+// runs the slow-closing groups first and on coarse pieces, so its other groups' tail pieces go down to
+// SELF_SERVED_MIN_TAIL_FRAMES: a short piece there is no longer a seam for the chain launch.
 // (3072 until round 4: at 128 channels that made 66 pieces of 3117 frames and the slow channel's seams stayed open -- 33.5 ms
 // against 21.2 ms with 64 pieces of 3215)
 constexpr int MIN_PIECE_FRAMES = 3584;
@@ -1726,11 +1837,20 @@ constexpr int PERSISTENT_BIG_ROUNDS = 3;       // a workgroup's share of the fra
 constexpr int PERSISTENT_SMALL_ROUNDS = 2;     // ... followed by this many rounds of short items
 constexpr int PERSISTENT_SMALL_FRAMES = 4096;  // ... of this many frames
 // The self-served shape (uniform batches): four big rounds and ONE round of short items -- its items are half the size, and
-// every short piece more is a seam that a slow-closing channel can leave open for the chain launch (one sweep on the
-// synthetic set, profiles/r13_encode_ab.log: big,small rounds 4,1 108.4 ms; 2,1 108.8; 2,2 109.3; 3,1 109.4; 5,2 112.8;
+// until round 15 every short piece more was a seam that a slow-closing channel could leave open for the chain launch (one
+// sweep on the synthetic set, profiles/r13_encode_ab.log: big,small rounds 4,1 108.4 ms; 2,1 108.8; 2,2 109.3; 3,1 109.4; 5,2 112.8;
 // 4,2 114.2; 4,3 116.5; 3,3 117.1; 3,2 115.7-117.7; the 2 + 1 shape's pieces as they are 110.5-110.8; parent 111.4-111.8).
 constexpr int SELF_SERVED_BIG_ROUNDS = 4;
 constexpr int SELF_SERVED_SMALL_ROUNDS = 1;
+// Round 16: since round 15 a seam that outlives its piece is continued inside the launch, so for the self-served shape on
+// uniform batches a short piece is no longer a seam for the chain launch, and the tail may descend: rounds of items of
+// SELF_SERVED_TAIL_FRAMES, none shorter than SELF_SERVED_MIN_TAIL_FRAMES.  The groups gc_self_served_prologue_kernel flags (their
+// seams need 1000-3000 frames) keep the two-size schedule above, tail pieces of SELF_SERVED_COARSE_FRAMES: cut finer,
+// every one of their tail seams would stay open and the token walk would re-encode the channel's tail serially.
+constexpr int SELF_SERVED_TAIL_ROUNDS[3] = {1, 1, 1};
+constexpr int SELF_SERVED_TAIL_FRAMES[3] = {4096, 2048, 1024};
+constexpr int SELF_SERVED_MIN_TAIL_FRAMES = 1024;
+constexpr int SELF_SERVED_COARSE_FRAMES = 4096;
 constexpr int MAX_PIECES = 1024;               // what encode_scratch_bytes() and the ragged item list (capi_gcadpcm_v.hip) are sized for
 
 // The piece schedule (see Pieces, gcadpcm_kernels.hpp).  Plain grid: as many equal pieces as put two encoder waves on
@@ -1762,6 +1882,17 @@ int plan_encode_pieces(int groups, int frames, int64_t group_frames, bool ragged
 // vga_testing_gc_plan_pieces)
 int plan_encode_pieces_on(int cus, int groups, int frames, int64_t group_frames, bool ragged, bool *persistent_out, Pieces *seg_out, int layout)
 {
+    // (two sizes: for the self-served shape on uniform batches the schedule of the groups that keep the coarse tail, which is
+    // the only one wherever the tail does not descend)
+    TailPieces seg;
+    const int segments = plan_encode_tail_pieces_on(cus, groups, frames, group_frames, ragged, persistent_out, &seg, layout, true);
+    *seg_out = seg.two();
+    return segments;
+}
+
+int plan_encode_tail_pieces_on(int cus, int groups, int frames, int64_t group_frames, bool ragged, bool *persistent_out, TailPieces *seg_out,
+                               int layout, bool coarse)
+{
     // persistent workgroups taking (channel group, piece) items from a queue (gc_encode_persistent_kernel) once the batch
     // has enough channel groups; test hook: 1 = never, 2 = always
     // layout 1, the self-served shape (forced by the test hook or the launcher's choice): it exists as persistent workgroups
@@ -1783,46 +1914,81 @@ int plan_encode_pieces_on(int cus, int groups, int frames, int64_t group_frames,
     if (segments < 1) segments = 1;
     if (segments > MAX_PIECES) segments = MAX_PIECES;
     if (encoder_segments_override() > 0) segments = imin(imin(imax(frames / 64, 1), encoder_segments_override()), MAX_PIECES);   // test hook
-    Pieces seg;
+    TailPieces seg;
     seg.big = (frames + segments - 1) / segments;
     seg.nb = segments;
     seg.small = seg.big;
-    if (persistent && encoder_segments_override() <= 0 && frames >= 4 * MIN_PIECE_FRAMES &&
-        (ragged || groups * PERSISTENT_SCHEDULE_GROUPS_FACTOR >= cus * 4)) {
+    // (the test hook's schedule -- the self-served shape on uniform batches only -- applies at any size)
+    const int *forced = self && !ragged ? gc_schedule_override() : nullptr;
+    if (persistent && encoder_segments_override() <= 0 &&
+        (forced || (frames >= 4 * MIN_PIECE_FRAMES && (ragged || groups * PERSISTENT_SCHEDULE_GROUPS_FACTOR >= cus * 4)))) {
         // (ragged batches, mixed-lengths set of bench.py: 4 rounds 151.7 ms, 3: 158.2, 6: 154.5, 8: 169.5; profiles/r04_a_ragged_schedules.log)
-        int big_rounds = ragged ? PERSISTENT_BIG_ROUNDS + 1 : PERSISTENT_BIG_ROUNDS, small_rounds = PERSISTENT_SMALL_ROUNDS, small = PERSISTENT_SMALL_FRAMES;
-        if (self && !ragged) { big_rounds = SELF_SERVED_BIG_ROUNDS; small_rounds = SELF_SERVED_SMALL_ROUNDS; }   // (ragged: not swept, kept)
+        int big_rounds = ragged ? PERSISTENT_BIG_ROUNDS + 1 : PERSISTENT_BIG_ROUNDS;
+        // the tail: up to three levels of (rounds of items, frames), descending; `floor`: no tail piece is shorter
+        int rounds[3] = {PERSISTENT_SMALL_ROUNDS, 0, 0}, size[3] = {PERSISTENT_SMALL_FRAMES, 0, 0}, count[3] = {-1, -1, -1}, floor = MIN_PIECE_FRAMES;
+        if (self && !ragged) {                                                              // (ragged: not swept, kept)
+            big_rounds = SELF_SERVED_BIG_ROUNDS;
+            rounds[0] = SELF_SERVED_SMALL_ROUNDS;
+            if (!coarse) {
+                for (int i = 0; i < 3; i++) { rounds[i] = SELF_SERVED_TAIL_ROUNDS[i]; size[i] = SELF_SERVED_TAIL_FRAMES[i]; }
+                floor = SELF_SERVED_MIN_TAIL_FRAMES;
+            }
+        }
 #ifdef VGA_TUNING   // tools/build_variants.sh only: the product never reads its schedule from the environment
-        if (const char *e = std::getenv("VGA_HIP_GC_SCHEDULE")) std::sscanf(e, "%d,%d,%d", &big_rounds, &small_rounds, &small);
+        if (const char *e = std::getenv("VGA_HIP_GC_SCHEDULE"))
+            if (!coarse) std::sscanf(e, "%d,%d,%d,%d,%d,%d,%d", &big_rounds, &rounds[0], &size[0], &rounds[1], &size[1], &rounds[2], &size[2]);
 #endif
-        small = imax(small, MIN_PIECE_FRAMES);
+        if (forced) {                                   // piece counts as given, not rounds
+            big_rounds = forced[0];
+            floor = forced[7];
+            for (int i = 0; i < 3; i++) { count[i] = forced[1 + i]; size[i] = forced[4 + i]; rounds[i] = 0; }
+            if (coarse) {                               // one level, no shorter than 4096 frames unless the floor is a test's
+                floor = size[0] = imax(size[0], imin(SELF_SERVED_COARSE_FRAMES, 4 * floor));
+                count[1] = count[2] = 0;
+            }
+        }
         big_rounds = imax(big_rounds, 1);
         const int wgs = cus * (self ? PLAN8_WGS_PER_CU : persistent_wgs_per_cu());
         const int queue_groups = self ? 2 * groups : groups;
         const int64_t per_wg = group_frames * (self ? 2 : 1) / wgs + 1;                     // a workgroup's share of the frames
-        int ns = (small_rounds * wgs + queue_groups / 2) / queue_groups;                    // piece indices that make small_rounds rounds of items
-        if ((int64_t)ns * small > frames / 2) ns = frames / (2 * small);
-        int big = (int)imax((int)((per_wg - (int64_t)small_rounds * small) / big_rounds), small);
-        int nb = (int)((frames - (int64_t)ns * small + big - 1) / big);
+        int64_t tail = 0, tail_share = 0;               // frames of a channel in tail pieces; of a workgroup's share in tail items
+        for (int i = 0; i < 3; i++) {
+            size[i] = imax(size[i], floor);
+            if (i > 0) size[i] = imin(size[i], size[i - 1]);
+            const bool given = count[i] >= 0;
+            if (!given) count[i] = (rounds[i] * wgs + queue_groups / 2) / queue_groups;     // piece indices that make rounds[i] rounds of items
+            if (tail + (int64_t)count[i] * size[i] > frames / 2) count[i] = (int)((frames / 2 - tail) / size[i]);
+            tail += (int64_t)count[i] * size[i];
+            tail_share += given ? (int64_t)count[i] * size[i] * queue_groups / wgs : (int64_t)rounds[i] * size[i];
+        }
+        const int small = size[0];
+        int big = (int)imax((int)((per_wg - tail_share) / big_rounds), small);
+        int nb = (int)((frames - tail + big - 1) / big);
         if (nb < 1) nb = 1;
-        if (!ragged) big = (int)((frames - (int64_t)ns * small + nb - 1) / nb);             // equal big pieces
+        if (!ragged) big = (int)((frames - tail + nb - 1) / nb);                            // equal big pieces
         if (big < small) big = small;
+        seg = TailPieces{};
         seg.big = big;
         seg.nb = nb;
         seg.small = small;
-        segments = nb + ns;
+        // (the last level in use has no end: the pieces cover whatever rounding leaves)
+        if (count[2] > 0) { seg.n1 = count[0]; seg.s2 = size[1]; seg.n2 = count[1]; seg.s3 = size[2]; }
+        else if (count[1] > 0) { seg.n1 = count[0]; seg.s2 = size[1]; }
+        segments = nb + count[0] + count[1] + count[2];
         while (segments > 1 && seg.first(segments - 1) >= frames) segments--;
         if (segments > MAX_PIECES) {
-            // A long channel in a batch of few groups: the two sizes would need more pieces than the scratch arrays and the
+            // A long channel in a batch of few groups: the sizes would need more pieces than the scratch arrays and the
             // host's item list hold.  Equal pieces instead -- the pieces must COVER the channel (nobody encodes what lies
             // past seg.first(segments)).
             segments = MAX_PIECES;
+            seg = TailPieces{};
             seg.big = seg.small = (frames + segments - 1) / segments;
             seg.nb = segments;
             while (segments > 1 && seg.first(segments - 1) >= frames) segments--;
         }
     }
     if (seg.first(segments) < frames) {                // (every branch above covers; should one ever not: equal pieces do)
+        seg = TailPieces{};
         seg.big = seg.small = (frames + segments - 1) / segments;
         seg.nb = segments;
     }
@@ -1874,21 +2040,39 @@ static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch
     }
     // the self-served shape takes the pieces in groups of eight channel slots (gc_plan8.hpp)
     const bool self = want_self && persistent;
+    // Round 16: the self-served kernel on a uniform batch takes its pieces as TailPieces (tseg: the tail may descend); `seg` stays
+    // what every other launch reads (with a descending tail nobody does: the repair launch returns before it looks).
+    TailPieces tseg, segc;
+    int segments_c = 0;
+    if (self && !RAGGED) {
+        bool p = false;
+        segments = plan_encode_tail_pieces_on(cus, groups, frames, (int64_t)groups * frames, false, &p, &tseg, 1, false);
+        seg = tseg.two();
+    }
     const Plan8 p8 = self ? plan_groups_of_eight(cus, nch, segments, RAGGED && rg.items ? rg.n_items : -1) : Plan8{};
     const int seam_groups = self ? p8.groups : groups;
     AsyncBuf scratch;                                  // freed (stream-ordered) on every exit path
     int16_t *seg_state = nullptr;
     int *first_open = nullptr, *seam_flag = nullptr, *seam_end = nullptr, *queue = nullptr, *seam_count = nullptr;
     // open seams handed on inside the self-served kernel (self_served_seams): uniform batches; the test hook switches it off
+    // Round 16: the groups the order table flags keep the coarse tail (plan_encode_tail_pieces_on); `rows`: the pieces of the
+    // longer of the two schedules, what the scratch arrays are sized for.  Without the hand-over nobody has the flags: one schedule.
     const bool handover = self && !RAGGED && segments > 1 && !gc_seam_handover_off();
+    if (handover) {
+        bool p = false;
+        segments_c = plan_encode_tail_pieces_on(cus, groups, frames, (int64_t)groups * frames, false, &p, &segc, 1, true);
+        if (segments_c == segments && segc.same_as(tseg)) segments_c = 0;     // (nothing to tell apart)
+    }
+    const bool tail_chain = self && !RAGGED && (segments_c > 0 || !tseg.two_sizes());
+    const int rows = imax(segments, segments_c);
     Handover hand;
     int *slow_order = nullptr;
     if (segments > 1 || persistent) {
-        const size_t state_bytes = segments > 1 ? (size_t)round_up((int64_t)segments * nch * 2 * (int64_t)sizeof(int16_t), 16) : 0;
+        const size_t state_bytes = segments > 1 ? (size_t)round_up((int64_t)rows * nch * 2 * (int64_t)sizeof(int16_t), 16) : 0;
         const size_t open_bytes = (size_t)round_up((int64_t)nch * (int64_t)sizeof(int), 16);
-        const size_t count_bytes = persistent && segments > 1 ? (size_t)round_up((int64_t)(segments - 1) * seam_groups * (int64_t)sizeof(int), 16) : 0;
+        const size_t count_bytes = persistent && segments > 1 ? (size_t)round_up((int64_t)(rows - 1) * seam_groups * (int64_t)sizeof(int), 16) : 0;
         // (the hand-over: a word per seam and group behind seam_count's, then a token and a V per piece and channel)
-        const size_t order_bytes = handover ? (size_t)round_up((int64_t)(seam_groups + 1) * (int64_t)sizeof(int), 16) : 0;   // (gc_slow_groups_kernel's table)
+        const size_t order_bytes = handover ? (size_t)round_up((int64_t)(2 * seam_groups + 1) * (int64_t)sizeof(int), 16) : 0;   // (gc_self_served_prologue_kernel's table and flags)
         const size_t need = 3 * state_bytes + open_bytes + 16 + count_bytes + (handover ? count_bytes + 2 * state_bytes + order_bytes : 0);
         // the caller's scratch when it brought one (the host pipeline: hipMallocAsync next to busy copy streams stalled
         // its launching thread for up to 300 ms per call), a stream-ordered allocation otherwise
@@ -1901,13 +2085,14 @@ static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch
         seam_end = reinterpret_cast<int *>(base + 2 * state_bytes);
         first_open = reinterpret_cast<int *>(base + 3 * state_bytes);
         queue = reinterpret_cast<int *>(base + 3 * state_bytes + open_bytes);
+        // (with the hand-over all the fills below are the prologue kernel's, one launch: gc_self_served_prologue_kernel)
         if (segments > 1) {
             seg_state = reinterpret_cast<int16_t *>(base);
-            VGA_HIP_TRY(fill_no_open_seams(first_open, nch, stream));
+            if (!handover) VGA_HIP_TRY(fill_no_open_seams(first_open, nch, stream));
         } else
             seg_state = nullptr;
         seam_count = queue + 4;
-        if (persistent) VGA_HIP_TRY(hipMemsetAsync(queue, 0, 16 + count_bytes * (handover ? 2 : 1), stream));    // the queue's head and every seam's counter (and word)
+        if (persistent && !handover) VGA_HIP_TRY(hipMemsetAsync(queue, 0, 16 + count_bytes, stream));    // the queue's head and every seam's counter
         if (handover) {
             unsigned char *words = base + 3 * state_bytes + open_bytes + 16 + count_bytes;
             hand.word = reinterpret_cast<int *>(words);
@@ -1915,15 +2100,22 @@ static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch
             hand.v = reinterpret_cast<int *>(words + count_bytes + state_bytes);
             slow_order = reinterpret_cast<int *>(words + count_bytes + 2 * state_bytes);
             // (the channels' records, the row behind the last piece: "not walked" unless the kernel says otherwise)
-            VGA_HIP_TRY(hipMemsetAsync(hand.token + (size_t)(segments - 1) * nch, 0, (size_t)nch * sizeof(int), stream));
+            if constexpr (CPW == 8 && !RAGGED) {
+                const int64_t zero_ints = (int64_t)(16 + 2 * count_bytes) / (int64_t)sizeof(int);    // the queue's head, every seam's counter and word
+                hipLaunchKernelGGL(gc_self_served_prologue_kernel, dim3(prologue_workgroups(zero_ints, nch)), dim3(PROLOGUE_THREADS), 0, stream,
+                                   d_coefs, nch, p8.groups, slow_order, queue, zero_ints, hand.token + (size_t)(rows - 1) * nch, first_open);
+                VGA_HIP_TRY(hipGetLastError());
+            }
         }
     }
     if (self) {
         if constexpr (CPW == 8) {
-            if (slow_order) hipLaunchKernelGGL(gc_slow_groups_kernel, dim3(1), dim3(64), 0, stream, d_coefs, nch, p8.groups, slow_order);
+            std::conditional_t<RAGGED, Pieces, TailPieces> self_seg;
+            if constexpr (RAGGED) self_seg = seg; else self_seg = tseg;
             hipLaunchKernelGGL((gc_encode_self_served_kernel<RAGGED>), dim3(p8.wgs), dim3(Lay<8, true>::THREADS), 0, stream, d_pcm, pcm_pitch,
-                               nch, sample_count, seg, d_coefs, d_hist1, d_hist2, d_adpcm, adpcm_pitch, seg_state, rg, p8.groups, p8.items,
-                               segments, queue, seam_count, first_open, seam_flag, seam_end, force_open_seams(), hand, (const int *)slow_order);
+                               nch, sample_count, self_seg, d_coefs, d_hist1, d_hist2, d_adpcm, adpcm_pitch, seg_state, rg, p8.groups, p8.items,
+                               segments, queue, seam_count, first_open, seam_flag, seam_end, force_open_seams(), hand, (const int *)slow_order, segc,
+                               segments_c);
         }
     } else if (persistent) {
         const int items = RAGGED && rg.items ? rg.n_items : groups * segments;
@@ -1960,6 +2152,12 @@ static int launch_encode_layout(const int16_t *d_pcm, int64_t pcm_pitch, int nch
             VGA_HIP_TRY(hipGetLastError());
         }
         // the seams that were still open at the end of their piece, chained piece after piece (none: every wave returns)
+        if (tail_chain)                                // (the self-served shape on a uniform batch whose tail descends)
+            hipLaunchKernelGGL(gc_encode_chain_tail_kernel, dim3((nch + 7) / 8), dim3(64), 0, stream, d_pcm, pcm_pitch, nch, sample_count, tseg,
+                               segments, d_coefs, d_adpcm, adpcm_pitch, seg_state, first_open, seam_flag, seam_end, force_open_seams(),
+                               (const int *)hand.token, (const int *)hand.v, rows - 1,
+                               (const int *)(segments_c > 0 ? slow_order + seam_groups + 1 : nullptr), segc, segments_c);
+        else
 #ifdef VGA_GC_SEAM16_ALWAYS
         if (CPW == 4)
 #else

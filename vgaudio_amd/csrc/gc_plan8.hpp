@@ -69,7 +69,7 @@ VGA_PLAN8_HD inline bool plan8_slow_channel(const int16_t *coefs16)
     return slow;
 }
 // The order of the groups: order[0 .. S) = the flagged groups, ascending, order[S .. groups8) = the others, ascending.
-// Returns S.  (The device builds the same table from the coefficients where they are: gc_slow_groups_kernel.)
+// Returns S.  (The device builds the same table from the coefficients where they are: gc_self_served_prologue_kernel.)
 inline int plan8_slow_order(const unsigned char *flagged, int groups8, int *order)
 {
     int s = 0;
@@ -85,7 +85,9 @@ inline int plan8_slow_order(const unsigned char *flagged, int groups8, int *orde
 // item's two halves next to each other.  false: nothing to encode (the half lies behind the batch's last channel).
 // order / slow (uniform batches, plan8_slow_order; order == nullptr: none): the first slow x segments items are all pieces
 // of the flagged groups, piece-major among them, the rest is the piece-major order over the other groups; with no flagged
-// group or with every group flagged the order is the plain one.
+// group or with every group flagged the order is the plain one.  Round 16: `segments` is the piece count of the FLAGGED
+// groups (they keep the coarse tail, a schedule of their own: gc::plan_encode_tail_pieces_on); the others' count only
+// bounds the queue, slow x segments + (groups8 - slow) x theirs, which the caller knows.
 VGA_PLAN8_HD inline bool plan8_item(int item, int groups8, int nch, const uint32_t *host_items, const int *order, int slow, int segments,
                                     int &g, int &y)
 {

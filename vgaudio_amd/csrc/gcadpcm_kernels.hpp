@@ -20,6 +20,24 @@ struct Pieces {
     __host__ __device__ int64_t first(int k) const { return (int64_t)(k < nb ? k : nb) * big + (int64_t)(k > nb ? k - nb : 0) * small; }
     __host__ __device__ int frames(int k) const { return k < nb ? big : small; }
 };
+// Round 16, the self-served shape on uniform batches only (every other kernel keeps Pieces): the tail is a short descending
+// sequence -- behind the big pieces `n1` pieces of `small` frames, then `n2` of `s2`, then pieces of `s3`.  The last level in
+// use has no end (n1 or n2 = PIECES_NO_END), so the pieces cover a channel of any length; n1 = PIECES_NO_END is Pieces.
+constexpr int PIECES_NO_END = 1 << 30;
+struct TailPieces {
+    int big = 0, nb = 0, small = 0;
+    int n1 = PIECES_NO_END, s2 = 0, n2 = PIECES_NO_END, s3 = 0;
+    __host__ __device__ int64_t first(int k) const
+    {
+        const int t = k > nb ? k - nb : 0;              // tail pieces before k
+        const int a = t < n1 ? t : n1, b = t - a < n2 ? t - a : n2;
+        return (int64_t)(k < nb ? k : nb) * big + (int64_t)a * small + (int64_t)b * s2 + (int64_t)(t - a - b) * s3;
+    }
+    __host__ __device__ int frames(int k) const { return k < nb ? big : k - nb < n1 ? small : k - nb - n1 < n2 ? s2 : s3; }
+    bool two_sizes() const { return n1 == PIECES_NO_END; }
+    Pieces two() const { Pieces p; p.big = big; p.nb = nb; p.small = small; return p; }   // (what it is when two_sizes())
+    bool same_as(const TailPieces &o) const { return big == o.big && nb == o.nb && small == o.small && n1 == o.n1 && s2 == o.s2 && n2 == o.n2 && s3 == o.s3; }
+};
 // The encoder's piece schedule for `groups` channel groups (16 channels each) whose longest channel has `frames` frames and
 // which hold `group_frames` frames of work in all (sum over groups of the group's longest channel); persistent = workgroups
 // that take (group, piece) items from a queue (the (channel, predictor) layout only: layout == 8, or layout == 1: the
@@ -30,6 +48,11 @@ int encoder_plan_layout(int groups, bool ragged);
 int plan_encode_pieces(int groups, int frames, int64_t group_frames, bool ragged, bool *persistent, Pieces *seg, int layout = 8);
 // ... on a device with `cus` compute units (host arithmetic only)
 int plan_encode_pieces_on(int cus, int groups, int frames, int64_t group_frames, bool ragged, bool *persistent, Pieces *seg, int layout = 8);
+// ... with the descending tail of the self-served shape on uniform batches (layout 1, not ragged; everything else comes out in
+// two sizes).  coarse: the schedule of the groups whose seams close slowly -- the two-size one, which is also what
+// plan_encode_pieces_on returns for the shape
+int plan_encode_tail_pieces_on(int cus, int groups, int frames, int64_t group_frames, bool ragged, bool *persistent, TailPieces *seg, int layout,
+                               bool coarse);
 
 struct Ragged {
     // the encoder's items (channel group | piece << 20), biggest first, when the host has planned them (ragged batches)

@@ -40,6 +40,7 @@ struct ThreadSettings {
     int encoder_persistent = 0;
     int hca_frames_per_group = 0;
     int gc_seam_handover_off = 0;
+    int gc_schedule[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // [0] != 0: forced (big rounds, three tail counts, three tail sizes, floor)
     PipeOverride pipe;
     FailStep fail;
 };

@@ -51,6 +51,7 @@ int encoder_segments_override() { return g_settings.encoder_segments; }
 int encoder_persistent_mode() { return g_settings.encoder_persistent; }
 int hca_frames_per_group_override() { return g_settings.hca_frames_per_group; }
 bool gc_seam_handover_off() { return g_settings.gc_seam_handover_off != 0; }
+const int *gc_schedule_override() { return g_settings.gc_schedule[0] > 0 ? g_settings.gc_schedule : nullptr; }
 // not a setting but a record: what the calling thread's last ADX launches chose (0 = none yet)
 static thread_local int g_adx_encode_path = 0, g_adx_decode_path = 0;
 void note_adx_encode_path(int path) { g_adx_encode_path = path; }
@@ -181,6 +182,20 @@ int vga_testing_gc_seam_handover_this_thread(int on)
 {
     const int old = g_settings.gc_seam_handover_off ? 0 : 1;
     g_settings.gc_seam_handover_off = on ? 0 : 1;
+    return old;
+}
+int vga_testing_gc_schedule_this_thread(int big_rounds, const int *tail_counts, const int *tail_frames, int min_tail_frames)
+{
+    int *s = g_settings.gc_schedule;
+    const int old = s[0];
+    for (int i = 0; i < 8; i++) s[i] = 0;
+    if (big_rounds <= 0 || !tail_counts || !tail_frames) return old;
+    s[0] = big_rounds;
+    s[7] = min_tail_frames < 64 ? 64 : min_tail_frames;
+    for (int i = 0; i < 3; i++) {
+        s[1 + i] = tail_counts[i] > 0 ? tail_counts[i] : 0;
+        s[4 + i] = tail_frames[i] < s[7] ? s[7] : tail_frames[i];
+    }
     return old;
 }
 int vga_testing_hca_frames_per_group_this_thread(int frames)
