@@ -76,7 +76,10 @@
  * call.  The object keeps its tables in the memory of the device that was current at create, is immutable and serves any
  * number of calls, concurrent calls on different streams included.
  *
- * LEFT OUT: keyed encryption in sets (encryption_type is the header byte only, as in vga_adx_write_device); host-pointer
+ * Keyed encryption of sets is vgaudio_hip_files/adx_keyed_files.h's, on the objects made here; in the calls of THIS header
+ * encryption_type is the header byte only, as in vga_adx_write_device.
+ *
+ * LEFT OUT: host-pointer
  * forms of the _v calls; HCA file sets (header plus copy: they can follow on this scaffolding); a ragged ADX decode with a
  * start history per channel (vga_adx_params.history is one value per object, so the read side ends at the rows and the
  * histories); moving the per-file vga_adx_write_device onto the span kernel (that changes an existing call's launches and

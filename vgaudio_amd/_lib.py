@@ -421,6 +421,12 @@ SIGNATURES = {
     "vga_hca_files_read_items_for": (ci, [vp, ci, C.POINTER(i64), C.POINTER(i64), ci, vp, i64, C.POINTER(i64)]),
     "vga_hca_files_stats": (ci, [vp, C.POINTER(i64)]),
     "vga_hca_files_force_general_this_thread": (ci, [ci]),
+    # include/vgaudio_hip_files/adx_keyed_files.h
+    "vga_adx_write_keyed_device_v": (ci, [vp, vp, vp, vp, ci, vp, vp, vp, vp]),
+    "vga_adx_read_keyed_device_v": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp]),
+    "vga_adx_find_keys_workspace_bytes": (C.c_size_t, [vp, ci, ci]),
+    "vga_adx_find_keys_device_v": (ci, [vp, vp, vp, ci, ci, vp, vp, C.c_size_t, vp]),
+    "vga_adx_find_keys_items_for": (ci, [vp, ci, C.POINTER(i64), vp, i64, C.POINTER(i64)]),
 }
 
 
@@ -451,6 +457,11 @@ class AdxFilesItemC(C.Structure):
     """vga_adx_files_item"""
     _fields_ = [("form", C.c_int), ("file", C.c_int), ("x", C.c_int), ("y", C.c_uint32), ("granule", C.c_int),
                 ("begin", C.c_int64), ("end", C.c_int64), ("keep_end", C.c_int64)]
+
+
+class AdxFindKeysItemC(C.Structure):
+    """vga_adx_find_keys_item (include/vgaudio_hip_files/adx_keyed_files.h)"""
+    _fields_ = [("file", C.c_int), ("first_slot", C.c_int), ("slot_count", C.c_int)]
 
 
 class WaveInfoC(C.Structure):

@@ -247,22 +247,102 @@ class AdxFileSet:
                                                ptr(audio, torch.uint8, t.audio_bytes, "audio"),
                                                ptr(history, torch.int16, self.channels, "history"), DspFileSet._stream(stream)))
 
+    # ---- keyed calls (include/vgaudio_hip_files/adx_keyed_files.h)
+    @staticmethod
+    def _keys(keys):
+        """(address, count) of device keys: an int32 tensor of 3 * n values (device_keys)"""
+        import torch
+        if keys is None:
+            return None, 0
+        if not (isinstance(keys, torch.Tensor) and keys.is_cuda and keys.dtype == torch.int32 and keys.is_contiguous() and keys.numel() % 3 == 0):
+            raise _lib.ArgumentError("keys: a contiguous int32 tensor on the device, (seed, mult, inc) per key (adx.device_keys)")
+        return keys.data_ptr(), keys.numel() // 3
+
+    def write_keyed_device(self, audio, images, keys, key_index=None, history=None, status=None, stream=None):
+        """vga_adx_write_keyed_device_v: write_device with the audio of file f encrypted under keys[key_index[f]] (key_index None:
+        keys[0] for every file; an index < 0: unkeyed) and the file's own encryption type.  keys: device_keys(...);
+        key_index, status: int32[files] on the device or None"""
+        import torch
+        from .dsp import DspFileSet
+        ptr, t = DspFileSet._ptr, self.totals
+        kp, nk = self._keys(keys)
+        check(_lib.lib().vga_adx_write_keyed_device_v(self._h, ptr(audio, torch.uint8, t.audio_bytes, "audio"),
+                                                      ptr(history, torch.int16, self.channels, "history"), kp, nk,
+                                                      ptr(key_index, torch.int32, self.files, "key_index"),
+                                                      ptr(images, torch.uint8, t.image_bytes, "images"),
+                                                      ptr(status, torch.int32, self.files, "status"), DspFileSet._stream(stream)))
+
+    def read_keyed_device(self, images, audio, keys, key_index=None, history=None, status=None, stream=None):
+        """vga_adx_read_keyed_device_v (a set from from_infos): read_device with the rows of file f decrypted under
+        keys[key_index[f]] and encryption type = the file's revision.  key_index: e.g. what find_keys_device returned"""
+        import torch
+        from .dsp import DspFileSet
+        ptr, t = DspFileSet._ptr, self.totals
+        kp, nk = self._keys(keys)
+        check(_lib.lib().vga_adx_read_keyed_device_v(self._h, ptr(images, torch.uint8, t.image_bytes, "images"), kp, nk,
+                                                     ptr(key_index, torch.int32, self.files, "key_index"),
+                                                     ptr(audio, torch.uint8, t.audio_bytes, "audio"),
+                                                     ptr(history, torch.int16, self.channels, "history"),
+                                                     ptr(status, torch.int32, self.files, "status"), DspFileSet._stream(stream)))
+
+    def find_keys_workspace_bytes(self, nkeys8, nkeys9):
+        return int(_lib.lib().vga_adx_find_keys_workspace_bytes(self._h, int(nkeys8), int(nkeys9)))
+
+    def find_keys_device(self, images, keys8, keys9, workspace=None, stream=None):
+        """vga_adx_find_keys_device_v (a set from from_infos).  keys8 / keys9: device_keys(...) or None, the candidates for files
+        of revision 8 / of any other non-zero revision.  Returns an int32[files] device tensor of indices into
+        torch.cat([keys8, keys9]) (-1: no candidate fits), written on the stream and not read here: it goes straight into
+        read_keyed_device with keys = that concatenation.  workspace: uint8[find_keys_workspace_bytes] or None (allocated)."""
+        import torch
+        from .dsp import DspFileSet
+        ptr, t = DspFileSet._ptr, self.totals
+        (_, n8), (_, n9) = self._keys(keys8), self._keys(keys9)
+        both = [k for k in (keys8, keys9) if k is not None and k.numel()]
+        keys = both[0] if len(both) == 1 else torch.cat(both) if both else None
+        need = self.find_keys_workspace_bytes(n8, n9)
+        if workspace is None:
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=images.device)
+        index = torch.empty(max(self.files, 1), dtype=torch.int32, device=images.device)
+        check(_lib.lib().vga_adx_find_keys_device_v(self._h, ptr(images, torch.uint8, t.image_bytes, "images"), self._keys(keys)[0], n8, n9,
+                                                    index.data_ptr(), ptr(workspace, torch.uint8, need, "workspace"), workspace.numel(),
+                                                    DspFileSet._stream(stream)))
+        self._find_keep = (keys, workspace)                            # alive until the next call (the stream may still read them)
+        return index[:self.files]
+
+    @classmethod
+    def find_items(cls, infos, image_offsets=None):
+        """the work items of find_keys_device's scan on a set of such infos (_lib.AdxFindKeysItemC), host only"""
+        infos = list(infos)
+        ptrs = (C.c_void_p * max(len(infos), 1))(*[C.addressof(i) for i in infos])
+        keep, offs = _i64_or_none(image_offsets)
+        call, count = _lib.lib().vga_adx_find_keys_items_for, C.c_int64()
+        check(call(ptrs, len(infos), offs, None, 0, C.byref(count)))
+        items = (_lib.AdxFindKeysItemC * max(count.value, 1))()
+        check(call(ptrs, len(infos), offs, items, count.value, C.byref(count)))
+        return list(items[:count.value])
+
     def images(self, host_buffer):
         """one `bytes` per file from the packed images (a device tensor or a numpy array); synchronises"""
         host = host_buffer.cpu().numpy() if hasattr(host_buffer, "cpu") else np.asarray(host_buffer, dtype=np.uint8)
         return [host[int(at):int(at) + int(size)].tobytes() for at, size in zip(self.image_offsets, self.image_sizes)]
 
 
+def device_keys(keys):
+    """a list of CriAdxKey as the keyed calls of AdxFileSet take it: an int32 tensor (seed, mult, inc per key) on the device"""
+    import torch
+    host = np.array([[k.Seed, k.Mult, k.Inc] for k in keys], dtype=np.int32).reshape(-1)
+    return torch.from_numpy(host).cuda()
+
+
 def write_files(pcm16_list, configuration=None):
     """AdxWriter(configuration).GetFile(file) for a list of Pcm16Format files, on the device and without a launch per file: the
     files are grouped by the codec parameter set they need (sample rate, loop padding), one criadx.RaggedAdx per group encodes
-    into one buffer, one AdxFileSet over all of them writes the images.  Returns one `bytes` per file, in the caller's order.
+    into one buffer, one AdxFileSet over all of them writes the images -- encrypted inside that call when the configuration
+    carries an EncryptionKey (AdxWriter.cs:123-131).  Returns one `bytes` per file, in the caller's order.
     A file the encoder refuses (no samples with version 4 and no padding) raises, naming the file."""
     import torch
     from .criadx import RaggedAdx, _get_next_multiple
     cfg = configuration or AdxConfiguration()
-    if cfg.EncryptionKey is not None:
-        raise _lib.ArgumentError("write_files: keyed encryption is not part of file sets; AdxWriter encrypts file by file")
     files = list(pcm16_list)
     spf = (cfg.FrameSize - 2) * 2
     groups, align = {}, []
@@ -313,7 +393,11 @@ def write_files(pcm16_list, configuration=None):
         for r, p0, a0, c0 in ragged:
             if r.channels:
                 r.encode_device(pcm[p0:], adx[a0:], ws, history=history[c0:])
-        s.write_device(adx, images, history=history)
+        if cfg.EncryptionKey is not None:
+            d_keys = device_keys([cfg.EncryptionKey])                  # (alive until the images have been copied back)
+            s.write_keyed_device(adx, images, d_keys, history=history)
+        else:
+            s.write_device(adx, images, history=history)
         out = s.images(images)
         result = [None] * len(files)
         for k, i in enumerate(order):
@@ -326,10 +410,14 @@ def write_files(pcm16_list, configuration=None):
             s.close()
 
 
-def read_files(list_of_bytes):
-    """AdxReader().ReadFormat(file) for a list of files: the headers are parsed on the host, all audio is taken out of the
-    images in one vga_adx_read_device_v call.  Returns one CriAdxFormat per file; an encrypted file's audio stays encrypted, as
-    AdxReader leaves it when it has no key."""
+def read_files(list_of_bytes, EncryptionKey=None, Keys=None, Keys8=None, Keys9=None):
+    """AdxReader(EncryptionKey, Keys).ReadFormat(file) for a list of files: the headers are parsed on the host, all audio is
+    taken out of the images in one call on the device.  EncryptionKey: a CriAdxKey applied to every file, whatever its revision
+    (AdxReader.cs:31,40-43).  Otherwise the key of every encrypted file is searched on the device among the candidates
+    (CriAdxEncryption.FindKey) and the rows are decrypted in the same read, nothing returning to the host in between: Keys is
+    tried on every encrypted file, as AdxReader(Keys=...) here tries it; or Keys8 on files of revision 8 and Keys9 on every
+    other non-zero revision, the reference's two lists (CriAdxEncryption.cs:46).  Returns one CriAdxFormat per file; a file no
+    candidate fits stays encrypted, as AdxReader leaves it.  With no key argument nothing is searched."""
     import torch
     datas = [bytes(d) for d in list_of_bytes]
     infos = [parse(d) for d in datas]
@@ -342,7 +430,17 @@ def read_files(list_of_bytes):
             host[int(at):int(at) + size] = np.frombuffer(d, dtype=np.uint8)[:size]
         images = torch.from_numpy(host).cuda()
         audio = torch.zeros(s.totals.audio_bytes, dtype=torch.uint8, device="cuda")
-        s.read_device(images, audio)
+        keys8, keys9 = list(Keys8 if Keys8 is not None else Keys or []), list(Keys9 if Keys9 is not None else Keys or [])
+        if EncryptionKey is not None:
+            d_keys = device_keys([EncryptionKey])                      # (alive until the rows have been copied back)
+            s.read_keyed_device(images, audio, d_keys)
+        elif keys8 or keys9:
+            d8, d9 = (device_keys(k) if k else None for k in (keys8, keys9))
+            index = s.find_keys_device(images, d8, d9)
+            d_keys = device_keys(keys8 + keys9)
+            s.read_keyed_device(images, audio, d_keys, key_index=index)
+        else:
+            s.read_device(images, audio)
         rows = audio.cpu().numpy()
         out = []
         for f, info in enumerate(infos):

@@ -20,6 +20,9 @@ namespace adxf {
 constexpr int64_t GUARD_BYTES = 256;             // behind the last row and behind the last image
 constexpr int CHUNK_GRANULES = 2048;             // of one general work item: 256 threads, eight granules each
 constexpr int64_t MAX_TOTAL = (int64_t)1 << 62;
+// keyed calls (include/vgaudio_hip_files/adx_keyed_files.h): a slot is frame * channels + channel, the cipher's own order
+constexpr int CIPHER_CHUNK_SLOTS = 2048;         // of one item of the general form's cipher pass: 256 threads, eight slots each
+constexpr int FIND_SPAN_SLOTS = 1024;            // of one item of the key search: 256 lanes = 64 candidates x 4 quarters
 
 // What the kernels need of one file (a device table, one per file).  A set for reading fills h.nch and h.frame_size only.
 struct FileTab {
@@ -47,6 +50,10 @@ struct FilesLayout {
     std::vector<Item> items[2];
     int span_items = 0;                          // of items[0]
     int span_files = 0, general_files = 0, moving_files = 0;   // of items[0]; files that move audio at all
+    // keyed calls: (file, chunk of CIPHER_CHUNK_SLOTS slots) of the files items[k] serves in the general form;
+    // (file, span of FIND_SPAN_SLOTS slots) of every file of a set for reading
+    std::vector<Item> cipher_items[2], find_items;
+    bool tiny_frame = false;                     // a file of 1-byte frames (a set for reading): no scale to cipher
 };
 
 // "file <f>: " in front of the message the per-file code left
@@ -83,6 +90,10 @@ inline void cut_items(FilesLayout &L, int f, bool span_ok)
         for (int i = 0; i < count; i++)
             for (int64_t at = 0, y = 0; at < per; at += unit, y++) L.items[k].push_back({first + i, (uint32_t)y});
     }
+    const int64_t slots = (int64_t)t.copy_frames * nch;
+    for (int k = 0; k < 2; k++)
+        for (int64_t at = 0, y = 0; at < slots && !(k == 0 && span_ok); at += CIPHER_CHUNK_SLOTS, y++) L.cipher_items[k].push_back({f, (uint32_t)y});
+    for (int64_t at = 0, y = 0; at < slots && L.from_infos; at += FIND_SPAN_SLOTS, y++) L.find_items.push_back({f, (uint32_t)y});
     if (span_ok) {
         t.span_frames = adxspan::span_frames(nch);
         L.span_files++;
@@ -102,7 +113,7 @@ inline void finish_items(FilesLayout &L)
 
 inline int check_item_counts(const FilesLayout &L)
 {
-    if (L.items[0].size() > 0x7FFFFFFF || L.items[1].size() > 0x7FFFFFFF) { set_error("the set has more than 2^31 work items"); return VGA_ERR_OUT_OF_RANGE; }
+    if (L.items[0].size() > 0x7FFFFFFF || L.items[1].size() > 0x7FFFFFFF || L.cipher_items[1].size() > 0x7FFFFFFF || L.find_items.size() > 0x7FFFFFFF) { set_error("the set has more than 2^31 work items"); return VGA_ERR_OUT_OF_RANGE; }
     return VGA_OK;
 }
 
@@ -239,6 +250,8 @@ inline int make_layout_from_infos(const vga_adx_file_info *const *infos, int nfi
         std::memset(&t, 0, sizeof t);
         t.h.nch = nch;
         t.h.frame_size = fs;
+        t.h.encryption_type = I->revision;                      // the file's own type (the keyed calls)
+        L.tiny_frame = L.tiny_frame || fs < 2;
         t.image_off = at;
         t.first_channel = (int)channels;
         t.audio_offset = I->audio_offset;

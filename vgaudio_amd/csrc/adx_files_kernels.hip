@@ -163,45 +163,73 @@ __global__ __launch_bounds__(256) void adx_files_history_kernel(const int16_t *_
 }
 
 // ---------------------------------------------------------------- launchers
+// The launches of a call one by one: the keyed calls (adx_keyed_files_kernels.hip) put their own between them.
+int launch_write_headers(const DeviceTables &t, const int16_t *d_history, uint8_t *d_images, hipStream_t stream)
+{
+    hipLaunchKernelGGL(adx_files_header_kernel, dim3(t.files), dim3(256), 0, stream, t.tab, d_history, d_images);
+    VGA_HIP_TRY(hipGetLastError());
+    return VGA_OK;
+}
+
+int launch_write_general(const DeviceTables &t, bool general, const uint8_t *d_audio, uint8_t *d_images, hipStream_t stream)
+{
+    const int k = general ? 1 : 0, span = general ? 0 : t.span_items, rest = t.item_count[k] - span;
+    if (rest <= 0) return VGA_OK;
+    hipLaunchKernelGGL(adx_files_interleave_kernel, dim3(rest), dim3(256), 0, stream, t.tab, t.row_off, t.items[k] + span, d_audio, d_images);
+    VGA_HIP_TRY(hipGetLastError());
+    return VGA_OK;
+}
+
+int launch_write_footers(const DeviceTables &t, uint8_t *d_images, hipStream_t stream)
+{
+    hipLaunchKernelGGL(adx_files_footer_kernel, dim3(t.files), dim3(256), 0, stream, t.tab, d_images);
+    VGA_HIP_TRY(hipGetLastError());
+    return VGA_OK;
+}
+
+int launch_read_history(const DeviceTables &t, int16_t *d_history_out, hipStream_t stream)
+{
+    if (!d_history_out) return VGA_OK;
+    hipLaunchKernelGGL(adx_files_history_kernel, dim3((t.channels + 255) / 256), dim3(256), 0, stream, t.history, t.channels, d_history_out);
+    VGA_HIP_TRY(hipGetLastError());
+    return VGA_OK;
+}
+
+int launch_read_general(const DeviceTables &t, bool general, const uint8_t *d_images, uint8_t *d_audio, hipStream_t stream)
+{
+    const int k = general ? 1 : 0, span = general ? 0 : t.span_items, rest = t.item_count[k] - span;
+    if (rest <= 0) return VGA_OK;
+    hipLaunchKernelGGL(adx_files_deinterleave_kernel, dim3(rest), dim3(256), 0, stream, t.tab, t.row_off, t.row_file, t.items[k] + span,
+                       d_images, d_audio);
+    VGA_HIP_TRY(hipGetLastError());
+    return VGA_OK;
+}
+
 int launch_write_images(const DeviceTables &t, bool general, const uint8_t *d_audio, const int16_t *d_history, uint8_t *d_images,
                         hipStream_t stream)
 {
     if (t.files <= 0) return VGA_OK;
-    const int k = general ? 1 : 0, span = general ? 0 : t.span_items, rest = t.item_count[k] - span;
-    hipLaunchKernelGGL(adx_files_header_kernel, dim3(t.files), dim3(256), 0, stream, t.tab, d_history, d_images);
-    VGA_HIP_TRY(hipGetLastError());
+    const int k = general ? 1 : 0, span = general ? 0 : t.span_items;
+    if (int rc = launch_write_headers(t, d_history, d_images, stream)) return rc;
     if (span > 0) {
         hipLaunchKernelGGL(adx_files_interleave_span_kernel, dim3(span), dim3(256), 0, stream, t.tab, t.row_off, t.items[k], d_audio, d_images);
         VGA_HIP_TRY(hipGetLastError());
     }
-    if (rest > 0) {
-        hipLaunchKernelGGL(adx_files_interleave_kernel, dim3(rest), dim3(256), 0, stream, t.tab, t.row_off, t.items[k] + span, d_audio, d_images);
-        VGA_HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(adx_files_footer_kernel, dim3(t.files), dim3(256), 0, stream, t.tab, d_images);
-    VGA_HIP_TRY(hipGetLastError());
-    return VGA_OK;
+    if (int rc = launch_write_general(t, general, d_audio, d_images, stream)) return rc;
+    return launch_write_footers(t, d_images, stream);
 }
 
 int launch_read_images(const DeviceTables &t, bool general, const uint8_t *d_images, uint8_t *d_audio, int16_t *d_history_out,
                        hipStream_t stream)
 {
     if (t.channels <= 0) return VGA_OK;
-    const int k = general ? 1 : 0, span = general ? 0 : t.span_items, rest = t.item_count[k] - span;
-    if (d_history_out) {
-        hipLaunchKernelGGL(adx_files_history_kernel, dim3((t.channels + 255) / 256), dim3(256), 0, stream, t.history, t.channels, d_history_out);
-        VGA_HIP_TRY(hipGetLastError());
-    }
+    const int k = general ? 1 : 0, span = general ? 0 : t.span_items;
+    if (int rc = launch_read_history(t, d_history_out, stream)) return rc;
     if (span > 0) {
         hipLaunchKernelGGL(adx_files_deinterleave_span_kernel, dim3(span), dim3(256), 0, stream, t.tab, t.row_off, t.items[k], d_images, d_audio);
         VGA_HIP_TRY(hipGetLastError());
     }
-    if (rest > 0) {
-        hipLaunchKernelGGL(adx_files_deinterleave_kernel, dim3(rest), dim3(256), 0, stream, t.tab, t.row_off, t.row_file, t.items[k] + span,
-                           d_images, d_audio);
-        VGA_HIP_TRY(hipGetLastError());
-    }
-    return VGA_OK;
+    return launch_read_general(t, general, d_images, d_audio, stream);
 }
 
 }  // namespace adxf

@@ -23,11 +23,16 @@ constexpr int span_frames(int nch) { return kSpanBytes / (kFrame * nch) / 8 * 8;
 
 #ifdef __HIPCC__
 
+// What a span body does to the frames it holds in LDS, between its load and its store phase.  NoCipher: nothing, and no
+// code.  A cipher with active == true is called by every thread as cipher(nch, k0, nk, frame_at) -- frame_at(fr, c): the 18
+// bytes of frame k0 + fr of channel c in LDS -- and a second barrier follows it (adx_keyed_files_kernels.hip).
+struct NoCipher { static constexpr bool active = false; };
+
 // image -> rows.  base: the image's audio (any alignment), frame_count frames per channel: nothing outside is read.
 // Frames k0 .. k0 + span - 1 (or to the end) go to row_of(c) + k0 * 18; rows are 16-byte aligned.
-template <class RowOf>
+template <class RowOf, class Cipher = NoCipher>
 __device__ __forceinline__ void deinterleave_span(uint8_t *__restrict__ lds, const uint8_t *__restrict__ base, int nch, int frame_count,
-                                                  int k0, int span, RowOf row_of)
+                                                  int k0, int span, RowOf row_of, Cipher cipher = Cipher())
 {
     const int64_t audio = (int64_t)frame_count * kFrame * nch;
     const int nk = min(span, frame_count - k0);
@@ -49,6 +54,10 @@ __device__ __forceinline__ void deinterleave_span(uint8_t *__restrict__ lds, con
         *reinterpret_cast<uint4 *>(lds + 16 * g) = v;
     }
     __syncthreads();
+    if constexpr (Cipher::active) {
+        cipher(nch, k0, nk, [&](int fr, int c) { return lds + mis + (fr * nch + c) * kFrame; });
+        __syncthreads();
+    }
     const int row_bytes = nk * kFrame;
     const int per_row = (row_bytes + 15) >> 4;
     for (int q = threadIdx.x; q < per_row * nch; q += kThreads) {
@@ -77,9 +86,9 @@ __device__ __forceinline__ void deinterleave_span(uint8_t *__restrict__ lds, con
 // lies at c * pitch.  The output's 16-byte granules are those of the image's own address grid: the bytes in front of the first
 // whole one and behind the last go out singly; a granule takes its bytes from at most two (frame, channel) runs, since a
 // run is 18 bytes.
-template <class RowOf>
+template <class RowOf, class Cipher = NoCipher>
 __device__ __forceinline__ void interleave_span(uint8_t *__restrict__ lds, RowOf row_of, int nch, int frame_count, int k0, int span,
-                                                uint8_t *__restrict__ out)
+                                                uint8_t *__restrict__ out, Cipher cipher = Cipher())
 {
     const int nk = min(span, frame_count - k0);
     const int row_bytes = nk * kFrame;
@@ -89,6 +98,10 @@ __device__ __forceinline__ void interleave_span(uint8_t *__restrict__ lds, RowOf
         *reinterpret_cast<uint4 *>(lds + c * pitch + 16 * g) = *reinterpret_cast<const uint4 *>(row_of(c) + (int64_t)k0 * kFrame + 16 * g);
     }
     __syncthreads();
+    if constexpr (Cipher::active) {
+        cipher(nch, k0, nk, [&](int fr, int c) { return lds + c * pitch + fr * kFrame; });
+        __syncthreads();
+    }
     const int group = kFrame * nch, total = nk * group;               // bytes of one frame of all channels; of the span
     uint8_t *d = out + (int64_t)k0 * group;
     const int lead = min((int)((16 - ((uintptr_t)d & 15)) & 15), total);

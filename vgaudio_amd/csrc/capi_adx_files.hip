@@ -2,27 +2,18 @@
 // (include/vgaudio_hip/adx_files.h).  Host side only: checks, layout and work items come from adx_files_host.hpp; create
 // uploads the tables the kernels read (adx_files_kernels.hpp), a call checks its pointers and launches.
 #include "common.hpp"
-#include "adx_files_kernels.hpp"
+#include "adx_files_object.hpp"
 
 #include <cstring>
 #include <vector>
 
 using namespace vga;
 
-struct vga_adx_files {
-    adxf::FilesLayout L;
-    void *d_tables = nullptr;
-    adxf::DeviceTables tables;
-    int device = 0;
-    ~vga_adx_files()
-    {
-        if (d_tables) (void)hipFree(d_tables);
-    }
-};
+thread_local int vga::adxf::g_force_general = 0;  // vga_adx_files_force_general_this_thread
 
 namespace {
 
-thread_local int g_force_general = 0;            // vga_adx_files_force_general_this_thread
+using adxf::g_force_general;
 
 template <class T> size_t place(size_t &at, const std::vector<T> &v)
 {
@@ -45,6 +36,8 @@ int finish_create(vga_adx_files *s)
     size_t bytes = 0;
     const size_t tab_at = place(bytes, L.tab), rows_at = place(bytes, L.row_off), file_at = place(bytes, L.row_file);
     const size_t hist_at = place(bytes, L.history), own_at = place(bytes, L.items[0]), general_at = place(bytes, L.items[1]);
+    const size_t cipher_own_at = place(bytes, L.cipher_items[0]), cipher_general_at = place(bytes, L.cipher_items[1]);
+    const size_t find_at = place(bytes, L.find_items);
     std::vector<unsigned char> host(bytes + 16, 0);
     fill(host, tab_at, L.tab);
     fill(host, rows_at, L.row_off);
@@ -52,6 +45,9 @@ int finish_create(vga_adx_files *s)
     fill(host, hist_at, L.history);
     fill(host, own_at, L.items[0]);
     fill(host, general_at, L.items[1]);
+    fill(host, cipher_own_at, L.cipher_items[0]);
+    fill(host, cipher_general_at, L.cipher_items[1]);
+    fill(host, find_at, L.find_items);
     VGA_HIP_TRY(device_malloc(&s->d_tables, host.size()));
     VGA_HIP_TRY(hipMemcpy(s->d_tables, host.data(), host.size(), hipMemcpyHostToDevice));
     const unsigned char *d = static_cast<const unsigned char *>(s->d_tables);
@@ -67,10 +63,18 @@ int finish_create(vga_adx_files *s)
     t.span_items = L.span_items;
     t.item_count[0] = (int)L.items[0].size();
     t.item_count[1] = (int)L.items[1].size();
+    t.cipher_items[0] = reinterpret_cast<const adxf::Item *>(d + cipher_own_at);
+    t.cipher_items[1] = reinterpret_cast<const adxf::Item *>(d + cipher_general_at);
+    t.find_items = reinterpret_cast<const adxf::Item *>(d + find_at);
+    t.cipher_count[0] = (int)L.cipher_items[0].size();
+    t.cipher_count[1] = (int)L.cipher_items[1].size();
+    t.find_count = (int)L.find_items.size();
     return VGA_OK;
 }
 
-int check_object(const vga_adx_files *s, const char *what)
+}  // namespace
+
+int vga::adxf::check_object(const vga_adx_files *s, const char *what)
 {
     if (!s) { set_error("%s: null vga_adx_files", what); return VGA_ERR_ARGUMENT; }
     int device = -1;
@@ -81,6 +85,10 @@ int check_object(const vga_adx_files *s, const char *what)
     }
     return VGA_OK;
 }
+
+namespace {
+
+using adxf::check_object;
 
 void copy_offsets(const adxf::FilesLayout &L, int *first_channel_out, int64_t *audio_offsets_out, int64_t *image_offsets_out)
 {

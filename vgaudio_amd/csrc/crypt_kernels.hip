@@ -4,6 +4,7 @@
 // HBM-bound: ADX touches 2 of every frame_size bytes (but reads the frame for the emptiness test), HCA reads and
 // writes every byte once.
 #include "crypt_kernels.hpp"
+#include "adx_lcg.hpp"
 #include "hca_device.hpp"
 #include "hca_frame_crc.hpp"
 
@@ -12,21 +13,9 @@
 namespace vga {
 namespace crypt {
 
-// The reference steps xor = (xor * mult + inc) & 0x7fff once per (frame, channel) slot, serially.  The k-th state is
-// an affine map of the seed modulo 2^15, obtained here by square-and-multiply so every slot is independent.
-struct Affine { unsigned a, c; };      // x -> a * x + c  (mod 2^15)
-__device__ __forceinline__ Affine lcg_power(unsigned mult, unsigned inc, uint64_t k)
-{
-    Affine r{1u, 0u};
-    unsigned a = mult & 0x7fffu, c = inc & 0x7fffu;
-    while (k) {
-        if (k & 1) { r.a = (r.a * a) & 0x7fffu; r.c = (r.c * a + c) & 0x7fffu; }
-        c = (c * (a + 1)) & 0x7fffu;
-        a = (a * a) & 0x7fffu;
-        k >>= 1;
-    }
-    return r;
-}
+// The LCG's k-th state as an affine map of the seed (adx_lcg.hpp): every slot is independent.
+using adxlcg::Affine;
+using adxlcg::lcg_power;
 
 // EncryptDecryptChannel (:16-41): one thread per (frame, channel)
 __global__ __launch_bounds__(256) void adx_crypt_kernel(uint8_t *__restrict__ audio, int64_t pitch, int frame_count, int nch,
