@@ -71,8 +71,9 @@
  * call.  The object keeps its tables in the memory of the device that was current at create, is immutable and serves any
  * number of calls, concurrent calls on different streams included.
  *
- * LEFT OUT: FindKey inside a set (it returns a host value and synchronises: a type-56 file without a key is the caller's
- * to resolve first, vga_hca_find_key_device); host-pointer forms of the _v calls; moving the per-file vga_hca_write_device,
+ * FindKey inside a set, and a read whose keys are indices in device memory, are vgaudio_hip_files/hca_keyed_files.h's
+ * (vga_hca_find_keys_device_v, vga_hca_read_keyed_device_v, on the objects of vga_hca_files_create_from_infos).
+ * LEFT OUT: host-pointer forms of the _v calls; moving the per-file vga_hca_write_device,
  * vga_hca_read_device and vga_hca_crypt_device onto the new body (that changes existing calls' launches and belongs to a
  * change of its own). */
 #ifndef VGAUDIO_HIP_HCA_FILES_H

@@ -56,8 +56,8 @@
  * and launches nothing.  All three run on the caller's stream and never synchronise it; they allocate nothing and copy
  * nothing from host memory.
  *
- * LEFT OUT: HCA FindKey inside a set (hca_files.h: it synchronises); the `crackadx` brute force (vga_adx_guess_keys) over a
- * set; host-pointer forms of these calls. */
+ * HCA FindKey inside a set is hca_keyed_files.h's, next to this header.
+ * LEFT OUT: the `crackadx` brute force (vga_adx_guess_keys) over a set; host-pointer forms of these calls. */
 #ifndef VGAUDIO_HIP_FILES_ADX_KEYED_FILES_H
 #define VGAUDIO_HIP_FILES_ADX_KEYED_FILES_H
 

@@ -427,6 +427,11 @@ SIGNATURES = {
     "vga_adx_find_keys_workspace_bytes": (C.c_size_t, [vp, ci, ci]),
     "vga_adx_find_keys_device_v": (ci, [vp, vp, vp, ci, ci, vp, vp, C.c_size_t, vp]),
     "vga_adx_find_keys_items_for": (ci, [vp, ci, C.POINTER(i64), vp, i64, C.POINTER(i64)]),
+    # include/vgaudio_hip_files/hca_keyed_files.h
+    "vga_hca_find_keys_workspace_bytes": (C.c_size_t, [vp, ci]),
+    "vga_hca_find_keys_device_v": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, C.c_size_t, vp]),
+    "vga_hca_read_keyed_device_v": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp]),
+    "vga_hca_find_keys_items_for": (ci, [vp, ci, ci, vp, i64, C.POINTER(i64)]),
 }
 
 
@@ -462,6 +467,11 @@ class AdxFilesItemC(C.Structure):
 class AdxFindKeysItemC(C.Structure):
     """vga_adx_find_keys_item (include/vgaudio_hip_files/adx_keyed_files.h)"""
     _fields_ = [("file", C.c_int), ("first_slot", C.c_int), ("slot_count", C.c_int)]
+
+
+class HcaFindKeysItemC(C.Structure):
+    """vga_hca_find_keys_item (include/vgaudio_hip_files/hca_keyed_files.h)"""
+    _fields_ = [("file", C.c_int), ("first_key", C.c_int), ("key_count", C.c_int)]
 
 
 class WaveInfoC(C.Structure):

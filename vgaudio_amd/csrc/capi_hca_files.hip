@@ -4,27 +4,31 @@
 // pointers and launches.
 #include "common.hpp"
 #include "hca_capi.hpp"
-#include "hca_files_kernels.hpp"
+#include "hca_files_object.hpp"
 
 #include <cstring>
 #include <vector>
 
 using namespace vga;
 
-struct vga_hca_files {
-    hcaf::FilesLayout L;
-    void *d_tables = nullptr;
-    hcaf::DeviceTables tables;
-    int device = 0;
-    ~vga_hca_files()
-    {
-        if (d_tables) (void)hipFree(d_tables);
+thread_local int vga::hcaf::g_force_general = 0; // vga_hca_files_force_general_this_thread
+
+int vga::hcaf::check_object(const vga_hca_files *s, const char *what)
+{
+    if (!s) { set_error("%s: null vga_hca_files", what); return VGA_ERR_ARGUMENT; }
+    int device = -1;
+    if (s->L.totals.files > 0) (void)hipGetDevice(&device);
+    if (s->L.totals.files > 0 && device != s->device) {
+        set_error("%s: the set was created on device %d, the current one is %d", what, s->device, device);
+        return VGA_ERR_ARGUMENT;
     }
-};
+    return VGA_OK;
+}
 
 namespace {
 
-thread_local int g_force_general = 0;            // vga_hca_files_force_general_this_thread
+using hcaf::check_object;
+using hcaf::g_force_general;
 
 template <class T> size_t place(size_t &at, const std::vector<T> &v)
 {
@@ -41,18 +45,22 @@ template <class T> void fill(std::vector<unsigned char> &host, size_t at, const 
 int finish_create(vga_hca_files *s)
 {
     hcaf::FilesLayout &L = s->L;
+    hcak::make_find_tables(L, s->find);
     if (L.totals.files == 0) return VGA_OK;                   // an empty set needs no device
     if (int rc = require_device()) return rc;
     (void)hipGetDevice(&s->device);
     size_t bytes = 0;
     const size_t headers_at = place(bytes, L.headers), tab_at = place(bytes, L.tab), keys_at = place(bytes, L.tables);
     const size_t own_at = place(bytes, L.items[0]), general_at = place(bytes, L.items[1]);
+    const size_t walk_at = place(bytes, s->find.walk), find_at = place(bytes, s->find.find_files);
     std::vector<unsigned char> host(bytes + 16, 0);
     fill(host, headers_at, L.headers);
     fill(host, tab_at, L.tab);
     fill(host, keys_at, L.tables);
     fill(host, own_at, L.items[0]);
     fill(host, general_at, L.items[1]);
+    fill(host, walk_at, s->find.walk);
+    fill(host, find_at, s->find.find_files);
     hcaf::DeviceTables &t = s->tables;
     if (int rc = hca::crc_pow_table(&t.crc_pow)) return rc;
     VGA_HIP_TRY(device_malloc(&s->d_tables, host.size()));
@@ -67,18 +75,10 @@ int finish_create(vga_hca_files *s)
     t.span_items = L.span_items;
     t.item_count[0] = (int)L.items[0].size();
     t.item_count[1] = (int)L.items[1].size();
-    return VGA_OK;
-}
-
-int check_object(const vga_hca_files *s, const char *what)
-{
-    if (!s) { set_error("%s: null vga_hca_files", what); return VGA_ERR_ARGUMENT; }
-    int device = -1;
-    if (s->L.totals.files > 0) (void)hipGetDevice(&device);
-    if (s->L.totals.files > 0 && device != s->device) {
-        set_error("%s: the set was created on device %d, the current one is %d", what, s->device, device);
-        return VGA_ERR_ARGUMENT;
-    }
+    t.walk = reinterpret_cast<const hcak::WalkFile *>(d + walk_at);
+    t.find_files = reinterpret_cast<const int *>(d + find_at);
+    t.find_file_count = (int)s->find.find_files.size();
+    t.find_max_channels = s->find.max_channels;
     return VGA_OK;
 }
 

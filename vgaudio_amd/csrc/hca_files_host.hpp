@@ -44,6 +44,8 @@ struct FilesLayout {
     bool from_infos = false;
     std::vector<int64_t> frame_off, image_off, stream_bytes;   // per file
     std::vector<int> image_size;                 // per file
+    std::vector<vga_hca_info> hca;               // (from parsed headers) per file, for the key search (hca_keyed_files_host.hpp)
+    std::vector<int> encryption_type;            // (from parsed headers) per file
     std::vector<uint8_t> headers;                // (write) every header, each at a multiple of 16
     std::vector<uint8_t> tables;                 // ntables x 256
     std::vector<FileTab> tab;
@@ -209,6 +211,8 @@ inline int make_layout_from_infos(const vga_hca_file_info *const *infos, int nfi
     L = FilesLayout();
     L.from_infos = true;
     L.totals.files = nfiles;
+    L.hca.resize(nfiles);
+    L.encryption_type.resize(nfiles);
     L.image_off.resize(nfiles);
     L.image_size.resize(nfiles);
     L.stream_bytes.resize(nfiles);
@@ -233,6 +237,8 @@ inline int make_layout_from_infos(const vga_hca_file_info *const *infos, int nfi
         L.totals.total_frames += H.frame_count;
         L.image_off[f] = at;
         L.image_size[f] = (int)size;
+        L.hca[f] = H;
+        L.encryption_type[f] = I->encryption_type;
         image_at = pad_to(at + size, 16);
         image_end = std::max(image_end, image_at);
         FileTab &t = L.tab[f];
@@ -280,9 +286,8 @@ inline int check_write(const FilesLayout &L, const void *d_frames, const void *d
     if (!aligned_to(d_frames, 4) || !aligned_to(d_images, 16)) { set_error("%s: d_frames needs 4-byte and d_images 16-byte alignment", what); return VGA_ERR_ARGUMENT; }
     return VGA_OK;
 }
-inline int check_read(const FilesLayout &L, const void *d_images, const void *d_frames)
+inline int check_read(const FilesLayout &L, const void *d_images, const void *d_frames, const char *what = "vga_hca_read_device_v")
 {
-    const char *what = "vga_hca_read_device_v";
     if (!L.from_infos) { set_error("%s: the set was not made from parsed headers (vga_hca_files_create_from_infos)", what); return VGA_ERR_INVALID_OP; }
     if ((!d_images || !d_frames) && L.moving_files > 0) { set_error("%s: null pointer", what); return VGA_ERR_ARGUMENT; }
     if (!aligned_to(d_frames, 4) || !aligned_to(d_images, 16)) { set_error("%s: d_frames needs 4-byte and d_images 16-byte alignment", what); return VGA_ERR_ARGUMENT; }

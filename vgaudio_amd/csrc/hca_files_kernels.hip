@@ -27,6 +27,14 @@ __device__ __forceinline__ unsigned table_step(const uint16_t *crc_tab, unsigned
     return ((crc << 8) ^ crc_tab[(crc >> 8) ^ byte]) & 0xFFFFu;
 }
 
+// the table of an item's file: the object's own, or the caller's through the per-file index (KeySource), -1 = none
+__device__ __forceinline__ int item_key(const KeySource &keys, int own, int file)
+{
+    if (!keys.external) return own;
+    const int k = keys.index ? keys.index[file] : 0;
+    return k >= 0 && k < keys.ntables ? k : -1;
+}
+
 __global__ __launch_bounds__(256) void hca_files_header_kernel(const FileTab *__restrict__ tab, const uint8_t *__restrict__ headers,
                                                                uint8_t *__restrict__ images)
 {
@@ -85,7 +93,7 @@ __device__ __forceinline__ void crypt_frames_lds(uint8_t *a0, int n, int fs, boo
 
 template <bool READ>
 __global__ __launch_bounds__(256) void hca_files_span_kernel(const FileTab *__restrict__ tab, const Item *__restrict__ items,
-                                                             const uint8_t *__restrict__ tables, const uint16_t *__restrict__ crc_pow,
+                                                             KeySource keys, const uint16_t *__restrict__ crc_pow,
                                                              const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
                                                              int *__restrict__ bad_crc)
 {
@@ -100,7 +108,8 @@ __global__ __launch_bounds__(256) void hca_files_span_kernel(const FileTab *__re
     const int bytes = n * fs;                                          // at most SPAN_BYTES: the form's condition
     const uint8_t *s = src + t.src_off + (int64_t)it.first_frame * fs;
     uint8_t *d = dst + t.dst_off + (int64_t)it.first_frame * fs;
-    const bool keyed = t.key >= 0, check = READ && bad_crc != nullptr;
+    const int key = item_key(keys, t.key, it.file);
+    const bool keyed = key >= 0, check = READ && bad_crc != nullptr;
 
     // in: the 16-byte granules that hold the span; byte i of the span is lds[lead + i]
     const int lead = (int)((uintptr_t)s & 15);
@@ -108,7 +117,7 @@ __global__ __launch_bounds__(256) void hca_files_span_kernel(const FileTab *__re
     const int granules = (lead + bytes + 15) >> 4;
     for (int g = tid; g < granules; g += 256) reinterpret_cast<uint4 *>(lds)[g] = s16[g];
     if (keyed || check) {
-        if (keyed) sub[tid] = tables[t.key * 256 + tid];
+        if (keyed) sub[tid] = keys.tables[(size_t)key * 256 + tid];
         crc_tab[tid] = (uint16_t)hca_crc::step(0u, (unsigned)tid);
         if (tid == 0) bad = 0;
         __syncthreads();
@@ -145,7 +154,7 @@ __global__ __launch_bounds__(256) void hca_files_span_kernel(const FileTab *__re
 
 template <bool READ>
 __global__ __launch_bounds__(256) void hca_files_general_kernel(const FileTab *__restrict__ tab, const Item *__restrict__ items,
-                                                                const uint8_t *__restrict__ tables, const uint16_t *__restrict__ crc_pow,
+                                                                KeySource keys, const uint16_t *__restrict__ crc_pow,
                                                                 const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
                                                                 int *__restrict__ bad_crc)
 {
@@ -158,12 +167,13 @@ __global__ __launch_bounds__(256) void hca_files_general_kernel(const FileTab *_
     const int fs = t.frame_size, n = min(t.item_frames, t.frame_count - it.first_frame);
     const uint8_t *s = src + t.src_off + (int64_t)it.first_frame * fs;
     uint8_t *d = dst + t.dst_off + (int64_t)it.first_frame * fs;
-    const bool keyed = t.key >= 0, check = READ && bad_crc != nullptr;
+    const int key = item_key(keys, t.key, it.file);
+    const bool keyed = key >= 0, check = READ && bad_crc != nullptr;
     const int64_t bytes = (int64_t)n * fs;
     if (!keyed && !check) {
         for (int64_t i = tid; i < bytes; i += 256) d[i] = s[i];
     } else {
-        if (keyed) sub[tid] = tables[t.key * 256 + tid];
+        if (keyed) sub[tid] = keys.tables[(size_t)key * 256 + tid];
         crc_tab[tid] = (uint16_t)hca_crc::step(0u, (unsigned)tid);
         const int nb = fs - 2, chunk = (nb + 255) / 256;
         const int begin = min(tid * chunk, nb), end = min(begin + chunk, nb);
@@ -209,15 +219,16 @@ __global__ __launch_bounds__(256) void hca_files_general_kernel(const FileTab *_
 
 // ---------------------------------------------------------------- launchers
 template <bool READ>
-static int launch_items(const DeviceTables &t, bool general, const uint8_t *src, uint8_t *dst, int *d_bad_crc, hipStream_t stream)
+static int launch_items(const DeviceTables &t, bool general, const uint8_t *src, uint8_t *dst, int *d_bad_crc, hipStream_t stream, KeySource keys)
 {
+    if (!keys.external) keys.tables = t.tables;
     const int k = general ? 1 : 0, span = general ? 0 : t.span_items, rest = t.item_count[k] - span;
     if (span > 0) {
-        hipLaunchKernelGGL(hca_files_span_kernel<READ>, dim3(span), dim3(256), 0, stream, t.tab, t.items[k], t.tables, t.crc_pow, src, dst, d_bad_crc);
+        hipLaunchKernelGGL(hca_files_span_kernel<READ>, dim3(span), dim3(256), 0, stream, t.tab, t.items[k], keys, t.crc_pow, src, dst, d_bad_crc);
         VGA_HIP_TRY(hipGetLastError());
     }
     if (rest > 0) {
-        hipLaunchKernelGGL(hca_files_general_kernel<READ>, dim3(rest), dim3(256), 0, stream, t.tab, t.items[k] + span, t.tables, t.crc_pow, src, dst,
+        hipLaunchKernelGGL(hca_files_general_kernel<READ>, dim3(rest), dim3(256), 0, stream, t.tab, t.items[k] + span, keys, t.crc_pow, src, dst,
                            d_bad_crc);
         VGA_HIP_TRY(hipGetLastError());
     }
@@ -229,13 +240,14 @@ int launch_write_images(const DeviceTables &t, bool general, const uint8_t *d_fr
     if (t.files <= 0) return VGA_OK;
     hipLaunchKernelGGL(hca_files_header_kernel, dim3(t.files), dim3(256), 0, stream, t.tab, t.headers, d_images);
     VGA_HIP_TRY(hipGetLastError());
-    return launch_items<false>(t, general, d_frames, d_images, nullptr, stream);
+    return launch_items<false>(t, general, d_frames, d_images, nullptr, stream, KeySource());
 }
 
-int launch_read_images(const DeviceTables &t, bool general, const uint8_t *d_images, uint8_t *d_frames, int *d_bad_crc, hipStream_t stream)
+int launch_read_images(const DeviceTables &t, bool general, const uint8_t *d_images, uint8_t *d_frames, int *d_bad_crc, hipStream_t stream,
+                       const KeySource &keys)
 {
     if (t.files <= 0) return VGA_OK;
-    return launch_items<true>(t, general, d_images, d_frames, d_bad_crc, stream);
+    return launch_items<true>(t, general, d_images, d_frames, d_bad_crc, stream, keys);
 }
 
 }  // namespace hcaf

@@ -273,10 +273,74 @@ class HcaFileSet:
                                                ptr(frames, torch.uint8, t.frame_bytes, "frames"),
                                                ptr(bad_crc, torch.int32, self.files, "bad_crc"), DspFileSet._stream(stream)))
 
+    # ---- keys on the device (include/vgaudio_hip_files/hca_keyed_files.h)
+    def find_keys_workspace_bytes(self, nkeys):
+        return int(_lib.lib().vga_hca_find_keys_workspace_bytes(self._h, int(nkeys)))
+
+    def find_keys_device(self, images, tables, nkeys, type1_index=-1, status=None, workspace=None, stream=None):
+        """vga_hca_find_keys_device_v (a set from from_infos, made without keys).  tables: a uint8 device tensor of decryption
+        tables, 256 bytes each (device_tables), whose first `nkeys` are the candidates for type-56 files; type1_index: what a
+        type-1 file gets.  Returns an int32[files] device tensor of table indices (-1: none), written on the stream and not
+        read here: it goes straight into read_keyed_device.  status: int32[files] or None; workspace: uint8[
+        find_keys_workspace_bytes(nkeys)] or None (allocated).  The object is not changed: what the call allocates (the index
+        tensor, the workspace when none is given) is recorded on `stream`, so torch's allocator does not hand it out again while
+        that stream still uses it; `tables` and a workspace of the caller's are the caller's to keep alive."""
+        import torch
+        from .dsp import DspFileSet
+        ptr, t = DspFileSet._ptr, self.totals
+        need = self.find_keys_workspace_bytes(nkeys)
+        own_workspace = None
+        if workspace is None:
+            workspace = own_workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=images.device)
+        index = torch.empty(max(self.files, 1), dtype=torch.int32, device=images.device)
+        check(_lib.lib().vga_hca_find_keys_device_v(self._h, ptr(images, torch.uint8, t.image_bytes, "images"),
+                                                    ptr(tables, torch.uint8, 256 * max(int(nkeys), 0), "tables"), int(nkeys), int(type1_index),
+                                                    index.data_ptr(), ptr(status, torch.int32, self.files, "status"),
+                                                    ptr(workspace, torch.uint8, need, "workspace"), workspace.numel(),
+                                                    DspFileSet._stream(stream)))
+        if stream is not None:                                         # what this call allocated is used on the caller's stream
+            for t_ in ([index] if own_workspace is None else [index, own_workspace]):
+                t_.record_stream(stream)
+        return index[:self.files]
+
+    def read_keyed_device(self, images, tables, frames, key_index=None, bad_crc=None, status=None, stream=None):
+        """vga_hca_read_keyed_device_v (a set from from_infos, made without keys): read_device with file f deciphered through
+        tables[key_index[f]] (uint8 device tensor, 256 bytes a table; key_index: int32[files] on the device, e.g. what
+        find_keys_device returned, or None for table 0); status: int32[files] or None"""
+        import torch
+        from .dsp import DspFileSet
+        ptr, t = DspFileSet._ptr, self.totals
+        ntables = 0 if tables is None else tables.numel() // 256
+        check(_lib.lib().vga_hca_read_keyed_device_v(self._h, ptr(images, torch.uint8, t.image_bytes, "images"),
+                                                     ptr(tables, torch.uint8, 0, "tables"), ntables,
+                                                     ptr(key_index, torch.int32, self.files, "key_index"),
+                                                     ptr(frames, torch.uint8, t.frame_bytes, "frames"),
+                                                     ptr(bad_crc, torch.int32, self.files, "bad_crc"),
+                                                     ptr(status, torch.int32, self.files, "status"), DspFileSet._stream(stream)))
+
+    @classmethod
+    def find_items(cls, infos, nkeys):
+        """the work items of find_keys_device's test launches on a set of such infos (_lib.HcaFindKeysItemC), host only"""
+        infos = list(infos)
+        ptrs = (C.c_void_p * max(len(infos), 1))(*[C.addressof(i) for i in infos])
+        call, count = _lib.lib().vga_hca_find_keys_items_for, C.c_int64()
+        check(call(ptrs, len(infos), int(nkeys), None, 0, C.byref(count)))
+        items = (_lib.HcaFindKeysItemC * max(count.value, 1))()
+        check(call(ptrs, len(infos), int(nkeys), items, count.value, C.byref(count)))
+        return list(items[:count.value])
+
     def images(self, host_buffer):
         """one `bytes` per file from the packed images (a device tensor or a numpy array); synchronises"""
         host = host_buffer.cpu().numpy() if hasattr(host_buffer, "cpu") else np.asarray(host_buffer, dtype=np.uint8)
         return [host[int(at):int(at) + int(size)].tobytes() for at, size in zip(self.image_offsets, self.image_sizes)]
+
+
+def device_tables(keys):
+    """a list of CriHcaKey as the keyed calls of HcaFileSet take it: their decryption tables, 256 bytes each, as one uint8
+    tensor on the device"""
+    import torch
+    host = np.ascontiguousarray(np.stack([k.DecryptionTable for k in keys]), dtype=np.uint8).reshape(-1)
+    return torch.from_numpy(host.copy()).cuda()
 
 
 def _shape_class(h):
@@ -378,14 +442,56 @@ def write_files(pcm16_list, configuration=None):
             s.close()
 
 
-def read_files(list_of_bytes, Decrypt=True, EncryptionKey=None):
-    """HcaReader(Decrypt, EncryptionKey).ReadWithConfig(file) for a list of files: the headers are parsed on the host, all
+def _read_files_found(datas, infos, Keys):
+    """read_files with candidates: keys found and frames deciphered on the device, one synchronisation (the copy back)"""
+    import torch
+    keys = list(Keys)
+    s = HcaFileSet.from_infos(infos)
+    try:
+        if s.files == 0:
+            return [], []
+        host = np.zeros(s.totals.image_bytes, dtype=np.uint8)
+        for d, at, size in zip(datas, s.image_offsets, s.image_sizes):
+            host[int(at):int(at) + size] = np.frombuffer(d, dtype=np.uint8)[:size]
+        images = torch.from_numpy(host).cuda()
+        tables = device_tables(keys + [CriHcaKey(CriHcaKey.Type1)])    # the type-1 table sits behind the candidates
+        frames = torch.zeros(s.totals.frame_bytes, dtype=torch.uint8, device="cuda")
+        bad = torch.zeros(s.files, dtype=torch.int32, device="cuda")
+        status = torch.empty(s.files, dtype=torch.int32, device="cuda")
+        index = s.find_keys_device(images, tables, len(keys), type1_index=len(keys), status=status)
+        s.read_keyed_device(images, tables, frames, key_index=index, bad_crc=bad)
+        flat = frames.cpu().numpy()                                     # the one synchronisation
+        found, state, counts = index.cpu().numpy(), status.cpu().numpy(), bad.cpu().numpy()
+        for f in range(s.files):
+            if state[f] == 1:
+                raise _lib.InvalidDataError("file %d: Cannot find key to decrypt HCA file." % f)
+            if state[f] == 2:
+                raise _lib.InvalidDataError("file %d: Invalid frame header" % f)
+        out = []
+        for f, info in enumerate(infos):
+            hca = hca_info_of(info)
+            at, n = int(s.frame_offsets[f]), hca.FrameCount * hca.FrameSize
+            if found[f] >= 0:
+                hca.EncryptionType = 0
+            out.append(CriHcaFormat(flat[at:at + n].copy().reshape(hca.FrameCount, hca.FrameSize), hca))
+        return out, [int(b) for b in counts]
+    finally:
+        s.close()
+
+
+def read_files(list_of_bytes, Decrypt=True, EncryptionKey=None, Keys=None):
+    """HcaReader(Decrypt, EncryptionKey, Keys).ReadWithConfig(file) for a list of files: the headers are parsed on the host, all
     frames are taken out of the images, CRC-checked and decrypted in one vga_hca_read_device_v call.  Returns
-    (formats, bad_crc): one CriHcaFormat per file, EncryptionType 0 where decrypted, and the bad-CRC frames per file.  A
-    type-56 file without a key is refused by name (FindKey synchronises and stays with the caller, HcaReader.Keys)."""
+    (formats, bad_crc): one CriHcaFormat per file, EncryptionType 0 where decrypted, and the bad-CRC frames per file.
+    Keys: the candidates for type-56 files when no EncryptionKey is given; the keys are then found and used on the device
+    (HcaFileSet.find_keys_device, read_keyed_device) and nothing but the final copy synchronises; a file no candidate fits
+    raises "file <f>: Cannot find key to decrypt HCA file." after that copy.  Without Keys a type-56 file without a key is
+    refused by name before anything runs."""
     import torch
     datas = [bytes(d) for d in list_of_bytes]
     infos = [parse(d) for d in datas]
+    if Decrypt and EncryptionKey is None and Keys is not None:
+        return _read_files_found(datas, infos, Keys)
     tables, keys, type1 = [], [], None
     for i, info in enumerate(infos):
         k = -1
