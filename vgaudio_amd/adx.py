@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._fileset import FileSetBase, fetch_items, i64_or_none as _i64_or_none
 from ._lib import check, u8p
 from .criadx import CriAdxChannel, CriAdxEncryption, CriAdxFormat, CriAdxParameters, CriAdxType
 from .gcadpcm import Pcm16Format, _i16, _ptr_array
@@ -121,19 +122,13 @@ def _adx_file(f):
     return _lib.AdxFileC(int(channels), params if isinstance(params, _lib.AdxFileParamsC) else _lib.AdxFileParamsC(*params))
 
 
-def _i64_or_none(values):
-    if values is None:
-        return None, None
-    a = np.ascontiguousarray(values, dtype=np.int64)
-    return a, a.ctypes.data_as(C.POINTER(C.c_int64))
-
-
-class AdxFileSet:
+class AdxFileSet(FileSetBase):
     """A set of ADX files of different shapes, resident on the device (include/vgaudio_hip/adx_files.h has the layout): the
     channels of all files are packed rows -- as criadx.RaggedAdx leaves its output, or at the caller's `audio_offsets` --, the
     images one packed buffer.  `files`: one _lib.AdxFileC or (channels, _lib.AdxFileParamsC) per file, the params what
     vga_adx_write_device takes.  The tensors are the caller's torch tensors on the current device; the calls run on torch's
     current stream and do not synchronise it."""
+    _destroy = "vga_adx_files_destroy"
 
     def __init__(self, files=None, audio_offsets=None, _handle=None):
         self._h, self.image_sizes = C.c_void_p(), None
@@ -192,34 +187,20 @@ class AdxFileSet:
         s.image_sizes = [i.audio_offset + i.audio_bytes * i.channel_count for i in infos]
         return s
 
-    @staticmethod
-    def _items(call, first, n, offsets, general):
-        keep, offs = _i64_or_none(offsets)
-        count = C.c_int64()
-        check(call(first, n, offs, int(general), None, 0, C.byref(count)))
-        items = (_lib.AdxFilesItemC * max(count.value, 1))()
-        check(call(first, n, offs, int(general), items, count.value, C.byref(count)))
-        return list(items[:count.value])
-
     @classmethod
     def write_items(cls, files, audio_offsets=None, general=False):
         """the work items of vga_adx_write_device_v on such a set (_lib.AdxFilesItemC), host only"""
         arr, n = cls._files_array(files)
-        return cls._items(_lib.lib().vga_adx_files_write_items_for, arr, n, audio_offsets, general)
+        keep, offs = _i64_or_none(audio_offsets)
+        return fetch_items(_lib.lib().vga_adx_files_write_items_for, (arr, n, offs, int(general)), _lib.AdxFilesItemC)
 
     @classmethod
     def read_items(cls, infos, image_offsets=None, general=False):
         """the work items of vga_adx_read_device_v on a set of such infos, host only"""
         infos = list(infos)
         ptrs = (C.c_void_p * max(len(infos), 1))(*[C.addressof(i) for i in infos])
-        return cls._items(_lib.lib().vga_adx_files_read_items_for, ptrs, len(infos), image_offsets, general)
-
-    def close(self):
-        if self._h:
-            _lib.lib().vga_adx_files_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
+        keep, offs = _i64_or_none(image_offsets)
+        return fetch_items(_lib.lib().vga_adx_files_read_items_for, (ptrs, len(infos), offs, int(general)), _lib.AdxFilesItemC)
 
     def stats(self):
         """(span files, general files, span items, general items) of a call made by this thread now"""
@@ -315,16 +296,7 @@ class AdxFileSet:
         infos = list(infos)
         ptrs = (C.c_void_p * max(len(infos), 1))(*[C.addressof(i) for i in infos])
         keep, offs = _i64_or_none(image_offsets)
-        call, count = _lib.lib().vga_adx_find_keys_items_for, C.c_int64()
-        check(call(ptrs, len(infos), offs, None, 0, C.byref(count)))
-        items = (_lib.AdxFindKeysItemC * max(count.value, 1))()
-        check(call(ptrs, len(infos), offs, items, count.value, C.byref(count)))
-        return list(items[:count.value])
-
-    def images(self, host_buffer):
-        """one `bytes` per file from the packed images (a device tensor or a numpy array); synchronises"""
-        host = host_buffer.cpu().numpy() if hasattr(host_buffer, "cpu") else np.asarray(host_buffer, dtype=np.uint8)
-        return [host[int(at):int(at) + int(size)].tobytes() for at, size in zip(self.image_offsets, self.image_sizes)]
+        return fetch_items(_lib.lib().vga_adx_find_keys_items_for, (ptrs, len(infos), offs), _lib.AdxFindKeysItemC)
 
 
 def device_keys(keys):

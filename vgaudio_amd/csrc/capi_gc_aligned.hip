@@ -1,8 +1,10 @@
 // capi_gc_aligned.hip -- sets of GC-ADPCM files whose loops need the alignment re-encode, on the device: aligned ADPCM, PCM,
 // seek tables and loop contexts of every file in one set of launches (include/vgaudio_hip/gc_files_aligned.h).  Host side
 // only: checks, layout, work tables and the cut of the workspace come from gc_aligned_host.hpp; create uploads the tables
-// the kernels read (gc_aligned_kernels.hpp) and the tail batch's shape, a call checks its pointers and launches.
+// the kernels read (gc_aligned_kernels.hpp) and the tail batch's shape through files_object.hpp, a call
+// checks its pointers and launches.
 #include "gc_capi.hpp"
+#include "files_object.hpp"
 #include "gc_aligned_kernels.hpp"
 
 #include <cstring>
@@ -11,33 +13,24 @@
 using namespace vga;
 
 struct vga_gc_aligned {
+    static constexpr const char *type_name = "vga_gc_aligned";
     gca::AlignedLayout L;
     vga_gcadpcm_ragged *ragged_in = nullptr, *ragged_out = nullptr;
     gc::RaggedShape tail;                        // the tails to encode: one row per channel of a file that needs alignment
     gc::Ragged tail_view;
-    void *d_tables = nullptr;
+    fileset::TableBlock block;
     gca::DeviceTables tables;
-    int device = 0;
+    int files() const { return L.totals.files; }
     ~vga_gc_aligned()
     {
         if (ragged_in) vga_gcadpcm_ragged_destroy(ragged_in);
         if (ragged_out) vga_gcadpcm_ragged_destroy(ragged_out);
-        if (d_tables) (void)hipFree(d_tables);
     }
 };
 
 namespace {
 
-template <class T> size_t place(size_t &at, const std::vector<T> &v)
-{
-    const size_t here = at;
-    at += (size_t)round_up((int64_t)(v.size() * sizeof(T)), 16);
-    return here;
-}
-template <class T> void fill(std::vector<unsigned char> &host, size_t at, const std::vector<T> &v)
-{
-    if (!v.empty()) memcpy(host.data() + at, v.data(), v.size() * sizeof(T));
-}
+using fileset::check_object;
 
 // the two ragged batches of the rows, the tail batch's shape and the tables in the current device's memory
 int finish_create(vga_gc_aligned *s)
@@ -49,7 +42,7 @@ int finish_create(vga_gc_aligned *s)
         return VGA_OK;
     }
     if (int rc = require_device()) return rc;
-    (void)hipGetDevice(&s->device);
+    (void)hipGetDevice(&s->block.device);
     const int nch = (int)L.channel.size();
     if (int rc = vga_gcadpcm_ragged_create(L.in.counts.data(), nch, &s->ragged_in)) return rc;
     if (int rc = vga_gcadpcm_ragged_create(L.out_counts.data(), nch, &s->ragged_out)) return rc;
@@ -64,43 +57,28 @@ int finish_create(vga_gc_aligned *s)
         set_error("internal: the tail batch is not the host layer's");
         return VGA_ERR_DEVICE;
     }
-    size_t bytes = 0;
-    const size_t rows_at = place(bytes, L.channel), gather_at = place(bytes, L.gather_items), adpcm_at = place(bytes, L.adpcm_items);
-    const size_t pcm_at = place(bytes, L.pcm_items), meta_at = place(bytes, L.meta_items), tail_at = bytes;
-    bytes += (size_t)round_up((int64_t)s->tail.table_bytes(), 16) + 16;
-    std::vector<unsigned char> host(bytes, 0);
-    fill(host, rows_at, L.channel);
-    fill(host, gather_at, L.gather_items);
-    fill(host, adpcm_at, L.adpcm_items);
-    fill(host, pcm_at, L.pcm_items);
-    fill(host, meta_at, L.meta_items);
+    fileset::TablePack pack;
+    const auto rows = pack.add(L.channel);
+    const auto gather = pack.add(L.gather_items);
+    const auto adpcm = pack.add(L.adpcm_items);
+    const auto pcm = pack.add(L.pcm_items);
+    const auto meta = pack.add(L.meta_items);
+    const size_t tail_at = pack.add_raw(s->tail.table_bytes());
+    std::vector<unsigned char> host = pack.image();
     if (s->tail.count > 0) s->tail.write_tables(host.data() + tail_at);
-    VGA_HIP_TRY(device_malloc(&s->d_tables, bytes));
-    VGA_HIP_TRY(hipMemcpy(s->d_tables, host.data(), bytes, hipMemcpyHostToDevice));
-    const unsigned char *d = static_cast<const unsigned char *>(s->d_tables);
-    s->tables.rows = reinterpret_cast<const gca::AlignRow *>(d + rows_at);
-    s->tables.gather = reinterpret_cast<const gca::Item *>(d + gather_at);
-    s->tables.adpcm = reinterpret_cast<const gca::Item *>(d + adpcm_at);
-    s->tables.pcm = reinterpret_cast<const gca::Item *>(d + pcm_at);
-    s->tables.meta = reinterpret_cast<const gca::MetaItem *>(d + meta_at);
+    if (int rc = s->block.upload(host)) return rc;
+    const unsigned char *d = static_cast<const unsigned char *>(s->block.d_tables);
+    s->tables.rows = pack.at(rows, d);
+    s->tables.gather = pack.at(gather, d);
+    s->tables.adpcm = pack.at(adpcm, d);
+    s->tables.pcm = pack.at(pcm, d);
+    s->tables.meta = pack.at(meta, d);
     s->tables.channels = nch;
     s->tables.gather_items = (int)L.gather_items.size();
     s->tables.adpcm_items = (int)L.adpcm_items.size();
     s->tables.pcm_items = (int)L.pcm_items.size();
     s->tables.meta_items = (int)L.meta_items.size();
     if (s->tail.count > 0) s->tail_view = s->tail.device_view(d + tail_at);
-    return VGA_OK;
-}
-
-int check_object(const vga_gc_aligned *s, const char *what)
-{
-    if (!s) { set_error("%s: null vga_gc_aligned", what); return VGA_ERR_ARGUMENT; }
-    int device = -1;
-    if (s->L.totals.files > 0) (void)hipGetDevice(&device);
-    if (s->L.totals.files > 0 && device != s->device) {
-        set_error("%s: the set was created on device %d, the current one is %d", what, s->device, device);
-        return VGA_ERR_ARGUMENT;
-    }
     return VGA_OK;
 }
 
@@ -128,17 +106,7 @@ int vga_gc_aligned_layout_for(const vga_gc_file *files, int nfiles, int *first_c
 
 int vga_gc_aligned_create(const vga_gc_file *files, int nfiles, vga_gc_aligned **out)
 {
-    if (!out) { set_error("null output"); return VGA_ERR_ARGUMENT; }
-    *out = nullptr;
-    vga_gc_aligned *s = new vga_gc_aligned;
-    int rc = gca::make_layout(files, nfiles, gc::encode_scratch_bytes, s->L);
-    if (!rc) rc = finish_create(s);
-    if (rc) {
-        delete s;
-        return rc;
-    }
-    *out = s;
-    return VGA_OK;
+    return fileset::create_with(out, [&](gca::AlignedLayout &L) { return gca::make_layout(files, nfiles, gc::encode_scratch_bytes, L); }, finish_create);
 }
 
 void vga_gc_aligned_destroy(vga_gc_aligned *s) { delete s; }

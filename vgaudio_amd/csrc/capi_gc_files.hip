@@ -1,7 +1,8 @@
 // capi_gc_files.hip -- sets of GC-ADPCM files on the device: channel metadata and DSP images of every file in one set of
 // launches (include/vgaudio_hip/gc_files.h).  Host side only: checks, layout and work tables come from gc_files_host.hpp;
-// create uploads the tables the kernels read (gc_files_kernels.hpp), a call checks its pointers and launches.
-#include "common.hpp"
+// create uploads the tables the kernels read (gc_files_kernels.hpp) through files_object.hpp, a call checks
+// its pointers and launches.
+#include "files_object.hpp"
 #include "gc_files_kernels.hpp"
 
 #include <cstring>
@@ -10,26 +11,21 @@
 using namespace vga;
 
 struct vga_gc_files {
+    static constexpr const char *type_name = "vga_gc_files";
     gcf::FilesLayout L;
     vga_gcadpcm_ragged *ragged = nullptr;
-    void *d_tables = nullptr;
+    fileset::TableBlock block;
     gcf::DeviceTables tables;
-    int device = 0;
+    int files() const { return L.totals.files; }
     ~vga_gc_files()
     {
         if (ragged) vga_gcadpcm_ragged_destroy(ragged);
-        if (d_tables) (void)hipFree(d_tables);
     }
 };
 
 namespace {
 
-template <class T> size_t place(size_t &at, const std::vector<T> &v)
-{
-    const size_t here = at;
-    at += (size_t)round_up((int64_t)(v.size() * sizeof(T)), 16);
-    return here;
-}
+using fileset::check_object;
 
 // the ragged batch of the rows and the tables in the current device's memory
 int finish_create(vga_gc_files *s)
@@ -40,42 +36,26 @@ int finish_create(vga_gc_files *s)
         return VGA_OK;
     }
     if (int rc = require_device()) return rc;
-    (void)hipGetDevice(&s->device);
+    (void)hipGetDevice(&s->block.device);
     if (int rc = vga_gcadpcm_ragged_create(L.counts.data(), (int)L.counts.size(), &s->ragged)) return rc;
     if (vga_gcadpcm_ragged_pcm_samples(s->ragged) != L.totals.pcm_samples || vga_gcadpcm_ragged_adpcm_bytes(s->ragged) != L.totals.adpcm_bytes) {
         set_error("internal: the set's rows are not the ragged batch's");
         return VGA_ERR_DEVICE;
     }
-    size_t bytes = 0;
-    const size_t geom_at = place(bytes, L.geom), rows_at = place(bytes, L.channel), audio_at = place(bytes, L.audio_items);
-    const size_t meta_at = place(bytes, L.meta_items);
-    std::vector<unsigned char> host(bytes, 0);
-    if (!L.geom.empty()) memcpy(host.data() + geom_at, L.geom.data(), L.geom.size() * sizeof(gcf::FileGeom));
-    memcpy(host.data() + rows_at, L.channel.data(), L.channel.size() * sizeof(gcf::ChannelRow));
-    if (!L.audio_items.empty()) memcpy(host.data() + audio_at, L.audio_items.data(), L.audio_items.size() * sizeof(gcf::Item));
-    memcpy(host.data() + meta_at, L.meta_items.data(), L.meta_items.size() * sizeof(gcf::MetaItem));
-    VGA_HIP_TRY(device_malloc(&s->d_tables, bytes));
-    VGA_HIP_TRY(hipMemcpy(s->d_tables, host.data(), bytes, hipMemcpyHostToDevice));
-    const unsigned char *d = static_cast<const unsigned char *>(s->d_tables);
-    s->tables.geom = reinterpret_cast<const gcf::FileGeom *>(d + geom_at);
-    s->tables.rows = reinterpret_cast<const gcf::ChannelRow *>(d + rows_at);
-    s->tables.audio = reinterpret_cast<const gcf::Item *>(d + audio_at);
-    s->tables.meta = reinterpret_cast<const gcf::MetaItem *>(d + meta_at);
+    fileset::TablePack pack;
+    const auto geom = pack.add(L.geom);
+    const auto rows = pack.add(L.channel);
+    const auto audio = pack.add(L.audio_items);
+    const auto meta = pack.add(L.meta_items);
+    if (int rc = s->block.upload(pack)) return rc;
+    const void *d = s->block.d_tables;
+    s->tables.geom = pack.at(geom, d);
+    s->tables.rows = pack.at(rows, d);
+    s->tables.audio = pack.at(audio, d);
+    s->tables.meta = pack.at(meta, d);
     s->tables.channels = (int)L.channel.size();
     s->tables.audio_items = (int)L.audio_items.size();
     s->tables.meta_items = (int)L.meta_items.size();
-    return VGA_OK;
-}
-
-int check_object(const vga_gc_files *s, const char *what)
-{
-    if (!s) { set_error("%s: null vga_gc_files", what); return VGA_ERR_ARGUMENT; }
-    int device = -1;
-    if (s->L.totals.files > 0) (void)hipGetDevice(&device);
-    if (s->L.totals.files > 0 && device != s->device) {
-        set_error("%s: the set was created on device %d, the current one is %d", what, s->device, device);
-        return VGA_ERR_ARGUMENT;
-    }
     return VGA_OK;
 }
 
@@ -104,32 +84,12 @@ int vga_gc_files_layout_for(const vga_gc_file *files, int nfiles, const vga_dsp_
 
 int vga_gc_files_create(const vga_gc_file *files, int nfiles, const vga_dsp_file_config *dsp, vga_gc_files **out)
 {
-    if (!out) { set_error("null output"); return VGA_ERR_ARGUMENT; }
-    *out = nullptr;
-    vga_gc_files *s = new vga_gc_files;
-    int rc = gcf::make_layout(files, nfiles, dsp, s->L);
-    if (!rc) rc = finish_create(s);
-    if (rc) {
-        delete s;
-        return rc;
-    }
-    *out = s;
-    return VGA_OK;
+    return fileset::create_with(out, [&](gcf::FilesLayout &L) { return gcf::make_layout(files, nfiles, dsp, L); }, finish_create);
 }
 
 int vga_gc_files_create_from_dsp(const vga_dsp_info *const *infos, int nfiles, const int64_t *image_offsets, vga_gc_files **out)
 {
-    if (!out) { set_error("null output"); return VGA_ERR_ARGUMENT; }
-    *out = nullptr;
-    vga_gc_files *s = new vga_gc_files;
-    int rc = gcf::make_layout_from_dsp(infos, nfiles, image_offsets, s->L);
-    if (!rc) rc = finish_create(s);
-    if (rc) {
-        delete s;
-        return rc;
-    }
-    *out = s;
-    return VGA_OK;
+    return fileset::create_with(out, [&](gcf::FilesLayout &L) { return gcf::make_layout_from_dsp(infos, nfiles, image_offsets, L); }, finish_create);
 }
 
 void vga_gc_files_destroy(vga_gc_files *s) { delete s; }

@@ -43,11 +43,7 @@ int vga_hca_find_keys_items_for(const vga_hca_file_info *const *infos, int nfile
     if (int rc = hcaf::make_layout_from_infos(infos, nfiles, nullptr, nullptr, nullptr, 0, false, nullptr, L)) return rc;
     std::vector<vga_hca_find_keys_item> v;
     hcak::describe_find_items(L.encryption_type, nkeys, v);
-    if (count_out) *count_out = (int64_t)v.size();
-    if (!items_out) return VGA_OK;
-    if ((int64_t)v.size() > capacity) { set_error("%lld work items, room for %lld", (long long)v.size(), (long long)capacity); return VGA_ERR_ARGUMENT; }
-    std::copy(v.begin(), v.end(), items_out);
-    return VGA_OK;
+    return fileset::copy_capped(v, items_out, capacity, count_out);
 }
 
 }  // extern "C"

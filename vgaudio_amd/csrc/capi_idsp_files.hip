@@ -1,7 +1,8 @@
 // capi_idsp_files.hip -- sets of IDSP files on the device: the images of every file written and read in one set of launches
 // (include/vgaudio_hip_files/idsp_files.h).  Host side only: checks, layout and work tables come from idsp_files_host.hpp;
-// create uploads the tables the kernels read (idsp_files_kernels.hpp), a call checks its pointers and launches.
-#include "common.hpp"
+// create uploads the tables the kernels read (idsp_files_kernels.hpp) through files_object.hpp, a call
+// checks its pointers and launches.
+#include "files_object.hpp"
 #include "idsp_files_kernels.hpp"
 
 #include <cstring>
@@ -10,33 +11,23 @@
 using namespace vga;
 
 struct vga_idsp_files {
+    static constexpr const char *type_name = "vga_idsp_files";
     idf::FilesLayout L;
     vga_gcadpcm_ragged *ragged = nullptr;
-    void *d_tables = nullptr;
-    size_t table_bytes = 0;
+    fileset::TableBlock block;
     idf::DeviceTables tables;
-    int device = 0;
+    int files() const { return L.totals.files; }
     ~vga_idsp_files()
     {
         if (ragged) vga_gcadpcm_ragged_destroy(ragged);
-        if (d_tables) (void)hipFree(d_tables);
     }
 };
 
 namespace {
 
-thread_local int t_last_launches = 0;            // of this thread's last _v call (vga_idsp_files_stats)
+using fileset::check_object;
 
-template <class T> size_t place(size_t &at, const std::vector<T> &v)
-{
-    const size_t here = at;
-    at += (size_t)round_up((int64_t)(v.size() * sizeof(T)), 16);
-    return here;
-}
-template <class T> void fill(std::vector<unsigned char> &host, size_t at, const std::vector<T> &v)
-{
-    if (!v.empty()) memcpy(host.data() + at, v.data(), v.size() * sizeof(T));
-}
+thread_local int t_last_launches = 0;            // of this thread's last _v call (vga_idsp_files_stats): cleared as the call begins
 
 // the ragged batch of the rows and the tables in the current device's memory
 int finish_create(vga_idsp_files *s)
@@ -47,44 +38,26 @@ int finish_create(vga_idsp_files *s)
         return VGA_OK;
     }
     if (int rc = require_device()) return rc;
-    (void)hipGetDevice(&s->device);
+    (void)hipGetDevice(&s->block.device);
     if (int rc = vga_gcadpcm_ragged_create(L.counts.data(), (int)L.counts.size(), &s->ragged)) return rc;
     if (vga_gcadpcm_ragged_pcm_samples(s->ragged) != L.totals.pcm_samples || vga_gcadpcm_ragged_adpcm_bytes(s->ragged) != L.totals.adpcm_bytes) {
         set_error("internal: the set's rows are not the ragged batch's");
         return VGA_ERR_DEVICE;
     }
-    size_t bytes = 0;
-    const size_t tab_at = place(bytes, L.tab), rows_at = place(bytes, L.channel), meta_at = place(bytes, L.meta);
-    const size_t audio_at = place(bytes, L.audio_items);
-    std::vector<unsigned char> host(bytes + 16, 0);
-    fill(host, tab_at, L.tab);
-    fill(host, rows_at, L.channel);
-    fill(host, meta_at, L.meta);
-    fill(host, audio_at, L.audio_items);
-    VGA_HIP_TRY(device_malloc(&s->d_tables, host.size()));
-    VGA_HIP_TRY(hipMemcpy(s->d_tables, host.data(), host.size(), hipMemcpyHostToDevice));
-    s->table_bytes = host.size();
-    const unsigned char *d = static_cast<const unsigned char *>(s->d_tables);
-    s->tables.tab = reinterpret_cast<const idf::FileTab *>(d + tab_at);
-    s->tables.rows = reinterpret_cast<const idf::ChannelRow *>(d + rows_at);
-    s->tables.meta = reinterpret_cast<const idf::ChannelMeta *>(d + meta_at);
-    s->tables.audio = reinterpret_cast<const idf::Item *>(d + audio_at);
+    fileset::TablePack pack;
+    const auto tab = pack.add(L.tab);
+    const auto rows = pack.add(L.channel);
+    const auto meta = pack.add(L.meta);
+    const auto audio = pack.add(L.audio_items);
+    if (int rc = s->block.upload(pack)) return rc;
+    const void *d = s->block.d_tables;
+    s->tables.tab = pack.at(tab, d);
+    s->tables.rows = pack.at(rows, d);
+    s->tables.meta = pack.at(meta, d);
+    s->tables.audio = pack.at(audio, d);
     s->tables.files = L.totals.files;
     s->tables.channels = (int)L.channel.size();
     s->tables.audio_items = (int)L.audio_items.size();
-    return VGA_OK;
-}
-
-int check_object(const vga_idsp_files *s, const char *what)
-{
-    t_last_launches = 0;
-    if (!s) { set_error("%s: null vga_idsp_files", what); return VGA_ERR_ARGUMENT; }
-    int device = -1;
-    if (s->L.totals.files > 0) (void)hipGetDevice(&device);
-    if (s->L.totals.files > 0 && device != s->device) {
-        set_error("%s: the set was created on device %d, the current one is %d", what, s->device, device);
-        return VGA_ERR_ARGUMENT;
-    }
     return VGA_OK;
 }
 
@@ -92,21 +65,6 @@ void copy_offsets(const idf::FilesLayout &L, int *first_channel_out, int64_t *im
 {
     if (first_channel_out) std::copy(L.first_channel.begin(), L.first_channel.end(), first_channel_out);
     if (image_offsets_out) std::copy(L.image_off.begin(), L.image_off.end(), image_offsets_out);
-}
-
-template <class Make> int create_with(vga_idsp_files **out, Make &&make)
-{
-    if (!out) { set_error("null output"); return VGA_ERR_ARGUMENT; }
-    *out = nullptr;
-    vga_idsp_files *s = new vga_idsp_files;
-    int rc = make(s->L);
-    if (!rc) rc = finish_create(s);
-    if (rc) {
-        delete s;
-        return rc;
-    }
-    *out = s;
-    return VGA_OK;
 }
 
 }  // namespace
@@ -126,12 +84,12 @@ int vga_idsp_files_layout_for(const vga_idsp_file *files, int nfiles, const vga_
 
 int vga_idsp_files_create(const vga_idsp_file *files, int nfiles, const vga_idsp_file_config *config, vga_idsp_files **out)
 {
-    return create_with(out, [&](idf::FilesLayout &L) { return idf::make_layout(files, nfiles, config, L); });
+    return fileset::create_with(out, [&](idf::FilesLayout &L) { return idf::make_layout(files, nfiles, config, L); }, finish_create);
 }
 
 int vga_idsp_files_create_from_infos(const vga_idsp_info *const *infos, int nfiles, const int64_t *image_offsets, vga_idsp_files **out)
 {
-    return create_with(out, [&](idf::FilesLayout &L) { return idf::make_layout_from_infos(infos, nfiles, image_offsets, L); });
+    return fileset::create_with(out, [&](idf::FilesLayout &L) { return idf::make_layout_from_infos(infos, nfiles, image_offsets, L); }, finish_create);
 }
 
 void vga_idsp_files_destroy(vga_idsp_files *s) { delete s; }
@@ -163,6 +121,7 @@ const vga_gcadpcm_ragged *vga_idsp_files_ragged(const vga_idsp_files *s) { retur
 int vga_idsp_write_device_v(const vga_idsp_files *s, const uint8_t *d_adpcm, const int16_t *d_coefs, const int16_t *d_gain,
                             const int16_t *d_start_context, const int16_t *d_loop_context, uint8_t *d_images, void *stream)
 {
+    t_last_launches = 0;
     if (int rc = check_object(s, "vga_idsp_write_device_v")) return rc;
     if (s->L.totals.files == 0) return VGA_OK;
     if (int rc = idf::check_write(s->L, d_adpcm, d_coefs, d_images)) return rc;
@@ -173,6 +132,7 @@ int vga_idsp_write_device_v(const vga_idsp_files *s, const uint8_t *d_adpcm, con
 int vga_idsp_read_device_v(const vga_idsp_files *s, const uint8_t *d_images, uint8_t *d_adpcm, int16_t *d_coefs, int16_t *d_gain,
                            int16_t *d_start_context, int16_t *d_loop_context, void *stream)
 {
+    t_last_launches = 0;
     if (int rc = check_object(s, "vga_idsp_read_device_v")) return rc;
     if (s->L.totals.files == 0) return VGA_OK;
     if (int rc = idf::check_read(s->L, d_images, d_adpcm)) return rc;
@@ -203,7 +163,7 @@ int vga_idsp_files_stats(const vga_idsp_files *s, int64_t *out)
     for (const idf::Item &it : s->L.audio_items) wide += it.y >> 31;
     out[0] = (int64_t)s->L.audio_items.size();
     out[1] = wide;
-    out[2] = (int64_t)s->table_bytes;
+    out[2] = (int64_t)s->block.table_bytes;
     out[3] = t_last_launches;
     return VGA_OK;
 }

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._fileset import FileSetHandle
 from ._lib import check, i16p, u8p
 from .gcadpcm import GcAdpcmChannel, GcAdpcmContext, GcAdpcmFormat, _i16, _ptr_array
 
@@ -142,13 +143,14 @@ def device_ptr(t, dtype, count, what):
     return t.data_ptr()
 
 
-class DspFileSet:
+class DspFileSet(FileSetHandle):
     """A set of GC-ADPCM files of different shapes, resident on the device (include/vgaudio_hip/gc_files.h has the layout): the
     channels of all files are the packed rows of one ragged batch, the seek tables one packed buffer, the DSP images another.
     `files`: one (channels, sample_rate, sample_count, looping, loop_start, loop_end[, alignment[, samples_per_seek_entry]])
     tuple or _lib.GcFileC per file; `configuration`: the DspConfiguration of the whole set (as VGAudio.Cli/Batch.cs applies
     one to every file), or None for a set without images.  The tensors are the caller's torch tensors on the current device;
     the calls run on torch's current stream and do not synchronise it."""
+    _destroy = "vga_gc_files_destroy"
 
     def __init__(self, files=None, configuration=None, _handle=None):
         self._h, sizes = C.c_void_p(), None
@@ -223,13 +225,6 @@ class DspFileSet:
         s = cls(_handle=h)
         s.image_sizes = [i.audio_offset + i.data_length for i in infos]
         return s
-
-    def close(self):
-        if self._h:
-            _lib.lib().vga_gc_files_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
     _stream = staticmethod(lambda stream: stream_handle(stream))
     _ptr = staticmethod(lambda t, dtype, count, what: device_ptr(t, dtype, count, what))

@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._fileset import FileSetHandle
 from ._lib import check, i16p, u8p
 
 
@@ -533,7 +534,7 @@ def decode_files(formats):
     return out
 
 
-class AlignedFileSet:
+class AlignedFileSet(FileSetHandle):
     """A set of GC-ADPCM files whose loop starts may need the GcAdpcmAlignment re-encode, resident on the device
     (include/vgaudio_hip/gc_files_aligned.h has the layout): the channels of all files are the packed rows of two ragged
     batches, `ragged_in` over the files' sample counts (what the _device_v codec calls wrote) and `ragged_out` over their
@@ -541,6 +542,7 @@ class AlignedFileSet:
     `files`: one (channels, sample_rate, sample_count, looping, loop_start, loop_end[, alignment[, samples_per_seek_entry]])
     tuple or _lib.GcFileC per file.  The tensors are the caller's torch tensors on the current device; the call runs on
     torch's current stream and does not synchronise it."""
+    _destroy = "vga_gc_aligned_destroy"
 
     def __init__(self, files=None):
         self._h = C.c_void_p()
@@ -576,13 +578,6 @@ class AlignedFileSet:
         check(_lib.lib().vga_gc_aligned_layout_for(arr, n, fc.ctypes.data_as(C.POINTER(C.c_int)), so.ctypes.data_as(C.POINTER(C.c_int64)),
                                                    C.byref(tot)))
         return fc[:n], so[:tot.channels], tot
-
-    def close(self):
-        if self._h:
-            _lib.lib().vga_gc_aligned_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
     def offsets(self, which):
         """(pcm offsets, adpcm offsets) int64[channels] of `ragged_in` ("in") or `ragged_out` ("out")"""

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._fileset import FileSetBase, fetch_items, i64_or_none as _i64_or_none
 from ._lib import check, u8p
 from .crihca import CriHcaEncryption, CriHcaFormat, CriHcaKey, CriHcaParameters, CriHcaQuality, HcaInfo
 from .gcadpcm import Pcm16Format
@@ -131,13 +132,6 @@ class HcaReader:
 
 
 # ---------------------------------------------------------------- sets of files on the device (include/vgaudio_hip/hca_files.h)
-def _i64_or_none(values):
-    if values is None:
-        return None, None
-    a = np.ascontiguousarray(values, dtype=np.int64)
-    return a, a.ctypes.data_as(C.POINTER(C.c_int64))
-
-
 def _tables_or_none(tables):
     """ntables x 256 bytes -> (keep-alive, pointer, count)"""
     if tables is None or len(tables) == 0:
@@ -156,13 +150,14 @@ def _hca_file(f):
     return _lib.HcaFileC(c, comment, float(volume), int(encryption_type), int(encrypted_ids), int(key))
 
 
-class HcaFileSet:
+class HcaFileSet(FileSetBase):
     """A set of HCA files of different shapes, resident on the device (include/vgaudio_hip/hca_files.h has the layout): the
     frames of all files lie packed -- as crihca.RaggedHca leaves its output, or at the caller's `frame_offsets` --, the images
     in one packed buffer.  `files`: one _lib.HcaFileC or (info, comment, volume, encryption_type, encrypted_ids, key) per file:
     what vga_hca_write_device takes, and the index of the file's table in `tables` (ntables x 256 bytes; -1: no key).  The
     tensors are the caller's torch tensors on the current device; the calls run on torch's current stream and do not
     synchronise it."""
+    _destroy = "vga_hca_files_destroy"
 
     def __init__(self, files=None, frame_offsets=None, tables=None, _handle=None):
         self._h, self.image_sizes = C.c_void_p(), None
@@ -218,20 +213,12 @@ class HcaFileSet:
         s.image_sizes = [i.frames_offset + i.hca.frame_count * i.hca.frame_size for i in infos]
         return s
 
-    @staticmethod
-    def _items(call, head, general):
-        count = C.c_int64()
-        check(call(*head, int(general), None, 0, C.byref(count)))
-        items = (_lib.HcaFilesItemC * max(count.value, 1))()
-        check(call(*head, int(general), items, count.value, C.byref(count)))
-        return list(items[:count.value])
-
     @classmethod
     def write_items(cls, files, frame_offsets=None, general=False):
         """the work items of vga_hca_write_device_v on such a set (_lib.HcaFilesItemC), host only"""
         arr, n = cls._files_array(files)
         keep, offs = _i64_or_none(frame_offsets)
-        return cls._items(_lib.lib().vga_hca_files_write_items_for, (arr, n, offs), general)
+        return fetch_items(_lib.lib().vga_hca_files_write_items_for, (arr, n, offs, int(general)), _lib.HcaFilesItemC)
 
     @classmethod
     def read_items(cls, infos, image_offsets=None, frame_offsets=None, general=False):
@@ -240,14 +227,7 @@ class HcaFileSet:
         ptrs = (C.c_void_p * max(len(infos), 1))(*[C.addressof(i) for i in infos])
         keep, offs = _i64_or_none(image_offsets)
         keep_f, foffs = _i64_or_none(frame_offsets)
-        return cls._items(_lib.lib().vga_hca_files_read_items_for, (ptrs, len(infos), offs, foffs), general)
-
-    def close(self):
-        if self._h:
-            _lib.lib().vga_hca_files_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
+        return fetch_items(_lib.lib().vga_hca_files_read_items_for, (ptrs, len(infos), offs, foffs, int(general)), _lib.HcaFilesItemC)
 
     def stats(self):
         """(span files, general files, span items, general items) of a call made by this thread now"""
@@ -323,16 +303,7 @@ class HcaFileSet:
         """the work items of find_keys_device's test launches on a set of such infos (_lib.HcaFindKeysItemC), host only"""
         infos = list(infos)
         ptrs = (C.c_void_p * max(len(infos), 1))(*[C.addressof(i) for i in infos])
-        call, count = _lib.lib().vga_hca_find_keys_items_for, C.c_int64()
-        check(call(ptrs, len(infos), int(nkeys), None, 0, C.byref(count)))
-        items = (_lib.HcaFindKeysItemC * max(count.value, 1))()
-        check(call(ptrs, len(infos), int(nkeys), items, count.value, C.byref(count)))
-        return list(items[:count.value])
-
-    def images(self, host_buffer):
-        """one `bytes` per file from the packed images (a device tensor or a numpy array); synchronises"""
-        host = host_buffer.cpu().numpy() if hasattr(host_buffer, "cpu") else np.asarray(host_buffer, dtype=np.uint8)
-        return [host[int(at):int(at) + int(size)].tobytes() for at, size in zip(self.image_offsets, self.image_sizes)]
+        return fetch_items(_lib.lib().vga_hca_find_keys_items_for, (ptrs, len(infos), int(nkeys)), _lib.HcaFindKeysItemC)
 
 
 def device_tables(keys):

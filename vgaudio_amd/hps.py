@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._fileset import FileSetBase
 from ._lib import check, i16p, u8p
 from .gcadpcm import GcAdpcmChannel, GcAdpcmContext, GcAdpcmDecoder, GcAdpcmFormat, GcAdpcmParameters, _i16, _ptr_array
 
@@ -127,12 +128,13 @@ def _hps_file(channels, sample_rate, sample_count, looping=False, loop_start=0, 
     return _lib.HpsFileC(int(channels), int(sample_rate), int(sample_count), int(bool(looping)), int(loop_start), int(loop_end))
 
 
-class HpsFileSet:
+class HpsFileSet(FileSetBase):
     """A set of HPS files of different shapes, resident on the device (include/vgaudio_hip_files/hps_files.h has the layout):
     the channels of all files are the packed rows gcadpcm.AlignedFileSet leaves as its output, the images another packed
     buffer.  `files`: one (channels, sample_rate, sample_count, looping, loop_start, loop_end) tuple or _lib.HpsFileC per
     file, the loop the format's, before the writer aligns it.  The tensors are the caller's torch tensors on the current
     device; the calls run on torch's current stream and do not synchronise it."""
+    _destroy = "vga_hps_files_destroy"
 
     def __init__(self, files=None, _handle=None):
         self._h, self.image_sizes = C.c_void_p(), None
@@ -198,13 +200,6 @@ class HpsFileSet:
                              for k in range(i.block_count)) for i, b in parsed]
         return s
 
-    def close(self):
-        if self._h:
-            _lib.lib().vga_hps_files_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
     def gc_files(self):
         """the _lib.GcFileC of every file (channel = vga_hps_layout_for(...).channel): what gcadpcm.AlignedFileSet takes"""
         arr = (_lib.GcFileC * max(self.files, 1))()
@@ -239,11 +234,6 @@ class HpsFileSet:
             ptr(coefs, torch.int16, n * 16, "coefs"), ptr(gain, torch.int16, n, "gain"),
             ptr(start_context, torch.int16, n * 3, "start_context"), ptr(loop_context, torch.int16, n * 3, "loop_context"),
             stream_handle(stream)))
-
-    def images(self, host_buffer):
-        """one `bytes` per file from the packed images (a device tensor or a numpy array); synchronises"""
-        host = host_buffer.cpu().numpy() if hasattr(host_buffer, "cpu") else np.asarray(host_buffer, dtype=np.uint8)
-        return [host[int(at):int(at) + int(size)].tobytes() for at, size in zip(self.image_offsets, self.image_sizes)]
 
 
 def write_files(pcm16_list):

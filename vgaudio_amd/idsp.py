@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._fileset import FileSetBase
 from ._lib import check, u8p
 from .gcadpcm import GcAdpcmChannel, GcAdpcmContext, GcAdpcmFormat, _i16, _ptr_array
 
@@ -136,13 +137,14 @@ def _file_config(configuration=None):
     return _lib.IdspFileConfigC(int(c.BlockSize), int(bool(c.TrimFile)))
 
 
-class IdspFileSet:
+class IdspFileSet(FileSetBase):
     """A set of IDSP files of different shapes, resident on the device (include/vgaudio_hip_files/idsp_files.h has the layout):
     the channels of all files are the packed rows gcadpcm.AlignedFileSet leaves as its output, the images another packed
     buffer.  `files`: one (channels, sample_rate, sample_count, looping, loop_start, loop_end) tuple or _lib.IdspFileC per
     file, the loop the format's, before the writer aligns it; `configuration`: the IdspConfiguration of the whole set (as
     VGAudio.Cli/Batch.cs applies one to every file).  The tensors are the caller's torch tensors on the current device; the
     calls run on torch's current stream and do not synchronise it."""
+    _destroy = "vga_idsp_files_destroy"
 
     def __init__(self, files=None, configuration=None, _handle=None):
         self._h, self.image_sizes = C.c_void_p(), None
@@ -204,13 +206,6 @@ class IdspFileSet:
         s.image_sizes = [i.audio_data_offset + i.channel_count * i.audio_data_length for i in infos]
         return s
 
-    def close(self):
-        if self._h:
-            _lib.lib().vga_idsp_files_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
     def gc_files(self):
         """the _lib.GcFileC of every file (channel = vga_idsp_layout_for(...).channel): what gcadpcm.AlignedFileSet takes"""
         arr = (_lib.GcFileC * max(self.files, 1))()
@@ -246,11 +241,6 @@ class IdspFileSet:
             ptr(coefs, torch.int16, n * 16, "coefs"), ptr(gain, torch.int16, n, "gain"),
             ptr(start_context, torch.int16, n * 3, "start_context"), ptr(loop_context, torch.int16, n * 3, "loop_context"),
             stream_handle(stream)))
-
-    def images(self, host_buffer):
-        """one `bytes` per file from the packed images (a device tensor or a numpy array); synchronises"""
-        host = host_buffer.cpu().numpy() if hasattr(host_buffer, "cpu") else np.asarray(host_buffer, dtype=np.uint8)
-        return [host[int(at):int(at) + int(size)].tobytes() for at, size in zip(self.image_offsets, self.image_sizes)]
 
 
 def write_files(pcm16_list, configuration=None):

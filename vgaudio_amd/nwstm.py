@@ -8,6 +8,7 @@ import enum
 import numpy as np
 
 from . import _lib
+from ._fileset import FileSetBase, FileSetHandle, fetch_items, i64_or_none as _i64_or_none
 from ._lib import check, i16p, u8p
 from .gcadpcm import AudioTrack, GcAdpcmChannel, GcAdpcmContext, GcAdpcmFormat, Pcm16Format, _i16, _ptr_array
 from .pcm8 import Pcm8Format, Pcm8SignedFormat
@@ -420,13 +421,14 @@ def _file_config(target, configuration=None):
                               -1 if c.Endianness is None else int(c.Endianness))
 
 
-class NwFileSet:
+class NwFileSet(FileSetBase):
     """A set of BRSTM / BCSTM / BFSTM files of different shapes, resident on the device (include/vgaudio_hip/nw_files.h has the
     layout): the channels of all files are the packed rows gcadpcm.AlignedFileSet leaves as its output, the seek tables one
     packed buffer, the images another.  `files`: one (channels, sample_rate, sample_count, looping, loop_start, loop_end) tuple or
     _lib.NwFileC per file, the loop the format's, before the writer aligns it; `target`: NwTarget; `configuration`: the
     BxstmConfiguration of the whole set (as VGAudio.Cli/Batch.cs applies one to every file).  The tensors are the caller's
     torch tensors on the current device; the calls run on torch's current stream and do not synchronise it."""
+    _destroy = "vga_nw_files_destroy"
 
     def __init__(self, files=None, target=NwTarget.Revolution, configuration=None, _handle=None):
         self._h, self.image_sizes = C.c_void_p(), None
@@ -493,13 +495,6 @@ class NwFileSet:
         s.image_sizes = [i.audio_data_offset + i.audio_data_length for i in infos]
         return s
 
-    def close(self):
-        if self._h:
-            _lib.lib().vga_nw_files_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
     def gc_files(self):
         """the _lib.GcFileC of every file (channel = vga_nwstm_layout_for(...).channel): what gcadpcm.AlignedFileSet takes"""
         arr = (_lib.GcFileC * max(self.files, 1))()
@@ -528,11 +523,6 @@ class NwFileSet:
             ptr(coefs, torch.int16, n * 16, "coefs"), ptr(gain, torch.int16, n, "gain"),
             ptr(start_context, torch.int16, n * 3, "start_context"), ptr(loop_context, torch.int16, n * 3, "loop_context"),
             DspFileSet._stream(stream)))
-
-    def images(self, host_buffer):
-        """one `bytes` per file from the packed images (a device tensor or a numpy array); synchronises"""
-        host = host_buffer.cpu().numpy() if hasattr(host_buffer, "cpu") else np.asarray(host_buffer, dtype=np.uint8)
-        return [host[int(at):int(at) + int(size)].tobytes() for at, size in zip(self.image_offsets, self.image_sizes)]
 
 
 def write_files(pcm16_list, target, configuration=None):
@@ -593,14 +583,7 @@ def _pcm_file_config(target, configuration):
     return cfg, int(c.Codec)
 
 
-def _i64_or_none(values):
-    if values is None:
-        return None, None
-    a = np.ascontiguousarray(values, dtype=np.int64)
-    return a, a.ctypes.data_as(C.POINTER(C.c_int64))
-
-
-class NwPcmFileSet:
+class NwPcmFileSet(FileSetHandle):
     """A set of PCM16 / PCM8 BRSTM / BCSTM / BFSTM files of different shapes, resident on the device
     (include/vgaudio_hip_files/nw_pcm_files.h has the layout): the channels of all files are packed int16 rows of ONE buffer,
     as wave.read_files_device leaves them, or at the caller's `pcm_offsets` (samples); the images one buffer, packed or at the
@@ -608,6 +591,7 @@ class NwPcmFileSet:
     _lib.NwFileC per file; `target`: NwTarget; `configuration`: the BxstmConfiguration of the whole set, its Codec Pcm16Bit
     or Pcm8Bit.  The tensors are the caller's torch tensors on the current device; the calls run on torch's current stream
     and do not synchronise it."""
+    _destroy = "vga_nw_pcm_files_destroy"
 
     def __init__(self, files=None, target=NwTarget.Revolution, configuration=None, pcm_offsets=None, image_offsets=None, _handle=None):
         self._h, self.image_sizes = C.c_void_p(), None
@@ -681,11 +665,7 @@ class NwPcmFileSet:
     def _items(call, args, pcm_offsets, image_offsets, general):
         keep_p, po = _i64_or_none(pcm_offsets)
         keep_i, io = _i64_or_none(image_offsets)
-        count = C.c_int64()
-        check(call(*args, po, io, int(general), None, 0, C.byref(count)))
-        items = (_lib.NwPcmFilesItemC * max(count.value, 1))()
-        check(call(*args, po, io, int(general), items, count.value, C.byref(count)))
-        return list(items[:count.value])
+        return fetch_items(call, (*args, po, io, int(general)), _lib.NwPcmFilesItemC)
 
     @classmethod
     def write_items(cls, files, target=NwTarget.Revolution, configuration=None, pcm_offsets=None, image_offsets=None, general=False):
@@ -700,13 +680,6 @@ class NwPcmFileSet:
         infos = list(infos)
         ptrs = (C.c_void_p * max(len(infos), 1))(*[C.addressof(i) for i in infos])
         return cls._items(_lib.lib().vga_nw_pcm_files_read_items_for, (ptrs, len(infos)), pcm_offsets, image_offsets, general)
-
-    def close(self):
-        if self._h:
-            _lib.lib().vga_nw_pcm_files_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
     def offsets(self):
         """(first_channel, pcm_offsets, image_offsets) of the object"""

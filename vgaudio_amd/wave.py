@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._fileset import FileSetHandle, fetch_items, i64_or_none as _i64_or_none
 from ._lib import check, i16p, u8p
 from .gcadpcm import Pcm16Format, _ptr_array
 from .pcm8 import Pcm8Format
@@ -89,24 +90,18 @@ class WaveWriter:
 
 
 # ---------------------------------------------------------------- sets of files (include/vgaudio_hip_files/wave_files.h)
-def _i64_or_none(values):
-    if values is None:
-        return None, None
-    a = np.ascontiguousarray(values, dtype=np.int64)
-    return a, a.ctypes.data_as(C.POINTER(C.c_int64))
-
-
 def _wave_file(f):
     """a _lib.WaveFileC from one, or from (channels, bits, _lib.WaveParamsC)"""
     return f if isinstance(f, _lib.WaveFileC) else _lib.WaveFileC(f[0], f[1], f[2])
 
 
-class WaveFileSet:
+class WaveFileSet(FileSetHandle):
     """A set of WAVE files of different shapes, resident on the device (include/vgaudio_hip_files/wave_files.h has the layout):
     the channels of all files are packed int16 rows of ONE buffer -- as criadx.RaggedAdx, crihca.RaggedHca and the GC ragged
     objects take their input, or at the caller's `pcm_offsets` (samples) --, the images one buffer, packed or at the caller's
     `image_offsets` (any byte).  `files`: one _lib.WaveFileC or (channels, bits, _lib.WaveParamsC) per file.  The tensors are
     the caller's torch tensors on the current device; the calls run on torch's current stream and do not synchronise it."""
+    _destroy = "vga_wave_files_destroy"
 
     def __init__(self, files=None, pcm_offsets=None, image_offsets=None, _handle=None):
         self._h, self.image_sizes = C.c_void_p(), None
@@ -174,11 +169,7 @@ class WaveFileSet:
     def _items(call, first, n, pcm_offsets, image_offsets, general):
         keep_p, po = _i64_or_none(pcm_offsets)
         keep_i, io = _i64_or_none(image_offsets)
-        count = C.c_int64()
-        check(call(first, n, po, io, int(general), None, 0, C.byref(count)))
-        items = (_lib.WaveFilesItemC * max(count.value, 1))()
-        check(call(first, n, po, io, int(general), items, count.value, C.byref(count)))
-        return list(items[:count.value])
+        return fetch_items(call, (first, n, po, io, int(general)), _lib.WaveFilesItemC)
 
     @classmethod
     def write_items(cls, files, pcm_offsets=None, image_offsets=None, general=False):
@@ -192,13 +183,6 @@ class WaveFileSet:
         infos = list(infos)
         ptrs = (C.c_void_p * max(len(infos), 1))(*[C.addressof(i) for i in infos])
         return cls._items(_lib.lib().vga_wave_files_read_items_for, ptrs, len(infos), pcm_offsets, image_offsets, general)
-
-    def close(self):
-        if self._h:
-            _lib.lib().vga_wave_files_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
     def stats(self):
         """(tile files, general files, tile items, general items) of a call made by this thread now"""
