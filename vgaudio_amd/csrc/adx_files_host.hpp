@@ -5,21 +5,20 @@
 // (tests/host/adx_files_host_driver.cpp) as capi_adx_files.hip does; whoever includes it supplies vga::set_error and
 // vga::last_error.
 #pragma once
+#include "files_layout.hpp"
 #include "adx_file_host.hpp"
 #include "adx_span.hpp"
 #include "../../include/vgaudio_hip/adx_files.h"
 
-#include <string>
-
 namespace vga {
-
-const char *last_error();                        // the message of the last set_error on this thread
-
 namespace adxf {
 
-constexpr int64_t GUARD_BYTES = 256;             // behind the last row and behind the last image
+using fileset::aligned16;
+using fileset::name_file;
+using fileset::pad_to;
+using fileset::MAX_TOTAL;
+constexpr int64_t GUARD_BYTES = fileset::IMAGE_GUARD_BYTES;   // behind the last row as behind the last image
 constexpr int CHUNK_GRANULES = 2048;             // of one general work item: 256 threads, eight granules each
-constexpr int64_t MAX_TOTAL = (int64_t)1 << 62;
 // keyed calls (include/vgaudio_hip_files/adx_keyed_files.h): a slot is frame * channels + channel, the cipher's own order
 constexpr int CIPHER_CHUNK_SLOTS = 2048;         // of one item of the general form's cipher pass: 256 threads, eight slots each
 constexpr int FIND_SPAN_SLOTS = 1024;            // of one item of the key search: 256 lanes = 64 candidates x 4 quarters
@@ -56,14 +55,6 @@ struct FilesLayout {
     bool tiny_frame = false;                     // a file of 1-byte frames (a set for reading): no scale to cipher
 };
 
-// "file <f>: " in front of the message the per-file code left
-inline int name_file(int f, int rc)
-{
-    const std::string msg = last_error();
-    set_error("file %d: %s", f, msg.c_str());
-    return rc;
-}
-
 // the widest power of two up to 16 that divides every bit set in `bits`
 inline int granule_of(uint64_t bits)
 {
@@ -81,15 +72,9 @@ inline void cut_items(FilesLayout &L, int f, bool span_ok)
     const int nch = t.h.nch, fs = t.h.frame_size;
     if (t.copy_frames <= 0) return;
     L.moving_files++;
-    const int64_t unit = (int64_t)CHUNK_GRANULES * t.granule;
     // write: chunks of the file's interleaved bytes; read: chunks of every row
-    const int64_t per = (int64_t)t.copy_frames * fs * (L.from_infos ? 1 : nch);
-    const int first = L.from_infos ? t.first_channel : f, count = L.from_infos ? nch : 1;
-    for (int k = 0; k < 2; k++) {
-        if (k == 0 && span_ok) continue;
-        for (int i = 0; i < count; i++)
-            for (int64_t at = 0, y = 0; at < per; at += unit, y++) L.items[k].push_back({first + i, (uint32_t)y});
-    }
+    fileset::cut_general_items(L.items, span_ok, L.from_infos ? t.first_channel : f, L.from_infos ? nch : 1,
+                               (int64_t)t.copy_frames * fs * (L.from_infos ? 1 : nch), (int64_t)CHUNK_GRANULES * t.granule);
     const int64_t slots = (int64_t)t.copy_frames * nch;
     for (int k = 0; k < 2; k++)
         for (int64_t at = 0, y = 0; at < slots && !(k == 0 && span_ok); at += CIPHER_CHUNK_SLOTS, y++) L.cipher_items[k].push_back({f, (uint32_t)y});
@@ -107,28 +92,22 @@ inline void finish_items(FilesLayout &L)
     std::vector<Item> span;
     for (size_t f = 0; f < L.tab.size(); f++)
         for (int k0 = 0; L.tab[f].span_frames > 0 && k0 < L.tab[f].copy_frames; k0 += L.tab[f].span_frames) span.push_back({(int)f, (uint32_t)k0});
-    L.span_items = (int)span.size();
-    L.items[0].insert(L.items[0].begin(), span.begin(), span.end());
+    L.span_items = fileset::put_in_front(L.items[0], span);
 }
 
 inline int check_item_counts(const FilesLayout &L)
 {
-    if (L.items[0].size() > 0x7FFFFFFF || L.items[1].size() > 0x7FFFFFFF || L.cipher_items[1].size() > 0x7FFFFFFF || L.find_items.size() > 0x7FFFFFFF) { set_error("the set has more than 2^31 work items"); return VGA_ERR_OUT_OF_RANGE; }
-    return VGA_OK;
+    return fileset::check_item_count(std::max({L.items[0].size(), L.items[1].size(), L.cipher_items[1].size(), L.find_items.size()}));
 }
 
 inline int make_layout(const vga_adx_file *files, int nfiles, const int64_t *audio_offsets, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !files) { set_error("null files"); return VGA_ERR_ARGUMENT; }
-    L = FilesLayout();
-    L.totals.files = nfiles;
+    if (int rc = fileset::check_files(nfiles, files != nullptr, "files")) return rc;
+    fileset::start_layout(L, nfiles, false);
     L.layout.resize(nfiles);
-    L.first_channel.resize(nfiles);
-    L.image_off.resize(nfiles);
-    L.image_size.resize(nfiles);
-    L.tab.resize(nfiles);
-    int64_t channels = 0, image_at = 0, audio_at = 0, audio_end = 0;
+    int64_t channels = 0;
+    fileset::Rows rows;
+    fileset::Images images;
     for (int f = 0; f < nfiles; f++) {
         const vga_adx_file &F = files[f];
         const vga_adx_file_params &p = F.params;
@@ -147,30 +126,26 @@ inline int make_layout(const vga_adx_file *files, int nfiles, const int64_t *aud
             set_error("file %d: ADX footer (4 bytes at %d) does not fit the %d-byte file", f, t.h.footer_pos, t.h.file_size);
             return VGA_ERR_INVALID_OP;
         }
-        if (channels + F.channels > 0x7FFFFFFF) { set_error("file %d: more than 2^31 rows", f); return VGA_ERR_ARGUMENT; }
+        const int first = (int)channels;
+        if (int rc = fileset::count_rows(f, F.channels, channels, "rows")) return rc;
         const vga_adx_file_layout &A = L.layout[f];
         L.any_v4 = L.any_v4 || p.version == 4;
-        L.first_channel[f] = (int)channels;
+        L.first_channel[f] = first;
         uint64_t bits = 0;
         for (int i = 0; i < F.channels; i++) {
-            int64_t at = audio_at;
-            if (audio_offsets) {
-                at = audio_offsets[channels + i];
-                if (at < 0 || at % 4) { set_error("file %d: audio offset %lld of row %lld is negative or no multiple of 4", f, (long long)at, (long long)(channels + i)); return VGA_ERR_ARGUMENT; }
-            } else {
-                audio_at += adx::pad_to(row, 16);
-            }
-            if (at > MAX_TOTAL) { set_error("file %d: the rows of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
+            const fileset::Placed r = rows.place(row, pad_to(row, 16), MAX_TOTAL, audio_offsets ? audio_offsets + first + i : nullptr);
+            const int64_t at = r.at;
+            if (at < 0 || at % 4) { set_error("file %d: audio offset %lld of row %lld is negative or no multiple of 4", f, (long long)at, (long long)(first + i)); return VGA_ERR_ARGUMENT; }
+            if (r.verdict & fileset::OFFSET_PAST_MAX) { set_error("file %d: the rows of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
             L.row_off.push_back(at);
             L.row_bytes.push_back((int)row);
             L.row_file.push_back(f);
-            if (row > 0) {
-                audio_end = std::max(audio_end, at + row);
-                bits |= (uint64_t)at;
-            }
+            if (row > 0) bits |= (uint64_t)at;
         }
+        const fileset::Placed image = images.place(A.file_size);
+        const int64_t image_at = image.at;
         t.image_off = image_at;
-        t.first_channel = (int)channels;
+        t.first_channel = first;
         t.audio_offset = A.audio_offset;
         t.copy_frames = (int)std::min<int64_t>(in_frames, A.frame_count);
         t.header_end = std::max(A.audio_offset, container::adx_header_fields_end(p.version, F.channels));
@@ -179,46 +154,29 @@ inline int make_layout(const vga_adx_file *files, int nfiles, const int64_t *aud
         cut_items(L, f, span_shape(p.frame_size, F.channels) && !(bits & 15));
         L.image_off[f] = image_at;
         L.image_size[f] = A.file_size;
-        image_at += adx::pad_to(A.file_size, 16);
-        if (image_at > MAX_TOTAL) { set_error("file %d: the images of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
-        channels += F.channels;
+        if (image.verdict & fileset::TOTAL_PAST_MAX) { set_error("file %d: the images of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
     }
-    if (audio_offsets) {                          // rows of bytes must not overlap
-        std::vector<int> order;
-        for (int c = 0; c < (int)channels; c++)
-            if (L.row_bytes[c] > 0) order.push_back(c);
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return L.row_off[a] != L.row_off[b] ? L.row_off[a] < L.row_off[b] : a < b; });
-        for (size_t i = 1; i < order.size(); i++) {
-            const int a = order[i - 1], b = order[i];
-            if (L.row_off[a] + L.row_bytes[a] > L.row_off[b]) {
-                set_error("file %d: row %d (offset %lld, %d bytes) overlaps row %d (offset %lld)", L.row_file[std::max(a, b)], a,
-                          (long long)L.row_off[a], L.row_bytes[a], b, (long long)L.row_off[b]);
-                return VGA_ERR_ARGUMENT;
-            }
-        }
-    } else {
-        audio_end = audio_at;
+    int a, b;                                     // rows of bytes must not overlap
+    if (audio_offsets && fileset::find_overlap((int)channels, [&](int c) { return L.row_off[c]; }, [&](int c) { return L.row_bytes[c]; }, a, b)) {
+        set_error("file %d: row %d (offset %lld, %d bytes) overlaps row %d (offset %lld)", L.row_file[std::max(a, b)], a,
+                  (long long)L.row_off[a], L.row_bytes[a], b, (long long)L.row_off[b]);
+        return VGA_ERR_ARGUMENT;
     }
     finish_items(L);
     L.totals.channels = (int)channels;
-    L.totals.audio_bytes = audio_end + GUARD_BYTES;
-    L.totals.image_bytes = image_at + GUARD_BYTES;
+    L.totals.audio_bytes = rows.end + GUARD_BYTES;
+    L.totals.image_bytes = images.total();
     return check_item_counts(L);
 }
 
 // a set for reading, from what vga_adx_parse returned for every file
 inline int make_layout_from_infos(const vga_adx_file_info *const *infos, int nfiles, const int64_t *image_offsets, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !infos) { set_error("null infos"); return VGA_ERR_ARGUMENT; }
-    L = FilesLayout();
-    L.from_infos = true;
-    L.totals.files = nfiles;
-    L.first_channel.resize(nfiles);
-    L.image_off.resize(nfiles);
-    L.image_size.resize(nfiles);
-    L.tab.resize(nfiles);
-    int64_t channels = 0, image_at = 0, image_end = 0, audio_at = 0;
+    if (int rc = fileset::check_files(nfiles, infos != nullptr, "infos")) return rc;
+    fileset::start_layout(L, nfiles, true);
+    int64_t channels = 0;
+    fileset::Rows rows;
+    fileset::Images images;
     for (int f = 0; f < nfiles; f++) {
         const vga_adx_file_info *I = infos[f];
         if (!I) { set_error("file %d: null info", f); return VGA_ERR_ARGUMENT; }
@@ -228,24 +186,23 @@ inline int make_layout_from_infos(const vga_adx_file_info *const *infos, int nfi
             set_error("file %d: info does not describe an ADX file", f);
             return VGA_ERR_ARGUMENT;
         }
-        const int64_t at = image_offsets ? image_offsets[f] : image_at;
-        if (at < 0) { set_error("file %d: negative image offset %lld", f, (long long)at); return VGA_ERR_ARGUMENT; }
         const int64_t size = (int64_t)I->audio_offset + (int64_t)I->audio_bytes * nch;
-        if (size > 0x7FFFFFFF || at > MAX_TOTAL) { set_error("file %d: image past 2 GiB or offset past 2^62", f); return VGA_ERR_OUT_OF_RANGE; }
-        if (channels + nch > 0x7FFFFFFF) { set_error("file %d: more than 2^31 rows", f); return VGA_ERR_ARGUMENT; }
-        L.first_channel[f] = (int)channels;
+        const fileset::Placed image = images.place(size, image_offsets ? image_offsets + f : nullptr);
+        const int64_t at = image.at;
+        if (image.verdict & fileset::OFFSET_NEGATIVE) { set_error("file %d: negative image offset %lld", f, (long long)at); return VGA_ERR_ARGUMENT; }
+        if (image.verdict & (fileset::IMAGE_PAST_2GIB | fileset::OFFSET_PAST_MAX)) { set_error("file %d: image past 2 GiB or offset past 2^62", f); return VGA_ERR_OUT_OF_RANGE; }
+        const int first = (int)channels;
+        if (int rc = fileset::count_rows(f, nch, channels, "rows")) return rc;
+        L.first_channel[f] = first;
         L.image_off[f] = at;
         L.image_size[f] = (int)size;
-        image_at = adx::pad_to(at + size, 16);
-        image_end = std::max(image_end, image_at);
         for (int i = 0; i < nch; i++) {
-            L.row_off.push_back(audio_at);
+            L.row_off.push_back(rows.place(I->audio_bytes, pad_to(I->audio_bytes, 16), MAX_TOTAL).at);
             L.row_bytes.push_back(I->audio_bytes);
             L.row_file.push_back(f);
             L.history.push_back(I->history[i][0]);
-            audio_at += adx::pad_to(I->audio_bytes, 16);
         }
-        if (audio_at > MAX_TOTAL) { set_error("file %d: the rows of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
+        if (rows.at > MAX_TOTAL) { set_error("file %d: the rows of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
         FileTab &t = L.tab[f];
         std::memset(&t, 0, sizeof t);
         t.h.nch = nch;
@@ -253,17 +210,16 @@ inline int make_layout_from_infos(const vga_adx_file_info *const *infos, int nfi
         t.h.encryption_type = I->revision;                      // the file's own type (the keyed calls)
         L.tiny_frame = L.tiny_frame || fs < 2;
         t.image_off = at;
-        t.first_channel = (int)channels;
+        t.first_channel = first;
         t.audio_offset = I->audio_offset;
         t.copy_frames = I->frame_count;
         t.granule = granule_of((uint64_t)(at + I->audio_offset) | (nch > 1 ? (uint64_t)fs : 0));   // the rows are on 16
         cut_items(L, f, span_shape(fs, nch));
-        channels += nch;
     }
     finish_items(L);
     L.totals.channels = (int)channels;
-    L.totals.audio_bytes = audio_at + GUARD_BYTES;
-    L.totals.image_bytes = image_end + GUARD_BYTES;
+    L.totals.audio_bytes = rows.end + GUARD_BYTES;
+    L.totals.image_bytes = images.total();
     return check_item_counts(L);
 }
 
@@ -297,8 +253,6 @@ inline void describe_items(const FilesLayout &L, bool general, std::vector<vga_a
         for (int f = 0; f < nfiles; f++)
             out.push_back({VGA_ADX_FILES_FOOTER, f, f, 0, 0, L.tab[f].h.footer_pos, L.tab[f].h.file_size, L.tab[f].header_end});
 }
-
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---- the calls' argument checks
 inline int check_write(const FilesLayout &L, const void *d_audio, const void *d_history, const void *d_images)

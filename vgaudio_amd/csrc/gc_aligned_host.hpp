@@ -127,7 +127,6 @@ inline int make_layout(const vga_gc_file *files, int nfiles, size_t (*encoder_sc
     const int nch = (int)L.channel.size();
     L.out_rows.lay_out(L.out_counts.data(), nch, 0, 0);
     L.tail_rows.lay_out(L.tail_counts.data(), tail_rows, 0, 0);
-    int64_t seek_at = 0;
     for (int c = 0; c < nch; c++) {
         AlignRow &r = L.channel[c];
         r.in_pcm_off = L.in.rows.pcm_off[c];
@@ -138,16 +137,12 @@ inline int make_layout(const vga_gc_file *files, int nfiles, size_t (*encoder_sc
             r.tail_pcm_off = L.tail_rows.pcm_off[r.tail_row];
             r.tail_adpcm_off = L.tail_rows.adpcm_off[r.tail_row];
         }
-        r.seek_off = seek_at;
-        seek_at += gc::pad_to(2 * (int64_t)r.entries, 8);
         // work items: no item lies wholly behind its channel's data
         for (int at = 0; at < r.samples_to_encode; at += CHUNK_SAMPLES) L.gather_items.push_back({c, (uint32_t)at});
         cut_assemble_items(L.adpcm_items, c, (uint64_t)r.bytes_to_keep, (uint64_t)r.out_bytes);
         cut_assemble_items(L.pcm_items, c, (uint64_t)r.samples_to_keep * 2, (uint64_t)r.out_samples * 2);
     }
-    for (int c = 0; c < nch; c++) L.meta_items.push_back({c, 0});
-    for (int c = 0; c < nch; c++)
-        for (int e = CHUNK_ENTRIES; e < L.channel[c].entries; e += CHUNK_ENTRIES) L.meta_items.push_back({c, e});
+    gcf::cut_meta_items(L.channel, L.meta_items);
 
     L.totals.channels = nch;
     L.totals.aligned_channels = tail_rows;
@@ -155,7 +150,7 @@ inline int make_layout(const vga_gc_file *files, int nfiles, size_t (*encoder_sc
     L.totals.adpcm_bytes = L.in.totals.adpcm_bytes;
     L.totals.out_pcm_samples = L.out_rows.pcm_end + gc::GUARD_BYTES / 2;
     L.totals.out_adpcm_bytes = L.out_rows.adpcm_end + gc::GUARD_BYTES;
-    L.totals.seek_shorts = seek_at;
+    L.totals.seek_shorts = fileset::lay_out_seek(L.channel);
     // the workspace: the plain decode of the input batch; then, when a file needs alignment, the tail batch (PCM rows that
     // the gather fills and the second decode overwrites, ADPCM rows, the tails' coefficients and histories), guards
     // included, and the encoder's scratch

@@ -3,14 +3,14 @@
 // Header-only and free of <hip/hip_runtime.h>, so that a stand-alone host program can include it
 // (tests/host/gc_files_host_driver.cpp) as capi_gc_files.hip does; whoever includes it supplies vga::set_error.
 #pragma once
-#include "gc_host.hpp"
+#include "gc_files_layout.hpp"
 #include "../../include/vgaudio_hip/gc_files.h"
 
 namespace vga {
 namespace gcf {
 
+using fileset::aligned16;
 constexpr int DSP_HEADER = 0x60;                 // DspWriter.cs:16, one per channel
-constexpr int64_t IMAGE_GUARD_BYTES = 256;       // behind the last image
 constexpr int CHUNK_GRANULES = 1024;             // granules of one audio work item: 256 threads, four each
 constexpr int CHUNK_ENTRIES = 1024;              // seek entries of one metadata work item
 
@@ -49,24 +49,31 @@ struct FilesLayout {
     int ctx_past_file = -1;                      // first file whose loop start lies past its data (the loop context's read)
 };
 
-inline bool writer_granule16(const FileGeom &g, bool last_block)
+// 16-byte granules need the interleave and the rows of the last block on 16: blocks are `interleave` bytes apart in the row
+// and in the image alike, and a granule must not straddle two of them (the rule of nw_files and idsp_files)
+inline bool interleaved_granule16(const FileGeom &g, bool last_block)
 {
-    if (g.channels == 1) return true;                                          // one row, copied from a 16-byte boundary to one
     if (g.interleave % 16 != 0) return false;
     if (!last_block) return true;
     const uint32_t out_blocks = (g.output_size + g.interleave - 1) / g.interleave;
     return (g.output_size - (out_blocks - 1) * g.interleave) % 16 == 0;        // rows of the last block lie last_out apart
 }
+// a DSP file of one channel is one row, copied from a 16-byte boundary to one
+inline bool writer_granule16(const FileGeom &g, bool last_block) { return g.channels == 1 || interleaved_granule16(g, last_block); }
+
+// where a per-file table keeps its FileGeom: the table is one (gc_files), or holds it as `audio` (nw_files, idsp_files)
+struct Self { template <class T> T &operator()(T &t) const { return t; } };
+struct AudioOf { template <class T> auto &operator()(T &t) const { return t.audio; } };
 
 // (file, chunk) items over the audio region of every image: the region of file f is output_size * nch bytes; its full
 // blocks and its last block are cut separately (the last block's rows are packed more tightly and may allow only the
 // smaller granule), each into chunks of CHUNK_GRANULES granules.  No item lies wholly outside its image.
-// granule16(geom, last_block): may that part of the file move 16-byte granules (the container's rule)
-template <class Rule>
-inline void cut_writer_items(std::vector<FileGeom> &geom, std::vector<Item> &items, Rule granule16)
+// granule16(geom, last_block): may that part of the file move 16-byte granules (the container's rule); geom_of: Self / AudioOf
+template <class Tab, class GeomOf, class Rule>
+inline void cut_writer_items(std::vector<Tab> &tab, GeomOf geom_of, std::vector<Item> &items, Rule granule16)
 {
-    for (size_t f = 0; f < geom.size(); f++) {
-        FileGeom &g = geom[f];
+    for (size_t f = 0; f < tab.size(); f++) {
+        FileGeom &g = geom_of(tab[f]);
         const uint64_t total = (uint64_t)g.output_size * g.channels;
         if (total == 0) continue;
         const uint32_t out_blocks = (g.output_size + g.interleave - 1) / g.interleave;
@@ -81,13 +88,14 @@ inline void cut_writer_items(std::vector<FileGeom> &geom, std::vector<Item> &ite
         }
     }
 }
-inline void cut_writer_items(FilesLayout &L) { cut_writer_items(L.geom, L.audio_items, writer_granule16); }
+inline void cut_writer_items(FilesLayout &L) { cut_writer_items(L.geom, Self(), L.audio_items, writer_granule16); }
 
 // (channel, chunk) items over the rows the reader fills: output_size bytes each
-inline void cut_reader_items(const std::vector<FileGeom> &geom, std::vector<Item> &items)
+template <class Tab, class GeomOf>
+inline void cut_reader_items(const std::vector<Tab> &tab, GeomOf geom_of, std::vector<Item> &items)
 {
-    for (size_t f = 0; f < geom.size(); f++) {
-        const FileGeom &g = geom[f];
+    for (size_t f = 0; f < tab.size(); f++) {
+        const FileGeom &g = geom_of(tab[f]);
         const bool g16 = g.granule16 & 1;
         const uint64_t step = (uint64_t)CHUNK_GRANULES * (g16 ? 16 : 8);
         for (int i = 0; i < g.channels; i++)
@@ -95,47 +103,36 @@ inline void cut_reader_items(const std::vector<FileGeom> &geom, std::vector<Item
                 items.push_back({g.first_channel + i, (uint32_t)(at >> 3) | (g16 ? 0x80000000u : 0u)});
     }
 }
-inline void cut_reader_items(FilesLayout &L) { cut_reader_items(L.geom, L.audio_items); }
+inline void cut_reader_items(FilesLayout &L) { cut_reader_items(L.geom, Self(), L.audio_items); }
 
-inline void cut_meta_items(FilesLayout &L)
+// chunk 0 of every channel first, then the other chunks
+template <class Row> inline void cut_meta_items(const std::vector<Row> &channel, std::vector<MetaItem> &items)
 {
-    const int nch = (int)L.channel.size();
-    for (int c = 0; c < nch; c++) L.meta_items.push_back({c, 0});
+    const int nch = (int)channel.size();
+    for (int c = 0; c < nch; c++) items.push_back({c, 0});
     for (int c = 0; c < nch; c++)
-        for (int e = CHUNK_ENTRIES; e < L.channel[c].entries; e += CHUNK_ENTRIES) L.meta_items.push_back({c, e});
+        for (int e = CHUNK_ENTRIES; e < channel[c].entries; e += CHUNK_ENTRIES) items.push_back({c, e});
 }
 
 // rows, seek offsets and totals once counts / channel[].entries are known
 inline void lay_out_rows(FilesLayout &L)
 {
-    const int nch = (int)L.counts.size();
-    L.rows.lay_out(L.counts.data(), nch, 0, 0);
-    int64_t seek_at = 0;
-    for (int c = 0; c < nch; c++) {
-        ChannelRow &r = L.channel[c];
-        r.pcm_off = L.rows.pcm_off[c];
-        r.adpcm_off = L.rows.adpcm_off[c];
-        r.seek_off = seek_at;
-        seek_at += gc::pad_to(2 * (int64_t)r.entries, 8);
-    }
-    L.totals.channels = nch;
-    L.totals.pcm_samples = L.rows.pcm_end + gc::GUARD_BYTES / 2;
-    L.totals.adpcm_bytes = L.rows.adpcm_end + gc::GUARD_BYTES;
-    L.totals.seek_shorts = seek_at;
+    fileset::lay_out_rows(L.rows, L.counts, L.channel, L.totals);
+    L.totals.seek_shorts = fileset::lay_out_seek(L.channel);
     L.totals.build_workspace_bytes = L.totals.files > 0 ? (size_t)L.totals.pcm_samples * 2 : 0;
 }
 
 inline int make_layout(const vga_gc_file *files, int nfiles, const vga_dsp_file_config *dsp, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !files) { set_error("null files"); return VGA_ERR_ARGUMENT; }
+    if (int rc = fileset::check_files(nfiles, files != nullptr, "files")) return rc;
     L = FilesLayout();
     L.has_dsp = dsp != nullptr;
     L.totals.files = nfiles;
     L.first_channel.resize(nfiles);
     L.image_off.resize(nfiles);
     if (dsp) L.geom.resize(nfiles);
-    int64_t channels = 0, image_at = 0;
+    int64_t channels = 0;
+    fileset::Images images;
     for (int f = 0; f < nfiles; f++) {
         const vga_gc_file &F = files[f];
         const vga_gcadpcm_channel_params &p = F.channel;
@@ -157,8 +154,9 @@ inline int make_layout(const vga_gc_file *files, int nfiles, const vga_dsp_file_
                       "through vga_gcadpcm_build_channels_device", f, p.loop_start, p.loop_alignment_multiple);
             return VGA_ERR_INVALID_OP;
         }
-        if (channels + F.channels > 0x7FFFFFFF) { set_error("file %d: more than 2^31 channels", f); return VGA_ERR_ARGUMENT; }
-        L.first_channel[f] = (int)channels;
+        const int first = (int)channels;
+        if (int rc = fileset::count_rows(f, F.channels, channels, "channels")) return rc;
+        L.first_channel[f] = first;
         const int row_bytes = gc::sample_count_to_byte_count(p.sample_count);
         const bool ctx_past = p.loop_start != 0 && p.loop_start / 14 * 8 >= row_bytes;      // (gc::plan_channels)
         if (ctx_past && L.ctx_past_file < 0) L.ctx_past_file = f;
@@ -186,8 +184,8 @@ inline int make_layout(const vga_gc_file *files, int nfiles, const vga_dsp_file_
             }
             FileGeom &g = L.geom[f];
             g = FileGeom();
-            g.image_off = image_at;
-            g.first_channel = (int)channels;
+            g.image_off = L.image_off[f] = images.place(D.file_size).at;
+            g.first_channel = first;
             g.channels = F.channels;
             g.sample_count = D.sample_count;
             g.nibble_count = gc::sample_count_to_nibble_count(D.sample_count);
@@ -201,29 +199,26 @@ inline int make_layout(const vga_gc_file *files, int nfiles, const vga_dsp_file_
             g.output_size = (uint32_t)D.audio_data_size;                        // (one channel: mono_bytes)
             // one channel: a plain copy, one block (container::launch_interleave)
             g.interleave = F.channels == 1 ? (uint32_t)gc::pad_to(std::max(row_bytes, 1), 16) : (uint32_t)D.bytes_per_interleave;
-            L.image_off[f] = image_at;
-            image_at += gc::pad_to(D.file_size, 16);
         }
-        channels += F.channels;
     }
     lay_out_rows(L);
-    L.totals.image_bytes = dsp ? image_at + IMAGE_GUARD_BYTES : 0;
+    L.totals.image_bytes = dsp ? images.total() : 0;
     if (dsp) cut_writer_items(L);
-    cut_meta_items(L);
+    cut_meta_items(L.channel, L.meta_items);
     return VGA_OK;
 }
 
 inline int make_layout_from_dsp(const vga_dsp_info *const *infos, int nfiles, const int64_t *image_offsets, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !infos) { set_error("null infos"); return VGA_ERR_ARGUMENT; }
+    if (int rc = fileset::check_files(nfiles, infos != nullptr, "infos")) return rc;
     L = FilesLayout();
     L.from_dsp = true;
     L.totals.files = nfiles;
     L.first_channel.resize(nfiles);
     L.image_off.resize(nfiles);
     L.geom.resize(nfiles);
-    int64_t channels = 0, image_at = 0, image_end = 0;
+    int64_t channels = 0;
+    fileset::Images images;
     for (int f = 0; f < nfiles; f++) {
         const vga_dsp_info *I = infos[f];
         if (!I) { set_error("file %d: null info", f); return VGA_ERR_ARGUMENT; }
@@ -236,14 +231,13 @@ inline int make_layout_from_dsp(const vga_dsp_info *const *infos, int nfiles, co
             set_error("file %d: info does not describe a DSP file", f);
             return VGA_ERR_ARGUMENT;
         }
-        const int64_t at = image_offsets ? image_offsets[f] : image_at;
+        // (an image past 2 GiB or an offset past 2^62 is not refused here)
+        const int64_t at = images.place((int64_t)I->audio_offset + I->data_length, image_offsets ? image_offsets + f : nullptr).at;
         if (at < 0 || at % 8) { set_error("file %d: image offset %lld is not a multiple of 8", f, (long long)at); return VGA_ERR_ARGUMENT; }
-        if (channels + nch > 0x7FFFFFFF) { set_error("file %d: more than 2^31 channels", f); return VGA_ERR_ARGUMENT; }
-        const int64_t size = (int64_t)I->audio_offset + I->data_length;
-        L.first_channel[f] = (int)channels;
+        const int first = (int)channels;
+        if (int rc = fileset::count_rows(f, nch, channels, "channels")) return rc;
+        L.first_channel[f] = first;
         L.image_off[f] = at;
-        image_at = gc::pad_to(at + size, 16);
-        image_end = std::max(image_end, image_at);
         for (int i = 0; i < nch; i++) {
             L.counts.push_back(I->sample_count);
             L.channel.push_back({0, 0, 0, f, 0, 0, 0});
@@ -251,7 +245,7 @@ inline int make_layout_from_dsp(const vga_dsp_info *const *infos, int nfiles, co
         FileGeom &g = L.geom[f];
         g = FileGeom();
         g.image_off = at;
-        g.first_channel = (int)channels;
+        g.first_channel = first;
         g.channels = nch;
         g.sample_count = I->sample_count;
         g.nibble_count = I->nibble_count;
@@ -266,18 +260,15 @@ inline int make_layout_from_dsp(const vga_dsp_info *const *infos, int nfiles, co
         g.input_size = nch == 1 ? g.output_size : (uint32_t)(I->data_length / nch);
         g.interleave = nch == 1 ? (uint32_t)gc::pad_to(std::max(I->adpcm_bytes, 1), 16) : (uint32_t)I->interleave_size;
         g.granule16 = (at % 16 == 0 && (nch == 1 || (g.interleave % 16 == 0 && g.input_size % 16 == 0))) ? 1u : 0u;
-        channels += nch;
     }
     lay_out_rows(L);
-    L.totals.image_bytes = image_end + IMAGE_GUARD_BYTES;
+    L.totals.image_bytes = images.total();
     cut_reader_items(L);
-    cut_meta_items(L);
+    cut_meta_items(L.channel, L.meta_items);
     return VGA_OK;
 }
 
 // ---- the calls' argument checks
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 // need_decode / workspace of vga_gcadpcm_build_channels_device_v
 inline bool build_needs_decode(const FilesLayout &L, bool want_pcm, bool want_seek, bool want_ctx)
 {

@@ -6,26 +6,18 @@
 // (tests/host/hca_files_host_driver.cpp) as capi_hca_files.hip does; whoever includes it supplies vga::set_error,
 // vga::last_error and the two per-file functions.
 #pragma once
+#include "files_layout.hpp"
 #include "../../include/vgaudio_hip/hca_files.h"
 
-#include <algorithm>
-#include <cstdint>
-#include <cstring>
-#include <string>
-#include <vector>
-
 namespace vga {
-
-void set_error(const char *fmt, ...);            // (common.hpp)
-const char *last_error();                        // the message of the last set_error on this thread
-
 namespace hcaf {
 
+using fileset::name_file;
+using fileset::pad_to;
+using fileset::MAX_TOTAL;
 constexpr int64_t SLACK_BYTES = 8;               // behind the last stream (hca_ragged.h's)
-constexpr int64_t GUARD_BYTES = 256;             // behind the last image
 constexpr int SPAN_BYTES = 16384;                // the whole frames of one work item, at most (a frame beyond it goes alone)
 constexpr int MAX_SPAN_FRAME = 4096;             // the largest frame of the span form: at least four frames per span
-constexpr int64_t MAX_TOTAL = (int64_t)1 << 62;
 
 // What the kernels need of one file (a device table, one per file).  src / dst are byte offsets into the call's source and
 // destination buffers: d_frames -> d_images + header for a write, d_images -> d_frames for a read.
@@ -55,16 +47,6 @@ struct FilesLayout {
     int span_files = 0, general_files = 0, moving_files = 0;   // of items[0]; files that move frame bytes at all
 };
 
-inline int64_t pad_to(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
-// "file <f>: " in front of the message the per-file code left
-inline int name_file(int f, int rc)
-{
-    const std::string msg = last_error();
-    set_error("file %d: %s", f, msg.c_str());
-    return rc;
-}
-
 inline bool span_shape(int frame_size) { return frame_size <= MAX_SPAN_FRAME; }
 inline int item_frames_of(int frame_size) { return frame_size > 0 ? std::max(1, SPAN_BYTES / frame_size) : 1; }
 
@@ -89,38 +71,22 @@ inline int check_key(int f, int key, int frame_size, int frame_count, int ntable
 inline int place_streams(FilesLayout &L, const int64_t *frame_offsets)
 {
     const int nfiles = L.totals.files;
-    int64_t at = 0, end = 0;
+    fileset::Rows streams;
     L.frame_off.resize(nfiles);
     for (int f = 0; f < nfiles; f++) {
-        const int64_t bytes = L.stream_bytes[f];
-        if (frame_offsets) {
-            const int64_t o = frame_offsets[f];
-            if (o < 0 || o % 4) { set_error("file %d: frame offset %lld is negative or no multiple of 4", f, (long long)o); return VGA_ERR_ARGUMENT; }
-            if (o > MAX_TOTAL) { set_error("file %d: the frames of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
-            L.frame_off[f] = o;
-            if (bytes > 0) end = std::max(end, o + pad_to(bytes, 4));
-        } else {
-            L.frame_off[f] = at;
-            at += pad_to(bytes, 4);
-            if (at > MAX_TOTAL) { set_error("file %d: the frames of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
-            end = at;
-        }
+        const int64_t room = pad_to(L.stream_bytes[f], 4);
+        const fileset::Placed s = streams.place(room, room, MAX_TOTAL, frame_offsets ? frame_offsets + f : nullptr);
+        if (s.at < 0 || s.at % 4) { set_error("file %d: frame offset %lld is negative or no multiple of 4", f, (long long)s.at); return VGA_ERR_ARGUMENT; }
+        if (s.verdict) { set_error("file %d: the frames of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
+        L.frame_off[f] = s.at;
     }
-    if (frame_offsets) {
-        std::vector<int> order;
-        for (int f = 0; f < nfiles; f++)
-            if (L.stream_bytes[f] > 0) order.push_back(f);
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return L.frame_off[a] != L.frame_off[b] ? L.frame_off[a] < L.frame_off[b] : a < b; });
-        for (size_t i = 1; i < order.size(); i++) {
-            const int a = order[i - 1], b = order[i];
-            if (L.frame_off[a] + pad_to(L.stream_bytes[a], 4) > L.frame_off[b]) {
-                set_error("file %d: stream %d (offset %lld, %lld bytes) overlaps stream %d (offset %lld)", std::max(a, b), a,
-                          (long long)L.frame_off[a], (long long)L.stream_bytes[a], b, (long long)L.frame_off[b]);
-                return VGA_ERR_ARGUMENT;
-            }
-        }
+    int a, b;                                     // a stream takes its bytes rounded up to 4
+    if (frame_offsets && fileset::find_overlap(nfiles, [&](int f) { return L.frame_off[f]; }, [&](int f) { return pad_to(L.stream_bytes[f], 4); }, a, b)) {
+        set_error("file %d: stream %d (offset %lld, %lld bytes) overlaps stream %d (offset %lld)", std::max(a, b), a,
+                  (long long)L.frame_off[a], (long long)L.stream_bytes[a], b, (long long)L.frame_off[b]);
+        return VGA_ERR_ARGUMENT;
     }
-    L.totals.frame_bytes = end + SLACK_BYTES;
+    L.totals.frame_bytes = streams.end + SLACK_BYTES;
     return VGA_OK;
 }
 
@@ -143,8 +109,7 @@ inline int cut_items(FilesLayout &L)
     }
     L.span_items = (int)L.items[0].size();
     L.items[0].insert(L.items[0].end(), own_general.begin(), own_general.end());
-    if (L.items[1].size() > 0x7FFFFFFF) { set_error("the set has more than 2^31 work items"); return VGA_ERR_OUT_OF_RANGE; }
-    return VGA_OK;
+    return fileset::check_item_count(L.items[1].size());
 }
 
 inline void keep_tables(FilesLayout &L, const uint8_t *tables, int ntables)
@@ -156,8 +121,7 @@ inline void keep_tables(FilesLayout &L, const uint8_t *tables, int ntables)
 inline int make_layout(const vga_hca_file *files, int nfiles, const int64_t *frame_offsets, const uint8_t *tables, int ntables, bool with_keys,
                        FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !files) { set_error("null files"); return VGA_ERR_ARGUMENT; }
+    if (int rc = fileset::check_files(nfiles, files != nullptr, "files")) return rc;
     if (with_keys)
         if (int rc = check_tables(tables, ntables)) return rc;
     L = FilesLayout();
@@ -166,7 +130,7 @@ inline int make_layout(const vga_hca_file *files, int nfiles, const int64_t *fra
     L.image_size.resize(nfiles);
     L.stream_bytes.resize(nfiles);
     L.tab.resize(nfiles);
-    int64_t image_at = 0;
+    fileset::Images images;
     for (int f = 0; f < nfiles; f++) {
         const vga_hca_file &F = files[f];
         const vga_hca_info &H = F.hca;
@@ -179,6 +143,8 @@ inline int make_layout(const vga_hca_file *files, int nfiles, const int64_t *fra
         L.headers.resize(header_at + (size_t)pad_to(std::min(std::max(H.header_size, 0), 0x7FFF), 16));
         if (int rc = vga_hca_file_header(&H, F.comment, F.volume, F.encryption_type, F.encrypted_ids, L.headers.data() + header_at)) return name_file(f, rc);
         if (int rc = check_key(f, F.key, H.frame_size, H.frame_count, ntables, with_keys)) return rc;
+        const fileset::Placed image = images.place(size);
+        const int64_t image_at = image.at;
         L.stream_bytes[f] = (int64_t)H.frame_size * H.frame_count;
         L.totals.total_frames += H.frame_count;
         L.image_off[f] = image_at;
@@ -190,12 +156,11 @@ inline int make_layout(const vga_hca_file *files, int nfiles, const int64_t *fra
         t.key = F.key;
         t.header_off = (int)header_at;
         t.header_size = H.header_size;
-        image_at += pad_to(size, 16);
-        if (image_at > MAX_TOTAL || header_at > 0x7FFFFFFF) { set_error("file %d: the images of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
+        if ((image.verdict & fileset::TOTAL_PAST_MAX) || header_at > 0x7FFFFFFF) { set_error("file %d: the images of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
     }
     if (int rc = place_streams(L, frame_offsets)) return rc;
     for (int f = 0; f < nfiles; f++) L.tab[f].src_off = L.frame_off[f];
-    L.totals.image_bytes = image_at + GUARD_BYTES;
+    L.totals.image_bytes = images.total();
     if (with_keys) keep_tables(L, tables, ntables);
     return cut_items(L);
 }
@@ -204,8 +169,7 @@ inline int make_layout(const vga_hca_file *files, int nfiles, const int64_t *fra
 inline int make_layout_from_infos(const vga_hca_file_info *const *infos, int nfiles, const int64_t *image_offsets, const int *keys,
                                   const uint8_t *tables, int ntables, bool with_keys, const int64_t *frame_offsets, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !infos) { set_error("null infos"); return VGA_ERR_ARGUMENT; }
+    if (int rc = fileset::check_files(nfiles, infos != nullptr, "infos")) return rc;
     if (with_keys)
         if (int rc = check_tables(tables, ntables)) return rc;
     L = FilesLayout();
@@ -217,7 +181,7 @@ inline int make_layout_from_infos(const vga_hca_file_info *const *infos, int nfi
     L.image_size.resize(nfiles);
     L.stream_bytes.resize(nfiles);
     L.tab.resize(nfiles);
-    int64_t image_at = 0, image_end = 0;
+    fileset::Images images;
     for (int f = 0; f < nfiles; f++) {
         const vga_hca_file_info *I = infos[f];
         if (!I) { set_error("file %d: null info", f); return VGA_ERR_ARGUMENT; }
@@ -227,10 +191,11 @@ inline int make_layout_from_infos(const vga_hca_file_info *const *infos, int nfi
             set_error("file %d: info does not describe an HCA file", f);
             return VGA_ERR_ARGUMENT;
         }
-        const int64_t at = image_offsets ? image_offsets[f] : image_at;
-        if (at < 0) { set_error("file %d: negative image offset %lld", f, (long long)at); return VGA_ERR_ARGUMENT; }
         const int64_t bytes = (int64_t)H.frame_size * H.frame_count, size = I->frames_offset + bytes;
-        if (size > 0x7FFFFFFF || at > MAX_TOTAL) { set_error("file %d: image past 2 GiB or offset past 2^62", f); return VGA_ERR_OUT_OF_RANGE; }
+        const fileset::Placed image = images.place(size, image_offsets ? image_offsets + f : nullptr);
+        const int64_t at = image.at;
+        if (image.verdict & fileset::OFFSET_NEGATIVE) { set_error("file %d: negative image offset %lld", f, (long long)at); return VGA_ERR_ARGUMENT; }
+        if (image.verdict & (fileset::IMAGE_PAST_2GIB | fileset::OFFSET_PAST_MAX)) { set_error("file %d: image past 2 GiB or offset past 2^62", f); return VGA_ERR_OUT_OF_RANGE; }
         const int key = keys ? keys[f] : -1;
         if (int rc = check_key(f, key, H.frame_size, H.frame_count, ntables, with_keys)) return rc;
         L.stream_bytes[f] = bytes;
@@ -239,8 +204,6 @@ inline int make_layout_from_infos(const vga_hca_file_info *const *infos, int nfi
         L.image_size[f] = (int)size;
         L.hca[f] = H;
         L.encryption_type[f] = I->encryption_type;
-        image_at = pad_to(at + size, 16);
-        image_end = std::max(image_end, image_at);
         FileTab &t = L.tab[f];
         std::memset(&t, 0, sizeof t);
         t.image_off = at;
@@ -251,7 +214,7 @@ inline int make_layout_from_infos(const vga_hca_file_info *const *infos, int nfi
     }
     if (int rc = place_streams(L, frame_offsets)) return rc;
     for (int f = 0; f < nfiles; f++) L.tab[f].dst_off = L.frame_off[f];
-    L.totals.image_bytes = image_end + GUARD_BYTES;
+    L.totals.image_bytes = images.total();
     if (with_keys) keep_tables(L, tables, ntables);
     return cut_items(L);
 }

@@ -9,16 +9,10 @@
 #include "gc_stream_host.hpp"
 #include "../../include/vgaudio_hip_files/hps_files.h"
 
-#include <string>
-
 namespace vga {
-
-const char *last_error();                        // the message of the last set_error on this thread
-
 namespace hpf {
 
-constexpr int64_t IMAGE_GUARD_BYTES = 256;       // behind the last image
-constexpr int64_t MAX_TOTAL = (int64_t)1 << 62;
+using fileset::name_file;
 constexpr uint32_t CHUNK_BYTES16 = 16384;        // of one work item of 16-byte granules: 256 threads, four granules each
 constexpr uint32_t CHUNK_BYTES1 = 1024;          // of one work item of the general (byte) form of the gather
 
@@ -40,8 +34,7 @@ static_assert(sizeof(Block) == 32, "block table entry");
 struct Row { int64_t pcm_off, adpcm_off; };      // of the ragged batch
 // a work item: bytes [start, end) of block `block`'s body (write) or of its audio of row `row` (read)
 struct Item { int block, row; uint32_t start, end; };
-// the reader's per-channel arrays as the object holds them: coefficients, gain, start and loop context
-struct ChannelMeta { int16_t v[23]; };
+struct ChannelMeta { int16_t v[23]; };           // the reader's per-channel arrays as the object holds them (fileset::fill_meta)
 
 struct FilesLayout {
     vga_hps_files_totals totals = {};
@@ -61,24 +54,13 @@ struct FilesLayout {
 
 inline vga_hps_params params_of(const vga_hps_file &F) { return {F.sample_rate, F.sample_count, F.looping, F.loop_start, F.loop_end}; }
 
-// "file <f>: " in front of the message the per-file code left
-inline int name_file(int f, int rc)
+// a fresh layout with its per-file arrays
+inline void start_layout(FilesLayout &L, int nfiles, bool from_infos)
 {
-    const std::string msg = last_error();
-    set_error("file %d: %s", f, msg.c_str());
-    return rc;
-}
-
-// rows and the sizes of the row buffers once counts are known
-inline void lay_out_rows(FilesLayout &L)
-{
-    const int nch = (int)L.counts.size();
-    L.rows.lay_out(L.counts.data(), nch, 0, 0);
-    L.channel.resize(nch);
-    for (int c = 0; c < nch; c++) L.channel[c] = {L.rows.pcm_off[c], L.rows.adpcm_off[c]};
-    L.totals.channels = nch;
-    L.totals.pcm_samples = L.rows.pcm_end + gc::GUARD_BYTES / 2;
-    L.totals.adpcm_bytes = L.rows.adpcm_end + gc::GUARD_BYTES;
+    fileset::start_layout(L, nfiles, from_infos);
+    L.sample_rate.resize(nfiles);
+    L.nch.resize(nfiles);
+    L.first_block.resize(nfiles);
 }
 
 inline int check_counts(const FilesLayout &L, int f)
@@ -92,19 +74,11 @@ inline int check_counts(const FilesLayout &L, int f)
 
 inline int make_layout(const vga_hps_file *files, int nfiles, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !files) { set_error("null files"); return VGA_ERR_ARGUMENT; }
-    L = FilesLayout();
-    L.totals.files = nfiles;
+    if (int rc = fileset::check_files(nfiles, files != nullptr, "files")) return rc;
+    start_layout(L, nfiles, false);
     L.layout.resize(nfiles);
-    L.sample_rate.resize(nfiles);
-    L.nch.resize(nfiles);
-    L.first_channel.resize(nfiles);
-    L.image_off.resize(nfiles);
-    L.first_block.resize(nfiles);
-    L.image_size.resize(nfiles);
-    L.tab.resize(nfiles);
-    int64_t channels = 0, image_at = 0;
+    int64_t channels = 0;
+    fileset::Images images;
     std::vector<vga_hps_block> map;
     for (int f = 0; f < nfiles; f++) {
         const vga_hps_file &F = files[f];
@@ -119,13 +93,15 @@ inline int make_layout(const vga_hps_file *files, int nfiles, FilesLayout &L)
             set_error("file %d: internal: the block map reaches past the row", f);
             return VGA_ERR_INVALID_OP;
         }
-        if (channels + F.channels > 0x7FFFFFFF) { set_error("file %d: more than 2^31 channels", f); return VGA_ERR_ARGUMENT; }
+        const int first = (int)channels;
+        if (int rc = fileset::count_rows(f, F.channels, channels, "channels")) return rc;
+        const fileset::Placed image = images.place(N.file_size);
         L.sample_rate[f] = F.sample_rate;
         L.nch[f] = F.channels;
-        L.first_channel[f] = (int)channels;
+        L.first_channel[f] = first;
         L.first_block[f] = (int64_t)L.blocks.size();
         for (int i = 0; i < F.channels; i++) L.counts.push_back(cl.sample_count_aligned);
-        L.tab[f] = {image_at, (int)channels, F.channels, F.sample_rate, gc::sample_to_nibble(N.sample_count - 1), N.header_size,
+        L.tab[f] = {image.at, first, F.channels, F.sample_rate, gc::sample_to_nibble(N.sample_count - 1), N.header_size,
                     N.block_header_size};
         for (const vga_hps_block &b : map) {
             Block B;
@@ -136,14 +112,12 @@ inline int make_layout(const vga_hps_file *files, int nfiles, FilesLayout &L)
                 L.items.push_back({at, 0, s, std::min(s + CHUNK_BYTES16, (uint32_t)b.written_size)});
         }
         if (int rc = check_counts(L, f)) return rc;
-        L.image_off[f] = image_at;
+        L.image_off[f] = image.at;
         L.image_size[f] = N.file_size;
-        image_at += gc::pad_to(N.file_size, 16);
-        if (image_at > MAX_TOTAL) { set_error("file %d: the images of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
-        channels += F.channels;
+        if (image.verdict & fileset::TOTAL_PAST_MAX) { set_error("file %d: the images of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
     }
-    lay_out_rows(L);
-    L.totals.image_bytes = image_at + IMAGE_GUARD_BYTES;
+    fileset::lay_out_rows(L.rows, L.counts, L.channel, L.totals);
+    L.totals.image_bytes = images.total();
     L.totals.blocks = (int64_t)L.blocks.size();
     return VGA_OK;
 }
@@ -152,19 +126,10 @@ inline int make_layout(const vga_hps_file *files, int nfiles, FilesLayout &L)
 inline int make_layout_from_infos(const vga_hps_info *const *infos, const vga_hps_block_info *const *blocks_per_file, int nfiles,
                                   const int64_t *image_offsets, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && (!infos || !blocks_per_file)) { set_error("null infos / block tables"); return VGA_ERR_ARGUMENT; }
-    L = FilesLayout();
-    L.from_infos = true;
-    L.totals.files = nfiles;
-    L.sample_rate.resize(nfiles);
-    L.nch.resize(nfiles);
-    L.first_channel.resize(nfiles);
-    L.image_off.resize(nfiles);
-    L.first_block.resize(nfiles);
-    L.image_size.resize(nfiles);
-    L.tab.resize(nfiles);
-    int64_t channels = 0, image_at = 0, image_end = 0;
+    if (int rc = fileset::check_files(nfiles, infos && blocks_per_file, "infos / block tables")) return rc;
+    start_layout(L, nfiles, true);
+    int64_t channels = 0;
+    fileset::Images images;
     for (int f = 0; f < nfiles; f++) {
         const vga_hps_info *I = infos[f];
         const vga_hps_block_info *blocks = blocks_per_file[f];
@@ -176,16 +141,18 @@ inline int make_layout_from_infos(const vga_hps_info *const *infos, const vga_hp
             set_error("file %d: the info's rows of %d bytes are not those of its %d samples", f, I->adpcm_bytes, I->sample_count);
             return VGA_ERR_ARGUMENT;
         }
-        const int64_t at = image_offsets ? image_offsets[f] : image_at;
+        // the image's size is known once its blocks are: it is placed behind them, where it lies is needed in front
+        const int64_t at = image_offsets ? image_offsets[f] : images.at;
         if (at < 0) { set_error("file %d: negative image offset %lld", f, (long long)at); return VGA_ERR_ARGUMENT; }
-        if (at > MAX_TOTAL) { set_error("file %d: image offset past 2^62", f); return VGA_ERR_OUT_OF_RANGE; }
-        if (channels + nch > 0x7FFFFFFF) { set_error("file %d: more than 2^31 channels", f); return VGA_ERR_ARGUMENT; }
+        if (at > fileset::MAX_TOTAL) { set_error("file %d: image offset past 2^62", f); return VGA_ERR_OUT_OF_RANGE; }
+        const int first = (int)channels;
+        if (int rc = fileset::count_rows(f, nch, channels, "channels")) return rc;
         L.sample_rate[f] = I->sample_rate;
         L.nch[f] = nch;
-        L.first_channel[f] = (int)channels;
+        L.first_channel[f] = first;
         L.first_block[f] = (int64_t)L.blocks.size();
         L.image_off[f] = at;
-        L.tab[f] = {at, (int)channels, nch, I->sample_rate, 0, 0, 0};
+        L.tab[f] = {at, first, nch, I->sample_rate, 0, 0, 0};
         int64_t size = 0;
         for (int i = 0; i < I->block_count; i++) {
             const vga_hps_block_info &b = blocks[i];
@@ -196,32 +163,24 @@ inline int make_layout_from_infos(const vga_hps_info *const *infos, const vga_hp
             size = std::max({size, (int64_t)b.audio_offset + b.size, (int64_t)b.audio_offset + (int64_t)stride * (nch - 1) + b.audio_bytes});
             Block B;
             const uint64_t geometry = (uint64_t)(at + b.audio_offset) | (uint64_t)stride | (uint64_t)b.out_offset;
-            B.r = {at + b.audio_offset, stride, b.audio_bytes, b.out_offset, (int)channels, f, geometry % 16 == 0 ? 16 : 1};
+            B.r = {at + b.audio_offset, stride, b.audio_bytes, b.out_offset, first, f, geometry % 16 == 0 ? 16 : 1};
             const int blk = (int)L.blocks.size();
             L.blocks.push_back(B);
             const uint32_t step = B.r.granule == 16 ? CHUNK_BYTES16 : CHUNK_BYTES1;
             for (int c = 0; c < nch; c++)
                 for (uint32_t s = 0; s < (uint32_t)b.audio_bytes; s += step)
-                    L.items.push_back({blk, (int)channels + c, s, std::min(s + step, (uint32_t)b.audio_bytes)});
+                    L.items.push_back({blk, first + c, s, std::min(s + step, (uint32_t)b.audio_bytes)});
         }
         if (int rc = check_counts(L, f)) return rc;
-        if (size > 0x7FFFFFFF) { set_error("file %d: image past 2 GiB", f); return VGA_ERR_OUT_OF_RANGE; }
+        if (images.place(size, &at).verdict & fileset::IMAGE_PAST_2GIB) { set_error("file %d: image past 2 GiB", f); return VGA_ERR_OUT_OF_RANGE; }
         L.image_size[f] = (int)size;
-        image_at = gc::pad_to(at + size, 16);
-        image_end = std::max(image_end, image_at);
         for (int c = 0; c < nch; c++) {
             L.counts.push_back(I->sample_count);
-            ChannelMeta m;
-            std::memcpy(m.v, I->coefs[c], 32);
-            m.v[16] = I->gain[c];
-            std::memcpy(m.v + 17, I->start_context[c], 6);
-            std::memcpy(m.v + 20, I->loop_context[c], 6);
-            L.meta.push_back(m);
+            L.meta.push_back(fileset::fill_meta<ChannelMeta>(*I, c));
         }
-        channels += nch;
     }
-    lay_out_rows(L);
-    L.totals.image_bytes = image_end + IMAGE_GUARD_BYTES;
+    fileset::lay_out_rows(L.rows, L.counts, L.channel, L.totals);
+    L.totals.image_bytes = images.total();
     L.totals.blocks = (int64_t)L.blocks.size();
     return VGA_OK;
 }
@@ -247,14 +206,9 @@ inline void regions_of(const FilesLayout &L, std::vector<vga_hps_files_region> &
 }
 inline int copy_regions(const FilesLayout &L, vga_hps_files_region *regions_out, int64_t capacity, int64_t *count_out)
 {
-    if (!count_out) { set_error("null count"); return VGA_ERR_ARGUMENT; }
     std::vector<vga_hps_files_region> r;
     regions_of(L, r);
-    *count_out = (int64_t)r.size();
-    if (!regions_out) return VGA_OK;
-    if ((int64_t)r.size() > capacity) { set_error("%lld regions: capacity %lld", (long long)r.size(), (long long)capacity); return VGA_ERR_ARGUMENT; }
-    std::copy(r.begin(), r.end(), regions_out);
-    return VGA_OK;
+    return fileset::copy_regions(r, regions_out, capacity, count_out);
 }
 
 // ---- the calls' argument checks

@@ -9,16 +9,10 @@
 #include "gc_stream_host.hpp"
 #include "../../include/vgaudio_hip_files/idsp_files.h"
 
-#include <string>
-
 namespace vga {
-
-const char *last_error();                        // the message of the last set_error on this thread
-
 namespace idf {
 
-constexpr int64_t IMAGE_GUARD_BYTES = 256;       // behind the last image
-constexpr int64_t MAX_TOTAL = (int64_t)1 << 62;
+using fileset::name_file;
 constexpr uint32_t GRANULE1 = 4;                 // FileGeom::granule16 of a file read byte by byte (bits 0, 1: gc_files_host.hpp's)
 constexpr int CHUNK_BYTES1 = gcf::CHUNK_GRANULES;   // bytes of one work item of that form
 
@@ -38,8 +32,7 @@ struct FileTab {
 };
 using ChannelRow = gcf::ChannelRow;              // adpcm_off, file (pcm_off of the same batch)
 using Item = gcf::Item;                          // as gc_files_host.hpp: x = file (writer) or row (reader), y = first byte / 8, bit 31: 16 bytes
-// the reader's per-channel arrays as the object holds them: coefficients, gain, start and loop context
-struct ChannelMeta { int16_t v[23]; };
+struct ChannelMeta { int16_t v[23]; };           // the reader's per-channel arrays as the object holds them (fileset::fill_meta)
 
 struct FilesLayout {
     vga_idsp_files_totals totals = {};
@@ -56,66 +49,30 @@ struct FilesLayout {
     std::vector<Item> audio_items;
 };
 
-// 16-byte granules need the interleave and the rows of the last block on 16: blocks are `interleave` bytes apart in the row,
-// and a granule must not straddle two of them (nw_files_host.hpp's rule; an IDSP header is a multiple of 0x20, so the audio
-// region starts on 16 whenever the image does)
-inline bool writer_granule16(const gcf::FileGeom &g, bool last_block)
-{
-    if (g.interleave % 16 != 0) return false;
-    if (!last_block) return true;
-    const uint32_t out_blocks = (g.output_size + g.interleave - 1) / g.interleave;
-    return (g.output_size - (out_blocks - 1) * g.interleave) % 16 == 0;
-}
-
 inline vga_idsp_params params_of(const vga_idsp_file &F, const vga_idsp_file_config &c)
 {
     return {F.sample_rate, F.sample_count, F.looping, F.loop_start, F.loop_end, c.block_size, c.trim_file};
 }
 
-// "file <f>: " in front of the message the per-file code left
-inline int name_file(int f, int rc)
-{
-    const std::string msg = last_error();
-    set_error("file %d: %s", f, msg.c_str());
-    return rc;
-}
-
-// rows and the sizes of the row buffers once counts are known
-inline void lay_out_rows(FilesLayout &L)
-{
-    const int nch = (int)L.counts.size();
-    L.rows.lay_out(L.counts.data(), nch, 0, 0);
-    for (int c = 0; c < nch; c++) {
-        L.channel[c].pcm_off = L.rows.pcm_off[c];
-        L.channel[c].adpcm_off = L.rows.adpcm_off[c];
-    }
-    L.totals.channels = nch;
-    L.totals.pcm_samples = L.rows.pcm_end + gc::GUARD_BYTES / 2;
-    L.totals.adpcm_bytes = L.rows.adpcm_end + gc::GUARD_BYTES;
-}
-
 inline int make_layout(const vga_idsp_file *files, int nfiles, const vga_idsp_file_config *config, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !files) { set_error("null files"); return VGA_ERR_ARGUMENT; }
+    if (int rc = fileset::check_files(nfiles, files != nullptr, "files")) return rc;
     if (!config) { set_error("null configuration"); return VGA_ERR_ARGUMENT; }
-    L = FilesLayout();
-    L.totals.files = nfiles;
+    fileset::start_layout(L, nfiles, false);
     L.layout.resize(nfiles);
     L.sample_rate.resize(nfiles);
-    L.first_channel.resize(nfiles);
-    L.image_off.resize(nfiles);
-    L.image_size.resize(nfiles);
-    L.tab.resize(nfiles);
-    int64_t channels = 0, image_at = 0;
+    int64_t channels = 0;
+    fileset::Images images;
     for (int f = 0; f < nfiles; f++) {
         const vga_idsp_file &F = files[f];
         const vga_idsp_params p = params_of(F, *config);
         vga_idsp_layout &N = L.layout[f];
         if (int rc = gcs::idsp_layout(&p, F.channels, &N)) return name_file(f, rc);
-        if (channels + F.channels > 0x7FFFFFFF) { set_error("file %d: more than 2^31 channels", f); return VGA_ERR_ARGUMENT; }
+        const int first = (int)channels;
+        if (int rc = fileset::count_rows(f, F.channels, channels, "channels")) return rc;
+        const fileset::Placed image = images.place(N.file_size);
         L.sample_rate[f] = F.sample_rate;
-        L.first_channel[f] = (int)channels;
+        L.first_channel[f] = first;
         for (int i = 0; i < F.channels; i++) {
             L.counts.push_back(N.channel_sample_count);
             L.channel.push_back({0, 0, 0, f, N.channel.loop_start, 0, 0});
@@ -125,42 +82,32 @@ inline int make_layout(const vga_idsp_file *files, int nfiles, const vga_idsp_fi
         t.h = {F.channels, F.sample_rate, N.sample_count, N.loop_start, N.loop_end, p.block_size, N.header_size, N.audio_data_size,
                N.channel_sample_count, gc::sample_count_to_nibble_count(N.channel_sample_count), N.looping, N.start_addr, N.end_addr,
                N.cur_addr};
-        t.audio.image_off = image_at;
-        t.audio.first_channel = (int)channels;
+        t.audio.image_off = image.at;
+        t.audio.first_channel = first;
         t.audio.channels = F.channels;
         t.audio.input_size = (uint32_t)N.channel_adpcm_bytes;
         t.audio.interleave = (uint32_t)N.interleave_size;
         t.audio.output_size = (uint32_t)N.audio_data_size;
         t.audio_offset = N.header_size;
-        L.image_off[f] = image_at;
+        L.image_off[f] = image.at;
         L.image_size[f] = N.file_size;
-        image_at += gc::pad_to(N.file_size, 16);
-        if (image_at > MAX_TOTAL) { set_error("file %d: the images of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
-        channels += F.channels;
+        if (image.verdict & fileset::TOTAL_PAST_MAX) { set_error("file %d: the images of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
     }
-    lay_out_rows(L);
-    L.totals.image_bytes = image_at + IMAGE_GUARD_BYTES;
-    std::vector<gcf::FileGeom> geom(L.tab.size());
-    for (size_t f = 0; f < L.tab.size(); f++) geom[f] = L.tab[f].audio;
-    gcf::cut_writer_items(geom, L.audio_items, writer_granule16);
-    for (size_t f = 0; f < L.tab.size(); f++) L.tab[f].audio.granule16 = geom[f].granule16;
+    fileset::lay_out_rows(L.rows, L.counts, L.channel, L.totals);
+    L.totals.image_bytes = images.total();
+    // (an IDSP header is a multiple of 0x20, so the audio region starts on 16 whenever the image does)
+    gcf::cut_writer_items(L.tab, gcf::AudioOf(), L.audio_items, gcf::interleaved_granule16);
     return VGA_OK;
 }
 
 // a set for reading, from what vga_idsp_parse returned for every file
 inline int make_layout_from_infos(const vga_idsp_info *const *infos, int nfiles, const int64_t *image_offsets, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !infos) { set_error("null infos"); return VGA_ERR_ARGUMENT; }
-    L = FilesLayout();
-    L.from_infos = true;
-    L.totals.files = nfiles;
+    if (int rc = fileset::check_files(nfiles, infos != nullptr, "infos")) return rc;
+    fileset::start_layout(L, nfiles, true);
     L.sample_rate.resize(nfiles);
-    L.first_channel.resize(nfiles);
-    L.image_off.resize(nfiles);
-    L.image_size.resize(nfiles);
-    L.tab.resize(nfiles);
-    int64_t channels = 0, image_at = 0, image_end = 0;
+    int64_t channels = 0;
+    fileset::Images images;
     for (int f = 0; f < nfiles; f++) {
         const vga_idsp_info *I = infos[f];
         if (!I) { set_error("file %d: null info", f); return VGA_ERR_ARGUMENT; }
@@ -172,32 +119,27 @@ inline int make_layout_from_infos(const vga_idsp_info *const *infos, int nfiles,
                       I->adpcm_bytes, I->sample_count, I->audio_data_offset);
             return VGA_ERR_ARGUMENT;
         }
-        const int64_t at = image_offsets ? image_offsets[f] : image_at;
-        if (at < 0) { set_error("file %d: negative image offset %lld", f, (long long)at); return VGA_ERR_ARGUMENT; }
-        if (channels + nch > 0x7FFFFFFF) { set_error("file %d: more than 2^31 channels", f); return VGA_ERR_ARGUMENT; }
         const int64_t size = (int64_t)I->audio_data_offset + (int64_t)nch * I->audio_data_length;
-        if (size > 0x7FFFFFFF || at > MAX_TOTAL) { set_error("file %d: image past 2 GiB or offset past 2^62", f); return VGA_ERR_OUT_OF_RANGE; }
+        const fileset::Placed image = images.place(size, image_offsets ? image_offsets + f : nullptr);
+        const int64_t at = image.at;
+        if (image.verdict & fileset::OFFSET_NEGATIVE) { set_error("file %d: negative image offset %lld", f, (long long)at); return VGA_ERR_ARGUMENT; }
+        const int first = (int)channels;
+        if (int rc = fileset::count_rows(f, nch, channels, "channels")) return rc;
+        if (image.verdict & (fileset::IMAGE_PAST_2GIB | fileset::OFFSET_PAST_MAX)) { set_error("file %d: image past 2 GiB or offset past 2^62", f); return VGA_ERR_OUT_OF_RANGE; }
         L.sample_rate[f] = I->sample_rate;
-        L.first_channel[f] = (int)channels;
+        L.first_channel[f] = first;
         L.image_off[f] = at;
         L.image_size[f] = (int)size;
-        image_at = gc::pad_to(at + size, 16);
-        image_end = std::max(image_end, image_at);
         for (int i = 0; i < nch; i++) {
             L.counts.push_back(I->sample_count);
             L.channel.push_back({0, 0, 0, f, 0, 0, 0});
-            ChannelMeta m;
-            std::memcpy(m.v, I->coefs[i], 32);
-            m.v[16] = I->gain[i];
-            std::memcpy(m.v + 17, I->start_context[i], 6);
-            std::memcpy(m.v + 20, I->loop_context[i], 6);
-            L.meta.push_back(m);
+            L.meta.push_back(fileset::fill_meta<ChannelMeta>(*I, i));
         }
         FileTab &t = L.tab[f];
         std::memset(&t, 0, sizeof t);
         t.h.nch = nch;
         t.audio.image_off = at;
-        t.audio.first_channel = (int)channels;
+        t.audio.first_channel = first;
         t.audio.channels = nch;
         t.audio.sample_count = I->sample_count;
         t.audio.output_size = (uint32_t)I->adpcm_bytes;
@@ -212,11 +154,10 @@ inline int make_layout_from_infos(const vga_idsp_info *const *infos, int nfiles,
         const uint64_t step = t.audio.granule16 & GRANULE1 ? (uint64_t)CHUNK_BYTES1 : (uint64_t)gcf::CHUNK_GRANULES * (g16 ? 16 : 8);
         for (int i = 0; i < nch; i++)
             for (uint64_t b = 0; b < t.audio.output_size; b += step)
-                L.audio_items.push_back({(int)channels + i, (uint32_t)(b >> 3) | (g16 ? 0x80000000u : 0u)});
-        channels += nch;
+                L.audio_items.push_back({first + i, (uint32_t)(b >> 3) | (g16 ? 0x80000000u : 0u)});
     }
-    lay_out_rows(L);
-    L.totals.image_bytes = image_end + IMAGE_GUARD_BYTES;
+    fileset::lay_out_rows(L.rows, L.counts, L.channel, L.totals);
+    L.totals.image_bytes = images.total();
     return VGA_OK;
 }
 
@@ -261,14 +202,9 @@ inline void regions_of(const FilesLayout &L, std::vector<vga_idsp_files_region> 
 }
 inline int copy_regions(const FilesLayout &L, vga_idsp_files_region *regions_out, int64_t capacity, int64_t *count_out)
 {
-    if (!count_out) { set_error("null count"); return VGA_ERR_ARGUMENT; }
     std::vector<vga_idsp_files_region> r;
     regions_of(L, r);
-    *count_out = (int64_t)r.size();
-    if (!regions_out) return VGA_OK;
-    if ((int64_t)r.size() > capacity) { set_error("%lld regions: capacity %lld", (long long)r.size(), (long long)capacity); return VGA_ERR_ARGUMENT; }
-    std::copy(r.begin(), r.end(), regions_out);
-    return VGA_OK;
+    return fileset::copy_regions(r, regions_out, capacity, count_out);
 }
 
 // ---- the calls' argument checks

@@ -9,17 +9,11 @@
 #include "nw_host.hpp"
 #include "../../include/vgaudio_hip/nw_files.h"
 
-#include <string>
-
 namespace vga {
-
-const char *last_error();                        // the message of the last set_error on this thread
-
 namespace nwf {
 
-constexpr int64_t IMAGE_GUARD_BYTES = 256;       // behind the last image
+using fileset::name_file;
 constexpr int CHUNK_SHORTS = 1024;               // shorts of one seek work item: 256 threads, four each
-constexpr int64_t MAX_TOTAL = (int64_t)1 << 62;
 
 // What the kernels need of one file (a device table, one per file): the header kernel's numbers, the audio as
 // Interleave(rows of channel_adpcm_bytes, interleave_size, audio_data_size) when written and DeInterleave(audio_data_length,
@@ -34,8 +28,7 @@ struct FileTab {
 };
 using ChannelRow = gcf::ChannelRow;              // adpcm_off, seek_off, file, entries (pcm_off of the same batch)
 using Item = gcf::Item;                          // audio: as gc_files_host.hpp; seek: x = file, y = first short of the body
-// the reader's per-channel arrays as the object holds them: coefficients, gain, start and loop context
-struct ChannelMeta { int16_t v[23]; };
+struct ChannelMeta { int16_t v[23]; };           // the reader's per-channel arrays as the object holds them (fileset::fill_meta)
 
 struct FilesLayout {
     vga_nw_files_totals totals = {};
@@ -52,16 +45,6 @@ struct FilesLayout {
     std::vector<Item> audio_items, seek_items;
     bool any_seek = false;
 };
-
-// 16-byte granules need the interleave and the rows of the last block on 16 (one channel is no exception here: its blocks
-// are `interleave` bytes apart in the row and in the image alike, but a granule must not straddle two of them)
-inline bool writer_granule16(const gcf::FileGeom &g, bool last_block)
-{
-    if (g.interleave % 16 != 0) return false;
-    if (!last_block) return true;
-    const uint32_t out_blocks = (g.output_size + g.interleave - 1) / g.interleave;
-    return (g.output_size - (out_blocks - 1) * g.interleave) % 16 == 0;
-}
 
 inline vga_nwstm_params params_of(const vga_nw_file &F, const vga_nw_file_config &c)
 {
@@ -82,31 +65,11 @@ inline vga_nwstm_params params_of(const vga_nw_file &F, const vga_nw_file_config
     return p;                                    // track_count 0: the default list; the keep_* flags do not exist here
 }
 
-// "file <f>: " in front of the message the per-file code left
-inline int name_file(int f, int rc)
-{
-    const std::string msg = last_error();
-    set_error("file %d: %s", f, msg.c_str());
-    return rc;
-}
-
 // rows, seek offsets and the sizes of the row buffers once counts / channel[].entries are known
 inline void lay_out_rows(FilesLayout &L)
 {
-    const int nch = (int)L.counts.size();
-    L.rows.lay_out(L.counts.data(), nch, 0, 0);
-    int64_t seek_at = 0;
-    for (int c = 0; c < nch; c++) {
-        ChannelRow &r = L.channel[c];
-        r.pcm_off = L.rows.pcm_off[c];
-        r.adpcm_off = L.rows.adpcm_off[c];
-        r.seek_off = seek_at;
-        seek_at += gc::pad_to(2 * (int64_t)r.entries, 8);
-    }
-    L.totals.channels = nch;
-    L.totals.pcm_samples = L.rows.pcm_end + gc::GUARD_BYTES / 2;
-    L.totals.adpcm_bytes = L.rows.adpcm_end + gc::GUARD_BYTES;
-    L.totals.seek_shorts = seek_at;
+    fileset::lay_out_rows(L.rows, L.counts, L.channel, L.totals);
+    L.totals.seek_shorts = fileset::lay_out_seek(L.channel);
 }
 
 // (file, chunk of CHUNK_SHORTS shorts) items over the body of every ADPC / SEEK block
@@ -118,27 +81,24 @@ inline void cut_seek_items(FilesLayout &L)
 
 inline int make_layout(const vga_nw_file *files, int nfiles, const vga_nw_file_config *config, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !files) { set_error("null files"); return VGA_ERR_ARGUMENT; }
+    if (int rc = fileset::check_files(nfiles, files != nullptr, "files")) return rc;
     if (!config) { set_error("null configuration"); return VGA_ERR_ARGUMENT; }
-    L = FilesLayout();
-    L.totals.files = nfiles;
+    fileset::start_layout(L, nfiles, false);
     L.layout.resize(nfiles);
     L.sample_rate.resize(nfiles);
-    L.first_channel.resize(nfiles);
-    L.image_off.resize(nfiles);
-    L.image_size.resize(nfiles);
-    L.tab.resize(nfiles);
-    int64_t channels = 0, image_at = 0;
+    int64_t channels = 0;
+    fileset::Images images;
     for (int f = 0; f < nfiles; f++) {
         const vga_nw_file &F = files[f];
         const vga_nwstm_params p = params_of(F, *config);
         vga_nwstm_layout &N = L.layout[f];
         std::memset(&N, 0, sizeof N);
         if (int rc = nw::nw_layout(&p, nw::kCodecGcAdpcm, F.channels, &N)) return name_file(f, rc);
-        if (channels + F.channels > 0x7FFFFFFF) { set_error("file %d: more than 2^31 channels", f); return VGA_ERR_ARGUMENT; }
+        const int first = (int)channels;
+        if (int rc = fileset::count_rows(f, F.channels, channels, "channels")) return rc;
+        const fileset::Placed image = images.place(N.file_size);
         L.sample_rate[f] = F.sample_rate;
-        L.first_channel[f] = (int)channels;
+        L.first_channel[f] = first;
         for (int i = 0; i < F.channels; i++) {
             L.counts.push_back(N.channel_sample_count);
             L.channel.push_back({0, 0, 0, f, N.channel.loop_start, N.channel.samples_per_seek_table_entry, N.channel_seek_entries});
@@ -147,8 +107,8 @@ inline int make_layout(const vga_nw_file *files, int nfiles, const vga_nw_file_c
         FileTab &t = L.tab[f];
         std::memset(&t, 0, sizeof t);
         nw::header_geom(N, &p, F.channels, nw::kCodecGcAdpcm, &t.h);
-        t.audio.image_off = image_at;
-        t.audio.first_channel = (int)channels;
+        t.audio.image_off = image.at;
+        t.audio.first_channel = first;
         t.audio.channels = F.channels;
         t.audio.input_size = (uint32_t)N.channel_adpcm_bytes;
         t.audio.interleave = (uint32_t)N.interleave_size;
@@ -158,18 +118,14 @@ inline int make_layout(const vga_nw_file *files, int nfiles, const vga_nw_file_c
         t.seek_entries = N.seek_table_entry_count;
         t.seek_body_shorts = (N.seek_block_size - 8) / 2;
         t.seek_big = N.endianness == VGA_NW_BIG_ENDIAN && N.target == VGA_NW_RSTM;
-        L.image_off[f] = image_at;
+        L.image_off[f] = image.at;
         L.image_size[f] = N.file_size;
-        image_at += gc::pad_to(N.file_size, 16);
-        if (image_at > MAX_TOTAL) { set_error("file %d: the images of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
-        channels += F.channels;
+        if (image.verdict & fileset::TOTAL_PAST_MAX) { set_error("file %d: the images of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
     }
     lay_out_rows(L);
-    L.totals.image_bytes = image_at + IMAGE_GUARD_BYTES;
-    std::vector<gcf::FileGeom> geom(L.tab.size());
-    for (size_t f = 0; f < L.tab.size(); f++) geom[f] = L.tab[f].audio;
-    gcf::cut_writer_items(geom, L.audio_items, writer_granule16);
-    for (size_t f = 0; f < L.tab.size(); f++) L.tab[f].audio.granule16 = geom[f].granule16;
+    L.totals.image_bytes = images.total();
+    // (one channel is no exception to the rule here: its blocks lie `interleave` bytes apart too)
+    gcf::cut_writer_items(L.tab, gcf::AudioOf(), L.audio_items, gcf::interleaved_granule16);
     cut_seek_items(L);
     return VGA_OK;
 }
@@ -177,17 +133,11 @@ inline int make_layout(const vga_nw_file *files, int nfiles, const vga_nw_file_c
 // a set for reading, from what vga_nwstm_parse returned for every file
 inline int make_layout_from_infos(const vga_nwstm_info *const *infos, int nfiles, const int64_t *image_offsets, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !infos) { set_error("null infos"); return VGA_ERR_ARGUMENT; }
-    L = FilesLayout();
-    L.from_infos = true;
-    L.totals.files = nfiles;
+    if (int rc = fileset::check_files(nfiles, infos != nullptr, "infos")) return rc;
+    fileset::start_layout(L, nfiles, true);
     L.sample_rate.resize(nfiles);
-    L.first_channel.resize(nfiles);
-    L.image_off.resize(nfiles);
-    L.image_size.resize(nfiles);
-    L.tab.resize(nfiles);
-    int64_t channels = 0, image_at = 0, image_end = 0;
+    int64_t channels = 0;
+    fileset::Images images;
     for (int f = 0; f < nfiles; f++) {
         const vga_nwstm_info *I = infos[f];
         if (!I) { set_error("file %d: null info", f); return VGA_ERR_ARGUMENT; }
@@ -204,31 +154,26 @@ inline int make_layout_from_infos(const vga_nwstm_info *const *infos, int nfiles
                       "with vga_nwstm_read_device", f, I->audio_data_offset, I->interleave_size, I->audio_data_length / nch);
             return VGA_ERR_INVALID_OP;
         }
-        const int64_t at = image_offsets ? image_offsets[f] : image_at;
-        if (at < 0 || at % 8) { set_error("file %d: image offset %lld is not a multiple of 8", f, (long long)at); return VGA_ERR_ARGUMENT; }
-        if (channels + nch > 0x7FFFFFFF) { set_error("file %d: more than 2^31 channels", f); return VGA_ERR_ARGUMENT; }
         const int64_t size = (int64_t)I->audio_data_offset + I->audio_data_length;
-        if (size > 0x7FFFFFFF || at > MAX_TOTAL) { set_error("file %d: image past 2 GiB or offset past 2^62", f); return VGA_ERR_OUT_OF_RANGE; }
+        const fileset::Placed image = images.place(size, image_offsets ? image_offsets + f : nullptr);
+        const int64_t at = image.at;
+        if (at < 0 || at % 8) { set_error("file %d: image offset %lld is not a multiple of 8", f, (long long)at); return VGA_ERR_ARGUMENT; }
+        const int first = (int)channels;
+        if (int rc = fileset::count_rows(f, nch, channels, "channels")) return rc;
+        if (image.verdict & (fileset::IMAGE_PAST_2GIB | fileset::OFFSET_PAST_MAX)) { set_error("file %d: image past 2 GiB or offset past 2^62", f); return VGA_ERR_OUT_OF_RANGE; }
         L.sample_rate[f] = I->sample_rate;
-        L.first_channel[f] = (int)channels;
+        L.first_channel[f] = first;
         L.image_off[f] = at;
         L.image_size[f] = (int)size;
-        image_at = gc::pad_to(at + size, 16);
-        image_end = std::max(image_end, image_at);
         for (int i = 0; i < nch; i++) {
             L.counts.push_back(I->sample_count);
             L.channel.push_back({0, 0, 0, f, 0, 0, 0});
-            ChannelMeta m;
-            std::memcpy(m.v, I->coefs[i], 32);
-            m.v[16] = I->gain[i];
-            std::memcpy(m.v + 17, I->start_context[i], 6);
-            std::memcpy(m.v + 20, I->loop_context[i], 6);
-            L.meta.push_back(m);
+            L.meta.push_back(fileset::fill_meta<ChannelMeta>(*I, i));
         }
         FileTab &t = L.tab[f];
         std::memset(&t, 0, sizeof t);
         t.audio.image_off = at;
-        t.audio.first_channel = (int)channels;
+        t.audio.first_channel = first;
         t.audio.channels = nch;
         t.audio.sample_count = I->sample_count;
         t.audio.output_size = (uint32_t)I->adpcm_bytes;
@@ -236,13 +181,10 @@ inline int make_layout_from_infos(const vga_nwstm_info *const *infos, int nfiles
         t.audio.interleave = (uint32_t)I->interleave_size;
         t.audio.granule16 = ((at + I->audio_data_offset) % 16 == 0 && t.audio.interleave % 16 == 0 && t.audio.input_size % 16 == 0) ? 1u : 0u;
         t.audio_offset = I->audio_data_offset;
-        channels += nch;
     }
     lay_out_rows(L);
-    L.totals.image_bytes = image_end + IMAGE_GUARD_BYTES;
-    std::vector<gcf::FileGeom> geom(L.tab.size());
-    for (size_t f = 0; f < L.tab.size(); f++) geom[f] = L.tab[f].audio;
-    gcf::cut_reader_items(geom, L.audio_items);
+    L.totals.image_bytes = images.total();
+    gcf::cut_reader_items(L.tab, gcf::AudioOf(), L.audio_items);
     return VGA_OK;
 }
 

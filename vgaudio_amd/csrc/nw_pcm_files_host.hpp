@@ -65,12 +65,8 @@ inline void cut_items(FilesLayout &L, int f)
     for (int c = 0; c < t.nch; c++) vec = vec && L.P.row_off[t.first_channel + c] % 8 == 0;
     t.vector = vec ? 1 : 0;
     (vec ? L.vector_files : L.general_files)++;
-    const int first = L.from_infos() ? t.first_channel : f, count = L.from_infos() ? t.nch : 1;
-    for (int k = 0; k < 2; k++) {
-        if (k == 0 && vec) continue;             // gathered by finish_items
-        for (int i = 0; i < count; i++)
-            for (int64_t at = 0, y = 0; at < per; at += CHUNK_BYTES, y++) L.items[k].push_back({first + i, (uint32_t)y});
-    }
+    // (the vector items are gathered by finish_items)
+    fileset::cut_general_items(L.items, vec, L.from_infos() ? t.first_channel : f, L.from_infos() ? t.nch : 1, per, CHUNK_BYTES);
 }
 // the vector items go in front (they are one launch, the general items the next)
 inline int finish_items(FilesLayout &L)
@@ -84,29 +80,27 @@ inline int finish_items(FilesLayout &L)
         for (int i = 0; i < count; i++)
             for (int64_t at = 0, y = 0; at < per; at += CHUNK_BYTES, y++) vec.push_back({first + i, (uint32_t)y});
     }
-    L.vector_items = (int)vec.size();
-    L.items[0].insert(L.items[0].begin(), vec.begin(), vec.end());
-    if (L.items[0].size() > 0x7FFFFFFF || L.items[1].size() > 0x7FFFFFFF) { set_error("the set has more than 2^31 work items"); return VGA_ERR_OUT_OF_RANGE; }
-    return VGA_OK;
+    L.vector_items = fileset::put_in_front(L.items[0], vec);
+    return fileset::check_item_count(std::max(L.items[0].size(), L.items[1].size()));
 }
 
 // a set for writing
 inline int make_layout(const vga_nw_file *files, int nfiles, const vga_nw_file_config *config, int codec, const int64_t *pcm_offsets,
                        const int64_t *image_offsets, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !files) { set_error("null files"); return VGA_ERR_ARGUMENT; }
+    if (int rc = fileset::check_files(nfiles, files != nullptr, "files")) return rc;
     if (!config) { set_error("null configuration"); return VGA_ERR_ARGUMENT; }
     if (codec != nw::kCodecPcm8 && codec != nw::kCodecPcm16) { set_error("codec %d: a set holds PCM8 (0) or PCM16 (1) streams (nw_files.h for GC-ADPCM)", codec); return VGA_ERR_ARGUMENT; }
     L = FilesLayout();
-    wavf::start_layout(L.P, nfiles, false);
+    fileset::start_layout(L.P, nfiles, false);
     L.layout.resize(nfiles);
     L.tab.resize(nfiles);
-    int64_t channels = 0, pcm_at = 0, pcm_end = 0, image_at = 0, image_end = 0, rows = 0;
+    wavf::Placement P;
+    int64_t rows = 0;
     for (int f = 0; f < nfiles; f++) {                       // every file's own checks first: nothing is placed for a set that is refused here
         const vga_nwstm_params p = nwf::params_of(files[f], *config);
         std::memset(&L.layout[f], 0, sizeof L.layout[f]);
-        if (int rc = nw::nw_layout(&p, codec, files[f].channels, &L.layout[f])) return nwf::name_file(f, rc);
+        if (int rc = nw::nw_layout(&p, codec, files[f].channels, &L.layout[f])) return fileset::name_file(f, rc);
         if (int rc = wavf::count_rows(f, files[f].channels, rows)) return rc;
     }
     L.P.row_off.reserve((size_t)rows);
@@ -116,7 +110,7 @@ inline int make_layout(const vga_nw_file *files, int nfiles, const vga_nw_file_c
         const vga_nw_file &F = files[f];
         const vga_nwstm_layout &N = L.layout[f];
         if (image_offsets && image_offsets[f] >= 0 && image_offsets[f] % 16) { set_error("file %d: image offset %lld is not a multiple of 16", f, (long long)image_offsets[f]); return VGA_ERR_ARGUMENT; }
-        if (int rc = wavf::place_file(L.P, f, F.channels, F.sample_count, N.file_size, pcm_offsets, image_offsets, channels, pcm_at, pcm_end, image_at, image_end)) return rc;
+        if (int rc = wavf::place_file(L.P, f, F.channels, F.sample_count, N.file_size, pcm_offsets, image_offsets, P)) return rc;
         const vga_nwstm_params p = nwf::params_of(F, *config);
         FileTab &t = L.tab[f];
         std::memset(&t, 0, sizeof t);
@@ -136,7 +130,7 @@ inline int make_layout(const vga_nw_file *files, int nfiles, const vga_nw_file_c
     }
     if (image_offsets)
         if (int rc = wavf::check_overlap(L.P.image_off, L.P.image_size, "image", [](int f) { return f; })) return rc;
-    if (int rc = wavf::finish_layout(L.P, pcm_offsets, channels, pcm_at, pcm_end, image_end)) return rc;
+    if (int rc = wavf::finish_layout(L.P, pcm_offsets, P)) return rc;
     return finish_items(L);
 }
 
@@ -144,17 +138,17 @@ inline int make_layout(const vga_nw_file *files, int nfiles, const vga_nw_file_c
 inline int make_layout_from_infos(const vga_nwstm_info *const *infos, int nfiles, const int64_t *pcm_offsets, const int64_t *image_offsets,
                                   FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !infos) { set_error("null infos"); return VGA_ERR_ARGUMENT; }
+    if (int rc = fileset::check_files(nfiles, infos != nullptr, "infos")) return rc;
     L = FilesLayout();
-    wavf::start_layout(L.P, nfiles, true);
+    fileset::start_layout(L.P, nfiles, true);
     L.tab.resize(nfiles);
-    int64_t channels = 0, pcm_at = 0, pcm_end = 0, image_at = 0, image_end = 0, rows = 0;
+    wavf::Placement P;
+    int64_t rows = 0;
     std::vector<int> sizes((size_t)nfiles);
     for (int f = 0; f < nfiles; f++) {                       // every file's own checks first
         const vga_nwstm_info *I = infos[f];
         if (!I) { set_error("file %d: null info", f); return VGA_ERR_ARGUMENT; }
-        if (int rc = nw::pcm_read_info_check(I, VGA_SAMPLES_S16, true)) return nwf::name_file(f, rc);
+        if (int rc = nw::pcm_read_info_check(I, VGA_SAMPLES_S16, true)) return fileset::name_file(f, rc);
         // what the per-file call leaves to its pointers and pitches: the set places rows and images from these numbers
         if (I->channel_count < 0 || I->channel_count > VGA_NW_MAX_CHANNELS || I->sample_count < 0 || I->audio_data_offset < 0 || I->audio_data_length < 0 ||
             I->adpcm_bytes != (int64_t)I->sample_count * (I->codec == nw::kCodecPcm16 ? 2 : 1)) {
@@ -177,7 +171,7 @@ inline int make_layout_from_infos(const vga_nwstm_info *const *infos, int nfiles
     L.P.row_file.reserve((size_t)rows);
     for (int f = 0; f < nfiles; f++) {
         const vga_nwstm_info *I = infos[f];
-        if (int rc = wavf::place_file(L.P, f, I->channel_count, I->sample_count, sizes[f], pcm_offsets, image_offsets, channels, pcm_at, pcm_end, image_at, image_end)) return rc;
+        if (int rc = wavf::place_file(L.P, f, I->channel_count, I->sample_count, sizes[f], pcm_offsets, image_offsets, P)) return rc;
         FileTab &t = L.tab[f];
         std::memset(&t, 0, sizeof t);
         t.image_off = L.P.image_off[f];
@@ -191,7 +185,7 @@ inline int make_layout_from_infos(const vga_nwstm_info *const *infos, int nfiles
         t.bps = I->codec == nw::kCodecPcm16 ? 2 : 1;
         cut_items(L, f);
     }
-    if (int rc = wavf::finish_layout(L.P, pcm_offsets, channels, pcm_at, pcm_end, image_end)) return rc;
+    if (int rc = wavf::finish_layout(L.P, pcm_offsets, P)) return rc;
     return finish_items(L);
 }
 

@@ -5,27 +5,21 @@
 // (tests/host/wave_files_host_driver.cpp) as capi_wave_files.hip does; whoever includes it supplies vga::set_error and
 // vga::last_error.
 #pragma once
+#include "files_layout.hpp"
 #include "wave_file_host.hpp"
 #include "../../include/vgaudio_hip_files/wave_files.h"
 
-#include <algorithm>
-#include <string>
-#include <vector>
-
 namespace vga {
-
-const char *last_error();                        // the message of the last set_error on this thread
-
 namespace wavf {
 
+using fileset::name_file;
+using fileset::pad_to;
 constexpr int64_t GUARD_SAMPLES = 128;           // behind the last row
-constexpr int64_t GUARD_BYTES = 256;             // behind the last image
 constexpr int ROW_ROUND = 8;                     // samples a packed row is rounded up to
 constexpr int SPAN_BYTES = 16384;                // interleaved bytes of one tile item, at most
 constexpr int MAX_TILE_FRAME = VGA_WAVE_FILES_MAX_TILE_FRAME;   // 8 frames fit a span
 constexpr int CHUNK_GRANULES = 2048;             // of one general work item: 256 threads, eight granules each
 constexpr int GRANULE_BYTES = 16;                // read: 8 samples of a row; write: 16 bytes of the data chunk
-constexpr int64_t MAX_TOTAL = (int64_t)1 << 62;
 constexpr int HEADER_PITCH = container::kWaveMaxHeader;
 
 // What the kernels need of one file (a device table, one per file)
@@ -54,16 +48,6 @@ struct FilesLayout {
     int tile_files = 0, general_files = 0, moving_files = 0;   // of items[0]; files that move samples at all
 };
 
-// "file <f>: " in front of the message the per-file code left
-inline int name_file(int f, int rc)
-{
-    const std::string msg = last_error();
-    set_error("file %d: %s", f, msg.c_str());
-    return rc;
-}
-
-inline int64_t pad_to(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
 // frames of one span of a file whose frame is `frame` bytes; 0: the file does not take the tile form
 inline int span_frames(int frame) { return frame <= MAX_TILE_FRAME ? SPAN_BYTES / frame / 8 * 8 : 0; }
 
@@ -75,14 +59,9 @@ inline void cut_items(FilesLayout &L, int f)
     L.moving_files++;
     // write: chunks of the file's interleaved bytes; read: chunks of every row
     const int64_t per = L.from_infos ? (int64_t)t.frames * 2 : (int64_t)t.frames * t.nch * t.bps;
-    const int first = L.from_infos ? t.first_channel : f, count = L.from_infos ? t.nch : 1;
-    const int64_t unit = (int64_t)CHUNK_GRANULES * GRANULE_BYTES;
     t.span_frames = span_frames(t.nch * t.bps);
-    for (int k = 0; k < 2; k++) {
-        if (k == 0 && t.span_frames > 0) continue;
-        for (int i = 0; i < count; i++)
-            for (int64_t at = 0, y = 0; at < per; at += unit, y++) L.items[k].push_back({first + i, (uint32_t)y});
-    }
+    fileset::cut_general_items(L.items, t.span_frames > 0, L.from_infos ? t.first_channel : f, L.from_infos ? t.nch : 1, per,
+                               (int64_t)CHUNK_GRANULES * GRANULE_BYTES);
     if (t.span_frames > 0) L.tile_files++;
     else L.general_files++;
 }
@@ -92,104 +71,71 @@ inline int finish_items(FilesLayout &L)
     std::vector<Item> tile;
     for (size_t f = 0; f < L.tab.size(); f++)
         for (int k0 = 0; L.tab[f].span_frames > 0 && k0 < L.tab[f].frames; k0 += L.tab[f].span_frames) tile.push_back({(int)f, (uint32_t)k0});
-    L.tile_items = (int)tile.size();
-    L.items[0].insert(L.items[0].begin(), tile.begin(), tile.end());
-    if (L.items[0].size() > 0x7FFFFFFF || L.items[1].size() > 0x7FFFFFFF) { set_error("the set has more than 2^31 work items"); return VGA_ERR_OUT_OF_RANGE; }
-    return VGA_OK;
+    L.tile_items = fileset::put_in_front(L.items[0], tile);
+    return fileset::check_item_count(std::max(L.items[0].size(), L.items[1].size()));
 }
 
 // ranges [off, off + len) (len > 0 only) must not overlap; `what` names them, file_of(i) the file of range i
 template <class FileOf>
 inline int check_overlap(const std::vector<int64_t> &off, const std::vector<int> &len, const char *what, FileOf file_of)
 {
-    std::vector<int> order;
-    for (int c = 0; c < (int)off.size(); c++)
-        if (len[c] > 0) order.push_back(c);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return off[a] != off[b] ? off[a] < off[b] : a < b; });
-    for (size_t i = 1; i < order.size(); i++) {
-        const int a = order[i - 1], b = order[i];
-        if (off[a] + len[a] > off[b]) {
-            set_error("file %d: %s %d (offset %lld, length %d) overlaps %s %d (offset %lld)", file_of(std::max(a, b)), what, a,
-                      (long long)off[a], len[a], what, b, (long long)off[b]);
-            return VGA_ERR_ARGUMENT;
-        }
-    }
-    return VGA_OK;
+    int a, b;
+    if (!fileset::find_overlap((int)off.size(), [&](int i) { return off[i]; }, [&](int i) { return len[i]; }, a, b)) return VGA_OK;
+    set_error("file %d: %s %d (offset %lld, length %d) overlaps %s %d (offset %lld)", file_of(std::max(a, b)), what, a, (long long)off[a],
+              len[a], what, b, (long long)off[b]);
+    return VGA_ERR_ARGUMENT;
 }
 
 // Called for every file, in order, BEFORE a row is placed (a row costs 16 bytes of host tables): the set's rows so far
-inline int count_rows(int f, int nch, int64_t &rows)
-{
-    rows += nch;
-    if (rows > 0x7FFFFFFF) { set_error("file %d: more than 2^31 rows", f); return VGA_ERR_ARGUMENT; }
-    return VGA_OK;
-}
+inline int count_rows(int f, int nch, int64_t &rows) { return fileset::count_rows(f, nch, rows, "rows"); }
+
+// the running placement of a set: the rows placed so far, where the next row (in samples) and the next image go
+struct Placement {
+    int64_t channels = 0;
+    fileset::Rows rows;
+    fileset::Images images;
+};
 
 // The rows and the image of file f, shared by both kinds of set.  `samples` per row, `size` bytes of image.
-inline int place_file(FilesLayout &L, int f, int nch, int samples, int64_t size, const int64_t *pcm_offsets, const int64_t *image_offsets,
-                      int64_t &channels, int64_t &pcm_at, int64_t &pcm_end, int64_t &image_at, int64_t &image_end)
+inline int place_file(FilesLayout &L, int f, int nch, int samples, int64_t size, const int64_t *pcm_offsets, const int64_t *image_offsets, Placement &P)
 {
-    L.first_channel[f] = (int)channels;
+    L.first_channel[f] = (int)P.channels;
     for (int i = 0; i < nch; i++) {
-        int64_t at = pcm_at;
-        if (pcm_offsets) {
-            at = pcm_offsets[channels + i];
-            if (at < 0) { set_error("file %d: pcm offset %lld of row %lld is negative", f, (long long)at, (long long)(channels + i)); return VGA_ERR_ARGUMENT; }
-        } else {
-            pcm_at += pad_to(samples, ROW_ROUND);
-        }
-        if (at > MAX_TOTAL / 2 || pcm_at > MAX_TOTAL / 2) { set_error("file %d: the rows of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
-        L.row_off.push_back(at);
+        const int64_t row = P.channels + i;
+        const fileset::Placed r = P.rows.place(samples, pad_to(samples, ROW_ROUND), fileset::MAX_TOTAL / 2, pcm_offsets ? pcm_offsets + row : nullptr);
+        if (r.verdict & fileset::OFFSET_NEGATIVE) { set_error("file %d: pcm offset %lld of row %lld is negative", f, (long long)r.at, (long long)row); return VGA_ERR_ARGUMENT; }
+        if (r.verdict) { set_error("file %d: the rows of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
+        L.row_off.push_back(r.at);
         L.row_samples.push_back(samples);
         L.row_file.push_back(f);
-        if (samples > 0) pcm_end = std::max(pcm_end, at + samples);
     }
-    int64_t at = image_at;
-    if (image_offsets) {
-        at = image_offsets[f];
-        if (at < 0) { set_error("file %d: negative image offset %lld", f, (long long)at); return VGA_ERR_ARGUMENT; }
-    }
-    if (at > MAX_TOTAL) { set_error("file %d: the images of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
-    L.image_off[f] = at;
+    const fileset::Placed image = P.images.place(size, image_offsets ? image_offsets + f : nullptr);
+    if (image.verdict & fileset::OFFSET_NEGATIVE) { set_error("file %d: negative image offset %lld", f, (long long)image.at); return VGA_ERR_ARGUMENT; }
+    if (image.verdict & fileset::OFFSET_PAST_MAX) { set_error("file %d: the images of the set exceed 2^62 bytes", f); return VGA_ERR_OUT_OF_RANGE; }
+    L.image_off[f] = image.at;
     L.image_size[f] = (int)size;
-    image_at = pad_to(at + size, 16);
-    image_end = std::max(image_end, image_at);
-    channels += nch;
+    P.channels += nch;
     return VGA_OK;
 }
 
-inline void start_layout(FilesLayout &L, int nfiles, bool from_infos)
+inline int finish_layout(FilesLayout &L, const int64_t *pcm_offsets, const Placement &P)
 {
-    L = FilesLayout();
-    L.from_infos = from_infos;
-    L.totals.files = nfiles;
-    L.first_channel.resize(nfiles);
-    L.image_off.resize(nfiles);
-    L.image_size.resize(nfiles);
-    L.tab.resize(nfiles);
-}
-
-inline int finish_layout(FilesLayout &L, const int64_t *pcm_offsets, int64_t channels, int64_t pcm_at, int64_t pcm_end, int64_t image_end)
-{
-    if (pcm_offsets) {
+    if (pcm_offsets)
         if (int rc = check_overlap(L.row_off, L.row_samples, "row", [&](int c) { return L.row_file[c]; })) return rc;
-    } else {
-        pcm_end = pcm_at;
-    }
-    L.totals.channels = (int)channels;
-    L.totals.pcm_samples = pcm_end + GUARD_SAMPLES;
-    L.totals.image_bytes = image_end + GUARD_BYTES;
+    L.totals.channels = (int)P.channels;
+    L.totals.pcm_samples = P.rows.end + GUARD_SAMPLES;
+    L.totals.image_bytes = P.images.total();
     return finish_items(L);
 }
 
 // a set for writing
 inline int make_layout(const vga_wave_file *files, int nfiles, const int64_t *pcm_offsets, const int64_t *image_offsets, FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !files) { set_error("null files"); return VGA_ERR_ARGUMENT; }
-    start_layout(L, nfiles, false);
+    if (int rc = fileset::check_files(nfiles, files != nullptr, "files")) return rc;
+    fileset::start_layout(L, nfiles, false);
     L.headers.assign((size_t)nfiles * HEADER_PITCH, 0);
-    int64_t channels = 0, pcm_at = 0, pcm_end = 0, image_at = 0, image_end = 0, rows = 0;
+    Placement P;
+    int64_t rows = 0;
     std::vector<int> sizes((size_t)nfiles);
     for (int f = 0; f < nfiles; f++) {                       // every file's own checks first: nothing is placed for a set that is refused here
         const vga_wave_file &F = files[f];
@@ -206,7 +152,7 @@ inline int make_layout(const vga_wave_file *files, int nfiles, const int64_t *pc
         const vga_wave_file &F = files[f];
         const int bps = F.bits / 8;
         const int64_t size = sizes[f];
-        if (int rc = place_file(L, f, F.channels, F.params.sample_count, size, pcm_offsets, image_offsets, channels, pcm_at, pcm_end, image_at, image_end)) return rc;
+        if (int rc = place_file(L, f, F.channels, F.params.sample_count, size, pcm_offsets, image_offsets, P)) return rc;
         FileTab &t = L.tab[f];
         std::memset(&t, 0, sizeof t);
         t.header_size = container::wave_header_size(&F.params, F.channels);
@@ -221,17 +167,17 @@ inline int make_layout(const vga_wave_file *files, int nfiles, const int64_t *pc
     }
     if (image_offsets)
         if (int rc = check_overlap(L.image_off, L.image_size, "image", [](int f) { return f; })) return rc;
-    return finish_layout(L, pcm_offsets, channels, pcm_at, pcm_end, image_end);
+    return finish_layout(L, pcm_offsets, P);
 }
 
 // a set for reading, from what vga_wave_parse returned for every file
 inline int make_layout_from_infos(const vga_wave_info *const *infos, int nfiles, const int64_t *pcm_offsets, const int64_t *image_offsets,
                                   FilesLayout &L)
 {
-    if (nfiles < 0) { set_error("negative file count"); return VGA_ERR_ARGUMENT; }
-    if (nfiles > 0 && !infos) { set_error("null infos"); return VGA_ERR_ARGUMENT; }
-    start_layout(L, nfiles, true);
-    int64_t channels = 0, pcm_at = 0, pcm_end = 0, image_at = 0, image_end = 0, rows = 0;
+    if (int rc = fileset::check_files(nfiles, infos != nullptr, "infos")) return rc;
+    fileset::start_layout(L, nfiles, true);
+    Placement P;
+    int64_t rows = 0;
     std::vector<int> sizes((size_t)nfiles);
     for (int f = 0; f < nfiles; f++) {                       // every file's own checks first: nothing is placed for a set that is refused here
         const vga_wave_info *I = infos[f];
@@ -253,7 +199,7 @@ inline int make_layout_from_infos(const vga_wave_info *const *infos, int nfiles,
     for (int f = 0; f < nfiles; f++) {
         const vga_wave_info *I = infos[f];
         const int64_t size = sizes[f];
-        if (int rc = place_file(L, f, I->channel_count, I->sample_count, size, pcm_offsets, image_offsets, channels, pcm_at, pcm_end, image_at, image_end)) return rc;
+        if (int rc = place_file(L, f, I->channel_count, I->sample_count, size, pcm_offsets, image_offsets, P)) return rc;
         FileTab &t = L.tab[f];
         std::memset(&t, 0, sizeof t);
         t.image_off = L.image_off[f];
@@ -264,7 +210,7 @@ inline int make_layout_from_infos(const vga_wave_info *const *infos, int nfiles,
         t.frames = I->channel_count > 0 ? I->sample_count : 0;
         cut_items(L, f);
     }
-    return finish_layout(L, pcm_offsets, channels, pcm_at, pcm_end, image_end);
+    return finish_layout(L, pcm_offsets, P);
 }
 
 // ---- the work items as the public accessor describes them: what the kernels compute from FileTab and Item
