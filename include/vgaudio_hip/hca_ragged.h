@@ -39,8 +39,8 @@
  * the slack, not d_frames.
  * ENCODE  streams that do not loop: the bytes of one vga_hca_encode_device call per stream with that stream's sample_count
  * as pcm_length; d_status[s] as there (4 bitrate too low, 8, 16).  An object that holds a looping stream gives
- * VGA_ERR_INVALID_OP from the encode call (the looping encoder replays loop audio behind the stream; such streams never
- * share launches) and is still good for decoding.
+ * VGA_ERR_INVALID_OP from THIS encode call and is still good for decoding; vga_hca_encode_loops_device_v of
+ * ../vgaudio_hip_files/hca_ragged_loops.h encodes such an object, looping streams beside plain ones, in the same launches.
  *
  * Both calls run on the caller's stream and never synchronise it; d_workspace is the caller's, the library allocates
  * nothing per call.  The object keeps its tables in the memory of the device that was current at create, is immutable and

@@ -174,6 +174,10 @@ int vga_testing_hca_decode_classes(const void *infos, int nstreams, int *class_o
  * launched (the sum over the chunks of streams x the chunk's longest frame_count; a slot behind a stream's own frames does
  * no work).  Writes min(n, 5) fields and returns 5. */
 int vga_testing_hca_decode_v_stats(long long *out, int n);
+/* The calling thread's last vga_hca_encode_batch_v call: [0] streams [1] groups (streams of one group may share launches:
+ * plain streams by quality, bitrate, channels and rate; looping streams by the same and NOT by their loops) [2] chunks
+ * [3] encode launches (one per chunk that has frames).  Writes min(n, 4) fields and returns 4. */
+int vga_testing_hca_encode_v_stats(long long *out, int n);
 /* A packed batch (vgaudio_hip/hca_ragged.h; ragged: a vga_hca_ragged): [0] own frames (the sum of the streams' frame_count)
  * [1] scan slots launched (own frames rounded up to the 64 lanes of a wave: no slot lies behind a stream's frames) [2]
  * workgroups of the decoder's second kernel [3] runs in its table (one workgroup each; streams without samples have none).

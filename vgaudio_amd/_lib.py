@@ -266,6 +266,9 @@ SIGNATURES = {
     "vga_hps_files_stats": (ci, [vp, C.POINTER(i64)]),
     "vga_hca_decode_device_v": (ci, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
     "vga_hca_encode_device_v": (ci, [vp, vp, vp, vp, vp]),
+    "vga_hca_encode_loops_device_v": (ci, [vp, vp, vp, vp, vp]),
+    "vga_hca_loop_may_read_tail": (ci, [vp]),
+    "vga_testing_hca_encode_v_stats": (ci, [C.POINTER(C.c_longlong), ci]),
     "vga_hca_stream_create": (ci, [vp, vp, C.POINTER(vp)]),
     "vga_hca_stream_encode": (ci, [vp, vp, u8p, C.POINTER(ci)]),
     "vga_hca_stream_pending_frame_count": (ci, [vp]),

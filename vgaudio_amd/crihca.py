@@ -334,6 +334,26 @@ class RaggedHca:
         self._need(status, torch.int32, self.streams, "status")
         check(_lib.lib().vga_hca_encode_device_v(self._h, pcm.data_ptr(), frames.data_ptr(), status.data_ptr(), self._stream(stream)))
 
+    def encode_loops_device(self, pcm, frames, status, stream=None):
+        """encode_device for an object that may hold looping streams (vga_hca_encode_loops_device_v,
+        include/vgaudio_hip_files/hca_ragged_loops.h): the same tensors, the same layout, the same launches"""
+        import torch
+        self._need(pcm, torch.int16, self.totals.pcm_samples, "pcm")
+        self._need(frames, torch.uint8, self.totals.frame_bytes, "frames")
+        self._need(status, torch.int32, self.streams, "status")
+        check(_lib.lib().vga_hca_encode_loops_device_v(self._h, pcm.data_ptr(), frames.data_ptr(), status.data_ptr(), self._stream(stream)))
+
+
+def loop_may_read_tail(info):
+    """vga_hca_loop_may_read_tail (include/vgaudio_hip_files/hca_ragged_loops.h): True if the reference's encode of a FILE
+    with audio behind info.sample_count reads that audio -- a loop shorter than the post audio --, which a packed row, ending
+    at sample_count, cannot supply.  Host only, needs no GPU."""
+    h = _lib.HcaInfoC.from_buffer_copy(info.c if isinstance(info, HcaInfo) else info)
+    rc = _lib.lib().vga_hca_loop_may_read_tail(C.byref(h))
+    if rc < 0:
+        check(rc)
+    return bool(rc)
+
 
 def decode_files(formats):
     """CriHcaFormat.ToPcm16 (CriHcaFormat.cs:26-32) of many files in one ragged GPU call: one Pcm16Format per CriHcaFormat."""

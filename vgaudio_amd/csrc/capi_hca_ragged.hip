@@ -2,6 +2,7 @@
 // Host side only: the packed layout, the shape-class check and the tables the PACKED instantiations of the kernels read
 // (hca_kernels.hpp: PackedRun, PackedScanStream), made once at create; a call checks its pointers and launches.
 #include "hca_capi.hpp"
+#include "../../include/vgaudio_hip_files/hca_ragged_loops.h"
 
 #include <algorithm>
 #include <map>
@@ -63,6 +64,7 @@ namespace {
 struct RunTable {
     hca::PackedRun *d = nullptr;
     int count = 0;
+    hca::PackedLoopMap *d_loops = nullptr;   // the encoder's, where a stream loops (vga_hca_encode_loops_device_v)
 };
 
 }  // namespace
@@ -76,18 +78,21 @@ struct vga_hca_ragged {
     RunTable dec_runs, enc_runs;           // at the launchers' own frames per run
     // tables cut at a run length the test hook forces (vga_testing_hca_frames_per_group_this_thread), made on first use
     mutable std::mutex mu;
-    mutable std::map<int, RunTable> hooked;   // key: hook value, + (1 << 20) for the encoder's
+    // and the encoder's tables of an object that holds a looping stream (hook value 0 included), made on first use too
+    mutable std::map<int, RunTable> hooked;   // key: hook value, + (1 << 20) for the encoder's, + (1 << 21) with loop maps
     ~vga_hca_ragged()
     {
         if (d_scan) (void)hipFree(d_scan);
         if (dec_runs.d) (void)hipFree(dec_runs.d);
         if (enc_runs.d) (void)hipFree(enc_runs.d);
-        for (auto &kv : hooked)
+        for (auto &kv : hooked) {
             if (kv.second.d) (void)hipFree(kv.second.d);
+            if (kv.second.d_loops) (void)hipFree(kv.second.d_loops);
+        }
     }
 };
 
-std::vector<hca::PackedRun> vga::hca::cut_runs(const RaggedLayout &L, int per_run, bool encoder)
+std::vector<hca::PackedRun> vga::hca::cut_runs(const RaggedLayout &L, int per_run, bool encoder, std::vector<hca::PackedLoopMap> *loops)
 {
     std::vector<hca::PackedRun> runs;
     for (int s = 0; s < (int)L.infos.size(); s++) {
@@ -102,10 +107,7 @@ std::vector<hca::PackedRun> vga::hca::cut_runs(const RaggedLayout &L, int per_ru
         r.frame_count = h.frame_count;
         r.sample_count = h.sample_count;
         r.inserted_samples = h.inserted_samples;
-        if (encoder) {
-            hca::PcmMap m;
-            if (make_pcm_map(h, h.sample_count, m) == VGA_OK) r.zero_pre = m.zero_pre;
-        }
+        if (encoder) (void)hca::set_encoder_map(r, h, h.sample_count, loops);    // (encoder_checks refuses what this refuses)
         r.stream = s;
         for (int f = 0; f < h.frame_count; f += per_run) {
             r.f0 = f;
@@ -120,19 +122,22 @@ namespace {
 
 using hca::cut_runs;
 
-int upload_runs(const std::vector<hca::PackedRun> &runs, RunTable &t)
+int upload_runs(const std::vector<hca::PackedRun> &runs, RunTable &t, const std::vector<hca::PackedLoopMap> &loops = {})
 {
     t.count = (int)runs.size();
     if (runs.empty()) return VGA_OK;
     VGA_HIP_TRY(device_malloc(reinterpret_cast<void **>(&t.d), runs.size() * sizeof(hca::PackedRun)));
     VGA_HIP_TRY(hipMemcpy(t.d, runs.data(), runs.size() * sizeof(hca::PackedRun), hipMemcpyHostToDevice));
+    if (loops.empty()) return VGA_OK;
+    VGA_HIP_TRY(device_malloc(reinterpret_cast<void **>(&t.d_loops), loops.size() * sizeof(hca::PackedLoopMap)));
+    VGA_HIP_TRY(hipMemcpy(t.d_loops, loops.data(), loops.size() * sizeof(hca::PackedLoopMap), hipMemcpyHostToDevice));
     return VGA_OK;
 }
 
-// what the encoder refuses, as one vga_hca_encode_device call per stream would
-int encoder_checks(const RaggedLayout &L)
+// what the encoder refuses, as one vga_hca_encode_device call per stream would; vga_hca_encode_device_v refuses loops too
+int encoder_checks(const RaggedLayout &L, bool loops_allowed)
 {
-    if (L.first_looping >= 0) {
+    if (L.first_looping >= 0 && !loops_allowed) {
         set_error("stream %d loops: vga_hca_encode_device_v encodes streams that do not loop (one vga_hca_encode_device call for a looping one)",
                   L.first_looping);
         return VGA_ERR_INVALID_OP;
@@ -198,7 +203,8 @@ int check_object(const vga_hca_ragged *r, const char *what)
 // the runs of this call: the object's own, or (test hook) a table cut at the forced length, made once per length
 int runs_for_call(const vga_hca_ragged *r, bool encoder, int hook, RunTable &out, bool *wave)
 {
-    if (hook == 0) {
+    const bool with_loops = encoder && r->L.first_looping >= 0;
+    if (hook == 0 && !with_loops) {
         out = encoder ? r->enc_runs : r->dec_runs;
         *wave = r->enc_wave;
         return VGA_OK;
@@ -207,11 +213,40 @@ int runs_for_call(const vga_hca_ragged *r, bool encoder, int hook, RunTable &out
     const int per_run = encoder ? hca::encode_frames_per_run(r->L.cls, total, hook, wave)
                                 : hca::decode_frames_per_group(total, hook >= 1000 ? hook - 1000 : hook);
     std::lock_guard<std::mutex> g(r->mu);
-    RunTable &t = r->hooked[hook + (encoder ? 1 << 20 : 0)];
-    if (!t.d && total > 0)
-        if (int rc = upload_runs(cut_runs(r->L, per_run, encoder), t)) return rc;
+    RunTable &t = r->hooked[hook + (encoder ? 1 << 20 : 0) + (with_loops ? 1 << 21 : 0)];
+    if (!t.d && total > 0) {
+        std::vector<hca::PackedLoopMap> loops;
+        const std::vector<hca::PackedRun> runs = cut_runs(r->L, per_run, encoder, with_loops ? &loops : nullptr);
+        if (int rc = upload_runs(runs, t, loops)) {             // never keep half a table: runs that name maps need the maps
+            if (t.d) (void)hipFree(t.d);
+            if (t.d_loops) (void)hipFree(t.d_loops);
+            t = RunTable();
+            return rc;
+        }
+    }
     out = t;
     return VGA_OK;
+}
+
+// both packed encode calls: the checks of one vga_hca_encode_device call per stream, the layout's, the launch
+int encode_call(const vga_hca_ragged *r, const int16_t *d_pcm, uint8_t *d_frames, int *d_status, void *stream, bool loops_allowed,
+                const char *what)
+{
+    if (int rc = encoder_checks(r->L, loops_allowed)) return rc;
+    const vga_hca_ragged_totals &t = r->L.totals;
+    if (t.total_frames <= 0) return VGA_OK;
+    if (!d_frames || !d_status || (!d_pcm && t.pcm_samples > 0)) { set_error("%s: null pointer", what); return VGA_ERR_ARGUMENT; }
+    if (((uintptr_t)d_frames & 3) || ((uintptr_t)d_pcm & 15)) {
+        set_error("bad alignment for %s (frames need 4-byte alignment, PCM 16)", what);
+        return VGA_ERR_ARGUMENT;
+    }
+    const uint16_t *pow = nullptr;
+    if (int rc = hca::crc_pow_table(&pow)) return rc;
+    RunTable runs;
+    bool wave = false;
+    if (int rc = runs_for_call(r, true, hca_frames_per_group_override(), runs, &wave)) return rc;
+    return hca::launch_encode_packed(d_pcm, r->L.cls, runs.d, runs.count, wave, d_frames, pow, d_status, (hipStream_t)stream,
+                                     runs.d_loops);
 }
 
 }  // namespace
@@ -290,20 +325,25 @@ int vga_hca_decode_device_v(const vga_hca_ragged *r, const uint8_t *d_frames, in
 int vga_hca_encode_device_v(const vga_hca_ragged *r, const int16_t *d_pcm, uint8_t *d_frames, int *d_status, void *stream)
 {
     if (int rc = check_object(r, "vga_hca_encode_device_v")) return rc;
-    if (int rc = encoder_checks(r->L)) return rc;
-    const vga_hca_ragged_totals &t = r->L.totals;
-    if (t.total_frames <= 0) return VGA_OK;
-    if (!d_frames || !d_status || (!d_pcm && t.pcm_samples > 0)) { set_error("vga_hca_encode_device_v: null pointer"); return VGA_ERR_ARGUMENT; }
-    if (((uintptr_t)d_frames & 3) || ((uintptr_t)d_pcm & 15)) {
-        set_error("bad alignment for vga_hca_encode_device_v (frames need 4-byte alignment, PCM 16)");
-        return VGA_ERR_ARGUMENT;
-    }
-    const uint16_t *pow = nullptr;
-    if (int rc = hca::crc_pow_table(&pow)) return rc;
-    RunTable runs;
-    bool wave = false;
-    if (int rc = runs_for_call(r, true, hca_frames_per_group_override(), runs, &wave)) return rc;
-    return hca::launch_encode_packed(d_pcm, r->L.cls, runs.d, runs.count, wave, d_frames, pow, d_status, (hipStream_t)stream);
+    return encode_call(r, d_pcm, d_frames, d_status, stream, false, "vga_hca_encode_device_v");
+}
+
+int vga_hca_encode_loops_device_v(const vga_hca_ragged *r, const int16_t *d_pcm, uint8_t *d_frames, int *d_status, void *stream)
+{
+    if (int rc = check_object(r, "vga_hca_encode_loops_device_v")) return rc;
+    return encode_call(r, d_pcm, d_frames, d_status, stream, true, "vga_hca_encode_loops_device_v");
+}
+
+int vga_hca_loop_may_read_tail(const vga_hca_info *info)
+{
+    if (!info) { set_error("null HcaInfo"); return VGA_ERR_ARGUMENT; }
+    hca::PcmMap m;
+    if (int rc = hca::make_pcm_map(*info, info->sample_count, m)) return rc;
+    if (!info->looping) return 0;
+    // SaveLoopAudio (CriHcaEncoder.cs:244-254) fills _postAudio from the loop start on; a loop shorter than the post audio
+    // makes it run on into what the file holds behind HcaInfo.SampleCount
+    const int post = m.post_end - m.main_end, loop_len = info->sample_count - m.loop_start;
+    return loop_len < post ? 1 : 0;
 }
 
 int vga_testing_hca_ragged_stats(const void *ragged, long long *out, int n)

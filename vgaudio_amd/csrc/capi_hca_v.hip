@@ -17,17 +17,28 @@ using namespace vga::hca;
 // and band counts come from the bitrate (CriHcaEncoder.cs:288-368), not from the length, every frame is encoded
 // independently of the others (hca_encode_kernel.hip) and the encoder's own input past the end of the PCM is silence
 // (:234-240), so a shorter stream's frames are the first frames of the padded one.  Looping streams (their loop audio is
-// replayed behind the main audio, :209-232) only share a launch with streams of exactly their shape.
+// replayed behind the main audio, :209-232) share launches too, whatever their loops: a chunk of them is ONE launch of the
+// PACKED encoder over the chunk's pitched rows, every stream with its own HcaInfo and its own stream map (hca_kernels.hpp:
+// PackedRun, PackedLoopMap), the rows as long as the caller's files -- so a loop shorter than the post audio replays what the
+// file holds behind its loop end, as the reference does (include/vgaudio_hip_files/hca_ragged_loops.h).
 namespace {
 
 struct HcaGroupKey {
-    int quality, bitrate, limit_bitrate, channel_count, sample_rate, looping, loop_start, loop_end, exact_count;
+    int quality, bitrate, limit_bitrate, channel_count, sample_rate, looping, shape_class;
 };
 
-int hca_group_of(std::vector<HcaGroupKey> &seen, const vga_hca_params &c)
+struct HcaEncodeVStats { long long v[4] = {0, 0, 0, 0}; };          // vga_testing_hca_encode_v_stats
+HcaEncodeVStats &hca_encode_v_last()
 {
-    HcaGroupKey k = {c.quality, c.bitrate, c.limit_bitrate, c.channel_count, c.sample_rate, c.looping ? 1 : 0,
-                     c.looping ? c.loop_start : 0, c.looping ? c.loop_end : 0, c.looping ? c.sample_count : -1};
+    static thread_local HcaEncodeVStats last;
+    return last;
+}
+
+// shape_class: of a looping stream, among the job's streams (streams of one key have one class: the frame size and the bands
+// follow from the key's fields; the launch is compiled data for the class, so the key says so); -1 for a plain one
+int hca_group_of(std::vector<HcaGroupKey> &seen, const vga_hca_params &c, int shape_class)
+{
+    HcaGroupKey k = {c.quality, c.bitrate, c.limit_bitrate, c.channel_count, c.sample_rate, c.looping ? 1 : 0, c.looping ? shape_class : -1};
     for (size_t i = 0; i < seen.size(); i++)
         if (memcmp(&seen[i], &k, sizeof k) == 0) return (int)i;
     seen.push_back(k);
@@ -39,28 +50,91 @@ int hca_encode_v_job(const std::vector<int> &units, int nch, const int16_t *cons
                      const vga_hca_params *configs, const vga_hca_info *infos, uint8_t *const *frames_out)
 {
     const int n = (int)units.size();
+    std::vector<hca::DeviceInfo> dev(n);
+    for (int i = 0; i < n; i++)
+        if (int rc = make_device_info(infos[units[i]], dev[i])) return rc;
+    std::vector<int> cls;
+    decode_classes(dev.data(), n, cls);
     std::vector<HcaGroupKey> keys;
     std::vector<int> group(n), length(n);
     for (int i = 0; i < n; i++) {
-        group[i] = hca_group_of(keys, configs[units[i]]);
+        group[i] = hca_group_of(keys, configs[units[i]], cls[i]);
         length[i] = configs[units[i]].sample_count;
     }
     const BucketPlan plan = plan_buckets(group, length, HCA_CHUNK_STREAMS, HCA_BUCKET_VOLUME, true);
     const int chunks = (int)plan.chunk_begin.size() - 1;
     std::vector<vga_hca_info> chunk_info(chunks);
-    for (int k = 0; k < chunks; k++) chunk_info[k] = infos[units[plan.order[plan.chunk_begin[k + 1] - 1]]];   // the bucket's longest stream
+    std::vector<int64_t> chunk_frames_pitch(chunks);
+    for (int k = 0; k < chunks; k++) {
+        chunk_info[k] = infos[units[plan.order[plan.chunk_begin[k + 1] - 1]]];   // the bucket's longest stream
+        chunk_frames_pitch[k] = frames_pitch_for(chunk_info[k]);
+        // looping streams: the longest file need not have the most frames (its loop may end early)
+        for (int i = plan.chunk_begin[k]; chunk_info[k].looping && i < plan.chunk_begin[k + 1]; i++)
+            chunk_frames_pitch[k] = std::max(chunk_frames_pitch[k], frames_pitch_for(infos[units[plan.order[i]]]));
+    }
+    HcaEncodeVStats &stats = hca_encode_v_last();
+    stats.v[0] += n;
+    stats.v[1] += (long long)keys.size();
+    stats.v[2] += chunks;
     // a unit is a stream: nch rows of PCM in, one row of frames out
     const BucketLayout lay = layout_buckets(
         plan, nch, 1,
         [&](int k) {
             return RowPitch{round_up(std::max(plan.chunk_length[k], 1), 8) * 2,
-                            frames_pitch_for(chunk_info[k])};
+                            chunk_frames_pitch[k]};
         },
         [&](int i, int c) { return InRow{pcm[first_row[units[i]] + c], (size_t)configs[units[i]].sample_count * 2}; },
         [&](int i, int) { return OutRow{frames_out[units[i]], (size_t)infos[units[i]].frame_count * infos[units[i]].frame_size}; });
     DevBuf d_pcm, d_frames, d_status;
     if (int rc = lay.alloc(d_pcm, d_frames)) return rc;                             // silence behind every row
     if (int rc = alloc_status_word(d_status)) return rc;
+    // the looping chunks' tables: the runs of every stream in the plan's order (run_at: position -> its first run), each with
+    // the rows and frames of its place in the bucket layout, and the looping streams' maps; one upload for the whole job
+    std::vector<hca::PackedRun> runs;
+    std::vector<hca::PackedLoopMap> loops;
+    std::vector<int> run_at(n + 1, 0);
+    std::vector<char> chunk_wave(chunks, 0);
+    const uint16_t *crc_pow = nullptr;
+    for (int k = 0; k < chunks; k++) {
+        const int begin = plan.chunk_begin[k], end = plan.chunk_begin[k + 1];
+        if (chunk_info[k].looping) {
+            if (int rc = crc_pow_table(&crc_pow)) return rc;
+            int64_t total = 0;
+            for (int i = begin; i < end; i++) total += infos[units[plan.order[i]]].frame_count;
+            bool wave = false;
+            const int per_run = hca::encode_frames_per_run(dev[plan.order[begin]], total, hca_frames_per_group_override(), &wave);
+            chunk_wave[k] = wave;
+            for (int i = begin; i < end; i++) {
+                const vga_hca_info &h = infos[units[plan.order[i]]];
+                run_at[i] = (int)runs.size();
+                if (bitrate_too_low(h)) { set_error("Bitrate is set too low."); return VGA_ERR_INVALID_DATA; }
+                hca::PackedRun r = {};
+                r.frames_at = lay.out.base[k] + (int64_t)(i - begin) * lay.out.pitch[k];
+                r.pcm_at = (lay.in.base[k] + (int64_t)(i - begin) * nch * lay.in.pitch[k]) / 2;
+                r.frames_room = lay.out.base.back() + 64 - r.frames_at;
+                r.ch_pitch = (int)(lay.in.pitch[k] / 2);
+                r.frame_count = h.frame_count;
+                r.sample_count = h.sample_count;
+                r.inserted_samples = h.inserted_samples;
+                if (int rc = set_encoder_map(r, h, configs[units[plan.order[i]]].sample_count, &loops)) return rc;
+                for (int f = 0; f < h.frame_count; f += per_run) {
+                    r.f0 = f;
+                    r.len = std::min(per_run, h.frame_count - f);
+                    runs.push_back(r);
+                }
+            }
+        } else
+            for (int i = begin; i < end; i++) run_at[i] = (int)runs.size();
+        run_at[end] = (int)runs.size();
+    }
+    DevBuf d_runs, d_loops;
+    if (!runs.empty()) {
+        VGA_HIP_TRY(d_runs.alloc(runs.size() * sizeof(hca::PackedRun)));
+        VGA_HIP_TRY(hipMemcpy(d_runs.p, runs.data(), runs.size() * sizeof(hca::PackedRun), hipMemcpyHostToDevice));
+        VGA_HIP_TRY(d_loops.alloc(loops.size() * sizeof(hca::PackedLoopMap)));
+        VGA_HIP_TRY(hipMemcpy(d_loops.p, loops.data(), loops.size() * sizeof(hca::PackedLoopMap), hipMemcpyHostToDevice));
+    }
+    for (int k = 0; k < chunks; k++) stats.v[3] += chunk_info[k].frame_count > 0 ? 1 : 0;
     pipe::Job job;
     job.units = n;
     lay.bind(job, d_pcm, d_frames);
@@ -68,6 +142,10 @@ int hca_encode_v_job(const std::vector<int> &units, int nch, const int16_t *cons
     job.compute = chunk_compute([&](int first, int count, hipStream_t s) {
         const int k = plan.chunk_of(first);
         if (chunk_info[k].frame_count <= 0) return VGA_OK;
+        if (chunk_info[k].looping)
+            return hca::launch_encode_packed(d_pcm.as<int16_t>(), shape_class_of(dev[plan.order[first]]), d_runs.as<hca::PackedRun>() + run_at[first],
+                                             run_at[first + count] - run_at[first], chunk_wave[k] != 0, d_frames.as<uint8_t>(),
+                                             crc_pow, d_status.as<int>(), s, d_loops.as<hca::PackedLoopMap>());
         const int64_t ch_pitch = lay.in.pitch[k] / 2;
         return vga_hca_encode_device(d_pcm.as<int16_t>() + lay.in.base[k] / 2, ch_pitch * nch, ch_pitch, count, plan.chunk_length[k],
                                      &chunk_info[k], d_frames.as<uint8_t>() + lay.out.base[k], lay.out.pitch[k], d_status.as<int>(), s);
@@ -174,6 +252,7 @@ extern "C" {
 int vga_hca_encode_batch_v(const int16_t *const *pcm, int nstreams, const vga_hca_params *configs, vga_hca_info *infos_out,
                            uint8_t *const *frames_out)
 {
+    hca_encode_v_last() = HcaEncodeVStats();
     if (nstreams < 0) { set_error("negative stream count"); return VGA_ERR_ARGUMENT; }
     if (nstreams == 0) return VGA_OK;
     if (!pcm || !configs || !infos_out || !frames_out) { set_error("null array"); return VGA_ERR_ARGUMENT; }
@@ -250,6 +329,13 @@ int vga_testing_hca_decode_classes(const void *infos, int nstreams, int *class_o
     const int classes = decode_classes(dev.data(), nstreams, cls);
     for (int s = 0; s < nstreams; s++) class_out[s] = cls[s];
     return classes;
+}
+
+int vga_testing_hca_encode_v_stats(long long *out, int n)
+{
+    const HcaEncodeVStats &last = hca_encode_v_last();
+    for (int i = 0; out && i < n && i < 4; i++) out[i] = last.v[i];
+    return 4;
 }
 
 int vga_testing_hca_decode_v_stats(long long *out, int n)

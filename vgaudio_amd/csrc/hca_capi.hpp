@@ -46,6 +46,20 @@ inline int make_pcm_map(const vga_hca_info &h, int pcm_length, PcmMap &m)
     return VGA_OK;
 }
 
+// the encoder's part of a PackedRun (hca_kernels.hpp) from the stream's map: zero_pre, and for a looping stream its entry of the
+// launch's PackedLoopMap table (loops == nullptr: the caller encodes plain streams only).  raw_len: samples in the stream's rows.
+inline int set_encoder_map(PackedRun &r, const vga_hca_info &h, int raw_len, std::vector<PackedLoopMap> *loops)
+{
+    PcmMap m;
+    if (int rc = make_pcm_map(h, raw_len, m)) return rc;
+    r.zero_pre = m.zero_pre;
+    if (h.looping && loops) {
+        loops->push_back(PackedLoopMap{m.post_end, m.loop_start, m.last_chunk, m.raw_len});
+        r.loop_map = (int)loops->size();
+    }
+    return VGA_OK;
+}
+
 // the status word of a host batch job, zeroed: its kernels OR their flag bits into it
 inline int alloc_status_word(DevBuf &d_status)
 {
@@ -92,7 +106,8 @@ struct RaggedLayout {
 int make_layout(const vga_hca_info *infos, int nstreams, RaggedLayout &L);
 // the runs {stream, first frame, length} of one launch: every stream's frames cut at per_run, never across a stream's end.
 // The decoder's second kernel has nothing to do for a stream without samples; the encoder writes such a stream's frames.
-std::vector<PackedRun> cut_runs(const RaggedLayout &L, int per_run, bool encoder);
+// loops (encoder): receives the PackedLoopMap of every looping stream, whose runs then name it; nullptr: plain maps only.
+std::vector<PackedRun> cut_runs(const RaggedLayout &L, int per_run, bool encoder, std::vector<PackedLoopMap> *loops = nullptr);
 
 }  // namespace hca
 }  // namespace vga

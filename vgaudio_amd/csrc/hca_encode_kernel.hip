@@ -46,12 +46,14 @@ constexpr int MAX_ENC_FRAMES_PER_GROUP = 16;
 
 // LDS gives six workgroups = three waves per SIMD; the hint keeps hipcc at the 168 VGPRs that fit (it takes 171 otherwise)
 // PACKED (vga_hca_encode_device_v, hca_kernels.hpp): the workgroup's run of frames, its stream's rows, length and status word
-// come from runs[blockIdx.x] instead of the pitches; the stream map is that of a stream that does not loop.
+// come from runs[blockIdx.x] instead of the pitches; the stream map is that of a stream that does not loop unless the run names
+// an entry of `loops` (vga_hca_encode_loops_device_v, the looping chunks of vga_hca_encode_batch_v).
 template <bool PACKED>
 __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void hca_encode_kernel(
     const int16_t *__restrict__ pcm, int64_t stream_pitch, int64_t ch_pitch, int frames_per_group, int groups_per_stream, PcmMap map,
     DeviceInfo info, uint8_t *__restrict__ frames, int64_t frames_pitch, const uint16_t *__restrict__ crc_pow,
-    int *__restrict__ status, int first_frame, int end_frame, const PackedRun *__restrict__ runs)
+    int *__restrict__ status, int first_frame, int end_frame, const PackedRun *__restrict__ runs,
+    const PackedLoopMap *__restrict__ loops)
 {
     PackedRun run = {};
     if constexpr (PACKED) {
@@ -62,6 +64,13 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(3, 
         map.post_end = map.main_end;                           // (not looping: _postAudio is all zero)
         map.loop_start = map.last_chunk = 0;
         map.raw_len = run.sample_count;
+        if (run.loop_map != 0) {                               // (uniform: one scalar load, once per workgroup)
+            const PackedLoopMap e = loops[run.loop_map - 1];
+            map.post_end = e.post_end;
+            map.loop_start = e.loop_start;
+            map.last_chunk = e.last_chunk;
+            map.raw_len = e.raw_len;
+        }
         ch_pitch = run.ch_pitch;
         status += run.stream;
     }
@@ -804,14 +813,14 @@ int encode_frames_per_run(const DeviceInfo &info, int64_t total_frames, int hook
 }
 
 int launch_encode_packed(const int16_t *d_pcm, const DeviceInfo &info, const PackedRun *d_runs, int nruns, bool wave_runs,
-                         uint8_t *d_frames, const uint16_t *d_crc_pow, int *d_status, hipStream_t stream)
+                         uint8_t *d_frames, const uint16_t *d_crc_pow, int *d_status, hipStream_t stream, const PackedLoopMap *d_loops)
 {
     if (nruns <= 0) return VGA_OK;
-    if (wave_runs) return launch_encode_wave_packed(d_pcm, info, d_runs, nruns, d_frames, d_crc_pow, d_status, stream);
+    if (wave_runs) return launch_encode_wave_packed(d_pcm, info, d_runs, nruns, d_frames, d_crc_pow, d_status, stream, d_loops);
     const size_t lds = encode_lds_bytes(info);
     if (lds > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_encode_kernel<true>, lds));
     hipLaunchKernelGGL(hca_encode_kernel<true>, dim3((unsigned)nruns), dim3(ENC_THREADS), lds, stream, d_pcm, (int64_t)0, (int64_t)0, 0,
-                       1, PcmMap{}, info, d_frames, (int64_t)0, d_crc_pow, d_status, 0, 0, d_runs);
+                       1, PcmMap{}, info, d_frames, (int64_t)0, d_crc_pow, d_status, 0, 0, d_runs, d_loops);
     VGA_HIP_TRY(hipGetLastError());
     return VGA_OK;
 }
@@ -839,7 +848,7 @@ int launch_encode(const int16_t *d_pcm, int64_t stream_pitch, int64_t ch_pitch, 
     const int groups = (frame_span + per_group - 1) / per_group;
     hipLaunchKernelGGL(hca_encode_kernel<false>, dim3((unsigned)((int64_t)nstreams * groups)), dim3(ENC_THREADS), lds, stream,
                        d_pcm, stream_pitch, ch_pitch, per_group, groups, map, info, d_frames, frames_pitch, d_crc_pow, d_status,
-                       first_frame, end_frame, (const PackedRun *)nullptr);
+                       first_frame, end_frame, (const PackedRun *)nullptr, (const PackedLoopMap *)nullptr);
     VGA_HIP_TRY(hipGetLastError());
     return VGA_OK;
 }

@@ -102,6 +102,7 @@ struct WaveArgs {
     PcmMap map;
     DeviceInfo info;
     const PackedRun *runs;             // PACKED: total_runs entries, one per wave (hca_kernels.hpp); the pitches and map are unused
+    const PackedLoopMap *loops;        // PACKED: what the runs' loop_map indexes (cold: read where the stream map is)
 };
 typedef const __attribute__((address_space(4))) WaveArgs *ColdArgs;
 __device__ __forceinline__ ColdArgs cold_args()
@@ -358,7 +359,7 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(VGA_
                 map.loop_start = k->map.loop_start;
                 map.last_chunk = k->map.last_chunk;
                 map.raw_len = k->map.raw_len;
-                if constexpr (PACKED) {                    // a stream that does not loop: _postAudio is all zero
+                if constexpr (PACKED) {                    // a stream that does not loop (_postAudio is all zero), or its entry
                     const PackedRun *r = k->runs + __builtin_amdgcn_readfirstlane(run);
                     map.zero_pre = r->zero_pre;
                     map.pre_end = r->inserted_samples - SPSF;
@@ -366,6 +367,14 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(VGA_
                     map.post_end = map.main_end;
                     map.loop_start = map.last_chunk = 0;
                     map.raw_len = r->sample_count;
+                    const int loop_map = r->loop_map;
+                    if (loop_map != 0) {
+                        const PackedLoopMap *e = k->loops + (loop_map - 1);
+                        map.post_end = e->post_end;
+                        map.loop_start = e->loop_start;
+                        map.last_chunk = e->last_chunk;
+                        map.raw_len = e->raw_len;
+                    }
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -964,7 +973,7 @@ int encode_wave_frames_per_run(int64_t total_frames, int override_value)
 }
 
 int launch_encode_wave_packed(const int16_t *d_pcm, const DeviceInfo &info, const PackedRun *d_runs, int nruns, uint8_t *d_frames,
-                              const uint16_t *d_crc_pow, int *d_status, hipStream_t stream)
+                              const uint16_t *d_crc_pow, int *d_status, hipStream_t stream, const PackedLoopMap *d_loops)
 {
     const size_t wave_bytes = wave_lds_bytes(info);
     const size_t lds = WG_WAVES * wave_bytes;
@@ -979,6 +988,7 @@ int launch_encode_wave_packed(const int16_t *d_pcm, const DeviceInfo &info, cons
     args.wave_bytes = (int)wave_bytes;
     args.info = info;
     args.runs = d_runs;
+    args.loops = d_loops;
     if (info.nch == 2) {
         if (lds > 32 * 1024) VGA_HIP_TRY(allow_dynamic_lds(hca_encode_wave_kernel<2, true>, lds));
         hipLaunchKernelGGL((hca_encode_wave_kernel<2, true>), dim3(grid), dim3(WG_THREADS), lds, stream, args);

@@ -40,9 +40,17 @@ struct PackedRun {                     // one workgroup (a wave of the one-wave 
     int frame_count, sample_count, inserted_samples;
     int zero_pre;                      // PcmMap::zero_pre of the stream (encoder)
     int stream;                        // the caller's index of the stream: its word of d_status
-    int reserved;
+    int loop_map;                      // encoder: 0 = the stream does not loop, else 1 + its entry of the launch's PackedLoopMap table
 };
 static_assert(sizeof(PackedRun) == 64, "PackedRun is read as four 16-byte pieces");
+// What the PcmMap of a looping stream has beyond a PackedRun (hca_device.hpp; made by make_pcm_map like every map): one entry
+// per looping stream of a launch, read only where a run's cold fields are read.  The runs of plain streams carry loop_map 0
+// and are byte for byte what they were before looping streams shared the packed launches.
+struct PackedLoopMap {
+    int post_end, loop_start, last_chunk;
+    int raw_len;                       // samples the stream's rows hold: >= sample_count (the host batch's rows hold the whole file)
+};
+static_assert(sizeof(PackedLoopMap) == 16, "PackedLoopMap is read as one 16-byte piece");
 struct PackedScanStream {              // the scan's view of a stream that has frames, in the caller's order
     int64_t frames_at, frames_room;
     int first_record, frame_count;
@@ -59,9 +67,11 @@ inline size_t packed_scan_table_bytes(int streams, int total_frames)
 // info: the class (frame_count, sample_count, inserted_samples are not read); d_status: one word per stream of the caller
 int launch_decode_packed(const uint8_t *d_frames, const DeviceInfo &info, int total_frames, const void *d_scan_table,
                          const PackedRun *d_runs, int nruns, int16_t *d_pcm, void *d_workspace, int *d_status, hipStream_t stream);
-// the runs of non-looping streams; wave_runs: d_runs was cut for the one-wave kernel (encode_wave_kernel_takes)
+// wave_runs: d_runs was cut for the one-wave kernel (encode_wave_kernel_takes); d_loops: the table the runs' loop_map indexes
+// (nullptr when no run has one)
 int launch_encode_packed(const int16_t *d_pcm, const DeviceInfo &info, const PackedRun *d_runs, int nruns, bool wave_runs,
-                         uint8_t *d_frames, const uint16_t *d_crc_pow, int *d_status, hipStream_t stream);
+                         uint8_t *d_frames, const uint16_t *d_crc_pow, int *d_status, hipStream_t stream,
+                         const PackedLoopMap *d_loops = nullptr);
 // frames per run the launchers would choose for total_frames frames (0 < override: the test hook's value)
 int decode_frames_per_group(int64_t total_frames, int override_value);
 int encode_frames_per_run(const DeviceInfo &info, int64_t total_frames, int override_value, bool *wave_kernel);
@@ -70,7 +80,7 @@ int encode_frames_per_run(const DeviceInfo &info, int64_t total_frames, int over
 bool encode_wave_kernel_takes(const DeviceInfo &info);
 int encode_wave_frames_per_run(int64_t total_frames, int override_value);
 int launch_encode_wave_packed(const int16_t *d_pcm, const DeviceInfo &info, const PackedRun *d_runs, int nruns, uint8_t *d_frames,
-                              const uint16_t *d_crc_pow, int *d_status, hipStream_t stream);
+                              const uint16_t *d_crc_pow, int *d_status, hipStream_t stream, const PackedLoopMap *d_loops);
 int launch_encode_wave(const int16_t *d_pcm, int64_t stream_pitch, int64_t ch_pitch, int nstreams, const PcmMap &map,
                        const DeviceInfo &info, uint8_t *d_frames, int64_t frames_pitch, const uint16_t *d_crc_pow,
                        int *d_status, hipStream_t stream, int first_frame, int end_frame, int frames_per_run_override);

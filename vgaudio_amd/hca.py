@@ -320,12 +320,34 @@ def _shape_class(h):
             h.total_band_count, h.base_band_count, h.stereo_band_count, h.bands_per_hfr_group, h.hfr_group_count, h.use_ath_curve)
 
 
+def plan_write_groups(infos, sample_counts):
+    """How write_files routes its files: (groups, singles).  groups: lists of file indices, one crihca.RaggedHca (one set of
+    encode launches) each, by shape class in the order the classes first appear; singles: the files that get a
+    vga_hca_encode_device call of their own.  A looping file joins its class like any other, except where
+      * the file holds audio behind its HcaInfo.sample_count (sample_counts[i] > infos[i].sample_count) and the reference's
+        encoder would read it (crihca.loop_may_read_tail: a loop shorter than the post audio) -- a packed row ends at
+        sample_count and cannot supply it --, or
+      * its class would be that file alone: its own call costs no object.
+    Host only, needs no GPU."""
+    from .crihca import loop_may_read_tail
+    groups, singles = {}, []
+    for i, (h, n) in enumerate(zip(infos, sample_counts)):
+        if h.looping and n > h.sample_count and loop_may_read_tail(h):
+            singles.append(i)
+        else:
+            groups.setdefault(_shape_class(h), []).append(i)
+    for key in [k for k, m in groups.items() if len(m) == 1 and infos[m[0]].looping]:
+        singles += groups.pop(key)
+    return list(groups.values()), sorted(singles)
+
+
 def write_files(pcm16_list, configuration=None):
     """HcaWriter(configuration).GetFile(file) for a list of Pcm16Format files, on the device and without a launch per file or
-    per key: files that do not loop are grouped by shape class and one crihca.RaggedHca per class encodes them, a looping file
-    is encoded by vga_hca_encode_device into its own place, all of it at explicit offsets in one frames buffer; one HcaFileSet
-    over everything encrypts (configuration.EncryptionKey: every file gets its table, KeyType as encryption type and masked
-    chunk ids) and writes the images.  Returns one `bytes` per file, in the caller's order."""
+    per key: the files are grouped by shape class and one crihca.RaggedHca per class encodes them, looping files beside plain
+    ones (encode_loops_device); the few files plan_write_groups names are encoded by vga_hca_encode_device into their own
+    place, all of it at explicit offsets in one frames buffer; one HcaFileSet over everything encrypts
+    (configuration.EncryptionKey: every file gets its table, KeyType as encryption type and masked chunk ids) and writes the
+    images.  Returns one `bytes` per file, in the caller's order."""
     import torch
     from .crihca import RaggedHca
     cfg = configuration or HcaConfiguration()
@@ -346,10 +368,8 @@ def write_files(pcm16_list, configuration=None):
         infos.append(h)
     key = cfg.EncryptionKey
     enc_type, tables = (key.KeyType, [key.EncryptionTable]) if key is not None else (0, None)
-    groups, loops = {}, []
-    for i, h in enumerate(infos):
-        (loops.append(i) if h.looping else groups.setdefault(_shape_class(h), []).append(i))
-    order = [i for members in groups.values() for i in members] + loops
+    groups, loops = plan_write_groups(infos, [f.SampleCount for f in files])
+    order = [i for members in groups for i in members] + loops
     described = [_lib.HcaFileC(infos[i], None, 1.0, enc_type, int(key is not None), 0 if key is not None else -1) for i in order]
     HcaFileSet.layout(described)                                      # every refusal of a file, before anything is allocated
     if not files:
@@ -357,12 +377,12 @@ def write_files(pcm16_list, configuration=None):
     ragged, s = [], None
     try:
         frames_at, offsets, jobs = 0, [], []
-        for members in groups.values():
+        for members in groups:
             r = RaggedHca([infos[i] for i in members])
             host, row = np.zeros(max(r.totals.pcm_samples, 8), dtype=np.int16), 0
             for i in members:
                 for ch in files[i].Channels:
-                    n = files[i].SampleCount
+                    n = infos[i].sample_count                         # (a looping file's rows end where its HcaInfo does)
                     host[r.pcm_row_offsets[row]:r.pcm_row_offsets[row] + n] = np.asarray(ch, dtype=np.int16)[:n]
                     row += 1
             ragged.append(r)
@@ -388,7 +408,7 @@ def write_files(pcm16_list, configuration=None):
             pcm = torch.from_numpy(host).cuda()
             keep.append(pcm)
             if r.streams:
-                r.encode_device(pcm, frames[at:], status[done:])
+                r.encode_loops_device(pcm, frames[at:], status[done:])
             done += r.streams
         for h, host, n, at in loop_jobs:
             pcm = torch.from_numpy(host).cuda()
